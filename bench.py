@@ -21,7 +21,11 @@ one padded gather of the blocks still resident in HBM (RCCL over xGMI) to rank 0
 `multi_gpu` record says which exchange ran, over which backend, how many ranks took part in the collectives, the bytes they
 moved and every rank's units / decode threads / ingest seconds.  Both workloads (10x, well) run at N > 1.
 
-Sub-records of the same JSON line:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline needs: inputs, engine, warmup, the timed
+steps, the result line.  --full adds the sub-records below (and the oracle comparison of --workload well); they stay null without it.
+--dump-outputs DIR writes what the timed pass computed (the four matrices of its last step) as .npy files: see dump_outputs().
+
+Sub-records of the same JSON line (--full):
   end_to_end_zlib6 / cellranger_shape   the same pipeline (same engine, same tables) on two 50 M-read files that look like what
                    users hold: BGZF blocks written by zlib level 6 (htslib's default; the headline file is written by this repo's own
                    fast compressor), and on top of that Cell Ranger's record shape (39-character read names, 16 aux tags with CB / UB
@@ -37,7 +41,9 @@ Sub-records of the same JSON line:
                    the boundary the headline has.
 
 --workload well    BASELINE.json configs[4]: 384 per-cell BAMs (paired-end 2 x 75, no CB / UB: the column is the BAM, the key the
-                   read name), basefc + pileup from one decode of every file, matrices compared with the oracle on sampled contigs.
+                   read name), basefc + pileup from one decode of every file, matrices compared with the oracle on sampled contigs
+                   (--full).  A step is one pass over the whole list: the line says steps=1 whatever --steps is (--warmup > 0: one
+                   untimed pass first).
 --selfcheck        N > 1: before the timed pass the N ranks count a smaller file together and rank 0 counts it alone; the eight
                    output files must be byte-identical (exit code 3 otherwise).
 """
@@ -245,6 +251,47 @@ def write_outputs(eng, coo, out_dir, regions, cols, rs):
     return nnz
 
 
+DUMP_MATRICES = ("count", "ad", "dp", "oth")
+DUMP_SAMPLE_1_IN = dict(count=256, ad=32, dp=32, oth=32)      # share of each matrix's entries that goes to <name>_sample.npy
+DUMP_BUDGET = 60_000_000                                       # bytes of all .npy files together (the contract says at most 64 MB)
+
+
+def dump_outputs(out_dir, coo, n_rows, n_cols, device, dist=None):
+    """--dump-outputs: the four matrices of the timed pass as float64 .npy files that two builds can be compared with, entry for entry.
+    Per matrix m: m_row_sums, m_col_sums, m_row_nnz (every entry counts in them) and m_sample, the (row, col, value) triples of a fixed
+    sample of the entries, sorted by (row, col): those whose (row, col) hashes into a fixed 1-in-k bucket (DUMP_SAMPLE_1_IN), so a
+    build that computes the same matrix samples the same entries, whichever order or rank produced them (at most an even share of
+    DUMP_BUDGET each; beyond it the first triples).  N > 1: the ranks own disjoint rows; rank 0 adds / joins their parts and writes."""
+    part = {}
+    for m in DUMP_MATRICES:
+        r, c, v = (torch.from_numpy(np.asarray(a, dtype=np.int32)).to(device).long() for a in coo[m])
+        key = r * n_cols + c
+        # integer hash of (row, col) without overflow (every product < 2^63): the same bits on any device
+        h = ((key & 0xFFFFF) * 40503) ^ (((key >> 20) & 0xFFFFF) * 2654435761) ^ ((key >> 40) * 97)
+        h = (((h & 0xFFFFFFFF) * 1540483477) >> 24) & 0xFFFF
+        sel = h < 65536 // DUMP_SAMPLE_1_IN[m]
+        vf = v.to(torch.float64)
+        part[m] = dict(row_sums=torch.bincount(r, weights=vf, minlength=n_rows).cpu().numpy(),
+                       col_sums=torch.bincount(c, weights=vf, minlength=n_cols).cpu().numpy(),
+                       row_nnz=torch.bincount(r, minlength=n_rows).to(torch.float64).cpu().numpy(),
+                       sample=torch.stack([r[sel], c[sel], v[sel]], 1).to(torch.float64).cpu().numpy())
+        del r, c, v, key, h, sel, vf
+    parts = [part]
+    if dist is not None:
+        parts = [None] * dist.get_world_size()
+        dist.all_gather_object(parts, part)
+        if dist.get_rank() != 0:
+            return
+    os.makedirs(out_dir, exist_ok=True)
+    sums = {m: {k: sum(p[m][k] for p in parts) for k in ("row_sums", "col_sums", "row_nnz")} for m in DUMP_MATRICES}
+    cap = max(0, DUMP_BUDGET - sum(a.nbytes for s in sums.values() for a in s.values())) // (24 * len(DUMP_MATRICES))
+    for m in DUMP_MATRICES:
+        smp = np.concatenate([p[m]["sample"] for p in parts])
+        smp = smp[np.lexsort((smp[:, 1], smp[:, 0]))][:cap]
+        for k, a in list(sums[m].items()) + [("sample", smp)]:
+            np.save(os.path.join(out_dir, "%s_%s.npy" % (m, k)), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def whole_file_pass(eng, bams, out_dir, regions, cols, threads, rs=None):
     """One untimed-setup, timed-run pass without slicing: every BAM (this rank's units when rs is given) -> xck_finish -> the four
     .mtx files + tables.  rs = RankSet of a multi-rank run.  -> (seconds, records, coo, nnz)."""
@@ -311,19 +358,35 @@ def rank_threads(world, local, cores, pool_threads, shared_gpu):
         return share
 
 
-def warm_page_cache(path):
-    """The metric reads the BAM from the page cache: touch every page once, untimed (a no-op cost right after generation)."""
-    buf = bytearray(64 << 20)
-    with open(path, "rb", buffering=0) as fp:
-        while fp.readinto(buf):
-            pass
+def warm_page_cache(path, threads=8):
+    """The metric reads the BAM from the page cache: touch every page once, untimed (a no-op cost right after generation).  The
+    1 GiB ranges of the file are read by `threads` threads side by side (os.preadv releases the GIL): one reader alone takes
+    several seconds for the 44.8 GB file even when every page is cached already."""
+    from concurrent.futures import ThreadPoolExecutor
+    size, step = os.path.getsize(path), 1 << 30
+    fd = os.open(path, os.O_RDONLY)
+
+    def read_range(off):
+        buf = bytearray(64 << 20)
+        end = min(size, off + step)
+        while off < end:
+            n = os.preadv(fd, [memoryview(buf)[:min(len(buf), end - off)]], off)
+            if n <= 0:
+                break
+            off += n
+    try:
+        with ThreadPoolExecutor(max_workers=max(1, threads)) as ex:
+            list(ex.map(read_range, range(0, size, step)))
+    finally:
+        os.close(fd)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (10x: slices of the file's records; --workload well times ONE pass over the "
+                    "whole list and does not use this number)")
+    ap.add_argument("--warmup", type=int, default=5, help="untimed warm-up slices before the timed steps (--workload well: > 0 = one untimed pass)")
     ap.add_argument("--reads", type=int, default=500_000_000, help="records in the BAM (BASELINE.json configs[2]; configs[1] = --reads 50000000 --cells 5000 --snps 100000)")
     ap.add_argument("--cells", type=int, default=10000)
     ap.add_argument("--snps", type=int, default=1_000_000)
@@ -349,6 +412,10 @@ def main():
     ap.add_argument("--make-room", action="store_true", help="short disk: delete the BAMs earlier runs of this tool generated under --work (those with its .ok marker) before generating new ones")
     ap.add_argument("--selfcheck", action="store_true", help="N > 1: first count a --selfcheck-reads file with N ranks and with rank 0 alone; the output files must be identical")
     ap.add_argument("--selfcheck-reads", type=int, default=50_000_000)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: CPU baseline + oracle parity, the zlib-6 / Cell Ranger side "
+                    "files, the configs[4] sub-record, the HBM-resident sub-record + roofline (10x); the oracle comparison (--workload well)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed pass computed (the four matrices) "
+                    "as DIR/<name>.npy, float64, under 64 MB in all: see dump_outputs()")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -392,7 +459,7 @@ def main():
     threads = args.threads if args.threads > 0 else rank_threads(world, local, cores, pool_threads, shared_gpu)
 
     if args.workload == "well":
-        line = well_workload(args, dev_idx, device, threads, cores, log, world, rank, dist, shared_gpu, barrier)
+        line = well_workload(args, dev_idx, device, threads, cores, log, world, rank, dist, shared_gpu, barrier, dump_dir=args.dump_outputs)
         if rank == 0:
             print(json.dumps(line))
         if dist is not None:
@@ -412,7 +479,7 @@ def main():
     if rank == 0:
         regions, snps, names, bcs, bam, fresh = make_inputs(args, args.work, cores, log)
         if not fresh:
-            warm_page_cache(bam)
+            warm_page_cache(bam, cores)
     barrier()
     if rank != 0:
         regions, snps, names, bcs, bam, fresh = make_inputs(args, args.work, cores, log)
@@ -503,6 +570,8 @@ def main():
         dt = float(tmax[0].item())
         mgpu = multi_gpu_record(rs, dist, device, threads, marks, done_records, shared_gpu)
     timed_all, decoded_all = int(t[1].item()), int(t[2].item())
+    if args.dump_outputs:                                      # (coo = views of the engine's buffers: before eng.close)
+        dump_outputs(args.dump_outputs, coo, len(regions), len(bcs), device, dist)
     if rank != 0:
         eng.close()
         if dist is not None:
@@ -527,13 +596,14 @@ def main():
 
     # ---- CPU baseline + parity of this run's matrices: whole contigs of the same BAM through the oracle ----
     cpu = None
-    if args.cpu_sample > 0 and world == 1:
+    if args.full and args.cpu_sample > 0 and world == 1:
         cpu = cpu_baseline(args, eng, bam, names, regions, snps, bcs, counts, coo, row_contig, threads, cores, log)
 
     # ---- the same pipeline on files that look like a user's: zlib-6 blocks; Cell Ranger's record shape on top ----
     subs = {}
     eng_host = None
-    if args.sub_reads > 0 and world == 1 and int(stats.get("gpu_inflate_chunks", 0)) > 0:
+    run_subs = args.full and args.sub_reads > 0 and world == 1
+    if run_subs and int(stats.get("gpu_inflate_chunks", 0)) > 0:
         # a second handle whose decoder never hands chunks to the GPU (the knob is read at xck_create): the side files are timed with it
         # too, so that every line shows what the device share of the inflate buys on this box
         prev = os.environ.get("XCK_GPU_INFLATE")
@@ -545,13 +615,13 @@ def main():
                 os.environ.pop("XCK_GPU_INFLATE", None)
             else:
                 os.environ["XCK_GPU_INFLATE"] = prev
-    if args.sub_reads > 0 and world == 1:
+    if run_subs:
         for key, level, shape, what in (("end_to_end_zlib6", 6, "", "the headline's record shape (12-character names, tags NH CB UB), BGZF blocks by zlib level 6"),
                                         ("cellranger_shape", 6, "cellranger", "Cell Ranger's record shape: 39-character read names, 16 aux tags (NH HI AS nM RE xf li RG TX GX GN CR CY CB UR UY UB), "
                                                                               "BGZF blocks by zlib level 6")):
             bam2 = os.path.join(args.work, "synth_%d_%d_l%d%s.bam" % (args.sub_reads, args.cells, level, "_" + shape if shape else ""))
             if not gen_bam(args, args.work, bam2, args.sub_reads, level, shape, cores, log):
-                warm_page_cache(bam2)
+                warm_page_cache(bam2, cores)
             runs2 = []
             for rep in range(max(1, args.sub_passes)):            # (the passes are 1 - 2 s long: the median of a few, with the spread shown)
                 tm, n2, _, _ = whole_file_pass(eng, [bam2], os.path.join(args.work, "out_" + key), regions, bcs, threads)
@@ -579,7 +649,7 @@ def main():
 
     # ---- BASELINE configs[4] at a reduced read count, so that every driver run carries a number for the multi-BAM well-based path ----
     well = None
-    if args.well_sub_reads > 0 and world == 1:
+    if args.full and args.well_sub_reads > 0 and world == 1:
         try:
             a4 = argparse.Namespace(**vars(args))
             a4.well_reads, a4.cpu_sample, a4.warmup = args.well_sub_reads, min(args.cpu_sample, 4_000_000), 1
@@ -594,7 +664,7 @@ def main():
 
     # ---- HBM-resident sub-record + roofline of the dominant kernel ----
     resident, roofline = None, None
-    if args.resident_passes > 0 and world == 1:
+    if args.full and args.resident_passes > 0 and world == 1:
         resident, roofline = device_resident(args, names, regions, snps, dev_idx, device, log)
 
     cfg_name = {(500_000_000, 10000, 1_000_000): "configs[2]", (50_000_000, 5000, 100_000): "configs[1]"}.get((args.reads, args.cells, args.snps), "configs[2] shape at a custom size")
@@ -648,11 +718,11 @@ def oracle_on_contigs(names, regions, snps, n_cols, bams, take, coo, threads, cp
     return dict(n_dec=n_dec, t_dec=t_dec, t_count=tc, n_cmp=n_cmp, parity=parity)
 
 
-def well_workload(args, dev_idx, device, threads, cores, log, world=1, rank=0, dist=None, shared_gpu=False, barrier=lambda: None):
+def well_workload(args, dev_idx, device, threads, cores, log, world=1, rank=0, dist=None, shared_gpu=False, barrier=lambda: None, dump_dir=None):
     """BASELINE.json configs[4]: N per-cell BAMs (SMART-seq style: paired-end 2 x 75, mates share the read name, no CB / UB tags) through
     the multi-BAM ingest path - column = index of the BAM, key = read name (interned per file), basefc + pileup from ONE decode of every
     file - to the four .mtx files; reference path: xcltk/rdr/fc/core.py:153-170 (the loop over sam_list), rdr/fc/mcount.py:37-42,120-127.
-    The matrices' rows of the sampled contigs are compared with the oracle (same files decoded again by the host decoder) in the run.
+    --full: the matrices' rows of the sampled contigs are compared with the oracle (same files decoded again by the host decoder) in the run.
     world > 1: every rank streams ITS units (contigs, shard.plan_units on the summed .bai counts of all files) of EVERY BAM, owns
     disjoint rows, and the ranks write the files together (or --gather); each rank checks the sampled contigs it owns against the oracle."""
     work = os.path.join(args.work, "well")
@@ -697,7 +767,7 @@ def well_workload(args, dev_idx, device, threads, cores, log, world=1, rank=0, d
     stats = eng.stats()
     # ---- the oracle on the smallest contigs of every file (up to --cpu-sample records in total), and the GPU's rows of those contigs
     cpu, parity_all = None, None
-    if args.cpu_sample > 0:
+    if args.full and args.cpu_sample > 0:
         counts = np.zeros(len(names), dtype=np.int64)
         for b in bams[:8]:                                         # (the per-contig shares are the same in every file: 8 files estimate them)
             counts += eng.contig_record_counts(b)
@@ -742,6 +812,8 @@ def well_workload(args, dev_idx, device, threads, cores, log, world=1, rank=0, d
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
         dt, n_all = float(tmax[0]), min(int(tt[1]), int(rs.d.contig_weights.sum()))   # (.bai counts of all files: every BAM record once)
         mgpu = multi_gpu_record(rs, dist, device, threads, dict(ingest=tm["ingest"], finish=tm["finish"]), n_rec, shared_gpu)
+    if dump_dir:
+        dump_outputs(dump_dir, coo, len(regions), len(cols), device, dist)
     eng.close()
     if rank != 0:
         return None

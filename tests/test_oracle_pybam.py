@@ -1,6 +1,6 @@
-"""The pysam/htslib boundary on a REAL, htslib-written BAM (container-only: the file lives in the read-only reference
-tree, /root/reference/preprocess/deprecated/merge_smartseq/BCH869.output.bam, `samtools merge` of 492 SMART-seq cells,
-and never travels to the GPU box).
+"""The pysam/htslib boundary on a REAL, htslib-written BAM: the reference's BCH869.output.bam (`samtools merge` of 492 SMART-seq
+cells, with its samtools-made .bai), stored under tests/golden/bch869 together with the barcode list and the hg19 gene list of the
+reference's md5 run (tests/golden/bch869/source.json: where the files come from and how they are stored).
 
 Every other BAM in the test suite was produced by this repo's own writers; here the two independent readers of the repo -
 oracle/pybam.py (pure Python, zlib) and csrc/bam.cpp (own inflate, speculative record walk; decoder-only handle, no GPU) -
@@ -11,8 +11,11 @@ meet a third party's file and its samtools-made .bai:
   * the .bai gives the per-reference record counts and byte ranges the contig sharding uses.
 """
 import ctypes as C
+import gzip
 import hashlib
+import json
 import os
+import shutil
 
 import numpy as np
 import pytest
@@ -22,17 +25,29 @@ import pybam
 from xcltk_amd import capi
 from xcltk_amd.engine import Engine
 
-D = "/root/reference/preprocess/deprecated/merge_smartseq/"
-BAM = D + "BCH869.output.bam"
-BARCODES = D + "BCH869.output.492.RG.barcodes.tsv"
-GENES = "/root/reference/data/anno/annotate_genes_hg19_update_20230126.txt"
+D = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bch869")
 SURVEY_MD5 = "308c881da3d4ae0434c576258b78c70f"          # reference fc_wrapper on this input
 
-pytestmark = [pytest.mark.container,
-              pytest.mark.skipif(not os.path.isfile(BAM), reason="needs /root/reference (build container only)")]
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    """The fixtures as the reference holds them: the BAM re-joined from its two block runs (checked against the recorded md5), the .bai,
+    the barcode list and the gene list decompressed.  -> (BAM, BARCODES, GENES)"""
+    d = tmp_path_factory.mktemp("bch869")
+    bam = str(d / "BCH869.output.bam")
+    with open(bam, "wb") as fp:
+        for part in ("part1", "part2"):
+            fp.write(open(os.path.join(D, "BCH869.output.bam." + part), "rb").read())
+    assert hashlib.md5(open(bam, "rb").read()).hexdigest() == json.load(open(os.path.join(D, "source.json")))["bam_md5"]
+    for gz, out in (("BCH869.output.bam.bai.gz", bam + ".bai"), ("BCH869.output.492.RG.barcodes.tsv.gz", str(d / "barcodes.tsv")),
+                    ("annotate_genes_hg19_update_20230126.txt.gz", str(d / "genes.txt"))):
+        with gzip.open(os.path.join(D, gz), "rb") as src, open(out, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    return bam, str(d / "barcodes.tsv"), str(d / "genes.txt")
 
 
-def test_real_bam_reference_md5_through_oracle(tmp_path):
+def test_real_bam_reference_md5_through_oracle(tmp_path, files):
+    BAM, BARCODES, GENES = files
     out = str(tmp_path / "out")
     O.run_files(capi.XCK_MODE_BASEFC, [BAM], GENES, out_dir=out, barcode_fn=BARCODES, cell_tag="RG", umi_tag=None)
     m = open(os.path.join(out, "matrix.mtx"), "rb").read()
@@ -45,7 +60,8 @@ def _decoder(regions, names, barcodes, **kw):
                   cell_tag="RG", umi_tag=None, decode_only=True, n_threads=3, **kw)
 
 
-def test_real_bam_decoder_vs_pybam():
+def test_real_bam_decoder_vs_pybam(files):
+    BAM, BARCODES, _ = files
     refs, recs = pybam.read_bam(BAM)
     names = [O.format_chrom(n) for n, _ in refs]
     names = list(dict.fromkeys(names))
@@ -83,7 +99,8 @@ def test_real_bam_decoder_vs_pybam():
     assert len(set(name_code.values())) == len(name_code)
 
 
-def test_real_bai_counts_and_ranges():
+def test_real_bai_counts_and_ranges(files):
+    BAM, BARCODES, _ = files
     refs, recs = pybam.read_bam(BAM)
     names = list(dict.fromkeys(O.format_chrom(n) for n, _ in refs))
     regions = [(n, 1, 1000, "r%d" % i) for i, n in enumerate(names)]

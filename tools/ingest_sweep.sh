@@ -10,7 +10,7 @@ i=0
 for cfg in "$@"; do
   i=$((i + 1)); tag=$(printf "%02d" $i)
   if [ "$cfg" = base ]; then envs=""; else envs="$cfg"; fi
-  env $envs XCK_DEBUG_TIMING=1 timeout -k 10 500 python3 bench.py --make-room --reads "$reads" --cpu-sample 4000000 --resident-passes 0 --sub-reads 20000000 --well-sub-reads 0 > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"
+  env $envs XCK_DEBUG_TIMING=1 timeout -k 10 500 python3 bench.py --full --make-room --reads "$reads" --cpu-sample 4000000 --resident-passes 0 --sub-reads 20000000 --well-sub-reads 0 > "$out/bench_$tag.json" 2> "$out/bench_$tag.err"
   python3 - "$out/bench_$tag.json" "$cfg" <<'PY'
 import json, sys
 try:
