@@ -33,7 +33,14 @@
  *                                         XCK_GPU_INFLATE_DEPTH (10) chunks on the device and leave the rest to the host pool, XCK_GPU_INFLATE_RING (12)
  *                                         chunks in flight in all; <percent>: a fixed share; 0 = host only.  XCK_GPU_INFLATE_FREE_CUS (32): CUs the
  *                                         inflate streams never use.  Bit-identical results either way (a block the kernel does not finish, and every
- *                                         chunk after a runtime error, is inflated by the host); off for handles without a device and with XCK_F_VERIFY_CRC.
+ *                                         chunk after a runtime error, is inflated by the host); off for handles without a device and with XCK_F_VERIFY_CRC
+ *                                         alone (XCK_F_DEVICE_CRC keeps it on).
+ *   XCK_VERIFY_CRC=0|host|device          check the CRC32 of every BGZF block the record decoder inflates, as if the handle had been made with
+ *                                         XCK_F_VERIFY_CRC (host: the GPU share of the inflate is off) or XCK_F_DEVICE_CRC (device: the GPU share checks
+ *                                         its own blocks) - for front-ends and benchmarks whose calls do not carry the flags.  0 (the default) adds
+ *                                         nothing to the flags; any other value means host.  Intact files give identical results either way; a damaged
+ *                                         block fails the decode call with XCK_E_IO ("BGZF CRC mismatch", the file and the block's offset) instead
+ *                                         of being counted.
  * Decoder (read when a BAM is opened or once per process): XCK_THREADS, XCK_NUMA=0, XCK_INFLATE=zlib, XCK_CHUNK_BYTES,
  * XCK_WRITE_THREADS (writer threads of xck_write_mtx), XCK_TEST_INTERN_LIMIT (tests). */
 #ifndef XCK_H
@@ -46,6 +53,7 @@
 extern "C" {
 #endif
 
+/* (XCK_F_DEVICE_CRC, xck_decode_stats and xck_get_decode_stats are additive: ABI 3 is unchanged, callers that do not use them see no difference) */
 #define XCK_ABI_VERSION 3   /* 3: xck_stats.fold_path / fold_fallbacks / pileup_sort_path / fold_refinements / pileup_sort2_path; 2: xck_config.n_excl_pairs / excl_region / excl_snp, xck_ingest_opts.pause_records (older, shorter xck_config / xck_ingest_opts are still accepted: they carry struct_size.  xck_stats does not: xck_get_stats writes the whole ABI-3 struct, so its caller must be built against this header - check xck_abi_version() first) */
 
 /* status codes */
@@ -130,7 +138,11 @@ typedef struct xck_config {
 } xck_config;
 
 #define XCK_F_FORCE_KEY128   1  /* always use 128-bit sort keys (testing)                    */
-#define XCK_F_VERIFY_CRC     2  /* verify BGZF CRC32 while decoding                          */
+#define XCK_F_VERIFY_CRC     2  /* verify BGZF CRC32 while decoding (on the host: the GPU share of the inflate is off) */
+#define XCK_F_DEVICE_CRC    16  /* verify BGZF CRC32 while decoding, keeping the GPU share of the inflate: blocks inflated on the
+                                   device are checked by the kernel (a block it finds damaged is inflated and checked again on the
+                                   host), the others by the host.  Takes precedence over XCK_F_VERIFY_CRC.  Either flag: a block
+                                   whose CRC32 differs from its footer's fails the decode call with XCK_E_IO                   */
 #define XCK_F_LOW_PRIORITY   8  /* run this engine's kernels on a low-priority HIP stream: lets a second
                                    engine fill the GPU while the first one copies results out */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
@@ -194,6 +206,22 @@ typedef struct xck_stats {
     int32_t gpu_inflate_chunks; /* BGZF chunks (~740 blocks each) whose inflate ran on the GPU since the last xck_reset (XCK_GPU_INFLATE; was reserved0) */
 } xck_stats;
 
+/* What the BAM decoder of a handle did, since the last xck_reset, summed over the readers that fed it (xck_ingest_bam,
+ * xck_bam_next_batch, xck_bam_prefetch; a reader's counts reach the handle at the end of each of these calls).  struct_size =
+ * sizeof(xck_decode_stats), as for xck_config / xck_ingest_opts. */
+typedef struct xck_decode_stats {
+    uint32_t struct_size;
+    uint32_t reserved0;
+    int64_t gpu_inflate_chunks;       /* BGZF chunks inflated on the GPU (XCK_GPU_INFLATE; = xck_stats.gpu_inflate_chunks)        */
+    int64_t gpu_inflate_blocks;       /* BGZF blocks of those chunks                                                              */
+    int64_t gpu_blocks_left_to_host;  /* blocks of device chunks the host inflated: non-zero kernel status (INFLATE_ST_CRC included), or the whole chunk after a runtime error */
+    int64_t crc_blocks_device;        /* non-empty blocks whose CRC32 the kernel checked and found right (XCK_F_DEVICE_CRC)       */
+    int64_t crc_blocks_host;          /* non-empty blocks whose CRC32 the host checked and found right (either CRC flag)          */
+    int64_t crc_mismatch_device;      /* blocks the kernel found with a CRC32 that differs from the footer's                      */
+    int64_t crc_device_host_disagree; /* ... of which the host's check passed (the host's bytes are used; 0 unless the device erred) */
+    int64_t gpu_path_given_up;        /* readers whose GPU share of the inflate was turned off by a runtime error or lack of memory */
+} xck_decode_stats;
+
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
 
@@ -237,6 +265,8 @@ int  xck_get_result_device(xck_engine* e, xck_result* out);
 /* Forget all pushed reads, keep tables and buffers (lets one engine be re-used per step). */
 int  xck_reset(xck_engine* e);
 int  xck_get_stats(const xck_engine* e, xck_stats* out);
+/* The decoder's counters (xck_decode_stats; set out->struct_size first).  Works on decode-only handles too. */
+int  xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

@@ -30,7 +30,7 @@ int  engine_device(const xck_engine*) { return -1; }                          //
 GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }
 void gpu_inflate_slot_destroy(GpuInflateSlot*) {}
 bool gpu_inflate_slot_reserve(GpuInflateSlot*, size_t, size_t, size_t) { return false; }
-int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t) { return -1; }
+int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool) { return -1; }
 int  gpu_inflate_slot_wait(GpuInflateSlot*) { return -1; }
 bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
 // stand-in for the engine's block push (called on the decoder's push thread): touches everything the batches claim to own

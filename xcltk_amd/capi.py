@@ -18,6 +18,7 @@ XCK_F_FORCE_KEY128 = 1
 XCK_F_VERIFY_CRC = 2
 XCK_F_DECODE_ONLY = 4
 XCK_F_LOW_PRIORITY = 8
+XCK_F_DEVICE_CRC = 16
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +97,13 @@ class Stats(C.Structure):
                 ("pileup_sort2_path", C.c_int32), ("gpu_inflate_chunks", C.c_int32)]
 
 
+class DecodeStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
+                ("gpu_inflate_chunks", C.c_int64), ("gpu_inflate_blocks", C.c_int64), ("gpu_blocks_left_to_host", C.c_int64),
+                ("crc_blocks_device", C.c_int64), ("crc_blocks_host", C.c_int64), ("crc_mismatch_device", C.c_int64),
+                ("crc_device_host_disagree", C.c_int64), ("gpu_path_given_up", C.c_int64)]
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -127,6 +135,7 @@ SYMBOLS = [
     ("xck_get_result_device", C.c_int, [C.c_void_p, _P(Result)]),
     ("xck_reset", C.c_int, [C.c_void_p]),
     ("xck_get_stats", C.c_int, [C.c_void_p, _P(Stats)]),
+    ("xck_get_decode_stats", C.c_int, [C.c_void_p, _P(DecodeStats)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

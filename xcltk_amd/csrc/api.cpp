@@ -58,6 +58,7 @@ Knobs xck::Knobs::from_env() {
     k.gpu_inflate_ring = (int)num("XCK_GPU_INFLATE_RING", 12);
     k.gpu_inflate_min_mb = (int)std::max(0ll, num("XCK_GPU_INFLATE_MIN_MB", 96));
     k.gpu_inflate_free_cus = (int)num("XCK_GPU_INFLATE_FREE_CUS", 32);
+    k.verify_crc = !strcmp(str("XCK_VERIFY_CRC"), "device") ? 2 : (!*str("XCK_VERIFY_CRC") || !strcmp(str("XCK_VERIFY_CRC"), "0")) ? 0 : 1;   // (any other value: host)
     return k;
 }
 
@@ -99,7 +100,9 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if (d.use_umi) { d.umi_tag[0] = cfg->umi_tag[0]; d.umi_tag[1] = cfg->umi_tag[1]; }
     d.umi_bits = e->umi_bits;
     d.want_seq = (cfg->mode & XCK_MODE_BAF) != 0;
-    d.verify_crc = (cfg->flags & XCK_F_VERIFY_CRC) != 0;
+    const int crc_flags = cfg->flags | (e->knobs.verify_crc == 2 ? XCK_F_DEVICE_CRC : e->knobs.verify_crc == 1 ? XCK_F_VERIFY_CRC : 0);
+    d.verify_crc = (crc_flags & (XCK_F_VERIFY_CRC | XCK_F_DEVICE_CRC)) != 0;
+    d.crc_on_device = (crc_flags & XCK_F_DEVICE_CRC) != 0;
     d.n_threads = cfg->n_threads;
     d.max_batch_reads = cfg->max_batch_reads;
     *out = e;
@@ -211,7 +214,16 @@ int xck_push_batch(xck_engine* e, const xck_batch* b) {
 }
 int xck_push_batch_device(xck_engine* e, const xck_batch* b) { if (!e || !b) return XCK_E_ARG; FOR_IMPLS(e, engine_push(e, b, true)); return XCK_OK; }
 int xck_flush(xck_engine* e) { if (!e) return XCK_E_ARG; FOR_IMPLS(e, engine_flush(e)); return XCK_OK; }
-int xck_reset(xck_engine* e) { if (!e) return XCK_E_ARG; FOR_IMPLS(e, engine_reset(e)); e->gpu_inflate_chunks = 0; return XCK_OK; }
+int xck_reset(xck_engine* e) { if (!e) return XCK_E_ARG; for (auto& v : e->dstat) v = 0; FOR_IMPLS(e, engine_reset(e)); e->gpu_inflate_chunks = 0; return XCK_OK; }
+
+int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_decode_stats)) { set_thread_error("xck_decode_stats.struct_size mismatch (ABI)"); return XCK_E_ARG; }
+    int64_t* f[DS_N] = { &out->gpu_inflate_chunks, &out->gpu_inflate_blocks, &out->gpu_blocks_left_to_host, &out->crc_blocks_device, &out->crc_blocks_host,
+                         &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up };
+    for (int k = 0; k < DS_N; k++) *f[k] = e->dstat[k].load();
+    return XCK_OK;
+}
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; FOR_IMPLS(e, engine_finish_async(e)); return XCK_OK; }
 

@@ -315,7 +315,7 @@ static bool bgzf_inflate(const uint8_t* map, const BlockRef& b, uint8_t* dst, bo
     }
     if (verify_crc) {
         uint32_t want = le32(map + b.coff + b.clen - 8);
-        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, b.isize) != want) { if (err) *err = "BGZF CRC mismatch"; return false; }
+        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, b.isize) != want) { if (err) *err = "BGZF CRC mismatch in the block at compressed offset " + std::to_string(b.coff); return false; }
     }
     return true;
 }
@@ -531,6 +531,7 @@ struct xck_bam {
     bool numa_bound = false, threads_auto = false; cpu_set_t numa_set, old_affinity;
     struct CallerBinding* cur_binding = nullptr;
     DecodeTimes tm;
+    std::atomic<int64_t> dstat[DS_N] = {}; int64_t dstat_folded[DS_N] = {};   // xck_decode_stats of this reader; the part already added to a handle's
     std::string err;
 };
 
@@ -778,7 +779,10 @@ static void set_ranges(xck_bam* b, const xck_ingest_opts* o) {
 // prepare the output layout of their own records
 // One part of a chunk: inflate its blocks (all of them, or - st given - only those the GPU kernel left: status != 0), then walk the
 // records of its byte range speculatively.  Pool task.
-static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* wpp, DecodeTimes* tmp_, const ContigMap cm, bool want_seq, const int32_t* st) {
+// verify_crc: every non-empty block it inflates is CRC-checked (dstat: the reader's counters); a block the kernel found damaged
+// (INFLATE_ST_CRC) that passes here is a disagreement of device and host.
+static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* wpp, DecodeTimes* tmp_, const ContigMap cm, bool want_seq, const int32_t* st,
+                     std::atomic<int64_t>* dstat) {
     if (!t_zs.ok) { cp->failed = true; return; }
     const auto t_a = std::chrono::steady_clock::now();
     struct Acc { DecodeTimes* t; std::chrono::steady_clock::time_point a, b; bool walked = false;
@@ -790,6 +794,10 @@ static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* w
         std::string e;
         if (!bgzf_inflate(map, cp->blocks[i], cp->ubase + cp->blocks[i].uoff, verify_crc, &t_zs.zs, &e)) {
             std::lock_guard<std::mutex> lk(cp->emu); cp->failed = true; cp->err = e; return;
+        }
+        if (verify_crc && cp->blocks[i].isize) {
+            dstat[DS_CRC_HOST].fetch_add(1, std::memory_order_relaxed);
+            if (st && st[i] == INFLATE_ST_CRC) dstat[DS_CRC_DISAGREE].fetch_add(1, std::memory_order_relaxed);
         }
     }
     // speculative record walk over this range
@@ -814,7 +822,7 @@ static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* w
     wpp->stop = o;
 }
 
-static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, const ContigMap cm_in, bool want_seq) {
+static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool crc_on_device, const ContigMap cm_in, bool want_seq) {
     c.blocks.clear(); c.usize = 0; c.valid = false; c.failed = false; c.err.clear(); c.new_range = false; c.first_skip = 0; c.gpu = false; c.gpu_rc = 0; c.launched = 0; c.stage2 = false;
     if (b->scan_end) return;
     ChunkPlan pl = b->scanner->next();
@@ -828,7 +836,7 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, const 
     // ---- does this chunk go to the GPU?  (a fixed share of the chunks; small chunks - the tail of a range - stay on the host)
     GpuShare& gi = b->gi;
     GpuInflateSlot* gs = nullptr;
-    if (gi.on && !gi.broken && !verify_crc && nb >= 64 && usz < (size_t(1) << 31)) {
+    if (gi.on && !gi.broken && (!verify_crc || crc_on_device) && nb >= 64 && usz < (size_t(1) << 31)) {
         bool want;
         if (gi.pct > 0) { gi.acc += gi.pct; want = gi.acc >= 100; if (want) gi.acc -= 100; }       // a fixed share
         else {                                                            // auto: keep gi.depth chunks on the device, the pool takes the rest -
@@ -860,7 +868,11 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, const 
     ContigMap cm = cm_in; cm.only_tid = b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1;
     if (gs) {                                       // block table: where every block's stream sits in the gathered input, where its bytes go
         size_t at = 0;
-        for (size_t i = 0; i < nb; i++) { gs->h_bl[i] = DevBlock{(uint32_t)at, c.blocks[i].data_len, (uint32_t)c.blocks[i].uoff, c.blocks[i].isize}; at += ((size_t)c.blocks[i].data_len + 3) & ~size_t(3); }
+        for (size_t i = 0; i < nb; i++) {
+            const BlockRef& br = c.blocks[i];                            // (crc: the footer's, the bytes bgzf_inflate checks)
+            gs->h_bl[i] = DevBlock{(uint32_t)at, br.data_len, (uint32_t)br.uoff, br.isize, crc_on_device ? le32(b->map + br.coff + br.clen - 8) : 0u};
+            at += ((size_t)br.data_len + 3) & ~size_t(3);
+        }
         c.copy_left = (int)n_parts; gi.chunks++; gi.blocks += nb;
     }
     for (size_t pi = 0; pi < n_parts; pi++) {
@@ -870,15 +882,15 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, const 
         wp.u_begin = c.blocks[i0].uoff; wp.u_end = c.blocks[i1 - 1].uoff + c.blocks[i1 - 1].isize;
         wp.spec_start = wp.u_begin + (pi == 0 ? skip0 : 0); wp.stop = wp.spec_start; wp.recs.clear();
         wp.n_out = wp.n_cig = wp.n_seq = 0; wp.runs.clear();
-        Chunk* cp = &c; const uint8_t* map = b->map; WalkPart* wpp = &wp; DecodeTimes* tmp_ = &b->tm;
-        if (!gs) { c.tg.later([cp, map, verify_crc, wpp, tmp_, cm, want_seq] { run_part(cp, map, verify_crc, wpp, tmp_, cm, want_seq, nullptr); }); continue; }
+        Chunk* cp = &c; const uint8_t* map = b->map; WalkPart* wpp = &wp; DecodeTimes* tmp_ = &b->tm; std::atomic<int64_t>* ds = b->dstat;
+        if (!gs) { c.tg.later([cp, map, verify_crc, wpp, tmp_, cm, want_seq, ds] { run_part(cp, map, verify_crc, wpp, tmp_, cm, want_seq, nullptr, ds); }); continue; }
         GpuShare* gip = &gi; const size_t nb_ = nb, usz_ = usz;
-        c.tg.later([cp, map, i0, i1, gs, gip, nb_, usz_] {
+        c.tg.later([cp, map, i0, i1, gs, gip, nb_, usz_, crc_on_device] {
             const auto t_a = std::chrono::steady_clock::now();
             for (size_t i = i0; i < i1; i++) memcpy(gs->h_in + gs->h_bl[i].in_off, map + cp->blocks[i].coff + cp->blocks[i].data_off, cp->blocks[i].data_len);
             __atomic_fetch_add(&gip->copy_ns, ns_since(t_a), __ATOMIC_RELAXED);
             if (cp->copy_left.fetch_sub(1) == 1) {                         // the chunk's compressed bytes are gathered: hand it to the device
-                const int rc = gpu_inflate_slot_launch(gs, cp->in_total, usz_, nb_);
+                const int rc = gpu_inflate_slot_launch(gs, cp->in_total, usz_, nb_, crc_on_device);
                 cp->gpu_rc = rc; cp->launched.store(1, std::memory_order_release);
             }
         });
@@ -1138,17 +1150,24 @@ static void start_stage_two(xck_engine* e, xck_bam* b, int ci, ContigMap cm, boo
     if (!dev_ok) b->gi.broken = true;                                    // the device path stays off for the rest of this reader
     else e->gpu_inflate_chunks++;
     const int32_t* st = dev_ok ? gs->h_st : nullptr;
-    if (dev_ok) for (size_t i = 0; i < c.blocks.size(); i++) b->gi.left_blocks += st[i] != 0;
-    else b->gi.left_blocks += c.blocks.size();
+    const size_t nb = c.blocks.size(); size_t left = nb;
+    if (dev_ok) {
+        left = 0; size_t crc_ok = 0, crc_bad = 0;
+        for (size_t i = 0; i < nb; i++) { left += st[i] != 0; crc_ok += st[i] == 0 && c.blocks[i].isize; crc_bad += st[i] == INFLATE_ST_CRC; }
+        b->dstat[DS_GPU_CHUNKS] += 1; b->dstat[DS_GPU_BLOCKS] += (int64_t)nb;
+        if (e->dec.crc_on_device) { b->dstat[DS_CRC_DEVICE] += (int64_t)crc_ok; b->dstat[DS_CRC_MISMATCH_DEVICE] += (int64_t)crc_bad; }
+    }
+    b->gi.left_blocks += left; b->dstat[DS_GPU_LEFT] += (int64_t)left;
     cm.only_tid = b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1;
-    Chunk* cp = &c; const uint8_t* map = b->map; DecodeTimes* tmp_ = &b->tm; const bool want_seq = e->dec.want_seq;
-    for (WalkPart& wp : c.parts) { WalkPart* wpp = &wp; c.tg.later([cp, map, wpp, tmp_, cm, want_seq, st] { run_part(cp, map, false, wpp, tmp_, cm, want_seq, st); }); }
+    // (what the device left - a CRC mismatch included - is checked on the host as every host block is)
+    Chunk* cp = &c; const uint8_t* map = b->map; DecodeTimes* tmp_ = &b->tm; const bool want_seq = e->dec.want_seq, crc = e->dec.verify_crc; std::atomic<int64_t>* ds = b->dstat;
+    for (WalkPart& wp : c.parts) { WalkPart* wpp = &wp; c.tg.later([cp, map, crc, wpp, tmp_, cm, want_seq, st, ds] { run_part(cp, map, crc, wpp, tmp_, cm, want_seq, st, ds); }); }
     c.tg.flush(*b->pool, true);                                          // (ahead of the later chunks' inflate tasks)
     c.stage2 = true;
 }
 
 static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only = false) {
-    const bool crc = e->dec.verify_crc;
+    const bool crc = e->dec.verify_crc, crc_dev = e->dec.crc_on_device;
     const int n_refs = (int)b->ref_names.size();
     const bool has_win = o->struct_size >= offsetof(xck_ingest_opts, tid_end) + sizeof(void*);
     ContigMap cm; cm.t2c = o->tid_to_contig; cm.n_refs = n_refs; cm.t_end = has_win ? o->tid_end : nullptr;
@@ -1161,14 +1180,14 @@ static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o
     }
     if (!b->ranges_set) {
         set_ranges(b, o);
-        if (!b->gi.tried) {                                    // GPU share of the inflate: a handle with a device, XCK_GPU_INFLATE > 0, no CRC checks asked for
+        if (!b->gi.tried) {                                    // GPU share of the inflate: a handle with a device, XCK_GPU_INFLATE > 0, no host-only CRC checks asked for
             b->gi.tried = true;
             const int dev = engine_device(e), pct = e->knobs.gpu_inflate_pct;
             // (files of a few chunks - the per-cell BAMs of a well-based run - are done before the device has returned its first chunk)
             uint64_t span = b->fsize;
             if (b->use_ranges) { span = 0; for (auto& r : b->ranges) span += (r.second >> 16) - (r.first >> 16); }
             const bool big = span >= (uint64_t)e->knobs.gpu_inflate_min_mb << 20 || schedule_only;   // (a file that is read ahead has the time a device chunk takes, whatever its size)
-            if (pct != 0 && dev >= 0 && !crc && (big || pct > 0)) { b->gi.on = true; b->gi.pct = pct < 0 ? 0 : std::min(pct, 100); b->gi.depth = e->knobs.gpu_inflate_depth; b->gi.max_held = std::min(b->gi.depth + 2, 12); b->gi.device = dev; b->gi.free_cus = e->knobs.gpu_inflate_free_cus; b->gi.verbose = e->knobs.debug_timing; b->n_ring = std::max(N_CHUNK + 1, std::min(N_CHUNK_GPU, e->knobs.gpu_inflate_ring)); }
+            if (pct != 0 && dev >= 0 && (!crc || crc_dev) && (big || pct > 0)) { b->gi.on = true; b->gi.pct = pct < 0 ? 0 : std::min(pct, 100); b->gi.depth = e->knobs.gpu_inflate_depth; b->gi.max_held = std::min(b->gi.depth + 2, 12); b->gi.device = dev; b->gi.free_cus = e->knobs.gpu_inflate_free_cus; b->gi.verbose = e->knobs.debug_timing; b->n_ring = std::max(N_CHUNK + 1, std::min(N_CHUNK_GPU, e->knobs.gpu_inflate_ring)); }
         }
         bind_to_numa_node(e, b);                               // (before the scanner thread is made: it inherits the mask)
         std::vector<ScanRange> rg;
@@ -1186,7 +1205,7 @@ static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o
     while (b->n_sched + back < b->n_ring && !b->scan_end) {
         const int ci = (b->head + b->n_sched) % b->n_ring;
         Chunk& nc = b->ch[ci];
-        schedule_chunk(b, nc, ci, crc, cm, e->dec.want_seq);
+        schedule_chunk(b, nc, ci, crc, crc_dev, cm, e->dec.want_seq);
         if (b->scan_end) break;
         b->n_sched++;
     }
@@ -1414,9 +1433,21 @@ int xck_bam_linear_index(xck_bam* b, int tid, int64_t* n, const uint64_t** voffs
     return XCK_OK;
 }
 
+// what the reader counted since the last decode call -> the handle's xck_decode_stats (at the end of every decode call)
+struct FoldDecodeStats {
+    xck_engine* e; xck_bam* b;
+    ~FoldDecodeStats() {
+        for (int k = 0; k < DS_N; k++) {
+            const int64_t v = k == DS_GPU_GIVEN_UP ? (int64_t)b->gi.broken : b->dstat[k].load();   // (given up: once per reader)
+            e->dstat[k] += v - b->dstat_folded[k]; b->dstat_folded[k] = v;
+        }
+    }
+};
+
 static int next_batch_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, xck_batch* out) {
     if (!e || !b || !o || !out) return XCK_E_ARG;
     CallerBinding on_node(b);
+    FoldDecodeStats fold{e, b};
     b->defer_parse = false;                                            // (this interface hands out finished batches: parse in place)
     while (b->pending.empty()) {
         if (b->done) return 0;
@@ -1460,6 +1491,7 @@ static int drain_ingest(xck_engine* e, xck_bam* b, int rc) {
 static int ingest_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, int64_t* n_records) {
     if (!e || !b || !o) return XCK_E_ARG;
     CallerBinding on_node(b);
+    FoldDecodeStats fold{e, b};
     const int64_t pause = o->struct_size >= offsetof(xck_ingest_opts, pause_records) + sizeof(int64_t) ? o->pause_records : 0;
     const int64_t start = b->n_records;
     b->defer_parse = e->n_impl > 0;
@@ -1499,6 +1531,7 @@ static int prefetch_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o) {
     if (!e || !b || !o) return XCK_E_ARG;
     if (b->done || b->started) return XCK_OK;
     CallerBinding on_node(b);
+    FoldDecodeStats fold{e, b};
     b->prefetching = true;
     const int rc = decode_next_chunk(e, b, o, true);
     b->prefetching = false;

@@ -5,14 +5,18 @@
 
 namespace xck {
 
-struct DevBlock { uint32_t in_off, in_len, out_off, out_len; };   // byte ranges of one block's deflate stream / inflated data inside the chunk buffers
+// byte ranges of one block's deflate stream / inflated data inside the chunk buffers; crc: the CRC-32 of the BGZF footer (read with check_crc only)
+struct DevBlock { uint32_t in_off, in_len, out_off, out_len; uint32_t crc; };
+constexpr int32_t INFLATE_ST_CRC = 50;   // status: the block was inflated to out_len bytes, but their CRC-32 is not DevBlock.crc (check_crc)
 
 // Enqueue the inflate of n_blocks blocks: d_in (compressed bytes of the chunk), d_out (inflated bytes), d_status[b] = 0 when block b
 // was inflated to exactly out_len bytes, non-zero when the block is left to the host decoder.  Returns 0 / -1 (launch error).
 void dev_inflate_read_prof(unsigned long long out[8]);   // variant 10 (phase clocks): cycles per phase, summed over the blocks
-int dev_inflate_launch(hipStream_t stream, const uint8_t* d_in, const DevBlock* d_blocks, int n_blocks, uint8_t* d_out, int32_t* d_status, uint8_t* host_out = nullptr, int variant = 0);
+int dev_inflate_launch(hipStream_t stream, const uint8_t* d_in, const DevBlock* d_blocks, int n_blocks, uint8_t* d_out, int32_t* d_status, uint8_t* host_out = nullptr, int variant = 0,
+                       bool check_crc = false);
 // host_out: device alias of a mapped host block that receives every finished block's bytes too; variant: 0 = the kernel, 10 = the same with
-// phase clocks (bench harness only, dev_inflate_read_prof)
+// phase clocks (bench harness only, dev_inflate_read_prof); check_crc: every inflated non-empty block's CRC-32 (zlib's crc32) is compared with
+// DevBlock.crc - status INFLATE_ST_CRC when they differ (empty blocks are not checked, as on the host)
 
 // One chunk of BGZF blocks in flight on the GPU (the host decoder keeps a ring of these, csrc/bam.cpp): pinned host buffers for the
 // compressed bytes, the block table, the inflated bytes and the per-block status; device twins; a stream and an event of its own,
@@ -28,7 +32,7 @@ struct GpuInflateSlot {
 GpuInflateSlot* gpu_inflate_slot_create(int device, int free_cus, bool verbose);           // nullptr when the device cannot be used; free_cus: CUs its stream never uses
 void gpu_inflate_slot_destroy(GpuInflateSlot* s);                                          // waits for whatever is in flight
 bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks);   // (re)allocates; false = out of memory
-int  gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks);    // inflate kernel (every wave also stores its finished block to h_out) + event, asynchronous; 0 = enqueued
+int  gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks, bool check_crc = false);   // inflate kernel (every wave also stores its finished block to h_out) + event, asynchronous; 0 = enqueued
 bool gpu_inflate_slot_done(GpuInflateSlot* s);                                            // non-blocking: has the last launch finished?
 int  gpu_inflate_slot_wait(GpuInflateSlot* s);                                             // 0 = the chunk's bytes and statuses are in h_out / h_st
 

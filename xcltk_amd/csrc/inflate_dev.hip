@@ -16,7 +16,9 @@
 //     (out[dst + i] = out[dst - dist + i % dist] reads only bytes that already exist, so overlapping matches need no serial loop);
 //   * the finished block goes to the chunk's pinned host block by the same wave (16-byte stores over PCIe).
 // Measured: DESIGN.md section 6, profiles/experiments/gpu_inflate/ (every step of the way, against zlib block by block).
-// Status per block: 0 = inflated (exactly isize bytes), non-zero = left to the host decoder (csrc/inflate_fast.h / zlib).
+//   * check_crc: the same epilogue computes the block's CRC-32 and compares it with the footer's (DevBlock.crc).
+// Status per block: 0 = inflated (exactly isize bytes; with check_crc also CRC-checked), non-zero = left to the host decoder
+// (csrc/inflate_fast.h / zlib); INFLATE_ST_CRC = inflated, but the CRC-32 differs from the footer's.
 #include <cstdint>
 #include <cstdio>
 #include <algorithm>
@@ -159,15 +161,64 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
     return x;
 }
 
+// XOR of x over the wave, in every lane (the same DPP steps; the missing neighbours read as 0)
+__device__ __forceinline__ uint32_t wave_xor_all(uint32_t x) {
+    x ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false);    // row_shr:1
+    x ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false);    // row_shr:2
+    x ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false);    // row_shr:4
+    x ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);    // row_shr:8
+    x ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);    // row_bcast:15
+    x ^= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);    // row_bcast:31
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
+
+// ---- CRC-32 of a finished block (check_crc): zlib's crc32(), reflected polynomial 0xEDB88320, init and xorout 0xFFFFFFFF ----
+// The epilogue reads the block in 16-byte pieces, lane l taking pieces l, l + 64, ... (the coalesced form of the host store).  The
+// CRC register is linear: crc(A | B) = crc(A) x^(8|B|) + crc(B) mod P (zlib's crc32_combine).  So every lane keeps a register of its
+// own pieces as if 1008 zero bytes stood between them - per piece R = R x^(8 * 1024) + crc(piece), the product by table (4 look-ups)
+// and crc(piece) by slice-by-4 from a zero register, independent of R - then shifts it over the bytes that follow its last piece
+// (< 1024: one product by x^(8 s) from a table) and the wave XORs the registers.  Lane 0 starts from the register of the bytes before
+// the first aligned piece (init included) and adds the bytes after the last one.
+constexpr uint32_t CRC_POLY = 0xEDB88320u;
+struct CrcTables {
+    uint32_t slice[4][256];        // slice[k][b]: register after byte b and k zero bytes (slice[0] is the byte-wise table)
+    uint32_t step[4][256];         // step[k][b]: (b << 8k) x^(8 * 1024) mod P - one lane's register moved past a round of the store loop
+    uint32_t xpow[1024];           // x^(8 s) mod P (in zlib's bit order: x^0 = 0x80000000)
+};
+constexpr uint32_t crc_mulmod(uint32_t a, uint32_t b) {          // a b mod P (zlib multmodp)
+    uint32_t p = 0;
+    for (int k = 31; k >= 0; k--) { if ((a >> k) & 1u) p ^= b; b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u); }
+    return p;
+}
+constexpr CrcTables make_crc_tables() {
+    CrcTables t{};
+    for (uint32_t i = 0; i < 256; i++) { uint32_t c = i; for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((c & 1u) ? CRC_POLY : 0u); t.slice[0][i] = c; }
+    for (int k = 1; k < 4; k++) for (uint32_t i = 0; i < 256; i++) t.slice[k][i] = (t.slice[k - 1][i] >> 8) ^ t.slice[0][t.slice[k - 1][i] & 0xffu];
+    t.xpow[0] = 0x80000000u;
+    for (int s = 1; s < 1024; s++) t.xpow[s] = (t.xpow[s - 1] >> 8) ^ t.slice[0][t.xpow[s - 1] & 0xffu];   // one more zero byte
+    const uint32_t x1024 = (t.xpow[1023] >> 8) ^ t.slice[0][t.xpow[1023] & 0xffu];
+    for (int k = 0; k < 4; k++) for (uint32_t i = 0; i < 256; i++) t.step[k][i] = crc_mulmod(i << (8 * k), x1024);
+    return t;
+}
+__device__ const CrcTables d_crc = make_crc_tables();
+constexpr int CRC_LDS_WORDS = 2 * 4 * 256;                      // slice + step tables, staged in the decode tables' LDS once a block is decoded
+
+__device__ __forceinline__ uint32_t crc_word(const uint32_t* tab, uint32_t c, uint32_t w) {   // four bytes, slice-by-4
+    c ^= w;
+    return tab[3 * 256 + (c & 0xffu)] ^ tab[2 * 256 + ((c >> 8) & 0xffu)] ^ tab[256 + ((c >> 16) & 0xffu)] ^ tab[c >> 24];
+}
+__device__ __forceinline__ uint32_t crc_byte(const uint32_t* tab, uint32_t c, uint8_t v) { return tab[(c ^ v) & 0xffu] ^ (c >> 8); }
+
 // Output bytes go straight to global memory and a match reads them back from there (behind a fence when they were stored since the
 // last one).  (A variant that kept the last 4 / 8 KB in an LDS ring - near matches as LDS-to-LDS copies, aligned 1 KB flushes - cost a
 // third of the occupancy and measured equal or slower: profiles/experiments/gpu_inflate/inflate_dev_with_lds_ring.hip.)
 __device__ unsigned long long d_prof[8];          // PROF builds only (tools/gpu_inflate_bench): cycles of wave-time per phase, summed over the blocks
 #define XCK_PROF_AT(k) do { if constexpr (PROF) { const long long t_ = clock64(); prof[k] += (unsigned long long)(t_ - t_prev); t_prev = t_; } } while (0)
 
-template <bool PROF>
+template <bool PROF, bool CRC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_inflate(const uint8_t* __restrict__ in, const DevBlock* __restrict__ blocks, int n_blocks,
                                                 uint8_t* out, int32_t* __restrict__ status, uint8_t* host_out) {
+    static_assert(sizeof(Smem) >= CRC_LDS_WORDS * sizeof(uint32_t), "the CRC tables live in the decode tables' LDS");
     __shared__ Smem sm;
     __shared__ uint32_t win[IN_WIN / 4];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -426,7 +477,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         }
         if (bfinal) break;
     }
-    if constexpr (PROF) { XCK_PROF_AT(7); if (lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&d_prof[k], prof[k]); }
     {
         // consumed input must lie inside the stream (the window is zero beyond it: a truncated stream must not pass)
         const long long used_bits = (long long)((uint32_t)__builtin_amdgcn_readfirstlane((int)bi.pos) - A) * 8 - __builtin_amdgcn_readfirstlane(bi.bc);
@@ -436,14 +486,50 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         // waves' decoding instead of following the whole launch as a kernel of its own (which cost every chunk 1 - 3 ms of latency and
         // sent its 50 MB over PCIe in one burst).  16-byte stores where the block's own bytes fill an aligned 16, single bytes at its ends
         // (the neighbours' bytes are theirs to write).  host_out and out are equally aligned (both allocations are page aligned).
-        if (host_out && !err) {
+        // CRC: the same pass computes the block's CRC-32 over exactly these bytes (see CrcTables); a mismatch is INFLATE_ST_CRC.
+        if ((host_out || CRC) && !err) {
             __threadfence_block();
-            const uint8_t* ob = out + blk.out_off; uint8_t* hb = host_out + blk.out_off; const uint32_t n = blk.out_len;
+            const uint8_t* ob = out + blk.out_off; uint8_t* hb = host_out ? host_out + blk.out_off : nullptr; const uint32_t n = blk.out_len;
             const uint32_t head = min((16u - (uint32_t)((uintptr_t)ob & 15u)) & 15u, n), body = (n - head) & ~15u;
-            if ((uint32_t)lane < head) hb[lane] = ob[lane];
-            for (uint32_t i = (uint32_t)lane * 16; i < body; i += 1024) *(uint4*)(hb + head + i) = *(const uint4*)(ob + head + i);
-            for (uint32_t i = head + body + (uint32_t)lane; i < n; i += 64) hb[i] = ob[i];
+            uint32_t* const ctab = reinterpret_cast<uint32_t*>(&sm);       // (the decode tables are dead now)
+            if constexpr (CRC) {
+                __syncthreads();                                            // every lane is past its last table read
+                for (int k = lane; k < CRC_LDS_WORDS; k += 64) ctab[k] = reinterpret_cast<const uint32_t*>(&d_crc)[k];
+                __syncthreads();
+            }
+            if (host_out && (uint32_t)lane < head) hb[lane] = ob[lane];
+            uint32_t reg = 0, after = 0;                                    // this lane's register; bytes of the body behind its last piece
+            uint32_t h = 0xffffffffu;                                       // lane 0: the register after the head bytes (init included)
+            if constexpr (CRC) { if (lane == 0) for (uint32_t k = 0; k < head; k++) h = crc_byte(ctab, h, ob[k]); }
+#pragma unroll 2
+            for (uint32_t i = (uint32_t)lane * 16; i < body; i += 1024) {
+                const uint4 v = *(const uint4*)(ob + head + i);
+                if (host_out) *(uint4*)(hb + head + i) = v;
+                if constexpr (CRC) {
+                    const uint32_t* st = ctab + 4 * 256;
+                    uint32_t c = i == 0 ? h : 0u;                           // (piece 0 follows the head: lane 0 goes on from there)
+                    c = crc_word(ctab, c, v.x); c = crc_word(ctab, c, v.y); c = crc_word(ctab, c, v.z); c = crc_word(ctab, c, v.w);
+                    reg = (st[3 * 256 + (reg >> 24)] ^ st[2 * 256 + ((reg >> 16) & 0xffu)] ^ st[256 + ((reg >> 8) & 0xffu)] ^ st[reg & 0xffu]) ^ c;
+                    after = body - i - 16;
+                }
+            }
+            for (uint32_t i = head + body + (uint32_t)lane; host_out && i < n; i += 64) hb[i] = ob[i];
+            if constexpr (CRC) {
+                if (body == 0 && lane == 0) reg = h;
+                const uint32_t tail = n - head - body;
+                // reg x^(8 (after + tail)): the bytes behind this lane's last piece (< 1024)
+                uint32_t p = 0, m = d_crc.xpow[(after + tail) & 1023u];
+#pragma unroll
+                for (int k = 31; k >= 0; k--) { p ^= ((reg >> k) & 1u) ? m : 0u; m = (m >> 1) ^ ((m & 1u) ? CRC_POLY : 0u); }
+                uint32_t all = wave_xor_all(p);
+                if (lane == 0) {
+                    uint32_t t = 0;                                         // the tail bytes, from a zero register
+                    for (uint32_t k = head + body; k < n; k++) t = crc_byte(ctab, t, ob[k]);
+                    if (((all ^ t) ^ 0xffffffffu) != blk.crc) err = INFLATE_ST_CRC;
+                }
+            }
         }
+        if constexpr (PROF) { XCK_PROF_AT(7); if (lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&d_prof[k], prof[k]); }
         if (lane == 0) status[b] = err;
     }
 }
@@ -455,11 +541,14 @@ void dev_inflate_read_prof(unsigned long long out[8]) {
     unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(d_prof), z, sizeof z);
 }
 
-int dev_inflate_launch(hipStream_t stream, const uint8_t* d_in, const DevBlock* d_blocks, int n_blocks, uint8_t* d_out, int32_t* d_status, uint8_t* host_out, int variant) {
+int dev_inflate_launch(hipStream_t stream, const uint8_t* d_in, const DevBlock* d_blocks, int n_blocks, uint8_t* d_out, int32_t* d_status, uint8_t* host_out, int variant, bool check_crc) {
     if (n_blocks <= 0) return 0;
     const dim3 g((unsigned)n_blocks), t(64);
-    if (variant >= 10) hipLaunchKernelGGL((k_inflate<true>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
-    else hipLaunchKernelGGL((k_inflate<false>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
+    if (variant >= 10) {
+        if (check_crc) hipLaunchKernelGGL((k_inflate<true, true>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
+        else hipLaunchKernelGGL((k_inflate<true, false>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
+    } else if (check_crc) hipLaunchKernelGGL((k_inflate<false, true>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
+    else hipLaunchKernelGGL((k_inflate<false, false>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -524,12 +613,12 @@ bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_byt
 // push time rose from 0.25 to 1.6 s per 100 M records.  The kernel is bound by its serial Huffman chain, not by bytes: it takes
 // the compressed stream from host memory in 1 KB coalesced windows, every wave stores its finished block to the host block, and the
 // statuses go straight back.
-int gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks) {
+int gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks, bool check_crc) {
     (void)in_bytes;
     if (hipSetDevice(s->device) != hipSuccess) return -1;
     for (size_t i = 0; i < n_blocks; i++) s->h_st[i] = -1;                  // (a block the kernel never reaches is left to the host)
     (void)out_bytes;
-    if (dev_inflate_launch(s->stream, s->a_in, s->a_bl, (int)n_blocks, s->d_out, s->a_st, s->a_out, s->variant) != 0) { (void)hipGetLastError(); return -1; }
+    if (dev_inflate_launch(s->stream, s->a_in, s->a_bl, (int)n_blocks, s->d_out, s->a_st, s->a_out, s->variant, check_crc) != 0) { (void)hipGetLastError(); return -1; }
     if (hipEventRecord(s->done, s->stream) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return 0;
 }

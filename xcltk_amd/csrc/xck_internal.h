@@ -52,7 +52,8 @@ struct DecodeCfg {
     char umi_tag[2] = {0, 0};
     int  umi_bits = 64;
     bool want_seq = false;
-    bool verify_crc = false;
+    bool verify_crc = false;             // check the CRC32 of every block the record decoder inflates (XCK_F_VERIFY_CRC, XCK_F_DEVICE_CRC)
+    bool crc_on_device = false;          // ... and keep the GPU share of the inflate: the kernel checks its blocks (XCK_F_DEVICE_CRC)
     int  n_threads = 0;
     int64_t max_batch_reads = 0;
     // barcode hash (open addressing over the barcode strings)
@@ -111,8 +112,13 @@ struct Knobs {
     int  gpu_inflate_ring = 12;          // XCK_GPU_INFLATE_RING: chunks in flight (host + device) while the GPU share is on
     int  gpu_inflate_min_mb = 96;        // XCK_GPU_INFLATE_MIN_MB: auto mode only for files (index ranges) of at least this many compressed MB
     int  gpu_inflate_free_cus = 32;      // XCK_GPU_INFLATE_FREE_CUS: CUs the inflate streams never use (they stay free for the join kernels)
+    int  verify_crc = 0;                 // XCK_VERIFY_CRC: 0 = as the flags say, 1 = host (XCK_F_VERIFY_CRC ORed in), 2 = device (XCK_F_DEVICE_CRC)
     static Knobs from_env();             // api.cpp
 };
+
+// xck_decode_stats counters (include/xck.h), in this order.  A reader counts in its own set; every decode call adds what it counted
+// since the last call to its handle's (bam.cpp fold_decode_stats).
+enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_N };
 
 // the decoder's own batches are valid by construction and skip the O(n) check of xck_push_batch()
 int push_trusted(xck_engine* e, const xck_batch* b);
@@ -136,6 +142,7 @@ struct xck_engine {
     struct PushRing { void* blk[3] = {nullptr, nullptr, nullptr}; size_t cap[3] = {0, 0, 0}; void* fence[3] = {nullptr, nullptr, nullptr}; int next = 0; } push_ring;   // pinned blocks of xck_push_batch's one-copy form (api.cpp)
     xck::Knobs knobs;                    // the environment, read once at xck_create
     std::atomic<int64_t> gpu_inflate_chunks{0};   // chunks inflated on the device by the readers that fed this handle (xck_stats)
+    std::atomic<int64_t> dstat[xck::DS_N] = {};   // xck_decode_stats, summed over the readers that fed this handle since the last xck_reset
     int mode = 0;
     int umi_bits = 64;
     int32_t n_cells = 0, n_contigs = 0;  // bounds that caller-supplied batches are checked against (xck_push_batch)

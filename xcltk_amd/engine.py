@@ -378,6 +378,13 @@ class Engine(object):
         self._check(self.lib.xck_get_stats(self.h, C.byref(st)), "xck_get_stats")
         return {k: getattr(st, k) for k, _ in capi.Stats._fields_}
 
+    def decode_stats(self):
+        """The BAM decoder's counters since the last reset (xck_get_decode_stats): GPU share of the inflate, CRC checks."""
+        st = capi.DecodeStats()
+        st.struct_size = C.sizeof(capi.DecodeStats)
+        self._check(self.lib.xck_get_decode_stats(self.h, C.byref(st)), "xck_get_decode_stats")
+        return {k: getattr(st, k) for k, _ in capi.DecodeStats._fields_ if k not in ("struct_size", "reserved0")}
+
 
 class BamStream(object):
     """One open BAM being streamed through an Engine in slices (xck_ingest_opts.pause_records)."""
