@@ -41,6 +41,10 @@
  *                                         nothing to the flags; any other value means host.  Intact files give identical results either way; a damaged
  *                                         block fails the decode call with XCK_E_IO ("BGZF CRC mismatch", the file and the block's offset) instead
  *                                         of being counted.
+ *   XCK_READ_FATE=1                       every handle that drives a GPU counts where its reads went, as if made with XCK_F_READ_FATE (xck_get_read_fate) -
+ *                                         for front-ends whose calls do not carry the flags: they then write read_summary.tsv next to their matrices.
+ *                                         One small kernel more per join launch; off (the default, or 0) nothing is allocated or launched.  Decode-only
+ *                                         handles ignore it.
  * Decoder (read when a BAM is opened or once per process): XCK_THREADS, XCK_NUMA=0, XCK_INFLATE=zlib, XCK_CHUNK_BYTES,
  * XCK_WRITE_THREADS (writer threads of xck_write_mtx), XCK_TEST_INTERN_LIMIT (tests). */
 #ifndef XCK_H
@@ -145,6 +149,9 @@ typedef struct xck_config {
                                    whose CRC32 differs from its footer's fails the decode call with XCK_E_IO                   */
 #define XCK_F_LOW_PRIORITY   8  /* run this engine's kernels on a low-priority HIP stream: lets a second
                                    engine fill the GPU while the first one copies results out */
+#define XCK_F_READ_FATE     32  /* count, on the device, which of the classes of xck_read_fate every pushed read falls into
+                                   (xck_get_read_fate; one more small kernel behind every join launch).  Changes no result.
+                                   XCK_E_ARG together with XCK_F_DECODE_ONLY                                              */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -222,6 +229,32 @@ typedef struct xck_decode_stats {
     int64_t gpu_path_given_up;        /* readers whose GPU share of the inflate was turned off by a runtime error or lack of memory */
 } xck_decode_stats;
 
+/* Where the reads of ONE pipeline went, since the last xck_reset (handles made with XCK_F_READ_FATE; additive, ABI 3 is unchanged).
+ * Every pushed record falls into exactly one class - the first that applies, in the order of the fields, which is the order of the
+ * reference's check_read() (rdr/fc/core.py:46-62 == baf/fc/core.py:18-34) followed by fetch() and the include test:
+ * n_reads == not_joined + low_mapq + ... + assigned.  struct_size = sizeof(xck_read_fate), as for xck_decode_stats. */
+typedef struct xck_read_fate {
+    uint32_t struct_size;
+    int32_t  mode;              /* XCK_MODE_BASEFC or XCK_MODE_BAF: the pipeline these counters belong to                    */
+    int64_t  n_reads;           /* = xck_stats.n_reads                                                                        */
+    int64_t  not_joined;        /* reads of batches no kernel saw (counted on the host): batch contig < 0, or a contig without
+                                   a region (basefc) / without a SNP (BAF) in this handle's tables                             */
+    int64_t  low_mapq;          /* mapq < min_mapq                                    (check_read -2,  rdr/fc/core.py:47-48)  */
+    int64_t  excl_flag;         /* excl_flag && (flag & excl_flag)                    (-3,  :49-50)                           */
+    int64_t  incl_flag;         /* incl_flag && !(flag & incl_flag)                   (-4,  :51-52)                           */
+    int64_t  orphan;            /* no_orphan, paired and not a proper pair            (-5,  :53-54)                           */
+    int64_t  no_cell;           /* cell < 0: tag missing, empty, or barcode not in the list (-11, :55-56; rdr/fc/mcount.py push_read) */
+    int64_t  no_umi;            /* key == XCK_UMI_NONE: tag missing or empty          (-12, :57-58)                           */
+    int64_t  short_aligned;     /* aligned (M/=/X) bases < min_len                    (-21, :59-60)                           */
+    int64_t  no_target;         /* basefc: no region with pos < end0 && endpos > start0 (the fetch() of utils/sam.py:85-118);
+                                   BAF: no SNP of the list with pos <= p0 < endpos (whether the SNP lies in a region is not asked) */
+    int64_t  include_fail;      /* basefc only: fetched by at least one region, none passes min_include (rdr/fc/core.py:160-165) */
+    int64_t  assigned;          /* at least one region accepts the read / at least one SNP is covered                         */
+    int64_t  multi;             /* ... of which two or more do (duplicate regions / SNPs count each, as in the join)           */
+    int64_t  pairs;             /* accepted (read, region) / (read, SNP) pairs, summed over the assigned reads: = the pipeline's
+                                   share of xck_stats.n_hits                                                                  */
+} xck_read_fate;
+
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
 
@@ -267,6 +300,12 @@ int  xck_reset(xck_engine* e);
 int  xck_get_stats(const xck_engine* e, xck_stats* out);
 /* The decoder's counters (xck_decode_stats; set out->struct_size first).  Works on decode-only handles too. */
 int  xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out);
+/* The read assignment summary of one pipeline (set out->struct_size first): mode = XCK_MODE_BASEFC or XCK_MODE_BAF names it - the
+ * handle's own mode, or either one on a XCK_MODE_BOTH handle, whose two pipelines keep their own counters (a contig may have
+ * regions and no SNPs).  Waits for the handle's queued work as xck_flush does.  XCK_E_STATE on a handle made without
+ * XCK_F_READ_FATE, XCK_E_ARG for a pipeline the handle does not have.  With contigs cut over several GPUs (xck_ingest_opts.tid_beg)
+ * the reads that straddle a cut are seen by both neighbours, and no_target is relative to the regions of the handle that saw the read. */
+int  xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

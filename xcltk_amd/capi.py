@@ -19,6 +19,7 @@ XCK_F_VERIFY_CRC = 2
 XCK_F_DECODE_ONLY = 4
 XCK_F_LOW_PRIORITY = 8
 XCK_F_DEVICE_CRC = 16
+XCK_F_READ_FATE = 32
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,6 +105,17 @@ class DecodeStats(C.Structure):
                 ("crc_device_host_disagree", C.c_int64), ("gpu_path_given_up", C.c_int64)]
 
 
+class ReadFate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32)] + [(k, C.c_int64) for k in (
+        "n_reads", "not_joined", "low_mapq", "excl_flag", "incl_flag", "orphan", "no_cell", "no_umi", "short_aligned",
+        "no_target", "include_fail", "assigned", "multi", "pairs")]
+
+
+# the counters of xck_read_fate in the struct's order: n_reads, the classes that sum to it (READ_FATE_CLASSES), multi, pairs
+READ_FATE_FIELDS = tuple(k for k, _ in ReadFate._fields_[2:])
+READ_FATE_CLASSES = READ_FATE_FIELDS[1:-2]
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -136,6 +148,7 @@ SYMBOLS = [
     ("xck_reset", C.c_int, [C.c_void_p]),
     ("xck_get_stats", C.c_int, [C.c_void_p, _P(Stats)]),
     ("xck_get_decode_stats", C.c_int, [C.c_void_p, _P(DecodeStats)]),
+    ("xck_get_read_fate", C.c_int, [C.c_void_p, C.c_int, _P(ReadFate)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

@@ -59,6 +59,7 @@ Knobs xck::Knobs::from_env() {
     k.gpu_inflate_min_mb = (int)std::max(0ll, num("XCK_GPU_INFLATE_MIN_MB", 96));
     k.gpu_inflate_free_cus = (int)num("XCK_GPU_INFLATE_FREE_CUS", 32);
     k.verify_crc = !strcmp(str("XCK_VERIFY_CRC"), "device") ? 2 : (!*str("XCK_VERIFY_CRC") || !strcmp(str("XCK_VERIFY_CRC"), "0")) ? 0 : 1;   // (any other value: host)
+    k.read_fate = num("XCK_READ_FATE", 0) != 0;
     return k;
 }
 
@@ -73,8 +74,10 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if (cfg->mode != XCK_MODE_BASEFC && cfg->mode != XCK_MODE_BAF && cfg->mode != XCK_MODE_BOTH) { set_thread_error("invalid mode"); return XCK_E_ARG; }
     if (cfg->n_cells <= 0 || cfg->n_contigs < 0 || cfg->n_regions < 0 || cfg->n_snps < 0) { set_thread_error("invalid table sizes"); return XCK_E_ARG; }
     if ((cfg->n_regions > 0 && !cfg->regions) || (cfg->n_snps > 0 && !cfg->snps)) { set_thread_error("null table pointer"); return XCK_E_ARG; }
+    if ((cfg->flags & XCK_F_READ_FATE) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_READ_FATE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
+    e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate);
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
     e->n_cells = cfg->n_cells; e->n_contigs = cfg->n_contigs;
@@ -85,6 +88,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             xck_config c = *cfg;
             c.mode = modes[k];
             if (n == 2) c.flags |= XCK_F_LAYOUT_BOTH;          // one key layout -> one decode serves both pipelines
+            if (e->read_fate) c.flags |= XCK_F_READ_FATE;      // (XCK_READ_FATE=1)
             e->impl = nullptr;
             int rc = engine_create(&c, e);
             e->impls[k] = e->impl; e->n_impl = k + 1;
@@ -223,6 +227,19 @@ int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
                          &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up };
     for (int k = 0; k < DS_N; k++) *f[k] = e->dstat[k].load();
     return XCK_OK;
+}
+
+int xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_read_fate)) { e->err = "xck_read_fate.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (!e->read_fate || e->n_impl <= 0) { e->err = "handle made without XCK_F_READ_FATE"; return XCK_E_STATE; }
+    if ((mode != XCK_MODE_BASEFC && mode != XCK_MODE_BAF) || !(e->mode & mode)) { e->err = "xck_get_read_fate: the handle has no such pipeline"; return XCK_E_ARG; }
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    e->impl = e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
+    const int rc = engine_read_fate(e, out);
+    e->impl = e->impls[0];
+    return rc;
 }
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; FOR_IMPLS(e, engine_finish_async(e)); return XCK_OK; }

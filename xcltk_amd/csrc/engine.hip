@@ -1795,6 +1795,9 @@ struct EngineImpl {
     int32_t* h_res[4] = {nullptr, nullptr, nullptr, nullptr}; size_t h_res_cap[4] = {0, 0, 0, 0}; size_t res_nnz[4] = {0, 0, 0, 0};
     int32_t* d_res[4] = {nullptr, nullptr, nullptr, nullptr};   // device copies [row | col | val] inside the workspace, valid until the next finish / reset
     bool finished = false;
+    // read assignment summary (XCK_F_READ_FATE, read_fate.h): device counters (null = off), reads of the batches no kernel saw
+    unsigned long long* d_fate = nullptr;
+    int64_t n_not_joined = 0;
 };
 
 static size_t key_bytes(const EngineImpl* im) { return im->key_bits == 64 ? 8 : 16; }
@@ -2015,6 +2018,8 @@ static int launch_join_t(EngineImpl* im) {
 }
 static int launch_join(EngineImpl* im) { return im->key_bits == 64 ? launch_join_t<uint64_t>(im) : launch_join_t<u128>(im); }
 
+#include "read_fate.h"
+
 // wait for the launch in flight, collect cursor / timing; if its fragments did not fit, grow, rewind and replay
 static int complete_pending(EngineImpl* im) {
     while (!im->inflight.empty()) {
@@ -2067,7 +2072,8 @@ static int launch_queue(EngineImpl* im, int slot_idx, int shared_slot = -1) {
     if (shared_slot >= 0) ((Stager*)im->eng->stager)->slot[shared_slot].users++;
     for (int sh = 0; sh < NSHARD; sh++) { im->cur_before[sh] = im->cur[sh]; im->ncur_before[sh] = im->ncur[sh]; im->acc_before[sh] = im->h_ctl[ctl_accepted(sh)]; }
     if (slot_idx >= 0) im->slot[slot_idx].busy = true;
-    return launch_join(im);
+    rc = launch_join(im); if (rc) return rc;
+    return launch_read_fate(im);                               // (off: returns at once)
 }
 
 int engine_push(xck_engine* e, const xck_batch* b, bool device_resident) {
@@ -2075,7 +2081,7 @@ int engine_push(xck_engine* e, const xck_batch* b, bool device_resident) {
     if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
     if (im->finished) { e->err = "push after finish (call xck_reset)"; return XCK_E_STATE; }
     im->st.n_batches++; im->st.n_reads += b->n_reads;
-    if (b->n_reads <= 0 || b->contig < 0) return 0;
+    if (b->n_reads <= 0 || b->contig < 0) { im->n_not_joined += std::max(b->n_reads, 0); return 0; }
     if (b->contig >= (int)im->ctab.size()) { e->err = "batch contig out of range"; return XCK_E_ARG; }
     // (host batches: a null cigar / seq pointer is fine when its offset range is empty - the same rule as xck_push_batch's check and
     // its packed form; device-resident batches: the offsets live in HBM, so the pointers must be there)
@@ -2085,7 +2091,7 @@ int engine_push(xck_engine* e, const xck_batch* b, bool device_resident) {
     HIP_TRY(hipSetDevice(im->device));
     const ContigTab& t = im->ctab[b->contig];
     bool has_targets = im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0;
-    if (!has_targets) return 0;
+    if (!has_targets) { im->n_not_joined += b->n_reads; return 0; }
     BatchDesc d;
     memset(&d, 0, sizeof d);
     d.n = b->n_reads; d.ordinal_base = b->ordinal_base;
@@ -2178,10 +2184,10 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
         for (int i = 0; i < n; i++) {
             const xck_batch* b = &batches[i];
             im->st.n_batches++; im->st.n_reads += b->n_reads;
-            if (b->n_reads <= 0 || b->contig < 0) continue;
+            if (b->n_reads <= 0 || b->contig < 0) { im->n_not_joined += std::max(b->n_reads, 0); continue; }
             if (b->contig >= (int)im->ctab.size()) { e->err = "batch contig out of range"; return XCK_E_ARG; }
             const ContigTab& t = im->ctab[b->contig];
-            if (!(im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0)) continue;
+            if (!(im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0)) { im->n_not_joined += b->n_reads; continue; }
             if (im->mode == XCK_MODE_BAF && (!b->seq_off || !b->seq)) { e->err = "BAF mode needs seq arrays"; return XCK_E_ARG; }
             BatchDesc d; memset(&d, 0, sizeof d);
             d.n = b->n_reads; d.ordinal_base = b->ordinal_base;
@@ -2723,6 +2729,8 @@ int engine_reset(xck_engine* e) {
     rc = complete_pending(im); if (rc) return rc;
     if (im->copy_pending) { HIP_TRY(hipStreamSynchronize(im->s_copy)); im->copy_pending = false; }
     HIP_TRY(hipMemsetAsync(im->d_ctl, 0, CTL_WORDS * sizeof(unsigned long long), im->s_comp));
+    if (im->d_fate) HIP_TRY(hipMemsetAsync(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long), im->s_comp));
+    im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false;
     for (int i = 0; i < CTL_WORDS; i++) im->h_ctl[i] = 0;
@@ -2797,6 +2805,10 @@ int engine_create(const xck_config* cfg, xck_engine* e) {
     memset(im->h_ctl, 0, CTL_WORDS * sizeof(unsigned long long));
     HIP_TRY(hipHostGetDevicePointer((void**)&im->d_hctl, im->h_ctl, 0));
     rc = ensure_hits(im, (size_t)e->knobs.hit_cap0); if (rc) return rc;   // (XCK_HIT_CAP0: test knob)
+    if (cfg->flags & XCK_F_READ_FATE) {
+        HIP_TRY(hipMalloc((void**)&im->d_fate, RF_WORDS * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long)));
+    }
     return 0;
 }
 
@@ -2806,7 +2818,7 @@ void engine_destroy(xck_engine* e) {
     hipSetDevice(im->device);
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
-                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta,
+                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate,
                      im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }

@@ -385,6 +385,22 @@ class Engine(object):
         self._check(self.lib.xck_get_decode_stats(self.h, C.byref(st)), "xck_get_decode_stats")
         return {k: getattr(st, k) for k, _ in capi.DecodeStats._fields_ if k not in ("struct_size", "reserved0")}
 
+    def read_fate(self, mode=None):
+        """Where the reads of one pipeline went since the last reset (xck_get_read_fate): dict of the counters in the struct's
+        order, or None on a handle made without XCK_F_READ_FATE (and without XCK_READ_FATE=1 in the environment).  mode names the
+        pipeline: the handle's own by default, XCK_MODE_BASEFC or XCK_MODE_BAF on a XCK_MODE_BOTH handle.  Waits for queued work."""
+        if mode is None:
+            if self.mode == capi.XCK_MODE_BOTH:
+                raise ValueError("read_fate(): a XCK_MODE_BOTH handle has two pipelines, name one")
+            mode = self.mode
+        rf = capi.ReadFate()
+        rf.struct_size = C.sizeof(capi.ReadFate)
+        rc = self.lib.xck_get_read_fate(self.h, int(mode), C.byref(rf))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_read_fate")
+        return {k: int(getattr(rf, k)) for k in capi.READ_FATE_FIELDS}
+
 
 class BamStream(object):
     """One open BAM being streamed through an Engine in slices (xck_ingest_opts.pause_records)."""

@@ -318,6 +318,39 @@ def write_mtx(eng, dist, path, coo_k, rm, n_rows_out):
         eng.write_mtx_arrays(path, coo_k, rm, n_rows_out)
 
 
+def read_summary_text(fate, n_ranks=1, cut_contigs=0):
+    """Text of read_summary.tsv: one `name\\tcount` line per counter of xck_read_fate, in the struct's order; runs of several
+    ranks start with `#ranks=N cut_contigs=K`."""
+    from .capi import READ_FATE_FIELDS
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    return head + "".join("%s\t%d\n" % (k, int(fate[k])) for k in READ_FATE_FIELDS)
+
+
+def write_read_summary(eng, dist, path, mode=None, log_prefix="[engine]"):
+    """Read assignment summary of one pipeline (Engine.read_fate) -> `path`, when the handle counts it (XCK_READ_FATE=1 in the
+    environment, or XCK_F_READ_FATE): nothing happens otherwise.  Multi-GPU: a collective call - the counters are summed over the
+    ranks and the writer rank writes the file.  Where a contig is cut over ranks (cut_contigs > 0) the reads that straddle a cut
+    are decoded by both neighbours and so counted twice, and each rank judges `no_target` against the regions it owns: the sums
+    then describe the ranks' work, not the file.  Returns the (summed) dict or None."""
+    from .capi import READ_FATE_FIELDS
+    read_fate = getattr(eng, "read_fate", None)                # (an engine-like object without the method counts nothing)
+    fate = read_fate(mode) if read_fate else None
+    if fate is None:
+        return None
+    n_ranks, cut = 1, 0
+    if dist is not None and dist.active:
+        v = dist.all_reduce_np(np.array([fate[k] for k in READ_FATE_FIELDS], dtype=np.int64))
+        fate = dict(zip(READ_FATE_FIELDS, (int(x) for x in v)))
+        n_ranks = dist.world
+        cut = len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
+    info("%s read summary: %s" % (log_prefix, " ".join("%s=%d" % (k, fate[k]) for k in READ_FATE_FIELDS)))
+    if is_writer_rank():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fp:
+            fp.write(read_summary_text(fate, n_ranks, cut))
+    return fate
+
+
 # ----------------------------------------------------------------------------- engine driver
 def make_engine(conf, mode, regions, snps=(), device=None, **extra):
     """Build the per-GPU engine from a resolved Config."""

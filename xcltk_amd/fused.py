@@ -14,7 +14,7 @@ from logging import error, info
 from . import fc_common as fcc
 from .baf.fc.config import Config as BafConfig
 from .baf.fc.main import prepare_config as baf_prepare
-from .capi import XCK_MODE_BOTH
+from .capi import XCK_MODE_BAF, XCK_MODE_BASEFC, XCK_MODE_BOTH
 from .engine import XckError
 
 
@@ -55,6 +55,9 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
         error(str(e))
         return -1
     try:
+        # (XCK_READ_FATE=1 only; the two pipelines keep their own counters: a contig may have regions and no SNPs)
+        fcc.write_read_summary(eng, dist, os.path.join(fc_dir, "read_summary.tsv"), XCK_MODE_BASEFC, "[fused basefc]")
+        fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"), XCK_MODE_BAF, "[fused baf]")
         if coo is None:
             return 0
         n = len(regions)                                  # (sharded output: every rank is here and the calls below are collective)
