@@ -284,8 +284,8 @@ int  xck_push_batch(xck_engine* e, const xck_batch* b);
  * The contents cannot be checked from the host: the same invariants are the caller's word. */
 int  xck_push_batch_device(xck_engine* e, const xck_batch* b);
 int  xck_flush(xck_engine* e);                    /* wait for all queued device work */
-/* Fold all hits into the final sparse matrices (radix sort + segmented reduce on the GPU) and copy
- * them to engine-owned pinned host memory. */
+/* Fold all hits into the final sparse matrices (on the GPU: partition + one LDS pass per work item, radix sort
+ * as the fallback) and copy them to engine-owned pinned host memory. */
 int  xck_finish(xck_engine* e, xck_result* out);
 /* Same fold, but returns as soon as the copy-out of the matrices has been ENQUEUED on the engine's copy
  * stream; a following xck_finish() waits for it and hands out the pointers.  Lets the caller run other

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """HBM-resident join / fold stage times of one engine build (XCK_LIB selects the .so): 500 M synthetic reads generated on the
-device, N passes per mode.  usage: join_time.py [reads] [passes] [modes: fc,baf]"""
-import os, sys
+device, N passes per mode; "first finish" = host time of the first xck_finish of the fresh handle (it pays the arena hipMallocs).
+usage: join_time.py [reads] [passes] [modes: fc,baf]"""
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT]
 import torch
@@ -24,10 +25,12 @@ for label in modes:
         for b in bs:
             eng.push(b, device_resident=True)
         eng.flush()
+        t0 = time.perf_counter()
         res = eng.finish(copy=False)
+        if rep == 0: first = (time.perf_counter() - t0) * 1e3
         st = eng.stats()
         if rep >= 2:
             js.append(st["ms_join"]); fs.append(st["ms_sort"])
-    print("%s %-4s join %.3f ms  fold %.3f ms  (hits %d unique %d nnz %s)" % (os.environ.get("XCK_LIB", "libxck.so").split("/")[-1], label, sum(js) / len(js), sum(fs) / len(fs),
+    print("%s %-4s join %.3f ms  fold %.3f ms  first finish %.1f ms  (hits %d unique %d nnz %s)" % (os.environ.get("XCK_LIB", "libxck.so").split("/")[-1], label, sum(js) / len(js), sum(fs) / len(fs), first,
           st["n_hits"], st["n_hits_unique"], [len(v[0]) for v in res.values()]), flush=True)
     eng.close()

@@ -1,0 +1,202 @@
+// engine_impl.h - what the two translation units of the engine share: engine.hip (tables, join kernels, push pipeline) and
+// finish.hip (fold kernels, finish driver).  Types, control-word layout, the per-GPU state (EngineImpl), the tuning macros both
+// sides read, and the host helpers one side defines for the other.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+#include <hip/hip_runtime.h>
+#include "xck_internal.h"
+
+namespace xck {
+typedef unsigned __int128 u128;
+constexpr int JOIN_BLOCK = 256;
+
+// hipGetLastError() after a launch also returns (and clears) an error that some EARLIER, unchecked runtime call of this thread
+// left behind; the launch sites clear it first, and XCK_DEBUG_TIMING reports what was there.
+static inline void clear_stale_error(const char* where, bool report = false) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess && report) fprintf(stderr, "[xck] %s: cleared a stale HIP error left by an earlier call: %s [%d]\n", where, hipGetErrorString(e), (int)e);
+}
+#define HIP_TRY(expr)                                                                      \
+    do { hipError_t e_ = (expr); if (e_ != hipSuccess) {                                   \
+        char b_[512]; snprintf(b_, sizeof b_, "%s failed: %s [%d] (%s:%d)", #expr,         \
+                               hipGetErrorString(e_), (int)e_, __FILE__, __LINE__);        \
+        im->eng->err = b_; return XCK_E_DEVICE; } } while (0)
+
+template <class K> struct KeyLayout {
+    int ubits, cbits;
+    __host__ __device__ K make(uint32_t row, uint32_t cell, uint64_t umi) const {
+        return (K(row) << (cbits + ubits)) | (K(cell) << ubits) | K(umi);
+    }
+    __host__ __device__ K rc(K k) const { return k >> ubits; }
+    __host__ __device__ uint32_t row(K k) const { return uint32_t(k >> (cbits + ubits)); }
+    __host__ __device__ uint32_t cell(K k) const { return uint32_t((k >> ubits) & ((K(1) << cbits) - 1)); }
+    __host__ __device__ uint64_t umi(K k) const { return ubits >= 64 ? uint64_t(k) : uint64_t(k & ((K(1) << ubits) - 1)); }
+};
+
+struct ReadFilter {                      // check_read(), rdr/fc/core.py:46-62
+    int32_t min_mapq, min_len;
+    uint32_t incl_flag, excl_flag;
+    int32_t no_orphan;
+    int32_t frac_mode;                   // rdr/fc/core.py:160-165
+    double  min_inc_frac;
+    int32_t min_inc_len;
+};
+
+struct SnpFilter { int32_t min_count; double min_maf; };
+
+#define XCK_GLOBAL __attribute__((address_space(1)))
+template <class T> __device__ __forceinline__ const XCK_GLOBAL T* as_global(const T* p) { return (const XCK_GLOBAL T*)p; }
+
+// One queued record batch (device pointers) inside a fused launch.
+struct BatchDesc {
+    int32_t n, tile0;                       // reads, first tile of this batch in the fused grid
+    const int32_t* pos; const uint16_t* flag; const uint8_t* mapq; const int32_t* cell;
+    const uint64_t* umi; const uint32_t* cig_off; const uint32_t* cigar;
+    const uint32_t* seq_off; const uint8_t* seq;
+    uint64_t ordinal_base;
+    int32_t reg_lo, reg_hi;                                 // regions of the batch's contig: [reg_lo, reg_hi) of the start-sorted arrays
+    const int32_t* snp_win; int32_t n_swin; int32_t snp_end; // SNP window table of the batch's contig
+};
+
+// Per-tile facts computed once by k_tile_meta (one thread per tile, all tiles in parallel) so that
+// the join kernel's prologue is ONE load of this record plus ONE round of independent staging loads.
+struct TileMeta {
+    uint32_t c_lo, cg_n;                  // CIGAR words of the tile: [c_lo, c_lo + cg_n) are staged
+    int32_t  w0, nw, e0, n_ent;           // basefc: staged regions [e0, e0 + n_ent) of the start-sorted arrays; pileup: staged SNP windows [w0, w0 + nw)
+    int32_t  k0, nk;                      // pileup: staged SNPs [k0, k0+nk); basefc: k0 = position of the tile's first read
+    int32_t  b, r0, r1, pad;              // batch index, first / one-past-last read of the tile
+};
+
+// The append cursor is sharded: a returning atomicAdd on one word tops out near 88 ops/us on gfx950
+// (one L2 channel), which bounded the first two versions of this kernel.  Tiles use shard
+// blockIdx % NSHARD; every shard owns its own cursor word (128 B apart -> different channels) and
+// its own slice [shard*cap, (shard+1)*cap) of the hit buffer; finish() packs the slices.
+constexpr int NSHARD = 16;
+constexpr int CTL_OVERFLOW = 1, CTL_GIANT = 2, CTL_SCRATCH = 3, CTL_SHARD0 = 16, CTL_STRIDE = 16;
+constexpr int XSHARD = NSHARD;            // k_expand: sharded totals / cursors (one shared word serialises at ~90 atomics/us); = NSHARD: its output slices feed the partition sort
+constexpr int CTL_X0 = CTL_SHARD0 + 2 * NSHARD * CTL_STRIDE;
+constexpr int CTL_WORDS = CTL_X0 + XSHARD * CTL_STRIDE;
+struct XBases { unsigned long long base[XSHARD]; };
+struct ShardSpan { unsigned long long start[NSHARD + 1]; };               // first packed index of every shard slice
+__host__ __device__ inline int ctl_cursor(int shard) { return CTL_SHARD0 + shard * CTL_STRIDE; }
+__host__ __device__ inline int ctl_umi_or(int shard) { return CTL_SHARD0 + shard * CTL_STRIDE + 1; }   // OR of the UMI codes seen
+__host__ __device__ inline int ctl_ncursor(int shard) { return CTL_SHARD0 + shard * CTL_STRIDE + 2; }  // cursor of the no-base stream
+__host__ __device__ inline int ctl_accepted(int shard) { return CTL_SHARD0 + (NSHARD + shard) * CTL_STRIDE; }
+
+// tuning macros that both translation units read (a variant build passes its -D flags to both)
+#ifndef XCK_BAF_SPLIT
+#define XCK_BAF_SPLIT 1           // pileup, 64-bit keys: hits without a base go to a second stream that is never sorted
+#endif
+
+// slot of a 64-bit key: full-rate VALU only (a 64-bit multiply is four quarter-rate v_mul ops on CDNA)
+template <int SLOTS>
+__device__ __forceinline__ uint32_t set_slot(unsigned long long kk) {
+    const uint32_t lo = (uint32_t)kk, hi = (uint32_t)(kk >> 32);
+    uint32_t x = lo ^ ((hi << 9) | (hi >> 23));
+    x ^= x >> 15;
+    // (written as asm: only bits 12.. of the product are used, so the compiler narrows __umul24 to a plain 32-bit multiply -
+    // v_mul_lo_u32, a quarter-rate instruction on gfx9 - where the 24-bit form issues at full rate)
+    uint32_t p;
+    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(p) : "v"(x), "v"(0x9E3779u));
+    return (p >> 12) & (SLOTS - 1);
+}
+
+// Control words go to the host through MAPPED pinned memory written by a tiny kernel, never through the
+// DMA engines: a 4 KB hipMemcpy D2H would queue behind a 170 MB result copy-out of another engine.
+static __global__ void k_publish(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ host_alias, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) host_alias[i] = src[i];
+}
+
+struct ContigTab { int32_t reg_base = 0, n_reg = 0, snp_base = 0, n_snp = 0, swin_base = 0, n_swin = 0; };
+
+struct BatchSlot {
+    int32_t* pos = nullptr; uint16_t* flag = nullptr; uint8_t* mapq = nullptr; int32_t* cell = nullptr;
+    uint64_t* umi = nullptr; uint32_t* cig_off = nullptr; uint32_t* cigar = nullptr; uint32_t* seq_off = nullptr; uint8_t* seq = nullptr;
+    size_t cap_reads = 0, cap_cig = 0, cap_seq = 0;
+    bool busy = false;
+};
+
+// grow-only device workspace: finish() sub-allocates from it instead of hipMalloc/hipFree per call
+struct Arena {
+    char* base = nullptr; size_t cap = 0, off = 0;
+    template <class T> T* get(size_t n) {
+        off = (off + 255) & ~size_t(255);
+        T* p = reinterpret_cast<T*>(base + off);
+        off += std::max<size_t>(n, 1) * sizeof(T);
+        return off <= cap ? p : nullptr;
+    }
+};
+
+struct EngineImpl {
+    xck_engine* eng = nullptr;
+    int mode = 0, device = 0;
+    int key_bits = 64, ubits = 0, cbits = 0, rbits = 0;
+    ReadFilter rf{};
+    SnpFilter sf{};
+    int no_dup_hap = 1;
+    int n_cells = 0, n_regions = 0, n_snps_sorted = 0;
+    std::vector<ContigTab> ctab;
+    // device tables
+    int32_t *d_reg_s0 = nullptr, *d_reg_e0 = nullptr, *d_reg_row = nullptr, *d_reg_pmax = nullptr;   // basefc: regions per contig sorted by start
+    int32_t *d_snp_p0 = nullptr, *d_snp_win = nullptr, *d_csr_off = nullptr, *d_csr_reg = nullptr;
+    uint32_t *d_snp_info = nullptr, *d_tally = nullptr;
+    hipStream_t s_copy = nullptr, s_comp = nullptr;
+    BatchSlot slot[2];
+    int next_slot = 0;
+    int64_t max_batch_reads = 0;
+    // hit accumulators (ping-pong pair so that sort results can stay where they land)
+    void* d_keys = nullptr; uint64_t* d_vals = nullptr; size_t hit_cap = 0;
+    void* d_nkeys = nullptr; uint64_t* d_nvals = nullptr;   // pileup split mode: hits without a base (same per-shard capacity)
+    unsigned long long ncur[NSHARD] = {0}, ncur_before[NSHARD] = {0}, ncursor = 0;
+    unsigned long long* d_ctl = nullptr;       // CTL_WORDS control words (overflow flag, scratch, sharded cursors)
+    unsigned long long* h_ctl = nullptr;       // pinned + mapped mirror
+    unsigned long long* d_hctl = nullptr;      // device alias of h_ctl (written by k_publish)
+    unsigned long long cur[NSHARD] = {0};      // host view of the shard cursors after the last completed launch
+    unsigned long long cur_before[NSHARD] = {0}, acc_before[NSHARD] = {0};
+    unsigned long long cursor = 0;             // sum of cur[]; hit_cap is the capacity of ONE shard
+    int fold_extra_digits = 0;                 // basefc hash fold: extra radix digits that earlier finishes needed (giant runs)
+    int fold_path = 0, fold_fallbacks = 0;     // xck_stats: which basefc fold ran last (1 partition, 2 radix sort), hand-overs so far
+    int pileup_sort_path = 0;                  // pileup hits of the last finish: 1 sorted by partition + LDS sort, 2 by the radix sort
+    int pileup_sort2_path = 0;                 // ... and its region-level hits
+    int fold_refinements = 0;                  // partition fold of the last finish: refinements of the level-2 geometry
+    // fused launch queue
+    std::vector<BatchDesc> queue;              // not yet launched (device-resident pushes are deferred)
+    std::vector<BatchDesc> inflight;           // launched, not yet confirmed (kept for overflow replay)
+    int inflight_slot = -1;
+    int inflight_shared = -1;                  // staging slot (Stager) the launch in flight reads, -1 = none
+    int64_t queued_reads = 0, inflight_reads = 0;
+    TileMeta* d_meta = nullptr; size_t meta_cap = 0;
+    // timing
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_res = nullptr, ev_c0 = nullptr, ev_c1 = nullptr;
+    hipEvent_t ev_f1 = nullptr, ev_f2 = nullptr;   // partition fold: level-1 bucket pass on the copy stream (fold_partition.h)
+    bool copy_timed = false, copy_pending = false;
+    xck_stats st{};
+    int64_t n_join_launches = 0;
+    bool fold_failed = false;             // xck_finish returned an error from inside a fold: only xck_reset makes the handle usable again
+    unsigned long long stamp_sum[12] = {0}; int stamp_tiles = 0; float stamp_ms = 0;   // XCK_STAMPS builds: phase cycles of the last join launch
+    // workspace + results
+    Arena ws1, ws2;
+    int32_t* h_res[4] = {nullptr, nullptr, nullptr, nullptr}; size_t h_res_cap[4] = {0, 0, 0, 0}; size_t res_nnz[4] = {0, 0, 0, 0};
+    int32_t* d_res[4] = {nullptr, nullptr, nullptr, nullptr};   // device copies [row | col | val] inside the workspace, valid until the next finish / reset
+    bool finished = false;
+    // read assignment summary (XCK_F_READ_FATE, read_fate.h): device counters (null = off), reads of the batches no kernel saw
+    unsigned long long* d_fate = nullptr;
+    int64_t n_not_joined = 0;
+};
+
+// host helpers defined in engine.hip
+size_t key_bytes(const EngineImpl* im);
+size_t hit_slack(const EngineImpl* im);
+bool split_mode(const EngineImpl* im);
+int arena_begin(EngineImpl* im, Arena& a, size_t need);
+int res_reserve(EngineImpl* im, int m, size_t nnz);
+int complete_pending(EngineImpl* im);
+int launch_queue(EngineImpl* im, int slot_idx, int shared_slot = -1);
+void join_stamps_report(const EngineImpl* im);             // XCK_STAMPS builds: the phase table of the last join launch
+// defined in finish.hip
+int finish_init(EngineImpl* im);                           // engine_create: per-device attributes of the fold kernels
+
+}  // namespace xck

@@ -1,5 +1,6 @@
 // fold_partition.h - basefc fold WITHOUT a sort (64-bit keys): adaptive two-level partition + one LDS pass per bucket.
-// Included by engine.hip inside namespace xck (it uses EngineImpl, Arena, KeyLayout, set_slot, copy_out, res_reserve).
+// Included by finish.hip inside namespace xck, behind its kernels and copy_out(), which it calls; from engine_impl.h it uses EngineImpl,
+// Arena, KeyLayout, NSHARD, CTL_X0, set_slot, HIP_TRY, arena_begin and res_reserve.
 //
 // Replaces, for the count matrix, what the reference does with one Python set per (region, cell):
 //   xcltk/rdr/fc/mcount.py:34-54 (MCount.add_read: set insert, len() at the end), rdr/fc/core.py:166-178.

@@ -1,5 +1,6 @@
 // read_fate.h - opt-in read assignment summary (XCK_F_READ_FATE / XCK_READ_FATE=1; xck_get_read_fate, include/xck.h).
-// Included by engine.hip inside namespace xck, behind launch_join().
+// Included by engine.hip inside namespace xck, behind launch_join(): it uses the join's BatchTable, ReadInfo, TILE, JOIN_BLOCK, op_aligned / op_ref and
+// frac_below, and from engine_impl.h ReadFilter, BatchDesc, as_global, EngineImpl and HIP_TRY.
 //
 // One more pass over the batches the join has just been launched on: every read gets exactly ONE class, the first that applies in
 // the order of the reference's check_read() (rdr/fc/core.py:46-62 == baf/fc/core.py:18-34) followed by the fetch overlap and the

@@ -151,7 +151,7 @@ struct xck_engine {
     // host pinned batch staging used by xck_ingest_bam lives in the xck_bam
 };
 
-// implemented in engine.hip
+// implemented in engine.hip (engine_finish, engine_finish_async, engine_result_device: finish.hip)
 namespace xck {
 int  engine_create(const xck_config* cfg, xck_engine* e);
 void engine_destroy(xck_engine* e);
