@@ -45,6 +45,11 @@
  *                                         for front-ends whose calls do not carry the flags: they then write read_summary.tsv next to their matrices.
  *                                         One small kernel more per join launch; off (the default, or 0) nothing is allocated or launched.  Decode-only
  *                                         handles ignore it.
+ *   XCK_CELL_SUMMARY=1                    every handle that drives a GPU also keeps the per-cell table, as if made with XCK_F_CELL_SUMMARY
+ *                                         (xck_get_cell_summary; implies XCK_READ_FATE=1): the front-ends then write cell_summary.tsv next to
+ *                                         read_summary.tsv.  Off (the default, or 0) nothing is allocated or launched.  Decode-only handles ignore it.
+ *   XCK_CELL_SUMMARY_SLOTS=<rows>         rows of the per-block LDS table of the per-cell accumulation (default and upper bound 512, rounded down to a
+ *                                         power of two; tests: a small table reaches the path of the rows that do not fit with small inputs)
  * Decoder (read when a BAM is opened or once per process): XCK_THREADS, XCK_NUMA=0, XCK_INFLATE=zlib, XCK_CHUNK_BYTES,
  * XCK_WRITE_THREADS (writer threads of xck_write_mtx), XCK_TEST_INTERN_LIMIT (tests). */
 #ifndef XCK_H
@@ -152,6 +157,10 @@ typedef struct xck_config {
 #define XCK_F_READ_FATE     32  /* count, on the device, which of the classes of xck_read_fate every pushed read falls into
                                    (xck_get_read_fate; one more small kernel behind every join launch).  Changes no result.
                                    XCK_E_ARG together with XCK_F_DECODE_ONLY                                              */
+#define XCK_F_CELL_SUMMARY  64  /* per-cell table: the classes of xck_read_fate per cell, and after xck_finish the column marginals of
+                                   the matrices (xck_get_cell_summary).  Implies XCK_F_READ_FATE (the global counters cost nothing
+                                   extra): the per-cell instantiation of that kernel runs in its place.  Changes no result.
+                                   XCK_E_ARG together with XCK_F_DECODE_ONLY                                              */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -255,6 +264,25 @@ typedef struct xck_read_fate {
                                    share of xck_stats.n_hits                                                                  */
 } xck_read_fate;
 
+/* The per-cell table of ONE pipeline, since the last xck_reset (handles made with XCK_F_CELL_SUMMARY; additive, ABI 3 is unchanged).
+ * fate: what xck_read_fate counts, per cell - every read the pipeline's kernels saw adds 1 to its class in its row (its cell, or row
+ * n_cells when cell < 0), an assigned read also its pairs, and 1 to multi when it has two or more.  The column sums equal the fields of
+ * xck_read_fate from low_mapq to pairs.  not_joined stays global-only: those batches reach no kernel, so no row sees their reads.
+ * matrix: column marginals of the result of xck_finish, computed on the device from its result blocks the first time the table is asked
+ * for after the finish.  basefc: umis / pairs of a cell is the share of its accepted pairs that survived the UMI de-duplication.
+ * The arrays are engine-owned host memory, valid until the next xck_get_cell_summary, xck_reset or xck_destroy on the handle. */
+typedef struct xck_cell_summary {
+    uint32_t struct_size;
+    int32_t  mode;              /* XCK_MODE_BASEFC or XCK_MODE_BAF: the pipeline, as xck_read_fate.mode                          */
+    int32_t  n_cells;           /* rows 0..n_cells-1 = the matrix columns; row n_cells = the reads with cell < 0               */
+    int32_t  n_fate_cols;       /* 12: the fields of xck_read_fate from low_mapq to pairs, in that order                        */
+    const int64_t* fate;        /* [(n_cells + 1) * n_fate_cols], row-major                                                     */
+    int32_t  has_matrix;        /* 1 once xck_finish has run since the last xck_reset                                           */
+    int32_t  n_matrix_cols;     /* basefc 2: umis (column sum of count), features (entries of the column);
+                                   BAF 4: ad, dp, oth (column sums), features (entries of the DP column)                        */
+    const int64_t* matrix;      /* [n_cells * n_matrix_cols], row-major; NULL while has_matrix == 0                             */
+} xck_cell_summary;
+
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
 
@@ -303,9 +331,14 @@ int  xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out);
 /* The read assignment summary of one pipeline (set out->struct_size first): mode = XCK_MODE_BASEFC or XCK_MODE_BAF names it - the
  * handle's own mode, or either one on a XCK_MODE_BOTH handle, whose two pipelines keep their own counters (a contig may have
  * regions and no SNPs).  Waits for the handle's queued work as xck_flush does.  XCK_E_STATE on a handle made without
- * XCK_F_READ_FATE, XCK_E_ARG for a pipeline the handle does not have.  With contigs cut over several GPUs (xck_ingest_opts.tid_beg)
+ * XCK_F_READ_FATE (XCK_F_CELL_SUMMARY implies it), XCK_E_ARG for a pipeline the handle does not have.  With contigs cut over several GPUs (xck_ingest_opts.tid_beg)
  * the reads that straddle a cut are seen by both neighbours, and no_target is relative to the regions of the handle that saw the read. */
 int  xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out);
+/* The per-cell table of one pipeline (set out->struct_size first); mode as for xck_get_read_fate.  Waits for the handle's queued work as
+ * xck_flush does; after xck_finish the first call also runs the small kernel of the matrix columns.  XCK_E_STATE on a handle made
+ * without XCK_F_CELL_SUMMARY, XCK_E_ARG for a pipeline the handle does not have or a short struct_size.  The caveat about cut contigs
+ * of xck_get_read_fate holds per cell. */
+int  xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

@@ -26,6 +26,7 @@ int  engine_reset(xck_engine*) { return XCK_E_ARG; }
 int  engine_stats(const xck_engine*, xck_stats*) { return XCK_E_ARG; }
 int  engine_umi_bits(const xck_engine* e) { return e ? e->umi_bits : 0; }
 int  engine_read_fate(xck_engine*, xck_read_fate*) { return XCK_E_ARG; }
+int  engine_cell_summary(xck_engine*, xck_cell_summary*) { return XCK_E_ARG; }
 int  engine_numa_node(const xck_engine*) { return -1; }
 int  engine_device(const xck_engine*) { return -1; }                          // no device: the decoder's GPU share of the inflate never starts
 GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }

@@ -1,5 +1,6 @@
 #!/opt/conda/bin/python3.9
-"""make_read_fate_goldens.py - CONTAINER-ONLY generator of tests/golden/read_fate/*.json (test infrastructure).
+"""make_read_fate_goldens.py - CONTAINER-ONLY generator of tests/golden/read_fate/*.json and tests/golden/cell_summary/*.json
+(test infrastructure).
 
 Expected values of the read assignment summary (xck_get_read_fate, include/xck.h), produced by the unmodified reference's own
 code on the golden datasets.  Like oracle/refgen/run_reference.py - whose stand-in set-up it repeats - it imports the
@@ -12,7 +13,12 @@ Per dataset and mode it calls
   * sam_fetch(sam, chrom, pos, pos) per SNP of load_snp_from_tsv (BAF),
 keys the records by their ordinal in the file, and gives each record the FIRST class that applies, in the order of
 xck_read_fate.  A barcode MCount.push_read would reject, or an empty key, falls under no_cell / no_umi.  Records on references
-outside the front-end's contig table (the regions' chromosomes, plus the SNPs' for BAF) are counted apart (`outside_table`: the
+Per cell (xck_get_cell_summary): the same class of every record, grouped by the record's row - its listed barcode, or the index of
+its BAM where the cells are files; `*` collects the records without a listed barcode.  Records that are `not_joined` or outside
+the table reach no kernel and so no row.  The rows are named in the engine's column order (sorted barcodes / sample ids) and
+only the non-zero ones are kept, as 12 numbers in the order of FIELDS[1:].
+
+Records on references outside the front-end's contig table (the regions' chromosomes, plus the SNPs' for BAF) are counted apart (`outside_table`: the
 decoder may drop them or forward them as skipped batches); records on a table contig without targets are `not_joined`.
 
 usage: make_read_fate_goldens.py [--check]      (--check: compare with the committed files instead of writing them)
@@ -30,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "oracle", "refgen"))
 REF = os.environ.get("XCLTK_REFERENCE", "/root/reference")
 DATASETS = os.path.join(ROOT, "tests", "golden", "datasets")
 OUT = os.path.join(ROOT, "tests", "golden", "read_fate")
+OUT_CELL = os.path.join(ROOT, "tests", "golden", "cell_summary")
 
 FIELDS = ("not_joined", "low_mapq", "excl_flag", "incl_flag", "orphan", "no_cell", "no_umi", "short_aligned", "no_target",
           "include_fail", "assigned", "multi", "pairs")
@@ -107,8 +114,9 @@ def run_case(pybam, stem, dataset, mode, over):
         table |= targets
         check_read = baf_core.check_read
     fate = collections.Counter()
+    rows = collections.defaultdict(collections.Counter)        # per-cell table: row name -> the same counters
     records = outside = 0
-    for b in ds["bams"]:
+    for bam_index, b in enumerate(ds["bams"]):
         sam = pybam.AlignmentFile(os.path.join(ddir, b), "r")
         n_acc, fetched = collections.Counter(), set()          # per record ordinal: accepting regions / covered SNPs; fetched by any region
         if mode == "basefc":
@@ -167,11 +175,27 @@ def run_case(pybam, stem, dataset, mode, over):
                 fate["pairs"] += n_acc[r.ordinal]
                 fate["multi"] += 1 if n_acc[r.ordinal] > 1 else 0
             fate[cls] += 1
+            if cls != "not_joined":
+                if bc is None:
+                    row = ds["sample_ids"][bam_index]
+                else:
+                    row = r.get_tag(p["cell_tag"]) if listed else "*"
+                rows[row][cls] += 1
+                if cls == "assigned":
+                    rows[row]["pairs"] += n_acc[r.ordinal]
+                    rows[row]["multi"] += 1 if n_acc[r.ordinal] > 1 else 0
     out = dict(name=stem, dataset=dataset, mode=mode, records=records, outside_table=outside,
                params={k: p[k] for k in sorted(p)}, fate={k: int(fate[k]) for k in FIELDS},
                reference="hxj5/xcltk check_read / sam_fetch / include test via tools/make_read_fate_goldens.py (pysam/anndata stand-ins)")
     assert sum(out["fate"][k] for k in FIELDS[:-2]) + outside == records
-    return out
+    names = sorted(bc) if bc is not None else list(ds["sample_ids"])
+    assert set(rows) <= set(names) | {"*"}
+    cell = dict(name=stem, dataset=dataset, mode=mode, cells=names, columns=list(FIELDS[1:]),
+                rows={k: [int(v[c]) for c in FIELDS[1:]] for k, v in sorted(rows.items())},
+                reference=out["reference"])
+    for j, c in enumerate(FIELDS[1:]):
+        assert sum(v[j] for v in cell["rows"].values()) == out["fate"][c], c
+    return out, cell
 
 
 def main():
@@ -181,13 +205,29 @@ def main():
     import logging
     logging.disable(logging.CRITICAL)
     os.makedirs(OUT, exist_ok=True)
+    os.makedirs(OUT_CELL, exist_ok=True)
     bad = 0
     for stem, dataset, mode, over in CASES:
-        out = run_case(pybam, stem, dataset, mode, over)
+        out, cell = run_case(pybam, stem, dataset, mode, over)
         text = json.dumps(out, indent=1, sort_keys=True) + "\n"
         fn = os.path.join(OUT, stem + ".json")
         f = out["fate"]
         print("%-24s records %5d outside %d  %s" % (stem, out["records"], out["outside_table"], " ".join("%s=%d" % (k, f[k]) for k in FIELDS)))
+        if check:
+            with open(fn) as fp:
+                if fp.read() != text:
+                    print("  DIFFERS from %s" % fn)
+                    bad += 1
+        else:
+            with open(fn, "w") as fp:
+                fp.write(text)
+        # (one line per row: a thousand short lists read better, and diff better, than twelve thousand lines of digits)
+        body = ",\n".join("  %s: %s" % (json.dumps(k), json.dumps(v)) for k, v in sorted(cell["rows"].items()))
+        head = json.dumps({k: v for k, v in cell.items() if k != "rows"}, indent=1, sort_keys=True)
+        text = head[:-2] + ',\n "rows": {\n' + body + "\n }\n}\n"
+        assert json.loads(text) == cell
+        fn = os.path.join(OUT_CELL, stem + ".json")
+        print("%-24s rows %d (of %d cells)" % ("", len(cell["rows"]), len(cell["cells"])))
         if check:
             with open(fn) as fp:
                 if fp.read() != text:

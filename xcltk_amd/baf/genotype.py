@@ -134,6 +134,7 @@ def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sa
     try:
         try:
             fcc.write_read_summary(eng, dist, os.path.join(out_dir, "read_summary.tsv"), log_prefix="[pileup]")   # (XCK_READ_FATE=1 only)
+            fcc.write_cell_summary(eng, dist, os.path.join(out_dir, "cell_summary.tsv"), conf.samples, log_prefix="[pileup]")   # (XCK_CELL_SUMMARY=1 only)
             if coo is not None:                                   # the matrices are views of the engine's pinned buffers: keep copies past close()
                 coo = {k: tuple(np.array(a) for a in v) for k, v in coo.items()}
         finally:

@@ -60,6 +60,8 @@ Knobs xck::Knobs::from_env() {
     k.gpu_inflate_free_cus = (int)num("XCK_GPU_INFLATE_FREE_CUS", 32);
     k.verify_crc = !strcmp(str("XCK_VERIFY_CRC"), "device") ? 2 : (!*str("XCK_VERIFY_CRC") || !strcmp(str("XCK_VERIFY_CRC"), "0")) ? 0 : 1;   // (any other value: host)
     k.read_fate = num("XCK_READ_FATE", 0) != 0;
+    k.cell_summary = num("XCK_CELL_SUMMARY", 0) != 0;
+    k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
     return k;
 }
 
@@ -75,9 +77,11 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if (cfg->n_cells <= 0 || cfg->n_contigs < 0 || cfg->n_regions < 0 || cfg->n_snps < 0) { set_thread_error("invalid table sizes"); return XCK_E_ARG; }
     if ((cfg->n_regions > 0 && !cfg->regions) || (cfg->n_snps > 0 && !cfg->snps)) { set_thread_error("null table pointer"); return XCK_E_ARG; }
     if ((cfg->flags & XCK_F_READ_FATE) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_READ_FATE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+    if ((cfg->flags & XCK_F_CELL_SUMMARY) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_CELL_SUMMARY needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
-    e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate);
+    e->cell_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_CELL_SUMMARY) || e->knobs.cell_summary);
+    e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate || e->cell_summary);
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
     e->n_cells = cfg->n_cells; e->n_contigs = cfg->n_contigs;
@@ -88,7 +92,8 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             xck_config c = *cfg;
             c.mode = modes[k];
             if (n == 2) c.flags |= XCK_F_LAYOUT_BOTH;          // one key layout -> one decode serves both pipelines
-            if (e->read_fate) c.flags |= XCK_F_READ_FATE;      // (XCK_READ_FATE=1)
+            if (e->read_fate) c.flags |= XCK_F_READ_FATE;      // (XCK_READ_FATE=1, or implied by the per-cell table)
+            if (e->cell_summary) c.flags |= XCK_F_CELL_SUMMARY;  // (XCK_CELL_SUMMARY=1)
             e->impl = nullptr;
             int rc = engine_create(&c, e);
             e->impls[k] = e->impl; e->n_impl = k + 1;
@@ -238,6 +243,19 @@ int xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out) {
     memset(out, 0, sizeof *out); out->struct_size = sz;
     e->impl = e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
     const int rc = engine_read_fate(e, out);
+    e->impl = e->impls[0];
+    return rc;
+}
+
+int xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_cell_summary)) { e->err = "xck_cell_summary.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (!e->cell_summary || e->n_impl <= 0) { e->err = "handle made without XCK_F_CELL_SUMMARY"; return XCK_E_STATE; }
+    if ((mode != XCK_MODE_BASEFC && mode != XCK_MODE_BAF) || !(e->mode & mode)) { e->err = "xck_get_cell_summary: the handle has no such pipeline"; return XCK_E_ARG; }
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    e->impl = e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
+    const int rc = engine_cell_summary(e, out);
     e->impl = e->impls[0];
     return rc;
 }

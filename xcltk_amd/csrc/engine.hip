@@ -1057,6 +1057,7 @@ static int launch_join_t(EngineImpl* im) {
 }
 static int launch_join(EngineImpl* im) { return im->key_bits == 64 ? launch_join_t<uint64_t>(im) : launch_join_t<u128>(im); }
 
+#include "cell_summary.h"
 #include "read_fate.h"
 
 // wait for the launch in flight, collect cursor / timing; if its fragments did not fit, grow, rewind and replay
@@ -1287,6 +1288,8 @@ int engine_reset(xck_engine* e) {
     if (im->copy_pending) { HIP_TRY(hipStreamSynchronize(im->s_copy)); im->copy_pending = false; }
     HIP_TRY(hipMemsetAsync(im->d_ctl, 0, CTL_WORDS * sizeof(unsigned long long), im->s_comp));
     if (im->d_fate) HIP_TRY(hipMemsetAsync(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long), im->s_comp));
+    if (im->d_cell) HIP_TRY(hipMemsetAsync(im->d_cell, 0, ((size_t)im->n_cells + 1) * CS_ROW_WORDS * sizeof(unsigned long long), im->s_comp));
+    im->cmat_valid = false;
     im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false;
@@ -1363,6 +1366,7 @@ int engine_create(const xck_config* cfg, xck_engine* e) {
         HIP_TRY(hipMalloc((void**)&im->d_fate, RF_WORDS * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long)));
     }
+    if (cfg->flags & XCK_F_CELL_SUMMARY) { rc = cell_summary_init(im); if (rc) return rc; }
     return 0;
 }
 
@@ -1372,7 +1376,7 @@ void engine_destroy(xck_engine* e) {
     hipSetDevice(im->device);
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
-                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate,
+                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat,
                      im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }

@@ -185,6 +185,11 @@ struct EngineImpl {
     // read assignment summary (XCK_F_READ_FATE, read_fate.h): device counters (null = off), reads of the batches no kernel saw
     unsigned long long* d_fate = nullptr;
     int64_t n_not_joined = 0;
+    // per-cell table (XCK_F_CELL_SUMMARY, cell_summary.h): [(n_cells + 1) * 16] words in HBM (null = off), the column marginals of the
+    // last finish, and the host copies xck_get_cell_summary hands out
+    unsigned long long* d_cell = nullptr; unsigned long long* d_cmat = nullptr;
+    std::vector<int64_t> h_cell_raw, h_cell, h_cmat;
+    bool cmat_valid = false;
 };
 
 // host helpers defined in engine.hip

@@ -1,6 +1,6 @@
 // read_fate.h - opt-in read assignment summary (XCK_F_READ_FATE / XCK_READ_FATE=1; xck_get_read_fate, include/xck.h).
 // Included by engine.hip inside namespace xck, behind launch_join(): it uses the join's BatchTable, ReadInfo, TILE, JOIN_BLOCK, op_aligned / op_ref and
-// frac_below, and from engine_impl.h ReadFilter, BatchDesc, as_global, EngineImpl and HIP_TRY.
+// frac_below, from engine_impl.h ReadFilter, BatchDesc, as_global, EngineImpl and HIP_TRY, and the grouped accumulation of cell_summary.h.
 //
 // One more pass over the batches the join has just been launched on: every read gets exactly ONE class, the first that applies in
 // the order of the reference's check_read() (rdr/fc/core.py:46-62 == baf/fc/core.py:18-34) followed by the fetch overlap and the
@@ -101,11 +101,15 @@ __device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& 
 
 // Block t covers the TILE reads of join tile t.  Per class a wave ballot + popcount (wave-uniform counts), the sums by a wave
 // reduction; the waves add into a small LDS array and the block sends one 64-bit atomicAdd per non-zero counter to HBM.
-template <int MODE>
-__global__ __launch_bounds__(JOIN_BLOCK) void k_read_fate(FateArgs a) {
+// PER_CELL (XCK_F_CELL_SUMMARY): the same classification also feeds the per-cell table, grouped by the read's row - its cell, or
+// the table's last row when it has none (cell_summary.h); without it nothing of that is in the code.
+template <int MODE, bool PER_CELL>
+__device__ __forceinline__ void read_fate_block(const FateArgs a, const CellArgs ca) {
     __shared__ unsigned long long s_cnt[RF_WORDS];
+    CellLds* const s_cell = cs_lds<PER_CELL>();
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < RF_WORDS) s_cnt[tid] = 0ull;
+    if (PER_CELL) cs_init(*s_cell, ca, tid);
     __syncthreads();
     const int t = blockIdx.x;
     int lo = 0, hi = a.bt.n_batches - 1;
@@ -124,6 +128,12 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_read_fate(FateArgs a) {
 #pragma unroll
         for (int c = 0; c < RF_CLASSES; c++) cnt[c] += (uint32_t)__popcll(__ballot(cls == c));
         pairs += np; multi += np >= 2u ? 1u : 0u;
+        if (PER_CELL) {
+            // (a cell index outside the table - a device-resident batch is the caller's word - counts in the last row, never beyond it)
+            int32_t row = ca.n_rows - 1;
+            if (cls >= 0) { const int32_t cell = as_global(d.cell)[i]; if ((uint32_t)cell < (uint32_t)(ca.n_rows - 1)) row = cell; }
+            cs_add(*s_cell, ca, lane, cls >= 0, row, cls, np, np >= 2u, RF_MULTI);   // (np != 0 only for RF_ASSIGNED)
+        }
     }
 #pragma unroll
     for (int dd = 32; dd >= 1; dd >>= 1) { pairs += __shfl_xor(pairs, dd, 64); multi += __shfl_xor(multi, dd, 64); }
@@ -135,7 +145,14 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_read_fate(FateArgs a) {
     }
     __syncthreads();
     if (tid < RF_USED) { const unsigned long long v = s_cnt[tid]; if (v) atomicAdd(&a.out[tid], v); }
+    if (PER_CELL) cs_flush(*s_cell, ca, tid);
 }
+template <int MODE>
+__global__ __launch_bounds__(JOIN_BLOCK) void k_read_fate(FateArgs a) { read_fate_block<MODE, false>(a, CellArgs{}); }
+template <int MODE>
+__global__ __launch_bounds__(JOIN_BLOCK) void k_read_fate_cell(FateArgs a, CellArgs ca) { read_fate_block<MODE, true>(a, ca); }
+static_assert(sizeof(FateArgs) + sizeof(CellArgs) <= 4000, "kernel arguments must stay under the 4 KiB kernarg limit");
+static_assert(RF_WORDS == CS_ROW_WORDS && RF_USED == CS_COLS && RF_MULTI < CS_C32 && RF_PAIRS == CS_C32, "the per-cell table keeps the columns of the global words");
 
 // Runs once per batch: called by launch_queue() behind the FIRST join launch of the batches in im->inflight (whose tile0 that
 // launch has set), on the same stream - so it is over before complete_pending() hands their staging slot back - and never by the
@@ -150,7 +167,12 @@ static int launch_read_fate(EngineImpl* im) {
     a.f = im->rf;
     a.reg_s0 = im->d_reg_s0; a.reg_e0 = im->d_reg_e0; a.reg_pmax = im->d_reg_pmax; a.snp_p0 = im->d_snp_p0;
     a.out = im->d_fate;
-    if (im->mode == XCK_MODE_BASEFC) hipLaunchKernelGGL((k_read_fate<XCK_MODE_BASEFC>), dim3(tiles), dim3(JOIN_BLOCK), 0, im->s_comp, a);
+    if (im->d_cell) {                                          // (XCK_F_CELL_SUMMARY: the instantiation that also fills the per-cell table)
+        CellArgs ca;
+        ca.tab = im->d_cell; ca.n_rows = im->n_cells + 1; ca.slot_mask = cs_slot_mask(im); ca.stride = CS_ROW_WORDS; ca.c32_base = 0; ca.wide_col = RF_PAIRS;
+        if (im->mode == XCK_MODE_BASEFC) hipLaunchKernelGGL((k_read_fate_cell<XCK_MODE_BASEFC>), dim3(tiles), dim3(JOIN_BLOCK), 0, im->s_comp, a, ca);
+        else hipLaunchKernelGGL((k_read_fate_cell<XCK_MODE_BAF>), dim3(tiles), dim3(JOIN_BLOCK), 0, im->s_comp, a, ca);
+    } else if (im->mode == XCK_MODE_BASEFC) hipLaunchKernelGGL((k_read_fate<XCK_MODE_BASEFC>), dim3(tiles), dim3(JOIN_BLOCK), 0, im->s_comp, a);
     else hipLaunchKernelGGL((k_read_fate<XCK_MODE_BAF>), dim3(tiles), dim3(JOIN_BLOCK), 0, im->s_comp, a);
     HIP_TRY(hipGetLastError());
     return 0;

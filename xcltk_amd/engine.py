@@ -401,6 +401,26 @@ class Engine(object):
         self._check(rc, "xck_get_read_fate")
         return {k: int(getattr(rf, k)) for k in capi.READ_FATE_FIELDS}
 
+    def cell_summary(self, mode=None):
+        """The per-cell table of one pipeline since the last reset (xck_get_cell_summary): dict of `fate`, int64 [(n_cells + 1), 12]
+        (row n_cells: the reads without a listed cell), `matrix`, int64 [n_cells, k] (None before finish()), and the column names
+        `fate_cols`, `matrix_cols` - copies, not views; or None on a handle made without XCK_F_CELL_SUMMARY (and without
+        XCK_CELL_SUMMARY=1 in the environment).  mode as for read_fate().  Waits for queued work."""
+        if mode is None:
+            if self.mode == capi.XCK_MODE_BOTH:
+                raise ValueError("cell_summary(): a XCK_MODE_BOTH handle has two pipelines, name one")
+            mode = self.mode
+        cs = capi.CellSummary()
+        cs.struct_size = C.sizeof(capi.CellSummary)
+        rc = self.lib.xck_get_cell_summary(self.h, int(mode), C.byref(cs))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_cell_summary")
+        n, k, km = int(cs.n_cells), int(cs.n_fate_cols), int(cs.n_matrix_cols)
+        fate = np.ctypeslib.as_array(cs.fate, shape=((n + 1) * k,)).reshape(n + 1, k).copy()
+        matrix = np.ctypeslib.as_array(cs.matrix, shape=(n * km,)).reshape(n, km).copy() if cs.has_matrix and cs.matrix else None
+        return dict(fate=fate, matrix=matrix, fate_cols=capi.CELL_FATE_COLS, matrix_cols=capi.CELL_MATRIX_COLS[int(cs.mode)])
+
 
 class BamStream(object):
     """One open BAM being streamed through an Engine in slices (xck_ingest_opts.pause_records)."""

@@ -351,6 +351,54 @@ def write_read_summary(eng, dist, path, mode=None, log_prefix="[engine]"):
     return fate
 
 
+def cell_summary_text(names, fate, matrix, fate_cols, matrix_cols, n_ranks=1, cut_contigs=0):
+    """Text of cell_summary.tsv: header `cell reads <fate columns> <matrix columns>`, one line per matrix column in column order
+    named by `names`, and a last line `*` for the reads without a listed cell (0 in the matrix columns).  `reads` is the sum of the
+    class columns (everything but multi and pairs).  Runs of several ranks start with `#ranks=N cut_contigs=K`."""
+    fate = np.asarray(fate, dtype=np.int64)
+    n = len(names)
+    assert fate.shape == (n + 1, len(fate_cols))
+    matrix = np.zeros((n, len(matrix_cols)), dtype=np.int64) if matrix is None else np.asarray(matrix, dtype=np.int64)
+    assert matrix.shape == (n, len(matrix_cols))
+    n_cls = len(fate_cols) - 2
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    lines = [head, "\t".join(("cell", "reads") + tuple(fate_cols) + tuple(matrix_cols)) + "\n"]
+    for i in range(n + 1):
+        m = matrix[i] if i < n else np.zeros(len(matrix_cols), dtype=np.int64)
+        vals = [int(fate[i, :n_cls].sum())] + [int(x) for x in fate[i]] + [int(x) for x in m]
+        lines.append((names[i] if i < n else "*") + "\t" + "\t".join("%d" % v for v in vals) + "\n")
+    return "".join(lines)
+
+
+def write_cell_summary(eng, dist, path, names, mode=None, log_prefix="[engine]"):
+    """Per-cell table of one pipeline (Engine.cell_summary, after finish()) -> `path`, when the handle keeps it (XCK_CELL_SUMMARY=1 in
+    the environment, or XCK_F_CELL_SUMMARY): nothing happens otherwise.  `names`: the matrix columns in order (barcodes or sample
+    ids).  Multi-GPU: a collective call - the two arrays are summed over the ranks in one all-reduce and the writer rank writes
+    the file; the caveat of write_read_summary about cut contigs holds per cell.  Returns the (summed) dict or None."""
+    cell_summary = getattr(eng, "cell_summary", None)          # (an engine-like object without the method keeps nothing)
+    cs = cell_summary(mode) if cell_summary else None
+    if cs is None:
+        return None
+    fate = np.asarray(cs["fate"], dtype=np.int64)
+    matrix = cs["matrix"]
+    if matrix is None:
+        matrix = np.zeros((fate.shape[0] - 1, len(cs["matrix_cols"])), dtype=np.int64)
+    n_ranks, cut = 1, 0
+    if dist is not None and dist.active:
+        v = dist.all_reduce_np(np.concatenate([fate.ravel(), np.asarray(matrix, dtype=np.int64).ravel()]))
+        fate, matrix = v[:fate.size].reshape(fate.shape), v[fate.size:].reshape(matrix.shape)
+        n_ranks = dist.world
+        cut = len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
+    cs = dict(cs, fate=fate, matrix=matrix)
+    info("%s cell summary: %d cells with reads, %d reads without a listed cell" %
+         (log_prefix, int((fate[:-1].sum(axis=1) > 0).sum()), int(fate[-1, :len(cs["fate_cols"]) - 2].sum())))
+    if is_writer_rank():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fp:
+            fp.write(cell_summary_text(list(names), fate, matrix, cs["fate_cols"], cs["matrix_cols"], n_ranks, cut))
+    return cs
+
+
 # ----------------------------------------------------------------------------- engine driver
 def make_engine(conf, mode, regions, snps=(), device=None, **extra):
     """Build the per-GPU engine from a resolved Config."""

@@ -58,6 +58,9 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
         # (XCK_READ_FATE=1 only; the two pipelines keep their own counters: a contig may have regions and no SNPs)
         fcc.write_read_summary(eng, dist, os.path.join(fc_dir, "read_summary.tsv"), XCK_MODE_BASEFC, "[fused basefc]")
         fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"), XCK_MODE_BAF, "[fused baf]")
+        # (XCK_CELL_SUMMARY=1 only; one table per pipeline, next to its matrices)
+        fcc.write_cell_summary(eng, dist, os.path.join(fc_dir, "cell_summary.tsv"), conf.samples, XCK_MODE_BASEFC, "[fused basefc]")
+        fcc.write_cell_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "cell_summary.tsv"), conf.samples, XCK_MODE_BAF, "[fused baf]")
         if coo is None:
             return 0
         n = len(regions)                                  # (sharded output: every rank is here and the calls below are collective)
