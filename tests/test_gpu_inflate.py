@@ -206,8 +206,10 @@ def test_device_decoder_on_crafted_streams(tmp_path):
     fn = os.path.join(str(tmp_path), "crafted.bgzf")
     open(fn, "wb").write(b"".join(blocks))
     for variant in ("0", "10"):                                       # (10: the same kernel with its phase clocks compiled in)
-        r = subprocess.run([exe, fn], env=dict(os.environ, INFLATE_VARIANT=variant), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
+        r = subprocess.run([exe, fn], env=dict(os.environ, INFLATE_VARIANT=variant, INFLATE_STATUSES="1"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, timeout=120)
         line = [l for l in r.stdout.splitlines() if l.startswith("verified against zlib")]
         assert r.returncode == 0 and line, r.stdout[-2000:]
         wrong, left = int(line[0].split(":")[1].split()[0]), int(line[0].split("wrong,")[1].split()[0])
-        assert "%d blocks" % len(blocks) in r.stdout and wrong == 0 and left <= 4, (variant, line[0])
+        st = [int(x) for l in r.stdout.splitlines() if l.startswith("statuses:") for x in l.split()[1:]]
+        which = {k: s for k, s in enumerate(st) if s != 0}                # (block index in the order of the add() calls above -> status)
+        assert len(st) == len(blocks) and "%d blocks" % len(blocks) in r.stdout and wrong == 0 and left == 0 and not which, (variant, line[0], which)

@@ -2,6 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ixcltk_amd/csrc tools/gpu_inflate_bench.hip xcltk_amd/csrc/inflate_dev.hip -lz -o tools/scratch/gpu_inflate_bench
 //   [INFLATE_VARIANT=0|1] [INFLATE_CRC=1] tools/scratch/gpu_inflate_bench FILE.bam [max_bytes [blocks_per_launch]]     (variant: see dev_inflate_launch)
 // INFLATE_CRC=1: every block's footer CRC goes to DevBlock.crc and the kernel checks it (check_crc); one more line says what it found.
+// INFLATE_STATUSES=1: one more line "statuses: s0 s1 ..." with every block's status in file order (tests/test_gpu_inflate_streams.py, tests/test_gpu_inflate.py).
 #include <zlib.h>
 #include <chrono>
 #include <cstdio>
@@ -66,6 +67,9 @@ int main(int argc, char** argv) {
     printf("verified against zlib: %zu blocks wrong, %zu left to the host (status histogram:", bad, left);
     for (int i = 0; i < 64; i++) if (hist[i]) printf(" %d:%d", i, hist[i]);
     printf(")\n");
+    if (getenv("INFLATE_STATUSES") && atoi(getenv("INFLATE_STATUSES")) != 0) {
+        printf("statuses:"); for (size_t b = 0; b < bl.size(); b++) printf(" %d", st[b]); printf("\n");
+    }
     if (check_crc) {
         printf("crc on the device: %zu verified, %zu mismatched, %zu left, %zu disagree with zlib (first mismatched blocks:", c_ok, c_bad, c_left, c_disagree);
         for (size_t b : c_first) printf(" %zu", b);

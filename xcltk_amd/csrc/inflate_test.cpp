@@ -1,6 +1,8 @@
 // inflate_test.cpp - checks inflate_fast.h against zlib: (1) every BGZF block of the BAM files given on the
 // command line, (2) synthetic buffers deflated with all levels / strategies (stored, fixed, dynamic blocks).
 // Prints throughput of both decoders. Exit code 0 = every block identical.
+// INFLATE_STATUSES=1: one more line "statuses: rc0 rc1 ..." with inflate_raw's verdict on every BGZF block of the files, in file
+// order (an empty block, which is never handed to the decoder, counts as 0).
 #include <zlib.h>
 #include <chrono>
 #include <cstdio>
@@ -17,6 +19,7 @@ static bool zinflate(const uint8_t* in, size_t n, uint8_t* out, size_t on) { z_s
 int main(int argc, char** argv) {
     static InflateTables tabs; long bad = 0, blocks = 0, fallback = 0; double tz = 0, tf = 0; size_t bytes = 0;
     std::vector<uint8_t> a(1 << 17), b(1 << 17);
+    const bool want_rc = getenv("INFLATE_STATUSES") && atoi(getenv("INFLATE_STATUSES")) != 0; std::vector<int> rcs;
     for (int f = 1; f < argc; f++) {
         FILE* fp = fopen(argv[f], "rb"); if (!fp) { perror(argv[f]); return 2; }
         std::vector<uint8_t> d; { fseek(fp, 0, SEEK_END); long n = ftell(fp); fseek(fp, 0, SEEK_SET); d.resize(n); if (fread(d.data(), 1, n, fp) != (size_t)n) return 2; fclose(fp); }
@@ -28,7 +31,9 @@ int main(int argc, char** argv) {
             const uint8_t* cd = p + 12 + xlen; size_t cl = bsize - 12 - xlen - 8; uint32_t isz; memcpy(&isz, p + bsize - 4, 4);
             if (isz) { double t0 = now(); bool okz = zinflate(cd, cl, a.data(), isz); double t1 = now(); int rc = inflate_raw(cd, cl, b.data(), isz, &tabs); double t2 = now();
                 tz += t1 - t0; tf += t2 - t1; bytes += isz; blocks++;
+                rcs.push_back(rc);
                 if (rc != 0) fallback++; else if (!okz || memcmp(a.data(), b.data(), isz) != 0) { bad++; fprintf(stderr, "MISMATCH %s block at %zu\n", argv[f], off); } }
+            else rcs.push_back(0);
             off += bsize;
         }
     }
@@ -57,6 +62,7 @@ int main(int argc, char** argv) {
 #ifdef XCK_INFLATE_PROF
     printf("prof: dynamic blocks %llu, build cycles %llu (%.1f%% of fast time at 2.1GHz)\n", g_prof_nblocks, g_prof_build, 100.0 * g_prof_build / 2.1e9 / (tf > 0 ? tf : 1));
 #endif
+    if (want_rc) { printf("statuses:"); for (int rc : rcs) printf(" %d", rc); printf("\n"); }
     printf("blocks %ld mismatches %ld fast-decoder-declined %ld | BAM bytes %.1f MB: zlib %.0f MB/s, fast %.0f MB/s\n", blocks, bad, fallback,
            bytes / 1e6, tz > 0 ? bytes / 1e6 / tz : 0, tf > 0 ? bytes / 1e6 / tf : 0);
     return bad ? 1 : 0;
