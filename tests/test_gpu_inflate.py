@@ -91,7 +91,7 @@ def _engine(regions, snps, names, bcs):
 
 @pytest.mark.parametrize("share", ["0", "100"])
 def test_sliced_ingest_equals_one_call(share, knob_env, tmp_path):
-    """xck_ingest_opts.pause_records: the parse and the push of a chunk run behind the decoder's coordinator (csrc/bam.cpp: IngestJob,
+    """xck_ingest_opts.pause_records: the parse and the push of a chunk run behind the decoder's coordinator (csrc/bam.cpp: ChunkJob,
     Pusher); a call that returns at a chunk boundary has drained them, so slices of any size give the matrices of one call."""
     bam, regions, snps, names, bcs = _make_bam(str(tmp_path), 600000, 6)
     knob_env["XCK_CHUNK_BYTES"] = str(3 << 20)

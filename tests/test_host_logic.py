@@ -631,6 +631,40 @@ def test_decoder_survives_corrupt_bams_under_sanitizers(tmp_path):
             assert int(m.group(3)) > len(files)                      # most damage is detected and reported as an error
 
 
+# (BAM below tests/golden/datasets, XCK_CHUNK_BYTES, chunks, of them stitched serially): counted on the decoder as it was before the
+# stitch and the speculative walk were given one layout / parse path; the split must not move
+_SMALL_CHUNK_LEGS = [("dense/possorted.bam", 4096, 23, 21), ("special/possorted.bam", 1024, 5, 4),
+                     ("c1/possorted.bam", 70000, 19, 0), ("multibam/possorted_0.bam", 20000, 10, 0)]
+
+
+def test_both_kinds_of_chunk_under_asan_and_tsan():
+    """tools/asan on the unmodified golden BAMs at chunk sizes that make many chunks of both kinds - stitched serially (a record
+    straddles the chunk boundary) and taken from the walk tasks as they are - with 4 pool threads: the pull decode and the
+    sliced ingest (parse and push of a chunk behind the coordinator, the stand-in for engine_push_block reads the SoA block on
+    the push thread while the coordinator lays out the next) must agree, with all contigs and with one contig wanted (whole
+    chunks without a kept record), under ASAN + UBSan and under ThreadSanitizer."""
+    asan = os.path.join(ROOT, "tools", "asan")
+    r = subprocess.run(["make", "-C", asan, "decoder_asan", "decoder_tsan"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0 and any(("cannot find -l" + n) in r.stdout or ("lib" + n) in r.stdout for n in ("asan", "ubsan", "tsan")):
+        pytest.skip("no sanitizer runtime for g++ here")
+    assert r.returncode == 0, r.stdout[-2000:]
+    gold = os.path.join(ROOT, "tests", "golden", "datasets")
+    for exe in ("decoder_asan", "decoder_tsan"):
+        for bam, chunk_bytes, chunks, stitched in _SMALL_CHUNK_LEGS:
+            env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0", XCK_CHUNK_BYTES=str(chunk_bytes), XCK_ASAN_THREADS="4", XCK_DEBUG_TIMING="1")
+            r = subprocess.run([os.path.join(asan, exe), os.path.join(gold, bam)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                               env=env, timeout=600)
+            what = "%s %s XCK_CHUNK_BYTES=%d" % (exe, bam, chunk_bytes)
+            assert r.returncode == 0, what + "\n" + (r.stdout + r.stderr)[-3000:]
+            assert "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, what + "\n" + r.stderr[-3000:]
+            assert "1 files: 4 clean decodes, 0 rejected" in r.stdout, what + "\n" + r.stdout
+            seen = [(int(a), int(b)) for a, b in re.findall(r"(\d+) chunks \((\d+) stitched serially\)", r.stderr)]
+            # 2 modes x 2 thread counts x 2 contig maps x (pull decode, sliced ingest): every reader reports when it is closed
+            assert len(seen) == 16 and set(seen) == {(chunks, stitched)}, (what, seen)
+            if bam.startswith("dense"):
+                assert 0 < stitched < chunks                           # both kinds of chunk occur in one file
+
+
 # ---------------------------------------------------------------- native SNP text parser (csrc/snptext.cpp) == the generic loaders
 _TSV_LINES = [
     "chrom\tpos\tref\talt\tref_hap\talt_hap",

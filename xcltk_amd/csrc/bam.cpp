@@ -212,7 +212,6 @@ class Pool {
 public:
     explicit Pool(int n) { for (int i = 0; i < n; i++) th_.emplace_back([this] { run(); }); }
     ~Pool() { { std::lock_guard<std::mutex> lk(mu_); stop_ = true; } cv_.notify_all(); for (auto& t : th_) t.join(); }
-    void submit(std::function<void()> f, bool front = false) { { std::lock_guard<std::mutex> lk(mu_); if (front) q_.push_front(std::move(f)); else q_.push_back(std::move(f)); } cv_.notify_one(); }
     // many tasks under ONE lock and one wake-up: a chunk hands ~100 part tasks to the pool three times (inflate / gather, walk, parse), and a
     // lock + futex wake per task cost the coordinator ~0.7 ms per chunk
     void submit_many(std::vector<std::function<void()>>& fs, bool front = false) {
@@ -241,18 +240,12 @@ struct TaskGroup {
     std::atomic<int> thrown{0};          // a task body threw: 1 = std::bad_alloc, 2 = anything else (checked by the waiter: an exception
                                          // that leaves a pool thread would otherwise end the process through std::terminate)
     int take_thrown() { return thrown.exchange(0); }
-    void add(Pool& p, std::function<void()> f, bool front = false) {     // front: ahead of what is queued (work the coordinator is waiting for)
-        { std::lock_guard<std::mutex> lk(mu); pending++; }
-        // The notify happens UNDER the lock: a TaskGroup on the waiter's stack may be destroyed as soon as wait() returns, and
-        // wait() cannot return before this task has released the mutex - after which it touches the group no more.  (Notifying
-        // after the unlock let a waiter that saw pending == 0 leave first; the late pthread_cond_broadcast then wrote into
-        // whatever the coordinator's stack held by then: "free(): invalid pointer", once per ~14 k chunks with more pool threads
-        // than CPUs, tools/stress_e2e.py.)
-        p.submit([this, f] {
-            try { f(); } catch (const std::bad_alloc&) { thrown.store(1); } catch (...) { thrown.store(2); }
-            std::lock_guard<std::mutex> lk(mu); if (--pending == 0) cv.notify_all(); }, front);
-    }
-    // collect tasks with later(), hand them to the pool in one go with flush()
+    // collect tasks with later(), hand them to the pool in one go with flush() (front: ahead of what is queued - work the coordinator
+    // is waiting for).  The notify of a finished task happens UNDER the lock: a waiter may reuse or destroy the group as soon as wait()
+    // returns, and wait() cannot return before the task has released the mutex - after which it touches the group no more.
+    // (Notifying after the unlock let a waiter that saw pending == 0 leave first; the late pthread_cond_broadcast then wrote into
+    // whatever the coordinator's stack held by then: "free(): invalid pointer", once per ~14 k chunks with more pool threads than
+    // CPUs, tools/stress_e2e.py.)
     std::vector<std::function<void()>> batch;
     void later(std::function<void()> f) {
         batch.push_back([this, f] {
@@ -331,9 +324,9 @@ using namespace xck;
 // the BAM file object
 // ---------------------------------------------------------------------------------------------
 // One decoded chunk as structure-of-arrays, all columns carved out of ONE pinned block: the whole chunk crosses PCIe in a
-// single hipMemcpyAsync (engine_push_block) and the batches of the chunk are slices of it.  Three blocks rotate, so the
-// decoder fills block i + 1 while block i is still being copied; `fence` (an event owned by this block, recorded by the
-// engine behind the copy) is waited for before the block is overwritten.
+// single hipMemcpyAsync (engine_push_block) and the batches of the chunk are slices of it.  Every ChunkJob (below) has one,
+// so the decoder fills the next job's block while this one is still being copied; `fence` (an event owned by this block,
+// recorded by the engine behind the copy) is waited for before the block is overwritten.
 struct HostSoA {
     uint8_t* base = nullptr; size_t cap = 0, used = 0; bool pinned = false; void* fence = nullptr;
     int32_t* pos = nullptr; uint16_t* flag = nullptr; uint8_t* mapq = nullptr; int32_t* cell = nullptr; uint64_t* umi = nullptr;
@@ -346,13 +339,14 @@ struct RecRef { const uint8_t* p; uint32_t len; int32_t tid; uint32_t l_seq; uin
 // still hot in that core's cache) under the SPECULATION that a record starts at the first byte of
 // the range - true for BGZF writers that flush a block before a record that would not fit (htslib,
 // samtools, this repo's writers).  The task also sums up what its records need in the SoA (kept records, CIGAR words,
-// sequence bytes) and notes where the contig changes, so that when every speculation of a chunk holds the output layout
-// is a prefix sum over the parts and each part is parsed by its own task; otherwise the stitch re-walks serially.
+// sequence bytes) and notes where the contig changes: the output layout is a prefix sum over the parts and each part is
+// parsed by its own task.  When a speculation of the chunk failed the stitch re-walks serially and cuts its record list
+// into pieces of the same shape (Chunk::stitched), so layout and parse know one kind of input.
 struct ContigRun { uint32_t first; int32_t contig; };                    // records [first, next run's first) of the part are on `contig` (-1: unused)
 struct WalkPart {
     size_t u_begin = 0, u_end = 0, spec_start = 0, stop = 0; std::vector<RecRef> recs;
     size_t n_out = 0, n_cig = 0, n_seq = 0; std::vector<ContigRun> runs;
-    size_t out_base = 0, cig_base = 0, seq_base = 0;                      // filled by the coordinator (fast path)
+    size_t out_base = 0, cig_base = 0, seq_base = 0;                      // filled by the coordinator (layout_chunk)
     size_t i0 = 0, i1 = 0;                                                // the part's blocks: [i0, i1) of the chunk
 };
 
@@ -361,6 +355,10 @@ struct Chunk {
     std::vector<uint8_t> ubuf; size_t usize = 0;
     uint8_t* ubase = nullptr;          // where the chunk's inflated bytes live: ubuf, or the pinned output block of its GPU slot
     std::vector<WalkPart> parts;
+    // a chunk that was stitched serially: its records in pieces of a parse task's size (only recs, runs and the n_* / *_base fields are
+    // used), and the record that straddles the boundary to the previous chunk, assembled from the reader's carry.  Both are read by the
+    // chunk's parse tasks, which may run behind the coordinator: they live here, with the inflated bytes, until the chunk is released.
+    std::vector<WalkPart> stitched; std::vector<uint8_t> stitch;
     TaskGroup tg; std::atomic<bool> failed{false}; std::string err; std::mutex emu;
     bool valid = false, new_range = false; uint32_t first_skip = 0; int range_id = 0;
     // GPU share of the inflate (csrc/inflate_dev.hip): the pool only gathers the compressed bytes into the slot's pinned block, the task
@@ -460,27 +458,37 @@ private:
 #define XCK_PUSH_Q 2
 #endif
 constexpr int PUSH_Q = XCK_PUSH_Q;      // chunks the coordinator may run ahead of the push thread (Pusher)
-constexpr int N_CHUNK = 3 + PUSH_Q, N_SOA = PUSH_Q + 1;
-// What follows a chunk's layout - wait for its parse tasks, then push it (engine_push_block: one H2D copy + the join launches, after
-// waiting for the previous chunk's launch to be confirmed) - runs on a thread of its own, in file order, up to two chunks behind the
-// coordinator, which meanwhile schedules, waits for and lays out the next chunks.  With the GPU share of the inflate the coordinator
-// had become the limiter of the ingest (schedule + wait for parse + push = 4.5 ms per chunk, the pool a third idle).
-// A job owns: the chunk's SoA block, its ring chunk (inflated bytes + record lists, until `parsed`), its batch list.
-struct IngestJob {
-    TaskGroup tg; std::atomic<int> flags{0}; bool has_parse = false; int soa = -1, ring_idx = -1; std::deque<PendingBatch> pending;
+constexpr int N_CHUNK = 3 + PUSH_Q, N_JOB = PUSH_Q + 1;
+// One decoded chunk in flight, from its layout to the end of its push: the SoA block, the batch list (slices of the block), the parse
+// tasks and their flags, the ring chunk the parse still reads (inflated bytes + record lists, until `parsed`) and the engine the chunk
+// goes to.  The k-th chunk a reader decodes takes jobs[k % N_JOB], whoever consumes it.  xck_bam_next_batch and a decode-only
+// xck_ingest_bam wait for the parse themselves.  On a GPU-backed handle EVERY chunk's job - one without batches too - goes to the push
+// thread (Pusher), which waits for the parse tasks and pushes the block (engine_push_block: one H2D copy + the join launches) in file
+// order while the coordinator schedules, waits for and lays out the next chunks (with the GPU share of the inflate the coordinator had
+// become the limiter: schedule + wait for parse + push = 4.5 ms per chunk, the pool a third idle).  At most Pusher::MAXQ = N_JOB - 1
+// jobs are with the push thread, so the slot of chunk k is free again when chunk k + N_JOB is laid out (take_job checks it).
+struct ChunkJob {
+    HostSoA soa; std::deque<PendingBatch> batches;
+    TaskGroup tg; std::atomic<int> flags{0};   // the parse tasks; what they found (parse_error)
+    xck_engine* e = nullptr;           // the handle of the call that decoded the chunk: where the push thread pushes it
+    int ring_idx = -1;                 // the ring chunk the parse tasks read, while the job holds it
     std::atomic<int> parsed{0};        // set by the push thread once the parse tasks have ended: the coordinator may take the ring chunk back
-    bool released = true;              // (coordinator) the ring chunk was taken back
+    bool released = true;              // (coordinator) the ring chunk was taken back, or was never held
+    std::atomic<int> queued{0};        // with the push thread: set by Pusher::submit, cleared when the job's push has ended
 };
 struct Pusher {
     static constexpr int MAXQ = PUSH_Q; // jobs the coordinator may run ahead
     std::thread th; std::mutex mu; std::condition_variable cv;
-    bool stop = false; IngestJob* q[MAXQ] = {}; int qh = 0, qn = 0;
+    bool stop = false; ChunkJob* q[MAXQ] = {}; int qh = 0, qn = 0;
     int rc = 0; std::string err;       // first failure (parse flags or push); later jobs are waited for, not pushed
-    xck_engine* e = nullptr; xck_bam* b = nullptr;
     uint64_t push_ns = 0, parse_wait_ns = 0;
-    void run();                        // (below: needs xck_bam)
+    void run();
+    Pusher() { th = std::thread([this] { run(); }); }
     // blocks while MAXQ jobs are outstanding; returns the first failure so far (the job is queued regardless: its parse must be waited for)
-    int submit(IngestJob* j) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return qn < MAXQ; }); q[(qh + qn) % MAXQ] = j; qn++; cv.notify_all(); return rc; }
+    int submit(ChunkJob* j) {
+        std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return qn < MAXQ; });
+        j->queued.store(1); q[(qh + qn) % MAXQ] = j; qn++; cv.notify_all(); return rc;
+    }
     int wait_idle() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return qn == 0; }); return rc; }
     ~Pusher() { { std::lock_guard<std::mutex> lk(mu); stop = true; cv.notify_all(); } if (th.joinable()) th.join(); }
 };
@@ -503,7 +511,6 @@ struct xck_bam {
     std::vector<uint64_t> idx_beg, idx_end; std::vector<int64_t> idx_mapped, idx_unmapped; std::vector<std::vector<uint64_t>> idx_lin;
     std::vector<std::pair<uint64_t, uint64_t>> ranges; bool use_ranges = false, ranges_set = false;
     uint32_t first_skip = 0;           // bytes of the first block that precede the first record
-    uint32_t stitch_skip = 0;          // same for the chunk being stitched
     Scanner* scanner = nullptr; bool scan_end = false;
     std::vector<int32_t> range_tid;                       // per_tid_ranges: reference of every range
     bool per_tid_ranges = false; int skip_range = -1;   // position windows: one range per reference; a range is dropped once a record starts beyond its window
@@ -512,16 +519,11 @@ struct xck_bam {
     GpuShare gi;
     bool started = false;              // a decode call has been made (xck_bam_prefetch alone does not count)
     bool prefetching = false;          // inside xck_bam_prefetch
-    Pusher* pusher = nullptr;          // made at the first push of a GPU-backed ingest
-    // xck_ingest_bam on a GPU-backed handle (defer_parse): the parse of a chunk (pool tasks: record fields -> SoA block) and its push run
-    // behind the coordinator (Pusher).  jobs[k % (PUSH_Q + 1)] belongs to the k-th chunk handed over; at most Pusher::MAXQ are outstanding.
-    IngestJob jobs[PUSH_Q + 1]; uint64_t job_n = 0;
-    bool defer_parse = false;          // set by xck_ingest_bam for GPU-backed handles
+    Pusher* pusher = nullptr;          // made at the first chunk of a GPU-backed ingest
+    ChunkJob jobs[N_JOB]; uint64_t n_jobs = 0;   // jobs[k % N_JOB] belongs to the k-th chunk decoded (take_job)
+    ChunkJob* cur = nullptr;           // the job of the chunk decoded last: xck_bam_next_batch hands its batches out
+    bool defer_parse = false;          // set by xck_ingest_bam for GPU-backed handles: parse and push run behind the coordinator
     std::vector<uint8_t> carry;        // partial record from the previous chunk
-    std::vector<uint8_t> stitch;       // boundary record assembled from carry + head of this chunk
-    std::vector<RecRef> recs; std::vector<int32_t> rec_contig; std::vector<int64_t> rec_out;   // serial walk output (slow path)
-    HostSoA soa[N_SOA]; int soa_i = 0;                 // soa[soa_i] holds the chunk decoded last
-    std::deque<PendingBatch> pending;
     int64_t n_records = 0;             // records walked so far (all, including unused contigs)
     bool done = false;
     size_t chunk_target = 48u << 20;   // uncompressed bytes per chunk
@@ -582,7 +584,7 @@ struct SeqReader {
 // pinned SoA arrays (hipHostMalloc pins page by page), the two inflate buffers, the record index, the thread pool - cost
 // ~30 ms to set up, twice the decode time of a 500 k-read file: closed readers park them here for the next open.
 struct BamScratch {
-    HostSoA soa[N_SOA]; std::vector<uint8_t> ubuf[N_CHUNK]; std::vector<RecRef> recs; std::vector<int32_t> rec_contig; std::vector<int64_t> rec_out;
+    HostSoA soa[N_JOB]; std::vector<uint8_t> ubuf[N_CHUNK];
     Pool* pool = nullptr; int n_threads = 0;
 };
 static std::mutex g_scratch_mu;
@@ -654,9 +656,8 @@ static int bam_open_impl(const char* path, int n_threads, xck_bam** out, char* e
     { BamScratch* sc = nullptr;
       { std::lock_guard<std::mutex> lk(g_scratch_mu); if (!g_scratch.empty()) { sc = g_scratch.back(); g_scratch.pop_back(); } }
       if (sc) {
-          for (int i = 0; i < N_SOA; i++) b->soa[i] = sc->soa[i];
+          for (int i = 0; i < N_JOB; i++) b->jobs[i].soa = sc->soa[i];
           for (int i = 0; i < N_CHUNK; i++) b->ch[i].ubuf.swap(sc->ubuf[i]);
-          b->recs.swap(sc->recs); b->rec_contig.swap(sc->rec_contig); b->rec_out.swap(sc->rec_out);
           if (sc->pool && sc->n_threads == n_threads) b->pool = sc->pool; else delete sc->pool;
           delete sc;
       } }
@@ -675,7 +676,7 @@ void xck_bam_close(xck_bam* b) {
     // no H2D copy may still read a block that is parked or freed - and a parked block must not keep its event: the copy stream
     // it was recorded on dies with the engine's staging, and waiting on such an event later fails (hipErrorStreamCaptureUnsupported
     // on ROCm 7: the next reader's first launch check then reported that stale error; tests/test_gpu_random_e2e.py seed 9)
-    for (auto& so : b->soa) if (so.fence) { fence_wait(so.fence); fence_destroy(so.fence); so.fence = nullptr; }
+    for (auto& j : b->jobs) if (j.soa.fence) { fence_wait(j.soa.fence); fence_destroy(j.soa.fence); j.soa.fence = nullptr; }
     if (getenv("XCK_DEBUG_TIMING") && b->gi.chunks)
         fprintf(stderr, "[xck] ingest %s: GPU share of the inflate: %llu chunks / %llu blocks on the device (%llu of them finished by the host), gather %.0f ms of pool time, coordinator waited %.0f ms%s\n",
                 b->path.c_str(), (unsigned long long)b->gi.chunks, (unsigned long long)b->gi.blocks, (unsigned long long)b->gi.left_blocks, b->gi.copy_ns * 1e-6, b->gi.wait_ns * 1e-6,
@@ -693,9 +694,8 @@ void xck_bam_close(xck_bam* b) {
                 t.wait_inflate * ms, t.sched * ms, t.stitch * ms, t.layout * ms, t.wait_parse * ms, t.wait_push * ms, t.push * ms);
     }
     { BamScratch* sc = new BamScratch();
-      for (int i = 0; i < N_SOA; i++) { sc->soa[i] = b->soa[i]; b->soa[i] = HostSoA(); }
+      for (int i = 0; i < N_JOB; i++) { sc->soa[i] = b->jobs[i].soa; b->jobs[i].soa = HostSoA(); }
       for (int i = 0; i < N_CHUNK; i++) sc->ubuf[i].swap(b->ch[i].ubuf);
-      sc->recs.swap(b->recs); sc->rec_contig.swap(b->rec_contig); sc->rec_out.swap(b->rec_out);
       sc->pool = b->pool; sc->n_threads = b->n_threads; b->pool = nullptr;
       std::lock_guard<std::mutex> lk(g_scratch_mu);
       if (g_scratch.size() < 4) g_scratch.push_back(sc);
@@ -775,8 +775,6 @@ static void set_ranges(xck_bam* b, const xck_ingest_opts* o) {
     b->use_ranges = true;
 }
 
-// take the next plan from the scanner and start inflating it into c (asynchronous); tid_to_contig lets the walk tasks
-// prepare the output layout of their own records
 // One part of a chunk: inflate its blocks (all of them, or - st given - only those the GPU kernel left: status != 0), then walk the
 // records of its byte range speculatively.  Pool task.
 // verify_crc: every non-empty block it inflates is CRC-checked (dstat: the reader's counters); a block the kernel found damaged
@@ -822,6 +820,11 @@ static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* w
     wpp->stop = o;
 }
 
+// position windows: the reference whose index range the chunk belongs to (ContigMap::only_tid), -1 without windows
+static int32_t range_only_tid(const xck_bam* b, const Chunk& c) { return b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1; }
+
+// take the next plan from the scanner and start inflating it into c (asynchronous); the contig map lets the walk tasks
+// prepare the output layout of their own records
 static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool crc_on_device, const ContigMap cm_in, bool want_seq) {
     c.blocks.clear(); c.usize = 0; c.valid = false; c.failed = false; c.err.clear(); c.new_range = false; c.first_skip = 0; c.gpu = false; c.gpu_rc = 0; c.launched = 0; c.stage2 = false;
     if (b->scan_end) return;
@@ -865,7 +868,7 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool c
     const size_t n_parts = (nb + per - 1) / per;
     c.parts.resize(n_parts);
     const size_t skip0 = c.first_skip;             // bytes before the first record (first chunk of the file / of an index range)
-    ContigMap cm = cm_in; cm.only_tid = b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1;
+    ContigMap cm = cm_in; cm.only_tid = range_only_tid(b, c);
     if (gs) {                                       // block table: where every block's stream sits in the gathered input, where its bytes go
         size_t at = 0;
         for (size_t i = 0; i < nb; i++) {
@@ -1030,24 +1033,8 @@ static inline void parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, 
         s.umi[o] = key;
 }
 
-// slow path: records [r0, r1) of the serially stitched list (b->recs / b->rec_out)
-static void parse_range(xck_bam* b, xck_engine* e, int32_t sample, int64_t r0, int64_t r1, std::atomic<int>* flags) {
-    const auto t_parse0 = std::chrono::steady_clock::now();
-    struct PAcc { xck_bam* b; std::chrono::steady_clock::time_point t0; ~PAcc() { b->tm.parse += ns_since(t0); } } pacc{b, t_parse0};
-    const DecodeCfg& dc = e->dec;
-    HostSoA& s = b->soa[b->soa_i];
-    // UMI-less mode: every read name goes through the intern table - collected here, interned in one batch at the end
-    std::vector<InternTable::Item> names;
-    if (!dc.use_umi) names.reserve((size_t)(r1 - r0));
-    for (int64_t r = r0; r < r1; r++) {
-        const int64_t o = b->rec_out[r];
-        if (o < 0) continue;
-        parse_record(dc, e, s, b->recs[r].p, b->recs[r].len, o, sample, names, flags);
-    }
-    if (!names.empty()) { bool ovf = false; e->intern.intern_batch(names, &ovf); if (ovf) flags->fetch_or(2); }
-}
-
-// fast path: the records of one walk part, whose output slots start at the part's bases (prefix sums over the parts)
+// the records of one piece of a chunk (a walk part, or a piece of the serial stitch), whose output slots start at the piece's bases
+// (prefix sums over the pieces: layout_chunk)
 static void parse_part(xck_bam* b, xck_engine* e, HostSoA* sp, int32_t sample, const WalkPart* wp, const ContigMap cm, std::atomic<int>* flags) {
     const auto t_parse0 = std::chrono::steady_clock::now();
     struct PAcc { xck_bam* b; std::chrono::steady_clock::time_point t0; ~PAcc() { b->tm.parse += ns_since(t0); } } pacc{b, t_parse0};
@@ -1069,13 +1056,13 @@ static void parse_part(xck_bam* b, xck_engine* e, HostSoA* sp, int32_t sample, c
     if (!names.empty()) { bool ovf = false; e->intern.intern_batch(names, &ovf); if (ovf) flags->fetch_or(2); }
 }
 
-// decode the next chunk into the SoA and fill b->pending. returns 1 (decoded), 0 (eof), <0 error
+// ---- a decoded chunk's way out: jobs, the push thread ------------------------------------------------------------------
 // the chunk at the head of the ring is consumed (or dropped): its slot, if it had one and nothing is in flight on it, serves the next device chunk
 static void release_chunk(xck_bam* b, int ci) {
     GpuShare& gi = b->gi;
     if (gi.slot[ci] && !gi.inflight[ci]) { gi.free_slots.push_back(gi.slot[ci]); gi.slot[ci] = nullptr; }
 }
-static void advance_head(xck_bam* b, IngestJob* hold = nullptr) {     // hold: that job's parse still reads the chunk (reap_jobs takes it back)
+static void advance_head(xck_bam* b, ChunkJob* hold = nullptr) {      // hold: that job's parse still reads the chunk (reap_jobs takes it back)
     if (hold) { hold->ring_idx = b->head; hold->released = false; } else release_chunk(b, b->head);
     b->head = (b->head + 1) % b->n_ring; b->n_sched--;
 }
@@ -1083,9 +1070,34 @@ static void advance_head(xck_bam* b, IngestJob* hold = nullptr) {     // hold: t
 static void reap_jobs(xck_bam* b) {
     for (auto& j : b->jobs) if (!j.released && j.parsed.load(std::memory_order_acquire)) { release_chunk(b, j.ring_idx); j.released = true; }
 }
-static Pusher* get_pusher(xck_engine* e, xck_bam* b) {
-    if (!b->pusher) { b->pusher = new Pusher(); Pusher* pp = b->pusher; pp->e = e; pp->b = b; pp->th = std::thread([pp] { pp->run(); }); }
-    return b->pusher;
+// The job of the chunk that is decoded now.  The push thread is never more than N_JOB - 1 jobs behind (Pusher::submit), so the slot's last
+// user is done with it; should that ever fail to hold the decode ends here rather than write into a block that is still parsed into or copied.
+static ChunkJob* take_job(xck_engine* e, xck_bam* b) {
+    ChunkJob& j = b->jobs[b->n_jobs % N_JOB];
+    reap_jobs(b);
+    if (j.queued.load(std::memory_order_acquire) || !j.released) { b->err = "internal: the job slot of this chunk is still in use"; return nullptr; }
+    b->n_jobs++; b->cur = &j;
+    if (j.soa.fence) fence_wait(j.soa.fence);                           // the H2D copy that last read this block has completed
+    j.e = e; j.flags.store(0); j.parsed.store(0); j.ring_idx = -1; j.batches.clear();
+    return &j;
+}
+// what a chunk's parse tasks reported (flags 1 / 2: parse_record; a task that threw) -> error code and text, 0 if nothing.  Call after tg.wait().
+static int parse_error(ChunkJob& j, std::string* msg) {
+    int fl = j.flags.load();
+    if (const int th = j.tg.take_thrown()) fl |= th == 1 ? 4 : 8;
+    if (fl & 4) { *msg = "out of host memory (record parse)"; return XCK_E_NOMEM; }
+    if (fl & 8) { *msg = "C++ exception in a parse task"; return XCK_E_IO; }
+    if (fl & 1) { *msg = "corrupt BAM record (fields exceed block_size)"; return XCK_E_IO; }
+    if (fl & 2) { *msg = "too many distinct non-ACGT keys for the key width"; return XCK_E_CAPACITY; }
+    return 0;
+}
+// a batch = a slice of the chunk's SoA block
+static void fill_batch(const HostSoA& s, const PendingBatch& pb, bool want_seq, xck_batch* bt) {
+    memset(bt, 0, sizeof *bt);
+    bt->contig = pb.contig; bt->n_reads = (int32_t)(pb.r1 - pb.r0); bt->ordinal_base = pb.ordinal_base;
+    bt->pos = s.pos + pb.r0; bt->flag = s.flag + pb.r0; bt->mapq = s.mapq + pb.r0; bt->cell = s.cell + pb.r0; bt->umi = s.umi + pb.r0;
+    bt->cig_off = s.cig_off + pb.r0; bt->cigar = s.cigar;
+    if (want_seq) { bt->seq_off = s.seq_off + pb.r0; bt->seq = s.seq; }
 }
 
 void Pusher::run() {
@@ -1093,42 +1105,30 @@ void Pusher::run() {
     for (;;) {
         cv.wait(lk, [this] { return stop || qn > 0; });
         if (qn == 0) return;
-        IngestJob* j = q[qh];
+        ChunkJob* j = q[qh];
         const bool failed = rc != 0;
         lk.unlock();
-        int r = 0; std::string msg;
-        if (j->has_parse) {
-            const auto t0 = std::chrono::steady_clock::now();
-            j->tg.wait();
-            parse_wait_ns += ns_since(t0);
-            int fl = j->flags.load();
-            if (const int th = j->tg.take_thrown()) fl |= th == 1 ? 4 : 8;
-            if (fl & 4) { msg = "out of host memory (record parse)"; r = XCK_E_NOMEM; }
-            else if (fl & 8) { msg = "C++ exception in a parse task"; r = XCK_E_IO; }
-            else if (fl & 1) { msg = "corrupt BAM record (fields exceed block_size)"; r = XCK_E_IO; }
-            else if (fl & 2) { msg = "too many distinct non-ACGT keys for the key width"; r = XCK_E_CAPACITY; }
-        }
+        std::string msg;
+        auto t0 = std::chrono::steady_clock::now();
+        j->tg.wait();
+        parse_wait_ns += ns_since(t0);
+        int r = parse_error(*j, &msg);
         j->parsed.store(1, std::memory_order_release);
-        if (!failed && !r && e->n_impl > 0 && !j->pending.empty()) {
+        if (!failed && !r && !j->batches.empty()) {
             // the whole chunk crosses PCIe as ONE block; its batches are slices of the block (fused handles: both pipelines read the same copy)
-            const auto t0 = std::chrono::steady_clock::now();
-            HostSoA& s = b->soa[j->soa];
-            std::vector<xck_batch> bts; bts.reserve(j->pending.size());
-            for (const PendingBatch& pb : j->pending) {
-                xck_batch bt; memset(&bt, 0, sizeof bt);
-                bt.contig = pb.contig; bt.n_reads = (int32_t)(pb.r1 - pb.r0); bt.ordinal_base = pb.ordinal_base;
-                bt.pos = s.pos + pb.r0; bt.flag = s.flag + pb.r0; bt.mapq = s.mapq + pb.r0; bt.cell = s.cell + pb.r0; bt.umi = s.umi + pb.r0;
-                bt.cig_off = s.cig_off + pb.r0; bt.cigar = s.cigar;
-                if (e->dec.want_seq) { bt.seq_off = s.seq_off + pb.r0; bt.seq = s.seq; }
-                bts.push_back(bt);
-            }
+            t0 = std::chrono::steady_clock::now();
+            xck_engine* e = j->e; HostSoA& s = j->soa;
+            std::vector<xck_batch> bts(j->batches.size());
+            for (size_t i = 0; i < bts.size(); i++) fill_batch(s, j->batches[i], e->dec.want_seq, &bts[i]);
             try { r = xck::engine_push_block(e, s.base, s.used, bts.data(), (int)bts.size(), &s.fence); } catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
             if (r) msg = e->err;
             push_ns += ns_since(t0);
         }
+        j->batches.clear();                                              // (handed over, or dropped behind a failure)
         lk.lock();
         if (r && !rc) { rc = r; err = msg; }
         qh = (qh + 1) % MAXQ; qn--;
+        j->queued.store(0, std::memory_order_release);
         cv.notify_all();
     }
 }
@@ -1158,7 +1158,7 @@ static void start_stage_two(xck_engine* e, xck_bam* b, int ci, ContigMap cm, boo
         if (e->dec.crc_on_device) { b->dstat[DS_CRC_DEVICE] += (int64_t)crc_ok; b->dstat[DS_CRC_MISMATCH_DEVICE] += (int64_t)crc_bad; }
     }
     b->gi.left_blocks += left; b->dstat[DS_GPU_LEFT] += (int64_t)left;
-    cm.only_tid = b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1;
+    cm.only_tid = range_only_tid(b, c);
     // (what the device left - a CRC mismatch included - is checked on the host as every host block is)
     Chunk* cp = &c; const uint8_t* map = b->map; DecodeTimes* tmp_ = &b->tm; const bool want_seq = e->dec.want_seq, crc = e->dec.verify_crc; std::atomic<int64_t>* ds = b->dstat;
     for (WalkPart& wp : c.parts) { WalkPart* wpp = &wp; c.tg.later([cp, map, crc, wpp, tmp_, cm, want_seq, st, ds] { run_part(cp, map, crc, wpp, tmp_, cm, want_seq, st, ds); }); }
@@ -1166,250 +1166,273 @@ static void start_stage_two(xck_engine* e, xck_bam* b, int ci, ContigMap cm, boo
     c.stage2 = true;
 }
 
-static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only = false) {
-    const bool crc = e->dec.verify_crc, crc_dev = e->dec.crc_on_device;
-    const int n_refs = (int)b->ref_names.size();
-    const bool has_win = o->struct_size >= offsetof(xck_ingest_opts, tid_end) + sizeof(void*);
-    ContigMap cm; cm.t2c = o->tid_to_contig; cm.n_refs = n_refs; cm.t_end = has_win ? o->tid_end : nullptr;
+// ---- decode_next_chunk and its stages ------------------------------------------------------------------------------------
+// the phases of the coordinating thread (DecodeTimes): lap() books the time since the last lap
+struct PhaseClock {
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(uint64_t& acc) { acc += ns_since(t); t = std::chrono::steady_clock::now(); }
+};
+
+// Stage 1, at the first call of a reader (decode or prefetch): the index ranges to read, whether the GPU takes a share of the inflate,
+// the NUMA binding, the scanner thread.
+static void begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only) {
     if (!schedule_only && !b->started) {
         b->started = true;
-        // well mode without UMIs: the key is the read name and the column is the BAM itself, so names only
-        // have to be unique within one file - restart the intern table per BAM (bounded memory for 384 x 2 M reads).
-        // (At the first DECODE call, not at xck_bam_prefetch: the file before this one may still be parsing.)
+        // well mode without UMIs: the key is the read name and the column is the BAM itself, so names only have to be unique within one file -
+        // restart the intern table per BAM (bounded memory for 384 x 2 M reads).  (At the first DECODE call, not at xck_bam_prefetch: the file
+        // before this one may still be parsing.)
         if (!e->dec.use_barcodes && !e->dec.use_umi) e->intern.clear();
     }
-    if (!b->ranges_set) {
-        set_ranges(b, o);
-        if (!b->gi.tried) {                                    // GPU share of the inflate: a handle with a device, XCK_GPU_INFLATE > 0, no host-only CRC checks asked for
-            b->gi.tried = true;
-            const int dev = engine_device(e), pct = e->knobs.gpu_inflate_pct;
-            // (files of a few chunks - the per-cell BAMs of a well-based run - are done before the device has returned its first chunk)
-            uint64_t span = b->fsize;
-            if (b->use_ranges) { span = 0; for (auto& r : b->ranges) span += (r.second >> 16) - (r.first >> 16); }
-            const bool big = span >= (uint64_t)e->knobs.gpu_inflate_min_mb << 20 || schedule_only;   // (a file that is read ahead has the time a device chunk takes, whatever its size)
-            if (pct != 0 && dev >= 0 && (!crc || crc_dev) && (big || pct > 0)) { b->gi.on = true; b->gi.pct = pct < 0 ? 0 : std::min(pct, 100); b->gi.depth = e->knobs.gpu_inflate_depth; b->gi.max_held = std::min(b->gi.depth + 2, 12); b->gi.device = dev; b->gi.free_cus = e->knobs.gpu_inflate_free_cus; b->gi.verbose = e->knobs.debug_timing; b->n_ring = std::max(N_CHUNK + 1, std::min(N_CHUNK_GPU, e->knobs.gpu_inflate_ring)); }
+    if (b->ranges_set) return;
+    set_ranges(b, o);
+    GpuShare& gi = b->gi;
+    if (!gi.tried) {                                           // GPU share of the inflate: a handle with a device, XCK_GPU_INFLATE > 0, no host-only CRC checks asked for
+        gi.tried = true;
+        const int dev = engine_device(e), pct = e->knobs.gpu_inflate_pct;
+        // (files of a few chunks - the per-cell BAMs of a well-based run - are done before the device has returned its first chunk)
+        uint64_t span = b->fsize;
+        if (b->use_ranges) { span = 0; for (auto& r : b->ranges) span += (r.second >> 16) - (r.first >> 16); }
+        const bool big = span >= (uint64_t)e->knobs.gpu_inflate_min_mb << 20 || schedule_only;   // (a file that is read ahead has the time a device chunk takes, whatever its size)
+        if (pct != 0 && dev >= 0 && (!e->dec.verify_crc || e->dec.crc_on_device) && (big || pct > 0)) {
+            gi.on = true; gi.pct = pct < 0 ? 0 : std::min(pct, 100); gi.device = dev;
+            gi.depth = e->knobs.gpu_inflate_depth; gi.max_held = std::min(gi.depth + 2, 12);
+            gi.free_cus = e->knobs.gpu_inflate_free_cus; gi.verbose = e->knobs.debug_timing;
+            b->n_ring = std::max(N_CHUNK + 1, std::min(N_CHUNK_GPU, e->knobs.gpu_inflate_ring));
         }
-        bind_to_numa_node(e, b);                               // (before the scanner thread is made: it inherits the mask)
-        std::vector<ScanRange> rg;
-        if (b->use_ranges) for (auto& r : b->ranges) rg.push_back({r.first >> 16, (uint32_t)(r.first & 0xffff), r.second >> 16});
-        else rg.push_back({b->next_coff, b->first_skip, ~0ull});
-        b->scanner = new Scanner(b->map, b->fsize, b->chunk_target, rg);
     }
-    auto t_ph = std::chrono::steady_clock::now();
-    auto phase = [&](uint64_t& acc) { const auto now = std::chrono::steady_clock::now(); acc += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(now - t_ph).count(); t_ph = now; };
-    // keep the ring full: while this chunk is stitched and parsed the pool inflates the next two
+    bind_to_numa_node(e, b);                                   // (before the scanner thread is made: it inherits the mask)
+    std::vector<ScanRange> rg;
+    if (b->use_ranges) for (auto& r : b->ranges) rg.push_back({r.first >> 16, (uint32_t)(r.first & 0xffff), r.second >> 16});
+    else rg.push_back({b->next_coff, b->first_skip, ~0ull});
+    b->scanner = new Scanner(b->map, b->fsize, b->chunk_target, rg);
+}
+
+// Stage 2, keep the ring full: while the head chunk is stitched and parsed the pool inflates the next ones
+static void fill_ring(xck_engine* e, xck_bam* b, const ContigMap& cm) {
     reap_jobs(b);
     // (the chunks behind `head` that a parse in flight still reads must not be scheduled over: `back` = how far the oldest of them lies behind)
     int back = 0;
     for (auto& j : b->jobs) if (!j.released) back = std::max(back, (b->head - j.ring_idx + b->n_ring) % b->n_ring);
     while (b->n_sched + back < b->n_ring && !b->scan_end) {
         const int ci = (b->head + b->n_sched) % b->n_ring;
-        Chunk& nc = b->ch[ci];
-        schedule_chunk(b, nc, ci, crc, crc_dev, cm, e->dec.want_seq);
+        schedule_chunk(b, b->ch[ci], ci, e->dec.verify_crc, e->dec.crc_on_device, cm, e->dec.want_seq);
         if (b->scan_end) break;
         b->n_sched++;
     }
-    phase(b->tm.sched);
-    if (schedule_only) return 2;                                         // xck_bam_prefetch: the pool is inflating the first chunks now
+}
+
+// the chunk's pool tasks (inflate / gather, walk) have ended; one that threw ends the stream
+static int wait_chunk_tasks(xck_bam* b, Chunk& c) {
+    c.tg.wait();
+    const int th = c.tg.take_thrown();
+    if (th) b->err = th == 1 ? "out of host memory (BGZF inflate / record walk)" : "C++ exception in a decoder task";
+    return !th ? 0 : th == 1 ? XCK_E_NOMEM : XCK_E_IO;
+}
+
+// Stage 3, wait for the chunk at the head of the ring: inflated and walked (a device chunk: stage two first), cm->only_tid set for it.
+// Returns 1, 0 at the end of the stream, < 0 on error, or HEAD_SKIPPED: the chunk belonged to an abandoned range and was dropped.
+constexpr int HEAD_SKIPPED = 2;
+static int wait_head(xck_engine* e, xck_bam* b, ContigMap* cm, PhaseClock& clk) {
     if (b->n_sched == 0) {
         if (!b->use_ranges && !b->carry.empty()) { b->err = "truncated BAM file (partial record at end of file)"; return XCK_E_IO; }
         return 0;
     }
-    if (b->gi.on) for (int k = 1; k < b->n_sched; k++) start_stage_two(e, b, (b->head + k) % b->n_ring, cm, false);   // device chunks that are back already: walk them now
+    if (b->gi.on) for (int k = 1; k < b->n_sched; k++) start_stage_two(e, b, (b->head + k) % b->n_ring, *cm, false);   // device chunks that are back already: walk them now
     Chunk& c = b->ch[b->head];
-    cm.only_tid = b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1;
-    c.tg.wait();
-    if (const int th = c.tg.take_thrown()) { b->err = th == 1 ? "out of host memory (BGZF inflate / record walk)" : "C++ exception in a decoder task"; return th == 1 ? XCK_E_NOMEM : XCK_E_IO; }
+    cm->only_tid = range_only_tid(b, c);
+    if (const int rc = wait_chunk_tasks(b, c)) return rc;
     if (c.gpu && !c.stage2) {
-        start_stage_two(e, b, b->head, cm, true);
-        c.tg.wait();
-        if (const int th = c.tg.take_thrown()) { b->err = th == 1 ? "out of host memory (BGZF inflate / record walk)" : "C++ exception in a decoder task"; return th == 1 ? XCK_E_NOMEM : XCK_E_IO; }
+        start_stage_two(e, b, b->head, *cm, true);
+        if (const int rc = wait_chunk_tasks(b, c)) return rc;
     }
     if (b->skip_range >= 0 && c.range_id == b->skip_range && !c.failed) {   // rest of a reference whose position window is behind us
         if (c.gpu && b->gi.inflight[b->head]) { gpu_inflate_slot_wait(b->gi.slot[b->head]); b->gi.inflight[b->head] = false; }
-        advance_head(b);
-        b->carry.clear();
-        return decode_next_chunk(e, b, o);
+        advance_head(b); b->carry.clear();
+        return HEAD_SKIPPED;
     }
-    phase(b->tm.wait_inflate); b->tm.chunks++;
+    clk.lap(b->tm.wait_inflate); b->tm.chunks++;
     if (c.failed) { b->err = c.err.empty() ? "BGZF decode error" : c.err; return XCK_E_IO; }
+    return 1;
+}
+
+// no carried-over bytes, no record limit, every part's speculative walk began where the previous one ended: the parts' lists are the chunk's
+static bool speculation_held(const xck_bam* b, const Chunk& c, const xck_ingest_opts* o, size_t off) {
+    if (!b->carry.empty() || o->max_records > 0) return false;
+    size_t at = off;
+    for (size_t pi = 0; pi < c.parts.size(); pi++) {
+        const WalkPart& wp = c.parts[pi];
+        if (wp.spec_start != at) return false;
+        at = wp.stop;
+        if (pi + 1 < c.parts.size() && wp.stop != wp.u_end) return false;       // a record straddles two parts
+    }
+    return !(at + 4 <= c.usize && le32(c.ubase + at) < 32);                     // not a straddling tail but a damaged record: the serial walk reports it
+}
+
+// The serial stitch: the boundary record from the carry, then the parts' lists where their speculation held and a re-walk where it did
+// not, cut into c.stitched (pieces of a parse task's size) and ended at the record limit; what follows the last whole record is carried.
+static int stitch_serially(xck_bam* b, Chunk& c, const ContigMap& cm, const xck_ingest_opts* o, bool want_seq, size_t off, bool* hit_limit) {
+    const uint8_t* u = c.ubase; const size_t usz = c.usize;
+    size_t est = 1; for (const WalkPart& wp : c.parts) est += wp.recs.size();
+    const size_t per = std::max<size_t>(4096, (est + (size_t)b->n_threads * 4 - 1) / ((size_t)b->n_threads * 4));
+    const int64_t limit = o->max_records > 0 ? std::max<int64_t>(0, o->max_records - b->n_records) : INT64_MAX;
+    int64_t n_walked = 0; int32_t cur_c = INT32_MIN;
+    c.stitched.clear();
+    auto add = [&](const uint8_t* r, uint32_t len) {                    // (as the walk tasks note their records: run_part)
+        if (n_walked++ >= limit) return;
+        if (c.stitched.empty() || c.stitched.back().recs.size() >= per) { c.stitched.emplace_back(); cur_c = INT32_MIN; }
+        WalkPart& wp = c.stitched.back();
+        const RecRef rr{r, len, (int32_t)le32(r), le32(r + 16), le16(r + 12)};
+        const int32_t ctg = cm(rr.tid, (int32_t)le32(r + 4));
+        if (ctg != cur_c) { wp.runs.push_back({(uint32_t)wp.recs.size(), ctg}); cur_c = ctg; }
+        if (ctg >= 0) { wp.n_out++; wp.n_cig += rr.n_cig; if (want_seq) wp.n_seq += (rr.l_seq + 1) / 2; }
+        wp.recs.push_back(rr);
+    };
+    c.stitch.clear();
+    if (!b->carry.empty()) {
+        c.stitch.swap(b->carry);
+        while (c.stitch.size() < 4 && off < usz) c.stitch.push_back(u[off++]);
+        if (c.stitch.size() >= 4) {
+            const uint32_t bs = le32(c.stitch.data());
+            const size_t need = 4 + (size_t)bs - c.stitch.size();
+            if (need <= usz - off) { c.stitch.insert(c.stitch.end(), u + off, u + off + need); off += need; }
+            else { c.stitch.insert(c.stitch.end(), u + off, u + usz); off = usz; b->carry.swap(c.stitch); }   // record larger than a chunk
+        } else { b->carry.swap(c.stitch); }
+    }
+    if (!c.stitch.empty()) {
+        if (c.stitch.size() < 36) { b->err = "corrupt BAM record"; return XCK_E_IO; }
+        add(c.stitch.data() + 4, (uint32_t)c.stitch.size() - 4);
+    }
+    size_t pi = 0; bool incomplete = false;
+    while (!incomplete) {
+        while (pi < c.parts.size() && c.parts[pi].u_end <= off) pi++;
+        if (pi == c.parts.size()) break;
+        const WalkPart& wp = c.parts[pi];
+        if (off == wp.spec_start) {                                     // speculation held: take the task's list
+            for (const RecRef& rr : wp.recs) add(rr.p, rr.len);
+            off = wp.stop;
+            if (off == wp.u_end) { pi++; continue; }
+        }
+        while (off < wp.u_end) {                                        // serial walk (record straddles ranges / mis-speculation)
+            if (off + 4 > usz) { incomplete = true; break; }
+            const uint32_t bs = le32(u + off);
+            if (off + 4 + (size_t)bs > usz) { incomplete = true; break; }
+            if (bs < 32) { b->err = "corrupt BAM record (block_size < 32)"; return XCK_E_IO; }
+            add(u + off + 4, bs);
+            off += 4 + (size_t)bs;
+        }
+        pi++;
+    }
+    if (off < usz) b->carry.insert(b->carry.end(), u + off, u + usz);
+    *hit_limit = n_walked > limit;
+    return 0;
+}
+
+// Stage 4, stitch: -> the chunk's records as a list of pieces (its walk parts, or what the serial stitch made), the reader's carry
+static int stitch_chunk(xck_bam* b, Chunk& c, const ContigMap& cm, const xck_ingest_opts* o, bool want_seq, std::vector<WalkPart>** pieces, bool* hit_limit) {
     if (c.new_range) {                                                  // start of the file's records / of an index range
         if (!b->use_ranges && b->tm.chunks > 1 && !b->carry.empty()) { b->err = "internal: carry at a range start"; return XCK_E_IO; }
-        b->carry.clear(); b->stitch_skip = c.first_skip;
+        b->carry.clear();
     }
-    const uint8_t* u = c.ubase; const size_t usz = c.usize; size_t off = 0;
-    if (b->stitch_skip) { off = b->stitch_skip; b->stitch_skip = 0; if (off > usz) { b->err = "corrupt BAM header offset"; return XCK_E_IO; } }
-    // ---- fast path: no carried-over bytes, and every part's speculative walk began where the previous one ended ----
-    bool fast = b->carry.empty() && !(o->max_records > 0);
-    if (fast) {
-        size_t at = off;
-        for (size_t pi = 0; pi < c.parts.size() && fast; pi++) {
-            const WalkPart& wp = c.parts[pi];
-            if (wp.spec_start != at) fast = false;
-            at = wp.stop;
-            if (pi + 1 < c.parts.size() && wp.stop != wp.u_end) fast = false;      // a record straddles two parts
-        }
-        if (fast && at + 4 <= usz && le32(u + at) < 32) fast = false;              // not a straddling tail but a damaged record: the serial walk reports it
+    const size_t off = c.new_range ? c.first_skip : 0;                  // bytes of the range's first block that precede its first record
+    if (off > c.usize) { b->err = "corrupt BAM header offset"; return XCK_E_IO; }
+    *hit_limit = false;
+    if (speculation_held(b, c, o, off)) {
+        const size_t stop = c.parts.back().stop;
+        if (stop < c.usize) b->carry.insert(b->carry.end(), c.ubase + stop, c.ubase + c.usize);
+        *pieces = &c.parts;
+        return 0;
     }
-    HostSoA& s = b->soa[(b->soa_i + 1) % N_SOA];
-    if (s.fence) fence_wait(s.fence);                                   // the H2D copy that last read this block has completed
-    b->soa_i = (b->soa_i + 1) % N_SOA;
-    b->pending.clear();
-    const uint64_t ord_hi = (uint64_t)(uint32_t)o->sample << ORD_REC_BITS;
-    std::atomic<int> flags{0};
-    int64_t limit = 0;
-    bool hit_limit = false;
-    if (fast) {
-        size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0;
-        for (WalkPart& wp : c.parts) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_rec += wp.recs.size(); }
-        const WalkPart& last = c.parts.back();
-        if (last.stop < usz) b->carry.insert(b->carry.end(), u + last.stop, u + usz);
-        phase(b->tm.stitch);
-        if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { b->err = "chunk too large"; return XCK_E_IO; }
-        if (!soa_reserve(s, n_out + 1, n_cig + 1, e->dec.want_seq ? n_seq + 1 : 1)) { b->err = "out of host memory"; return XCK_E_NOMEM; }
-        s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
-        // batches = runs of records on one contig, across part boundaries
-        { int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0; int64_t rec0 = 0;
-          for (const WalkPart& wp : c.parts) {
-              int64_t oi = (int64_t)wp.out_base;
-              for (size_t ri = 0; ri < wp.runs.size(); ri++) {
-                  const ContigRun& rn = wp.runs[ri];
-                  const uint32_t nxt = ri + 1 < wp.runs.size() ? wp.runs[ri + 1].first : (uint32_t)wp.recs.size();
-                  if (rn.contig != cur_c) {
-                      if (cur_c >= 0 && oi > seg0) b->pending.push_back({cur_c, seg0, oi, ord_hi | (uint64_t)(b->n_records + seg_r)});
-                      cur_c = rn.contig; seg0 = oi; seg_r = rec0 + rn.first;
-                  }
-                  if (rn.contig >= 0) oi += nxt - rn.first;
-              }
-              rec0 += (int64_t)wp.recs.size();
-          }
-          if (cur_c >= 0 && (int64_t)n_out > seg0) b->pending.push_back({cur_c, seg0, (int64_t)n_out, ord_hi | (uint64_t)(b->n_records + seg_r)}); }
-        phase(b->tm.layout);
-        limit = (int64_t)n_rec;
-        if (b->defer_parse) {
-            IngestJob& jb = b->jobs[b->job_n % (PUSH_Q + 1)];           // (free: at most PUSH_Q jobs are outstanding)
-            reap_jobs(b);
-            const int32_t smp = o->sample; HostSoA* sp = &s; std::atomic<int>* fl = &jb.flags;
-            jb.flags.store(0); jb.parsed.store(0); jb.has_parse = true; jb.soa = b->soa_i; jb.pending.swap(b->pending); b->pending.clear();
-            for (const WalkPart& wp : c.parts) { if (!wp.n_out) continue; const WalkPart* wpp = &wp;
-                jb.tg.later([b, e, sp, smp, wpp, cm, fl] { parse_part(b, e, sp, smp, wpp, cm, fl); }); }
-            jb.tg.flush(*b->pool, true);                                // (ahead of the later chunks' inflate tasks)
-            if (b->per_tid_ranges && cm.t_end) {                        // (same check as below: it only looks at the record lists)
-                const RecRef* last = nullptr;
-                for (size_t pi = c.parts.size(); pi-- > 0 && !last;) if (!c.parts[pi].recs.empty()) last = &c.parts[pi].recs.back();
-                if (last && last->tid >= 0 && last->tid < n_refs && cm.t_end[last->tid] > 0 && (int32_t)le32(last->p + 4) >= cm.t_end[last->tid]) {
-                    b->skip_range = c.range_id; b->scanner->abandon(c.range_id);
-                }
-            }
-            b->n_records += limit;
-            advance_head(b, &jb);
-            b->job_n++;
-            const int prc = get_pusher(e, b)->submit(&jb);              // waits while two chunks are outstanding behind this one
-            phase(b->tm.wait_push);
-            if (prc) { b->err = b->pusher->err; return prc; }
-            return 2;                                                   // parse + push in flight
-        }
-        { TaskGroup tg; const int32_t smp = o->sample; HostSoA* sp = &s;
-          for (const WalkPart& wp : c.parts) { if (!wp.n_out) continue; const WalkPart* wpp = &wp;
-              tg.later([b, e, sp, smp, wpp, cm, &flags] { parse_part(b, e, sp, smp, wpp, cm, &flags); }); }
-          tg.flush(*b->pool, true);                                     // (ahead of the later chunks' inflate tasks: the coordinator waits for these)
-          tg.wait();
-          if (const int th = tg.take_thrown()) flags.fetch_or(th == 1 ? 4 : 8); }
-        phase(b->tm.wait_parse);
-    } else {
-    // ---- slow path: stitch the per-task record lists serially; re-walk where the speculation failed ----
     b->tm.slow_chunks++;
-    b->recs.clear(); b->rec_contig.clear();
-    b->stitch.clear();
-    if (!b->carry.empty()) {
-        b->stitch = b->carry; b->carry.clear();
-        while (b->stitch.size() < 4 && off < usz) b->stitch.push_back(u[off++]);
-        if (b->stitch.size() >= 4) {
-            uint32_t bs = le32(b->stitch.data());
-            size_t need = 4 + (size_t)bs - b->stitch.size();
-            if (need <= usz - off) { b->stitch.insert(b->stitch.end(), u + off, u + off + need); off += need; }
-            else { b->stitch.insert(b->stitch.end(), u + off, u + usz); off = usz; b->carry.swap(b->stitch); }   // record larger than a chunk
-        } else { b->carry.swap(b->stitch); }
-    }
-    if (!b->stitch.empty()) {
-        if (b->stitch.size() < 36) { b->err = "corrupt BAM record"; return XCK_E_IO; }
-        const uint8_t* r = b->stitch.data() + 4;
-        b->recs.push_back({r, (uint32_t)b->stitch.size() - 4, (int32_t)le32(r), le32(r + 16), le16(r + 12)});
-    }
-    { size_t pi = 0; bool incomplete = false;
-      while (!incomplete) {
-          while (pi < c.parts.size() && c.parts[pi].u_end <= off) pi++;
-          if (pi == c.parts.size()) break;
-          WalkPart& wp = c.parts[pi];
-          if (off == wp.spec_start) {                                   // speculation held: take the task's list
-              b->recs.insert(b->recs.end(), wp.recs.begin(), wp.recs.end());
-              off = wp.stop;
-              if (off == wp.u_end) { pi++; continue; }
-          }
-          while (off < wp.u_end) {                                      // serial walk (record straddles ranges / mis-speculation)
-              if (off + 4 > usz) { incomplete = true; break; }
-              uint32_t bs = le32(u + off);
-              if (off + 4 + (size_t)bs > usz) { incomplete = true; break; }
-              if (bs < 32) { b->err = "corrupt BAM record (block_size < 32)"; return XCK_E_IO; }
-              const uint8_t* r = u + off + 4;
-              b->recs.push_back({r, bs, (int32_t)le32(r), le32(r + 16), le16(r + 12)});
-              off += 4 + (size_t)bs;
-          }
-          pi++;
-      } }
-    if (off < usz) b->carry.insert(b->carry.end(), u + off, u + usz);
-    phase(b->tm.stitch);
-    b->rec_contig.resize(b->recs.size());
-    for (size_t r = 0; r < b->recs.size(); r++) b->rec_contig[r] = cm(b->recs[r].tid, (int32_t)le32(b->recs[r].p + 4));
-    // ---- output layout: prefix sums + batch segmentation ----
-    const int64_t nrec = (int64_t)b->recs.size();
-    limit = nrec;
-    if (o->max_records > 0 && b->n_records + nrec > o->max_records) { limit = std::max<int64_t>(0, o->max_records - b->n_records); }
-    hit_limit = limit < nrec;
-    b->rec_out.assign(nrec, -1);
-    size_t n_out = 0, n_cig = 0, n_seq = 0;
-    for (int64_t r = 0; r < limit; r++) if (b->rec_contig[r] >= 0) { n_out++; n_cig += b->recs[r].n_cig; n_seq += (b->recs[r].l_seq + 1) / 2; }
+    *pieces = &c.stitched;
+    return stitch_serially(b, c, cm, o, want_seq, off, hit_limit);
+}
+
+// Stage 5, layout: where every piece's records go in the job's SoA block (prefix sums over the pieces), and the batches - runs of
+// records on one contig, across piece boundaries.  Returns the number of records of the chunk (kept or not), < 0 on error.
+static int64_t layout_chunk(xck_bam* b, ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq) {
+    size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0;
+    for (WalkPart& wp : pieces) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_rec += wp.recs.size(); }
     if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { b->err = "chunk too large"; return XCK_E_IO; }
-    if (!soa_reserve(s, n_out + 1, n_cig + 1, e->dec.want_seq ? n_seq + 1 : 1)) { b->err = "out of host memory"; return XCK_E_NOMEM; }
-    { size_t oi = 0; uint32_t co = 0, so = 0; int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0;
-      s.cig_off[0] = 0; s.seq_off[0] = 0;
-      for (int64_t r = 0; r < limit; r++) {
-          int32_t ctg = b->rec_contig[r];
-          if (ctg != cur_c) {                                     // a run of records on one contig = one batch
-              if (cur_c >= 0 && (int64_t)oi > seg0) b->pending.push_back({cur_c, seg0, (int64_t)oi, ord_hi | (uint64_t)(b->n_records + seg_r)});
-              cur_c = ctg; seg0 = (int64_t)oi; seg_r = r;
-          }
-          if (ctg < 0) continue;
-          b->rec_out[r] = (int64_t)oi;
-          co += b->recs[r].n_cig; so += e->dec.want_seq ? (b->recs[r].l_seq + 1) / 2 : 0; oi++;
-          s.cig_off[oi] = co; s.seq_off[oi] = so;
-      }
-      if (cur_c >= 0 && (int64_t)oi > seg0) b->pending.push_back({cur_c, seg0, (int64_t)oi, ord_hi | (uint64_t)(b->n_records + seg_r)});
-    }
-    phase(b->tm.layout);
-    // ---- parse (parallel) ----
-    { TaskGroup tg; const int64_t per = std::max<int64_t>(4096, (limit + b->n_threads * 4 - 1) / (b->n_threads * 4));
-      for (int64_t r0 = 0; r0 < limit; r0 += per) { int64_t r1 = std::min(limit, r0 + per); int32_t smp = o->sample;
-          tg.later([b, e, smp, r0, r1, &flags] { parse_range(b, e, smp, r0, r1, &flags); }); }
-      tg.flush(*b->pool, true);
-      tg.wait();
-      if (const int th = tg.take_thrown()) flags.fetch_or(th == 1 ? 4 : 8); }
-    phase(b->tm.wait_parse);
-    }
-    if (flags.load() & 4) { b->err = "out of host memory (record parse)"; return XCK_E_NOMEM; }
-    if (flags.load() & 8) { b->err = "C++ exception in a parse task"; return XCK_E_IO; }
-    if (flags.load() & 1) { b->err = "corrupt BAM record (fields exceed block_size)"; return XCK_E_IO; }
-    if (flags.load() & 2) { b->err = "too many distinct non-ACGT keys for the key width"; return XCK_E_CAPACITY; }
-    if (b->per_tid_ranges && cm.t_end) {                               // last record of the chunk starts beyond its reference's window: drop the rest
-        const RecRef* last = nullptr;
-        if (fast) { for (size_t pi = c.parts.size(); pi-- > 0 && !last;) if (!c.parts[pi].recs.empty()) last = &c.parts[pi].recs.back(); }
-        else if (!b->recs.empty()) last = &b->recs.back();
-        if (last && last->tid >= 0 && last->tid < n_refs && cm.t_end[last->tid] > 0 && (int32_t)le32(last->p + 4) >= cm.t_end[last->tid]) {
-            b->skip_range = c.range_id; b->scanner->abandon(c.range_id);
+    HostSoA& s = j.soa;
+    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) { b->err = "out of host memory"; return XCK_E_NOMEM; }
+    s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
+    const uint64_t ord_hi = (uint64_t)(uint32_t)o->sample << ORD_REC_BITS;
+    int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0, rec0 = 0;
+    auto close_batch = [&](int64_t oi) { if (cur_c >= 0 && oi > seg0) j.batches.push_back({cur_c, seg0, oi, ord_hi | (uint64_t)(b->n_records + seg_r)}); };
+    for (const WalkPart& wp : pieces) {
+        int64_t oi = (int64_t)wp.out_base;
+        for (size_t ri = 0; ri < wp.runs.size(); ri++) {
+            const ContigRun& rn = wp.runs[ri];
+            const uint32_t nxt = ri + 1 < wp.runs.size() ? wp.runs[ri + 1].first : (uint32_t)wp.recs.size();
+            if (rn.contig != cur_c) { close_batch(oi); cur_c = rn.contig; seg0 = oi; seg_r = rec0 + rn.first; }
+            if (rn.contig >= 0) oi += nxt - rn.first;
         }
+        rec0 += (int64_t)wp.recs.size();
     }
-    b->n_records += limit;
-    advance_head(b);
+    close_batch((int64_t)n_out);
+    return (int64_t)n_rec;
+}
+
+// position windows: the chunk's last record starts beyond its reference's window - the rest of that reference's range is dropped
+static void drop_range_past_window(xck_bam* b, const Chunk& c, const ContigMap& cm, const std::vector<WalkPart>& pieces) {
+    if (!b->per_tid_ranges || !cm.t_end) return;
+    const RecRef* last = nullptr;
+    for (size_t pi = pieces.size(); pi-- > 0 && !last;) if (!pieces[pi].recs.empty()) last = &pieces[pi].recs.back();
+    if (last && last->tid >= 0 && last->tid < cm.n_refs && cm.t_end[last->tid] > 0 && (int32_t)le32(last->p + 4) >= cm.t_end[last->tid]) {
+        b->skip_range = c.range_id; b->scanner->abandon(c.range_id);
+    }
+}
+
+// Stage 6, parse: one pool task per piece, record fields -> the job's SoA block.  The coordinator waits for them here, or
+// (defer_parse) hands the job to the push thread, which does; the ring chunk goes with the job until its parse has ended.
+static int parse_or_defer(xck_bam* b, Chunk& c, ChunkJob& j, const std::vector<WalkPart>& pieces, int64_t n_rec, const ContigMap& cm, int32_t sample, PhaseClock& clk) {
+    xck_engine* e = j.e; HostSoA* sp = &j.soa; std::atomic<int>* fl = &j.flags;
+    for (const WalkPart& wp : pieces) { if (!wp.n_out) continue; const WalkPart* wpp = &wp;
+        j.tg.later([b, e, sp, sample, wpp, cm, fl] { parse_part(b, e, sp, sample, wpp, cm, fl); }); }
+    j.tg.flush(*b->pool, true);                                         // (ahead of the later chunks' inflate tasks)
+    if (!b->defer_parse) {
+        j.tg.wait();
+        clk.lap(b->tm.wait_parse);
+        if (const int rc = parse_error(j, &b->err)) return rc;
+    }
+    drop_range_past_window(b, c, cm, pieces);                           // (it only looks at the record lists)
+    b->n_records += n_rec;
+    advance_head(b, b->defer_parse ? &j : nullptr);
+    if (!b->defer_parse) return 0;
+    if (!b->pusher) b->pusher = new Pusher();
+    const int prc = b->pusher->submit(&j);                              // waits while two chunks are outstanding behind this one
+    clk.lap(b->tm.wait_push);
+    if (prc) b->err = b->pusher->err;
+    return prc;
+}
+
+// decode the next chunk into the SoA block of its job (b->cur) and fill the job's batch list; returns 1 (decoded: parsed in place or,
+// defer_parse, parse + push in flight), 0 (end of the stream), < 0 on error; schedule_only (xck_bam_prefetch): 1 once the pool is
+// inflating the first chunks
+static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only = false) {
+    const bool has_win = o->struct_size >= offsetof(xck_ingest_opts, tid_end) + sizeof(void*);
+    ContigMap cm; cm.t2c = o->tid_to_contig; cm.n_refs = (int)b->ref_names.size(); cm.t_end = has_win ? o->tid_end : nullptr;
+    begin_decode(e, b, o, schedule_only);
+    PhaseClock clk;
+    int rc;
+    do {
+        clk = PhaseClock();
+        fill_ring(e, b, cm);
+        clk.lap(b->tm.sched);
+        if (schedule_only) return 1;
+        rc = wait_head(e, b, &cm, clk);
+    } while (rc == HEAD_SKIPPED);
+    if (rc <= 0) return rc;
+    Chunk& c = b->ch[b->head];
+    ChunkJob* j = take_job(e, b);
+    if (!j) return XCK_E_IO;
+    std::vector<WalkPart>* pieces = nullptr; bool hit_limit = false;
+    if ((rc = stitch_chunk(b, c, cm, o, e->dec.want_seq, &pieces, &hit_limit)) < 0) return rc;
+    clk.lap(b->tm.stitch);
+    const int64_t n_rec = layout_chunk(b, *j, *pieces, o, e->dec.want_seq);
+    if (n_rec < 0) return (int)n_rec;
+    clk.lap(b->tm.layout);
+    if ((rc = parse_or_defer(b, c, *j, *pieces, n_rec, cm, o->sample, clk)) < 0) return rc;
     if (hit_limit) { b->done = true; for (auto& cc : b->ch) cc.tg.wait(); }
     return 1;
 }
@@ -1449,40 +1472,19 @@ static int next_batch_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, 
     CallerBinding on_node(b);
     FoldDecodeStats fold{e, b};
     b->defer_parse = false;                                            // (this interface hands out finished batches: parse in place)
-    while (b->pending.empty()) {
+    while (!b->cur || b->cur->batches.empty()) {
         if (b->done) return 0;
         int rc = decode_next_chunk(e, b, o);
         if (rc < 0) { e->err = b->path + ": " + b->err; return rc; }
         if (rc == 0) { b->done = true; return 0; }
     }
-    PendingBatch pb = b->pending.front(); b->pending.pop_front();
-    HostSoA& s = b->soa[b->soa_i];
-    memset(out, 0, sizeof *out);
-    out->contig = pb.contig; out->n_reads = (int32_t)(pb.r1 - pb.r0); out->ordinal_base = pb.ordinal_base;
-    out->pos = s.pos + pb.r0; out->flag = s.flag + pb.r0; out->mapq = s.mapq + pb.r0; out->cell = s.cell + pb.r0; out->umi = s.umi + pb.r0;
-    out->cig_off = s.cig_off + pb.r0; out->cigar = s.cigar;
-    if (e->dec.want_seq) { out->seq_off = s.seq_off + pb.r0; out->seq = s.seq; }
+    fill_batch(b->cur->soa, b->cur->batches.front(), e->dec.want_seq, out);
+    b->cur->batches.pop_front();
     return 1;
 }
 
-// a chunk that was parsed in place (slow path) -> the push thread, behind the chunks already queued there
-static int push_chunk(xck_engine* e, xck_bam* b) {
-    if (e->n_impl <= 0 || b->pending.empty()) return XCK_OK;    // (a decode-only handle decodes and discards: host-ingest benchmarks)
-    const auto t_p = std::chrono::steady_clock::now();
-    IngestJob& jb = b->jobs[b->job_n % (PUSH_Q + 1)];
-    reap_jobs(b);
-    jb.flags.store(0); jb.parsed.store(0); jb.has_parse = false; jb.soa = b->soa_i; jb.ring_idx = -1; jb.released = true;
-    jb.pending.swap(b->pending); b->pending.clear();
-    b->job_n++;
-    const int prc = get_pusher(e, b)->submit(&jb);
-    b->tm.wait_push += ns_since(t_p);
-    if (prc) b->err = b->pusher->err;
-    return prc;
-}
-
 // nothing of this reader is in flight any more: parse tasks ended, their chunks pushed (unless something failed), push thread idle
-static int drain_ingest(xck_engine* e, xck_bam* b, int rc) {
-    (void)e;
+static int drain_ingest(xck_bam* b, int rc) {
     if (b->pusher) { const int prc = b->pusher->wait_idle(); if (rc >= 0 && prc) { b->err = b->pusher->err; rc = prc; } }
     reap_jobs(b);
     return rc;
@@ -1494,23 +1496,20 @@ static int ingest_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, int6
     FoldDecodeStats fold{e, b};
     const int64_t pause = o->struct_size >= offsetof(xck_ingest_opts, pause_records) + sizeof(int64_t) ? o->pause_records : 0;
     const int64_t start = b->n_records;
-    b->defer_parse = e->n_impl > 0;
-    auto fail = [&](int rc) { rc = drain_ingest(e, b, rc); e->err = b->path + ": " + b->err; return rc; };
-    while (!b->done) {
-        int rc = decode_next_chunk(e, b, o);
-        if (rc < 0) return fail(rc);
-        if (rc == 0) { b->done = true; break; }
-        if (rc == 1) { if (const int prc = push_chunk(e, b)) return fail(prc); }   // (parsed in place: the slow path, or no deferral)
-        b->pending.clear();
-        if (pause > 0 && !b->done && b->n_records - start >= pause) {   // chunk boundary: the reader stays positioned
-            if (const int drc = drain_ingest(e, b, 0)) return fail(drc);   // (the caller may talk to the engine now: nothing is in flight)
-            if (n_records) *n_records = b->n_records;
-            return 1;
+    b->defer_parse = e->n_impl > 0;                                    // (a decode-only handle decodes in place and discards: host-ingest benchmarks)
+    auto fail = [&](int rc) { rc = drain_ingest(b, rc); e->err = b->path + ": " + b->err; return rc; };
+    try {
+        while (!b->done) {
+            const int rc = decode_next_chunk(e, b, o);
+            if (rc < 0) return fail(rc);
+            if (rc == 0) { b->done = true; break; }
+            if (!b->defer_parse) b->cur->batches.clear();
+            if (pause > 0 && !b->done && b->n_records - start >= pause) break;   // chunk boundary: the reader stays positioned
         }
-    }
-    if (const int drc = drain_ingest(e, b, 0)) return fail(drc);
+    } catch (...) { drain_ingest(b, 0); throw; }                       // (XCK_GUARD makes an error code of it: no job may stay with the push thread)
+    if (const int drc = drain_ingest(b, 0)) return fail(drc);          // (the caller may talk to the engine now: nothing is in flight)
     if (n_records) *n_records = b->n_records;
-    return XCK_OK;
+    return b->done ? XCK_OK : 1;
 }
 
 // C++ exceptions (std::bad_alloc from a buffer that a damaged file made huge, ...) must not unwind through the C ABI into
