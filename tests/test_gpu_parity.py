@@ -113,7 +113,7 @@ def test_large_scale_parity(large, mode, mats):
 
 def test_deep_nesting_spill_and_overflow_replay():
     """12 identical + 6 nested regions over every read: >12 accepted pairs per read saturates the LDS
-    set (spill through emit_global) and exceeds the 5-hits-per-read capacity estimate (overflow flag,
+    set (spill through append_one) and exceeds the 5-hits-per-read capacity estimate (overflow flag,
     buffer growth, cursor rewind and replay).  Result must still equal the oracle."""
     rng = np.random.default_rng(5)
     regions = [("1", 1000, 900000, "big%d" % i) for i in range(12)] + [("1", 1000 + 50000 * i, 400000 + 50000 * i, "n%d" % i) for i in range(6)]
@@ -362,6 +362,29 @@ def test_unmapped_flag_with_cigar_include_test():
     got, exp, st = util.engine_vs_oracle(capi.XCK_MODE_BASEFC, names, regions, [], 1, batches, excl_flag=0, min_include=0.3)
     assert exp["count"][0].tolist() == [0, 1] and exp["count"][2].tolist() == [3, 4]
     util.assert_coo_equal(got, exp, ["count"])
+
+
+@pytest.mark.parametrize("mode,mats,filt", [(capi.XCK_MODE_BASEFC, ["count"], dict(min_include=0.9)), (capi.XCK_MODE_BASEFC, ["count"], dict(min_include=20)),
+                                            (capi.XCK_MODE_BAF, ["ad", "dp", "oth"], dict())])
+@pytest.mark.parametrize("n_reads,split", [(300, None), (1324, None), (1324, 662)])
+def test_unsorted_reads(n_reads, split, mode, mats, filt):
+    """Sortedness of a batch is a speed assumption of the join, never a correctness one (tests/test_host_logic.py
+    ::test_oracle_basefc_does_not_depend_on_read_order: the expected values do not depend on the order).  300 reads are one partial
+    tile whose first read, at 150500, has region 150 as its first candidate: the waves that hold a read left of it walk the regions
+    from the contig's first one in chunks of 64, and the chunk from 128 starts left of the staged slice and ends inside it.  1324
+    reads are a full tile and a partial one - or, pushed as two batches, two partial ones - each opened by a read right of reads it holds."""
+    names, regions, snps, d = util.unsorted_case(n_reads)
+    assert (np.diff(d["pos"]) < 0).sum() > n_reads // 3
+    parts = [d] if split is None else [util.take_reads(d, np.arange(0, split)), util.take_reads(d, np.arange(split, n_reads))]
+    if split is not None:
+        parts[1]["ordinal_base"] = split
+    batches = [util.batch_from_dict(p) for p in parts]
+    got, exp, st = util.engine_vs_oracle(mode, names, regions, snps, 40, batches, **filt)
+    # the expected matrices are not trivial: ~60 % of the reads lie in a region (600 of every 1000 bases); nearly every one of them is a
+    # (region, cell, UMI) of its own for basefc, and for the pileup covers 1 - 2 SNPs of the region and shows the ref or alt base (2 of
+    # the 4) at one of them with probability ~0.65, which makes a (region, cell) entry of DP: ~0.6 n and ~0.4 n entries
+    assert len(exp["count" if mode == capi.XCK_MODE_BASEFC else "dp"][0]) > n_reads // 4
+    util.assert_coo_equal(got, exp, mats)
 
 
 def test_documented_divergences_from_the_reference_are_the_chosen_behaviour():

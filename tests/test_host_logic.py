@@ -827,3 +827,18 @@ def test_io_adapters_build_the_reference_anndata_objects(tmp_path, monkeypatch):
     for k in bio.LAYERS:
         assert np.array_equal(spio.mmread(str(tmp_path / "baf" / ("xcltk.%s.mtx" % k))).toarray(), np.asarray(a.layers[k]))
     assert open(str(tmp_path / "baf" / "xcltk.region.tsv")).read() == open(os.path.join(d, "xcltk.region.tsv")).read()
+
+
+@pytest.mark.parametrize("n_reads", [300, 1324])
+@pytest.mark.parametrize("min_include", [0.9, 20])
+def test_oracle_basefc_does_not_depend_on_read_order(oracle_lib, n_reads, min_include):
+    """What tests/test_gpu_parity.py::test_unsorted_reads expects of the engine on reads in random order is what the same reads
+    give in position order: a basefc count is a set of (region, cell, UMI), whichever read comes first."""
+    names, regions, snps, d = util.unsorted_case(n_reads)
+    kw = dict(min_mapq=20, min_len=30, incl_flag=0, excl_flag=772, no_orphan=True, min_include=min_include, min_count=1, min_maf=0, no_dup_hap=True)
+    cfg, _ = O.make_config(capi.XCK_MODE_BASEFC, names, regions, [], 40, **kw)
+    a = util.batch_from_dict(d)
+    b = util.batch_from_dict(util.take_reads(d, np.argsort(d["pos"], kind="stable")))
+    shuffled, in_order = O.run_oracle(cfg, [a[0]]), O.run_oracle(cfg, [b[0]])
+    assert len(shuffled["count"][0]) > n_reads // 4
+    util.assert_coo_equal(shuffled, in_order, ["count"])

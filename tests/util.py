@@ -51,6 +51,45 @@ def assert_coo_equal(got, exp, names):
             assert np.array_equal(g[j], e[j]), "%s.%s differs" % (k, what)
 
 
+def unsorted_case(n_reads, seed=5):
+    """Reads that are NOT position sorted, on one contig: 200 regions [1000g+1, 1000g+600], a SNP every 37 bases, 40 cells.
+    91M reads with a few 40M500N51M among them, positions uniform in [0, 200000) in random order; read 0 sits at 150500, so the
+    tile it opens has region 150 as its first candidate and holds reads left of it.  -> names, regions, snps, batch dict."""
+    rng = np.random.default_rng(seed)
+    names = ["1"]
+    regions = [("1", 1000 * g + 1, 1000 * g + 600, "g%03d" % g) for g in range(200)]
+    snps = [("1", p, "ACGT"[k % 4], "ACGT"[(k + 1) % 4], k & 1, 1 - (k & 1)) for k, p in enumerate(range(37, 200600, 37))]
+    pos = rng.integers(0, 200000, n_reads).astype(np.int32)
+    pos[0] = 150500
+    spliced = rng.random(n_reads) < 0.06
+    ncig = np.where(spliced, 3, 1).astype(np.uint32)
+    cig_off = np.zeros(n_reads + 1, np.uint32); np.cumsum(ncig, out=cig_off[1:])
+    cigar = np.zeros(int(cig_off[-1]), np.uint32)
+    cigar[cig_off[:-1][~spliced]] = (91 << 4) | 0
+    b3 = cig_off[:-1][spliced]
+    cigar[b3] = (40 << 4) | 0; cigar[b3 + 1] = (500 << 4) | 3; cigar[b3 + 2] = (51 << 4) | 0
+    nb = 46                                                              # bytes of a 91-base sequence
+    seq = (1 << rng.integers(0, 4, (n_reads * nb, 2))).astype(np.uint8)
+    d = dict(contig=0, ordinal_base=0, pos=pos, flag=np.zeros(n_reads, np.uint16), mapq=np.full(n_reads, 60, np.uint8),
+             cell=rng.integers(0, 40, n_reads).astype(np.int32), umi=((1 << 24) | rng.integers(0, 64, n_reads)).astype(np.uint64),
+             cig_off=cig_off, cigar=cigar, seq_off=(np.arange(n_reads + 1) * nb).astype(np.uint32), seq=(seq[:, 0] << 4) | seq[:, 1])
+    return names, regions, snps, d
+
+
+def take_reads(d, idx):
+    """The reads idx (an index array, in that order) of batch dict d as a batch dict of their own (ordinals restart at 0)."""
+    idx = np.asarray(idx, np.int64)
+    out = dict(contig=d["contig"], ordinal_base=0)
+    for k in ("pos", "flag", "mapq", "cell", "umi"):
+        out[k] = d[k][idx].copy()
+    for off, dat in (("cig_off", "cigar"), ("seq_off", "seq")):
+        n = (d[off][idx + 1] - d[off][idx]).astype(np.int64)
+        o = np.zeros(len(idx) + 1, np.uint32); np.cumsum(n, out=o[1:])
+        src = np.repeat(d[off][idx].astype(np.int64) - o[:-1], n) + np.arange(int(o[-1]))
+        out[off] = o; out[dat] = d[dat][src].copy()
+    return out
+
+
 # ----------------------------------------------------------------------------- golden cases
 import json
 

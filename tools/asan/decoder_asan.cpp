@@ -15,18 +15,17 @@
 #include "../../xcltk_amd/csrc/inflate_dev.h"
 
 namespace xck {   // what engine.hip provides; never reached through a decode-only handle
-int  engine_create(const xck_config*, xck_engine*) { return XCK_E_ARG; }
-void engine_destroy(xck_engine*) {}
-int  engine_push(xck_engine*, const xck_batch*, bool) { return XCK_E_ARG; }
-int  engine_flush(xck_engine*) { return XCK_E_ARG; }
-int  engine_finish(xck_engine*, xck_result*) { return XCK_E_ARG; }
-int  engine_finish_async(xck_engine*) { return XCK_E_ARG; }
-int  engine_result_device(xck_engine*, xck_result*) { return XCK_E_ARG; }
-int  engine_reset(xck_engine*) { return XCK_E_ARG; }
-int  engine_stats(const xck_engine*, xck_stats*) { return XCK_E_ARG; }
-int  engine_umi_bits(const xck_engine* e) { return e ? e->umi_bits : 0; }
-int  engine_read_fate(xck_engine*, xck_read_fate*) { return XCK_E_ARG; }
-int  engine_cell_summary(xck_engine*, xck_cell_summary*) { return XCK_E_ARG; }
+int  engine_create(const xck_config*, xck_engine*, EngineImpl**) { return XCK_E_ARG; }
+void engine_destroy(EngineImpl*) {}
+int  engine_push(EngineImpl*, const xck_batch*, bool) { return XCK_E_ARG; }
+int  engine_flush(EngineImpl*) { return XCK_E_ARG; }
+int  engine_finish(EngineImpl*, xck_result*) { return XCK_E_ARG; }
+int  engine_finish_async(EngineImpl*) { return XCK_E_ARG; }
+int  engine_result_device(EngineImpl*, xck_result*) { return XCK_E_ARG; }
+int  engine_reset(EngineImpl*) { return XCK_E_ARG; }
+int  engine_stats(const EngineImpl*, xck_stats*) { return XCK_E_ARG; }
+int  engine_read_fate(EngineImpl*, xck_read_fate*) { return XCK_E_ARG; }
+int  engine_cell_summary(EngineImpl*, xck_cell_summary*) { return XCK_E_ARG; }
 int  engine_numa_node(const xck_engine*) { return -1; }
 int  engine_device(const xck_engine*) { return -1; }                          // no device: the decoder's GPU share of the inflate never starts
 GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }

@@ -94,12 +94,10 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             if (n == 2) c.flags |= XCK_F_LAYOUT_BOTH;          // one key layout -> one decode serves both pipelines
             if (e->read_fate) c.flags |= XCK_F_READ_FATE;      // (XCK_READ_FATE=1, or implied by the per-cell table)
             if (e->cell_summary) c.flags |= XCK_F_CELL_SUMMARY;  // (XCK_CELL_SUMMARY=1)
-            e->impl = nullptr;
-            int rc = engine_create(&c, e);
-            e->impls[k] = e->impl; e->n_impl = k + 1;
+            const int rc = engine_create(&c, e, &e->impls[k]);
+            e->n_impl = k + 1;                                 // (a pipeline that failed half-way is destroyed with the rest)
             if (rc) { set_thread_error(e->err); xck_destroy(e); return rc; }
         }
-        e->impl = e->impls[0];
     }
     // decoder settings
     DecodeCfg& d = e->dec;
@@ -118,9 +116,19 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     return XCK_OK;
 }
 
-#define FOR_IMPLS(e, expr) do { if ((e)->n_impl == 0) { (e)->impl = nullptr; int rc_ = (expr); if (rc_) return rc_; }         \
-    for (int k_ = 0; k_ < (e)->n_impl; k_++) { (e)->impl = (e)->impls[k_]; int rc_ = (expr); if (rc_) { (e)->impl = (e)->impls[0]; return rc_; } } \
-    (e)->impl = (e)->impls[0]; } while (0)
+// the one answer of every call that needs a pipeline to a handle that has none
+static int no_engine(xck_engine* e) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
+// fn(pipeline) on every pipeline of the handle, up to the first error
+static int for_pipelines(xck_engine* e, const std::function<int(EngineImpl*)>& fn) {
+    if (e->n_impl <= 0) return no_engine(e);
+    for (int k = 0; k < e->n_impl; k++) if (int rc = fn(e->impls[k])) return rc;
+    return XCK_OK;
+}
+// the pipeline that xck_get_read_fate / xck_get_cell_summary ask about, or null with e->err set
+static EngineImpl* pipeline_of(xck_engine* e, int mode, const char* who) {
+    if ((mode != XCK_MODE_BASEFC && mode != XCK_MODE_BAF) || !(e->mode & mode)) { e->err = std::string(who) + ": the handle has no such pipeline"; return nullptr; }
+    return e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
+}
 
 void xck_destroy(xck_engine* e) {
     if (!e) return;
@@ -128,7 +136,7 @@ void xck_destroy(xck_engine* e) {
         if (e->push_ring.fence[k]) { fence_wait(e->push_ring.fence[k]); fence_destroy(e->push_ring.fence[k]); }
         if (e->push_ring.blk[k]) pinned_free(e->push_ring.blk[k]);
     }
-    for (int k = 0; k < e->n_impl; k++) { e->impl = e->impls[k]; engine_destroy(e); }
+    for (int k = 0; k < e->n_impl; k++) engine_destroy(e->impls[k]);
     if (e->stager) engine_release_staging(e);
     delete e;
 }
@@ -151,7 +159,7 @@ static int check_host_batch(xck_engine* e, const xck_batch* b) {
     if (bad) { e->err = "batch: offsets run backwards or a cell index is outside the cell table"; return XCK_E_ARG; }
     return XCK_OK;
 }
-extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* b) { FOR_IMPLS(e, engine_push(e, b, false)); return XCK_OK; } } }
+extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* b) { return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, false); }); } } }
 
 // xck_push_batch, one-copy form for SMALL batches: the caller's nine arrays are packed into ONE engine-owned pinned block (ring of
 // three), which crosses PCIe with ONE hipMemcpyAsync into a device staging slot shared by the handle's pipelines
@@ -163,7 +171,6 @@ extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* 
 // the packed form is used where the nine calls and the wait dominate: below XCK_PUSH_STAGE_BYTES (default 2 MB) per batch.
 // XCK_PUSH_STAGE=0 / 1 forces one form.
 static int push_staged(xck_engine* e, const xck_batch* b) {
-    if (e->n_impl <= 0) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
     const bool seq = (e->mode & XCK_MODE_BAF) != 0;
     const size_t n = (size_t)b->n_reads;
     const uint32_t c_lo = b->cig_off[0], s_lo = seq ? b->seq_off[0] : 0;
@@ -213,7 +220,7 @@ static int push_staged(xck_engine* e, const xck_batch* b) {
 int xck_push_batch(xck_engine* e, const xck_batch* b) {
     if (!e || !b) return XCK_E_ARG;
     if (int rc = check_host_batch(e, b)) return rc;
-    if (b->n_reads <= 0 || b->contig < 0 || e->n_impl <= 0) return push_trusted(e, b);     // nothing to copy / decode-only: engine_push reports
+    if (b->n_reads <= 0 || b->contig < 0 || e->n_impl <= 0) return push_trusted(e, b);     // nothing to copy / decode-only: reported there
     const int force = e->knobs.push_stage;
     const long long small = e->knobs.push_stage_bytes;
     const size_t n = (size_t)b->n_reads;
@@ -221,9 +228,15 @@ int xck_push_batch(xck_engine* e, const xck_batch* b) {
     const bool stage = force >= 0 ? force != 0 : (long long)bytes < small;
     return stage ? push_staged(e, b) : push_trusted(e, b);
 }
-int xck_push_batch_device(xck_engine* e, const xck_batch* b) { if (!e || !b) return XCK_E_ARG; FOR_IMPLS(e, engine_push(e, b, true)); return XCK_OK; }
-int xck_flush(xck_engine* e) { if (!e) return XCK_E_ARG; FOR_IMPLS(e, engine_flush(e)); return XCK_OK; }
-int xck_reset(xck_engine* e) { if (!e) return XCK_E_ARG; for (auto& v : e->dstat) v = 0; FOR_IMPLS(e, engine_reset(e)); e->gpu_inflate_chunks = 0; return XCK_OK; }
+int xck_push_batch_device(xck_engine* e, const xck_batch* b) { if (!e || !b) return XCK_E_ARG; return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, true); }); }
+int xck_flush(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_flush); }
+int xck_reset(xck_engine* e) {
+    if (!e) return XCK_E_ARG;
+    for (auto& v : e->dstat) v = 0;
+    if (int rc = for_pipelines(e, engine_reset)) return rc;
+    e->gpu_inflate_chunks = 0;
+    return XCK_OK;
+}
 
 int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
     if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
@@ -238,76 +251,54 @@ int xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out) {
     if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
     if (out->struct_size < sizeof(xck_read_fate)) { e->err = "xck_read_fate.struct_size mismatch (ABI)"; return XCK_E_ARG; }
     if (!e->read_fate || e->n_impl <= 0) { e->err = "handle made without XCK_F_READ_FATE"; return XCK_E_STATE; }
-    if ((mode != XCK_MODE_BASEFC && mode != XCK_MODE_BAF) || !(e->mode & mode)) { e->err = "xck_get_read_fate: the handle has no such pipeline"; return XCK_E_ARG; }
+    EngineImpl* im = pipeline_of(e, mode, "xck_get_read_fate");
+    if (!im) return XCK_E_ARG;
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
-    e->impl = e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
-    const int rc = engine_read_fate(e, out);
-    e->impl = e->impls[0];
-    return rc;
+    return engine_read_fate(im, out);
 }
 
 int xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out) {
     if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
     if (out->struct_size < sizeof(xck_cell_summary)) { e->err = "xck_cell_summary.struct_size mismatch (ABI)"; return XCK_E_ARG; }
     if (!e->cell_summary || e->n_impl <= 0) { e->err = "handle made without XCK_F_CELL_SUMMARY"; return XCK_E_STATE; }
-    if ((mode != XCK_MODE_BASEFC && mode != XCK_MODE_BAF) || !(e->mode & mode)) { e->err = "xck_get_cell_summary: the handle has no such pipeline"; return XCK_E_ARG; }
+    EngineImpl* im = pipeline_of(e, mode, "xck_get_cell_summary");
+    if (!im) return XCK_E_ARG;
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
-    e->impl = e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
-    const int rc = engine_cell_summary(e, out);
-    e->impl = e->impls[0];
-    return rc;
+    return engine_cell_summary(im, out);
 }
 
-int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; FOR_IMPLS(e, engine_finish_async(e)); return XCK_OK; }
+int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }
 
-int xck_finish(xck_engine* e, xck_result* out) {
-    if (!e || !out) return XCK_E_ARG;
+// the handle's result from those of its pipelines (get: engine_finish or engine_result_device): a fused handle takes the count matrix
+// of its basefc pipeline and the three allele matrices of its pileup pipeline
+static int merged_result(xck_engine* e, xck_result* out, int (*get)(EngineImpl*, xck_result*)) {
     memset(out, 0, sizeof *out);
-    if (e->n_impl == 0) { e->impl = nullptr; return engine_finish(e, out); }
-    for (int k = 0; k < e->n_impl; k++) {
+    int k = 0;
+    return for_pipelines(e, [&](EngineImpl* im) -> int {
         xck_result r;
-        e->impl = e->impls[k];
-        int rc = engine_finish(e, &r);
-        if (rc) { e->impl = e->impls[0]; return rc; }
-        if (e->mode == XCK_MODE_BOTH) { if (k == 0) out->count = r.count; else { out->ad = r.ad; out->dp = r.dp; out->oth = r.oth; } }
-        else *out = r;
-    }
-    e->impl = e->impls[0];
-    return XCK_OK;
+        if (int rc = get(im, &r)) return rc;
+        if (e->mode != XCK_MODE_BOTH) *out = r;
+        else if (k++ == 0) out->count = r.count;
+        else { out->ad = r.ad; out->dp = r.dp; out->oth = r.oth; }
+        return XCK_OK;
+    });
 }
+int xck_finish(xck_engine* e, xck_result* out) { if (!e || !out) return XCK_E_ARG; return merged_result(e, out, engine_finish); }
+int xck_get_result_device(xck_engine* e, xck_result* out) { if (!e || !out) return XCK_E_ARG; return merged_result(e, out, engine_result_device); }
 
-int xck_get_result_device(xck_engine* e, xck_result* out) {
+int xck_get_stats(const xck_engine* e, xck_stats* out) {
     if (!e || !out) return XCK_E_ARG;
-    memset(out, 0, sizeof *out);
-    if (e->n_impl == 0) { e->impl = nullptr; return engine_result_device(e, out); }
-    for (int k = 0; k < e->n_impl; k++) {
-        xck_result r;
-        e->impl = e->impls[k];
-        int rc = engine_result_device(e, &r);
-        if (rc) { e->impl = e->impls[0]; return rc; }
-        if (e->mode == XCK_MODE_BOTH) { if (k == 0) out->count = r.count; else { out->ad = r.ad; out->dp = r.dp; out->oth = r.oth; } }
-        else *out = r;
-    }
-    e->impl = e->impls[0];
-    return XCK_OK;
-}
-
-int xck_get_stats(const xck_engine* ce, xck_stats* out) {
-    if (!ce || !out) return XCK_E_ARG;
-    xck_engine* e = const_cast<xck_engine*>(ce);
     if (e->n_impl == 0) return XCK_E_STATE;
     memset(out, 0, sizeof *out);
     for (int k = 0; k < e->n_impl; k++) {
-        xck_stats s; e->impl = e->impls[k];
-        int rc = engine_stats(e, &s);
-        if (rc) { e->impl = e->impls[0]; return rc; }
+        xck_stats s;
+        if (int rc = engine_stats(e->impls[k], &s)) return rc;
         if (k == 0) *out = s;
         else { out->n_hits += s.n_hits; out->n_hits_unique += s.n_hits_unique; out->ms_h2d += s.ms_h2d; out->ms_device += s.ms_device;
                out->ms_join += s.ms_join; out->ms_sort += s.ms_sort; out->ms_d2h += s.ms_d2h; out->algo_bytes_join += s.algo_bytes_join; out->n_join_launches += s.n_join_launches; }
     }
-    e->impl = e->impls[0];
     return XCK_OK;
 }
 

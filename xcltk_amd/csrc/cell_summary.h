@@ -184,12 +184,11 @@ static int cell_marginals(EngineImpl* im, const int k) {
     return 0;
 }
 
-// xck_get_cell_summary() for the pipeline e->impl: waits for the queued work, copies the table; the matrix half runs the first
+// xck_get_cell_summary() for one pipeline: waits for the queued work, copies the table; the matrix half runs the first
 // time after a finish and is kept until the next reset (a finished handle takes no more reads)
-int engine_cell_summary(xck_engine* e, xck_cell_summary* out) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im || !im->d_cell) { e->err = "handle made without XCK_F_CELL_SUMMARY"; return XCK_E_STATE; }
-    int rc = engine_flush(e); if (rc) return rc;
+int engine_cell_summary(EngineImpl* im, xck_cell_summary* out) {
+    if (!im->d_cell) { im->eng->err = "handle made without XCK_F_CELL_SUMMARY"; return XCK_E_STATE; }
+    int rc = engine_flush(im); if (rc) return rc;
     const size_t rows = (size_t)im->n_cells + 1;
     im->h_cell_raw.resize(rows * CS_ROW_WORDS);
     HIP_TRY(hipMemcpy(im->h_cell_raw.data(), im->d_cell, im->h_cell_raw.size() * sizeof(int64_t), hipMemcpyDeviceToHost));

@@ -204,6 +204,36 @@ __device__ __forceinline__ RawRead fetch_read(const BatchDesc& d, int tile0, uin
     return w;
 }
 
+// The two pure CIGAR loops, generic over where a word comes from (word_at(c): cig_at in the join, a plain global load in
+// read_fate.h).  Reference length and aligned bases of the words [c0, c1):
+template <class WordAt>
+__device__ __forceinline__ void cigar_summary(WordAt word_at, uint32_t c0, uint32_t c1, int32_t& rlen, int32_t& n_al) {
+    for (uint32_t c = c0; c < c1; c++) {
+        uint32_t w = word_at(c); uint32_t op = w & 15u; int32_t l = int32_t(w >> 4);
+        if (op_ref(op)) rlen += l;
+        if (op_aligned(op)) n_al += l;
+    }
+}
+// __get_include_len(): aligned bases with s0 <= p < e0 (reads pos, endpos, n_al, c0, c1 and span_is_cigar of r)
+template <class WordAt>
+__device__ __forceinline__ int32_t included_len(WordAt word_at, const ReadInfo& r, int32_t s0, int32_t e0) {
+    // both shortcuts need endpos to be the CIGAR's own end (an unmapped-flagged read with a CIGAR is fetched by its first base
+    // only, yet its aligned positions are counted over the whole CIGAR)
+    if (r.span_is_cigar && r.pos >= s0 && r.endpos <= e0) return r.n_al;
+    // no D / N in the CIGAR (reference span == aligned length): the aligned bases are one block, no walk needed
+    if (r.span_is_cigar && r.endpos - r.pos == r.n_al) return max(min(r.endpos, e0) - max(r.pos, s0), 0);
+    int32_t p = r.pos, m = 0;
+    for (uint32_t c = r.c0; c < r.c1; c++) {
+        uint32_t w = word_at(c); uint32_t op = w & 15u; int32_t l = int32_t(w >> 4);
+        if (op_aligned(op)) {
+            int32_t lo = max(p, s0), hi = min(p + l, e0);
+            if (hi > lo) m += hi - lo;
+            p += l;
+        } else if (op_ref(op)) p += l;
+    }
+    return m;
+}
+
 // filter + CIGAR summary of a read (endpos = htslib bam_endpos, n_al = len(read.positions))
 template <class K, int MODE>
 __device__ __forceinline__ ReadInfo load_read(const JoinArgs<K>& a, const BatchDesc& d, const JoinSmem<K, MODE>& sm, const RawRead& w) {
@@ -222,11 +252,7 @@ __device__ __forceinline__ ReadInfo load_read(const JoinArgs<K>& a, const BatchD
     ok = ok && r.cell >= 0 && r.umi != XCK_UMI_NONE;                  // (a negative pos is kept: fetch() only asks pos < stop && endpos > start)
     if (!ok) return r;
     int32_t rlen = 0, n_al = 0;
-    for (uint32_t c = r.c0; c < r.c1; c++) {
-        uint32_t w = cig_at(a, d, sm, c); uint32_t op = w & 15u; int32_t l = int32_t(w >> 4);
-        if (op_ref(op)) rlen += l;
-        if (op_aligned(op)) n_al += l;
-    }
+    cigar_summary([&](uint32_t c) { return cig_at(a, d, sm, c); }, r.c0, r.c1, rlen, n_al);
     // htslib bam_endpos(): an unmapped-flagged read, or one without reference-consuming CIGAR, spans one base for fetch();
     // read.positions (the include test) still follows the CIGAR
     r.span_is_cigar = !((flag & BAM_FUNMAP) || r.c1 == r.c0 || rlen == 0);
@@ -237,34 +263,26 @@ __device__ __forceinline__ ReadInfo load_read(const JoinArgs<K>& a, const BatchD
     return r;
 }
 
-// __get_include_len(): aligned bases with s0 <= p < e0
-template <class K, int MODE>
-__device__ __forceinline__ int32_t included_len(const JoinArgs<K>& a, const BatchDesc& d, const JoinSmem<K, MODE>& sm, const ReadInfo& r, int32_t s0, int32_t e0) {
-    // both shortcuts need endpos to be the CIGAR's own end (an unmapped-flagged read with a CIGAR is fetched by its first base
-    // only, yet its aligned positions are counted over the whole CIGAR)
-    if (r.span_is_cigar && r.pos >= s0 && r.endpos <= e0) return r.n_al;
-    // no D / N in the CIGAR (reference span == aligned length): the aligned bases are one block, no walk needed
-    if (r.span_is_cigar && r.endpos - r.pos == r.n_al) return max(min(r.endpos, e0) - max(r.pos, s0), 0);
-    int32_t p = r.pos, m = 0;
-    for (uint32_t c = r.c0; c < r.c1; c++) {
-        uint32_t w = cig_at(a, d, sm, c); uint32_t op = w & 15u; int32_t l = int32_t(w >> 4);
-        if (op_aligned(op)) {
-            int32_t lo = max(p, s0), hi = min(p + l, e0);
-            if (hi > lo) m += hi - lo;
-            p += l;
-        } else if (op_ref(op)) p += l;
-    }
-    return m;
-}
-
-
-// append straight to HBM (slow path: LDS set/queue saturated)
-template <class K, int MODE>
-__device__ __forceinline__ void emit_global(const JoinArgs<K>& a, K key, uint64_t val) {
+// ---- appending to the sharded HBM streams (ctl_word: ctl_cursor / ctl_ncursor of the block's shard) ----
+// one record straight to HBM (slow path: the LDS set / queue is saturated)
+template <class K, bool WITH_VAL>
+__device__ __forceinline__ void append_one(const JoinArgs<K>& a, int ctl_word, K* keys, uint64_t* vals, K key, uint64_t val) {
     const int shard = JOIN_SHARD;
-    unsigned long long idx = atomicAdd(&a.ctl[ctl_cursor(shard)], 1ull);
-    if (idx < a.cap) { idx += (unsigned long long)shard * a.cap; a.keys[idx] = key; if (MODE == XCK_MODE_BAF) a.vals[idx] = val; }
+    unsigned long long idx = atomicAdd(&a.ctl[ctl_word], 1ull);
+    if (idx < a.cap) { idx += (unsigned long long)shard * a.cap; keys[idx] = key; if (WITH_VAL) vals[idx] = val; }
     else atomicExch(&a.ctl[CTL_OVERFLOW], 1ull);
+}
+// room for a fragment of `total` records: its first index in the stream, or ~0 (with the overflow flag raised) when it does not fit
+template <class K>
+__device__ __forceinline__ unsigned long long reserve_fragment(const JoinArgs<K>& a, int ctl_word, uint32_t total) {
+    unsigned long long b = 0;
+    if (total) {
+        const int shard = JOIN_SHARD;
+        b = atomicAdd(&a.ctl[ctl_word], (unsigned long long)total);
+        if (b + total > a.cap) { atomicExch(&a.ctl[CTL_OVERFLOW], 1ull); b = ~0ull; }
+        else b += (unsigned long long)shard * a.cap;
+    }
+    return b;
 }
 
 template <class K, int MODE>
@@ -283,11 +301,11 @@ __device__ __forceinline__ void emit(const JoinArgs<K>& a, JoinSmem<K, MODE>& sm
             if (prev == ~0ull || prev == kk) return;                 // new key, or a duplicate (same region, cell, UMI); no shared counter: flush points are static
             slot = (slot + stride) & (SLOTS - 1);
         }
-        emit_global<K, MODE>(a, key, val);
+        append_one<K, MODE == XCK_MODE_BAF>(a, ctl_cursor(JOIN_SHARD), a.keys, a.vals, key, val);
     } else {
         uint32_t idx = atomicAdd(&sm.count, 1u);
         if (idx < (uint32_t)JoinSmem<K, MODE>::QCAP) { sm.keys()[idx] = key; if (MODE == XCK_MODE_BAF) sm.vals()[idx] = val; }
-        else emit_global<K, MODE>(a, key, val);
+        else append_one<K, MODE == XCK_MODE_BAF>(a, ctl_cursor(JOIN_SHARD), a.keys, a.vals, key, val);
     }
 }
 
@@ -296,12 +314,7 @@ template <class K, int MODE>
 __device__ __forceinline__ void emit_nobase(const JoinArgs<K>& a, JoinSmem<K, MODE>& sm, K key, uint64_t val) {
     const uint32_t idx = atomicAdd(&sm.ncount, 1u);
     if (idx < (uint32_t)JoinSmem<K, MODE>::NQCAP) { sm.nq_key[idx] = (uint64_t)key; sm.nq_val[idx] = val; }
-    else {
-        const int shard = JOIN_SHARD;
-        unsigned long long g = atomicAdd(&a.ctl[ctl_ncursor(shard)], 1ull);
-        if (g < a.cap) { g += (unsigned long long)shard * a.cap; a.nkeys[g] = key; a.nvals[g] = val; }
-        else atomicExch(&a.ctl[CTL_OVERFLOW], 1ull);
-    }
+    else append_one<K, true>(a, ctl_ncursor(JOIN_SHARD), a.nkeys, a.nvals, key, val);
 }
 // phase stamps of the join kernel (build with -DXCK_STAMPS=1): cycles of wave 0 of every block between two stamps, kept in
 // registers and stored over the block's own TileMeta record (12 words, read in the prologue and dead since) - no atomics, no
@@ -319,14 +332,7 @@ template <class K, int MODE>
 __device__ __forceinline__ void flush_split(const JoinArgs<K>& a, JoinSmem<K, MODE>& sm, StampRec* ts = nullptr) {   // block-wide; all inserts are complete (barrier before)
     const uint32_t tb = min(sm.count, (uint32_t)JoinSmem<K, MODE>::QCAP), tn = min(sm.ncount, (uint32_t)JoinSmem<K, MODE>::NQCAP);
     if (threadIdx.x < 2) {
-        const uint32_t total = threadIdx.x ? tn : tb;
-        unsigned long long b = 0;
-        if (total) {
-            const int shard = JOIN_SHARD;
-            b = atomicAdd(&a.ctl[threadIdx.x ? ctl_ncursor(shard) : ctl_cursor(shard)], (unsigned long long)total);
-            if (b + total > a.cap) { atomicExch(&a.ctl[CTL_OVERFLOW], 1ull); b = ~0ull; }
-            else b += (unsigned long long)shard * a.cap;
-        }
+        const unsigned long long b = reserve_fragment(a, threadIdx.x ? ctl_ncursor(JOIN_SHARD) : ctl_cursor(JOIN_SHARD), threadIdx.x ? tn : tb);
         if (threadIdx.x) sm.nbase = b; else sm.base = b;
     }
     __syncthreads();
@@ -355,15 +361,8 @@ __device__ __forceinline__ void flush(const JoinArgs<K>& a, JoinSmem<K, MODE>& s
         __syncthreads();
         XCK_STAMP(ts, 8);
         if (threadIdx.x == 0) {
-            uint32_t total = sm.wcnt[0] + sm.wcnt[1] + sm.wcnt[2] + sm.wcnt[3];
-            unsigned long long b = 0;
-            if (total) {
-                const int shard = JOIN_SHARD;
-                b = atomicAdd(&a.ctl[ctl_cursor(shard)], (unsigned long long)total);
-                if (b + total > a.cap) { atomicExch(&a.ctl[CTL_OVERFLOW], 1ull); b = ~0ull; }
-                else b += (unsigned long long)shard * a.cap;
-            }
-            sm.base = b; sm.count = 0;
+            sm.base = reserve_fragment(a, ctl_cursor(JOIN_SHARD), sm.wcnt[0] + sm.wcnt[1] + sm.wcnt[2] + sm.wcnt[3]);
+            sm.count = 0;
         }
         __syncthreads();
         XCK_STAMP(ts, 9);
@@ -388,16 +387,7 @@ __device__ __forceinline__ void flush(const JoinArgs<K>& a, JoinSmem<K, MODE>& s
     } else {
         __syncthreads();
         const uint32_t total = min(sm.count, (uint32_t)JoinSmem<K, MODE>::QCAP);
-        if (threadIdx.x == 0) {
-            unsigned long long b = 0;
-            if (total) {
-                const int shard = JOIN_SHARD;
-                b = atomicAdd(&a.ctl[ctl_cursor(shard)], (unsigned long long)total);
-                if (b + total > a.cap) { atomicExch(&a.ctl[CTL_OVERFLOW], 1ull); b = ~0ull; }
-                else b += (unsigned long long)shard * a.cap;
-            }
-            sm.base = b;
-        }
+        if (threadIdx.x == 0) sm.base = reserve_fragment(a, ctl_cursor(JOIN_SHARD), total);
         __syncthreads();
         const unsigned long long dst = sm.base;
         if (dst != ~0ull)
@@ -417,7 +407,9 @@ __device__ __forceinline__ void flush(const JoinArgs<K>& a, JoinSmem<K, MODE>& s
 // region that starts at or after the end of every read of the wave (one ballot per step, no reduction).  Start, end and row of a region are wave-uniform (LDS
 // broadcast reads of the staged slice); each lane only compares its own read against them - no per-lane index lookups,
 // no divergent loop counts.  A wave that holds a read left of the tile's first read (unsorted input) scans from the
-// contig's first region, so sortedness is a speed assumption, never a correctness one.
+// contig's first region: its chunks left of the staged slice [lb, lb + n_st) take start / end / row from global memory, lane
+// by lane (`whole` below is false for them), so sortedness is a speed assumption, never a correctness one
+// (tests/test_gpu_parity.py::test_unsorted_reads).
 // minimum / maximum of one int32 per lane over the 64 lanes of a wave (all lanes active): four row_shr steps inside the rows
 // of 16 lanes, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3 - lane 63 then holds the result.  Six DPP
 // VALU ops and one v_readlane; no LDS traffic (a __shfl_xor butterfly is six ds_bpermute round trips).
@@ -461,8 +453,10 @@ __device__ __forceinline__ uint32_t join_regions(const JoinArgs<K>& a, const Bat
     for (int32_t kb = __ballot(r.ok && r.pos < p_first) ? reg_lo : lb; kb < reg_hi; kb += 64) {
         const int32_t k = kb + lane;
         const uint32_t rel = (uint32_t)(k - lb);
-        // (scalar: the whole chunk is staged and inside the contig - the usual case; the per-lane form below is the general one)
-        const bool whole = (uint32_t)(kb - lb) + 64u <= (uint32_t)n_st && kb + 64 <= reg_hi;
+        // (scalar: the whole chunk is staged and inside the contig - the usual case; the per-lane form below is the general one.
+        // kb < lb happens on the walk from reg_lo: a chunk that starts up to 63 regions left of the staged slice is not "whole",
+        // although (uint32_t)(kb - lb) + 64 wraps to a small number)
+        const bool whole = kb >= lb && (uint32_t)(kb - lb) + 64u <= (uint32_t)n_st && kb + 64 <= reg_hi;
         bool in = true, staged = true;
         int32_t s0 = std::numeric_limits<int32_t>::max(), e0 = std::numeric_limits<int32_t>::min(), row = 0;
         if (whole) { s0 = sm.st_a[rel]; e0 = sm.st_b[rel]; }
@@ -485,7 +479,7 @@ __device__ __forceinline__ uint32_t join_regions(const JoinArgs<K>& a, const Bat
                 continue;
             }
             if (!(r.ok && r.pos < re0 && r.endpos > rs0)) continue;  // htslib fetch overlap
-            const int32_t m = included_len(a, d, sm, r, rs0, re0);
+            const int32_t m = included_len([&](uint32_t c) { return cig_at(a, d, sm, c); }, r, rs0, re0);
             if (a.f.frac_mode) {
                 if (r.n_al <= 0) continue;
                 // m == n gives exactly 1.0, never below a threshold in (0,1): skip the fp64 divide
@@ -528,6 +522,12 @@ __device__ __forceinline__ int32_t lower_snp(const JoinArgs<K>& a, const BatchDe
     }
     return lower_snp_tail<K, MODE>(a, d, k, x);
 }
+// base of a read at query offset qi: the allele nibble of its 4-bit sequence [s0, s0 + sl), or -1 where no sequence is stored for that offset
+__device__ __forceinline__ int base_at(const BatchDesc& d, uint32_t s0, uint32_t sl, int32_t qi) {
+    int al = -1;
+    if ((uint32_t)(qi >> 1) < sl) { const uint32_t by = as_global(d.seq)[s0 + (uint32_t)(qi >> 1)]; al = (qi & 1) ? int(by & 15u) : int(by >> 4); }
+    return al;
+}
 // One read whose reference span is not one aligned block (N / D gaps, no CIGAR span, unmapped flag): the pileup of
 // baf/fc/mcount.py:109-127 + utils/sam.py:4-40 over its CIGAR.  SNPs under aligned blocks are hits with a base (fetched
 // here: these reads are few); the SNPs inside a gap - where the read holds the key but shows no base - leave as ONE range
@@ -539,7 +539,6 @@ __device__ __forceinline__ uint32_t pileup_complex(const JoinArgs<K>& a, const B
                                                    uint32_t c0, uint32_t c1, int32_t cell, uint64_t umi, uint32_t s0, uint32_t sl, int32_t idx) {
     const int32_t w_lo = max(pos, 0) >> WSS;
     if (w_lo >= d.n_swin) return 0;
-    constexpr uint64_t AL_MASK = (uint64_t)((1u << ALLELE_BITS) - 1);
     const int32_t k_w = (uint32_t)(w_lo - sm.w0) < (uint32_t)sm.nw ? sm.st_w[w_lo - sm.w0] : as_global(d.snp_win)[w_lo];
     int32_t k = lower_snp<K, MODE>(a, d, sm, k_w, pos);
     const uint64_t ordv = (d.ordinal_base + (uint64_t)idx) << ALLELE_BITS;
@@ -559,8 +558,7 @@ __device__ __forceinline__ uint32_t pileup_complex(const JoinArgs<K>& a, const B
             if (op_aligned(op)) {
                 for (int32_t kk = k; kk < k2; kk++) {
                     const int32_t qi = q + (snp_p0<K, MODE>(a, sm, kk) - rp);
-                    int al = -1;
-                    if ((uint32_t)(qi >> 1) < sl) { const uint32_t by = as_global(d.seq)[s0 + (uint32_t)(qi >> 1)]; al = (qi & 1) ? int(by & 15u) : int(by >> 4); }
+                    const int al = base_at(d, s0, sl, qi);
                     const K key = a.kl.make((uint32_t)kk, (uint32_t)cell, umi);
                     if (JoinSmem<K, MODE>::SPLIT && al < 0) emit_nobase<K, MODE>(a, sm, key, ordv);
                     else emit<K, MODE>(a, sm, key, ordv | (uint64_t)(al + 1));
@@ -575,7 +573,6 @@ __device__ __forceinline__ uint32_t pileup_complex(const JoinArgs<K>& a, const B
         const int32_t k2 = lower_snp<K, MODE>(a, d, sm, k, endpos);
         if (k2 > k) gap(k, k2);
     }
-    (void)AL_MASK;
     return n;
 }
 
@@ -590,7 +587,7 @@ __global__ __launch_bounds__(256) void k_tile_meta(BatchTable bt, TileMeta* __re
     TileMeta m;
     m.b = lo; m.r0 = (t - d.tile0) * TILE; m.r1 = min(m.r0 + TILE, d.n); m.pad = 0;
     const uint32_t c_lo = as_global(d.cig_off)[m.r0], c_hi = as_global(d.cig_off)[m.r1];
-    const int32_t p_first = max(as_global(d.pos)[m.r0], 0), p_last = max(as_global(d.pos)[m.r1 - 1], 0);
+    const int32_t p_first = max(as_global(d.pos)[m.r0], 0);
     m.c_lo = c_lo; m.cg_n = min(c_hi - c_lo, (uint32_t)CigCap<MODE>::value); m.pad = c_hi - c_lo <= (uint32_t)CigCap<MODE>::value ? 1 : 0;
     m.w0 = p_first >> WSS; m.nw = 0; m.e0 = 0; m.n_ent = 0; m.k0 = 0; m.nk = 0;
     if (MODE == XCK_MODE_BASEFC) {
@@ -600,51 +597,122 @@ __global__ __launch_bounds__(256) void k_tile_meta(BatchTable bt, TileMeta* __re
         int32_t lo = d.reg_lo, hi = d.reg_hi;
         while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (as_global(rpmax)[mid] > p0) hi = mid; else lo = mid + 1; }
         m.e0 = lo; m.n_ent = min(d.reg_hi - lo, ST_CAP); m.k0 = p0;
-        (void)p_last;
     } else {
         if (m.w0 < d.n_swin) { m.k0 = as_global(d.snp_win)[m.w0]; m.nk = min(d.snp_end - m.k0, ST_CAP); m.nw = min(d.n_swin - m.w0, ST_WIN); }
     }
     out[t] = m;
 }
 
-// (64-bit pileup: asked to stay at 80 VGPRs, i.e. 6 waves per SIMD beside its 26.5 KB of LDS; the others have room anyway, and the
-// 128-bit pileup kernel would spill under that bound)
+// ---- the pileup walk of one sweep: the counterpart of join_regions() ----
+// the bases of the pairs a wave has parked (pr_n of them, wave-uniform) are fetched together and leave as hits; the segment is free again
 template <class K, int MODE>
-__global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((sizeof(K) == 8 && MODE == XCK_MODE_BAF) ? 6 : 4, 8))) void k_join(JoinArgs<K> a) {
-    __shared__ JoinSmem<K, MODE> sm;
-    const int tid = threadIdx.x, lane = tid & 63;
-    StampRec t_s0;
-#if XCK_STAMPS
-    for (int q = 0; q < 12; q++) t_s0.d[q] = 0;
-    t_s0.t = clock64();
-#endif
-#define STAMP(slot) XCK_STAMP(&t_s0, slot)
-    // ---- prologue: one record from k_tile_meta, then ONE round of independent loads ----
-    const XCK_GLOBAL TileMeta* mp = as_global(a.meta) + blockIdx.x;
-    const uint32_t c_lo = mp->c_lo, cg_n = mp->cg_n;
-    const int32_t w0 = mp->w0, nw = mp->nw, e0 = mp->e0, n_ent = mp->n_ent, k0 = mp->k0, nk = mp->nk;
-    const int b = __builtin_amdgcn_readfirstlane(mp->b);
-    const int tile0 = __builtin_amdgcn_readfirstlane(mp->r0);
-    const BatchDesc& d = a.bt.desc[b];                                // kernarg: scalar loads through the constant cache
-    const int32_t u_lb = __builtin_amdgcn_readfirstlane(e0), u_nst = __builtin_amdgcn_readfirstlane(n_ent), u_p0 = __builtin_amdgcn_readfirstlane(k0);   // basefc: the tile's region slice as scalars
-    unsigned long long uor = 0;
-    STAMP(0);
-    RawRead W[TILE_ITEMS];
-    if (__builtin_amdgcn_readfirstlane(tile0 + TILE <= d.n)) {        // a full tile (all but the last of a batch): no per-lane bounds
-#pragma unroll
-        for (int j = 0; j < TILE_ITEMS; j++) W[j] = fetch_read<MODE == XCK_MODE_BAF>(d, tile0, (uint32_t)(j * JOIN_BLOCK + tid), true);
-    } else {
-#pragma unroll
-        for (int j = 0; j < TILE_ITEMS; j++) W[j] = fetch_read<MODE == XCK_MODE_BAF>(d, tile0, (uint32_t)(j * JOIN_BLOCK + tid), tile0 + j * JOIN_BLOCK + tid < d.n);
-    }                                                                 // the whole tile's loads fly during the staging
+__device__ __forceinline__ void drain(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, int& pr_n) {
+    const int lane = threadIdx.x & 63, wb = threadIdx.x & ~63;          // wb: first slot of this wave's segment
+    constexpr uint64_t AL_MASK = (uint64_t)((1u << ALLELE_BITS) - 1);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < pr_n) {
+        const int u = wb + lane;
+        const int al = base_at(d, sm.pk_s0[u], sm.pk_sl[u], sm.pk_qi[u]);   // -1: key held, no base
+        const K key = a.kl.make((uint32_t)sm.pk_k[u], (uint32_t)sm.pk_cell[u], sm.pk_umi[u]);
+        const uint64_t val = ((d.ordinal_base + (uint64_t)sm.pk_idx[u]) << ALLELE_BITS) | (uint64_t)(al + 1);
+        if (JoinSmem<K, MODE>::SPLIT && al < 0) emit_nobase<K, MODE>(a, sm, key, val & ~AL_MASK);   // a record of one SNP
+        else emit<K, MODE>(a, sm, key, val);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+    pr_n = 0;
+}
+
+// read x SNP join, SNP-major: the 64 reads of a wave are (in a sorted BAM) a narrow position range, so the wave walks the few
+// SNPs of that range TOGETHER - position of SNP k is wave-uniform, every lane only asks "inside my read?" - instead of every
+// read searching the SNP table for itself (two or three binary searches per read, most of them to learn that a 91-base read
+// covers no SNP).  A hit parks its (SNP, query offset) pair in the wave's LDS segment; the bases of the parked pairs are
+// fetched together later (drain: one HBM latency per batch, not per hit).  i = the read's index in its batch; pr_n = parked
+// pairs of this wave, wave-uniform state that lives across the sweeps; last_sweep: drain what is parked and walk the tile's
+// set-aside reads.  Returns the (read, SNP) pairs of this lane.
+template <class K, int MODE>
+__device__ __forceinline__ uint32_t pileup_sweep(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, const ReadInfo& r, const RawRead& cur,
+                                                 const int i, int& pr_n, const bool last_sweep) {
+    const int tid = threadIdx.x, wb = tid & ~63;
+    uint32_t c = 0, n_gap = 0;
+    // reads whose reference span is ONE aligned block (no N / D; 85 % of a 10x run) take the wave-uniform walk below; the
+    // others are set aside in LDS and walked together after the last sweep (pileup_complex)
+    const bool simple = r.ok && r.span_is_cigar && r.endpos - r.pos == r.n_al;
+    const unsigned long long cxm = __ballot(r.ok && !simple);
+    if (cxm) {
+        uint32_t base = 0;
+        if ((tid & 63) == 0) base = atomicAdd(&sm.cx_n, (uint32_t)__popcll(cxm));
+        base = __builtin_amdgcn_readfirstlane(base);
+        if (r.ok && !simple) {
+            const uint32_t u = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(cxm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cxm, 0u));
+            if (u < (uint32_t)JoinSmem<K, MODE>::CXCAP) {
+                sm.cx_pos[u] = r.pos; sm.cx_end[u] = r.endpos; sm.cx_c0[u] = r.c0; sm.cx_c1[u] = r.c1; sm.cx_cell[u] = r.cell; sm.cx_umi[u] = r.umi;
+                sm.cx_s0[u] = cur.s0; sm.cx_sl[u] = cur.s1 - cur.s0; sm.cx_idx[u] = i;
+            } else n_gap += pileup_complex<K, MODE>(a, d, sm, r.pos, r.endpos, r.c0, r.c1, r.cell, r.umi, cur.s0, cur.s1 - cur.s0, i);   // list full: walk it here
+        }
+    }
+    if (__ballot(simple)) {                                         // wave-uniform
+        // first SNP to look at: the 1 kb window of the wave's first read (lane 0 exists whenever any lane does); a read
+        // left of it means unsorted input - then the contig's SNPs are walked from the start (speed, never correctness)
+        const int32_t p_w = __builtin_amdgcn_readfirstlane(cur.pos);
+        int32_t k;
+        if (__ballot(simple && r.pos < p_w)) k = d.n_swin > 0 ? as_global(d.snp_win)[0] : d.snp_end;
+        else { const int32_t w = max(p_w, 0) >> WSS;
+               k = w >= d.n_swin ? d.snp_end : ((uint32_t)(w - sm.w0) < (uint32_t)sm.nw ? sm.st_w[w - sm.w0] : as_global(d.snp_win)[w]); }
+        k = __builtin_amdgcn_readfirstlane(k);
+        for (; k < d.snp_end; k++) {
+            const int32_t p = __builtin_amdgcn_readfirstlane(snp_p0<K, MODE>(a, sm, k));
+            const bool reach = simple && p < r.endpos;
+            if (!__ballot(reach)) break;                            // SNPs are sorted: no read of the wave reaches this or any later one
+            const bool hit = reach && p >= r.pos;
+            const unsigned long long am = __ballot(hit);
+            if (!am) continue;
+            int32_t qi = p - r.pos;                                 // one aligned op: query offset = reference offset
+            if (hit && r.c1 - r.c0 != 1) {                          // I / S / H / P around the aligned blocks shift the query offset
+                int32_t rp = r.pos, q = 0;
+                for (uint32_t cc = r.c0; cc < r.c1; cc++) {
+                    const uint32_t w = cig_at(a, d, sm, cc); const uint32_t op = w & 15u; const int32_t l = int32_t(w >> 4);
+                    if (op_aligned(op)) { if (p < rp + l) { qi = q + (p - rp); break; } rp += l; q += l; }
+                    else if (op == 1u || op == 4u) q += l;
+                }
+            }
+            const int n_new = __popcll(am);
+            if (pr_n + n_new > 64) drain<K, MODE>(a, d, sm, pr_n);
+            if (hit) {
+                const int u = wb + pr_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+                sm.pk_k[u] = k; sm.pk_qi[u] = qi; sm.pk_cell[u] = r.cell; sm.pk_umi[u] = r.umi; sm.pk_s0[u] = cur.s0; sm.pk_sl[u] = cur.s1 - cur.s0; sm.pk_idx[u] = i;
+                c++;
+            }
+            pr_n += n_new;
+        }
+    }
+    if (last_sweep) {
+        if (pr_n) drain<K, MODE>(a, d, sm, pr_n);
+        // the set-aside reads of the whole tile, one per thread: full waves of long walks instead of one long walk per wave and sweep
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        const uint32_t cx_n = min(sm.cx_n, (uint32_t)JoinSmem<K, MODE>::CXCAP);
+        for (uint32_t u = tid; u < cx_n; u += JOIN_BLOCK)
+            n_gap += pileup_complex<K, MODE>(a, d, sm, sm.cx_pos[u], sm.cx_end[u], sm.cx_c0[u], sm.cx_c1[u], sm.cx_cell[u], sm.cx_umi[u], sm.cx_s0[u], sm.cx_sl[u], sm.cx_idx[u]);
+    }
+    return c + n_gap;
+}
+
+// ---- the pieces of k_join around the sweeps ----
+// Staging: the empty set / queues, the tile's facts (m: its record from k_tile_meta), its CIGAR run and its slice of the region /
+// SNP tables go to LDS.  Every global load is issued BEFORE the first LDS store: written as load/store loops the compiler waits
+// (s_waitcnt vmcnt(0)) inside each iteration, which serialised ~7 HBM round trips per tile.  u_lb: the first staged region, a scalar.
+template <class K, int MODE>
+__device__ __forceinline__ void stage_tile(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, const TileMeta& m, const int32_t u_lb) {
+    const int tid = threadIdx.x;
+    const uint32_t c_lo = m.c_lo, cg_n = m.cg_n;
+    const int32_t w0 = m.w0, nw = m.nw, e0 = m.e0, n_ent = m.n_ent, k0 = m.k0, nk = m.nk;
     if constexpr (JoinSmem<K, MODE>::USE_SET) {
         unsigned long long* set = sm.hkeys();                         // all ones = empty
         for (int s = tid; s < JoinSmem<K, MODE>::SLOTS; s += JOIN_BLOCK) set[s] = ~0ull;
     }
-    if (tid == 0) { sm.count = 0; sm.ncount = 0; sm.cx_n = 0; sm.cg_lo = c_lo; sm.cg_n = cg_n; sm.cg_all = mp->pad; sm.k0 = k0; sm.nk = nk;
+    if (tid == 0) { sm.count = 0; sm.ncount = 0; sm.cx_n = 0; sm.cg_lo = c_lo; sm.cg_n = cg_n; sm.cg_all = m.pad; sm.k0 = k0; sm.nk = nk;
                     if (MODE == XCK_MODE_BASEFC) { sm.w0 = e0; sm.nw = n_ent; } else { sm.w0 = w0; sm.nw = nw; } }
-    // Every global load of the prologue is issued BEFORE the first LDS store: written as load/store loops the
-    // compiler waits (s_waitcnt vmcnt(0)) inside each iteration, which serialised ~7 HBM round trips per tile.
     static_assert(ST_CAP <= JOIN_BLOCK && ST_WIN + 1 <= JOIN_BLOCK, "staging assumes one element per thread");
     constexpr int CG_IT = (CigCap<MODE>::value + JOIN_BLOCK - 1) / JOIN_BLOCK;
     uint32_t cw[CG_IT];
@@ -667,140 +735,17 @@ __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((siz
         if (tid < nk) sm.st_a[tid] = g_a;
         if (tid < nw) sm.st_w[tid] = g_w;
     }
-    STAMP(1);
-    __syncthreads();
-    STAMP(2);
-    // ---- TILE_ITEMS coalesced sweeps over the tile (the reads were requested in the prologue) ----
-    uint32_t acc = 0;
-    int pr_n = 0;                                                     // pileup: parked pairs of this wave (wave-uniform)
-    // sweeps between two flushes: keep the expected fill (256 reads x ~2 pairs per sweep) under half the set / queue
-    constexpr int CAP_ENTRIES = JoinSmem<K, MODE>::USE_SET ? JoinSmem<K, MODE>::SLOTS : JoinSmem<K, MODE>::QCAP;
-    // set mode: the de-duplicated fill of a 1024-read tile is a few hundred keys, so flush once, at the end
-    // (better de-duplication, half the cursor atomics); saturation still spills correctly through emit_global()
-#ifndef XCK_SET_FLUSH_EVERY
-#define XCK_SET_FLUSH_EVERY TILE_ITEMS
-#endif
-    constexpr int FLUSH_EVERY = JoinSmem<K, MODE>::USE_SET ? XCK_SET_FLUSH_EVERY : JoinSmem<K, MODE>::SPLIT ? TILE_ITEMS
-                              : ((CAP_ENTRIES / 2 / (JOIN_BLOCK * 2)) < 1 ? 1 : (CAP_ENTRIES / 2 / (JOIN_BLOCK * 2)));
-#pragma unroll
-    for (int j = 0; j < TILE_ITEMS; j++) {
-        const int i = tile0 + j * JOIN_BLOCK + tid;
-        const RawRead cur = W[j];
-        ReadInfo r = load_read<K, MODE>(a, d, sm, cur);
-#if XCK_STAMPS == 2
-        if (j == 0) { uint32_t x_ = (uint32_t)r.endpos ^ (uint32_t)r.n_al; asm volatile("" :: "v"(x_)); STAMP(3); }   // (the summary is complete)
-#endif
-        if constexpr (MODE == XCK_MODE_BAF) {
-            // read x SNP join, SNP-major: the 64 reads of a wave are (in a sorted BAM) a narrow position range, so the wave
-            // walks the few SNPs of that range TOGETHER - position of SNP k is wave-uniform, every lane only asks "inside my
-            // read?" - instead of every read searching the SNP table for itself (two or three binary searches per read, most of
-            // them to learn that a 91-base read covers no SNP).  A hit parks its (SNP, query offset) pair in the wave's LDS
-            // segment; the bases of the parked pairs are fetched together later (one HBM latency per batch, not per hit).
-            uint32_t c = 0, n_gap = 0;
-            const int wb = tid & ~63;                                       // first slot of this wave's segment
-            constexpr uint64_t AL_MASK = (uint64_t)((1u << ALLELE_BITS) - 1);
-            auto drain = [&]() {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();
-                if (lane < pr_n) {
-                    const int u = wb + lane;
-                    const int32_t qi = sm.pk_qi[u];
-                    int al = -1;                                            // no sequence stored for that offset: key held, no base
-                    if ((uint32_t)(qi >> 1) < sm.pk_sl[u]) { const uint32_t by = as_global(d.seq)[sm.pk_s0[u] + (uint32_t)(qi >> 1)]; al = (qi & 1) ? int(by & 15u) : int(by >> 4); }
-                    const K key = a.kl.make((uint32_t)sm.pk_k[u], (uint32_t)sm.pk_cell[u], sm.pk_umi[u]);
-                    const uint64_t val = ((d.ordinal_base + (uint64_t)sm.pk_idx[u]) << ALLELE_BITS) | (uint64_t)(al + 1);
-                    if (JoinSmem<K, MODE>::SPLIT && al < 0) emit_nobase<K, MODE>(a, sm, key, val & ~AL_MASK);   // a record of one SNP
-                    else emit<K, MODE>(a, sm, key, val);
-                }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                __builtin_amdgcn_wave_barrier();                            // the segment is free again
-                pr_n = 0;
-            };
-            // reads whose reference span is ONE aligned block (no N / D; 85 % of a 10x run) take the wave-uniform walk below; the
-            // others are set aside in LDS and walked together after the last sweep (pileup_complex)
-            const bool simple = r.ok && r.span_is_cigar && r.endpos - r.pos == r.n_al;
-            const unsigned long long cxm = __ballot(r.ok && !simple);
-            if (cxm) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(&sm.cx_n, (uint32_t)__popcll(cxm));
-                base = __builtin_amdgcn_readfirstlane(base);
-                if (r.ok && !simple) {
-                    const uint32_t u = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(cxm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cxm, 0u));
-                    if (u < (uint32_t)JoinSmem<K, MODE>::CXCAP) {
-                        sm.cx_pos[u] = r.pos; sm.cx_end[u] = r.endpos; sm.cx_c0[u] = r.c0; sm.cx_c1[u] = r.c1; sm.cx_cell[u] = r.cell; sm.cx_umi[u] = r.umi;
-                        sm.cx_s0[u] = cur.s0; sm.cx_sl[u] = cur.s1 - cur.s0; sm.cx_idx[u] = i;
-                    } else n_gap += pileup_complex<K, MODE>(a, d, sm, r.pos, r.endpos, r.c0, r.c1, r.cell, r.umi, cur.s0, cur.s1 - cur.s0, i);   // list full: walk it here
-                }
-            }
-            if (__ballot(simple)) {                                         // wave-uniform
-                // first SNP to look at: the 1 kb window of the wave's first read (lane 0 exists whenever any lane does); a read
-                // left of it means unsorted input - then the contig's SNPs are walked from the start (speed, never correctness)
-                const int32_t p_w = __builtin_amdgcn_readfirstlane(cur.pos);
-                int32_t k;
-                if (__ballot(simple && r.pos < p_w)) k = d.n_swin > 0 ? as_global(d.snp_win)[0] : d.snp_end;
-                else { const int32_t w = max(p_w, 0) >> WSS;
-                       k = w >= d.n_swin ? d.snp_end : ((uint32_t)(w - sm.w0) < (uint32_t)sm.nw ? sm.st_w[w - sm.w0] : as_global(d.snp_win)[w]); }
-                k = __builtin_amdgcn_readfirstlane(k);
-                for (; k < d.snp_end; k++) {
-                    const int32_t p = __builtin_amdgcn_readfirstlane(snp_p0<K, MODE>(a, sm, k));
-                    const bool reach = simple && p < r.endpos;
-                    if (!__ballot(reach)) break;                            // SNPs are sorted: no read of the wave reaches this or any later one
-                    const bool hit = reach && p >= r.pos;
-                    const unsigned long long am = __ballot(hit);
-                    if (!am) continue;
-                    int32_t qi = p - r.pos;                                 // one aligned op: query offset = reference offset
-                    if (hit && r.c1 - r.c0 != 1) {                          // I / S / H / P around the aligned blocks shift the query offset
-                        int32_t rp = r.pos, q = 0;
-                        for (uint32_t cc = r.c0; cc < r.c1; cc++) {
-                            const uint32_t w = cig_at(a, d, sm, cc); const uint32_t op = w & 15u; const int32_t l = int32_t(w >> 4);
-                            if (op_aligned(op)) { if (p < rp + l) { qi = q + (p - rp); break; } rp += l; q += l; }
-                            else if (op == 1u || op == 4u) q += l;
-                        }
-                    }
-                    const int n_new = __popcll(am);
-                    if (pr_n + n_new > 64) drain();
-                    if (hit) {
-                        const int u = wb + pr_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
-                        sm.pk_k[u] = k; sm.pk_qi[u] = qi; sm.pk_cell[u] = r.cell; sm.pk_umi[u] = r.umi; sm.pk_s0[u] = cur.s0; sm.pk_sl[u] = cur.s1 - cur.s0; sm.pk_idx[u] = i;
-                        c++;
-                    }
-                    pr_n += n_new;
-                }
-            }
-            if (j + 1 == TILE_ITEMS) {
-                if (pr_n) drain();
-                // the set-aside reads of the whole tile, one per thread: full waves of long walks instead of one long walk per wave and sweep
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                const uint32_t cx_n = min(sm.cx_n, (uint32_t)JoinSmem<K, MODE>::CXCAP);
-                for (uint32_t u = tid; u < cx_n; u += JOIN_BLOCK)
-                    n_gap += pileup_complex<K, MODE>(a, d, sm, sm.cx_pos[u], sm.cx_end[u], sm.cx_c0[u], sm.cx_c1[u], sm.cx_cell[u], sm.cx_umi[u], sm.cx_s0[u], sm.cx_sl[u], sm.cx_idx[u]);
-            }
-            if (r.ok) uor |= r.umi;                                   // (finish() puts the haplotype class of the region-level keys into UMI-field bits no code uses)
-            acc += c + n_gap;
-        } else {
-            if (r.ok) uor |= r.umi;
-            acc += join_regions<K, MODE>(a, d, sm, r, u_lb, u_nst, u_p0, &t_s0, j);   // wave-uniform call: the sweep over the regions is shared by all 64 lanes
-        }
-        // Flush points are fixed at compile time, never decided from sm.count: a count-based decision read
-        // after the barrier races with the next sweep's inserts (threads could disagree and split at the
-        // barriers inside flush()).  A set / queue that saturates between two flush points spills through
-        // emit_global(), which is always correct.
-#if XCK_STAMPS == 2
-        if (j == 0) STAMP(5); else STAMP(6);                          // sweep 0 in three parts (3 read summary, 4 chunk scan, 5 candidates), 6 = sweeps 1-3
-#else
-        STAMP(3 + j);
-#endif
-        if ((j + 1) % FLUSH_EVERY == 0 || j + 1 == TILE_ITEMS) {
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: global prefetches stay in flight
-            STAMP(7);
-            if constexpr (JoinSmem<K, MODE>::SPLIT) flush_split<K, MODE>(a, sm, &t_s0); else flush<K, MODE>(a, sm, &t_s0);
-        }
-    }
-    // accepted (read, region|SNP) pairs before the LDS de-duplication: the algorithmic unit of the join
+}
+
+// The tile's totals, one atomic each per block on the shard cursor's cache line (a single shared word serialises at ~90 atomics/us):
+// acc = accepted (read, region|SNP) pairs before the LDS de-duplication, the algorithmic unit of the join; uor = OR of the UMI codes of
+// the accepted reads (highest UMI-code bit in use: the radix-sort fold drops the dead bits between the UMI codes and the cell field)
+template <class K, int MODE>
+__device__ __forceinline__ void publish_tile_totals(const JoinArgs<K>& a, JoinSmem<K, MODE>& sm, uint32_t acc, unsigned long long uor) {
+    const int tid = threadIdx.x, lane = tid & 63;
 #pragma unroll
     for (int dd = 32; dd >= 1; dd >>= 1) acc += __shfl_xor(acc, dd, 64);
     {
-        // highest UMI-code bit in use: the radix-sort fold drops the dead bits between the UMI codes and the cell field before the sort
         uint32_t ulo = (uint32_t)uor, uhi = (uint32_t)(uor >> 32);
 #pragma unroll
         for (int dd = 32; dd >= 1; dd >>= 1) { ulo |= __shfl_xor(ulo, dd, 64); uhi |= __shfl_xor(uhi, dd, 64); }
@@ -812,11 +757,83 @@ __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((siz
         uor = 0;
 #pragma unroll
         for (int w = 0; w < JOIN_BLOCK / 64; w++) uor |= ((unsigned long long)sm.wuor[2 * w + 1] << 32) | sm.wuor[2 * w];
-        // one word per shard, on the shard cursor's cache line (a single shared word serialises at ~90 atomics/us)
         if (uor) atomicOr(&a.ctl[ctl_umi_or(JOIN_SHARD)], uor);
     }
     if (tid == 0) { acc = sm.wcnt[0] + sm.wcnt[1] + sm.wcnt[2] + sm.wcnt[3];
                     if (acc) atomicAdd(&a.ctl[ctl_accepted(JOIN_SHARD)], (unsigned long long)acc); }
+}
+
+// (64-bit pileup: asked to stay at 80 VGPRs, i.e. 6 waves per SIMD beside its 26.5 KB of LDS; the others have room anyway, and the
+// 128-bit pileup kernel would spill under that bound)
+template <class K, int MODE>
+__global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((sizeof(K) == 8 && MODE == XCK_MODE_BAF) ? 6 : 4, 8))) void k_join(JoinArgs<K> a) {
+    __shared__ JoinSmem<K, MODE> sm;
+    const int tid = threadIdx.x;
+    StampRec t_s0;
+#if XCK_STAMPS
+    for (int q = 0; q < 12; q++) t_s0.d[q] = 0;
+    t_s0.t = clock64();
+#endif
+#define STAMP(slot) XCK_STAMP(&t_s0, slot)
+    // ---- prologue: one record from k_tile_meta, then ONE round of independent loads ----
+    const XCK_GLOBAL TileMeta* mp = as_global(a.meta) + blockIdx.x;
+    const TileMeta m = { mp->c_lo, mp->cg_n, mp->w0, mp->nw, mp->e0, mp->n_ent, mp->k0, mp->nk, mp->b, mp->r0, 0, mp->pad };
+    const int b = __builtin_amdgcn_readfirstlane(m.b);
+    const int tile0 = __builtin_amdgcn_readfirstlane(m.r0);
+    const BatchDesc& d = a.bt.desc[b];                                // kernarg: scalar loads through the constant cache
+    const int32_t u_lb = __builtin_amdgcn_readfirstlane(m.e0), u_nst = __builtin_amdgcn_readfirstlane(m.n_ent), u_p0 = __builtin_amdgcn_readfirstlane(m.k0);   // basefc: the tile's region slice as scalars
+    STAMP(0);
+    RawRead W[TILE_ITEMS];
+    if (__builtin_amdgcn_readfirstlane(tile0 + TILE <= d.n)) {        // a full tile (all but the last of a batch): no per-lane bounds
+#pragma unroll
+        for (int j = 0; j < TILE_ITEMS; j++) W[j] = fetch_read<MODE == XCK_MODE_BAF>(d, tile0, (uint32_t)(j * JOIN_BLOCK + tid), true);
+    } else {
+#pragma unroll
+        for (int j = 0; j < TILE_ITEMS; j++) W[j] = fetch_read<MODE == XCK_MODE_BAF>(d, tile0, (uint32_t)(j * JOIN_BLOCK + tid), tile0 + j * JOIN_BLOCK + tid < d.n);
+    }                                                                 // the whole tile's loads fly during the staging
+    stage_tile<K, MODE>(a, d, sm, m, u_lb);
+    STAMP(1);
+    __syncthreads();
+    STAMP(2);
+    // ---- TILE_ITEMS coalesced sweeps over the tile (the reads were requested in the prologue) ----
+    uint32_t acc = 0;
+    unsigned long long uor = 0;
+    int pr_n = 0;                                                     // pileup: parked pairs of this wave (wave-uniform)
+    // sweeps between two flushes: keep the expected fill (256 reads x ~2 pairs per sweep) under half the set / queue
+    constexpr int CAP_ENTRIES = JoinSmem<K, MODE>::USE_SET ? JoinSmem<K, MODE>::SLOTS : JoinSmem<K, MODE>::QCAP;
+    // set mode: the de-duplicated fill of a 1024-read tile is a few hundred keys, so flush once, at the end
+    // (better de-duplication, half the cursor atomics); saturation still spills correctly through append_one()
+#ifndef XCK_SET_FLUSH_EVERY
+#define XCK_SET_FLUSH_EVERY TILE_ITEMS
+#endif
+    constexpr int FLUSH_EVERY = JoinSmem<K, MODE>::USE_SET ? XCK_SET_FLUSH_EVERY : JoinSmem<K, MODE>::SPLIT ? TILE_ITEMS
+                              : ((CAP_ENTRIES / 2 / (JOIN_BLOCK * 2)) < 1 ? 1 : (CAP_ENTRIES / 2 / (JOIN_BLOCK * 2)));
+#pragma unroll
+    for (int j = 0; j < TILE_ITEMS; j++) {
+        const ReadInfo r = load_read<K, MODE>(a, d, sm, W[j]);
+#if XCK_STAMPS == 2
+        if (j == 0) { uint32_t x_ = (uint32_t)r.endpos ^ (uint32_t)r.n_al; asm volatile("" :: "v"(x_)); STAMP(3); }   // (the summary is complete)
+#endif
+        if (r.ok) uor |= r.umi;                                       // (finish() puts the haplotype class of the region-level keys into UMI-field bits no code uses)
+        // wave-uniform calls: the walk over the regions / SNPs is shared by all 64 lanes
+        if constexpr (MODE == XCK_MODE_BAF) acc += pileup_sweep<K, MODE>(a, d, sm, r, W[j], tile0 + j * JOIN_BLOCK + tid, pr_n, j + 1 == TILE_ITEMS);
+        else acc += join_regions<K, MODE>(a, d, sm, r, u_lb, u_nst, u_p0, &t_s0, j);
+        // Flush points are fixed at compile time, never decided from sm.count: a count-based decision read
+        // after the barrier races with the next sweep's inserts (threads could disagree and split at the
+        // barriers inside flush()).  A set / queue that saturates between two flush points spills through
+        // append_one(), which is always correct.
+#if XCK_STAMPS == 2
+        if (j == 0) STAMP(5); else STAMP(6);                          // sweep 0 in three parts (3 read summary, 4 chunk scan, 5 candidates), 6 = sweeps 1-3
+#else
+        STAMP(3 + j);
+#endif
+        if ((j + 1) % FLUSH_EVERY == 0 || j + 1 == TILE_ITEMS) {
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: global prefetches stay in flight
+            STAMP(7);
+            if constexpr (JoinSmem<K, MODE>::SPLIT) flush_split<K, MODE>(a, sm, &t_s0); else flush<K, MODE>(a, sm, &t_s0);
+        }
+    }
+    publish_tile_totals<K, MODE>(a, sm, acc, uor);
 #if XCK_STAMPS != 2
     STAMP(11);
 #endif
@@ -883,7 +900,6 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
                 reg_s0.push_back(r.start - 1); reg_e0.push_back(r.end); reg_row.push_back(g);
                 max_e = std::max(max_e, r.end); reg_pmax.push_back(max_e);          // running maximum of the ends: first candidate of a position by binary search
             }
-            (void)max_e;
         }
     } else {
         std::vector<std::vector<int32_t>> by_c(nc);
@@ -948,27 +964,33 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
     return 0;
 }
 
-int arena_begin(EngineImpl* im, Arena& a, size_t need) {
-    a.off = 0;
-    if (need > a.cap) {
-        if (a.base) HIP_TRY(hipFree(a.base));
-        a.base = nullptr; a.cap = 0;
-        size_t c = need + need / 4 + (1 << 20);
-        HIP_TRY(hipMalloc((void**)&a.base, c));
-        a.cap = c;
-    }
+// Grow-only buffers (capacities in bytes): afterwards *p holds at least `need` bytes.  A buffer that is too small is freed and
+// allocated anew with need + slack bytes - its contents are not kept - and a failure leaves it empty (null, capacity 0).
+static int grow_device(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack) {
+    if (need <= *cap) return 0;
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc(p, need + slack));
+    *cap = need + slack;
+    return 0;
+}
+// ... and its twin for pinned, mapped host memory
+static int grow_pinned(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack) {
+    if (need <= *cap) return 0;
+    if (*p) HIP_TRY(hipHostFree(*p));
+    *p = nullptr; *cap = 0;
+    HIP_TRY(hipHostMalloc(p, need + slack, hipHostMallocMapped));
+    *cap = need + slack;
     return 0;
 }
 
+int arena_begin(EngineImpl* im, Arena& a, size_t need) {
+    a.off = 0;
+    return grow_device(im, (void**)&a.base, &a.cap, need, need / 4 + (1 << 20));
+}
+
 int res_reserve(EngineImpl* im, int m, size_t nnz) {
-    if (nnz * 3 > im->h_res_cap[m]) {
-        if (im->h_res[m]) HIP_TRY(hipHostFree(im->h_res[m]));
-        im->h_res[m] = nullptr; im->h_res_cap[m] = 0;
-        size_t c = nnz * 3 + nnz / 2 + 1024;
-        HIP_TRY(hipHostMalloc((void**)&im->h_res[m], c * sizeof(int32_t), hipHostMallocMapped));
-        im->h_res_cap[m] = c;
-    }
-    return 0;
+    return grow_pinned(im, (void**)&im->h_res[m], &im->h_res_cap[m], nnz * 3 * sizeof(int32_t), (nnz / 2 + 1024) * sizeof(int32_t));
 }
 
 // per-shard head room added to every capacity guess (XCK_HIT_SLACK: test knob that makes the overflow / replay path easy to reach)
@@ -977,44 +999,46 @@ bool split_mode(const EngineImpl* im) { return XCK_BAF_SPLIT && im->mode == XCK_
 
 static int ensure_hits(EngineImpl* im, size_t need) {           // need = elements per shard
     if (need <= im->hit_cap) return 0;
-    size_t ncap = std::max<size_t>(need, im->hit_cap * 2);
-    void* nk = nullptr; uint64_t* nv = nullptr;
-    HIP_TRY(hipMalloc(&nk, ncap * NSHARD * key_bytes(im)));
-    if (im->mode == XCK_MODE_BAF) HIP_TRY(hipMalloc((void**)&nv, ncap * NSHARD * sizeof(uint64_t)));
-    for (int sh = 0; sh < NSHARD; sh++) if (im->cur[sh]) {
-        HIP_TRY(hipMemcpyAsync((char*)nk + (size_t)sh * ncap * key_bytes(im), (char*)im->d_keys + (size_t)sh * im->hit_cap * key_bytes(im),
-                               im->cur[sh] * key_bytes(im), hipMemcpyDeviceToDevice, im->s_comp));
-        if (nv) HIP_TRY(hipMemcpyAsync(nv + (size_t)sh * ncap, im->d_vals + (size_t)sh * im->hit_cap, im->cur[sh] * sizeof(uint64_t), hipMemcpyDeviceToDevice, im->s_comp));
-    }
-    void* nnk = nullptr; uint64_t* nnv = nullptr;
-    if (split_mode(im)) {
-        HIP_TRY(hipMalloc(&nnk, ncap * NSHARD * sizeof(uint64_t))); HIP_TRY(hipMalloc((void**)&nnv, ncap * NSHARD * sizeof(uint64_t)));
-        for (int sh = 0; sh < NSHARD; sh++) if (im->ncur[sh]) {
-            HIP_TRY(hipMemcpyAsync((uint64_t*)nnk + (size_t)sh * ncap, (uint64_t*)im->d_nkeys + (size_t)sh * im->hit_cap, im->ncur[sh] * sizeof(uint64_t), hipMemcpyDeviceToDevice, im->s_comp));
-            HIP_TRY(hipMemcpyAsync(nnv + (size_t)sh * ncap, im->d_nvals + (size_t)sh * im->hit_cap, im->ncur[sh] * sizeof(uint64_t), hipMemcpyDeviceToDevice, im->s_comp));
+    const size_t ncap = std::max<size_t>(need, im->hit_cap * 2), kb = key_bytes(im);
+    // the four streams (keys, vals; no-base keys, vals), each with its element size (0 = this pipeline has no such stream)
+    void* old[4] = { im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals };
+    void* nw[4] = { nullptr, nullptr, nullptr, nullptr };
+    const size_t elt[4] = { kb, im->mode == XCK_MODE_BAF ? sizeof(uint64_t) : 0, split_mode(im) ? sizeof(uint64_t) : 0, split_mode(im) ? sizeof(uint64_t) : 0 };
+    // new buffers, and what the shards hold moved to its place in them
+    const auto move = [&]() -> int {
+        for (int q = 0; q < 4; q++) {
+            if (!elt[q]) continue;
+            HIP_TRY(hipMalloc(&nw[q], ncap * NSHARD * elt[q]));
+            const unsigned long long* cnt = q < 2 ? im->cur : im->ncur;
+            for (int sh = 0; sh < NSHARD; sh++) if (cnt[sh])
+                HIP_TRY(hipMemcpyAsync((char*)nw[q] + (size_t)sh * ncap * elt[q], (char*)old[q] + (size_t)sh * im->hit_cap * elt[q], cnt[sh] * elt[q], hipMemcpyDeviceToDevice, im->s_comp));
         }
+        HIP_TRY(hipStreamSynchronize(im->s_comp));
+        return 0;
+    };
+    if (const int rc = move()) {                                 // (the old buffers stay as they are; nothing new is kept)
+        hipStreamSynchronize(im->s_comp);
+        for (void* p : nw) if (p) hipFree(p);
+        return rc;
     }
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    if (im->d_keys) HIP_TRY(hipFree(im->d_keys));
-    if (im->d_vals) HIP_TRY(hipFree(im->d_vals));
-    if (im->d_nkeys) HIP_TRY(hipFree(im->d_nkeys));
-    if (im->d_nvals) HIP_TRY(hipFree(im->d_nvals));
-    im->d_keys = nk; im->d_vals = nv; im->d_nkeys = nnk; im->d_nvals = nnv; im->hit_cap = ncap;
+    for (void* p : old) if (p) HIP_TRY(hipFree(p));
+    im->d_keys = nw[0]; im->d_vals = (uint64_t*)nw[1]; im->d_nkeys = nw[2]; im->d_nvals = (uint64_t*)nw[3]; im->hit_cap = ncap;
     return 0;
 }
 
+// (capacities: cap_reads in reads, shared by the seven per-read columns; cap_cig and cap_seq in bytes.  Every one at least doubles.)
 static int slot_reserve(EngineImpl* im, BatchSlot& s, size_t n_reads, size_t n_cig, size_t n_seq) {
     if (n_reads > s.cap_reads) {
-        size_t c = std::max(n_reads, s.cap_reads * 2);
-        if (s.pos) { hipFree(s.pos); hipFree(s.flag); hipFree(s.mapq); hipFree(s.cell); hipFree(s.umi); hipFree(s.cig_off); hipFree(s.seq_off); }
-        HIP_TRY(hipMalloc((void**)&s.pos, c * 4)); HIP_TRY(hipMalloc((void**)&s.flag, c * 2)); HIP_TRY(hipMalloc((void**)&s.mapq, c));
-        HIP_TRY(hipMalloc((void**)&s.cell, c * 4)); HIP_TRY(hipMalloc((void**)&s.umi, c * 8));
-        HIP_TRY(hipMalloc((void**)&s.cig_off, (c + 1) * 4)); HIP_TRY(hipMalloc((void**)&s.seq_off, (c + 1) * 4));
+        const size_t c = std::max(n_reads, s.cap_reads * 2);
+        struct { void** p; size_t bytes; } col[7] = { { (void**)&s.pos, c * 4 }, { (void**)&s.flag, c * 2 }, { (void**)&s.mapq, c }, { (void**)&s.cell, c * 4 }, { (void**)&s.umi, c * 8 },
+                                                       { (void**)&s.cig_off, (c + 1) * 4 }, { (void**)&s.seq_off, (c + 1) * 4 } };
+        s.cap_reads = 0;
+        for (auto& x : col) { size_t cap = 0; if (const int rc = grow_device(im, x.p, &cap, x.bytes, 0)) return rc; }
         s.cap_reads = c;
     }
-    if (n_cig > s.cap_cig) { size_t c = std::max(n_cig, s.cap_cig * 2); if (s.cigar) hipFree(s.cigar); HIP_TRY(hipMalloc((void**)&s.cigar, c * 4)); s.cap_cig = c; }
-    if (n_seq > s.cap_seq) { size_t c = std::max(n_seq, s.cap_seq * 2); if (s.seq) hipFree(s.seq); HIP_TRY(hipMalloc((void**)&s.seq, c)); s.cap_seq = c; }
-    return 0;
+    const size_t cig = n_cig * 4;
+    if (const int rc = grow_device(im, (void**)&s.cigar, &s.cap_cig, cig, std::max(cig, s.cap_cig * 2) - cig)) return rc;
+    return grow_device(im, (void**)&s.seq, &s.cap_seq, n_seq, std::max(n_seq, s.cap_seq * 2) - n_seq);
 }
 
 // launch ONE fused join kernel over every batch in im->inflight
@@ -1025,13 +1049,7 @@ static int launch_join_t(EngineImpl* im) {
     int32_t tiles = 0;
     for (int i = 0; i < nb; i++) { im->inflight[i].tile0 = tiles; tiles += (im->inflight[i].n + TILE - 1) / TILE; a.bt.desc[i] = im->inflight[i]; }
     a.bt.n_batches = nb; a.bt.n_tiles = tiles;
-    if ((size_t)tiles > im->meta_cap) {
-        if (im->d_meta) HIP_TRY(hipFree(im->d_meta));
-        im->d_meta = nullptr; im->meta_cap = 0;
-        size_t c = (size_t)tiles + tiles / 2 + 1024;
-        HIP_TRY(hipMalloc((void**)&im->d_meta, c * sizeof(TileMeta)));
-        im->meta_cap = c;
-    }
+    if (const int rc = grow_device(im, (void**)&im->d_meta, &im->meta_cap, (size_t)tiles * sizeof(TileMeta), (size_t)(tiles / 2 + 1024) * sizeof(TileMeta))) return rc;
     a.meta = im->d_meta; a.f = im->rf;
     a.reg_s0 = im->d_reg_s0; a.reg_e0 = im->d_reg_e0; a.reg_row = im->d_reg_row; a.reg_pmax = im->d_reg_pmax;
     a.snp_p0 = im->d_snp_p0;
@@ -1090,7 +1108,7 @@ int complete_pending(EngineImpl* im) {
         for (int sh = 0; sh < NSHARD; sh++) { im->cur[sh] = im->h_ctl[ctl_cursor(sh)]; im->cursor += im->cur[sh];
                                               im->ncur[sh] = split_mode(im) ? im->h_ctl[ctl_ncursor(sh)] : 0; im->ncursor += im->ncur[sh]; }
         if (im->inflight_slot >= 0) im->slot[im->inflight_slot].busy = false;
-        if (im->inflight_shared >= 0 && im->eng->stager) { ((Stager*)im->eng->stager)->slot[im->inflight_shared].users--; im->inflight_shared = -1; }
+        if (im->inflight_shared >= 0 && im->eng->stager) { im->eng->stager->slot[im->inflight_shared].users--; im->inflight_shared = -1; }
         im->inflight.clear(); im->inflight_slot = -1; im->inflight_reads = 0;
     }
     return 0;
@@ -1109,34 +1127,57 @@ int launch_queue(EngineImpl* im, int slot_idx, int shared_slot) {
     im->inflight_reads = im->queued_reads; im->queued_reads = 0;
     im->inflight_slot = slot_idx;
     im->inflight_shared = shared_slot;
-    if (shared_slot >= 0) ((Stager*)im->eng->stager)->slot[shared_slot].users++;
+    if (shared_slot >= 0) im->eng->stager->slot[shared_slot].users++;
     for (int sh = 0; sh < NSHARD; sh++) { im->cur_before[sh] = im->cur[sh]; im->ncur_before[sh] = im->ncur[sh]; im->acc_before[sh] = im->h_ctl[ctl_accepted(sh)]; }
     if (slot_idx >= 0) im->slot[slot_idx].busy = true;
     rc = launch_join(im); if (rc) return rc;
     return launch_read_fate(im);                               // (off: returns at once)
 }
 
-int engine_push(xck_engine* e, const xck_batch* b, bool device_resident) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
-    if (im->finished) { e->err = "push after finish (call xck_reset)"; return XCK_E_STATE; }
+// ---- the push paths ----
+// Which columns of a batch may be null differs by where they live.  COLS_HOST (engine_push from host arrays): a null cigar / seq
+// pointer is fine when its offset range is empty - the same rule as xck_push_batch's check and its packed form.  COLS_DEVICE
+// (device-resident batches): the offsets live in HBM, so the pointers must be there.  COLS_BLOCK (engine_push_block): the columns are
+// slices of the block, laid out by the decoder or by xck_push_batch's packed form; only the sequence columns are asked about.
+enum Columns { COLS_HOST, COLS_DEVICE, COLS_BLOCK };
+static const char* null_column(const EngineImpl* im, const xck_batch* b, Columns c) {
+    const bool seq = im->mode == XCK_MODE_BAF;
+    if (c == COLS_BLOCK) return seq && (!b->seq_off || !b->seq) ? "BAF mode needs seq arrays" : nullptr;
+    const bool dev = c == COLS_DEVICE;
+    if (!b->pos || !b->flag || !b->mapq || !b->cell || !b->umi || !b->cig_off) return "null batch array";
+    if (!b->cigar && (dev || b->cig_off[b->n_reads] != b->cig_off[0])) return "null batch array";
+    if (seq && (!b->seq_off || (!b->seq && (dev || b->seq_off[b->n_reads] != b->seq_off[0])))) return "BAF mode needs seq arrays";
+    return nullptr;
+}
+
+// What a push does with one batch, decided in one place: the batch is counted, its contig and its columns are checked, and the table
+// half of its BatchDesc is filled (the column pointers are the caller's: they are what differs between the paths).
+enum BatchFate { BATCH_ERROR = -1, BATCH_SKIP = 0, BATCH_QUEUE = 1 };    // ERROR: XCK_E_ARG, the text is in the handle; SKIP: counted, no kernel will see it
+static BatchFate describe_batch(EngineImpl* im, const xck_batch* b, Columns cols, BatchDesc& d) {
     im->st.n_batches++; im->st.n_reads += b->n_reads;
-    if (b->n_reads <= 0 || b->contig < 0) { im->n_not_joined += std::max(b->n_reads, 0); return 0; }
-    if (b->contig >= (int)im->ctab.size()) { e->err = "batch contig out of range"; return XCK_E_ARG; }
-    // (host batches: a null cigar / seq pointer is fine when its offset range is empty - the same rule as xck_push_batch's check and
-    // its packed form; device-resident batches: the offsets live in HBM, so the pointers must be there)
-    if (!b->pos || !b->flag || !b->mapq || !b->cell || !b->umi || !b->cig_off) { e->err = "null batch array"; return XCK_E_ARG; }
-    if (!b->cigar && (device_resident || b->cig_off[b->n_reads] != b->cig_off[0])) { e->err = "null batch array"; return XCK_E_ARG; }
-    if (im->mode == XCK_MODE_BAF && (!b->seq_off || (!b->seq && (device_resident || b->seq_off[b->n_reads] != b->seq_off[0])))) { e->err = "BAF mode needs seq arrays"; return XCK_E_ARG; }
-    HIP_TRY(hipSetDevice(im->device));
+    if (b->n_reads <= 0 || b->contig < 0) { im->n_not_joined += std::max(b->n_reads, 0); return BATCH_SKIP; }
+    if (b->contig >= (int)im->ctab.size()) { im->eng->err = "batch contig out of range"; return BATCH_ERROR; }
     const ContigTab& t = im->ctab[b->contig];
-    bool has_targets = im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0;
-    if (!has_targets) { im->n_not_joined += b->n_reads; return 0; }
-    BatchDesc d;
+    const bool has_targets = im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0;
+    if (cols != COLS_BLOCK || has_targets)                           // (a block's batch is asked about only if a kernel will read it)
+        if (const char* what = null_column(im, b, cols)) { im->eng->err = what; return BATCH_ERROR; }
+    if (!has_targets) { im->n_not_joined += b->n_reads; return BATCH_SKIP; }
     memset(&d, 0, sizeof d);
     d.n = b->n_reads; d.ordinal_base = b->ordinal_base;
     d.reg_lo = t.reg_base; d.reg_hi = t.reg_base + t.n_reg;
     d.snp_win = im->d_snp_win + t.swin_base; d.n_swin = t.n_swin; d.snp_end = t.snp_base + t.n_snp;
+    return BATCH_QUEUE;
+}
+// algorithmic bytes the join reads for a batch whose sizes the host knows (xck_stats.algo_bytes_join; n_seq: 0 without sequences)
+static int64_t join_bytes(size_t n, size_t n_cig, size_t n_seq) { return (int64_t)n * 20 + (int64_t)n_cig * 4 + (int64_t)(n_seq / 2); }
+
+int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident) {
+    xck_engine* e = im->eng;
+    if (im->finished) { e->err = "push after finish (call xck_reset)"; return XCK_E_STATE; }
+    HIP_TRY(hipSetDevice(im->device));
+    BatchDesc d;
+    const BatchFate fate = describe_batch(im, b, device_resident ? COLS_DEVICE : COLS_HOST, d);
+    if (fate != BATCH_QUEUE) return fate == BATCH_SKIP ? 0 : XCK_E_ARG;
     if (device_resident) {
         // deferred: consecutive device-resident batches are fused into one launch (>> 256 workgroups)
         d.pos = b->pos; d.flag = b->flag; d.mapq = b->mapq; d.cell = b->cell; d.umi = b->umi;
@@ -1146,11 +1187,12 @@ int engine_push(xck_engine* e, const xck_batch* b, bool device_resident) {
         return 0;
     }
     int rc = launch_queue(im, -1); if (rc) return rc;          // keep launch order == push order
+    const bool seq = im->mode == XCK_MODE_BAF;
     size_t n = (size_t)b->n_reads;
     // offsets need not start at 0 (a batch may be a window into a larger decode buffer)
-    const uint32_t c_lo = b->cig_off[0], s_lo = im->mode == XCK_MODE_BAF ? b->seq_off[0] : 0;
-    if (b->cig_off[n] < c_lo || (im->mode == XCK_MODE_BAF && b->seq_off[n] < s_lo)) { e->err = "batch offsets are not monotonic"; return XCK_E_ARG; }
-    uint32_t n_cig = b->cig_off[n] - c_lo, n_seq = im->mode == XCK_MODE_BAF ? b->seq_off[n] - s_lo : 0;
+    const uint32_t c_lo = b->cig_off[0], s_lo = seq ? b->seq_off[0] : 0;
+    if (b->cig_off[n] < c_lo || (seq && b->seq_off[n] < s_lo)) { e->err = "batch offsets are not monotonic"; return XCK_E_ARG; }
+    uint32_t n_cig = b->cig_off[n] - c_lo, n_seq = seq ? b->seq_off[n] - s_lo : 0;
     int slot_idx = im->next_slot; im->next_slot ^= 1;
     BatchSlot& s = im->slot[slot_idx];
     if (s.busy) { rc = complete_pending(im); if (rc) return rc; }   // slot still feeds the launch in flight
@@ -1163,82 +1205,62 @@ int engine_push(xck_engine* e, const xck_batch* b, bool device_resident) {
     HIP_TRY(hipMemcpyAsync(s.umi, b->umi, n * 8, hipMemcpyHostToDevice, im->s_copy));
     HIP_TRY(hipMemcpyAsync(s.cig_off, b->cig_off, (n + 1) * 4, hipMemcpyHostToDevice, im->s_copy));
     if (n_cig) HIP_TRY(hipMemcpyAsync(s.cigar, b->cigar + c_lo, (size_t)n_cig * 4, hipMemcpyHostToDevice, im->s_copy));
-    if (im->mode == XCK_MODE_BAF) {
+    if (seq) {
         HIP_TRY(hipMemcpyAsync(s.seq_off, b->seq_off, (n + 1) * 4, hipMemcpyHostToDevice, im->s_copy));
         if (n_seq) HIP_TRY(hipMemcpyAsync(s.seq, b->seq + s_lo, n_seq, hipMemcpyHostToDevice, im->s_copy));
     }
     HIP_TRY(hipStreamSynchronize(im->s_copy));                 // caller may reuse its arrays now
     im->st.ms_h2d += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    im->st.algo_bytes_join += (int64_t)n * 20 + (int64_t)n_cig * 4 + (int64_t)(n_seq / 2);
+    im->st.algo_bytes_join += join_bytes(n, n_cig, n_seq);
     d.pos = s.pos; d.flag = s.flag; d.mapq = s.mapq; d.cell = s.cell; d.umi = s.umi;
     d.cig_off = s.cig_off; d.cigar = s.cigar - c_lo; d.seq_off = s.seq_off; d.seq = s.seq - s_lo;   // rebased, never read below *_lo
     im->queue.push_back(d); im->queued_reads += b->n_reads;
     return launch_queue(im, slot_idx);                         // the kernel overlaps the caller's next decode + copy
 }
 
-// ---- host ingest: one decoded chunk = one H2D copy, shared by every pipeline of the handle ----
-#define HIP_TRY_E(e_, expr)                                                                 \
-    do { hipError_t e__ = (expr); if (e__ != hipSuccess) {                                  \
-        char b_[512]; snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr,               \
-                               hipGetErrorString(e__), __FILE__, __LINE__);                 \
-        (e_)->err = b_; return XCK_E_DEVICE; } } while (0)
-
+// ---- host ingest: one decoded chunk = one H2D copy, shared by every pipeline of the handle (which has at least one) ----
 int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence) {
-    if (e->n_impl <= 0) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
-    EngineImpl* im0 = (EngineImpl*)e->impls[0];
-    HIP_TRY_E(e, hipSetDevice(im0->device));
-    Stager* st = (Stager*)e->stager;
+    EngineImpl* im = e->impls[0];                                        // (errors of the shared part are reported through it)
+    HIP_TRY(hipSetDevice(im->device));
+    Stager* st = e->stager;
     if (!st) {
-        st = new Stager(); st->device = im0->device; e->stager = st;
-        HIP_TRY_E(e, hipStreamCreateWithFlags(&st->s_copy, hipStreamNonBlocking));
-        for (auto& sl : st->slot) { HIP_TRY_E(e, hipEventCreate(&sl.t0)); HIP_TRY_E(e, hipEventCreate(&sl.copied)); }
+        st = new Stager(); st->device = im->device; e->stager = st;
+        HIP_TRY(hipStreamCreateWithFlags(&st->s_copy, hipStreamNonBlocking));
+        for (auto& sl : st->slot) { HIP_TRY(hipEventCreate(&sl.t0)); HIP_TRY(hipEventCreate(&sl.copied)); }
     }
     const int si = st->next; st->next = (st->next + 1) % 3;
     Stager::Slot& sl = st->slot[si];
-    for (int k = 0; k < e->n_impl && sl.users > 0; k++) {                // launches that still read this slot: confirm them
-        EngineImpl* im = (EngineImpl*)e->impls[k];
-        if (im->inflight_shared == si) { int rc = complete_pending(im); if (rc) return rc; }
-    }
+    for (int k = 0; k < e->n_impl && sl.users > 0; k++)                  // launches that still read this slot: confirm them
+        if (e->impls[k]->inflight_shared == si) { int rc = complete_pending(e->impls[k]); if (rc) return rc; }
     if (sl.users != 0) { e->err = "internal: staging slot still in use"; return XCK_E_STATE; }
-    if (sl.timed) { float ms = 0; if (hipEventElapsedTime(&ms, sl.t0, sl.copied) == hipSuccess) im0->st.ms_h2d += ms; sl.timed = false; }
-    if (bytes > sl.cap) {
-        if (sl.buf) HIP_TRY_E(e, hipFree(sl.buf));
-        sl.buf = nullptr; sl.cap = 0;
-        const size_t c = bytes + bytes / 4 + (1 << 20);
-        HIP_TRY_E(e, hipMalloc((void**)&sl.buf, c));
-        sl.cap = c;
-    }
-    if (!*fence) { hipEvent_t ev; HIP_TRY_E(e, hipEventCreateWithFlags(&ev, hipEventDisableTiming)); *fence = (void*)ev; }
-    HIP_TRY_E(e, hipEventRecord(sl.t0, st->s_copy));
-    HIP_TRY_E(e, hipMemcpyAsync(sl.buf, host_base, bytes, hipMemcpyHostToDevice, st->s_copy));
-    HIP_TRY_E(e, hipEventRecord(sl.copied, st->s_copy));
-    HIP_TRY_E(e, hipEventRecord((hipEvent_t)*fence, st->s_copy));
+    if (sl.timed) { float ms = 0; if (hipEventElapsedTime(&ms, sl.t0, sl.copied) == hipSuccess) im->st.ms_h2d += ms; sl.timed = false; }
+    if (int rc = grow_device(im, (void**)&sl.buf, &sl.cap, bytes, bytes / 4 + (1 << 20))) return rc;
+    if (!*fence) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); *fence = (void*)ev; }
+    HIP_TRY(hipEventRecord(sl.t0, st->s_copy));
+    HIP_TRY(hipMemcpyAsync(sl.buf, host_base, bytes, hipMemcpyHostToDevice, st->s_copy));
+    HIP_TRY(hipEventRecord(sl.copied, st->s_copy));
+    HIP_TRY(hipEventRecord((hipEvent_t)*fence, st->s_copy));
     sl.timed = true;
     const char* hb = (const char*)host_base;
-    auto dev = [&](const void* hp) { return (void*)(sl.buf + ((const char*)hp - hb)); };
+    auto dev = [&](const void* hp) { return (void*)(sl.buf + ((const char*)hp - hb)); };   // a column's place in the staged copy
     for (int k = 0; k < e->n_impl; k++) {
-        EngineImpl* im = (EngineImpl*)e->impls[k];
+        im = e->impls[k];
         if (im->finished) { e->err = "push after finish (call xck_reset)"; return XCK_E_STATE; }
         int rc = launch_queue(im, -1); if (rc) return rc;                 // earlier device-resident pushes keep their order
-        HIP_TRY_E(e, hipStreamWaitEvent(im->s_comp, sl.copied, 0));
+        HIP_TRY(hipStreamWaitEvent(im->s_comp, sl.copied, 0));
+        const bool seq = im->mode == XCK_MODE_BAF;
         for (int i = 0; i < n; i++) {
             const xck_batch* b = &batches[i];
-            im->st.n_batches++; im->st.n_reads += b->n_reads;
-            if (b->n_reads <= 0 || b->contig < 0) { im->n_not_joined += std::max(b->n_reads, 0); continue; }
-            if (b->contig >= (int)im->ctab.size()) { e->err = "batch contig out of range"; return XCK_E_ARG; }
-            const ContigTab& t = im->ctab[b->contig];
-            if (!(im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0)) { im->n_not_joined += b->n_reads; continue; }
-            if (im->mode == XCK_MODE_BAF && (!b->seq_off || !b->seq)) { e->err = "BAF mode needs seq arrays"; return XCK_E_ARG; }
-            BatchDesc d; memset(&d, 0, sizeof d);
-            d.n = b->n_reads; d.ordinal_base = b->ordinal_base;
-            d.reg_lo = t.reg_base; d.reg_hi = t.reg_base + t.n_reg;
-            d.snp_win = im->d_snp_win + t.swin_base; d.n_swin = t.n_swin; d.snp_end = t.snp_base + t.n_snp;
+            BatchDesc d;
+            const BatchFate fate = describe_batch(im, b, COLS_BLOCK, d);
+            if (fate == BATCH_ERROR) return XCK_E_ARG;
+            if (fate == BATCH_SKIP) continue;
             d.pos = (const int32_t*)dev(b->pos); d.flag = (const uint16_t*)dev(b->flag); d.mapq = (const uint8_t*)dev(b->mapq);
             d.cell = (const int32_t*)dev(b->cell); d.umi = (const uint64_t*)dev(b->umi);
             d.cig_off = (const uint32_t*)dev(b->cig_off); d.cigar = (const uint32_t*)dev(b->cigar);
-            if (im->mode == XCK_MODE_BAF) { d.seq_off = (const uint32_t*)dev(b->seq_off); d.seq = (const uint8_t*)dev(b->seq); }
+            if (seq) { d.seq_off = (const uint32_t*)dev(b->seq_off); d.seq = (const uint8_t*)dev(b->seq); }
             const size_t nr = (size_t)b->n_reads;
-            im->st.algo_bytes_join += (int64_t)nr * 20 + (int64_t)(b->cig_off[nr] - b->cig_off[0]) * 4 + (im->mode == XCK_MODE_BAF ? (int64_t)((b->seq_off[nr] - b->seq_off[0]) / 2) : 0);
+            im->st.algo_bytes_join += join_bytes(nr, b->cig_off[nr] - b->cig_off[0], seq ? b->seq_off[nr] - b->seq_off[0] : 0);
             im->queue.push_back(d); im->queued_reads += b->n_reads;
             if ((int)im->queue.size() >= MAX_FUSE) { rc = launch_queue(im, -1, si); if (rc) return rc; }
         }
@@ -1248,7 +1270,7 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
 }
 
 void engine_release_staging(xck_engine* e) {
-    Stager* st = (Stager*)e->stager;
+    Stager* st = e->stager;
     if (!st) return;
     hipSetDevice(st->device);
     if (st->s_copy) hipStreamSynchronize(st->s_copy);
@@ -1260,9 +1282,7 @@ void engine_release_staging(xck_engine* e) {
 void fence_wait(void* f) { if (f) hipEventSynchronize((hipEvent_t)f); }
 void fence_destroy(void* f) { if (f) hipEventDestroy((hipEvent_t)f); }
 
-int engine_flush(xck_engine* e) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
+int engine_flush(EngineImpl* im) {
     HIP_TRY(hipSetDevice(im->device));
     int rc = launch_queue(im, -1); if (rc) return rc;
     return complete_pending(im);
@@ -1279,9 +1299,7 @@ void join_stamps_report(const EngineImpl* im) {
 #endif
 }
 
-int engine_reset(xck_engine* e) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
+int engine_reset(EngineImpl* im) {
     HIP_TRY(hipSetDevice(im->device));
     int rc = launch_queue(im, -1); if (rc) return rc;
     rc = complete_pending(im); if (rc) return rc;
@@ -1301,20 +1319,18 @@ int engine_reset(xck_engine* e) {
     return 0;
 }
 
-int engine_device(const xck_engine* e) { return e->n_impl > 0 && e->impls[0] ? ((const EngineImpl*)e->impls[0])->device : -1; }
+int engine_device(const xck_engine* e) { return e->n_impl > 0 && e->impls[0] ? e->impls[0]->device : -1; }
 
-int engine_stats(const xck_engine* e, xck_stats* out) {
-    const EngineImpl* im = (const EngineImpl*)e->impl;
-    if (!im) return XCK_E_STATE;
+int engine_stats(const EngineImpl* im, xck_stats* out) {
     *out = im->st; out->key_bits = im->key_bits; out->umi_bits = im->ubits;
     out->n_join_launches = im->n_join_launches;
     out->fold_path = im->fold_path; out->fold_fallbacks = im->fold_fallbacks; out->pileup_sort_path = im->pileup_sort_path; out->fold_refinements = im->fold_refinements;
-    out->pileup_sort2_path = im->pileup_sort2_path; out->gpu_inflate_chunks = (int32_t)std::min<int64_t>(e->gpu_inflate_chunks.load(), INT32_MAX);
+    out->pileup_sort2_path = im->pileup_sort2_path; out->gpu_inflate_chunks = (int32_t)std::min<int64_t>(im->eng->gpu_inflate_chunks.load(), INT32_MAX);
     return 0;
 }
 
 int engine_numa_node(const xck_engine* e) {
-    const EngineImpl* im = e && e->n_impl > 0 ? (const EngineImpl*)e->impls[0] : nullptr;
+    const EngineImpl* im = e && e->n_impl > 0 ? e->impls[0] : nullptr;
     if (!im) return -1;
     char bus[64] = {0};
     if (hipDeviceGetPCIBusId(bus, (int)sizeof bus, im->device) != hipSuccess) { (void)hipGetLastError(); return -1; }
@@ -1324,11 +1340,10 @@ int engine_numa_node(const xck_engine* e) {
     int node = -1; if (fscanf(f, "%d", &node) != 1) node = -1; fclose(f);
     return node;
 }
-int engine_umi_bits(const xck_engine* e) { const EngineImpl* im = (const EngineImpl*)e->impl; return im ? im->ubits : 0; }
 
-int engine_create(const xck_config* cfg, xck_engine* e) {
+int engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out) {
     EngineImpl* im = new EngineImpl();
-    im->eng = e; e->impl = im;
+    im->eng = e; *out = im;
     im->mode = cfg->mode; im->device = cfg->device;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { e->err = "no HIP device available (the engine has no CPU fallback)"; return XCK_E_DEVICE; }
@@ -1370,8 +1385,7 @@ int engine_create(const xck_config* cfg, xck_engine* e) {
     return 0;
 }
 
-void engine_destroy(xck_engine* e) {
-    EngineImpl* im = (EngineImpl*)e->impl;
+void engine_destroy(EngineImpl* im) {
     if (!im) return;
     hipSetDevice(im->device);
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
@@ -1391,7 +1405,7 @@ void engine_destroy(xck_engine* e) {
     if (im->ev_f2) hipEventDestroy(im->ev_f2);
     if (im->s_copy) hipStreamDestroy(im->s_copy);
     if (im->s_comp) hipStreamDestroy(im->s_comp);
-    delete im; e->impl = nullptr;
+    delete im;
 }
 
 void* pinned_alloc(size_t bytes) {

@@ -115,7 +115,7 @@ struct ContigTab { int32_t reg_base = 0, n_reg = 0, snp_base = 0, n_snp = 0, swi
 struct BatchSlot {
     int32_t* pos = nullptr; uint16_t* flag = nullptr; uint8_t* mapq = nullptr; int32_t* cell = nullptr;
     uint64_t* umi = nullptr; uint32_t* cig_off = nullptr; uint32_t* cigar = nullptr; uint32_t* seq_off = nullptr; uint8_t* seq = nullptr;
-    size_t cap_reads = 0, cap_cig = 0, cap_seq = 0;
+    size_t cap_reads = 0, cap_cig = 0, cap_seq = 0;          // reads (the seven per-read columns); bytes; bytes
     bool busy = false;
 };
 
@@ -168,7 +168,7 @@ struct EngineImpl {
     int inflight_slot = -1;
     int inflight_shared = -1;                  // staging slot (Stager) the launch in flight reads, -1 = none
     int64_t queued_reads = 0, inflight_reads = 0;
-    TileMeta* d_meta = nullptr; size_t meta_cap = 0;
+    TileMeta* d_meta = nullptr; size_t meta_cap = 0;        // (bytes)
     // timing
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_res = nullptr, ev_c0 = nullptr, ev_c1 = nullptr;
     hipEvent_t ev_f1 = nullptr, ev_f2 = nullptr;   // partition fold: level-1 bucket pass on the copy stream (fold_partition.h)
@@ -179,7 +179,7 @@ struct EngineImpl {
     unsigned long long stamp_sum[12] = {0}; int stamp_tiles = 0; float stamp_ms = 0;   // XCK_STAMPS builds: phase cycles of the last join launch
     // workspace + results
     Arena ws1, ws2;
-    int32_t* h_res[4] = {nullptr, nullptr, nullptr, nullptr}; size_t h_res_cap[4] = {0, 0, 0, 0}; size_t res_nnz[4] = {0, 0, 0, 0};
+    int32_t* h_res[4] = {nullptr, nullptr, nullptr, nullptr}; size_t h_res_cap[4] = {0, 0, 0, 0} /* bytes */; size_t res_nnz[4] = {0, 0, 0, 0};
     int32_t* d_res[4] = {nullptr, nullptr, nullptr, nullptr};   // device copies [row | col | val] inside the workspace, valid until the next finish / reset
     bool finished = false;
     // read assignment summary (XCK_F_READ_FATE, read_fate.h): device counters (null = off), reads of the batches no kernel saw

@@ -1354,16 +1354,14 @@ static int finish_t(EngineImpl* im) {
 }
 
 // fold everything on the GPU and ENQUEUE the copy-out of the matrices; does not wait for the copy
-int engine_finish_async(xck_engine* e) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
+int engine_finish_async(EngineImpl* im) {
     HIP_TRY(hipSetDevice(im->device));
     int rc = launch_queue(im, -1); if (rc) return rc;
     rc = complete_pending(im); if (rc) return rc;
     if (!im->finished) {
         // a finish that failed half-way may have overwritten the accumulated keys (the folds reuse the shard slices as scratch): it
         // cannot be tried again on them
-        if (im->fold_failed) { e->err = "an earlier xck_finish failed inside the fold: the accumulated hits are gone (call xck_reset)"; return XCK_E_STATE; }
+        if (im->fold_failed) { im->eng->err = "an earlier xck_finish failed inside the fold: the accumulated hits are gone (call xck_reset)"; return XCK_E_STATE; }
         im->copy_timed = false;
         rc = im->key_bits == 64 ? finish_t<uint64_t>(im) : finish_t<u128>(im);
         if (rc) { im->fold_failed = true; hipStreamSynchronize(im->s_comp); hipStreamSynchronize(im->s_copy); return rc; }   // (nothing of the failed fold is still running when the arenas are reused)
@@ -1372,10 +1370,8 @@ int engine_finish_async(xck_engine* e) {
     return 0;
 }
 
-int engine_finish(xck_engine* e, xck_result* out) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
-    int rc = engine_finish_async(e); if (rc) return rc;
+int engine_finish(EngineImpl* im, xck_result* out) {
+    int rc = engine_finish_async(im); if (rc) return rc;
     if (im->copy_pending) {
         const bool dbg = im->eng->knobs.debug_timing;
         const auto t0_ = std::chrono::steady_clock::now();
@@ -1397,10 +1393,8 @@ int engine_finish(xck_engine* e, xck_result* out) {
 }
 
 // device-resident copy of the last finish() result (for device-to-device exchanges such as the RCCL gather)
-int engine_result_device(xck_engine* e, xck_result* out) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im) { e->err = "decode-only handle: no GPU engine behind it"; return XCK_E_STATE; }
-    if (!im->finished) { e->err = "xck_get_result_device before xck_finish"; return XCK_E_STATE; }
+int engine_result_device(EngineImpl* im, xck_result* out) {
+    if (!im->finished) { im->eng->err = "xck_get_result_device before xck_finish"; return XCK_E_STATE; }
     memset(out, 0, sizeof *out);
     xck_coo* dst[4] = { &out->count, &out->ad, &out->dp, &out->oth };
     for (int m = 0; m < 4; m++) {

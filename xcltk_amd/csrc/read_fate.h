@@ -1,5 +1,5 @@
 // read_fate.h - opt-in read assignment summary (XCK_F_READ_FATE / XCK_READ_FATE=1; xck_get_read_fate, include/xck.h).
-// Included by engine.hip inside namespace xck, behind launch_join(): it uses the join's BatchTable, ReadInfo, TILE, JOIN_BLOCK, op_aligned / op_ref and
+// Included by engine.hip inside namespace xck, behind launch_join(): it uses the join's BatchTable, ReadInfo, TILE, JOIN_BLOCK, cigar_summary, included_len and
 // frac_below, from engine_impl.h ReadFilter, BatchDesc, as_global, EngineImpl and HIP_TRY, and the grouped accumulation of cell_summary.h.
 //
 // One more pass over the batches the join has just been launched on: every read gets exactly ONE class, the first that applies in
@@ -9,7 +9,8 @@
 //
 // A kernel of its own on purpose.  k_join<u64, pileup> sits one VGPR under its occupancy bound and both joins are bound by VALU
 // issue: a reason code carried through load_read() / join_regions() would put the hot instantiations' code at
-// risk for a diagnostic.  The price is a second statement of the accept rule; `pairs` below must equal the join's own count of
+// risk for a diagnostic.  The price is a second statement of the accept rule's control flow (its two CIGAR loops are the join's own,
+// cigar_summary() and included_len() over plain global loads); `pairs` below must equal the join's own count of
 // accepted pairs (xck_stats.n_hits), which tests/test_gpu_read_fate.py holds on every input it has.
 //
 // One lane per read, CIGAR words and tables straight from global memory (no LDS staging: the pass is opt-in and small next to the
@@ -50,12 +51,9 @@ __device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& 
     if (as_global(d.cell)[i] < 0) return RF_NO_CELL;
     if (as_global(d.umi)[i] == XCK_UMI_NONE) return RF_NO_UMI;
     const uint32_t c0 = as_global(d.cig_off)[i], c1 = as_global(d.cig_off)[i + 1];
+    const auto word_at = [&](uint32_t c) { return as_global(d.cigar)[c]; };
     int32_t rlen = 0, n_al = 0;
-    for (uint32_t c = c0; c < c1; c++) {
-        const uint32_t w = as_global(d.cigar)[c]; const uint32_t op = w & 15u; const int32_t l = int32_t(w >> 4);
-        if (op_ref(op)) rlen += l;
-        if (op_aligned(op)) n_al += l;
-    }
+    cigar_summary(word_at, c0, c1, rlen, n_al);
     if (n_al < a.f.min_len) return RF_SHORT;
     // the fetch span, as load_read(): htslib bam_endpos() gives an unmapped-flagged read, or one without reference-consuming
     // CIGAR, one base
@@ -63,7 +61,7 @@ __device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& 
     if (!span_is_cigar) rlen = 1;
     const int32_t pos = as_global(d.pos)[i], endpos = pos + rlen;
     if (MODE == XCK_MODE_BASEFC) {
-        ReadInfo r = {}; r.n_al = n_al;   // (frac_below() reads n_al only)
+        ReadInfo r = {}; r.pos = pos; r.endpos = endpos; r.n_al = n_al; r.c0 = c0; r.c1 = c1; r.span_is_cigar = span_is_cigar;   // (what included_len() and frac_below() read)
         uint32_t n_ov = 0;
         // every region before the first one whose running-maximum end lies beyond pos ends at or before pos
         for (int32_t k = rf_bisect<true>(a.reg_pmax, d.reg_lo, d.reg_hi, pos); k < d.reg_hi; k++) {
@@ -72,16 +70,7 @@ __device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& 
             const int32_t e0 = as_global(a.reg_e0)[k];
             if (!(pos < e0)) continue;                                // htslib fetch overlap: pos < end0 && endpos > start0
             n_ov++;
-            int32_t m;                                                // __get_include_len(): aligned bases with s0 <= p < e0
-            if (span_is_cigar && pos >= s0 && endpos <= e0) m = n_al;
-            else {
-                int32_t p = pos; m = 0;
-                for (uint32_t c = c0; c < c1; c++) {
-                    const uint32_t w = as_global(d.cigar)[c]; const uint32_t op = w & 15u; const int32_t l = int32_t(w >> 4);
-                    if (op_aligned(op)) { const int32_t lo = max(p, s0), hi = min(p + l, e0); if (hi > lo) m += hi - lo; p += l; }
-                    else if (op_ref(op)) p += l;
-                }
-            }
+            const int32_t m = included_len(word_at, r, s0, e0);
             if (a.f.frac_mode) {                                      // rdr/fc/core.py:160-165, exactly as join_regions()
                 if (n_al <= 0) continue;
                 if (m != n_al && frac_below(m, r, a.f.min_inc_frac)) continue;
@@ -178,11 +167,10 @@ static int launch_read_fate(EngineImpl* im) {
     return 0;
 }
 
-// xck_get_read_fate() for the pipeline e->impl: waits for the queued work, copies the counters
-int engine_read_fate(xck_engine* e, xck_read_fate* out) {
-    EngineImpl* im = (EngineImpl*)e->impl;
-    if (!im || !im->d_fate) { e->err = "handle made without XCK_F_READ_FATE"; return XCK_E_STATE; }
-    int rc = engine_flush(e); if (rc) return rc;
+// xck_get_read_fate() for one pipeline: waits for the queued work, copies the counters
+int engine_read_fate(EngineImpl* im, xck_read_fate* out) {
+    if (!im->d_fate) { im->eng->err = "handle made without XCK_F_READ_FATE"; return XCK_E_STATE; }
+    int rc = engine_flush(im); if (rc) return rc;
     unsigned long long h[RF_WORDS];
     HIP_TRY(hipMemcpy(h, im->d_fate, sizeof h, hipMemcpyDeviceToHost));
     out->mode = im->mode;

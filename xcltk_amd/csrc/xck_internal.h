@@ -123,6 +123,9 @@ struct Knobs {
 // since the last call to its handle's (bam.cpp fold_decode_stats).
 enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_N };
 
+struct EngineImpl;                       // one GPU pipeline of a handle (engine_impl.h)
+struct Stager;                           // device staging slots of engine_push_block (engine.hip)
+
 // the decoder's own batches are valid by construction and skip the O(n) check of xck_push_batch()
 int push_trusted(xck_engine* e, const xck_batch* b);
 // host threads this process may really use: min(hardware threads, CPU affinity, cgroup CPU quota) - a container with a
@@ -138,10 +141,9 @@ struct xck_engine {
     std::string err;
     xck::DecodeCfg dec;
     xck::InternTable intern;
-    void* impl = nullptr;                // xck::EngineImpl being addressed (engine.hip); null for decode-only handles
-    void* impls[2] = {nullptr, nullptr}; // fused handle (XCK_MODE_BOTH): [0] basefc pipeline, [1] pileup pipeline
-    int n_impl = 0;
-    void* stager = nullptr;              // xck::Stager (engine.hip): device staging slots of engine_push_block
+    xck::EngineImpl* impls[2] = {nullptr, nullptr};   // the handle's pipelines; fused handle (XCK_MODE_BOTH): [0] basefc, [1] pileup
+    int n_impl = 0;                      // 0: decode-only handle, no GPU engine behind it
+    xck::Stager* stager = nullptr;       // device staging slots of engine_push_block
     struct PushRing { void* blk[3] = {nullptr, nullptr, nullptr}; size_t cap[3] = {0, 0, 0}; void* fence[3] = {nullptr, nullptr, nullptr}; int next = 0; } push_ring;   // pinned blocks of xck_push_batch's one-copy form (api.cpp)
     xck::Knobs knobs;                    // the environment, read once at xck_create
     std::atomic<int64_t> gpu_inflate_chunks{0};   // chunks inflated on the device by the readers that fed this handle (xck_stats)
@@ -154,20 +156,20 @@ struct xck_engine {
     // host pinned batch staging used by xck_ingest_bam lives in the xck_bam
 };
 
-// implemented in engine.hip (engine_finish, engine_finish_async, engine_result_device: finish.hip)
+// implemented in engine.hip (engine_finish, engine_finish_async, engine_result_device: finish.hip).  A per-pipeline call takes the
+// pipeline it works on; nothing in the handle says which one is "current", so calls from several threads do not meet there.
 namespace xck {
-int  engine_create(const xck_config* cfg, xck_engine* e);
-void engine_destroy(xck_engine* e);
-int  engine_push(xck_engine* e, const xck_batch* b, bool device_resident);
-int  engine_flush(xck_engine* e);
-int  engine_finish(xck_engine* e, xck_result* out);
-int  engine_finish_async(xck_engine* e);
-int  engine_result_device(xck_engine* e, xck_result* out);
-int  engine_reset(xck_engine* e);
-int  engine_stats(const xck_engine* e, xck_stats* out);
-int  engine_umi_bits(const xck_engine* e);
-int  engine_read_fate(xck_engine* e, xck_read_fate* out);   // read_fate.h: the pipeline e->impl
-int  engine_cell_summary(xck_engine* e, xck_cell_summary* out);   // cell_summary.h: the pipeline e->impl
+int  engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out);   // *out is set as soon as it exists: a failed create still has to be destroyed
+void engine_destroy(EngineImpl* im);
+int  engine_push(EngineImpl* im, const xck_batch* b, bool device_resident);
+int  engine_flush(EngineImpl* im);
+int  engine_finish(EngineImpl* im, xck_result* out);
+int  engine_finish_async(EngineImpl* im);
+int  engine_result_device(EngineImpl* im, xck_result* out);
+int  engine_reset(EngineImpl* im);
+int  engine_stats(const EngineImpl* im, xck_stats* out);
+int  engine_read_fate(EngineImpl* im, xck_read_fate* out);         // read_fate.h
+int  engine_cell_summary(EngineImpl* im, xck_cell_summary* out);   // cell_summary.h
 int  engine_device(const xck_engine* e);      // HIP device of the handle (-1: decode-only handle)
 int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (sysfs, by PCI bus id); -1 = unknown
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE
