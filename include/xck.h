@@ -49,7 +49,12 @@
  *                                         (xck_get_cell_summary; implies XCK_READ_FATE=1): the front-ends then write cell_summary.tsv next to
  *                                         read_summary.tsv.  Off (the default, or 0) nothing is allocated or launched.  Decode-only handles ignore it.
  *   XCK_CELL_SUMMARY_SLOTS=<rows>         rows of the per-block LDS table of the per-cell accumulation (default and upper bound 512, rounded down to a
- *                                         power of two; tests: a small table reaches the path of the rows that do not fit with small inputs)
+ *                                         power of two; tests: a small table reaches the path of the rows that do not fit with small inputs).  The same
+ *                                         number governs the table of the per-feature / per-SNP accumulation (default and upper bound 1024 there)
+ *   XCK_FEATURE_SUMMARY=1                 every handle that drives a GPU also keeps the per-feature and per-SNP tables, as if made with
+ *                                         XCK_F_FEATURE_SUMMARY (xck_get_feature_summary): the front-ends then write feature_summary.tsv and, for the
+ *                                         pileup, snp_summary.tsv next to their matrices.  One kernel more per join launch; does not imply XCK_READ_FATE.
+ *                                         Off (the default, or 0) nothing is allocated or launched.  Decode-only handles ignore it.
  * Decoder (read when a BAM is opened or once per process): XCK_THREADS, XCK_NUMA=0, XCK_INFLATE=zlib, XCK_CHUNK_BYTES,
  * XCK_WRITE_THREADS (writer threads of xck_write_mtx), XCK_TEST_INTERN_LIMIT (tests). */
 #ifndef XCK_H
@@ -161,6 +166,11 @@ typedef struct xck_config {
                                    the matrices (xck_get_cell_summary).  Implies XCK_F_READ_FATE (the global counters cost nothing
                                    extra): the per-cell instantiation of that kernel runs in its place.  Changes no result.
                                    XCK_E_ARG together with XCK_F_DECODE_ONLY                                              */
+#define XCK_F_FEATURE_SUMMARY 128 /* per-feature and per-SNP tables: which regions lose reads to the include test or share them with an
+                                   overlapping region, which SNPs the reads cover, and after xck_finish the row marginals of the
+                                   matrices and the allele tallies and filter verdict of every SNP (xck_get_feature_summary; one more
+                                   kernel behind every join launch).  Does not imply XCK_F_READ_FATE; combines freely with it and with
+                                   XCK_F_CELL_SUMMARY.  Changes no result.  XCK_E_ARG together with XCK_F_DECODE_ONLY            */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -283,6 +293,37 @@ typedef struct xck_cell_summary {
     const int64_t* matrix;      /* [n_cells * n_matrix_cols], row-major; NULL while has_matrix == 0                             */
 } xck_cell_summary;
 
+/* The per-feature and per-SNP tables of ONE pipeline, since the last xck_reset (handles made with XCK_F_FEATURE_SUMMARY; additive, ABI 3 is
+ * unchanged).  All arrays are row-major int64 in the caller's INPUT order of xck_config.regions / xck_config.snps (a region or SNP the
+ * engine's tables leave out - contig outside the table, SNP position < 1 - keeps a row of zeros), engine-owned host memory, valid until
+ * the next xck_get_feature_summary, xck_reset or xck_destroy on the handle.
+ * reads (basefc only, available before xck_finish): over the (read, region) pairs of the reads that pass everything up to short_aligned in
+ *   the classes of xck_read_fate - check_read, a listed cell, a non-empty key, min_len: include_fail = pairs that pass the fetch overlap
+ *   (pos < end0 && endpos > start0) but fail min_include; pairs = pairs the join accepts (the column sums to the pipeline's share of
+ *   xck_stats.n_hits); shared = accepted pairs whose read is accepted by two or more regions.  Duplicate regions each get their own numbers.
+ * matrix (after xck_finish), computed on the device from the result blocks the first time the table is asked for after the finish:
+ *   basefc  umis (row sum of count), cells (entries of the row);
+ *   BAF     snps (SNPs of the list joined to the region, after excl_region / excl_snp), snps_kept (those that pass min_count / min_maf),
+ *           ad, dp, oth (row sums), cells (entries of the DP row).
+ * snp (BAF only): reads = filtered reads whose fetch span covers the SNP (pos <= p0 < endpos, a SNP inside an N gap included: the per-SNP
+ *   split of xck_read_fate.pairs; available before xck_finish); a c g t n = the pseudo-bulk tallies of the fold, one count per
+ *   (cell, UMI) that shows a base (the reference's MCount.tcount order); kept = verdict of the fold's own per-SNP filter (plp_snp,
+ *   baf/fc/core.py:238-246) under xck_config.min_count / min_maf of THIS handle, 0 or 1 (a front-end that filters later, on sums of the
+ *   matrices, creates the handle with 1 / 0: kept then only says that a molecule showed a base); regions = regions the SNP feeds.  Tallies and kept are zero while has_matrix == 0. */
+typedef struct xck_feature_summary {
+    uint32_t struct_size;
+    int32_t  mode;              /* XCK_MODE_BASEFC or XCK_MODE_BAF: the pipeline, as xck_read_fate.mode                          */
+    int32_t  n_regions;         /* rows of reads and matrix                                                                    */
+    int32_t  n_read_cols;       /* basefc 3: include_fail, pairs, shared; BAF 0                                                */
+    const int64_t* reads;       /* [n_regions * n_read_cols]; NULL for the BAF pipeline                                        */
+    int32_t  has_matrix;        /* 1 once xck_finish has run since the last xck_reset                                          */
+    int32_t  n_matrix_cols;     /* basefc 2, BAF 6 (see above)                                                                 */
+    const int64_t* matrix;      /* [n_regions * n_matrix_cols]; NULL while has_matrix == 0                                     */
+    int32_t  n_snps;            /* BAF: xck_config.n_snps; basefc 0                                                            */
+    int32_t  n_snp_cols;        /* BAF 8: reads, a, c, g, t, n, kept, regions                                                  */
+    const int64_t* snp;         /* [n_snps * n_snp_cols]; NULL for the basefc pipeline                                         */
+} xck_feature_summary;
+
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
 
@@ -339,6 +380,12 @@ int  xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out);
  * without XCK_F_CELL_SUMMARY, XCK_E_ARG for a pipeline the handle does not have or a short struct_size.  The caveat about cut contigs
  * of xck_get_read_fate holds per cell. */
 int  xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out);
+/* The per-feature / per-SNP tables of one pipeline (set out->struct_size first); mode as for xck_get_read_fate.  Waits for the handle's
+ * queued work as xck_flush does; after xck_finish the first call also runs the small kernels of the matrix rows and the SNP verdicts, and
+ * later calls return the same numbers.  XCK_E_STATE on a handle made without XCK_F_FEATURE_SUMMARY, XCK_E_ARG for a pipeline the handle
+ * does not have or a short struct_size.  With contigs cut over several GPUs every handle counts the regions it was given; the SNPs
+ * near a cut are seen by both neighbours. */
+int  xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

@@ -26,6 +26,7 @@ int  engine_reset(EngineImpl*) { return XCK_E_ARG; }
 int  engine_stats(const EngineImpl*, xck_stats*) { return XCK_E_ARG; }
 int  engine_read_fate(EngineImpl*, xck_read_fate*) { return XCK_E_ARG; }
 int  engine_cell_summary(EngineImpl*, xck_cell_summary*) { return XCK_E_ARG; }
+int  engine_feature_summary(EngineImpl*, xck_feature_summary*) { return XCK_E_ARG; }
 int  engine_numa_node(const xck_engine*) { return -1; }
 int  engine_device(const xck_engine*) { return -1; }                          // no device: the decoder's GPU share of the inflate never starts
 GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }

@@ -21,6 +21,7 @@ XCK_F_LOW_PRIORITY = 8
 XCK_F_DEVICE_CRC = 16
 XCK_F_READ_FATE = 32
 XCK_F_CELL_SUMMARY = 64
+XCK_F_FEATURE_SUMMARY = 128
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -128,6 +129,18 @@ CELL_FATE_COLS = READ_FATE_FIELDS[2:]
 CELL_MATRIX_COLS = {XCK_MODE_BASEFC: ("umis", "features"), XCK_MODE_BAF: ("ad", "dp", "oth", "features")}
 
 
+class FeatureSummary(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("n_regions", C.c_int32), ("n_read_cols", C.c_int32),
+                ("reads", C.POINTER(C.c_int64)), ("has_matrix", C.c_int32), ("n_matrix_cols", C.c_int32),
+                ("matrix", C.POINTER(C.c_int64)), ("n_snps", C.c_int32), ("n_snp_cols", C.c_int32), ("snp", C.POINTER(C.c_int64))]
+
+
+# the columns of xck_feature_summary.reads (basefc), of .matrix per pipeline and of .snp (BAF)
+FEATURE_READ_COLS = ("include_fail", "pairs", "shared")
+FEATURE_MATRIX_COLS = {XCK_MODE_BASEFC: ("umis", "cells"), XCK_MODE_BAF: ("snps", "snps_kept", "ad", "dp", "oth", "cells")}
+SNP_COLS = ("reads", "a", "c", "g", "t", "n", "kept", "regions")
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -162,6 +175,7 @@ SYMBOLS = [
     ("xck_get_decode_stats", C.c_int, [C.c_void_p, _P(DecodeStats)]),
     ("xck_get_read_fate", C.c_int, [C.c_void_p, C.c_int, _P(ReadFate)]),
     ("xck_get_cell_summary", C.c_int, [C.c_void_p, C.c_int, _P(CellSummary)]),
+    ("xck_get_feature_summary", C.c_int, [C.c_void_p, C.c_int, _P(FeatureSummary)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

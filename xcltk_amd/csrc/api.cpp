@@ -61,6 +61,7 @@ Knobs xck::Knobs::from_env() {
     k.verify_crc = !strcmp(str("XCK_VERIFY_CRC"), "device") ? 2 : (!*str("XCK_VERIFY_CRC") || !strcmp(str("XCK_VERIFY_CRC"), "0")) ? 0 : 1;   // (any other value: host)
     k.read_fate = num("XCK_READ_FATE", 0) != 0;
     k.cell_summary = num("XCK_CELL_SUMMARY", 0) != 0;
+    k.feature_summary = num("XCK_FEATURE_SUMMARY", 0) != 0;
     k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
     return k;
 }
@@ -78,9 +79,11 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if ((cfg->n_regions > 0 && !cfg->regions) || (cfg->n_snps > 0 && !cfg->snps)) { set_thread_error("null table pointer"); return XCK_E_ARG; }
     if ((cfg->flags & XCK_F_READ_FATE) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_READ_FATE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
     if ((cfg->flags & XCK_F_CELL_SUMMARY) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_CELL_SUMMARY needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+    if ((cfg->flags & XCK_F_FEATURE_SUMMARY) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_FEATURE_SUMMARY needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
     e->cell_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_CELL_SUMMARY) || e->knobs.cell_summary);
+    e->feature_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_FEATURE_SUMMARY) || e->knobs.feature_summary);   // (does not imply the read summary)
     e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate || e->cell_summary);
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
@@ -94,6 +97,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             if (n == 2) c.flags |= XCK_F_LAYOUT_BOTH;          // one key layout -> one decode serves both pipelines
             if (e->read_fate) c.flags |= XCK_F_READ_FATE;      // (XCK_READ_FATE=1, or implied by the per-cell table)
             if (e->cell_summary) c.flags |= XCK_F_CELL_SUMMARY;  // (XCK_CELL_SUMMARY=1)
+            if (e->feature_summary) c.flags |= XCK_F_FEATURE_SUMMARY;  // (XCK_FEATURE_SUMMARY=1)
             const int rc = engine_create(&c, e, &e->impls[k]);
             e->n_impl = k + 1;                                 // (a pipeline that failed half-way is destroyed with the rest)
             if (rc) { set_thread_error(e->err); xck_destroy(e); return rc; }
@@ -124,7 +128,7 @@ static int for_pipelines(xck_engine* e, const std::function<int(EngineImpl*)>& f
     for (int k = 0; k < e->n_impl; k++) if (int rc = fn(e->impls[k])) return rc;
     return XCK_OK;
 }
-// the pipeline that xck_get_read_fate / xck_get_cell_summary ask about, or null with e->err set
+// the pipeline that xck_get_read_fate / xck_get_cell_summary / xck_get_feature_summary ask about, or null with e->err set
 static EngineImpl* pipeline_of(xck_engine* e, int mode, const char* who) {
     if ((mode != XCK_MODE_BASEFC && mode != XCK_MODE_BAF) || !(e->mode & mode)) { e->err = std::string(who) + ": the handle has no such pipeline"; return nullptr; }
     return e->impls[e->mode == XCK_MODE_BOTH && mode == XCK_MODE_BAF ? 1 : 0];
@@ -267,6 +271,17 @@ int xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out) {
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
     return engine_cell_summary(im, out);
+}
+
+int xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_feature_summary)) { e->err = "xck_feature_summary.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (!e->feature_summary || e->n_impl <= 0) { e->err = "handle made without XCK_F_FEATURE_SUMMARY"; return XCK_E_STATE; }
+    EngineImpl* im = pipeline_of(e, mode, "xck_get_feature_summary");
+    if (!im) return XCK_E_ARG;
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    return engine_feature_summary(im, out);
 }
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }

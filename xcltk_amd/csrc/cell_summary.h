@@ -40,28 +40,34 @@ struct CellArgs {
     int32_t  wide_col;                    // table column of the 64-bit sum
 };
 
-struct CellLds {
-    uint32_t cnt[CS_SLOTS * (CS_C32 + 1)];      // per row: CS_C32 counters, then the key
-    unsigned long long wide[CS_SLOTS];          // per row: the 64-bit sum
-    uint16_t list[CS_SLOTS];                    // the occupied rows, in the order they were claimed
+// The LDS table of a block: SLOTS rows of C32 32-bit counters and the row's key, a 64-bit sum per row when WIDE.  The per-cell
+// table is CellLds; the per-feature and per-SNP tables (feature_summary.h) carry three counters and one, no sum, and so twice the rows.
+template <int C32, int SLOTS, bool WIDE>
+struct SumLds {
+    uint32_t cnt[SLOTS * (C32 + 1)];            // per row: C32 counters, then the key
+    unsigned long long wide[WIDE ? SLOTS : 1];  // per row: the 64-bit sum
+    uint16_t list[SLOTS];                       // the occupied rows, in the order they were claimed
     uint32_t n_list;
 };
+typedef SumLds<CS_C32, CS_SLOTS, true> CellLds;
 
 // the block's table (ON = false: no LDS at all)
 template <bool ON> __device__ __forceinline__ CellLds* cs_lds() {
     if constexpr (ON) { __shared__ CellLds s; return &s; } else return nullptr;
 }
 
-__device__ __forceinline__ void cs_init(CellLds& s, const CellArgs& ca, const int tid) {
+template <int C32, int SLOTS, bool WIDE>
+__device__ __forceinline__ void cs_init(SumLds<C32, SLOTS, WIDE>& s, const CellArgs& ca, const int tid) {
     const uint32_t slots = ca.slot_mask + 1u;
-    for (uint32_t k = tid; k < slots * (CS_C32 + 1); k += JOIN_BLOCK) s.cnt[k] = (k % (CS_C32 + 1)) == CS_C32 ? CS_EMPTY : 0u;
-    for (uint32_t k = tid; k < slots; k += JOIN_BLOCK) s.wide[k] = 0ull;
+    for (uint32_t k = tid; k < slots * (C32 + 1); k += JOIN_BLOCK) s.cnt[k] = (k % (C32 + 1)) == C32 ? CS_EMPTY : 0u;
+    if constexpr (WIDE) for (uint32_t k = tid; k < slots; k += JOIN_BLOCK) s.wide[k] = 0ull;
     if (tid == 0) s.n_list = 0u;
 }
 
 // One contribution per valid lane: +1 in the 32-bit column c32 of `row`, +wv in its 64-bit sum, +1 in column xcol when `extra`.
 // Every lane of the wave calls it (wave-uniform control flow).
-__device__ __forceinline__ void cs_add(CellLds& s, const CellArgs& ca, const int lane, const bool valid, const int32_t row, const int c32,
+template <int C32, int SLOTS, bool WIDE>
+__device__ __forceinline__ void cs_add(SumLds<C32, SLOTS, WIDE>& s, const CellArgs& ca, const int lane, const bool valid, const int32_t row, const int c32,
                                        const uint32_t wv, const bool extra, const int xcol) {
     // step 1: one round per distinct (row, c32) of the wave; the lowest lane of a group keeps the group's sums
     unsigned long long todo = __ballot(valid);
@@ -72,7 +78,7 @@ __device__ __forceinline__ void cs_add(CellLds& s, const CellArgs& ca, const int
         const bool in = valid && row == r && c32 == c;
         const unsigned long long same = __ballot(in);
         unsigned long long w = 0;
-        if (__ballot(in && wv != 0u)) {
+        if (WIDE && __ballot(in && wv != 0u)) {
             if (!(same & (same - 1))) w = (uint32_t)__builtin_amdgcn_readlane((int)wv, ld);      // a group of one
             else {
                 w = in ? wv : 0u;
@@ -89,15 +95,15 @@ __device__ __forceinline__ void cs_add(CellLds& s, const CellArgs& ca, const int
     uint32_t h = (((uint32_t)row * 0x9E3779B1u) >> 16) & ca.slot_mask;
     int slot = -1;
     for (int q = 0; q < CS_PROBES; q++) {
-        const uint32_t old = atomicCAS(&s.cnt[h * (CS_C32 + 1) + CS_C32], CS_EMPTY, (uint32_t)row);
+        const uint32_t old = atomicCAS(&s.cnt[h * (C32 + 1) + C32], CS_EMPTY, (uint32_t)row);
         if (old == CS_EMPTY) { s.list[atomicAdd(&s.n_list, 1u)] = (uint16_t)h; slot = (int)h; break; }
         if (old == (uint32_t)row) { slot = (int)h; break; }
         h = (h + 1u) & ca.slot_mask;
     }
     if (slot >= 0) {
-        atomicAdd(&s.cnt[slot * (CS_C32 + 1) + c32], g_n);
-        if (g_x) atomicAdd(&s.cnt[slot * (CS_C32 + 1) + xcol], g_x);
-        if (g_w) atomicAdd(&s.wide[slot], g_w);
+        atomicAdd(&s.cnt[slot * (C32 + 1) + c32], g_n);
+        if (g_x) atomicAdd(&s.cnt[slot * (C32 + 1) + xcol], g_x);
+        if (WIDE && g_w) atomicAdd(&s.wide[slot], g_w);
     } else {                                                   // no slot within CS_PROBES: straight to HBM
         unsigned long long* t = ca.tab + (size_t)row * ca.stride;
         if (ca.c32_base >= 0) { atomicAdd(&t[ca.c32_base + c32], (unsigned long long)g_n); if (g_x) atomicAdd(&t[ca.c32_base + xcol], (unsigned long long)g_x); }
@@ -105,16 +111,19 @@ __device__ __forceinline__ void cs_add(CellLds& s, const CellArgs& ca, const int
     }
 }
 
-// step 3, behind a __syncthreads(): 16 lanes per occupied row
-__device__ __forceinline__ void cs_flush(CellLds& s, const CellArgs& ca, const int tid) {
+// step 3, behind a __syncthreads(): LPR lanes per occupied row (16 for the twelve columns of the per-cell table)
+template <int C32, int SLOTS, bool WIDE>
+__device__ __forceinline__ void cs_flush(SumLds<C32, SLOTS, WIDE>& s, const CellArgs& ca, const int tid) {
+    constexpr int COLS = C32 + (WIDE ? 1 : 0), LPR = COLS <= 1 ? 1 : COLS <= 4 ? 4 : 16;
+    static_assert(COLS <= 16, "a row is flushed by at most 16 lanes");
     const uint32_t n = s.n_list;
-    const int j = tid & 15;
-    for (uint32_t k = tid >> 4; k < n; k += JOIN_BLOCK / 16) {
+    const int j = tid & (LPR - 1);
+    for (uint32_t k = tid / LPR; k < n; k += JOIN_BLOCK / LPR) {
         const uint32_t slot = s.list[k];
-        const uint32_t row = s.cnt[slot * (CS_C32 + 1) + CS_C32];
+        const uint32_t row = s.cnt[slot * (C32 + 1) + C32];
         unsigned long long v = 0; int col = -1;
-        if (j < CS_C32) { v = s.cnt[slot * (CS_C32 + 1) + j]; col = ca.c32_base >= 0 ? ca.c32_base + j : -1; }
-        else if (j == CS_C32) { v = s.wide[slot]; col = ca.wide_col; }
+        if (j < C32) { v = s.cnt[slot * (C32 + 1) + j]; col = ca.c32_base >= 0 ? ca.c32_base + j : -1; }
+        else if (WIDE && j == C32) { v = s.wide[slot]; col = ca.wide_col; }
         if (v && col >= 0) atomicAdd(&ca.tab[(size_t)row * ca.stride + col], v);
     }
 }
@@ -142,9 +151,9 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_cell_marginals(MargArgs a) {
     cs_flush(s, a.ca, tid);
 }
 
-static uint32_t cs_slot_mask(const EngineImpl* im) {
+static uint32_t cs_slot_mask(const EngineImpl* im, const int slots = CS_SLOTS) {
     long long want = im->eng->knobs.cell_summary_slots;
-    if (want <= 0 || want > CS_SLOTS) want = CS_SLOTS;
+    if (want <= 0 || want > slots) want = slots;
     uint32_t p = 1; while ((long long)p * 2 <= want) p *= 2;
     return p - 1u;
 }

@@ -946,6 +946,10 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
             for (int32_t k = 0; k < t.n_snp; k++) { std::sort(hits[k].begin(), hits[k].end()); for (int32_t g : hits[k]) csr_reg.push_back(g); csr_off.push_back((int32_t)csr_reg.size()); }
         }
         im->n_snps_sorted = (int)snp_p0.size();
+        if (cfg->flags & XCK_F_FEATURE_SUMMARY) {              // the per-SNP summary answers in the caller's order
+            for (int c = 0; c < nc; c++) im->snp_perm.insert(im->snp_perm.end(), by_c[c].begin(), by_c[c].end());
+            im->h_csr_off = csr_off; im->h_csr_reg = csr_reg; im->n_snps_in = cfg->n_snps;
+        }
     }
     int rc;
     if ((rc = dev_upload(im, &im->d_reg_s0, reg_s0))) return rc;
@@ -1077,6 +1081,7 @@ static int launch_join(EngineImpl* im) { return im->key_bits == 64 ? launch_join
 
 #include "cell_summary.h"
 #include "read_fate.h"
+#include "feature_summary.h"
 
 // wait for the launch in flight, collect cursor / timing; if its fragments did not fit, grow, rewind and replay
 int complete_pending(EngineImpl* im) {
@@ -1131,7 +1136,8 @@ int launch_queue(EngineImpl* im, int slot_idx, int shared_slot) {
     for (int sh = 0; sh < NSHARD; sh++) { im->cur_before[sh] = im->cur[sh]; im->ncur_before[sh] = im->ncur[sh]; im->acc_before[sh] = im->h_ctl[ctl_accepted(sh)]; }
     if (slot_idx >= 0) im->slot[slot_idx].busy = true;
     rc = launch_join(im); if (rc) return rc;
-    return launch_read_fate(im);                               // (off: returns at once)
+    rc = launch_read_fate(im); if (rc) return rc;              // (off: returns at once)
+    return launch_feature_fate(im);                            // (likewise)
 }
 
 // ---- the push paths ----
@@ -1308,6 +1314,7 @@ int engine_reset(EngineImpl* im) {
     if (im->d_fate) HIP_TRY(hipMemsetAsync(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long), im->s_comp));
     if (im->d_cell) HIP_TRY(hipMemsetAsync(im->d_cell, 0, ((size_t)im->n_cells + 1) * CS_ROW_WORDS * sizeof(unsigned long long), im->s_comp));
     im->cmat_valid = false;
+    if (im->d_feat) { rc = feature_summary_reset(im); if (rc) return rc; }
     im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false;
@@ -1382,6 +1389,7 @@ int engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out) {
         HIP_TRY(hipMemset(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long)));
     }
     if (cfg->flags & XCK_F_CELL_SUMMARY) { rc = cell_summary_init(im); if (rc) return rc; }
+    if (cfg->flags & XCK_F_FEATURE_SUMMARY) { rc = feature_summary_init(im); if (rc) return rc; }
     return 0;
 }
 
@@ -1390,7 +1398,7 @@ void engine_destroy(EngineImpl* im) {
     hipSetDevice(im->device);
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
-                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat,
+                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept,
                      im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }

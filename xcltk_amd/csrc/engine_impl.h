@@ -190,6 +190,16 @@ struct EngineImpl {
     unsigned long long* d_cell = nullptr; unsigned long long* d_cmat = nullptr;
     std::vector<int64_t> h_cell_raw, h_cell, h_cmat;
     bool cmat_valid = false;
+    // per-feature / per-SNP tables (XCK_F_FEATURE_SUMMARY, feature_summary.h): the read half in HBM (null = off; basefc [n_regions * 4]
+    // words by the caller's region index, pileup one word per SNP of the sorted table), the row marginals of the last finish, the
+    // verdicts of snp_passes(), and the host copies xck_get_feature_summary hands out.  snp_perm: sorted SNP -> the caller's index;
+    // h_csr_off / h_csr_reg: the SNP -> region relation as uploaded (these three are kept only with the flag)
+    unsigned long long* d_feat = nullptr; unsigned long long* d_fmat = nullptr; uint32_t* d_kept = nullptr;
+    std::vector<int64_t> h_feat_raw, h_feat, h_fmat;
+    std::vector<uint32_t> h_tally, h_kept;
+    std::vector<int32_t> snp_perm, h_csr_off, h_csr_reg;
+    int n_snps_in = 0;
+    bool fmat_valid = false;
 };
 
 // host helpers defined in engine.hip
@@ -203,5 +213,6 @@ int launch_queue(EngineImpl* im, int slot_idx, int shared_slot = -1);
 void join_stamps_report(const EngineImpl* im);             // XCK_STAMPS builds: the phase table of the last join launch
 // defined in finish.hip
 int finish_init(EngineImpl* im);                           // engine_create: per-device attributes of the fold kernels
+int snp_verdicts(EngineImpl* im, uint32_t* d_kept);        // d_kept[s] = snp_passes() of sorted SNP s on the tallies of the last finish (enqueued on s_comp)
 
 }  // namespace xck

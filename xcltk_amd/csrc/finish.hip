@@ -496,6 +496,12 @@ __device__ __forceinline__ bool snp_passes(const uint32_t* tally, const uint32_t
     return true;
 }
 
+// the verdict itself, per SNP of the sorted table, for the per-SNP summary (feature_summary.h): the rule is stated above and only there
+__global__ void __launch_bounds__(256) k_snp_verdict(const uint32_t* __restrict__ tally, const uint32_t* __restrict__ info, uint32_t n, SnpFilter f, uint32_t* __restrict__ kept) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s < n) kept[s] = snp_passes(tally, info, s, f) ? 1u : 0u;
+}
+
 // BAF step 2: expand each surviving (snp, cell, umi, allele) to the regions that contain the SNP
 // (baf/fc/main.py:92-101, core.py:156-166).  COUNT pass sums the fan-out, EMIT pass writes.
 template <class K, bool EMIT, class V>
@@ -1402,6 +1408,14 @@ int engine_result_device(EngineImpl* im, xck_result* out) {
         dst[m]->nnz = (int64_t)z;
         if (z && im->d_res[m]) { dst[m]->row = im->d_res[m]; dst[m]->col = im->d_res[m] + z; dst[m]->val = im->d_res[m] + 2 * z; }
     }
+    return 0;
+}
+
+int snp_verdicts(EngineImpl* im, uint32_t* d_kept) {
+    const uint32_t n = (uint32_t)im->n_snps_sorted;
+    if (!n) return 0;
+    hipLaunchKernelGGL(k_snp_verdict, dim3((n + 255) / 256), dim3(256), 0, im->s_comp, (const uint32_t*)im->d_tally, (const uint32_t*)im->d_snp_info, n, im->sf, d_kept);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

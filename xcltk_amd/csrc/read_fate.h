@@ -38,9 +38,52 @@ __device__ __forceinline__ int32_t rf_bisect(const int32_t* v, int32_t lo, int32
     return lo;
 }
 
-// class of read i of batch d; n_pairs = regions that accept it / SNPs it covers (0 unless the class is RF_ASSIGNED)
-template <int MODE>
-__device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& d, const int32_t i, uint32_t& n_pairs) {
+// What the walk keeps of a read that passed the filter, for a caller that comes back to it: fetch span, aligned bases, CIGAR words
+struct RfSpan { int32_t pos, endpos, n_al; uint32_t c0, c1; bool span_is_cigar; };
+
+// The targets of a read that passed the filter, seen through two hooks:
+//   on_region(k, accepted)  basefc: region k of the start-sorted arrays fetches the read; false stops the walk
+//   on_snps(k0, k1)         pileup: SNPs [k0, k1) of the sorted table lie under the read's fetch span
+// k_from: first region to look at (< 0: the read's first candidate).  Returns the class; n_pairs as read_fate_walk.
+template <int MODE, class OnRegion, class OnSnps>
+__device__ __forceinline__ int rf_targets(const FateArgs& a, const BatchDesc& d, const RfSpan sp, const int32_t k_from, uint32_t& n_pairs, OnRegion on_region, OnSnps on_snps) {
+    const int32_t pos = sp.pos, endpos = sp.endpos, n_al = sp.n_al; const uint32_t c0 = sp.c0, c1 = sp.c1; const bool span_is_cigar = sp.span_is_cigar;
+    const auto word_at = [&](uint32_t c) { return as_global(d.cigar)[c]; };
+    if (MODE == XCK_MODE_BASEFC) {
+        ReadInfo r = {}; r.pos = pos; r.endpos = endpos; r.n_al = n_al; r.c0 = c0; r.c1 = c1; r.span_is_cigar = span_is_cigar;   // (what included_len() and frac_below() read)
+        uint32_t n_ov = 0;
+        // every region before the first one whose running-maximum end lies beyond pos ends at or before pos
+        for (int32_t k = k_from < 0 ? rf_bisect<true>(a.reg_pmax, d.reg_lo, d.reg_hi, pos) : k_from; k < d.reg_hi; k++) {
+            const int32_t s0 = as_global(a.reg_s0)[k];
+            if (s0 >= endpos) break;                                  // sorted by start
+            const int32_t e0 = as_global(a.reg_e0)[k];
+            if (!(pos < e0)) continue;                                // htslib fetch overlap: pos < end0 && endpos > start0
+            n_ov++;
+            const int32_t m = included_len(word_at, r, s0, e0);
+            if (a.f.frac_mode) {                                      // rdr/fc/core.py:160-165, exactly as join_regions()
+                if (n_al <= 0) { if (on_region(k, false)) continue; break; }
+                if (m != n_al && frac_below(m, r, a.f.min_inc_frac)) { if (on_region(k, false)) continue; break; }
+            } else if (m < a.f.min_inc_len) { if (on_region(k, false)) continue; break; }
+            n_pairs++;
+            if (!on_region(k, true)) break;
+        }
+        return n_pairs ? RF_ASSIGNED : n_ov ? RF_INCLUDE_FAIL : RF_NO_TARGET;
+    } else {
+        // SNPs of the contig with pos <= p0 < endpos (whether a SNP lies in a region is not asked: the join does not ask either)
+        const int32_t snp_lo = d.n_swin > 0 ? as_global(d.snp_win)[0] : d.snp_end;   // window 0 starts at the contig's first SNP
+        const int32_t k0 = rf_bisect<false>(a.snp_p0, snp_lo, d.snp_end, pos);
+        const int32_t k1 = rf_bisect<false>(a.snp_p0, k0, d.snp_end, endpos);
+        n_pairs = (uint32_t)(k1 - k0);
+        on_snps(k0, k1);
+        return n_pairs ? RF_ASSIGNED : RF_NO_TARGET;
+    }
+}
+
+// Class of read i of batch d; n_pairs = regions that accept it / SNPs it covers (0 unless the class is RF_ASSIGNED).  The one statement
+// of the read filter outside the join, in front of the one statement of the accept rule (rf_targets): every pass that follows the
+// join (k_read_fate*, k_feature_fate of feature_summary.h) goes through here.  sp: filled when the read passes the filter.
+template <int MODE, class OnRegion, class OnSnps>
+__device__ __forceinline__ int read_fate_walk(const FateArgs& a, const BatchDesc& d, const int32_t i, uint32_t& n_pairs, RfSpan& sp, OnRegion on_region, OnSnps on_snps) {
     n_pairs = 0;
     const uint32_t flag = as_global(d.flag)[i];
     const int32_t mapq = as_global(d.mapq)[i];
@@ -60,32 +103,14 @@ __device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& 
     const bool span_is_cigar = !((flag & BAM_FUNMAP) || c1 == c0 || rlen == 0);
     if (!span_is_cigar) rlen = 1;
     const int32_t pos = as_global(d.pos)[i], endpos = pos + rlen;
-    if (MODE == XCK_MODE_BASEFC) {
-        ReadInfo r = {}; r.pos = pos; r.endpos = endpos; r.n_al = n_al; r.c0 = c0; r.c1 = c1; r.span_is_cigar = span_is_cigar;   // (what included_len() and frac_below() read)
-        uint32_t n_ov = 0;
-        // every region before the first one whose running-maximum end lies beyond pos ends at or before pos
-        for (int32_t k = rf_bisect<true>(a.reg_pmax, d.reg_lo, d.reg_hi, pos); k < d.reg_hi; k++) {
-            const int32_t s0 = as_global(a.reg_s0)[k];
-            if (s0 >= endpos) break;                                  // sorted by start
-            const int32_t e0 = as_global(a.reg_e0)[k];
-            if (!(pos < e0)) continue;                                // htslib fetch overlap: pos < end0 && endpos > start0
-            n_ov++;
-            const int32_t m = included_len(word_at, r, s0, e0);
-            if (a.f.frac_mode) {                                      // rdr/fc/core.py:160-165, exactly as join_regions()
-                if (n_al <= 0) continue;
-                if (m != n_al && frac_below(m, r, a.f.min_inc_frac)) continue;
-            } else if (m < a.f.min_inc_len) continue;
-            n_pairs++;
-        }
-        return n_pairs ? RF_ASSIGNED : n_ov ? RF_INCLUDE_FAIL : RF_NO_TARGET;
-    } else {
-        // SNPs of the contig with pos <= p0 < endpos (whether a SNP lies in a region is not asked: the join does not ask either)
-        const int32_t snp_lo = d.n_swin > 0 ? as_global(d.snp_win)[0] : d.snp_end;   // window 0 starts at the contig's first SNP
-        const int32_t k0 = rf_bisect<false>(a.snp_p0, snp_lo, d.snp_end, pos);
-        const int32_t k1 = rf_bisect<false>(a.snp_p0, k0, d.snp_end, endpos);
-        n_pairs = (uint32_t)(k1 - k0);
-        return n_pairs ? RF_ASSIGNED : RF_NO_TARGET;
-    }
+    sp.pos = pos; sp.endpos = endpos; sp.n_al = n_al; sp.c0 = c0; sp.c1 = c1; sp.span_is_cigar = span_is_cigar;
+    return rf_targets<MODE>(a, d, sp, -1, n_pairs, on_region, on_snps);
+}
+// ... for a pass that only counts: no hooks
+template <int MODE>
+__device__ __forceinline__ int read_fate_of(const FateArgs& a, const BatchDesc& d, const int32_t i, uint32_t& n_pairs) {
+    RfSpan sp;
+    return read_fate_walk<MODE>(a, d, i, n_pairs, sp, [](int32_t, bool) { return true; }, [](int32_t, int32_t) {});
 }
 
 // Block t covers the TILE reads of join tile t.  Per class a wave ballot + popcount (wave-uniform counts), the sums by a wave
@@ -143,18 +168,26 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_read_fate_cell(FateArgs a, CellA
 static_assert(sizeof(FateArgs) + sizeof(CellArgs) <= 4000, "kernel arguments must stay under the 4 KiB kernarg limit");
 static_assert(RF_WORDS == CS_ROW_WORDS && RF_USED == CS_COLS && RF_MULTI < CS_C32 && RF_PAIRS == CS_C32, "the per-cell table keeps the columns of the global words");
 
-// Runs once per batch: called by launch_queue() behind the FIRST join launch of the batches in im->inflight (whose tile0 that
-// launch has set), on the same stream - so it is over before complete_pending() hands their staging slot back - and never by the
-// overflow replay.
-static int launch_read_fate(EngineImpl* im) {
-    if (!im->d_fate || im->inflight.empty()) return 0;
-    FateArgs a;
+// The arguments every pass behind the join shares (launch_read_fate, launch_feature_fate of feature_summary.h): the batches in
+// im->inflight with the join's tile numbering, the filter, the tables.  -> tiles = blocks of the launch; a.out is the caller's.
+static int32_t fill_fate_args(const EngineImpl* im, FateArgs& a) {
     const int nb = (int)im->inflight.size();
     int32_t tiles = 0;
     for (int i = 0; i < nb; i++) { a.bt.desc[i] = im->inflight[i]; tiles += (im->inflight[i].n + TILE - 1) / TILE; }
     a.bt.n_batches = nb; a.bt.n_tiles = tiles;
     a.f = im->rf;
     a.reg_s0 = im->d_reg_s0; a.reg_e0 = im->d_reg_e0; a.reg_pmax = im->d_reg_pmax; a.snp_p0 = im->d_snp_p0;
+    a.out = nullptr;
+    return tiles;
+}
+
+// Runs once per batch: called by launch_queue() behind the FIRST join launch of the batches in im->inflight (whose tile0 that
+// launch has set), on the same stream - so it is over before complete_pending() hands their staging slot back - and never by the
+// overflow replay.
+static int launch_read_fate(EngineImpl* im) {
+    if (!im->d_fate || im->inflight.empty()) return 0;
+    FateArgs a;
+    const int32_t tiles = fill_fate_args(im, a);
     a.out = im->d_fate;
     if (im->d_cell) {                                          // (XCK_F_CELL_SUMMARY: the instantiation that also fills the per-cell table)
         CellArgs ca;

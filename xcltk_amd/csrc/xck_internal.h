@@ -114,7 +114,8 @@ struct Knobs {
     int  gpu_inflate_free_cus = 32;      // XCK_GPU_INFLATE_FREE_CUS: CUs the inflate streams never use (they stay free for the join kernels)
     bool read_fate = false;              // XCK_READ_FATE=1: XCK_F_READ_FATE ORed into the flags of every handle that drives a GPU
     bool cell_summary = false;           // XCK_CELL_SUMMARY=1: XCK_F_CELL_SUMMARY ORed into the flags of every handle that drives a GPU
-    int  cell_summary_slots = 0;         // XCK_CELL_SUMMARY_SLOTS: rows of the per-block LDS table (0 = the built-in 512; tests: small tables reach the no-fit path)
+    int  cell_summary_slots = 0;         // XCK_CELL_SUMMARY_SLOTS: rows of the per-block LDS tables (0 = the built-in 512 per-cell, 1024 per-feature / per-SNP; tests: small tables reach the no-fit path)
+    bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
     int  verify_crc = 0;                 // XCK_VERIFY_CRC: 0 = as the flags say, 1 = host (XCK_F_VERIFY_CRC ORed in), 2 = device (XCK_F_DEVICE_CRC)
     static Knobs from_env();             // api.cpp
 };
@@ -151,6 +152,7 @@ struct xck_engine {
     int mode = 0;
     bool read_fate = false;              // made with XCK_F_READ_FATE (or XCK_READ_FATE=1), or with the flag below, which implies it
     bool cell_summary = false;           // made with XCK_F_CELL_SUMMARY (or XCK_CELL_SUMMARY=1)
+    bool feature_summary = false;        // made with XCK_F_FEATURE_SUMMARY (or XCK_FEATURE_SUMMARY=1)
     int umi_bits = 64;
     int32_t n_cells = 0, n_contigs = 0;  // bounds that caller-supplied batches are checked against (xck_push_batch)
     // host pinned batch staging used by xck_ingest_bam lives in the xck_bam
@@ -170,6 +172,7 @@ int  engine_reset(EngineImpl* im);
 int  engine_stats(const EngineImpl* im, xck_stats* out);
 int  engine_read_fate(EngineImpl* im, xck_read_fate* out);         // read_fate.h
 int  engine_cell_summary(EngineImpl* im, xck_cell_summary* out);   // cell_summary.h
+int  engine_feature_summary(EngineImpl* im, xck_feature_summary* out);   // feature_summary.h
 int  engine_device(const xck_engine* e);      // HIP device of the handle (-1: decode-only handle)
 int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (sysfs, by PCI bus id); -1 = unknown
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE

@@ -421,6 +421,34 @@ class Engine(object):
         matrix = np.ctypeslib.as_array(cs.matrix, shape=(n * km,)).reshape(n, km).copy() if cs.has_matrix and cs.matrix else None
         return dict(fate=fate, matrix=matrix, fate_cols=capi.CELL_FATE_COLS, matrix_cols=capi.CELL_MATRIX_COLS[int(cs.mode)])
 
+    def feature_summary(self, mode=None):
+        """The per-feature and per-SNP tables of one pipeline since the last reset (xck_get_feature_summary), all in the input order
+        of the regions / SNPs the engine was made with: dict of `reads`, int64 [n_regions, 3] (basefc; None for the BAF pipeline),
+        `matrix`, int64 [n_regions, k] (None before finish()), `snp`, int64 [n_snps, 8] (BAF; None for basefc; the tallies and
+        `kept` are zero before finish()), `has_matrix`, and the column names `read_cols`, `matrix_cols`, `snp_cols` - copies, not
+        views; or None on a handle made without XCK_F_FEATURE_SUMMARY (and without XCK_FEATURE_SUMMARY=1 in the environment).
+        mode as for read_fate().  Waits for queued work."""
+        if mode is None:
+            if self.mode == capi.XCK_MODE_BOTH:
+                raise ValueError("feature_summary(): a XCK_MODE_BOTH handle has two pipelines, name one")
+            mode = self.mode
+        fs = capi.FeatureSummary()
+        fs.struct_size = C.sizeof(capi.FeatureSummary)
+        rc = self.lib.xck_get_feature_summary(self.h, int(mode), C.byref(fs))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_feature_summary")
+
+        def table(p, rows, cols):
+            if not p:
+                return None
+            return np.ctypeslib.as_array(p, shape=(rows * cols,)).reshape(rows, cols).copy() if rows * cols else np.zeros((rows, cols), dtype=np.int64)
+        n = int(fs.n_regions)
+        return dict(reads=table(fs.reads, n, int(fs.n_read_cols)),
+                    matrix=table(fs.matrix, n, int(fs.n_matrix_cols)) if fs.has_matrix else None,
+                    snp=table(fs.snp, int(fs.n_snps), int(fs.n_snp_cols)), has_matrix=bool(fs.has_matrix),
+                    read_cols=capi.FEATURE_READ_COLS, matrix_cols=capi.FEATURE_MATRIX_COLS[int(fs.mode)], snp_cols=capi.SNP_COLS)
+
 
 class BamStream(object):
     """One open BAM being streamed through an Engine in slices (xck_ingest_opts.pause_records)."""

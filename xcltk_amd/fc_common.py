@@ -399,6 +399,119 @@ def write_cell_summary(eng, dist, path, names, mode=None, log_prefix="[engine]")
     return cs
 
 
+def feature_summary_text(regions, reads, matrix, mode, n_ranks=1, cut_contigs=0):
+    """Text of feature_summary.tsv: header, then one line per input region in input order (regions that got no output row too): the
+    four fields of the features.tsv / region.tsv line, then the counters - basefc `fetched include_fail pairs shared umis cells`
+    (fetched = pairs + include_fail), BAF `snps snps_kept ad dp oth cells`.  Runs of several ranks start with
+    `#ranks=N cut_contigs=K`."""
+    from .capi import FEATURE_READ_COLS, FEATURE_MATRIX_COLS, XCK_MODE_BASEFC
+    n = len(regions)
+    mcols = FEATURE_MATRIX_COLS[mode]
+    matrix = np.zeros((n, len(mcols)), dtype=np.int64) if matrix is None else np.asarray(matrix, dtype=np.int64)
+    assert matrix.shape == (n, len(mcols))
+    if mode == XCK_MODE_BASEFC:
+        reads = np.asarray(reads, dtype=np.int64)
+        assert reads.shape == (n, len(FEATURE_READ_COLS))
+        fail, pairs = FEATURE_READ_COLS.index("include_fail"), FEATURE_READ_COLS.index("pairs")
+        table = np.concatenate([(reads[:, pairs] + reads[:, fail])[:, None], reads, matrix], axis=1)
+        cols = ("fetched",) + tuple(FEATURE_READ_COLS) + tuple(mcols)
+    else:
+        table, cols = matrix, tuple(mcols)
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    lines = [head, "\t".join(("chrom", "start", "end", "name") + cols) + "\n"]
+    for (ch, s, e, name), row in zip(regions, table.tolist()):
+        lines.append("%s\t%d\t%d\t%s\t%s\n" % (ch, s, e, name, "\t".join("%d" % v for v in row)))
+    return "".join(lines)
+
+
+def _summary_ranks(dist):
+    """(ranks, contigs cut over ranks) for the `#ranks` line of a summary file"""
+    if dist is None or not dist.active:
+        return 1, 0
+    return dist.world, len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
+
+
+def write_feature_summary(eng, dist, path, regions, mode=None, log_prefix="[engine]"):
+    """Per-feature table of one pipeline (Engine.feature_summary, after finish()) -> `path`, when the handle keeps it
+    (XCK_FEATURE_SUMMARY=1 in the environment, or XCK_F_FEATURE_SUMMARY): nothing happens otherwise.  `regions`: the input regions
+    (chrom, start, end, name) in input order.  Multi-GPU: a collective call - one summing all-reduce, and the writer rank writes
+    the file.  Every rank counts only the regions of its region_mask and a region belongs to exactly one rank, so the file is
+    exact even where a contig is cut over ranks.  Returns the (summed) dict or None."""
+    from .capi import XCK_MODE_BASEFC
+    feature_summary = getattr(eng, "feature_summary", None)    # (an engine-like object without the method keeps nothing)
+    fs = feature_summary(mode) if feature_summary else None
+    if fs is None:
+        return None
+    mode = eng.mode if mode is None else mode
+    n = len(regions)
+    from .capi import FEATURE_READ_COLS
+    if mode == XCK_MODE_BASEFC:                                # (a handle without a region hands out no array: an empty table of the same columns)
+        reads = np.zeros((n, len(FEATURE_READ_COLS)), dtype=np.int64) if fs["reads"] is None else np.asarray(fs["reads"], dtype=np.int64)
+    else:
+        reads = np.zeros((n, 0), dtype=np.int64)
+    matrix = np.zeros((n, len(fs["matrix_cols"])), dtype=np.int64) if fs["matrix"] is None else np.asarray(fs["matrix"], dtype=np.int64)
+    n_ranks, cut = _summary_ranks(dist)
+    if dist is not None and dist.active:
+        v = dist.all_reduce_np(np.concatenate([reads.ravel(), matrix.ravel()]))
+        reads, matrix = v[:reads.size].reshape(reads.shape), v[reads.size:].reshape(matrix.shape)
+    fs = dict(fs, reads=reads if mode == XCK_MODE_BASEFC else None, matrix=matrix)
+    info("%s feature summary: %d of %d regions with an entry" % (log_prefix, int((matrix[:, -1] > 0).sum()), n))
+    if is_writer_rank():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fp:
+            fp.write(feature_summary_text(list(regions), fs["reads"], matrix, mode, n_ranks, cut))
+    return fs
+
+
+def snp_summary_text(snps, table, n_ranks=1, cut_contigs=0):
+    """Text of snp_summary.tsv: header `chrom pos ref alt ref_hap alt_hap reads A C G T N total ref_umis alt_umis kept regions`, then
+    one line per SNP of the list in input order.  `snps`: (chrom, pos, ref, alt, ref_hap, alt_hap); `table`: the `snp` array of
+    Engine.feature_summary (columns capi.SNP_COLS).  total = A + C + G + T + N; ref_umis / alt_umis = the tally of the SNP's REF /
+    ALT base (N for a base outside ACGT).  Runs of several ranks start with `#ranks=N cut_contigs=K`."""
+    table = np.asarray(table, dtype=np.int64)
+    assert table.shape == (len(snps), 8)
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    lines = [head, "chrom\tpos\tref\talt\tref_hap\talt_hap\treads\tA\tC\tG\tT\tN\ttotal\tref_umis\talt_umis\tkept\tregions\n"]
+    idx = {"A": 0, "C": 1, "G": 2, "T": 3}
+    for (ch, pos, ref, alt, rh, ah), row in zip(snps, table.tolist()):
+        tally = row[1:6]
+        lines.append("%s\t%d\t%s\t%s\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\n" % (
+            ch, pos, ref, alt, rh, ah, row[0], "\t".join("%d" % v for v in tally), sum(tally),
+            tally[idx.get(ref, 4)], tally[idx.get(alt, 4)], row[6], row[7]))
+    return "".join(lines)
+
+
+def write_snp_summary(eng, dist, path, snps, mode=None, log_prefix="[engine]"):
+    """Per-SNP table of the pileup pipeline (Engine.feature_summary, after finish()) -> `path`, when the handle keeps it: nothing
+    happens otherwise.  `snps`: the input list, tuples (chrom, pos, ref, alt, ref_hap, alt_hap) or a SnpTable.  Multi-GPU: a
+    collective call - a rank zeroes the rows of the SNPs on contigs it does not stream, one summing all-reduce, and the writer
+    rank writes the file.  Where a contig is cut over ranks (cut_contigs > 0 in the `#ranks` line) both neighbours see the reads
+    and count the tallies of the SNPs near the cut, and `kept` is then the number of ranks that kept the SNP: those rows describe
+    the ranks' work, not the file; nothing corrects for it.  `kept` (and `snps_kept` of feature_summary.tsv) is the verdict under
+    the min_count / min_maf the ENGINE was made with: baf.genotype.pileup() makes its engine with 1 / 0 and applies the caller's
+    thresholds to the summed matrices afterwards (filter_snps), so there `kept` says "some molecule showed a base", not "survived
+    pileup's filter".  Returns the (summed) array or None."""
+    from .capi import XCK_MODE_BAF
+    feature_summary = getattr(eng, "feature_summary", None)
+    fs = feature_summary(XCK_MODE_BAF) if feature_summary and eng.mode & XCK_MODE_BAF else None
+    if fs is None or fs["snp"] is None:
+        return None
+    table = np.asarray(fs["snp"], dtype=np.int64)
+    n_ranks, cut = _summary_ranks(dist)
+    if dist is not None and dist.active:
+        mask = getattr(dist, "contig_mask", None)
+        if mask is not None and len(table):
+            table[~np.asarray(mask, dtype=bool)[eng._snp["contig"]]] = 0
+        table = dist.all_reduce_np(table)
+    snps = list(snps)
+    info("%s SNP summary: %d of %d SNPs kept" % (log_prefix, int((table[:, 6] > 0).sum()), len(table)))
+    if is_writer_rank():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fp:
+            fp.write(snp_summary_text(snps, table, n_ranks, cut))
+    return table
+
+
 # ----------------------------------------------------------------------------- engine driver
 def make_engine(conf, mode, regions, snps=(), device=None, **extra):
     """Build the per-GPU engine from a resolved Config."""

@@ -61,6 +61,10 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
         # (XCK_CELL_SUMMARY=1 only; one table per pipeline, next to its matrices)
         fcc.write_cell_summary(eng, dist, os.path.join(fc_dir, "cell_summary.tsv"), conf.samples, XCK_MODE_BASEFC, "[fused basefc]")
         fcc.write_cell_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "cell_summary.tsv"), conf.samples, XCK_MODE_BAF, "[fused baf]")
+        # (XCK_FEATURE_SUMMARY=1 only; likewise, and the per-SNP table of the pileup pipeline)
+        fcc.write_feature_summary(eng, dist, os.path.join(fc_dir, "feature_summary.tsv"), regions, XCK_MODE_BASEFC, "[fused basefc]")
+        fcc.write_feature_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "feature_summary.tsv"), regions, XCK_MODE_BAF, "[fused baf]")
+        fcc.write_snp_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "snp_summary.tsv"), snps, XCK_MODE_BAF, "[fused baf]")
         if coo is None:
             return 0
         n = len(regions)                                  # (sharded output: every rank is here and the calls below are collective)

@@ -166,6 +166,7 @@ def fc_core(conf):
     try:
         fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"))   # (XCK_READ_FATE=1 only)
         fcc.write_cell_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "cell_summary.tsv"), conf.samples)   # (XCK_CELL_SUMMARY=1 only)
+        fcc.write_feature_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "feature_summary.tsv"), regions)   # (XCK_FEATURE_SUMMARY=1 only)
         if coo is not None:                               # the only process / rank 0 after a gather / every rank (sharded output)
             rm = fcc.output_row_map(dist, len(regions), conf.output_all_reg, coo["count"][0])   # all_reg: row = input line number
             if fcc.is_writer_rank():
