@@ -364,6 +364,42 @@ int  xck_finish_async(xck_engine* e);
  * engine's workspace, valid until the next xck_finish / xck_reset): lets a multi-GPU driver exchange the
  * per-contig sparse blocks GPU-to-GPU (RCCL over xGMI) without a host round trip. */
 int  xck_get_result_device(xck_engine* e, xck_result* out);
+/* Recount the pileup under new tables without the reads (additive: ABI 3 is unchanged).  The read x SNP join and the first half of
+ * the pileup fold - the sort of the hits, the base the first read of every (SNP, cell, UMI) shows, the tallies per SNP - depend on
+ * nothing but the reads, the read filters, the cells and the SNP positions; xck_finish keeps what they leave, and xck_refold runs the
+ * second half again: the fan-out to the regions, REF / ALT and the haplotype indices, the exclusion pairs, min_count / min_maf and
+ * no_dup_hap.  It returns the matrices a fresh handle would return that was created with these tables and filters and the original
+ * read filters and cells and was fed the same reads, bit for bit.
+ *   regions      the new feature table; output row = index, as in xck_config.  n_regions + 1 must fit the row field of the handle's key
+ *                layout, which xck_create sized from max(n_regions, n_snps) + 1: XCK_E_ARG otherwise (create the handle with the
+ *                largest table it will see).  Regions on a contig outside the handle's contig table keep empty rows.
+ *   snps         NULL / 0 = keep the handle's; otherwise n_snps and every (contig, pos) must equal the list given to xck_create index
+ *                by index; ref, alt, ref_hap, alt_hap may differ.
+ *   snp_enabled  [n_snps of the handle] or NULL = all; a disabled SNP feeds no region (the handle then answers as one created with
+ *                the list without it; in xck_feature_summary.snp its tallies and verdict stay, its regions are 0).
+ *   excl_*       as in xck_config: indices into the NEW regions and the handle's SNP order.
+ * Valid on a handle with a BAF pipeline (XCK_MODE_BAF, or the BAF half of XCK_MODE_BOTH, whose out->count is the last finish's,
+ * untouched), between a successful xck_finish and the next xck_reset, as often as wanted.  Pointers handed out by an earlier
+ * xck_finish / xck_refold / xck_get_result_device die with the call, as at a second finish.  The handle's n_regions, filters and
+ * tables follow the call, and xck_get_cell_summary / xck_get_feature_summary recompute their matrix halves, the kept and regions
+ * columns of the SNP table included; the read-side counters do not change.
+ * XCK_E_STATE before a finish, after a reset, on a decode-only handle, or when a fold of the handle has failed; XCK_E_ARG for a
+ * basefc-only handle, a short struct_size, an SNP list whose positions differ, exclusion pairs outside the tables, or too many
+ * regions - the handle is then as it was.  A call that fails inside the fold leaves the handle failed, like a finish: xck_reset. */
+typedef struct xck_refold_config {
+    uint32_t struct_size;       /* sizeof(xck_refold_config)                                 */
+    int32_t  n_regions;
+    const xck_region* regions;
+    int32_t  n_snps;
+    const xck_snp* snps;
+    const uint8_t* snp_enabled;
+    double   min_count, min_maf;
+    int32_t  no_dup_hap;
+    int32_t  n_excl_pairs;
+    const int32_t* excl_region;
+    const int32_t* excl_snp;
+} xck_refold_config;
+int  xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out);
 /* Forget all pushed reads, keep tables and buffers (lets one engine be re-used per step). */
 int  xck_reset(xck_engine* e);
 int  xck_get_stats(const xck_engine* e, xck_stats* out);

@@ -148,6 +148,26 @@ def regions_with_snps(regions, snps):
     return out
 
 
+def phased_tables(conf, regions, snps, has_snp):
+    """-> (the SNP list the engine counts with, (region indices, SNP indices) left out of the SNP -> region join or None): the
+    input as it is without local phasing; otherwise region-wise local phasing (baf/fc/main.py:107-153) gives new haplotype indices
+    for flipped SNPs, and the SNPs without coverage in the pileup leave the SNP list of the region that was phased."""
+    if not conf.use_local_phasing():
+        return snps, None
+    from .phasing import local_phasing
+    from ...snptable import SnpTable
+    phase_regions = regions if conf.output_all_reg else [r for r, h in zip(regions, has_snp) if h]
+    phase_index = list(range(len(regions))) if conf.output_all_reg else [i for i, h in enumerate(has_snp) if h]
+    rh, ah, ex_r, ex_s, _ = local_phasing(phase_regions, snps, conf.snp_csp, conf.ref_cells, conf.debug)
+    ex_r = np.array([phase_index[i] for i in ex_r.tolist()], dtype=np.int32)
+    if isinstance(snps, SnpTable):
+        snps = SnpTable(snps.names, snps.chrom_id, snps.pos, snps.ref, snps.alt, rh, ah)
+    else:
+        snps = [(s[0], s[1], s[2], s[3], int(r), int(a)) for s, r, a in zip(snps, rh.tolist(), ah.tolist())]
+    conf.snp_csp = conf.ref_cells = None
+    return snps, (ex_r, ex_s)
+
+
 def afc_core(conf):
     if prepare_config(conf) < 0:
         raise ValueError("errcode -2")
@@ -156,22 +176,7 @@ def afc_core(conf):
     regions, snps = conf.reg_list, conf.snp_list
     has_snp = regions_with_snps(regions, snps)
     info("#regions: total=%d; with_snps=%d." % (len(regions), sum(has_snp)))
-    excl = None
-    if conf.use_local_phasing():
-        # region-wise local phasing (baf/fc/main.py:107-153): new haplotype indices for flipped SNPs, and the SNPs without
-        # coverage in the pileup leave the SNP list of the region that was phased
-        from .phasing import local_phasing
-        from ...snptable import SnpTable
-        phase_regions = regions if conf.output_all_reg else [r for r, h in zip(regions, has_snp) if h]
-        phase_index = list(range(len(regions))) if conf.output_all_reg else [i for i, h in enumerate(has_snp) if h]
-        rh, ah, ex_r, ex_s, _ = local_phasing(phase_regions, snps, conf.snp_csp, conf.ref_cells, conf.debug)
-        ex_r = np.array([phase_index[i] for i in ex_r.tolist()], dtype=np.int32)
-        if isinstance(snps, SnpTable):
-            snps = SnpTable(snps.names, snps.chrom_id, snps.pos, snps.ref, snps.alt, rh, ah)
-        else:
-            snps = [(s[0], s[1], s[2], s[3], int(r), int(a)) for s, r, a in zip(snps, rh.tolist(), ah.tolist())]
-        excl = (ex_r, ex_s)
-        conf.snp_csp = conf.ref_cells = None
+    snps, excl = phased_tables(conf, regions, snps, has_snp)
     eng, coo, dist = fcc.make_and_count(conf, XCK_MODE_BAF, regions, snps, excl_pairs=excl)
     try:
         fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"))   # (XCK_READ_FATE=1 only)

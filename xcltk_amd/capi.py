@@ -61,6 +61,15 @@ class Config(C.Structure):
     ]
 
 
+class RefoldConfig(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("n_regions", C.c_int32), ("regions", C.POINTER(Region)),
+        ("n_snps", C.c_int32), ("snps", C.POINTER(Snp)), ("snp_enabled", C.POINTER(C.c_uint8)),
+        ("min_count", C.c_double), ("min_maf", C.c_double), ("no_dup_hap", C.c_int32),
+        ("n_excl_pairs", C.c_int32), ("excl_region", C.POINTER(C.c_int32)), ("excl_snp", C.POINTER(C.c_int32)),
+    ]
+
+
 class Batch(C.Structure):
     _fields_ = [
         ("contig", C.c_int32), ("n_reads", C.c_int32), ("ordinal_base", C.c_uint64),
@@ -170,6 +179,7 @@ SYMBOLS = [
     ("xck_finish", C.c_int, [C.c_void_p, _P(Result)]),
     ("xck_finish_async", C.c_int, [C.c_void_p]),
     ("xck_get_result_device", C.c_int, [C.c_void_p, _P(Result)]),
+    ("xck_refold", C.c_int, [C.c_void_p, _P(RefoldConfig), _P(Result)]),
     ("xck_reset", C.c_int, [C.c_void_p]),
     ("xck_get_stats", C.c_int, [C.c_void_p, _P(Stats)]),
     ("xck_get_decode_stats", C.c_int, [C.c_void_p, _P(DecodeStats)]),

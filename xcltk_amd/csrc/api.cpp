@@ -303,6 +303,22 @@ static int merged_result(xck_engine* e, xck_result* out, int (*get)(EngineImpl*,
 int xck_finish(xck_engine* e, xck_result* out) { if (!e || !out) return XCK_E_ARG; return merged_result(e, out, engine_finish); }
 int xck_get_result_device(xck_engine* e, xck_result* out) { if (!e || !out) return XCK_E_ARG; return merged_result(e, out, engine_result_device); }
 
+int xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out) {
+    if (!e || !cfg || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (e->n_impl <= 0) return no_engine(e);
+    if (!(e->mode & XCK_MODE_BAF)) { e->err = "xck_refold: the handle has no BAF pipeline (a basefc recount needs the reads)"; return XCK_E_ARG; }
+    if (cfg->struct_size < sizeof(xck_refold_config)) { e->err = "xck_refold_config.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    xck_result r;
+    if (int rc = engine_refold(e->impls[e->n_impl - 1], cfg, &r)) return rc;
+    if (e->mode == XCK_MODE_BOTH) {                        // the count matrix is the last finish's, untouched
+        xck_result c;
+        if (int rc = engine_finish(e->impls[0], &c)) return rc;
+        r.count = c.count;
+    }
+    *out = r;
+    return XCK_OK;
+}
+
 int xck_get_stats(const xck_engine* e, xck_stats* out) {
     if (!e || !out) return XCK_E_ARG;
     if (e->n_impl == 0) return XCK_E_STATE;

@@ -865,10 +865,6 @@ template <class T> static int dev_upload(EngineImpl* im, T** dptr, const std::ve
     return 0;
 }
 
-static uint32_t nib_of(uint8_t ch) {
-    switch (ch) { case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8; default: return 15; }
-}
-
 static int build_tables(EngineImpl* im, const xck_config* cfg) {
     const int nc = cfg->n_contigs;
     im->ctab.assign(std::max(nc, 1), ContigTab());
@@ -878,29 +874,10 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
     if (im->mode == XCK_MODE_BASEFC) {
         // regions valid for fetch(): pysam raises (-> region silently gets 0, utils/sam.py:105-118)
         // when start-1 < 0 or start-1 > end.
-        std::vector<std::vector<int32_t>> by_c(nc);
-        for (int g = 0; g < cfg->n_regions; g++) {
-            const xck_region& r = cfg->regions[g];
-            if (r.contig < 0 || r.contig >= nc) continue;
-            if (r.start < 1 || (int64_t)r.start - 1 > (int64_t)r.end) continue;
-            by_c[r.contig].push_back(g);
-        }
-        for (int c = 0; c < nc; c++) {
-            auto& v = by_c[c];
-            std::sort(v.begin(), v.end(), [&](int32_t a, int32_t b) {
-                const xck_region &x = cfg->regions[a], &y = cfg->regions[b];
-                if (x.start != y.start) return x.start < y.start;
-                if (x.end != y.end) return x.end < y.end;
-                return a < b; });
-            ContigTab& t = im->ctab[c];
-            t.reg_base = (int32_t)reg_s0.size(); t.n_reg = (int32_t)v.size();
-            int32_t max_e = 0;
-            for (int32_t g : v) {
-                const xck_region& r = cfg->regions[g];
-                reg_s0.push_back(r.start - 1); reg_e0.push_back(r.end); reg_row.push_back(g);
-                max_e = std::max(max_e, r.end); reg_pmax.push_back(max_e);          // running maximum of the ends: first candidate of a position by binary search
-            }
-        }
+        std::vector<int32_t> base, count;
+        sort_regions_by_contig(cfg->regions, cfg->n_regions, nc, [](const xck_region& r) { return !(r.start < 1 || (int64_t)r.start - 1 > (int64_t)r.end); },
+                               [](const xck_region& r) { return r.start - 1; }, reg_s0, reg_e0, reg_row, reg_pmax, base, count);
+        for (int c = 0; c < nc; c++) { im->ctab[c].reg_base = base[c]; im->ctab[c].n_reg = count[c]; }
     } else {
         std::vector<std::vector<int32_t>> by_c(nc);
         for (int s = 0; s < cfg->n_snps; s++) {
@@ -914,6 +891,7 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
         std::vector<uint64_t> excl;                                       // (snp index << 32 | region index), sorted
         for (int i = 0; i < cfg->n_excl_pairs; i++) excl.push_back(((uint64_t)(uint32_t)cfg->excl_snp[i] << 32) | (uint32_t)cfg->excl_region[i]);
         std::sort(excl.begin(), excl.end());
+        double ms_csr = 0;                                               // XCK_DEBUG_TIMING: the SNP -> region loop alone (refold.h builds the same relation on the device)
         csr_off.push_back(0);
         for (int c = 0; c < nc; c++) {
             auto& v = by_c[c];
@@ -924,7 +902,7 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
             for (int32_t s : v) {
                 const xck_snp& x = cfg->snps[s];
                 snp_p0.push_back(x.pos - 1);
-                snp_info.push_back(nib_of(x.ref) | (nib_of(x.alt) << 4) | ((uint32_t)(x.ref_hap & 1) << 8) | ((uint32_t)(x.alt_hap & 1) << 9));
+                snp_info.push_back(snp_info_word(x));
             }
             int32_t max_p = v.empty() ? 0 : cfg->snps[v.back()].pos;
             t.n_swin = v.empty() ? 0 : (max_p >> WSS) + 1;
@@ -932,6 +910,7 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
             { int32_t k = 0; for (int32_t w = 0; w < t.n_swin; w++) { while (k < t.n_snp && snp_p0[t.snp_base + k] < (w << WSS)) k++; snp_win.push_back(t.snp_base + k); } }
             // SNP -> regions: start <= pos <= end_incl; rows ascending so keys stay deterministic
             // (minus the caller's exclusion pairs: SNPs that local phasing removed from one region's list)
+            const auto t_csr = std::chrono::steady_clock::now();
             std::vector<std::vector<int32_t>> hits(t.n_snp);
             for (int32_t g : reg_c[c]) {
                 const xck_region& r = cfg->regions[g];
@@ -944,12 +923,16 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
                 }
             }
             for (int32_t k = 0; k < t.n_snp; k++) { std::sort(hits[k].begin(), hits[k].end()); for (int32_t g : hits[k]) csr_reg.push_back(g); csr_off.push_back((int32_t)csr_reg.size()); }
+            ms_csr += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_csr).count();
         }
+        if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] create: host SNP -> region CSR loop %.3f ms (%d SNPs, %d regions, %zu pairs)\n", ms_csr, cfg->n_snps, cfg->n_regions, csr_reg.size());
         im->n_snps_sorted = (int)snp_p0.size();
-        if (cfg->flags & XCK_F_FEATURE_SUMMARY) {              // the per-SNP summary answers in the caller's order
-            for (int c = 0; c < nc; c++) im->snp_perm.insert(im->snp_perm.end(), by_c[c].begin(), by_c[c].end());
-            im->h_csr_off = csr_off; im->h_csr_reg = csr_reg; im->n_snps_in = cfg->n_snps;
-        }
+        // sorted SNP -> the caller's index: the per-SNP summary answers in the caller's order, and xck_refold takes its tables in it
+        for (int c = 0; c < nc; c++) im->snp_perm.insert(im->snp_perm.end(), by_c[c].begin(), by_c[c].end());
+        im->n_snps_in = cfg->n_snps;
+        im->snps_in.assign(cfg->snps, cfg->snps + cfg->n_snps);
+        im->csr_reg_cap_bytes = std::max<size_t>(csr_reg.size(), 1) * sizeof(int32_t);
+        if (cfg->flags & XCK_F_FEATURE_SUMMARY) { im->h_csr_off = csr_off; im->h_csr_reg = csr_reg; }
     }
     int rc;
     if ((rc = dev_upload(im, &im->d_reg_s0, reg_s0))) return rc;
@@ -1317,7 +1300,7 @@ int engine_reset(EngineImpl* im) {
     if (im->d_feat) { rc = feature_summary_reset(im); if (rc) return rc; }
     im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
-    im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false;
+    im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false; im->mol_valid = false;
     for (int i = 0; i < CTL_WORDS; i++) im->h_ctl[i] = 0;
     for (int sh = 0; sh < NSHARD; sh++) { im->cur[sh] = 0; im->ncur[sh] = 0; }
     int kb = im->key_bits, ub = im->ubits;
@@ -1399,7 +1382,7 @@ void engine_destroy(EngineImpl* im) {
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
                      im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept,
-                     im->ws1.base, im->ws2.base };
+                     im->d_csr_alt, im->d_rf, im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }
     for (int m = 0; m < 4; m++) if (im->h_res[m]) hipHostFree(im->h_res[m]);
@@ -1411,6 +1394,7 @@ void engine_destroy(EngineImpl* im) {
     if (im->ev_c1) hipEventDestroy(im->ev_c1);
     if (im->ev_f1) hipEventDestroy(im->ev_f1);
     if (im->ev_f2) hipEventDestroy(im->ev_f2);
+    for (hipEvent_t ev : { im->ev_r0, im->ev_r1, im->ev_r2, im->ev_r3 }) if (ev) hipEventDestroy(ev);
     if (im->s_copy) hipStreamDestroy(im->s_copy);
     if (im->s_comp) hipStreamDestroy(im->s_comp);
     delete im;

@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <climits>
 #include <cstdio>
 #include <vector>
 #include <hip/hip_runtime.h>
@@ -200,7 +201,55 @@ struct EngineImpl {
     std::vector<int32_t> snp_perm, h_csr_off, h_csr_reg;
     int n_snps_in = 0;
     bool fmat_valid = false;
+    // what the molecule stage of the pileup fold leaves for the region stage (finish.hip fold_molecules / fold_regions): the hits sorted
+    // by key - in workspace 1 after the partition sort, in d_keys after the radix sort - and the base the first read of every key
+    // shows (workspace 1).  Valid from a successful finish to the next reset; nothing in the region stage takes memory in either place.
+    const void* mol_keys = nullptr; uint8_t* mol_al = nullptr; size_t mol_n = 0; bool mol_valid = false;
+    // xck_refold (refold.h): the caller's SNP list as given to xck_create, the regrown tables' capacities, and the builder's own buffers
+    std::vector<xck_snp> snps_in;
+    size_t csr_reg_cap_bytes = 0, fmat_cap_bytes = 0;     // of d_csr_reg and d_fmat, which a refold may have to regrow
+    bool csr_host_stale = false;                          // h_csr_off / h_csr_reg lag behind the device tables (feature_summary.h reloads them)
+    int32_t* d_csr_alt = nullptr;                         // the next d_csr_off: counted and scanned here, swapped in once the total is known
+    char* d_rf = nullptr; size_t rf_cap = 0;              // sorted regions, exclusion words, SNP mask, contig table, scan block sums
+    hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr, ev_r2 = nullptr, ev_r3 = nullptr;   // count pass + scan, fill pass
+    double rf_ms_upload = 0, rf_ms_build = 0, rf_ms_regions = 0, rf_ms_total = 0;   // the last refold, for XCK_DEBUG_TIMING and tools/refold_time.py
 };
+
+// d_snp_info: ref nibble | alt nibble << 4 | ref_hap << 8 | alt_hap << 9
+static inline uint32_t nib_of(uint8_t ch) {
+    switch (ch) { case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8; default: return 15; }
+}
+static inline uint32_t snp_info_word(const xck_snp& x) { return nib_of(x.ref) | (nib_of(x.alt) << 4) | ((uint32_t)(x.ref_hap & 1) << 8) | ((uint32_t)(x.alt_hap & 1) << 9); }
+
+// Regions per contig sorted by (start, end, index), with the running maximum of the ends (the first candidate of a position is one
+// bisection over it).  keep(region) says which regions enter the table; base[c] / count[c] are the contig's slice.  s0 holds what
+// start0(region) returns: the basefc join stores 0-based starts, the SNP -> region builder 1-based ones.
+template <class Keep, class Start>
+static inline void sort_regions_by_contig(const xck_region* regions, int n_regions, int nc, Keep keep, Start start0, std::vector<int32_t>& s0, std::vector<int32_t>& e0,
+                                          std::vector<int32_t>& row, std::vector<int32_t>& pmax, std::vector<int32_t>& base, std::vector<int32_t>& count) {
+    std::vector<std::vector<int32_t>> by_c(nc);
+    for (int g = 0; g < n_regions; g++) {
+        const xck_region& r = regions[g];
+        if (r.contig < 0 || r.contig >= nc || !keep(r)) continue;
+        by_c[r.contig].push_back(g);
+    }
+    base.assign(std::max(nc, 1), 0); count.assign(std::max(nc, 1), 0);
+    for (int c = 0; c < nc; c++) {
+        auto& v = by_c[c];
+        std::sort(v.begin(), v.end(), [&](int32_t a, int32_t b) {
+            const xck_region &x = regions[a], &y = regions[b];
+            if (x.start != y.start) return x.start < y.start;
+            if (x.end != y.end) return x.end < y.end;
+            return a < b; });
+        base[c] = (int32_t)s0.size(); count[c] = (int32_t)v.size();
+        int32_t max_e = INT32_MIN;
+        for (int32_t g : v) {
+            const xck_region& r = regions[g];
+            s0.push_back(start0(r)); e0.push_back(r.end); row.push_back(g);
+            max_e = std::max(max_e, r.end); pmax.push_back(max_e);          // running maximum of the ends: first candidate of a position by binary search
+        }
+    }
+}
 
 // host helpers defined in engine.hip
 size_t key_bytes(const EngineImpl* im);

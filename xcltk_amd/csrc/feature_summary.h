@@ -69,7 +69,8 @@ static int feature_summary_init(EngineImpl* im) {
     const size_t words = im->mode == XCK_MODE_BASEFC ? (size_t)im->n_regions * FS_REG_WORDS : (size_t)im->n_snps_sorted;
     HIP_TRY(hipMalloc((void**)&im->d_feat, std::max<size_t>(words, 1) * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(im->d_feat, 0, std::max<size_t>(words, 1) * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc((void**)&im->d_fmat, std::max<size_t>((size_t)im->n_regions * 6, 1) * sizeof(unsigned long long)));
+    im->fmat_cap_bytes = std::max<size_t>((size_t)im->n_regions * 6, 1) * sizeof(unsigned long long);
+    HIP_TRY(hipMalloc((void**)&im->d_fmat, im->fmat_cap_bytes));
     if (im->mode == XCK_MODE_BAF) {
         // (a finish that finds no hit returns before the fold clears the tallies: they start, and after every reset are, zero)
         HIP_TRY(hipMemset(im->d_tally, 0, std::max<size_t>((size_t)im->n_snps_sorted * 5, 1) * sizeof(uint32_t)));
@@ -136,6 +137,13 @@ static int feature_marginals(EngineImpl* im, const int k) {
         if (ns) {
             HIP_TRY(hipMemcpyAsync(im->h_tally.data(), im->d_tally, ns * 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, im->s_comp));
             HIP_TRY(hipMemcpyAsync(im->h_kept.data(), im->d_kept, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, im->s_comp));
+        }
+        if (im->csr_host_stale) {                              // xck_refold built new SNP -> region tables on the device
+            im->h_csr_off.resize(ns + 1);
+            HIP_TRY(hipMemcpy(im->h_csr_off.data(), im->d_csr_off, (ns + 1) * sizeof(int32_t), hipMemcpyDeviceToHost));
+            im->h_csr_reg.resize((size_t)im->h_csr_off[ns]);
+            if (!im->h_csr_reg.empty()) HIP_TRY(hipMemcpy(im->h_csr_reg.data(), im->d_csr_reg, im->h_csr_reg.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            im->csr_host_stale = false;
         }
     }
     HIP_TRY(hipStreamSynchronize(im->s_comp));

@@ -13,6 +13,7 @@
 //
 // Integer / byte work only - HBM-bound, no MFMA.  See DESIGN.md for layouts, byte counts and measurements.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <chrono>
@@ -1300,11 +1301,13 @@ static int sum_sorted_runs(EngineImpl* im, const PileupFold<K>& pf) {
     return 0;
 }
 
+// The pileup fold in two stages, cut where the dependence on the regions ends.
+// fold_molecules: the hits sorted by key, the base the first read of every (SNP, cell, UMI) shows, the tallies per SNP.  It reads
+// nothing but the hits and the SNP positions, and what it leaves (EngineImpl::mol_keys / mol_al / mol_n, d_tally) stays valid until
+// the next reset.
 template <class K>
-static int finish_pileup(EngineImpl* im, size_t n) {
-    Timer tm{im, im->ev0, im->ev1};
+static int fold_molecules(EngineImpl* im, size_t n) {
     int rc;
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
     const int top = im->ubits + im->cbits + im->rbits;
     PileupFold<K> pf{};
     const size_t tmpb = sort_tmp_bytes<K, uint64_t>(n, top);
@@ -1315,8 +1318,8 @@ static int finish_pileup(EngineImpl* im, size_t n) {
                       + (size_t)std::max(im->n_snps_sorted, 1) * 17           // first_reads_split: row_lo and row_hi (16 bytes per SNP), blk_lo (8 bytes per 32 SNPs)
                       + std::max<size_t>(n * 8, 8192)                         // first_reads_split: bloom
                       + (1 << 16);                                            // the 256-byte alignment of every get
+    im->mol_valid = false;
     if ((rc = arena_begin(im, im->ws1, need))) return rc;
-    if ((rc = tm.start())) return rc;
     if ((rc = sort_pileup_hits<K>(im, n, tmpb, pf))) return rc;
     pf.al = im->ws1.get<uint8_t>(n);
     HIP_TRY(hipMemsetAsync(im->d_tally, 0, std::max<size_t>((size_t)im->n_snps_sorted * 5, 1) * sizeof(uint32_t), im->s_comp));
@@ -1327,6 +1330,22 @@ static int finish_pileup(EngineImpl* im, size_t n) {
     if constexpr (sizeof(K) == 8) rc = split_mode(im) ? first_reads_split<K>(im, n, pf) : first_reads_plain<K>(im, n, pf);
     else rc = first_reads_plain<K>(im, n, pf);
     if (rc) return rc;
+    im->mol_keys = pf.keys; im->mol_al = pf.al; im->mol_n = n; im->mol_valid = true;
+    return 0;
+}
+
+// fold_regions: everything that depends on the regions, REF / ALT, the haplotype indices, the exclusion pairs and the per-SNP filters -
+// the fan-out of the molecules to the regions of their SNP, the haplotype algebra per (region, cell), the COO blocks and their
+// copy-out.  Allocates from workspace 2 only, so it runs again under new tables (xck_refold) on what fold_molecules left.
+template <class K>
+static int fold_regions(EngineImpl* im) {
+    int rc;
+    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    const size_t n = im->mol_n;
+    PileupFold<K> pf{};
+    pf.keys = (const K*)im->mol_keys; pf.al = im->mol_al;
+    for (int m = 1; m < 4; m++) { im->res_nnz[m] = 0; im->d_res[m] = nullptr; }
+    if (n == 0) return 0;
     if ((rc = count_region_hits<K>(im, n, pf))) return rc;
     if (pf.n2) {
         const bool try_part = sizeof(K) == 8 && !im->eng->knobs.pileup_radix;
@@ -1340,6 +1359,16 @@ static int finish_pileup(EngineImpl* im, size_t n) {
         }
         if ((rc = compact_coo<K>(im, im->ws2, hs, pf.k2, pf.n2, kl, 1))) return rc;   // AD, DP, OTH together, from the per-run sums
     }
+    return 0;
+}
+
+template <class K>
+static int finish_pileup(EngineImpl* im, size_t n) {
+    Timer tm{im, im->ev0, im->ev1};
+    int rc;
+    if ((rc = tm.start())) return rc;
+    if ((rc = fold_molecules<K>(im, n))) return rc;
+    if ((rc = fold_regions<K>(im))) return rc;
     return tm.stop(&im->st.ms_sort);
 }
 
@@ -1352,7 +1381,7 @@ static int finish_t(EngineImpl* im) {
       im->st.n_hits = acc; }                          // accepted pairs (before the LDS de-duplication)
     im->st.n_hits_unique = (int64_t)(n + im->ncursor);   // keys that reached HBM
     join_stamps_report(im);
-    if (n == 0) return 0;
+    if (n == 0) { im->mol_keys = nullptr; im->mol_al = nullptr; im->mol_n = 0; im->mol_valid = im->mode == XCK_MODE_BAF; return 0; }
     const int rc = im->mode == XCK_MODE_BASEFC ? finish_basefc<K>(im, n) : finish_pileup<K>(im, n);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
@@ -1376,8 +1405,8 @@ int engine_finish_async(EngineImpl* im) {
     return 0;
 }
 
-int engine_finish(EngineImpl* im, xck_result* out) {
-    int rc = engine_finish_async(im); if (rc) return rc;
+// wait for the copy-out of the last fold and hand out the host blocks
+static int result_host(EngineImpl* im, xck_result* out) {
     if (im->copy_pending) {
         const bool dbg = im->eng->knobs.debug_timing;
         const auto t0_ = std::chrono::steady_clock::now();
@@ -1396,6 +1425,10 @@ int engine_finish(EngineImpl* im, xck_result* out) {
         dst[m]->row = im->h_res[m]; dst[m]->col = im->h_res[m] ? im->h_res[m] + z : nullptr; dst[m]->val = im->h_res[m] ? im->h_res[m] + 2 * z : nullptr;
     }
     return 0;
+}
+int engine_finish(EngineImpl* im, xck_result* out) {
+    if (int rc = engine_finish_async(im)) return rc;
+    return result_host(im, out);
 }
 
 // device-resident copy of the last finish() result (for device-to-device exchanges such as the RCCL gather)
@@ -1418,6 +1451,8 @@ int snp_verdicts(EngineImpl* im, uint32_t* d_kept) {
     HIP_TRY(hipGetLastError());
     return 0;
 }
+
+#include "refold.h"
 
 int finish_init(EngineImpl* im) {
     // the hash fold needs 64 KB of dynamic LDS: raise the limit on THIS engine's device (a per-process flag would leave every

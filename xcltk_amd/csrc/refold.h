@@ -1,0 +1,230 @@
+// refold.h - xck_refold (include/xck.h): the region stage of the pileup fold again, under new regions, REF / ALT, haplotype indices,
+// exclusion pairs and per-SNP filters, on the molecule stage the last xck_finish left (finish.hip fold_molecules / fold_regions).
+// Included by finish.hip inside namespace xck, behind fold_partition.h: it uses that file's device-wide scan (pf_scan).
+//
+// The SNP -> region tables (d_csr_off / d_csr_reg) are built on the device.  The host handles only tables of at most n_regions
+// entries: it validates the regions, sorts them per contig by (start, end, index) with the running maximum of the ends
+// (sort_regions_by_contig, the code xck_create uses for the basefc table) and turns the exclusion pairs into sorted words
+// `sorted SNP index << 32 | region`.  One thread per SNP of the sorted table then finds its first candidate by one bisection over the
+// running maxima and walks the regions up to the first that starts behind the SNP, keeping those that contain it and are not
+// excluded.  The same kernel runs twice, as k_expand does: a count pass, a device-wide exclusive scan of the counts (which is
+// csr_off), and a fill pass.  The order of a SNP's list is free: k_expand's output is sorted next.
+//
+// Bound of the walk: a SNP visits the regions of its contig from the first whose running maximum reaches its position to the
+// last that starts at or before it.  Tables whose regions nest little (genes, bins) give a walk of a few regions; one region that
+// spans the contig and sorts first makes every SNP walk all regions left of it (DESIGN.md 3.7 states the bound and the measured time).
+#pragma once
+
+constexpr int RF_BLOCK = 256;
+
+struct RefoldTabs {
+    const int32_t* snp_p0; const uint8_t* enabled;                       // per sorted SNP: 0-based position; 0 = feeds no region (null = all feed)
+    const int32_t *ct_snp_end, *ct_reg_base, *ct_reg_n; int32_t n_ct;    // per contig: one past its last sorted SNP, its slice of the sorted regions
+    const int32_t *start, *end, *row, *pmax;                             // the sorted regions: 1-based inclusive bounds, the caller's index, running maximum of the ends
+    const unsigned long long* excl; int32_t n_excl;                      // sorted (sorted SNP index << 32 | region)
+    uint32_t n_snps;
+};
+
+// COUNT pass (EMIT = false): cnt[s] = regions of sorted SNP s for s < n_snps, cnt[n_snps] = 0 (the scan turns cnt into csr_off), and
+// their sum, in 64 bits, added to *total.  EMIT pass: reg[off[s] ..] = the regions.
+template <bool EMIT>
+__global__ __launch_bounds__(RF_BLOCK) void k_snp_regions(RefoldTabs t, uint32_t* __restrict__ cnt, const int32_t* __restrict__ off, int32_t* __restrict__ reg,
+                                                          unsigned long long* __restrict__ total) {
+    const uint32_t s = blockIdx.x * RF_BLOCK + threadIdx.x;
+    uint32_t c = 0;
+    if (s < t.n_snps && (!t.enabled || t.enabled[s])) {
+        int32_t lo = 0, hi = t.n_ct - 1;                                 // the SNP's contig: the first whose SNPs end behind s
+        while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if ((int32_t)s < t.ct_snp_end[mid]) hi = mid; else lo = mid + 1; }
+        const int32_t rb = t.ct_reg_base[lo], rn = t.ct_reg_n[lo];
+        const int32_t pos = t.snp_p0[s] + 1;
+        int32_t a = 0, b = rn;                                           // first region whose running maximum of the ends reaches pos
+        while (a < b) { const int32_t mid = (a + b) >> 1; if (t.pmax[rb + mid] >= pos) b = mid; else a = mid + 1; }
+        const int32_t dst = EMIT ? off[s] : 0;
+        for (int32_t j = a; j < rn && t.start[rb + j] <= pos; j++) {
+            if (t.end[rb + j] < pos) continue;
+            const int32_t g = t.row[rb + j];
+            if (t.n_excl) {
+                const unsigned long long w = ((unsigned long long)s << 32) | (uint32_t)g;
+                int32_t x = 0, y = t.n_excl;
+                while (x < y) { const int32_t mid = (x + y) >> 1; if (t.excl[mid] < w) x = mid + 1; else y = mid; }
+                if (x < t.n_excl && t.excl[x] == w) continue;
+            }
+            if (EMIT) reg[dst + (int32_t)c] = g;
+            c++;
+        }
+    }
+    if (!EMIT) {
+        if (s <= t.n_snps) cnt[s] = c;
+        unsigned long long sum = c;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+        if ((threadIdx.x & 63) == 0 && sum) atomicAdd(total, sum);
+    }
+}
+
+static int refold_grow(EngineImpl* im, void** p, size_t* cap, size_t need) {
+    if (need <= *cap) return 0;
+    if (*p) HIP_TRY(hipFree(*p));
+    *p = nullptr; *cap = 0;
+    HIP_TRY(hipMalloc(p, need + need / 4 + 4096));
+    *cap = need + need / 4 + 4096;
+    return 0;
+}
+
+// what the host hands to the builder: one block, one copy
+struct RefoldHost {
+    std::vector<int32_t> start, end, row, pmax, ct_snp_end, ct_reg_base, ct_reg_n;
+    std::vector<unsigned long long> excl;
+    std::vector<uint8_t> enabled;
+    std::vector<uint32_t> info;
+};
+
+static int refold_check(EngineImpl* im, const xck_refold_config* cfg) {
+    xck_engine* e = im->eng;
+    char b[320];
+    if (cfg->n_regions < 0 || (cfg->n_regions > 0 && !cfg->regions)) { e->err = "xck_refold: invalid region table"; return XCK_E_ARG; }
+    if ((int64_t)cfg->n_regions + 1 > (int64_t(1) << im->rbits)) {
+        snprintf(b, sizeof b, "xck_refold: n_regions + 1 = %lld does not fit the %d-bit row field of this handle's key layout (sized at xck_create from max(n_regions, n_snps) + 1): "
+                 "at most %lld regions", (long long)cfg->n_regions + 1, im->rbits, (long long)((int64_t(1) << im->rbits) - 1));
+        e->err = b; return XCK_E_ARG;
+    }
+    if (cfg->snps || cfg->n_snps) {
+        if (!cfg->snps || cfg->n_snps != im->n_snps_in) { e->err = "xck_refold: the SNP list must have the handle's number of SNPs"; return XCK_E_ARG; }
+        for (int i = 0; i < cfg->n_snps; i++)
+            if (cfg->snps[i].contig != im->snps_in[i].contig || cfg->snps[i].pos != im->snps_in[i].pos) {
+                snprintf(b, sizeof b, "xck_refold: SNP %d is at another (contig, pos) than in the handle's list (only ref, alt, ref_hap, alt_hap may differ)", i);
+                e->err = b; return XCK_E_ARG;
+            }
+    }
+    if (cfg->n_excl_pairs < 0 || (cfg->n_excl_pairs > 0 && (!cfg->excl_region || !cfg->excl_snp))) { e->err = "xck_refold: invalid exclusion pairs"; return XCK_E_ARG; }
+    for (int i = 0; i < cfg->n_excl_pairs; i++)
+        if (cfg->excl_region[i] < 0 || cfg->excl_region[i] >= cfg->n_regions || cfg->excl_snp[i] < 0 || cfg->excl_snp[i] >= im->n_snps_in) {
+            snprintf(b, sizeof b, "xck_refold: exclusion pair %d names a region or a SNP outside the tables", i);
+            e->err = b; return XCK_E_ARG;
+        }
+    return 0;
+}
+
+static void refold_host_tables(const EngineImpl* im, const xck_refold_config* cfg, RefoldHost& h) {
+    const int nc = (int)im->ctab.size();
+    const size_t ns = (size_t)im->n_snps_sorted;
+    sort_regions_by_contig(cfg->regions, cfg->n_regions, nc, [](const xck_region& r) { return r.end >= r.start; }, [](const xck_region& r) { return r.start; },
+                           h.start, h.end, h.row, h.pmax, h.ct_reg_base, h.ct_reg_n);
+    h.ct_snp_end.resize(nc);
+    for (int c = 0; c < nc; c++) h.ct_snp_end[c] = im->ctab[c].snp_base + im->ctab[c].n_snp;
+    if (cfg->snp_enabled) { h.enabled.resize(ns); for (size_t s = 0; s < ns; s++) h.enabled[s] = cfg->snp_enabled[im->snp_perm[s]] ? 1 : 0; }
+    if (cfg->n_excl_pairs > 0) {
+        std::vector<int32_t> inv((size_t)im->n_snps_in, -1);              // the caller's index -> sorted SNP (-1: the tables left it out)
+        for (size_t s = 0; s < ns; s++) inv[(size_t)im->snp_perm[s]] = (int32_t)s;
+        for (int i = 0; i < cfg->n_excl_pairs; i++) {
+            const int32_t s = inv[(size_t)cfg->excl_snp[i]];
+            if (s >= 0) h.excl.push_back(((unsigned long long)(uint32_t)s << 32) | (uint32_t)cfg->excl_region[i]);
+        }
+        std::sort(h.excl.begin(), h.excl.end());
+    }
+    if (cfg->snps) {
+        h.info.resize(ns);
+        for (size_t s = 0; s < ns; s++) {
+            const xck_snp& x = cfg->snps[im->snp_perm[s]];
+            h.info[s] = snp_info_word(x);
+        }
+    }
+}
+
+// upload + count + scan + fill: the new d_csr_off / d_csr_reg / d_snp_info.  Up to the check of the total nothing of the handle's
+// tables is touched.
+static int refold_build_tables(EngineImpl* im, const xck_refold_config* cfg, bool* touched) {
+    const auto t0 = std::chrono::steady_clock::now();
+    RefoldHost h;
+    refold_host_tables(im, cfg, h);
+    const size_t ns = (size_t)im->n_snps_sorted, nsb = (ns + 1 + SC_TILE - 1) / SC_TILE;
+    struct Piece { const void* src; size_t bytes, off; } pc[10] = {
+        { h.start.data(), h.start.size() * 4, 0 }, { h.end.data(), h.end.size() * 4, 0 }, { h.row.data(), h.row.size() * 4, 0 }, { h.pmax.data(), h.pmax.size() * 4, 0 },
+        { h.ct_snp_end.data(), h.ct_snp_end.size() * 4, 0 }, { h.ct_reg_base.data(), h.ct_reg_base.size() * 4, 0 }, { h.ct_reg_n.data(), h.ct_reg_n.size() * 4, 0 },
+        { h.excl.data(), h.excl.size() * 8, 0 }, { h.enabled.data(), h.enabled.size(), 0 }, { nullptr, nsb * 4, 0 } };        // (the last: the scan's block sums)
+    size_t total_b = 0;
+    for (auto& p : pc) { p.off = total_b; total_b += (std::max<size_t>(p.bytes, 4) + 255) & ~size_t(255); }
+    if (int rc = refold_grow(im, (void**)&im->d_rf, &im->rf_cap, total_b)) return rc;
+    if (!im->d_csr_alt) HIP_TRY(hipMalloc((void**)&im->d_csr_alt, (ns + 1) * sizeof(int32_t)));
+    if (!im->ev_r0) { HIP_TRY(hipEventCreate(&im->ev_r0)); HIP_TRY(hipEventCreate(&im->ev_r1)); HIP_TRY(hipEventCreate(&im->ev_r2)); HIP_TRY(hipEventCreate(&im->ev_r3)); }
+    { std::vector<char> blk(pc[9].off);
+      for (int q = 0; q < 9; q++) if (pc[q].bytes) memcpy(blk.data() + pc[q].off, pc[q].src, pc[q].bytes);
+      if (!blk.empty()) HIP_TRY(hipMemcpyAsync(im->d_rf, blk.data(), blk.size(), hipMemcpyHostToDevice, im->s_comp));
+      HIP_TRY(hipStreamSynchronize(im->s_comp)); }
+    im->rf_ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    RefoldTabs t;
+    t.snp_p0 = im->d_snp_p0; t.enabled = cfg->snp_enabled ? (const uint8_t*)(im->d_rf + pc[8].off) : nullptr;
+    t.ct_snp_end = (const int32_t*)(im->d_rf + pc[4].off); t.ct_reg_base = (const int32_t*)(im->d_rf + pc[5].off); t.ct_reg_n = (const int32_t*)(im->d_rf + pc[6].off);
+    t.n_ct = (int32_t)h.ct_snp_end.size();
+    t.start = (const int32_t*)(im->d_rf + pc[0].off); t.end = (const int32_t*)(im->d_rf + pc[1].off); t.row = (const int32_t*)(im->d_rf + pc[2].off); t.pmax = (const int32_t*)(im->d_rf + pc[3].off);
+    t.excl = (const unsigned long long*)(im->d_rf + pc[7].off); t.n_excl = (int32_t)h.excl.size();
+    t.n_snps = (uint32_t)ns;
+    uint32_t* bsum = (uint32_t*)(im->d_rf + pc[9].off);
+    const unsigned grid = (unsigned)((ns + 1 + RF_BLOCK - 1) / RF_BLOCK);
+    HIP_TRY(hipEventRecord(im->ev_r0, im->s_comp));
+    HIP_TRY(hipMemsetAsync(im->d_ctl + CTL_SCRATCH, 0, sizeof(unsigned long long), im->s_comp));
+    hipLaunchKernelGGL((k_snp_regions<false>), dim3(grid), dim3(RF_BLOCK), 0, im->s_comp, t, (uint32_t*)im->d_csr_alt, (const int32_t*)nullptr, (int32_t*)nullptr, im->d_ctl + CTL_SCRATCH);
+    HIP_TRY(hipGetLastError());
+    if (int rc = pf_scan(im, (uint32_t*)im->d_csr_alt, ns + 1, bsum, nullptr)) return rc;
+    HIP_TRY(hipEventRecord(im->ev_r1, im->s_comp));
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, im->s_comp, (const unsigned long long*)(im->d_ctl + CTL_SCRATCH), im->d_hctl + CTL_SCRATCH, 1);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(im->s_comp));
+    const unsigned long long total = im->h_ctl[CTL_SCRATCH];
+    if (total > (unsigned long long)INT32_MAX) {
+        char b[200]; snprintf(b, sizeof b, "xck_refold: %llu (SNP, region) pairs: the SNP -> region table holds at most 2^31 - 1", total);
+        im->eng->err = b; return XCK_E_NOMEM;
+    }
+    *touched = true;
+    if (int rc = refold_grow(im, (void**)&im->d_csr_reg, &im->csr_reg_cap_bytes, std::max<size_t>((size_t)total, 1) * sizeof(int32_t))) return rc;
+    HIP_TRY(hipEventRecord(im->ev_r2, im->s_comp));
+    hipLaunchKernelGGL((k_snp_regions<true>), dim3(grid), dim3(RF_BLOCK), 0, im->s_comp, t, (uint32_t*)nullptr, (const int32_t*)im->d_csr_alt, im->d_csr_reg, (unsigned long long*)nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(im->ev_r3, im->s_comp));
+    std::swap(im->d_csr_off, im->d_csr_alt);
+    if (!h.info.empty()) {
+        const auto t1 = std::chrono::steady_clock::now();
+        HIP_TRY(hipMemcpyAsync(im->d_snp_info, h.info.data(), h.info.size() * sizeof(uint32_t), hipMemcpyHostToDevice, im->s_comp));
+        HIP_TRY(hipStreamSynchronize(im->s_comp));                          // (h.info leaves with this function)
+        im->rf_ms_upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+    }
+    return 0;
+}
+
+int engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out) {
+    xck_engine* e = im->eng;
+    if (im->fold_failed) { e->err = "xck_refold: an earlier fold of this handle failed (call xck_reset)"; return XCK_E_STATE; }
+    if (!im->finished || !im->mol_valid) { e->err = "xck_refold: valid between a successful xck_finish and the next xck_reset"; return XCK_E_STATE; }
+    if (int rc = refold_check(im, cfg)) return rc;
+    HIP_TRY(hipSetDevice(im->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (im->copy_pending) { HIP_TRY(hipStreamSynchronize(im->s_copy)); im->copy_pending = false; }   // the last fold's copy-out reads workspace 2
+    clear_stale_error("refold", e->knobs.debug_timing);
+    bool touched = false;
+    int rc = refold_build_tables(im, cfg, &touched);
+    if (rc) { if (touched || rc != XCK_E_NOMEM) im->fold_failed = true; hipStreamSynchronize(im->s_comp); return rc; }
+    im->n_regions = cfg->n_regions;
+    im->sf.min_count = cfg->min_count <= 0.0 ? 0 : (int32_t)std::min(2147483647.0, std::ceil(cfg->min_count));
+    im->sf.min_maf = cfg->min_maf;
+    im->no_dup_hap = cfg->no_dup_hap;
+    im->cmat_valid = false; im->fmat_valid = false; im->csr_host_stale = im->d_feat != nullptr;
+    im->copy_timed = false;
+    const auto fold = [&]() -> int {
+        if (im->d_feat) if (int r = refold_grow(im, (void**)&im->d_fmat, &im->fmat_cap_bytes, std::max<size_t>((size_t)im->n_regions * 6, 1) * sizeof(unsigned long long))) return r;
+        Timer tm{im, im->ev0, im->ev1};
+        double ms = 0;
+        if (int r = tm.start()) return r;
+        if (int r = im->key_bits == 64 ? fold_regions<uint64_t>(im) : fold_regions<u128>(im)) return r;
+        if (int r = tm.stop(&ms)) return r;
+        im->st.ms_sort += ms; im->rf_ms_regions = ms;
+        HIP_TRY(hipStreamSynchronize(im->s_comp));
+        return 0;
+    };
+    if ((rc = fold())) { im->fold_failed = true; hipStreamSynchronize(im->s_comp); hipStreamSynchronize(im->s_copy); return rc; }
+    { float a = 0, b = 0; HIP_TRY(hipEventElapsedTime(&a, im->ev_r0, im->ev_r1)); HIP_TRY(hipEventElapsedTime(&b, im->ev_r2, im->ev_r3)); im->rf_ms_build = (double)a + b; }
+    im->rf_ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (e->knobs.debug_timing) fprintf(stderr, "[xck] refold: total %.3f ms (host clock to the stream synchronise): table upload %.3f, builder kernels + scan %.3f, region stage %.3f\n",
+                                       im->rf_ms_total, im->rf_ms_upload, im->rf_ms_build, im->rf_ms_regions);
+    im->copy_pending = true;
+    return result_host(im, out);
+}

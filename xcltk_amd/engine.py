@@ -44,6 +44,40 @@ def resolve_contigs(bam_refs, contig_names):
     return t2c
 
 
+def region_array(regions, cidx, strict=True):
+    """xck_region records of (chrom, start1, end1_incl[, name]) tuples; strict=False: a chrom outside cidx becomes contig -1."""
+    # column-wise fills (a per-row structured assignment costs ~1.5 us: 1.5 s for 1 M SNPs)
+    reg = np.zeros(len(regions), dtype=capi.REGION_DTYPE)
+    if len(regions):
+        reg["contig"] = [cidx[r[0]] for r in regions] if strict else [cidx.get(r[0], -1) for r in regions]
+        reg["start"] = [r[1] for r in regions]
+        reg["end"] = [r[2] for r in regions]
+    return reg
+
+
+def snp_array(snps, cidx):
+    """xck_snp records of a SnpTable or of (chrom, pos1, ref, alt, ref_hap, alt_hap) tuples."""
+    snp = np.zeros(len(snps), dtype=capi.SNP_DTYPE)
+    if isinstance(snps, SnpTable):
+        if len(snps):
+            if int(snps.pos.max()) > 2 ** 31 - 1 or int(snps.pos.min()) < -2 ** 31:
+                raise OverflowError("SNP position does not fit the engine's int32 coordinate")
+            snp["contig"] = np.array([cidx[n] for n in snps.names], dtype=np.int32)[snps.chrom_id]
+            snp["pos"] = snps.pos
+            snp["ref"] = snps.ref
+            snp["alt"] = snps.alt
+            snp["ref_hap"] = snps.ref_hap
+            snp["alt_hap"] = snps.alt_hap
+    elif len(snps):
+        snp["contig"] = [cidx[s[0]] for s in snps]
+        snp["pos"] = [s[1] for s in snps]
+        snp["ref"] = [ord(s[2]) for s in snps]
+        snp["alt"] = [ord(s[3]) for s in snps]
+        snp["ref_hap"] = [s[4] for s in snps]
+        snp["alt_hap"] = [s[5] for s in snps]
+    return snp
+
+
 class Engine(object):
     def __init__(self, mode, contig_names, regions, n_cells, snps=(), barcodes=None,
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
@@ -61,32 +95,10 @@ class Engine(object):
         regions = list(regions)
         if not isinstance(snps, SnpTable):
             snps = list(snps)
-        # column-wise fills (a per-row structured assignment costs ~1.5 us: 1.5 s for 1 M SNPs)
-        self._reg = np.zeros(len(regions), dtype=capi.REGION_DTYPE)
-        if regions:
-            self._reg["contig"] = [cidx[r[0]] for r in regions]
-            self._reg["start"] = [r[1] for r in regions]
-            self._reg["end"] = [r[2] for r in regions]
-            if region_mask is not None:
-                self._reg["contig"][~np.asarray(region_mask, dtype=bool)] = -1
-        self._snp = np.zeros(len(snps), dtype=capi.SNP_DTYPE)
-        if isinstance(snps, SnpTable):
-            if len(snps):
-                if int(snps.pos.max()) > 2 ** 31 - 1 or int(snps.pos.min()) < -2 ** 31:
-                    raise OverflowError("SNP position does not fit the engine's int32 coordinate")
-                self._snp["contig"] = np.array([cidx[n] for n in snps.names], dtype=np.int32)[snps.chrom_id]
-                self._snp["pos"] = snps.pos
-                self._snp["ref"] = snps.ref
-                self._snp["alt"] = snps.alt
-                self._snp["ref_hap"] = snps.ref_hap
-                self._snp["alt_hap"] = snps.alt_hap
-        elif snps:
-            self._snp["contig"] = [cidx[s[0]] for s in snps]
-            self._snp["pos"] = [s[1] for s in snps]
-            self._snp["ref"] = [ord(s[2]) for s in snps]
-            self._snp["alt"] = [ord(s[3]) for s in snps]
-            self._snp["ref_hap"] = [s[4] for s in snps]
-            self._snp["alt_hap"] = [s[5] for s in snps]
+        self._reg = region_array(regions, cidx)
+        if regions and region_mask is not None:
+            self._reg["contig"][~np.asarray(region_mask, dtype=bool)] = -1
+        self._snp = snp_array(snps, cidx)
         cfg = capi.Config()
         cfg.struct_size = C.sizeof(capi.Config)
         cfg.mode = mode
@@ -336,6 +348,54 @@ class Engine(object):
             out["count"] = res.count.to_numpy(copy)
         if self.mode & XCK_MODE_BAF:
             out.update(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
+        return out
+
+    def refold(self, regions, snps=None, snp_enabled=None, min_count=1, min_maf=0, no_dup_hap=True, excl_pairs=None, copy=True):
+        """Recount the pileup of the last finish() under new tables and filters, without the reads (xck_refold): returns what
+        finish() returns, as a fresh engine would that was made with these tables and fed the same reads.  regions as for the
+        constructor (a chrom outside contig_names gives an empty row); snps=None keeps the engine's, otherwise the same SNPs index
+        by index with their own ref / alt / haplotype columns; snp_enabled (bool per SNP): False feeds no region; excl_pairs =
+        (region indices into the NEW regions, snp indices).  Valid between finish() and reset(), as often as wanted."""
+        cidx = {n: i for i, n in enumerate(self.contig_names)}
+        regions = list(regions)
+        reg = region_array(regions, cidx, strict=False)
+        cfg = capi.RefoldConfig()
+        cfg.struct_size = C.sizeof(capi.RefoldConfig)
+        cfg.n_regions = len(regions)
+        cfg.regions = reg.ctypes.data_as(C.POINTER(capi.Region))
+        keep = [reg]
+        if snps is not None:
+            if not isinstance(snps, SnpTable):
+                snps = list(snps)
+            snp = snp_array(snps, cidx)
+            cfg.n_snps = len(snp)
+            cfg.snps = snp.ctypes.data_as(C.POINTER(capi.Snp))
+            keep.append(snp)
+        if snp_enabled is not None:
+            en = np.ascontiguousarray(np.asarray(snp_enabled, dtype=bool).astype(np.uint8))
+            if len(en) != len(self._snp):
+                raise ValueError("snp_enabled needs one entry per SNP of the engine")
+            cfg.snp_enabled = en.ctypes.data_as(C.POINTER(C.c_uint8))
+            keep.append(en)
+        cfg.min_count = float(min_count)
+        cfg.min_maf = float(min_maf)
+        cfg.no_dup_hap = 1 if no_dup_hap else 0
+        if excl_pairs is not None and len(excl_pairs[0]):
+            er = np.ascontiguousarray(excl_pairs[0], dtype=np.int32)
+            es = np.ascontiguousarray(excl_pairs[1], dtype=np.int32)
+            assert len(er) == len(es)
+            cfg.n_excl_pairs = len(er)
+            cfg.excl_region = er.ctypes.data_as(C.POINTER(C.c_int32))
+            cfg.excl_snp = es.ctypes.data_as(C.POINTER(C.c_int32))
+            keep += [er, es]
+        res = capi.Result()
+        self._check(self.lib.xck_refold(self.h, C.byref(cfg), C.byref(res)), "xck_refold")
+        self._result = res
+        self.n_regions = len(regions)
+        out = {}
+        if self.mode & XCK_MODE_BASEFC:
+            out["count"] = res.count.to_numpy(copy)
+        out.update(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
         return out
 
     def result_device(self):

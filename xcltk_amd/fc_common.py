@@ -536,6 +536,12 @@ def make_engine(conf, mode, regions, snps=(), device=None, **extra):
     return eng
 
 
+def dist_requested():
+    """True when the environment asks for a multi-GPU run (several ranks, or XCK_DIST_FORCE): what makes a Dist active, asked
+    without making one."""
+    return int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("XCK_DIST_FORCE", "0") not in ("", "0")
+
+
 class Dist(object):
     """Multi-GPU context (one process per GPU).  With WORLD_SIZE > 1 every
     rank builds the full tables, streams only the contigs it owns (LPT on .bai record counts,
