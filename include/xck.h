@@ -400,6 +400,25 @@ typedef struct xck_refold_config {
     const int32_t* excl_snp;
 } xck_refold_config;
 int  xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out);
+/* The SNP x cell matrices of the finished pileup (additive, as xck_refold is: ABI 3 is unchanged; a caller built against an older header
+ * of ABI 3 does not see the symbol and loses nothing): out->ad / dp / oth with row = index of the SNP in the
+ * list given to xck_create, col = cell, sorted by (row, col); out->count is empty.  Counted from what xck_finish keeps of the molecule
+ * stage - the hits sorted by (SNP, cell, UMI) and the base the first read of every molecule shows - without the reads, without a region
+ * table and without a sort.  Per (SNP, cell): AD = molecules that show the SNP's ALT, DP = molecules that show REF or ALT (ALT wins when
+ * REF == ALT), OTH = molecules that show another base; zero values are not emitted; a molecule that a gap record claims (an N / D
+ * gap over the SNP earlier in fetch order) counts nowhere.  These are the matrices of a handle made with one one-base region per SNP,
+ * REF on haplotype 0, ALT on haplotype 1, min_count 1, min_maf 0.  Every SNP of the handle's table counts, whatever snp_enabled mask,
+ * regions, exclusion pairs, haplotype indices, filters or no_dup_hap the handle or its last xck_refold carry; REF / ALT are the
+ * handle's current ones (an xck_refold with other alleles is followed).
+ * Valid where xck_refold is: on a handle with a BAF pipeline (a XCK_MODE_BOTH handle answers from it), between a successful
+ * xck_finish and the next xck_reset, as often as wanted.  The call uses buffers of its own: it leaves the handle's tables and
+ * results alone and does not invalidate what xck_finish / xck_refold / xck_get_result_device handed out, and a later xck_refold
+ * does not invalidate its blocks, which are valid until the next xck_snp_counts, xck_reset or xck_destroy.
+ * XCK_E_STATE before a finish, after a reset, on a decode-only handle, or when a fold of the handle has failed; XCK_E_ARG for a
+ * basefc-only handle or a null out; XCK_E_CAPACITY when the sorted stream holds 2^32 hits or more (the call counts in 32 bits;
+ * the split pileup fold has the same limit).  A handle without hits gives XCK_OK and three empty matrices.  An error leaves the handle as it
+ * was: a failure inside the call (no memory for its own buffers) does not mark the handle failed. */
+int  xck_snp_counts(xck_engine* e, xck_result* out);
 /* Forget all pushed reads, keep tables and buffers (lets one engine be re-used per step). */
 int  xck_reset(xck_engine* e);
 int  xck_get_stats(const xck_engine* e, xck_stats* out);

@@ -30,6 +30,17 @@ def afc_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_list_
                 ref_cell_fn=None, cell_tag="CB", umi_tag="UB", min_count=1, min_maf=0,
                 output_all_reg=False, no_dup_hap=True, min_mapq=20, min_len=30, incl_flag=0,
                 excl_flag=None, no_orphan=True):
+    return afc_run(afc_conf(sam_fn=sam_fn, barcode_fn=barcode_fn, region_fn=region_fn, phased_snp_fn=phased_snp_fn, out_dir=out_dir,
+                            sam_list_fn=sam_list_fn, sample_ids=sample_ids, sample_id_fn=sample_id_fn, debug_level=debug_level, ncores=ncores,
+                            cellsnp_dir=cellsnp_dir, ref_cell_fn=ref_cell_fn, cell_tag=cell_tag, umi_tag=umi_tag, min_count=min_count,
+                            min_maf=min_maf, output_all_reg=output_all_reg, no_dup_hap=no_dup_hap, min_mapq=min_mapq, min_len=min_len,
+                            incl_flag=incl_flag, excl_flag=excl_flag, no_orphan=no_orphan))
+
+
+def afc_conf(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_list_fn=None, sample_ids=None, sample_id_fn=None, debug_level=0,
+             ncores=1, cellsnp_dir=None, ref_cell_fn=None, cell_tag="CB", umi_tag="UB", min_count=1, min_maf=0, output_all_reg=False,
+             no_dup_hap=True, min_mapq=20, min_len=30, incl_flag=0, excl_flag=None, no_orphan=True):
+    """The Config of one afc_wrapper call, not yet resolved (prepare_config)."""
     conf = Config()
     conf.sam_fn, conf.sam_list_fn = sam_fn, sam_list_fn
     conf.barcode_fn, conf.region_fn, conf.snp_fn = barcode_fn, region_fn, phased_snp_fn
@@ -44,7 +55,7 @@ def afc_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_list_
     conf.incl_flag = incl_flag
     conf.excl_flag = -1 if excl_flag is None else excl_flag
     conf.no_orphan = no_orphan
-    return afc_run(conf)
+    return conf
 
 
 def prepare_config(conf):
@@ -168,6 +179,18 @@ def phased_tables(conf, regions, snps, has_snp):
     return snps, (ex_r, ex_s)
 
 
+def write_matrices(conf, eng, dist, regions, coo):
+    """xcltk.region.tsv and the three .mtx files of one counted table (afc_wrapper, afc_variants and the one-pass `xcltk baf` write
+    through here).  Only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113), unless output_all_reg."""
+    rm = fcc.output_row_map(dist, len(regions), conf.output_all_reg, coo["dp"][0], coo["oth"][0])
+    n_rows = int(rm.max()) if len(rm) else 0
+    if fcc.is_writer_rank():
+        fcc.write_region_tsv(conf.out_region_fn, regions, rm)
+    fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, n_rows)
+    fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, n_rows)
+    fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, n_rows)
+
+
 def afc_core(conf):
     if prepare_config(conf) < 0:
         raise ValueError("errcode -2")
@@ -184,14 +207,7 @@ def afc_core(conf):
         fcc.write_feature_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "feature_summary.tsv"), regions)   # (XCK_FEATURE_SUMMARY=1 only)
         fcc.write_snp_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "snp_summary.tsv"), snps)
         if coo is not None:                               # the only process / rank 0 after a gather / every rank (sharded output)
-            # only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113)
-            rm = fcc.output_row_map(dist, len(regions), conf.output_all_reg, coo["dp"][0], coo["oth"][0])
-            n_rows = int(rm.max()) if len(rm) else 0
-            if fcc.is_writer_rank():
-                fcc.write_region_tsv(conf.out_region_fn, regions, rm)
-            fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, n_rows)
-            fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, n_rows)
-            fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, n_rows)
+            write_matrices(conf, eng, dist, regions, coo)
         if conf.debug > 0:
             info("engine stats: %s" % eng.stats())
     finally:

@@ -17,7 +17,7 @@ import numpy as np
 from ... import fc_common as fcc
 from ...capi import XCK_MODE_BAF
 from .config import Config
-from .main import phased_tables, prepare_config, regions_with_snps
+from .main import phased_tables, prepare_config, regions_with_snps, write_matrices
 
 # what all variants share (arguments of afc_wrapper), and what a variant may set
 COMMON_KEYS = ("sam_fn", "sam_list_fn", "barcode_fn", "sample_ids", "sample_id_fn", "phased_snp_fn", "debug_level", "ncores", "cell_tag",
@@ -44,6 +44,28 @@ def map_to_universe(universe, snps):
         idx[k] = i
         enabled[i] = True
     return idx, enabled
+
+
+def plan_tables(universe, conf):
+    """What one prepared Config (prepare_config) counts with on an engine whose SNP table is `universe`: its regions, its own SNP
+    list after local phasing, where those SNPs sit in the universe, which of the universe it lists, the universe with this list's
+    alleles and haplotype indices, and the exclusion pairs in the universe's numbering.  ValueError as map_to_universe."""
+    regions, snps = conf.reg_list, list(conf.snp_list)
+    u_idx, enabled = map_to_universe(universe, snps)
+    snps, excl = phased_tables(conf, regions, snps, regions_with_snps(regions, snps))
+    table = list(universe)
+    for i, s in zip(u_idx.tolist(), snps):
+        table[i] = tuple(s)
+    if excl is not None:
+        excl = (np.asarray(excl[0], dtype=np.int32), u_idx[np.asarray(excl[1], dtype=np.int64)].astype(np.int32))
+    return dict(conf=conf, regions=regions, snps=snps, u_idx=u_idx, enabled=enabled, table=table, excl=excl)
+
+
+def refold_plan(eng, p, copy=False):
+    """Engine.refold under the tables of one plan_tables() result."""
+    conf = p["conf"]
+    return eng.refold(p["regions"], snps=p["table"], snp_enabled=None if p["enabled"].all() else p["enabled"],
+                      min_count=conf.min_count, min_maf=conf.min_maf, no_dup_hap=conf.no_dup_hap, excl_pairs=p["excl"], copy=copy)
 
 
 def _variant_conf(common, var):
@@ -95,15 +117,7 @@ def afc_variants(common, variants):
         conf = _variant_conf(common, var)
         if prepare_config(conf) < 0:
             raise ValueError("errcode -2")
-        regions, snps = conf.reg_list, list(conf.snp_list)
-        u_idx, enabled = map_to_universe(universe, snps)
-        snps, excl = phased_tables(conf, regions, snps, regions_with_snps(regions, snps))
-        table = list(universe)                             # the universe with this variant's alleles and haplotype indices
-        for i, s in zip(u_idx.tolist(), snps):
-            table[i] = tuple(s)
-        if excl is not None:
-            excl = (np.asarray(excl[0], dtype=np.int32), u_idx[np.asarray(excl[1], dtype=np.int64)].astype(np.int32))
-        plans.append(dict(conf=conf, regions=regions, snps=snps, u_idx=u_idx, enabled=enabled, table=table, excl=excl))
+        plans.append(plan_tables(universe, conf))
     # the engine is made with the variant that has the most regions: the row field of its keys then fits every table
     first = max(range(len(plans)), key=lambda i: len(plans[i]["regions"]))
     order = [first] + [i for i in range(len(plans)) if i != first]
@@ -114,8 +128,7 @@ def afc_variants(common, variants):
             p = plans[i]
             conf = p["conf"]
             if i != first or not p["enabled"].all():       # (the engine was made with the whole universe enabled)
-                coo = eng.refold(p["regions"], snps=p["table"], snp_enabled=None if p["enabled"].all() else p["enabled"],
-                                 min_count=conf.min_count, min_maf=conf.min_maf, no_dup_hap=conf.no_dup_hap, excl_pairs=p["excl"], copy=False)
+                coo = refold_plan(eng, p)
                 info("[engine] variant %d recounted under its own tables (%d regions)" % (i, len(p["regions"])))
             pre = os.path.join(conf.out_dir, conf.out_prefix)
             fcc.write_read_summary(eng, dist, pre + "read_summary.tsv")
@@ -128,12 +141,7 @@ def afc_variants(common, variants):
                 if fs is not None and fs["snp"] is not None:
                     with open(pre + "snp_summary.tsv", "w") as fp:
                         fp.write(fcc.snp_summary_text(list(p["snps"]), np.asarray(fs["snp"], dtype=np.int64)[p["u_idx"]]))
-            rm = fcc.output_row_map(dist, len(p["regions"]), conf.output_all_reg, coo["dp"][0], coo["oth"][0])
-            n_rows = int(rm.max()) if len(rm) else 0
-            fcc.write_region_tsv(conf.out_region_fn, p["regions"], rm)
-            fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, n_rows)
-            fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, n_rows)
-            fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, n_rows)
+            write_matrices(conf, eng, dist, p["regions"], coo)
     finally:
         eng.close()
     return 0

@@ -93,11 +93,9 @@ def filter_snps(in_dir, out_dir, min_count, min_maf):
     return fn, d.shape[1], sub.shape[1]
 
 
-def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sample_id=None, snp_vcf_fn=None,
-           out_dir=None, mode="droplet", cell_tag="CB", umi_tag="UB", ncores=1, min_count=20, min_maf=0.1,
-           script_fn=None, log_fn=None):
-    """Signature of the reference's pileup() (baf/genotype.py:20-187); the engine replaces the cellsnp-lite call.
-    Returns (output VCF, #SNPs in <out_dir>/raw, #SNPs after filtering)."""
+def pileup_conf(sam_fn, sam_list_fn, barcode_fn, sample_id_fn, sample_id, mode, cell_tag, umi_tag, ncores):
+    """The resolved configuration of the step-1 pileup: BAM list, cells, tags and the read filters cellsnp-lite and xcltk share; the
+    per-SNP filters are off in the engine (they are applied to the sums of raw/ afterwards).  ValueError for invalid inputs."""
     if mode not in ("droplet", "well", "bulk"):
         raise ValueError("mode must be droplet, well or bulk")
     conf = type("PileupConf", (), {})()
@@ -114,6 +112,15 @@ def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sa
     conf.defaults = type("D", (), dict(UMI_TAG_BC="UB"))()
     if fcc.resolve_inputs(conf) < 0 or fcc.resolve_tags(conf) < 0:
         raise ValueError("invalid pileup inputs")
+    return conf
+
+
+def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sample_id=None, snp_vcf_fn=None,
+           out_dir=None, mode="droplet", cell_tag="CB", umi_tag="UB", ncores=1, min_count=20, min_maf=0.1,
+           script_fn=None, log_fn=None):
+    """Signature of the reference's pileup() (baf/genotype.py:20-187); the engine replaces the cellsnp-lite call.
+    Returns (output VCF, #SNPs in <out_dir>/raw, #SNPs after filtering)."""
+    conf = pileup_conf(sam_fn, sam_list_fn, barcode_fn, sample_id_fn, sample_id, mode, cell_tag, umi_tag, ncores)
     if not snp_vcf_fn or not os.path.isfile(snp_vcf_fn):
         raise ValueError("SNP vcf '%s' does not exist." % snp_vcf_fn)
     cand = load_candidate_snps(snp_vcf_fn)

@@ -103,6 +103,17 @@ def pipeline_main(argv):
     return ret
 
 
+def step3_arguments(sam_fn, sam_list_fn, barcode_fn, sample_id, sample_id_fn, region_fn, phased_snp_fn, fc_dir, pileup_dir, ref_cell_fn,
+                    cell_tag, umi_tag, ncores):
+    """The keyword arguments of step 3's afc_wrapper call, the same as the reference's (baf/pipeline.py:341-360): the pileup directory
+    drives the local phasing.  pipeline_wrapper and the one-pass path (baf/onepass.py) both count with exactly these."""
+    return dict(sam_fn=sam_fn, barcode_fn=barcode_fn, region_fn=region_fn, phased_snp_fn=phased_snp_fn,
+                out_dir=fc_dir, sam_list_fn=sam_list_fn, sample_ids=sample_id, sample_id_fn=sample_id_fn,
+                debug_level=0, ncores=ncores, cellsnp_dir=pileup_dir, ref_cell_fn=ref_cell_fn,
+                cell_tag=cell_tag, umi_tag=umi_tag, min_count=1, min_maf=0, output_all_reg=True,
+                no_dup_hap=True, min_mapq=20, min_len=30, incl_flag=0, excl_flag=None, no_orphan=True)
+
+
 def pipeline_wrapper(label, sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None,
                      snp_vcf_fn=None, region_fn=None, out_dir=None, gmap_fn=None, eagle_fn=None,
                      panel_dir=None, ref_cell_fn=None, cell_tag="CB", umi_tag="UB", min_count=11,
@@ -116,6 +127,14 @@ def pipeline_wrapper(label, sam_fn=None, sam_list_fn=None, barcode_fn=None, samp
     mode = "droplet" if barcode_fn is not None else ("well" if sample_id_fn is not None else "bulk")
     if mode == "bulk":
         sample_id = label                      # bulk: the label is the sample id
+    # XCK_BAF_ONE_PASS=1 (opt-in): steps 1 and 3 from one pass over the BAMs (baf/onepass.py); None = it named a reason to fall back
+    if os.environ.get("XCK_BAF_ONE_PASS", "0") not in ("", "0"):
+        from . import onepass
+        step3 = step3_arguments(sam_fn, sam_list_fn, barcode_fn, sample_id, sample_id_fn, region_fn, phased_snp_fn, os.path.join(out_dir, "3_baf_fc"),
+                                os.path.join(out_dir, "1_pileup"), ref_cell_fn, cell_tag, umi_tag, ncores)
+        ret = onepass.run(sam_fn, sam_list_fn, barcode_fn, sample_id_fn, sample_id, mode, snp_vcf_fn, cell_tag, umi_tag, min_count, min_maf, ncores, step3)
+        if ret is not None:
+            return ret
     # step 1: per-SNP x cell pileup of the candidate SNPs.  The reference runs the external cellsnp-lite binary here
     # (baf/genotype.py:144-187); this engine produces the same directory itself (baf/genotype.py of this package).
     pileup_dir = None
@@ -143,11 +162,7 @@ def pipeline_wrapper(label, sam_fn=None, sam_list_fn=None, barcode_fn=None, samp
     fc_dir = os.path.join(out_dir, "3_baf_fc")
     os.makedirs(fc_dir, exist_ok=True)
     info("BAF feature counting ...")
-    # same arguments as the reference's call of baf_fc (baf/pipeline.py:341-360): the pileup directory drives the local phasing
-    ret = baf_fc(sam_fn=sam_fn, barcode_fn=barcode_fn, region_fn=region_fn, phased_snp_fn=phased_snp_fn,
-                 out_dir=fc_dir, sam_list_fn=sam_list_fn, sample_ids=sample_id, sample_id_fn=sample_id_fn,
-                 debug_level=0, ncores=ncores, cellsnp_dir=pileup_dir, ref_cell_fn=ref_cell_fn,
-                 cell_tag=cell_tag, umi_tag=umi_tag, min_count=1, min_maf=0, output_all_reg=True,
-                 no_dup_hap=True, min_mapq=20, min_len=30, incl_flag=0, excl_flag=None, no_orphan=True)
+    ret = baf_fc(**step3_arguments(sam_fn, sam_list_fn, barcode_fn, sample_id, sample_id_fn, region_fn, phased_snp_fn, fc_dir, pileup_dir, ref_cell_fn,
+                                   cell_tag, umi_tag, ncores))
     info("feature BAFs are at '%s'." % fc_dir)
     return ret

@@ -180,6 +180,7 @@ SYMBOLS = [
     ("xck_finish_async", C.c_int, [C.c_void_p]),
     ("xck_get_result_device", C.c_int, [C.c_void_p, _P(Result)]),
     ("xck_refold", C.c_int, [C.c_void_p, _P(RefoldConfig), _P(Result)]),
+    ("xck_snp_counts", C.c_int, [C.c_void_p, _P(Result)]),
     ("xck_reset", C.c_int, [C.c_void_p]),
     ("xck_get_stats", C.c_int, [C.c_void_p, _P(Stats)]),
     ("xck_get_decode_stats", C.c_int, [C.c_void_p, _P(DecodeStats)]),

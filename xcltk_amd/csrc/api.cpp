@@ -319,6 +319,14 @@ int xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out) {
     return XCK_OK;
 }
 
+int xck_snp_counts(xck_engine* e, xck_result* out) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (!out) { e->err = "xck_snp_counts: null result"; return XCK_E_ARG; }
+    if (e->n_impl <= 0) return no_engine(e);
+    if (!(e->mode & XCK_MODE_BAF)) { e->err = "xck_snp_counts: the handle has no BAF pipeline"; return XCK_E_ARG; }
+    return engine_snp_counts(e->impls[e->n_impl - 1], out);              // (a fused handle answers from its pileup pipeline)
+}
+
 int xck_get_stats(const xck_engine* e, xck_stats* out) {
     if (!e || !out) return XCK_E_ARG;
     if (e->n_impl == 0) return XCK_E_STATE;

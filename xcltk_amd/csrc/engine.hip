@@ -953,7 +953,7 @@ static int build_tables(EngineImpl* im, const xck_config* cfg) {
 
 // Grow-only buffers (capacities in bytes): afterwards *p holds at least `need` bytes.  A buffer that is too small is freed and
 // allocated anew with need + slack bytes - its contents are not kept - and a failure leaves it empty (null, capacity 0).
-static int grow_device(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack) {
+int grow_device(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack) {
     if (need <= *cap) return 0;
     if (*p) HIP_TRY(hipFree(*p));
     *p = nullptr; *cap = 0;
@@ -962,7 +962,7 @@ static int grow_device(EngineImpl* im, void** p, size_t* cap, size_t need, size_
     return 0;
 }
 // ... and its twin for pinned, mapped host memory
-static int grow_pinned(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack) {
+int grow_pinned(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack) {
     if (need <= *cap) return 0;
     if (*p) HIP_TRY(hipHostFree(*p));
     *p = nullptr; *cap = 0;
@@ -1300,7 +1300,7 @@ int engine_reset(EngineImpl* im) {
     if (im->d_feat) { rc = feature_summary_reset(im); if (rc) return rc; }
     im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
-    im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false; im->mol_valid = false;
+    im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false; im->mol_valid = false; im->sc_valid = false;
     for (int i = 0; i < CTL_WORDS; i++) im->h_ctl[i] = 0;
     for (int sh = 0; sh < NSHARD; sh++) { im->cur[sh] = 0; im->ncur[sh] = 0; }
     int kb = im->key_bits, ub = im->ubits;
@@ -1382,10 +1382,12 @@ void engine_destroy(EngineImpl* im) {
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
                      im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept,
-                     im->d_csr_alt, im->d_rf, im->ws1.base, im->ws2.base };
+                     im->d_csr_alt, im->d_rf, im->d_sc, im->d_sc_res, im->d_sc_perm, im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }
     for (int m = 0; m < 4; m++) if (im->h_res[m]) hipHostFree(im->h_res[m]);
+    if (im->h_sc_res) hipHostFree(im->h_sc_res);
+    if (im->h_sc_tot) hipHostFree(im->h_sc_tot);
     if (im->h_ctl) hipHostFree(im->h_ctl);
     if (im->ev0) hipEventDestroy(im->ev0);
     if (im->ev1) hipEventDestroy(im->ev1);
@@ -1395,6 +1397,7 @@ void engine_destroy(EngineImpl* im) {
     if (im->ev_f1) hipEventDestroy(im->ev_f1);
     if (im->ev_f2) hipEventDestroy(im->ev_f2);
     for (hipEvent_t ev : { im->ev_r0, im->ev_r1, im->ev_r2, im->ev_r3 }) if (ev) hipEventDestroy(ev);
+    for (hipEvent_t ev : im->ev_s) if (ev) hipEventDestroy(ev);
     if (im->s_copy) hipStreamDestroy(im->s_copy);
     if (im->s_comp) hipStreamDestroy(im->s_comp);
     delete im;

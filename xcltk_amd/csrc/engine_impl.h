@@ -213,6 +213,16 @@ struct EngineImpl {
     char* d_rf = nullptr; size_t rf_cap = 0;              // sorted regions, exclusion words, SNP mask, contig table, scan block sums
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr, ev_r2 = nullptr, ev_r3 = nullptr;   // count pass + scan, fill pass
     double rf_ms_upload = 0, rf_ms_build = 0, rf_ms_regions = 0, rf_ms_total = 0;   // the last refold, for XCK_DEBUG_TIMING and tools/refold_time.py
+    // xck_snp_counts (snp_counts.h): buffers of its own, grow-only - scratch, the three COO blocks [ad | dp | oth] on the device and in
+    // pinned host memory (valid until the next xck_snp_counts / reset), the sorted SNP -> caller index table on the device
+    char* d_sc = nullptr; size_t sc_cap = 0;
+    int32_t* d_sc_res = nullptr; size_t sc_res_cap = 0;
+    int32_t* h_sc_res = nullptr; size_t h_sc_res_cap = 0;
+    int32_t* d_sc_perm = nullptr;
+    unsigned long long *h_sc_tot = nullptr, *d_sc_tot_alias = nullptr;   // the three totals: pinned + mapped words and their device alias
+    size_t sc_nnz[3] = {0, 0, 0}; bool sc_valid = false;
+    hipEvent_t ev_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double sc_ms_heads = 0, sc_ms_rows = 0, sc_ms_emit = 0, sc_ms_copy = 0, sc_ms_total = 0;   // the last call, for XCK_DEBUG_TIMING and tools/snp_counts_time.py
 };
 
 // d_snp_info: ref nibble | alt nibble << 4 | ref_hap << 8 | alt_hap << 9
@@ -256,6 +266,8 @@ size_t key_bytes(const EngineImpl* im);
 size_t hit_slack(const EngineImpl* im);
 bool split_mode(const EngineImpl* im);
 int arena_begin(EngineImpl* im, Arena& a, size_t need);
+int grow_device(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack);   // grow-only buffers (capacities in bytes); contents are not kept
+int grow_pinned(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack);
 int res_reserve(EngineImpl* im, int m, size_t nnz);
 int complete_pending(EngineImpl* im);
 int launch_queue(EngineImpl* im, int slot_idx, int shared_slot = -1);

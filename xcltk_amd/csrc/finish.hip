@@ -9,6 +9,7 @@
 //                 SNP -> region fan-out), region-level hits partitioned again and classified per item by an LDS hash set
 //                 (k_hap_items; fallback: sort + k_hap_class / k_hap_sum), k_hap_count / k_hap_scatter (AD / DP / OTH -> COO);
 //                 128-bit keys: k_first_read and the sorted path.
+//   snp_counts  : the SNP x cell matrices of the finished pileup from the molecule stage alone (snp_counts.h).
 //                 Copy-out on the copy stream (xck_finish_async).
 //
 // Integer / byte work only - HBM-bound, no MFMA.  See DESIGN.md for layouts, byte counts and measurements.
@@ -503,6 +504,15 @@ __global__ void __launch_bounds__(256) k_snp_verdict(const uint32_t* __restrict_
     if (s < n) kept[s] = snp_passes(tally, info, s, f) ? 1u : 0u;
 }
 
+// which allele of its SNP a base is: 1 = ALT, 0 = REF, -1 = another base (snp.gt = {ref: ref_idx, alt: alt_idx}: ALT wins when REF == ALT).
+// nib: the base's nibble; inf: the SNP's d_snp_info word.  k_expand and the SNP-level counts (snp_counts.h) both decide with it.
+__device__ __forceinline__ int allele_side(int nib, uint32_t inf) {
+    int side = -1;
+    if (nib == int(inf & 15)) side = 0;
+    if (nib == int((inf >> 4) & 15)) side = 1;
+    return side;
+}
+
 // BAF step 2: expand each surviving (snp, cell, umi, allele) to the regions that contain the SNP
 // (baf/fc/main.py:92-101, core.py:156-166).  COUNT pass sums the fan-out, EMIT pass writes.
 template <class K, bool EMIT, class V>
@@ -537,9 +547,8 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_expand(const K* __restrict__ k, 
     unsigned long long dst = s_base + excl;
     uint32_t inf = info[s];
     int nib = int(code) - 1;
-    int idx = -1;                                        // snp.gt = {ref: ref_idx, alt: alt_idx}: alt wins if equal
-    if (nib == int(inf & 15)) idx = int((inf >> 8) & 1);
-    if (nib == int((inf >> 4) & 15)) idx = int((inf >> 9) & 1);
+    const int side = allele_side(nib, inf);
+    const int idx = side < 0 ? -1 : int((inf >> (8 + side)) & 1);   // the haplotype index of that allele
     const V bits = idx == 0 ? 1 : idx == 1 ? 2 : 4;
     uint32_t cell = kl.cell(me); uint64_t umi = kl.umi(me);
     if (pack_shift >= 0) umi |= (uint64_t)(idx == 0 ? 0u : idx == 1 ? 1u : 2u) << pack_shift;
@@ -1453,6 +1462,7 @@ int snp_verdicts(EngineImpl* im, uint32_t* d_kept) {
 }
 
 #include "refold.h"
+#include "snp_counts.h"
 
 int finish_init(EngineImpl* im) {
     // the hash fold needs 64 KB of dynamic LDS: raise the limit on THIS engine's device (a per-process flag would leave every

@@ -169,6 +169,7 @@ int  engine_finish(EngineImpl* im, xck_result* out);
 int  engine_finish_async(EngineImpl* im);
 int  engine_result_device(EngineImpl* im, xck_result* out);
 int  engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out);   // refold.h (finish.hip): the pileup pipeline's region stage under new tables
+int  engine_snp_counts(EngineImpl* im, xck_result* out);           // snp_counts.h (finish.hip): SNP x cell AD / DP / OTH of the finished pileup
 int  engine_reset(EngineImpl* im);
 int  engine_stats(const EngineImpl* im, xck_stats* out);
 int  engine_read_fate(EngineImpl* im, xck_read_fate* out);         // read_fate.h

@@ -398,6 +398,17 @@ class Engine(object):
         out.update(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
         return out
 
+    def snp_counts(self, copy=True):
+        """The SNP x cell matrices of the last finish() (xck_snp_counts): {"ad": (row, col, val), "dp": .., "oth": ..} with row =
+        index into the SNP list the engine was made with, col = cell, sorted by (row, col) - what an engine with one one-base region
+        per SNP (REF on haplotype 0, ALT on 1, min_count 1, min_maf 0) would return.  Every SNP counts, whatever regions, mask and
+        filters the engine or its last refold() carry; REF / ALT are the current ones.  Valid between finish() and reset(); it
+        leaves the results of finish() / refold() / result_device() alone.  copy=False returns views of the engine's pinned
+        buffers, valid until the next snp_counts(), reset() or close()."""
+        res = capi.Result()
+        self._check(self.lib.xck_snp_counts(self.h, C.byref(res)), "xck_snp_counts")
+        return dict(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
+
     def result_device(self):
         """Device-resident copy of the last finish(): {name: (device_ptr_of_[row|col|val], nnz)}."""
         res = capi.Result()
