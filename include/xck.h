@@ -24,7 +24,6 @@
  *   XCK_FULL_SORT=1                       radix-sort fold over all key bits
  *   XCK_PILEUP_SORT=radix                 library radix sorts for both pileup stages (the fallback path, forced)
  *   XCK_PILEUP_HAP=sorted|values          region-level hits: sorted items + k_hap_class, or class in a value word instead of packed bits
- *   XCK_PILEUP_ITEM_SORT=bitonic          LDS item sort by the bitonic network
  *   XCK_PILEUP_LGG=<l>                    at most 2^l cell groups per SNP in the pileup partitions (default 10)
  *   XCK_HIT_CAP0, XCK_HIT_SLACK           first capacity / head room of the hit accumulators (tests: reach the overflow-replay path)
  *   XCK_PUSH_STAGE=0|1, XCK_PUSH_STAGE_BYTES   xck_push_batch: packed one-copy form always / never / below this size (default 2 MB)

@@ -19,7 +19,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.fixture
 def fold_env():
-    saved = {k: os.environ.get(k) for k in ("XCK_FOLD", "XCK_FOLD_C", "XCK_FOLD_LGG", "XCK_PILEUP_SORT", "XCK_PILEUP_ITEM_SORT", "XCK_PILEUP_HAP")}
+    saved = {k: os.environ.get(k) for k in ("XCK_FOLD", "XCK_FOLD_C", "XCK_FOLD_LGG", "XCK_FOLD_OVERLAP", "XCK_FOLD_COPIES_LG", "XCK_PILEUP_SORT", "XCK_PILEUP_HAP")}
     yield os.environ
     for k, v in saved.items():
         if v is None:
@@ -95,6 +95,25 @@ def test_hot_gene_goes_through_level_two(fold_env):
     assert st["fold_path"] == 1
 
 
+def test_bucket_pass_order_and_counter_copies_do_not_change_the_matrix(fold_env):
+    """The workload of test_hot_gene_goes_through_level_two (big cells exist, more than 2^4 level-1 blocks): the level-1 bucket pass on
+    the second stream beside level 2 (XCK_FOLD_OVERLAP=1, the default) and after it on the main stream (0), with 2^4 copies of the level-1
+    counters and with one (XCK_FOLD_COPIES_LG).  Every combination must give the matrix of the radix-sort fold."""
+    names, regions, batches = _workload(200000, 4096, 3, seed=33, span=400000)
+    for k in ("XCK_FOLD_OVERLAP", "XCK_FOLD_COPIES_LG"):
+        fold_env.pop(k, None)
+    fold_env["XCK_FOLD_C"], fold_env["XCK_FOLD_LGG"] = "64", "3"
+    fold_env["XCK_FOLD"] = "sort"
+    ref, _ = _run(names, regions, 4096, batches)
+    fold_env.pop("XCK_FOLD")
+    for overlap in ("1", "0"):
+        for copies_lg in ("4", "0"):
+            fold_env["XCK_FOLD_OVERLAP"], fold_env["XCK_FOLD_COPIES_LG"] = overlap, copies_lg
+            got, st = _run(names, regions, 4096, batches)
+            util.assert_coo_equal(got, ref, ["count"])
+            assert st["fold_path"] == 1 and st["fold_fallbacks"] == 0
+
+
 def test_deep_cell_is_cut_by_umi_hash(fold_env):
     """Bulk-like input: ONE cell, so a (gene, cell) holds ~20 k distinct keys - more than a work item (2 x 1024 keys) holds: level 2 cuts
     such a cell into UMI-hash parts, the parts' counts are added into one entry (continuation entries across work items)."""
@@ -141,23 +160,20 @@ def test_unplaceable_input_hands_over_to_the_sort_fold(fold_env):
 
 def test_pileup_hits_sorted_by_partition_equal_the_radix_sort(fold_env):
     """The pileup's (key, value) hits: row partition + one LDS sort per item (the default) against the library radix sort
-    (XCK_PILEUP_SORT=radix) and the oracle, at the default page size and at small ones, with both item sorts."""
+    (XCK_PILEUP_SORT=radix) and the oracle, at the default page size and at small ones."""
     regions, snps, names = soa.make_tables(120, 4000, [1500000], seed=51, max_len=150000)
     bs = soa.gen_reads(regions, names, 150000, 300, seed=52)
     batches = [util.batch_from_dict(b) for b in bs]
-    for k in ("XCK_FOLD", "XCK_FOLD_C", "XCK_FOLD_LGG", "XCK_PILEUP_SORT", "XCK_PILEUP_ITEM_SORT", "XCK_PILEUP_HAP"):
+    for k in ("XCK_FOLD", "XCK_FOLD_C", "XCK_FOLD_LGG", "XCK_PILEUP_SORT", "XCK_PILEUP_HAP"):
         fold_env.pop(k, None)
     got, exp, st = util.engine_vs_oracle(capi.XCK_MODE_BAF, names, regions, snps, 300, batches)
     util.assert_coo_equal(got, exp, ["ad", "dp", "oth"])
     assert st["pileup_sort_path"] == 1 and st["pileup_sort2_path"] == 1 and len(exp["dp"][0]) > 1000
-    for item_sort in ("radix", "bitonic"):              # the LDS radix sort of an item (default) and the bitonic network
-        fold_env["XCK_PILEUP_ITEM_SORT"] = item_sort
-        for page in ("1024", "64", "8"):
-            fold_env["XCK_FOLD_C"] = page
-            got, _, st = util.engine_vs_oracle(capi.XCK_MODE_BAF, names, regions, snps, 300, batches)
-            util.assert_coo_equal(got, exp, ["ad", "dp", "oth"])
-            assert st["pileup_sort_path"] in (1, 2)
-    fold_env.pop("XCK_PILEUP_ITEM_SORT")
+    for page in ("1024", "64", "8"):
+        fold_env["XCK_FOLD_C"] = page
+        got, _, st = util.engine_vs_oracle(capi.XCK_MODE_BAF, names, regions, snps, 300, batches)
+        util.assert_coo_equal(got, exp, ["ad", "dp", "oth"])
+        assert st["pileup_sort_path"] in (1, 2)
     # region-level items: "values" = the haplotype class in a value word beside the key (default: in two free bits of the UMI field);
     # "sorted" = items sorted completely + k_hap_class / k_hap_sum, instead of k_hap_items
     for hap, paths in (("values", (1, 2)), ("sorted", (3, 2))):

@@ -21,7 +21,7 @@ from xcltk_amd.synth import soa
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("XCK_FOLD", "XCK_FOLD_C", "XCK_FOLD_LGG", "XCK_FULL_SORT", "XCK_PILEUP_SORT", "XCK_PILEUP_ITEM_SORT", "XCK_PILEUP_HAP")
+KNOBS = ("XCK_FOLD", "XCK_FOLD_C", "XCK_FOLD_LGG", "XCK_FULL_SORT", "XCK_PILEUP_SORT", "XCK_PILEUP_HAP")
 KW = dict(min_mapq=20, min_len=30, incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1, min_maf=0, no_dup_hap=True)
 FC, BAF = capi.XCK_MODE_BASEFC, capi.XCK_MODE_BAF
 MATS = {FC: ["count"], BAF: ["ad", "dp", "oth"]}

@@ -47,7 +47,6 @@ Knobs xck::Knobs::from_env() {
     k.full_sort = num("XCK_FULL_SORT", 0) != 0;
     k.pileup_radix = !strcmp(str("XCK_PILEUP_SORT"), "radix");
     k.pileup_hap = !strcmp(str("XCK_PILEUP_HAP"), "sorted") ? 1 : !strcmp(str("XCK_PILEUP_HAP"), "values") ? 2 : 0;
-    k.pileup_bitonic = !strcmp(str("XCK_PILEUP_ITEM_SORT"), "bitonic");
     k.pileup_lgg = (int)num("XCK_PILEUP_LGG", 10);
     k.hit_slack = std::max(0ll, num("XCK_HIT_SLACK", 65536));
     k.hit_cap0 = std::max(64ll, num("XCK_HIT_CAP0", 1ll << 20));

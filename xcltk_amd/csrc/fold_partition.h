@@ -59,6 +59,19 @@ struct PartGeom {
     uint32_t n_cells;
     const uint32_t* rowtab;                            // per row: (first level-1 cell of the row << 5) | sg;  z = base + (cell >> sg)
 };
+// The words of `ctr`, the fold's device counters: written by the plan / item kernels and as scan totals, read on the host through
+// pf_read_counters().  CTR_NO_FIT: basefc = a level-2 sub-cell is above CAP (its big z is refined), pileup = a cell group is (PF_FALLBACK).
+enum PfCtr {
+    CTR_ITEMS = 0, CTR_BIG = 1,                        // work items (basefc: of level 1); big cells
+    CTR_CHUNKS2 = 2, CTR_BIGKEYS = 3,                  // level-2 chunks; keys in big cells (k_pf_plan1 adds: not reset between level-2 attempts)
+    CTR_ITEMS2 = 4, CTR_NO_FIT = 5,                    // level-2 work items; a cell does not fit a work item
+    CTR_NNZ = 6, CTR_ITEM_OVER = 7,                    // non-zeros of the matrix; an item came out above its capacity (internal error)
+    CTR_CELLS = 8, CTR_CELLS2 = 9,                     // level-1 cells Z; level-2 cells
+    CTR_DEEPEST = 10, CTR_NO_REFINE = 11,              // keys of the deepest level-2 sub-cell; a big z is at 2^16 sub-cells already and cannot be refined
+    CTR_N                                              // (one past the last name)
+};
+constexpr int CTR_PUBLISHED = 16, CTR_WORDS = 64;      // words k_pf_publish copies to the host; words allocated (and cleared) per fold
+static_assert(CTR_N <= CTR_PUBLISHED && CTR_PUBLISHED <= CTR_WORDS && CTR_NO_REFINE == CTR_DEEPEST + 1, "every counter is published; one memset clears CTR_DEEPEST and CTR_NO_REFINE");
 struct WorkItem { uint32_t off, span, aux, pad; };     // first key, (row, cell) >> sb of every key in it, level 1: big index / level 2: parent big z,
                                                        // level 2: (row, cell) & mask of the item's first sub-cell | PF_CONT
 constexpr uint32_t PF_CONT = 0x80000000u;              // WorkItem.pad: that (row, cell) already has keys in earlier items of the same big z
@@ -389,7 +402,7 @@ __global__ __launch_bounds__(PT_THREADS) __attribute__((amdgpu_waves_per_eu(6, 8
 // ---- work items --------------------------------------------------------------------------------------------------------
 // S = exclusive scan of the histogram, Z + 1 entries (S[Z] = number of keys).  Flags per cell z: fs = "starts a work item",
 // level 1 also fb = "big" (more than CAP keys: goes through level 2), fc = its number of level-2 chunks, fz = its sub-cells.
-// ctr: [3] += keys in big cells, [5] = 1 when some cell cannot be placed (PF_FALLBACK)
+// ctr (PfCtr): CTR_BIGKEYS += keys in big cells, CTR_NO_FIT = 1 when some cell does not fit a work item
 struct BigArrays { uint32_t* off; uint32_t* cnt; uint32_t* chunk0; uint32_t* wi; uint32_t* span; uint32_t* first2; uint32_t* z2base; uint32_t* sg; uint32_t* eb; uint32_t* rcl0; uint32_t* need; };
 // Level-2 geometry of a big z with c keys over `cells` existing cells (of the 2^sg the z spans; the last group of a row is only
 // partly filled).  depth = keys per cell if the cells were even.  Shallow cells: groups of 2^tb cells of about C / 2 keys; cells
@@ -418,19 +431,22 @@ __device__ __forceinline__ uint32_t pf_cells_in(uint32_t z, const PartGeom& g, c
     if (lo >= g.n_cells) return 1u;
     return (uint32_t)min((unsigned long long)g.n_cells - lo, 1ull << sg);
 }
+// The page rule: cell z (first key s, c keys; before it a cell with first key sp and cp keys) starts a work item when it is the first
+// cell, when its first key opens a new page of C keys, or when it or its predecessor holds more than C keys on its own.
+__device__ __forceinline__ bool pf_starts_item(uint32_t z, uint32_t s, uint32_t c, uint32_t sp, uint32_t cp, int lgC) { return z == 0 || (s >> lgC) != (sp >> lgC) || c > (1u << lgC) || cp > (1u << lgC); }
 __global__ void k_pf_plan1(const uint32_t* __restrict__ Sp, int pl, uint32_t Z, PartGeom g, const uint32_t* __restrict__ zrow,
                            uint32_t* __restrict__ fs, uint32_t* __restrict__ fb, uint32_t* __restrict__ fc, uint32_t* __restrict__ ctr) {
     const uint32_t z = blockIdx.x * blockDim.x + threadIdx.x;
     if (z > Z) return;
     if (z == Z) { fs[z] = 0; fb[z] = 0; fc[z] = 0; return; }                             // sentinel: the scans then end with the totals
-    const uint32_t C = 1u << g.lgC, CAP = 2u << g.lgC;
+    const uint32_t CAP = 2u << g.lgC;
     const uint32_t s = Sp[(size_t)z << pl], c = Sp[(size_t)(z + 1) << pl] - s, sp = z ? Sp[(size_t)(z - 1) << pl] : 0u, cp = z ? s - sp : 0u;
     int sg;
     const uint32_t span = pf_span1(z, g, zrow, &sg), spanp = z ? pf_span1(z - 1, g, zrow, nullptr) : 0u;
-    const bool start = z == 0 || (s >> g.lgC) != (sp >> g.lgC) || c > C || cp > C || span != spanp;
+    const bool start = pf_starts_item(z, s, c, sp, cp, g.lgC) || span != spanp;
     const bool big = c > CAP;
     fs[z] = start ? 1u : 0u; fb[z] = big ? 1u : 0u; fc[z] = big ? (c + PT_CHUNK - 1) / PT_CHUNK : 0u;
-    if (big) atomicAdd(&ctr[3], c);
+    if (big) atomicAdd(&ctr[CTR_BIGKEYS], c);
 }
 // id / bid / ch0 = exclusive scans of fs / fb / fc (Z + 1 entries each)
 __global__ void k_pf_emit1(const uint32_t* __restrict__ Sp, int pl, uint32_t Z, PartGeom g, const uint32_t* __restrict__ zrow, const uint32_t* __restrict__ id, const uint32_t* __restrict__ bid,
@@ -462,8 +478,8 @@ __device__ __forceinline__ uint32_t pf_big_of(const uint32_t* __restrict__ z2bas
 }
 // The geometry of a big z (pf_sub_geom) assumes its cells even.  Where they are not (well-based data: every cell has its own hot genes) a
 // sub-cell comes out above CAP: its big z then asks for single cells cut into enough UMI-hash parts for the case that ALL keys of the
-// sub-cell belong to one cell (big.need), and the host runs the level-2 histogram again (k_pf_big_refine; ctr[5] = 1).  A z that is
-// already at 2^16 sub-cells cannot be refined: ctr[11] = 1 -> PF_FALLBACK.
+// sub-cell belong to one cell (big.need), and the host runs the level-2 histogram again (k_pf_big_refine; CTR_NO_FIT).  A z that is
+// already at 2^16 sub-cells cannot be refined: CTR_NO_REFINE -> PF_FALLBACK.
 __global__ void k_pf_big_sub(uint32_t n_big, BigArrays big) {                            // big.z2base[b] := sub-cells of b (scanned next)
     const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b > n_big) return;
@@ -483,14 +499,14 @@ __global__ void k_pf_plan2(const uint32_t* __restrict__ S, uint32_t Z, PartGeom 
     const uint32_t C = 1u << g.lgC, CAP = 2u << g.lgC;
     const uint32_t s = S[z], c = S[z + 1] - s, sp = z ? S[z - 1] : 0u, cp = z ? s - sp : 0u;
     const bool first = z2base[pf_big_of(z2base, n_big, z)] == z;                          // first sub-cell of a big z
-    fs[z] = (z == 0 || first || (s >> g.lgC) != (sp >> g.lgC) || c > C || cp > C) ? 1u : 0u;
+    fs[z] = (first || pf_starts_item(z, s, c, sp, cp, g.lgC)) ? 1u : 0u;
     if (c > CAP) {                                                                    // a sub-cell the geometry could not bring under CAP
         const uint32_t b = pf_big_of(z2base, n_big, z);
         const int sg = (int)big.sg[b], eb = (int)(big.eb[b] & 31u), tb = (int)(big.eb[b] >> 5);
         int more = 1; while ((c >> more) > max(1u, C / 4)) more++;                      // parts that bring c under a quarter page
         const int eb_new = (tb ? 0 : eb) + more;
-        ctr[5] = 1u; atomicMax(&ctr[10], c);
-        if (sg + eb_new > 16) ctr[11] = 1u; else atomicMax(&big.need[b], (uint32_t)eb_new + 1u);
+        ctr[CTR_NO_FIT] = 1u; atomicMax(&ctr[CTR_DEEPEST], c);
+        if (sg + eb_new > 16) ctr[CTR_NO_REFINE] = 1u; else atomicMax(&big.need[b], (uint32_t)eb_new + 1u);
     }
 }
 __global__ void k_pf_emit2(const uint32_t* __restrict__ S, uint32_t Z, const uint32_t* __restrict__ id, uint32_t n_big, WorkItem* __restrict__ wi, BigArrays big) {
@@ -563,7 +579,7 @@ __global__ __launch_bounds__(PF_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
         const uint32_t off = cur.off, n = n_cur;
         if (cur.span & PF_BIG) { /* level 1: its keys went through level 2 (k_pf_bignnz fills nnz_out) */ }
         else if (n == 0 || n > (uint32_t)PF_CAP_MAX) {
-            if (tid == 0) { if (n) ctr[7] = 1u; nnz_out[item] = 0; if (cont_out) cont_out[item] = 0; }   // n > CAP cannot happen (k_pf_plan); never index out of the LDS arrays
+            if (tid == 0) { if (n) ctr[CTR_ITEM_OVER] = 1u; nnz_out[item] = 0; if (cont_out) cont_out[item] = 0; }   // n > CAP cannot happen (k_pf_plan); never index out of the LDS arrays
         } else {
             int lg_slots = 8; while ((1u << lg_slots) < 2 * n) lg_slots++;  // load <= 0.5; small items clear and probe a small table
             const uint32_t smask = (1u << lg_slots) - 1u;
@@ -681,227 +697,250 @@ __global__ void k_pf_publish(const uint32_t* __restrict__ src, unsigned long lon
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
+// (A failed launch leaves its error for the next hipGetLastError(): pf_scan() and pf_read_counters() check after their own launches and so
+// report the launches before them as well; a launch that neither follows within the stage gets a check of its own.)
 static int pf_scan(EngineImpl* im, uint32_t* data, size_t n, uint32_t* bsum, uint32_t* total_out) {       // in place, exclusive
     const size_t nb = (n + SC_TILE - 1) / SC_TILE;
     hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(SC_T), 0, im->s_comp, (const uint32_t*)data, n, bsum);
     hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, im->s_comp, bsum, nb, total_out);
     hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(SC_T), 0, im->s_comp, data, n, (const uint32_t*)bsum);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError()); return 0;
+}
+static inline size_t pf_scan_words(size_t n) { return (n + SC_TILE - 1) / SC_TILE + 8; }                   // words of `bsum` for a scan of n
+static inline int pf_bucket_lds(int sb) { return PF_SLOTS * 8 + (1 << sb) / 8; }
+// The counters on the host: publish them, wait for the stream; h[PfCtr] = their values.  h aliases the k_expand words of h_ctl (unused in
+// basefc mode, not yet in use when the pileup's sorts run).
+static int pf_read_counters(EngineImpl* im, const uint32_t* ctr, const unsigned long long*& h) {
+    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, ctr, im->d_hctl + CTL_X0, CTR_PUBLISHED);
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(im->s_comp));
+    h = im->h_ctl + CTL_X0; return 0;
+}
+// A workspace is carved by ONE function (its get<>() calls), which also yields its size: it runs on an arena without memory first, then
+// on the real one (begun with that many bytes when `begin`).  The first get of the measuring arena returns offset 0, i.e. null, and
+// Arena::get only ever moves `off` forward: success is `off <= cap` after the last get, not a chain of null checks.
+template <class F> static size_t pf_carved_bytes(F carve) { Arena m; m.cap = ~size_t(0); carve(m); return m.off; }
+template <class F> static int pf_carve(EngineImpl* im, Arena& ar, bool begin, F carve, const char* what) {
+    if (begin) if (const int rc = arena_begin(im, ar, pf_carved_bytes(carve))) return rc;
+    carve(ar);
+    if (ar.off > ar.cap) { im->eng->err = what; return XCK_E_NOMEM; }
     return 0;
 }
-static inline int pf_bucket_lds(int sb) { return PF_SLOTS * 8 + (1 << sb) / 8; }
 
-// basefc fold of the n keys in the shard slices of im->d_keys -> result matrix 0.  0 = done, PF_FALLBACK = take the radix path
-// (the shard slices are then untouched), < 0 = error.
-static int fold_partition(EngineImpl* im, KeyLayout<unsigned long long> kl, size_t n) {
+// ---- the front of both partitions: where the blocks find their keys, row geometry, level-1 histogram ---------------------------------
+// page size C = 2^lgC (XCK_FOLD_C, a test knob: small pages reach every path with small inputs)
+static int partition_sort_lgC(const EngineImpl* im) { int lgC = 0; const int c = im->eng->knobs.fold_c > 0 ? im->eng->knobs.fold_c : PF_C_MAX; while ((2 << lgC) <= c && (2 << lgC) <= PF_C_MAX) lgC++; return lgC; }
+// sc: the 16 slices as the level-1 blocks see them (n_blocks1 blocks: segment b of every slice); scs: as the row sample does (one piece of
+// 64 keys in `stride`, >= 16 M keys; a block covers PT_CHUNK * stride stream keys)
+constexpr uint32_t PF_STRIDE_MAX = 16;
+struct PartFront { ShardChunks sc, scs; uint32_t stride; unsigned n_blocks1; int lgC; };
+static PartFront pf_front(const EngineImpl* im, size_t cap, const unsigned long long* cnt) {
+    PartFront f; f.lgC = partition_sort_lgC(im); f.sc.cap = cap; f.sc.chunk0[0] = 0; size_t max_cnt = 0;
+    for (int sh = 0; sh < NSHARD; sh++) { f.sc.cnt[sh] = (uint32_t)cnt[sh]; f.sc.chunk0[sh + 1] = f.sc.chunk0[sh] + (uint32_t)((cnt[sh] + PT_CHUNK - 1) / PT_CHUNK); max_cnt = std::max<size_t>(max_cnt, cnt[sh]); }
+    f.n_blocks1 = (unsigned)((max_cnt + PT_THREADS - 1) / PT_THREADS);
+    f.stride = (uint32_t)std::min<size_t>(PF_STRIDE_MAX, std::max<size_t>(1, f.sc.chunk0[NSHARD] / 4096));
+    f.scs = f.sc;                                                                          // (the same slices in blocks of PT_CHUNK * stride keys)
+    for (int sh = 0; sh < NSHARD; sh++) f.scs.chunk0[sh + 1] = f.scs.chunk0[sh] + (uint32_t)((cnt[sh] + (size_t)PT_CHUNK * f.stride - 1) / ((size_t)PT_CHUNK * f.stride));
+    return f;
+}
+// bound on the level-1 cells, the sum of 2^l over the rows (k_pf_rowplan): 2^lg_min per row + 4 per page of keys
+static size_t pf_cells_bound(size_t n_rows, int lg_min, size_t n, uint32_t stride, int lgC) { return (n_rows << lg_min) + 4 * ((n + (size_t)NSHARD * stride * PT_CHUNK) >> lgC) + 64; }
+// What differs between the two callers of pf_level1_hist(), and the buffers it works on (from the caller's workspace function)
+struct Level1 {
+    int lg_min, lg_max, pl;                            // 2^lg_min .. 2^lg_max cell groups per row; 2^pl copies of the level-1 counters / cursors
+    size_t z_cap; const char* over;                    // bound on the cells (the caller has held it against ITS limit before asking for memory), error text beyond it
+    uint32_t *rowcnt, *zb, *rowtab, *S, *zrow, *bsum, *ctr;    // rows + 1 each; (z_cap << pl) + 1; z_cap + 1, or null: not wanted; scan scratch; CTR_WORDS
+};
+static const BigChunks PF_NO_BIG{};                    // (what the level-1 launches pass for the level-2 chunks)
+// keys -> g.rowtab, L.S = exclusive scan of the keys per (cell, copy), *Z = level-1 cells.  Clears the counters.
+static int pf_level1_hist(EngineImpl* im, const PartFront& f, const Level1& L, const unsigned long long* keys, uint32_t n_rows, PartGeom& g, uint32_t* Z) {
+    int rc; const unsigned long long* h;
+    const size_t rs = (size_t)n_rows + 1; const unsigned gr = (unsigned)((rs + 255) / 256);
+    g.rowtab = L.rowtab;
+    HIP_TRY(hipMemsetAsync(L.rowcnt, 0, rs * 4, im->s_comp)); HIP_TRY(hipMemsetAsync(L.ctr, 0, CTR_WORDS * 4, im->s_comp));
+    hipLaunchKernelGGL(k_pf_rowhist, dim3(f.scs.chunk0[NSHARD]), dim3(PT_THREADS), 0, im->s_comp, keys, f.scs, f.stride, g.ubits + g.cbits, L.rowcnt);
+    hipLaunchKernelGGL(k_pf_rowplan, dim3(gr), dim3(256), 0, im->s_comp, L.rowcnt, n_rows, f.stride, L.lg_min, L.lg_max, f.lgC, L.zb);
+    if ((rc = pf_scan(im, L.zb, rs, L.bsum, L.ctr + CTR_CELLS)) || (rc = pf_read_counters(im, L.ctr, h))) return rc;
+    *Z = (uint32_t)h[CTR_CELLS]; if ((size_t)*Z > L.z_cap) { im->eng->err = L.over; return XCK_E_STATE; }
+    hipLaunchKernelGGL(k_pf_rowtab, dim3(gr), dim3(256), 0, im->s_comp, L.zb, n_rows, g.cbits, L.rowtab, L.zrow);
+    const size_t ss = ((size_t)*Z << L.pl) + 1;
+    HIP_TRY(hipMemsetAsync(L.S, 0, ss * 4, im->s_comp));
+    hipLaunchKernelGGL((k_pf_hist<1>), dim3(f.n_blocks1), dim3(PT_THREADS), 0, im->s_comp, keys, f.sc, PF_NO_BIG, g, L.pl, L.S);
+    return pf_scan(im, L.S, ss, L.bsum, nullptr);
+}
+
+// ---- the basefc fold: four stages that hand a PartFold on ----------------------------------------------------------------------------
+struct PartFold {
     typedef unsigned long long K;
-    if (n >= (size_t(1) << 32) - (size_t(1) << 20)) return PF_FALLBACK;                   // 32-bit offsets
-    int lgC = 0;
-    { const int c = im->eng->knobs.fold_c > 0 ? im->eng->knobs.fold_c : PF_C_MAX; while ((2 << lgC) <= c && (2 << lgC) <= PF_C_MAX) lgC++; }   // (test knob: small pages reach every path with small inputs)
-    PartGeom g; g.ubits = kl.ubits; g.cbits = kl.cbits; g.lgC = lgC; g.n_cells = (uint32_t)im->n_cells;
-    g.sb = std::min(PF_SB_MAX, std::max(kl.cbits, 11));                                    // 14 cell bits: one row per span, a 2 KB bitmap
-    const int lg_min = std::max(0, kl.cbits - g.sb);                                      // a level-1 cell never straddles two spans
-    // at most 2^6 cell groups per row: more groups keep more keys out of level 2 but leave the level-1 kernels more (block, cell) pairs -
-    // atomics, short runs (A/B on one box at configs[2]: 8 -> 9.6 ms, 7 -> 8.9, 6 -> 8.7, 5 -> 8.9; profiles/r03_x_fold_variants_ab.log)
-    // with at most 512 cells (well-based data: one BAM per cell) a row may get one group per cell: the cells of such data are far from
-    // even (every cell has its own hot genes), and a level-1 cell that IS one (row, cell) knows its depth exactly
-    const int lg_max = std::max(lg_min, std::min((im->eng->knobs.fold_lgg >= 0 ? im->eng->knobs.fold_lgg : kl.cbits <= 9 ? kl.cbits : 6), kl.cbits));
-    const uint32_t n_rows = (uint32_t)im->n_regions;
-    ShardChunks sc; sc.cap = im->hit_cap; sc.chunk0[0] = 0;
-    for (int sh = 0; sh < NSHARD; sh++) { sc.cnt[sh] = (uint32_t)im->cur[sh]; sc.chunk0[sh + 1] = sc.chunk0[sh] + (uint32_t)((im->cur[sh] + PT_CHUNK - 1) / PT_CHUNK); }
-    const unsigned n_chunks1 = sc.chunk0[NSHARD];
-    size_t max_cur = 0; for (int sh = 0; sh < NSHARD; sh++) max_cur = std::max<size_t>(max_cur, im->cur[sh]);
-    const unsigned n_blocks1 = (unsigned)((max_cur + PT_THREADS - 1) / PT_THREADS);       // level-1 blocks: segment b of every slice
-    const uint32_t stride = (uint32_t)std::min<size_t>(16, std::max<size_t>(1, n_chunks1 / 4096));          // the row sample: one piece of 64 keys in `stride`, >= 16 M keys
-    ShardChunks scs = sc;                                                                  // its blocks: PT_CHUNK * stride stream keys each
-    for (int sh = 0; sh < NSHARD; sh++) scs.chunk0[sh + 1] = scs.chunk0[sh] + (uint32_t)((im->cur[sh] + (size_t)PT_CHUNK * stride - 1) / ((size_t)PT_CHUNK * stride));
-    const unsigned n_sample = scs.chunk0[NSHARD];
-    const size_t z_cap = ((size_t)n_rows << lg_min) + 4 * ((n + (size_t)NSHARD * stride * PT_CHUNK) >> lgC) + 64;   // sum of 2^l over the rows (k_pf_rowplan)
-    if (z_cap > (size_t(1) << 24)) { if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: level-1 cell bound %zu\n", z_cap); return PF_FALLBACK; }
-    const size_t zs_cap = z_cap + 1, rs = (size_t)n_rows + 1;
-    const size_t sb1 = (std::max(zs_cap, rs) + SC_TILE - 1) / SC_TILE + 8;
-    int rc;
-    // ---- workspace 1: level-1 output, row geometry, histogram / flags over the cells
-    const int pl = std::max(0, std::min(im->eng->knobs.fold_copies_lg, 6));            // 2^pl copies of the level-1 counters / cursors
-    const size_t ss_cap = (z_cap << pl) + 1;
-    const size_t sbs = (ss_cap + SC_TILE - 1) / SC_TILE + 8;
-    if ((rc = arena_begin(im, im->ws1, n * sizeof(K) + 3 * (rs * 4 + 256) + 5 * (zs_cap * 4 + 256) + ss_cap * 4 + (sb1 + sbs) * 4 + 64 * 4 + (1 << 16)))) return rc;
-    K* A = im->ws1.get<K>(n);
-    uint32_t* rowcnt = im->ws1.get<uint32_t>(rs); uint32_t* zb = im->ws1.get<uint32_t>(rs); uint32_t* rowtab = im->ws1.get<uint32_t>(rs);
-    uint32_t* S1 = im->ws1.get<uint32_t>(ss_cap); uint32_t* fs = im->ws1.get<uint32_t>(zs_cap); uint32_t* fb = im->ws1.get<uint32_t>(zs_cap);
-    uint32_t* fc = im->ws1.get<uint32_t>(zs_cap); uint32_t* zrow = im->ws1.get<uint32_t>(zs_cap);
-    uint32_t* bsum = im->ws1.get<uint32_t>(sb1 + sbs); uint32_t* ctr = im->ws1.get<uint32_t>(64);
-    if (!A || !rowcnt || !zb || !rowtab || !S1 || !fs || !fb || !fc || !zrow || !bsum || !ctr) { im->eng->err = "workspace exhausted (partition fold)"; return XCK_E_NOMEM; }
-    g.rowtab = rowtab;
-    unsigned long long* h_ctr = im->h_ctl + CTL_X0; unsigned long long* d_hctr = im->d_hctl + CTL_X0;   // (the k_expand words: unused in basefc mode)
-    BigChunks bc0; memset(&bc0, 0, sizeof bc0);
-    const unsigned gr = (unsigned)((rs + 255) / 256);
-    // ---- row geometry from a sample of the stream
-    HIP_TRY(hipMemsetAsync(rowcnt, 0, rs * 4, im->s_comp));
-    HIP_TRY(hipMemsetAsync(ctr, 0, 64 * 4, im->s_comp));
-    hipLaunchKernelGGL(k_pf_rowhist, dim3(n_sample), dim3(PT_THREADS), 0, im->s_comp, (const K*)im->d_keys, scs, stride, kl.ubits + kl.cbits, rowcnt);
-    hipLaunchKernelGGL(k_pf_rowplan, dim3(gr), dim3(256), 0, im->s_comp, (const uint32_t*)rowcnt, n_rows, stride, lg_min, lg_max, lgC, zb);
-    HIP_TRY(hipGetLastError());
-    if ((rc = pf_scan(im, zb, rs, bsum, ctr + 8))) return rc;                              // ctr[8] = level-1 cells
-    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    const uint32_t Z = (uint32_t)h_ctr[8];
-    if ((size_t)Z > z_cap) { im->eng->err = "internal: level-1 cells exceed their bound"; return XCK_E_STATE; }
-    const size_t zs = (size_t)Z + 1;
-    const unsigned gz = (unsigned)((zs + 255) / 256);
-    hipLaunchKernelGGL(k_pf_rowtab, dim3(gr), dim3(256), 0, im->s_comp, (const uint32_t*)zb, n_rows, kl.cbits, rowtab, zrow);
-    // ---- level 1: histogram over the cells, work items
-    const size_t ss = ((size_t)Z << pl) + 1;
-    HIP_TRY(hipMemsetAsync(S1, 0, ss * 4, im->s_comp));
-    hipLaunchKernelGGL((k_pf_hist<1>), dim3(n_blocks1), dim3(PT_THREADS), 0, im->s_comp, (const K*)im->d_keys, sc, bc0, g, pl, S1);
-    HIP_TRY(hipGetLastError());
-    if ((rc = pf_scan(im, S1, ss, bsum, nullptr))) return rc;
-    hipLaunchKernelGGL(k_pf_plan1, dim3(gz), dim3(256), 0, im->s_comp, (const uint32_t*)S1, pl, Z, g, (const uint32_t*)zrow, fs, fb, fc, ctr);
-    HIP_TRY(hipGetLastError());
-    if ((rc = pf_scan(im, fs, zs, bsum, ctr + 0))) return rc;                              // ctr[0] = level-1 work items
-    if ((rc = pf_scan(im, fb, zs, bsum, ctr + 1))) return rc;                              // ctr[1] = big cells
-    if ((rc = pf_scan(im, fc, zs, bsum, ctr + 2))) return rc;                              // ctr[2] = level-2 chunks
-    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    const size_t n_wi1 = h_ctr[0], n_big = h_ctr[1], n_chunks2 = h_ctr[2], n_bigkeys = h_ctr[3];
+    KeyLayout<K> kl; size_t n; uint32_t n_rows; PartGeom g; PartFront f;
+    K* A; Level1 l1; uint32_t *fs, *fb, *fc;                               // workspace 1 (pf_carve1): level-1 output, row geometry, histogram / flags over the cells
+    uint32_t Z; size_t n_wi1, n_big, n_chunks2, n_bigkeys;                 // pf_level1: cells, work items, big cells, their level-2 chunks and keys
+    size_t z2_cap, wi2_cap, coo_at;                                        // workspace 2 (pf_carve2), sized by those counts: room for level-2 cells / work items, place of the COO block
+    WorkItem *wi1, *wi2; uint32_t *nnz1, *res1, *S2, *fs2, *nnz2, *cont2, *res2, *bsum2; BigArrays big;
+    bool side;                                                             // pf_level1: the level-1 bucket pass is on the copy stream, which reads workspace 2
+    BigChunks bc; size_t Z2, n_wi2, total;                                 // pf_plan_level2: level-2 cells and work items; pf_bucket_passes: non-zeros
+};
+static void pf_carve1(Arena& ar, PartFold& pf) {
+    Level1& L = pf.l1; const size_t rs = (size_t)pf.n_rows + 1, zs_cap = L.z_cap + 1, ss_cap = (L.z_cap << L.pl) + 1;
+    pf.A = ar.get<PartFold::K>(pf.n);
+    L.rowcnt = ar.get<uint32_t>(rs); L.zb = ar.get<uint32_t>(rs); L.rowtab = ar.get<uint32_t>(rs);
+    L.S = ar.get<uint32_t>(ss_cap); pf.fs = ar.get<uint32_t>(zs_cap); pf.fb = ar.get<uint32_t>(zs_cap); pf.fc = ar.get<uint32_t>(zs_cap); L.zrow = ar.get<uint32_t>(zs_cap);
+    L.bsum = ar.get<uint32_t>(pf_scan_words(std::max(zs_cap, rs)) + pf_scan_words(ss_cap)); L.ctr = ar.get<uint32_t>(CTR_WORDS);
+}
+static void pf_carve2(Arena& ar, PartFold& pf) {
+    const size_t n_wi1 = pf.n_wi1, n_big = pf.n_big, big_pages = pf.n_bigkeys >> pf.g.lgC;
     // level-2 cells: about 4 per page of big keys; room for 16x that (refined geometries of uneven cells), beyond it the radix fold
-    const size_t z2_cap = std::min<size_t>(size_t(1) << 26, 64 * (n_bigkeys >> lgC) + 64 * n_big + 65536);
-    const size_t zs2 = z2_cap + 1;
-    const size_t wi2_cap = n_big + 3 * (n_bigkeys >> lgC) + 8;
-    const size_t sb2 = (std::max(std::max(zs2, wi2_cap + 1), n_wi1 + 1) + SC_TILE - 1) / SC_TILE + 8;
-    // ---- workspace 2: everything whose size is known now
-    if ((rc = arena_begin(im, im->ws2, (n_wi1 + 1) * (sizeof(WorkItem) + 4) + (n_big + 2) * 4 * 12 + n * 4 + 2 * (zs2 * 4 + 256) + (wi2_cap + 1) * (sizeof(WorkItem) + 8)
-                                       + n_bigkeys * 4 + sb2 * 4 + n * 12 + (1 << 16)))) return rc;
-    WorkItem* wi1 = im->ws2.get<WorkItem>(n_wi1 + 1); uint32_t* nnz1 = im->ws2.get<uint32_t>(n_wi1 + 1);
-    BigArrays big; big.off = im->ws2.get<uint32_t>(n_big + 2); big.cnt = im->ws2.get<uint32_t>(n_big + 2); big.chunk0 = im->ws2.get<uint32_t>(n_big + 2);
-    big.wi = im->ws2.get<uint32_t>(n_big + 2); big.span = im->ws2.get<uint32_t>(n_big + 2); big.first2 = im->ws2.get<uint32_t>(n_big + 2);
-    big.z2base = im->ws2.get<uint32_t>(n_big + 2); big.sg = im->ws2.get<uint32_t>(n_big + 2); big.eb = im->ws2.get<uint32_t>(n_big + 2); big.rcl0 = im->ws2.get<uint32_t>(n_big + 2); big.need = im->ws2.get<uint32_t>(n_big + 2);
-    uint32_t* res1 = im->ws2.get<uint32_t>(n);
-    uint32_t* S2 = im->ws2.get<uint32_t>(zs2); uint32_t* fs2 = im->ws2.get<uint32_t>(zs2);
-    WorkItem* wi2 = im->ws2.get<WorkItem>(wi2_cap + 1); uint32_t* nnz2 = im->ws2.get<uint32_t>(wi2_cap + 1); uint32_t* cont2 = im->ws2.get<uint32_t>(wi2_cap + 1);
-    uint32_t* res2 = im->ws2.get<uint32_t>(n_bigkeys); uint32_t* bsum2 = im->ws2.get<uint32_t>(sb2);
-    if (!wi1 || !nnz1 || !big.need || !res1 || !S2 || !fs2 || !wi2 || !nnz2 || !cont2 || !res2 || !bsum2) { im->eng->err = "workspace exhausted (partition fold, stage 2)"; return XCK_E_NOMEM; }
-    hipLaunchKernelGGL(k_pf_emit1, dim3(gz), dim3(256), 0, im->s_comp, (const uint32_t*)S1, pl, Z, g, (const uint32_t*)zrow, (const uint32_t*)fs, (const uint32_t*)fb, (const uint32_t*)fc,
-                       wi1, big);
+    pf.z2_cap = std::min<size_t>(size_t(1) << 26, 64 * big_pages + 64 * n_big + 65536); pf.wi2_cap = n_big + 3 * big_pages + 8;
+    pf.wi1 = ar.get<WorkItem>(n_wi1 + 1); pf.nnz1 = ar.get<uint32_t>(n_wi1 + 1);
+    BigArrays& b = pf.big; for (uint32_t** p : { &b.off, &b.cnt, &b.chunk0, &b.wi, &b.span, &b.first2, &b.z2base, &b.sg, &b.eb, &b.rcl0, &b.need }) *p = ar.get<uint32_t>(n_big + 2);
+    pf.res1 = ar.get<uint32_t>(pf.n);
+    pf.S2 = ar.get<uint32_t>(pf.z2_cap + 1); pf.fs2 = ar.get<uint32_t>(pf.z2_cap + 1);
+    pf.wi2 = ar.get<WorkItem>(pf.wi2_cap + 1); pf.nnz2 = ar.get<uint32_t>(pf.wi2_cap + 1); pf.cont2 = ar.get<uint32_t>(pf.wi2_cap + 1);
+    pf.res2 = ar.get<uint32_t>(pf.n_bigkeys); pf.bsum2 = ar.get<uint32_t>(pf_scan_words(std::max(std::max(pf.z2_cap, pf.wi2_cap), n_wi1) + 1));
+    pf.coo_at = ar.off; ar.get<int32_t>(pf.n * 3);                         // upper bound of the COO block: total * 3 words, total <= n
+}
+// one bucket pass, at most `grid` persistent blocks: over the level-1 items (keys in A) or the level-2 items (keys in the shard slices)
+static void pf_bucket(EngineImpl* im, const PartFold& pf, int level, hipStream_t stream, size_t grid) {
+    const bool l2 = level == 2; const size_t n_items = l2 ? pf.n_wi2 : pf.n_wi1;
+    hipLaunchKernelGGL(k_pf_bucket, dim3((unsigned)std::min(n_items, grid)), dim3(PF_THREADS), pf_bucket_lds(pf.g.sb), stream, l2 ? (const PartFold::K*)im->d_keys : pf.A, l2 ? pf.wi2 : pf.wi1,
+                       (uint32_t)n_items, pf.kl.ubits, pf.g.sb, l2 ? pf.res2 : pf.res1, l2 ? pf.nnz2 : pf.nnz1, l2 ? pf.cont2 : nullptr, pf.l1.ctr);
+}
+
+// stage 1: row geometry, level-1 histogram, its work items and the big cells counted; the keys to their level-1 cells (A), and the bucket
+// pass over the level-1 items started beside what follows
+static int pf_level1(EngineImpl* im, PartFold& pf) {
+    int rc; const unsigned long long* h; const KeyLayout<PartFold::K>& kl = pf.kl; PartGeom& g = pf.g; Level1& L = pf.l1;
+    pf.f = pf_front(im, im->hit_cap, im->cur); pf.n_rows = (uint32_t)im->n_regions;
+    g.ubits = kl.ubits; g.cbits = kl.cbits; g.lgC = pf.f.lgC; g.n_cells = (uint32_t)im->n_cells;
+    g.sb = std::min(PF_SB_MAX, std::max(kl.cbits, 11));                                    // 14 cell bits: one row per span, a 2 KB bitmap
+    L.lg_min = std::max(0, kl.cbits - g.sb);                                              // a level-1 cell never straddles two spans
+    // at most 2^6 cell groups per row: more keep more keys out of level 2 but leave the level-1 kernels more (block, cell) pairs - atomics, short
+    // runs (A/B at configs[2]: 8 -> 9.6 ms, 7 -> 8.9, 6 -> 8.7, 5 -> 8.9; profiles/r03_x_fold_variants_ab.log); with at most 512 cells (well-based
+    // data, whose cells are far from even) one group per cell: a level-1 cell that IS one (row, cell) knows its depth exactly.  DESIGN.md 3.2
+    L.lg_max = std::max(L.lg_min, std::min((im->eng->knobs.fold_lgg >= 0 ? im->eng->knobs.fold_lgg : kl.cbits <= 9 ? kl.cbits : 6), kl.cbits));
+    L.pl = std::max(0, std::min(im->eng->knobs.fold_copies_lg, 6));
+    L.z_cap = pf_cells_bound(pf.n_rows, L.lg_min, pf.n, pf.f.stride, g.lgC); L.over = "internal: level-1 cells exceed their bound";
+    if (L.z_cap > (size_t(1) << 24)) { if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: level-1 cell bound %zu\n", L.z_cap); return PF_FALLBACK; }
+    if ((rc = pf_carve(im, im->ws1, true, [&](Arena& ar) { pf_carve1(ar, pf); }, "workspace exhausted (partition fold)"))) return rc;
+    if ((rc = pf_level1_hist(im, pf.f, L, (const PartFold::K*)im->d_keys, pf.n_rows, g, &pf.Z))) return rc;
+    const size_t zs = (size_t)pf.Z + 1;
+    hipLaunchKernelGGL(k_pf_plan1, dim3((unsigned)((zs + 255) / 256)), dim3(256), 0, im->s_comp, L.S, L.pl, pf.Z, g, L.zrow, pf.fs, pf.fb, pf.fc, L.ctr);
+    if ((rc = pf_scan(im, pf.fs, zs, L.bsum, L.ctr + CTR_ITEMS)) || (rc = pf_scan(im, pf.fb, zs, L.bsum, L.ctr + CTR_BIG)) || (rc = pf_scan(im, pf.fc, zs, L.bsum, L.ctr + CTR_CHUNKS2))) return rc;
+    if ((rc = pf_read_counters(im, L.ctr, h))) return rc;
+    pf.n_wi1 = h[CTR_ITEMS]; pf.n_big = h[CTR_BIG]; pf.n_chunks2 = h[CTR_CHUNKS2]; pf.n_bigkeys = h[CTR_BIGKEYS];
+    if ((rc = pf_carve(im, im->ws2, true, [&](Arena& ar) { pf_carve2(ar, pf); }, "workspace exhausted (partition fold, stage 2)"))) return rc;
+    im->ws2.off = pf.coo_at;
+    hipLaunchKernelGGL(k_pf_emit1, dim3((unsigned)(((size_t)pf.Z + 1 + 255) / 256)), dim3(256), 0, im->s_comp, L.S, L.pl, pf.Z, pf.g, L.zrow, pf.fs, pf.fb, pf.fc, pf.wi1, pf.big);
+    hipLaunchKernelGGL((k_pf_part<1>), dim3(pf.f.n_blocks1), dim3(PT_THREADS), 0, im->s_comp, (const PartFold::K*)im->d_keys, pf.f.sc, PF_NO_BIG, pf.g, L.pl, L.S, pf.A);   // (S is the cursor array from here on)
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((k_pf_part<1>), dim3(n_blocks1), dim3(PT_THREADS), 0, im->s_comp, (const K*)im->d_keys, sc, bc0, g, pl, S1, A);   // (S1 is the cursor array from here on)
-    HIP_TRY(hipGetLastError());
-    const int lds = pf_bucket_lds(g.sb);
-    const size_t bucket_grid = (size_t)std::max(1, im->eng->knobs.fold_bucket_blocks);     // resident blocks (4 per CU by LDS) x 2: the tail evens out
-    size_t n_wi2 = 0;
-    K* B = (K*)im->d_keys;                                                                 // level-2 output: the shard slices are dead once level 1 has moved the keys
     // The level-1 items do not depend on level 2: their bucket pass runs on the copy stream (idle until the copy-out) beside the
     // level-2 histogram / partition - two latency-bound kernels share the CUs better than either fills them (XCK_FOLD_OVERLAP=0: serial).
-    const bool overlap = n_big && im->eng->knobs.fold_overlap != 0;
-    if (overlap) {
-        if (!im->ev_f1) { HIP_TRY(hipEventCreateWithFlags(&im->ev_f1, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&im->ev_f2, hipEventDisableTiming)); }
-        HIP_TRY(hipEventRecord(im->ev_f1, im->s_comp));
-        HIP_TRY(hipStreamWaitEvent(im->s_copy, im->ev_f1, 0));
-        // (half of the CUs' wave slots - 2 blocks of 8 waves per CU: a persistent grid that fills the device would leave the level-2
-        // kernels waiting for a slot until it retires)
-        const size_t side_grid = (size_t)std::max(1, im->eng->knobs.fold_overlap_blocks);
-        hipLaunchKernelGGL(k_pf_bucket, dim3((unsigned)std::min<size_t>(n_wi1, side_grid)), dim3(PF_THREADS), lds, im->s_copy, (const K*)A, (const WorkItem*)wi1, (uint32_t)n_wi1, kl.ubits, g.sb, res1, nnz1, (uint32_t*)nullptr, ctr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(im->ev_f2, im->s_copy));
+    if (!pf.n_big || im->eng->knobs.fold_overlap == 0) return 0;
+    if (!im->ev_f1) { HIP_TRY(hipEventCreateWithFlags(&im->ev_f1, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&im->ev_f2, hipEventDisableTiming)); }
+    HIP_TRY(hipEventRecord(im->ev_f1, im->s_comp)); HIP_TRY(hipStreamWaitEvent(im->s_copy, im->ev_f1, 0));
+    pf.side = true;
+    // (half of the CUs' wave slots - 2 blocks of 8 waves per CU: a persistent grid that fills the device would leave the level-2
+    // kernels waiting for a slot until it retires)
+    pf_bucket(im, pf, 1, im->s_copy, (size_t)std::max(1, im->eng->knobs.fold_overlap_blocks));
+    HIP_TRY(hipGetLastError()); HIP_TRY(hipEventRecord(im->ev_f2, im->s_copy));
+    return 0;
+}
+// stage 2: the sub-cells of the big cells and their work items counted, with a finer geometry where a sub-cell comes out above a work
+// item.  Writes to workspace 2 only: on PF_FALLBACK the shard slices still hold the keys.
+static int pf_plan_level2(EngineImpl* im, PartFold& pf) {
+    if (!pf.n_big) return 0;                                                               // (Z2 = n_wi2 = 0)
+    int rc; const unsigned long long* h; const size_t n_big = pf.n_big; BigArrays& big = pf.big; uint32_t* ctr = pf.l1.ctr;
+    BigChunks& bc = pf.bc; bc.off = big.off; bc.cnt = big.cnt; bc.chunk0 = big.chunk0; bc.z2base = big.z2base; bc.sg = big.sg; bc.eb = big.eb; bc.n_big = (uint32_t)n_big;
+    const unsigned gb = (unsigned)((n_big + 1 + 255) / 256);
+    im->fold_refinements = 0;
+    for (int attempt = 0;; attempt++) {
+        // sub-cells of every big z from its geometry -> first level-2 cell of every big z
+        hipLaunchKernelGGL(k_pf_big_sub, dim3(gb), dim3(256), 0, im->s_comp, (uint32_t)n_big, big);
+        if ((rc = pf_scan(im, big.z2base, n_big + 1, pf.bsum2, ctr + CTR_CELLS2)) || (rc = pf_read_counters(im, ctr, h))) return rc;
+        pf.Z2 = h[CTR_CELLS2];
+        if (pf.Z2 > pf.z2_cap) { if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: %zu level-2 cells (room for %zu)\n", pf.Z2, pf.z2_cap); return PF_FALLBACK; }
+        const size_t zs2 = pf.Z2 + 1;
+        HIP_TRY(hipMemsetAsync(pf.S2, 0, zs2 * 4, im->s_comp));
+        HIP_TRY(hipMemsetAsync(ctr + CTR_NO_FIT, 0, 4, im->s_comp)); HIP_TRY(hipMemsetAsync(ctr + CTR_DEEPEST, 0, 8, im->s_comp));   // (CTR_DEEPEST and CTR_NO_REFINE)
+        hipLaunchKernelGGL((k_pf_hist<2>), dim3((unsigned)pf.n_chunks2), dim3(PT_THREADS), 0, im->s_comp, pf.A, pf.f.sc, bc, pf.g, 0, pf.S2);
+        if ((rc = pf_scan(im, pf.S2, zs2, pf.bsum2, nullptr))) return rc;
+        hipLaunchKernelGGL(k_pf_plan2, dim3((unsigned)((zs2 + 255) / 256)), dim3(256), 0, im->s_comp, pf.S2, (uint32_t)pf.Z2, pf.g, big, (uint32_t)n_big, pf.fs2, ctr);
+        if ((rc = pf_scan(im, pf.fs2, zs2, pf.bsum2, ctr + CTR_ITEMS2)) || (rc = pf_read_counters(im, ctr, h))) return rc;
+        if (!h[CTR_NO_FIT]) break;
+        const bool give_up = h[CTR_NO_REFINE] || attempt >= 3;
+        if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: a level-2 sub-cell holds %llu keys (more than %d) - %s (n=%zu cells=%u big=%zu, %zu keys, %zu sub-cells)\n",
+                                                h[CTR_DEEPEST], 2 << pf.g.lgC, give_up ? "radix fold" : "finer geometry for its big cell", pf.n, pf.Z, n_big, pf.n_bigkeys, pf.Z2);
+        if (give_up) return PF_FALLBACK;
+        im->fold_refinements++;
+        hipLaunchKernelGGL(k_pf_big_refine, dim3(gb), dim3(256), 0, im->s_comp, (uint32_t)n_big, big);
     }
-    size_t Z2 = 0;
+    pf.n_wi2 = h[CTR_ITEMS2];
+    if (pf.n_wi2 > pf.wi2_cap) { im->eng->err = "internal: level-2 work items exceed their bound"; return XCK_E_STATE; }
+    return 0;
+}
+// stage 3: the keys of the big cells to their sub-cells (into the shard slices: dead once level 1 has moved the keys), the bucket pass
+// over the level-2 items, the level-1 bucket pass joined (or run here), the non-zeros counted
+static int pf_bucket_passes(EngineImpl* im, PartFold& pf) {
+    int rc; const unsigned long long* h; const size_t n_big = pf.n_big, n_wi1 = pf.n_wi1, n_wi2 = pf.n_wi2;
+    const size_t bucket_grid = (size_t)std::max(1, im->eng->knobs.fold_bucket_blocks);     // resident blocks (4 per CU by LDS) x 2: the tail evens out
     if (n_big) {
-        BigChunks bc; bc.off = big.off; bc.cnt = big.cnt; bc.chunk0 = big.chunk0; bc.z2base = big.z2base; bc.sg = big.sg; bc.eb = big.eb; bc.n_big = (uint32_t)n_big;
-        const unsigned gb = (unsigned)((n_big + 1 + 255) / 256);
-        im->fold_refinements = 0;
-        for (int attempt = 0;; attempt++) {
-            // sub-cells of every big z from its geometry -> first level-2 cell of every big z
-            hipLaunchKernelGGL(k_pf_big_sub, dim3(gb), dim3(256), 0, im->s_comp, (uint32_t)n_big, big);
-            if ((rc = pf_scan(im, big.z2base, n_big + 1, bsum2, ctr + 9))) return rc;       // ctr[9] = level-2 cells
-            hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(im->s_comp));
-            Z2 = h_ctr[9];
-            if (Z2 > z2_cap) { if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: %zu level-2 cells (room for %zu)\n", Z2, z2_cap);
-                               if (overlap) HIP_TRY(hipStreamSynchronize(im->s_copy));      // (the level-1 bucket pass still reads this workspace)
-                               return PF_FALLBACK; }
-            const size_t zs2n = Z2 + 1;
-            const unsigned gz2 = (unsigned)((zs2n + 255) / 256);
-            HIP_TRY(hipMemsetAsync(S2, 0, zs2n * 4, im->s_comp));
-            HIP_TRY(hipMemsetAsync(ctr + 5, 0, 4, im->s_comp)); HIP_TRY(hipMemsetAsync(ctr + 10, 0, 8, im->s_comp));
-            hipLaunchKernelGGL((k_pf_hist<2>), dim3((unsigned)n_chunks2), dim3(PT_THREADS), 0, im->s_comp, (const K*)A, sc, bc, g, 0, S2);
-            HIP_TRY(hipGetLastError());
-            if ((rc = pf_scan(im, S2, zs2n, bsum2, nullptr))) return rc;
-            hipLaunchKernelGGL(k_pf_plan2, dim3(gz2), dim3(256), 0, im->s_comp, (const uint32_t*)S2, (uint32_t)Z2, g, big, (uint32_t)n_big, fs2, ctr);
-            HIP_TRY(hipGetLastError());
-            if ((rc = pf_scan(im, fs2, zs2n, bsum2, ctr + 4))) return rc;                   // ctr[4] = level-2 work items
-            hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(im->s_comp));
-            if (!h_ctr[5]) break;
-            // (the shard slices still hold the keys: level 2 has not written yet)
-            if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: a level-2 sub-cell holds %llu keys (more than %d) - %s (n=%zu cells=%u big=%zu, %zu keys, %zu sub-cells)\n",
-                                                    h_ctr[10], 2 << lgC, h_ctr[11] || attempt >= 3 ? "radix fold" : "finer geometry for its big cell", n, Z, n_big, n_bigkeys, Z2);
-            if (h_ctr[11] || attempt >= 3) { if (overlap) HIP_TRY(hipStreamSynchronize(im->s_copy)); return PF_FALLBACK; }
-            im->fold_refinements++;
-            hipLaunchKernelGGL(k_pf_big_refine, dim3(gb), dim3(256), 0, im->s_comp, (uint32_t)n_big, big);
-            HIP_TRY(hipGetLastError());
-        }
-        const unsigned gz2 = (unsigned)((Z2 + 1 + 255) / 256);
-        n_wi2 = h_ctr[4];
-        if (n_wi2 > wi2_cap) { im->eng->err = "internal: level-2 work items exceed their bound"; return XCK_E_STATE; }
-        hipLaunchKernelGGL(k_pf_emit2, dim3(gz2), dim3(256), 0, im->s_comp, (const uint32_t*)S2, (uint32_t)Z2, (const uint32_t*)fs2, (uint32_t)n_big, wi2, big);
-        hipLaunchKernelGGL((k_pf_part<2>), dim3((unsigned)n_chunks2), dim3(PT_THREADS), 0, im->s_comp, (const K*)A, sc, bc, g, 0, S2, B);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_pf_bucket, dim3((unsigned)std::min<size_t>(n_wi2, bucket_grid)), dim3(PF_THREADS), lds, im->s_comp, (const K*)B, (const WorkItem*)wi2, (uint32_t)n_wi2, kl.ubits, g.sb, res2, nnz2, cont2, ctr);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(nnz2 + n_wi2, 0, 4, im->s_comp));
-        if ((rc = pf_scan(im, nnz2, n_wi2 + 1, bsum2, nullptr))) return rc;                // nnz2 -> O2
-        hipLaunchKernelGGL(k_pf_bignnz, dim3((unsigned)((n_big + 255) / 256)), dim3(256), 0, im->s_comp, (uint32_t)n_big, big, (const uint32_t*)nnz2, nnz1);
-        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_pf_emit2, dim3((unsigned)((pf.Z2 + 1 + 255) / 256)), dim3(256), 0, im->s_comp, pf.S2, (uint32_t)pf.Z2, pf.fs2, (uint32_t)n_big, pf.wi2, pf.big);
+        hipLaunchKernelGGL((k_pf_part<2>), dim3((unsigned)pf.n_chunks2), dim3(PT_THREADS), 0, im->s_comp, pf.A, pf.f.sc, pf.bc, pf.g, 0, pf.S2, (PartFold::K*)im->d_keys);
+        pf_bucket(im, pf, 2, im->s_comp, bucket_grid);
+        HIP_TRY(hipMemsetAsync(pf.nnz2 + n_wi2, 0, 4, im->s_comp));
+        if ((rc = pf_scan(im, pf.nnz2, n_wi2 + 1, pf.bsum2, nullptr))) return rc;          // nnz2 -> O2
+        hipLaunchKernelGGL(k_pf_bignnz, dim3((unsigned)((n_big + 255) / 256)), dim3(256), 0, im->s_comp, (uint32_t)n_big, pf.big, pf.nnz2, pf.nnz1);
     }
-    if (overlap) HIP_TRY(hipStreamWaitEvent(im->s_comp, im->ev_f2, 0));
-    else {
-        hipLaunchKernelGGL(k_pf_bucket, dim3((unsigned)std::min<size_t>(n_wi1, bucket_grid)), dim3(PF_THREADS), lds, im->s_comp, (const K*)A, (const WorkItem*)wi1, (uint32_t)n_wi1, kl.ubits, g.sb, res1, nnz1, (uint32_t*)nullptr, ctr);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemsetAsync(nnz1 + n_wi1, 0, 4, im->s_comp));
-    if ((rc = pf_scan(im, nnz1, n_wi1 + 1, bsum2, ctr + 6))) return rc;                    // nnz1 -> O1, ctr[6] = non-zeros of the matrix
-    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    if (h_ctr[7]) { im->eng->err = "internal: a work item of the partition fold exceeds its capacity"; return XCK_E_STATE; }
-    const size_t total = h_ctr[6];
+    if (pf.side) HIP_TRY(hipStreamWaitEvent(im->s_comp, im->ev_f2, 0));
+    else pf_bucket(im, pf, 1, im->s_comp, bucket_grid);
+    HIP_TRY(hipMemsetAsync(pf.nnz1 + n_wi1, 0, 4, im->s_comp));
+    if ((rc = pf_scan(im, pf.nnz1, n_wi1 + 1, pf.bsum2, pf.l1.ctr + CTR_NNZ)) || (rc = pf_read_counters(im, pf.l1.ctr, h))) return rc;   // nnz1 -> O1
+    pf.side = false;                                                                       // (the main stream has waited for it)
+    if (h[CTR_ITEM_OVER]) { im->eng->err = "internal: a work item of the partition fold exceeds its capacity"; return XCK_E_STATE; }
+    pf.total = h[CTR_NNZ];
     if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] partition fold: n=%zu rows=%u cells=%u (sample stride %u) items=%zu big=%zu (%zu keys, %zu sub-cells, %zu items) nnz=%zu C=%d sb=%d\n",
-                                            n, n_rows, Z, stride, n_wi1, n_big, n_bigkeys, Z2, n_wi2, total, 1 << lgC, g.sb);
-    im->res_nnz[0] = total; im->d_res[0] = nullptr;
-    if (!total) return 0;
-    if ((rc = res_reserve(im, 0, total))) return rc;
+                                            pf.n, pf.n_rows, pf.Z, pf.f.stride, n_wi1, n_big, pf.n_bigkeys, pf.Z2, n_wi2, pf.total, 1 << pf.g.lgC, pf.g.sb);
+    return 0;
+}
+// stage 4: the per-item results -> COO [row | col | val] -> result matrix 0
+static int pf_write(EngineImpl* im, PartFold& pf) {
+    const size_t total = pf.total, n_wi2 = pf.n_wi2;
+    im->res_nnz[0] = total; im->d_res[0] = nullptr; if (!total) return 0;
+    if (const int rc = res_reserve(im, 0, total)) return rc;
     int32_t* d_o = im->ws2.get<int32_t>(total * 3);
     if (!d_o) { im->eng->err = "workspace exhausted (COO)"; return XCK_E_NOMEM; }
     if (n_wi2) HIP_TRY(hipMemsetAsync(d_o + 2 * total, 0, total * sizeof(int32_t), im->s_comp));      // level-2 counts are added
-    hipLaunchKernelGGL((k_pf_write<1>), dim3((unsigned)n_wi1), dim3(128), 0, im->s_comp, (const WorkItem*)wi1, (const uint32_t*)res1, (const uint32_t*)nnz1, (const uint32_t*)nnz2, (const uint32_t*)nullptr, big,
-                       kl.cbits, g.sb, (unsigned long long)total, d_o);
-    if (n_wi2) hipLaunchKernelGGL((k_pf_write<2>), dim3((unsigned)n_wi2), dim3(128), 0, im->s_comp, (const WorkItem*)wi2, (const uint32_t*)res2, (const uint32_t*)nnz1, (const uint32_t*)nnz2, (const uint32_t*)cont2, big,
-                                  kl.cbits, g.sb, (unsigned long long)total, d_o);
+    hipLaunchKernelGGL((k_pf_write<1>), dim3((unsigned)pf.n_wi1), dim3(128), 0, im->s_comp, pf.wi1, pf.res1, pf.nnz1, pf.nnz2, nullptr, pf.big, pf.kl.cbits, pf.g.sb, (unsigned long long)total, d_o);
+    if (n_wi2) hipLaunchKernelGGL((k_pf_write<2>), dim3((unsigned)n_wi2), dim3(128), 0, im->s_comp, pf.wi2, pf.res2, pf.nnz1, pf.nnz2, pf.cont2, pf.big, pf.kl.cbits, pf.g.sb, (unsigned long long)total, d_o);
     HIP_TRY(hipGetLastError());
     return copy_out(im, 0, d_o, total);
 }
 
+// basefc fold of the n keys in the shard slices of im->d_keys -> result matrix 0.  0 = done, PF_FALLBACK = take the radix path
+// (the shard slices are then untouched: level 2 writes into them only after pf_plan_level2 has passed), < 0 = error.
+static int fold_partition(EngineImpl* im, KeyLayout<unsigned long long> kl, size_t n) {
+    if (n >= (size_t(1) << 32) - (size_t(1) << 20)) return PF_FALLBACK;                   // 32-bit offsets
+    PartFold pf{}; pf.kl = kl; pf.n = n;
+    int rc = pf_level1(im, pf);
+    if (!rc && !(rc = pf_plan_level2(im, pf))) rc = pf_bucket_passes(im, pf);
+    if (rc && pf.side) HIP_TRY(hipStreamSynchronize(im->s_copy));                          // (the level-1 bucket pass may still read workspace 2)
+    return rc ? rc : pf_write(im, pf);
+}
 
 // ---- pileup: the (key, value) hits sorted WITHOUT a radix sort -------------------------------------------------------------------
 // The hits with a base leave k_join<pileup> in position order and a key's top field is the SNP's index in position order: the
 // stream is almost sorted by row already.  The radix sort took 8 passes over the 25 M pairs of configs[2] (4.0 of the pileup
 // fold's 11 ms); here the pairs are partitioned by row (one pass, the kernels above with z = row) into items of whole SNPs of at
-// most 2C pairs, and every item is sorted in LDS (k_pf_radix_items below; the bitonic network k_pf_sort_items was the first form and
-// stays selectable).  A (SNP, cell group) deeper than an item (UMI-less deep pileups) returns PF_FALLBACK: the radix sort handles it.  Reference semantics: first read per (SNP, cell, UMI) in fetch order,
+// most 2C pairs, and every item is sorted in LDS (k_pf_radix_items below).  A (SNP, cell group) deeper than an item (UMI-less deep pileups) returns PF_FALLBACK: the radix sort handles it.  Reference semantics: first read per (SNP, cell, UMI) in fetch order,
 // xcltk/baf/fc/mcount.py:109-127 - the order inside a key run is irrelevant to what follows (k_first_base takes the minimum).
-constexpr int PS_CAP = PF_CAP_MAX, PS_THREADS = 256;
+constexpr int PS_CAP = PF_CAP_MAX;
 __global__ void k_pf_plan0(const uint32_t* __restrict__ S, uint32_t Z, int lgC, uint32_t* __restrict__ fs, uint32_t* __restrict__ ctr) {
     const uint32_t z = blockIdx.x * blockDim.x + threadIdx.x;
     if (z > Z) return;
     if (z == Z) { fs[z] = 0; return; }
-    const uint32_t C = 1u << lgC, CAP = 2u << lgC;
+    const uint32_t CAP = 2u << lgC;
     const uint32_t s = S[z], c = S[z + 1] - s, sp = z ? S[z - 1] : 0u, cp = z ? s - sp : 0u;
-    fs[z] = (z == 0 || (s >> lgC) != (sp >> lgC) || c > C || cp > C) ? 1u : 0u;
-    if (c > CAP) ctr[5] = 1u;
+    fs[z] = pf_starts_item(z, s, c, sp, cp, lgC) ? 1u : 0u;
+    if (c > CAP) ctr[CTR_NO_FIT] = 1u;
 }
 __global__ void k_pf_emit0(const uint32_t* __restrict__ S, uint32_t Z, const uint32_t* __restrict__ id, uint32_t* __restrict__ item_off) {
     const uint32_t z = blockIdx.x * blockDim.x + threadIdx.x;
@@ -909,50 +948,13 @@ __global__ void k_pf_emit0(const uint32_t* __restrict__ S, uint32_t Z, const uin
     if (z == 0) item_off[id[Z]] = S[Z];
     if (id[z + 1] != id[z]) item_off[id[z]] = S[z];
 }
-__global__ __launch_bounds__(PS_THREADS) void k_pf_sort_items(unsigned long long* __restrict__ keys, uint64_t* __restrict__ vals, const uint32_t* __restrict__ item_off, uint32_t* __restrict__ ctr) {
-    // Bitonic network on (key, value) in LDS.  Every wave owns a quarter of the array: the stages whose partner distance stays inside
-    // a quarter are run by that wave alone, in lock step, without block barriers (63 of the 66 stages of a 2048-pair item); only
-    // the three stages that pair elements of different quarters meet at a barrier.  (A barrier per stage: 67 us per item, 1.9 ms
-    // for the 29 k items of configs[2].)
-    __shared__ unsigned long long sk[PS_CAP];
-    __shared__ unsigned long long sv[PS_CAP];
-    const uint32_t off = item_off[blockIdx.x], n = item_off[blockIdx.x + 1] - off;
-    if (n < 2) return;
-    if (n > (uint32_t)PS_CAP) { if (threadIdx.x == 0) ctr[7] = 1u; return; }
-    uint32_t N2 = 2; while (N2 < n) N2 <<= 1;
-    for (uint32_t i = threadIdx.x; i < N2; i += PS_THREADS) { sk[i] = i < n ? keys[off + i] : ~0ull; sv[i] = i < n ? vals[off + i] : ~0ull; }
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t SEG = max(N2 / (PS_THREADS / 64), 128u);                // elements of a wave's segment (a power of two, >= 2 per lane)
-    const bool wave_on = wave * SEG < N2;
-    auto cmpx = [&](uint32_t p, uint32_t j, uint32_t k) {                 // pair number p of stage (k, j)
-        const uint32_t i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), x = i | j;
-        const unsigned long long ka = sk[i], kb = sk[x], va = sv[i], vb = sv[x];
-        const bool gt = ka > kb || (ka == kb && va > vb);
-        if (gt == ((i & k) == 0)) { sk[i] = kb; sk[x] = ka; sv[i] = vb; sv[x] = va; }
-    };
-    __syncthreads();
-    for (uint32_t k = 2; k <= N2; k <<= 1)
-        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-            if (j >= SEG) {                                               // partners in different segments: the whole block, between barriers
-                __syncthreads();
-                for (uint32_t p = threadIdx.x; p < N2 / 2; p += PS_THREADS) cmpx(p, j, k);
-                __syncthreads();
-            } else {
-                if (wave_on) for (uint32_t p = lane; p < min(SEG, N2) / 2; p += 64) cmpx(wave * (SEG / 2) + p, j, k);
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's exchanges have landed before its next stage reads
-            }
-        }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n; i += PS_THREADS) { keys[off + i] = sk[i]; vals[off + i] = sv[i]; }
-}
 
-// The same items sorted by an LSD radix sort in LDS (default; XCK_PILEUP_ITEM_SORT=bitonic keeps the network above).  512 threads, four
+// The items sorted by an LSD radix sort in LDS.  512 threads, four
 // pairs per thread held in REGISTERS between the passes; element e = wave * 256 + round * 64 + lane.  One pass per 8-bit window of key
 // bits in which the item's keys differ at all (4 windows where an item is one hot SNP, ~6 where it is many cold ones): every wave ranks its 256 elements round by
 // round with ballots (lanes of equal digit: eight ballots; rank = the wave's running count of the digit + lanes of the group below me),
 // the 8 x 256 wave counts are scanned digit-major, and the pairs go through ONE LDS buffer to their new places and back into
-// registers.  Stable, so equal keys keep their order and the padding (~0 keys) stays behind.  ~0.5 MB of LDS traffic per item
-// against the network's 4.3 MB.
+// registers.  Stable, so equal keys keep their order and the padding (~0 keys) stays behind.  ~0.5 MB of LDS traffic per item.
 constexpr int RS_THREADS = 512, RS_WAVES = RS_THREADS / 64, RS_EPT = PS_CAP / RS_THREADS, RS_SEG = PS_CAP / RS_WAVES;
 static_assert(RS_EPT * RS_THREADS == PS_CAP && RS_SEG == RS_EPT * 64, "item capacity = threads x elements per thread");
 struct RsShared {
@@ -1038,7 +1040,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_pf_radix_items(unsigned long lon
     __shared__ RsShared sm;
     const uint32_t off = item_off[blockIdx.x], n = item_off[blockIdx.x + 1] - off;
     if (n < 2) return;
-    if (n > (uint32_t)PS_CAP) { if (threadIdx.x == 0) ctr[7] = 1u; return; }
+    if (n > (uint32_t)PS_CAP) { if (threadIdx.x == 0) ctr[CTR_ITEM_OVER] = 1u; return; }
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, e0 = wave * RS_SEG + lane;
     const int n_rounds = (int)min((uint32_t)RS_EPT, wave * RS_SEG >= n ? 0u : (n - wave * RS_SEG + 63) / 64);   // rounds of this wave that hold anything (wave-uniform)
     unsigned long long key[RS_EPT], val[RS_EPT];
@@ -1079,7 +1081,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_hap_items(const unsigned long lo
     __shared__ uint32_t s_wheads[RS_WAVES];
     const uint32_t off = item_off[blockIdx.x], n = item_off[blockIdx.x + 1] - off;
     if (n == 0) return;
-    if (n > (uint32_t)PS_CAP) { if (threadIdx.x == 0) ctr[7] = 1u; return; }
+    if (n > (uint32_t)PS_CAP) { if (threadIdx.x == 0) ctr[CTR_ITEM_OVER] = 1u; return; }
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63, e0 = wave * RS_SEG + lane;
     const int n_rounds = (int)min((uint32_t)RS_EPT, wave * RS_SEG >= n ? 0u : (n - wave * RS_SEG + 63) / 64);
     unsigned long long key[RS_EPT], val[RS_EPT];
@@ -1169,91 +1171,46 @@ __global__ __launch_bounds__(RS_THREADS) void k_hap_items(const unsigned long lo
 // thousands of reads deep); the groups of a row are in cell order, so cell order = key order.  0 = done, PF_FALLBACK = use the radix
 // sort (the source slices are untouched either way), < 0 = error.  Scratch: `ar`, begun here when `own_arena`, else reserved by the
 // caller (partition_sort_scratch()).  With `hap` the items are not sorted: k_hap_items classifies them in place (region-level hits).
-struct PartSortSizes { size_t rs, z_cap, zs_cap, wi_cap, sb, bytes; };
-static PartSortSizes partition_sort_sizes(size_t n, size_t n_rows, int lgC) {
-    PartSortSizes q;
-    q.rs = n_rows + 1;
-    q.z_cap = n_rows + 4 * ((n + (size_t)NSHARD * 16 * PT_CHUNK) >> lgC) + 64;      // (16 = the largest sampling stride of the row histogram)
-    q.zs_cap = q.z_cap + 1; q.wi_cap = 3 * (n >> lgC) + 8;
-    q.sb = (std::max(std::max(q.zs_cap, q.rs), q.wi_cap + 1) + SC_TILE - 1) / SC_TILE + 8;
-    q.bytes = 3 * (q.rs * 4 + 256) + 2 * (q.zs_cap * 4 + 256) + (q.wi_cap + 1) * 4 + q.sb * 4 + 64 * 4 + (1 << 16);
-    return q;
+struct PartSortWs { Level1 l1; uint32_t *fs, *item_off; size_t wi_cap; };
+static void partition_sort_carve(Arena& ar, size_t n, size_t n_rows, int lgC, PartSortWs& w) {
+    Level1& L = w.l1; const size_t rs = n_rows + 1;
+    L.z_cap = pf_cells_bound(n_rows, 0, n, PF_STRIDE_MAX, lgC); w.wi_cap = 3 * (n >> lgC) + 8;      // (the scratch is sized before the slices are counted: the largest stride)
+    L.rowcnt = ar.get<uint32_t>(rs); L.zb = ar.get<uint32_t>(rs); L.rowtab = ar.get<uint32_t>(rs);
+    L.S = ar.get<uint32_t>(L.z_cap + 1); w.fs = ar.get<uint32_t>(L.z_cap + 1); w.item_off = ar.get<uint32_t>(w.wi_cap + 1);
+    L.bsum = ar.get<uint32_t>(pf_scan_words(std::max(std::max(L.z_cap + 1, rs), w.wi_cap + 1))); L.ctr = ar.get<uint32_t>(CTR_WORDS); L.zrow = nullptr;
 }
-static int partition_sort_lgC(const EngineImpl* im) { int lgC = 0; const int c = im->eng->knobs.fold_c > 0 ? im->eng->knobs.fold_c : PF_C_MAX; while ((2 << lgC) <= c && (2 << lgC) <= PF_C_MAX) lgC++; return lgC; }
-static size_t partition_sort_scratch(const EngineImpl* im, size_t n, size_t n_rows) { return partition_sort_sizes(n, n_rows, partition_sort_lgC(im)).bytes; }
+static size_t partition_sort_scratch(const EngineImpl* im, size_t n, size_t n_rows) {     // (+ 256: the caller's arena need not stand at a multiple of 256)
+    PartSortWs w; return pf_carved_bytes([&](Arena& ar) { partition_sort_carve(ar, n, n_rows, partition_sort_lgC(im), w); }) + 256;
+}
 static int pileup_partition_sort(EngineImpl* im, Arena& ar, bool own_arena, KeyLayout<unsigned long long> kl, const unsigned long long* src_keys, const uint64_t* src_vals,
                                  size_t src_cap, const unsigned long long* src_cnt, uint32_t n_rows, size_t n, unsigned long long* out_keys, uint64_t* out_vals,
                                  const HapItemsOut* hap = nullptr, PartIndex* index = nullptr) {
-    typedef unsigned long long K;
     if (n >= (size_t(1) << 32) - (size_t(1) << 20)) return PF_FALLBACK;
-    const int lgC = partition_sort_lgC(im);
-    PartGeom g; memset(&g, 0, sizeof g); g.ubits = kl.ubits; g.cbits = kl.cbits; g.lgC = lgC; g.sb = PF_SB_MAX; g.n_cells = (uint32_t)im->n_cells;
+    const PartFront f = pf_front(im, src_cap, src_cnt);
+    PartGeom g; memset(&g, 0, sizeof g); g.ubits = kl.ubits; g.cbits = kl.cbits; g.lgC = f.lgC; g.sb = PF_SB_MAX; g.n_cells = (uint32_t)im->n_cells;
+    PartSortWs w; Level1& L = w.l1; int rc; uint32_t Z; const unsigned long long* h;
     // (there is no second level here: a SNP of a hot gene - 100 k hits at configs[2] - must come apart in the first one, so up to 2^10 groups per SNP)
-    const int lg_max = std::max(0, std::min(im->eng->knobs.pileup_lgg, kl.cbits));
-    ShardChunks sc; sc.cap = src_cap; sc.chunk0[0] = 0;
-    for (int sh = 0; sh < NSHARD; sh++) { sc.cnt[sh] = (uint32_t)src_cnt[sh]; sc.chunk0[sh + 1] = sc.chunk0[sh] + (uint32_t)((src_cnt[sh] + PT_CHUNK - 1) / PT_CHUNK); }
-    const unsigned n_chunks = sc.chunk0[NSHARD];
-    size_t max_cur = 0; for (int sh = 0; sh < NSHARD; sh++) max_cur = std::max<size_t>(max_cur, src_cnt[sh]);
-    const unsigned n_blocks1 = (unsigned)((max_cur + PT_THREADS - 1) / PT_THREADS);
-    const uint32_t stride = (uint32_t)std::min<size_t>(16, std::max<size_t>(1, n_chunks / 4096));
-    ShardChunks scs = sc;
-    for (int sh = 0; sh < NSHARD; sh++) scs.chunk0[sh + 1] = scs.chunk0[sh] + (uint32_t)((src_cnt[sh] + (size_t)PT_CHUNK * stride - 1) / ((size_t)PT_CHUNK * stride));
-    BigChunks bc0; memset(&bc0, 0, sizeof bc0);
-    const PartSortSizes q = partition_sort_sizes(n, n_rows, lgC);
-    const size_t rs = q.rs, z_cap = q.z_cap, zs_cap = q.zs_cap, wi_cap = q.wi_cap, sb = q.sb;
-    if (z_cap > (size_t(1) << 26)) return PF_FALLBACK;
-    int rc;
-    if (own_arena && (rc = arena_begin(im, ar, q.bytes))) return rc;
-    uint32_t* rowcnt = ar.get<uint32_t>(rs); uint32_t* zb = ar.get<uint32_t>(rs); uint32_t* rowtab = ar.get<uint32_t>(rs);
-    uint32_t* S = ar.get<uint32_t>(zs_cap); uint32_t* fs = ar.get<uint32_t>(zs_cap); uint32_t* item_off = ar.get<uint32_t>(wi_cap + 1);
-    uint32_t* bsum = ar.get<uint32_t>(sb); uint32_t* ctr = ar.get<uint32_t>(64);
-    if (!rowcnt || !zb || !rowtab || !S || !fs || !item_off || !bsum || !ctr) { im->eng->err = "workspace exhausted (pileup partition)"; return XCK_E_NOMEM; }
-    g.rowtab = rowtab;
-    unsigned long long* h_ctr = im->h_ctl + CTL_X0; unsigned long long* d_hctr = im->d_hctl + CTL_X0;   // (the k_expand words: not in use yet)
-    const unsigned gr = (unsigned)((rs + 255) / 256);
-    HIP_TRY(hipMemsetAsync(rowcnt, 0, rs * 4, im->s_comp));
-    HIP_TRY(hipMemsetAsync(ctr, 0, 64 * 4, im->s_comp));
-    hipLaunchKernelGGL(k_pf_rowhist, dim3(scs.chunk0[NSHARD]), dim3(PT_THREADS), 0, im->s_comp, (const K*)src_keys, scs, stride, kl.ubits + kl.cbits, rowcnt);
-    hipLaunchKernelGGL(k_pf_rowplan, dim3(gr), dim3(256), 0, im->s_comp, (const uint32_t*)rowcnt, n_rows, stride, 0, lg_max, lgC, zb);
-    HIP_TRY(hipGetLastError());
-    if ((rc = pf_scan(im, zb, rs, bsum, ctr + 8))) return rc;
-    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    const uint32_t Z = (uint32_t)h_ctr[8];
-    if ((size_t)Z > z_cap) { im->eng->err = "internal: pileup cells exceed their bound"; return XCK_E_STATE; }
-    const size_t zs = (size_t)Z + 1;
-    const unsigned gz = (unsigned)((zs + 255) / 256);
-    hipLaunchKernelGGL(k_pf_rowtab, dim3(gr), dim3(256), 0, im->s_comp, (const uint32_t*)zb, n_rows, kl.cbits, rowtab, (uint32_t*)nullptr);
-    HIP_TRY(hipMemsetAsync(S, 0, zs * 4, im->s_comp));
-    hipLaunchKernelGGL((k_pf_hist<1>), dim3(n_blocks1), dim3(PT_THREADS), 0, im->s_comp, (const K*)src_keys, sc, bc0, g, 0, S);
-    HIP_TRY(hipGetLastError());
-    if ((rc = pf_scan(im, S, zs, bsum, nullptr))) return rc;
-    hipLaunchKernelGGL(k_pf_plan0, dim3(gz), dim3(256), 0, im->s_comp, (const uint32_t*)S, Z, lgC, fs, ctr);
-    HIP_TRY(hipGetLastError());
-    if ((rc = pf_scan(im, fs, zs, bsum, ctr + 0))) return rc;
-    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    if (h_ctr[5]) {                                                                       // a (SNP, cell group) with more hits than an item holds
+    L.lg_min = 0; L.lg_max = std::max(0, std::min(im->eng->knobs.pileup_lgg, kl.cbits)); L.pl = 0; L.over = "internal: pileup cells exceed their bound";
+    if (pf_cells_bound(n_rows, 0, n, PF_STRIDE_MAX, f.lgC) > (size_t(1) << 26)) return PF_FALLBACK;
+    if ((rc = pf_carve(im, ar, own_arena, [&](Arena& a) { partition_sort_carve(a, n, n_rows, f.lgC, w); }, "workspace exhausted (pileup partition)"))) return rc;
+    uint32_t* const S = L.S; uint32_t* const ctr = L.ctr;
+    if ((rc = pf_level1_hist(im, f, L, src_keys, n_rows, g, &Z))) return rc;
+    const size_t zs = (size_t)Z + 1; const unsigned gz = (unsigned)((zs + 255) / 256);
+    hipLaunchKernelGGL(k_pf_plan0, dim3(gz), dim3(256), 0, im->s_comp, S, Z, f.lgC, w.fs, ctr);
+    if ((rc = pf_scan(im, w.fs, zs, L.bsum, ctr + CTR_ITEMS)) || (rc = pf_read_counters(im, ctr, h))) return rc;
+    if (h[CTR_NO_FIT]) {                                                                  // a (SNP, cell group) with more hits than an item holds
         if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] pileup partition sort: a cell group exceeds an item (n=%zu cells=%u): radix sort\n", n, Z);
         return PF_FALLBACK;
     }
-    const size_t n_items = h_ctr[0];
-    if (n_items > wi_cap) { im->eng->err = "internal: pileup items exceed their bound"; return XCK_E_STATE; }
-    hipLaunchKernelGGL(k_pf_emit0, dim3(gz), dim3(256), 0, im->s_comp, (const uint32_t*)S, Z, (const uint32_t*)fs, item_off);
-    hipLaunchKernelGGL((k_pf_part<1>), dim3(n_blocks1), dim3(PT_THREADS), 0, im->s_comp, (const K*)src_keys, sc, bc0, g, 0, S, out_keys, src_vals, out_vals);
-    const bool bitonic = im->eng->knobs.pileup_bitonic;
-    if (hap && hap->pack_shift >= 0) hipLaunchKernelGGL((k_hap_items<true>), dim3((unsigned)n_items), dim3(RS_THREADS), 0, im->s_comp, (const unsigned long long*)out_keys, (const uint64_t*)nullptr, (const uint32_t*)item_off, kl.ubits, *hap, ctr);
-    else if (hap) hipLaunchKernelGGL((k_hap_items<false>), dim3((unsigned)n_items), dim3(RS_THREADS), 0, im->s_comp, (const unsigned long long*)out_keys, (const uint64_t*)out_vals, (const uint32_t*)item_off, kl.ubits, *hap, ctr);
-    else if (bitonic) hipLaunchKernelGGL(k_pf_sort_items, dim3((unsigned)n_items), dim3(PS_THREADS), 0, im->s_comp, out_keys, out_vals, (const uint32_t*)item_off, ctr);
-    else hipLaunchKernelGGL(k_pf_radix_items, dim3((unsigned)n_items), dim3(RS_THREADS), 0, im->s_comp, out_keys, out_vals, (const uint32_t*)item_off, ctr);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_pf_publish, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)ctr, d_hctr, 16);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    if (h_ctr[7]) { im->eng->err = "internal: a pileup item exceeds its capacity"; return XCK_E_STATE; }
-    if (index) { index->rowtab = rowtab; index->end = S; }
-    if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] pileup partition sort: n=%zu snps=%u cells=%u items=%zu C=%d\n", n, n_rows, Z, n_items, 1 << lgC);
+    const size_t n_items = h[CTR_ITEMS]; if (n_items > w.wi_cap) { im->eng->err = "internal: pileup items exceed their bound"; return XCK_E_STATE; }
+    hipLaunchKernelGGL(k_pf_emit0, dim3(gz), dim3(256), 0, im->s_comp, S, Z, w.fs, w.item_off);
+    hipLaunchKernelGGL((k_pf_part<1>), dim3(f.n_blocks1), dim3(PT_THREADS), 0, im->s_comp, src_keys, f.sc, PF_NO_BIG, g, 0, S, out_keys, src_vals, out_vals);
+    if (hap && hap->pack_shift >= 0) hipLaunchKernelGGL((k_hap_items<true>), dim3((unsigned)n_items), dim3(RS_THREADS), 0, im->s_comp, out_keys, nullptr, w.item_off, kl.ubits, *hap, ctr);
+    else if (hap) hipLaunchKernelGGL((k_hap_items<false>), dim3((unsigned)n_items), dim3(RS_THREADS), 0, im->s_comp, out_keys, out_vals, w.item_off, kl.ubits, *hap, ctr);
+    else hipLaunchKernelGGL(k_pf_radix_items, dim3((unsigned)n_items), dim3(RS_THREADS), 0, im->s_comp, out_keys, out_vals, w.item_off, ctr);
+    if ((rc = pf_read_counters(im, ctr, h))) return rc;
+    if (h[CTR_ITEM_OVER]) { im->eng->err = "internal: a pileup item exceeds its capacity"; return XCK_E_STATE; }
+    if (index) { index->rowtab = L.rowtab; index->end = S; }                              // (k_pf_part<1> has turned S into end offsets)
+    if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] pileup partition sort: n=%zu snps=%u cells=%u items=%zu C=%d\n", n, n_rows, Z, n_items, 1 << f.lgC);
     return 0;
 }

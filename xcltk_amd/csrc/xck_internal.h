@@ -101,7 +101,6 @@ struct Knobs {
     bool full_sort = false;              // XCK_FULL_SORT
     bool pileup_radix = false;           // XCK_PILEUP_SORT=radix
     int  pileup_hap = 0;                 // XCK_PILEUP_HAP: 0 = packed class bits, 1 = sorted, 2 = values
-    bool pileup_bitonic = false;         // XCK_PILEUP_ITEM_SORT=bitonic
     int  pileup_lgg = 10;                // XCK_PILEUP_LGG
     long long hit_slack = 65536;         // XCK_HIT_SLACK
     long long hit_cap0 = 1 << 20;        // XCK_HIT_CAP0
