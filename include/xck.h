@@ -54,6 +54,15 @@
  *                                         XCK_F_FEATURE_SUMMARY (xck_get_feature_summary): the front-ends then write feature_summary.tsv and, for the
  *                                         pileup, snp_summary.tsv next to their matrices.  One kernel more per join launch; does not imply XCK_READ_FATE.
  *                                         Off (the default, or 0) nothing is allocated or launched.  Decode-only handles ignore it.
+ *   XCK_DEVICE_PHASING=1                  (read by the Python front-ends, not by a handle) region-wise local phasing before the allele-specific counting runs
+ *                                         on the device (xck_local_phase below; xcltk_amd/baf/fc/phasing_dev.py) instead of the float64 host loop
+ *                                         of baf/fc/phasing.py, which stays the default and the specification.  Covers afc_wrapper, afc_variants and the
+ *                                         one-pass `xcltk baf`.  With no usable device the front-end says so in its log and runs the host loop.
+ *   XCK_PHASE_WCAP=<snps>, XCK_PHASE_LDS_SNPS=<snps>, XCK_PHASE_BLOCKS=<n>   xck_local_phase, read at every call (tests: small values reach the other path with small regions):
+ *                                         regions of at most WCAP SNPs (default and upper bound 512) keep their smoothing weights in the workgroup's HBM
+ *                                         scratch slice, larger ones recompute them; regions of at most LDS_SNPS SNPs (default and upper bound 1024)
+ *                                         keep their per-SNP state in LDS, larger ones in the slice; a launch has at most BLOCKS workgroups (default and upper
+ *                                         bound 2048), which walk the regions of a level in a grid-stride loop.  None changes a result.
  * Decoder (read when a BAM is opened or once per process): XCK_THREADS, XCK_NUMA=0, XCK_INFLATE=zlib, XCK_CHUNK_BYTES,
  * XCK_WRITE_THREADS (writer threads of xck_write_mtx), XCK_TEST_INTERN_LIMIT (tests). */
 #ifndef XCK_H
@@ -523,6 +532,69 @@ typedef struct xck_snp_text {
 #define XCK_SNP_REJ_GT          7   /* genotype is not 0|1 / 1|0 (0/1, 1/0)                   */
 int  xck_parse_snp_text(const char* path, int is_vcf, xck_snp_text** out);
 void xck_free_snp_text(xck_snp_text* t);
+
+/* -- region-wise local phasing (replaces reg_local_phasing / snp_local_phasing, baf/fc/phasing.py:13-78, baf/localphase.py:14-343) -- */
+/* Additive, ABI 3 is unchanged.  A stateless call: it needs no engine handle, allocates its own device buffers on `device` and frees them
+ * before it returns.  It restates, in fp64 HIP (csrc/local_phase.hip), what xcltk_amd/baf/fc/phasing.py and xcltk_amd/baf/localphase.py
+ * do on the host, region after region: the SNP and cell masks, the entry orientation of AD (ref_hap == 1 swaps AD with DP - AD), the rounds
+ * of BAF filter (cells with 0.45 <= BAF <= 0.55 leave, for good) + two-haplotype EM with Gaussian smoothing (width 20000) + XOR of the
+ * round's flip, and the majority rule.  The flips of a region's kept SNPs are applied to ref_hap / alt_hap (x -> 1 - x) before a later
+ * region that shares a SNP reads them: regions are levelled on the host (level 0: shares no SNP with an earlier region; otherwise 1 + the
+ * highest level among the earlier regions it shares a SNP with) and every level is one launch.  All sums run in a fixed order and no
+ * floating-point atomic is used: the same problem gives the same bytes on every run and every device.
+ *   pileup   cell x SNP counts as CSC by pileup column: col_ptr[n_cols + 1] (col_ptr[0] = 0, not decreasing), and per entry cell (strictly
+ *            ascending inside a column), ad, dp with 0 <= ad <= dp.  An entry with dp = 0 counts as absent.
+ *   cell_enabled   [n_cells] or NULL = all: a disabled cell is not seen at all (the --refcell subset).
+ *   ref_hap / alt_hap   [n_snps], 0 / 1: the haplotype state at entry.
+ *   regions  a CSR of slots, reg_ptr[n_regions + 1]; slot s pairs the pileup column slot_col[s] (or -1: the slot has no column and is never
+ *            kept) with the SNP slot_snp[s] of the phased list, at position slot_pos[s] for the smoothing.  The slots of one region name
+ *            distinct SNPs.  Regions are phased in the order given.
+ * Result (library-owned host memory, until xck_free_phase_result): kept[s] = 1 when slot s has depth in the enabled cells (0: the (region,
+ * SNP) pair leaves the region's list), flip[s] = 1 when the region flipped that SNP (after the majority rule; 0 for slots not kept and for
+ * failed regions), status[r] = XCK_PHASE_PHASED or XCK_PHASE_FAILED (no informative cell left: nothing was flipped), the final ref_hap /
+ * alt_hap, the number of levels (= launches), and host-measured milliseconds per stage.
+ * XCK_E_ARG: null pointers, a short struct_size, pointers that run backwards, indices outside the tables, cells not strictly ascending
+ * in a column, ad outside [0, dp], a haplotype index other than 0 / 1, a SNP twice in one region - all found before the device is touched.
+ * XCK_E_DEVICE / XCK_E_NOMEM as elsewhere.  Nothing is returned on error (*out = NULL; xck_last_error(NULL) has the text). */
+#define XCK_PHASE_FAILED 0
+#define XCK_PHASE_PHASED 1
+typedef struct xck_phase_problem {
+    uint32_t struct_size;       /* sizeof(xck_phase_problem)                                 */
+    int32_t  device;            /* HIP device ordinal                                        */
+    int32_t  n_cells;
+    int32_t  n_cols;
+    const int64_t* col_ptr;     /* [n_cols + 1]                                              */
+    const int32_t* cell;        /* [col_ptr[n_cols]]                                         */
+    const int32_t* ad;
+    const int32_t* dp;
+    const uint8_t* cell_enabled;/* [n_cells] or NULL                                         */
+    int32_t  n_snps;
+    int32_t  n_regions;
+    const int8_t*  ref_hap;     /* [n_snps]                                                  */
+    const int8_t*  alt_hap;
+    const int64_t* reg_ptr;     /* [n_regions + 1]                                           */
+    const int32_t* slot_col;    /* [reg_ptr[n_regions]]                                      */
+    const int32_t* slot_snp;
+    const int64_t* slot_pos;
+} xck_phase_problem;
+typedef struct xck_phase_result {
+    int64_t  n_slots;
+    const uint8_t* kept;        /* [n_slots]                                                 */
+    const uint8_t* flip;        /* [n_slots]                                                 */
+    int32_t  n_regions;
+    int32_t  n_snps;
+    const uint8_t* status;      /* [n_regions] XCK_PHASE_*                                   */
+    const int8_t*  ref_hap;     /* [n_snps]                                                  */
+    const int8_t*  alt_hap;
+    int32_t  n_levels;
+    int32_t  n_blocks;          /* workgroups of the widest launch (each owns a scratch slice) */
+    double   ms_prepare;        /* validation, levels, sizing (host)                         */
+    double   ms_h2d;            /* allocation and copies to the device                       */
+    double   ms_kernel;         /* all levels, launch to completion                          */
+    double   ms_d2h;            /* copies back, frees                                        */
+} xck_phase_result;
+int  xck_local_phase(const xck_phase_problem* p, xck_phase_result** out);
+void xck_free_phase_result(xck_phase_result* r);
 
 /* -- output (replaces merge_mtx(), rdr/fc/utils.py:54-93) ------------------------------------ */
 /* Write a MatrixMarket file byte-identical to the reference: header

@@ -8,7 +8,7 @@ pysam pileup of plp_snp()/fc_fet1() (baf/fc/core.py:143-247) runs as HIP kernels
 Region-wise local phasing from a cellsnp-lite pileup (`cellsnp_dir` / `ref_cell_fn`,
 baf/fc/main.py:107-153) runs on the host before the counting (baf/fc/phasing.py, baf/localphase.py):
 it changes the haplotype index of SNP alleles and drops uncovered SNPs from region lists; the
-engine then counts with that phase.
+engine then counts with that phase.  XCK_DEVICE_PHASING=1 phases the regions on the GPU instead (baf/fc/phasing_dev.py).
 """
 
 import os
@@ -159,6 +159,24 @@ def regions_with_snps(regions, snps):
     return out
 
 
+def _device_phasing_or_host(host_fn):
+    """local_phasing() as XCK_DEVICE_PHASING says: unset / 0 -> the host loop (the default and the specification); 1 -> the regions are
+    phased on the GPU (phasing_dev.py, csrc/local_phase.hip).  Without a usable device the host loop runs and the log says why; any
+    other failure of the device path raises."""
+    if os.environ.get("XCK_DEVICE_PHASING", "0") != "1":
+        return host_fn
+    from ... import capi
+    n_dev = capi.load().xck_device_count()
+    device = int(os.environ.get("XCK_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+    if n_dev <= 0:
+        warn("XCK_DEVICE_PHASING=1 but no usable HIP device: local phasing runs on the host.")
+        return host_fn
+    if device >= n_dev:
+        device = 0
+    from .phasing_dev import local_phasing_dev
+    return lambda *a: local_phasing_dev(*a, device=device)
+
+
 def phased_tables(conf, regions, snps, has_snp):
     """-> (the SNP list the engine counts with, (region indices, SNP indices) left out of the SNP -> region join or None): the
     input as it is without local phasing; otherwise region-wise local phasing (baf/fc/main.py:107-153) gives new haplotype indices
@@ -169,7 +187,7 @@ def phased_tables(conf, regions, snps, has_snp):
     from ...snptable import SnpTable
     phase_regions = regions if conf.output_all_reg else [r for r, h in zip(regions, has_snp) if h]
     phase_index = list(range(len(regions))) if conf.output_all_reg else [i for i, h in enumerate(has_snp) if h]
-    rh, ah, ex_r, ex_s, _ = local_phasing(phase_regions, snps, conf.snp_csp, conf.ref_cells, conf.debug)
+    rh, ah, ex_r, ex_s, _ = _device_phasing_or_host(local_phasing)(phase_regions, snps, conf.snp_csp, conf.ref_cells, conf.debug)
     ex_r = np.array([phase_index[i] for i in ex_r.tolist()], dtype=np.int32)
     if isinstance(snps, SnpTable):
         snps = SnpTable(snps.names, snps.chrom_id, snps.pos, snps.ref, snps.alt, rh, ah)

@@ -5,7 +5,7 @@ features, step 3 (afc_wrapper) makes a second handle and streams the same reads 
 of the same SNP positions.  Here one BAF engine is made with the step-3 regions and the candidate SNPs as its SNP table (alleles of
 the candidate VCF, REF on haplotype 0, ALT on 1, as genotype.py counts them), the BAMs are streamed once, and after finish()
   - Engine.snp_counts() gives the SNP x cell matrices of step 1 (xck_snp_counts), written with genotype._write_pileup_dirs;
-  - step 3's prepare_config / phased_tables run on that directory (local phasing stays on the host);
+  - step 3's prepare_config / phased_tables run on that directory (local phasing on the host, or on the device with XCK_DEVICE_PHASING=1);
   - Engine.refold() recounts under the phased list - its entries mapped into the candidates, the others disabled - and the result
     is written by the writers afc_wrapper uses.
 Both directories hold what the two-pass pipeline writes.

@@ -157,6 +157,24 @@ class IngestOpts(C.Structure):
                 ("tid_beg", C.POINTER(C.c_int32)), ("tid_end", C.POINTER(C.c_int32))]
 
 
+class PhaseProblem(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("device", C.c_int32), ("n_cells", C.c_int32), ("n_cols", C.c_int32),
+                ("col_ptr", C.POINTER(C.c_int64)), ("cell", C.POINTER(C.c_int32)), ("ad", C.POINTER(C.c_int32)), ("dp", C.POINTER(C.c_int32)),
+                ("cell_enabled", C.POINTER(C.c_uint8)), ("n_snps", C.c_int32), ("n_regions", C.c_int32),
+                ("ref_hap", C.POINTER(C.c_int8)), ("alt_hap", C.POINTER(C.c_int8)), ("reg_ptr", C.POINTER(C.c_int64)),
+                ("slot_col", C.POINTER(C.c_int32)), ("slot_snp", C.POINTER(C.c_int32)), ("slot_pos", C.POINTER(C.c_int64))]
+
+
+class PhaseResult(C.Structure):
+    _fields_ = [("n_slots", C.c_int64), ("kept", C.POINTER(C.c_uint8)), ("flip", C.POINTER(C.c_uint8)),
+                ("n_regions", C.c_int32), ("n_snps", C.c_int32), ("status", C.POINTER(C.c_uint8)),
+                ("ref_hap", C.POINTER(C.c_int8)), ("alt_hap", C.POINTER(C.c_int8)), ("n_levels", C.c_int32), ("n_blocks", C.c_int32),
+                ("ms_prepare", C.c_double), ("ms_h2d", C.c_double), ("ms_kernel", C.c_double), ("ms_d2h", C.c_double)]
+
+
+XCK_PHASE_FAILED, XCK_PHASE_PHASED = 0, 1
+
+
 # every symbol include/xck.h declares: (name, restype, argtypes)
 _P = C.POINTER
 class SnpText(C.Structure):
@@ -202,6 +220,8 @@ SYMBOLS = [
     ("xck_write_mtx_part", C.c_int, [C.c_char_p, C.c_int64, _P(Coo), _P(C.c_int32)]),
     ("xck_parse_snp_text", C.c_int, [C.c_char_p, C.c_int, _P(_P(SnpText))]),
     ("xck_free_snp_text", None, [_P(SnpText)]),
+    ("xck_local_phase", C.c_int, [_P(PhaseProblem), _P(_P(PhaseResult))]),
+    ("xck_free_phase_result", None, [_P(PhaseResult)]),
 ]
 
 _lib = None
@@ -310,3 +330,47 @@ def make_batch(contig, ordinal_base, pos, flag, mapq, cell, umi, cig_off, cigar,
         b.seq = np_ptr(seq, C.c_uint8)
         keep += [seq_off, seq]
     return b, keep
+
+
+def local_phase(n_cells, col_ptr, cell, ad, dp, ref_hap, alt_hap, reg_ptr, slot_col, slot_snp, slot_pos, cell_enabled=None, device=0,
+                struct_size=None):
+    """xck_local_phase over numpy arrays (include/xck.h): -> dict(kept, flip: uint8 per slot; status: uint8 per region; ref_hap,
+    alt_hap: int8 per SNP; n_levels, n_blocks, ms: dict of the stage times).  Raises engine.XckError with the library's code and text."""
+    from .engine import XckError
+    lib = load()
+    arr = lambda a, dt: np.ascontiguousarray(a, dtype=dt)
+    col_ptr, reg_ptr, slot_pos = arr(col_ptr, np.int64), arr(reg_ptr, np.int64), arr(slot_pos, np.int64)
+    cell, ad, dp = arr(cell, np.int32), arr(ad, np.int32), arr(dp, np.int32)
+    slot_col, slot_snp = arr(slot_col, np.int32), arr(slot_snp, np.int32)
+    ref_hap, alt_hap = arr(ref_hap, np.int8), arr(alt_hap, np.int8)
+    if len(col_ptr) < 1 or len(reg_ptr) < 1:
+        raise ValueError("col_ptr / reg_ptr need at least one element")
+    if not (len(cell) == len(ad) == len(dp)) or len(ref_hap) != len(alt_hap) or not (len(slot_col) == len(slot_snp) == len(slot_pos)):
+        raise ValueError("parallel arrays differ in length")
+    if (len(col_ptr) > 1 and int(col_ptr[-1]) > len(cell)) or (len(reg_ptr) > 1 and int(reg_ptr[-1]) > len(slot_col)):
+        raise ValueError("a pointer array ends beyond its table")
+    p = PhaseProblem()
+    p.struct_size = C.sizeof(PhaseProblem) if struct_size is None else struct_size
+    p.device, p.n_cells, p.n_cols = device, n_cells, len(col_ptr) - 1
+    p.col_ptr, p.cell, p.ad, p.dp = np_ptr(col_ptr, C.c_int64), np_ptr(cell, C.c_int32), np_ptr(ad, C.c_int32), np_ptr(dp, C.c_int32)
+    if cell_enabled is not None:
+        cell_enabled = arr(cell_enabled, np.uint8)
+        if len(cell_enabled) != n_cells:
+            raise ValueError("cell_enabled needs one byte per cell")
+        p.cell_enabled = np_ptr(cell_enabled, C.c_uint8)
+    p.n_snps, p.n_regions = len(ref_hap), len(reg_ptr) - 1
+    p.ref_hap, p.alt_hap = np_ptr(ref_hap, C.c_int8), np_ptr(alt_hap, C.c_int8)
+    p.reg_ptr, p.slot_col, p.slot_snp, p.slot_pos = np_ptr(reg_ptr, C.c_int64), np_ptr(slot_col, C.c_int32), np_ptr(slot_snp, C.c_int32), np_ptr(slot_pos, C.c_int64)
+    out = _P(PhaseResult)()
+    rc = lib.xck_local_phase(C.byref(p), C.byref(out))
+    if rc != 0:
+        raise XckError("xck_local_phase failed (%d): %s" % (rc, (lib.xck_last_error(None) or b"").decode()), rc)
+    try:
+        r = out.contents
+        take = lambda ptr, n, dt: np.ctypeslib.as_array(ptr, shape=(n,)).astype(dt, copy=True) if n else np.zeros(0, dtype=dt)
+        return dict(kept=take(r.kept, int(r.n_slots), np.uint8), flip=take(r.flip, int(r.n_slots), np.uint8),
+                    status=take(r.status, int(r.n_regions), np.uint8), ref_hap=take(r.ref_hap, int(r.n_snps), np.int8),
+                    alt_hap=take(r.alt_hap, int(r.n_snps), np.int8), n_levels=int(r.n_levels), n_blocks=int(r.n_blocks),
+                    ms=dict(prepare=r.ms_prepare, h2d=r.ms_h2d, kernel=r.ms_kernel, d2h=r.ms_d2h))
+    finally:
+        lib.xck_free_phase_result(out)

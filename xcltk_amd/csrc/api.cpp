@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <functional>
 #include <memory>
 #include <string>
@@ -325,6 +326,62 @@ int xck_snp_counts(xck_engine* e, xck_result* out) {
     if (!(e->mode & XCK_MODE_BAF)) { e->err = "xck_snp_counts: the handle has no BAF pipeline"; return XCK_E_ARG; }
     return engine_snp_counts(e->impls[e->n_impl - 1], out);              // (a fused handle answers from its pileup pipeline)
 }
+
+// Region-wise local phasing on the device (local_phase.hip).  Everything that can be wrong with the arguments is found here, before
+// the device is touched; the levels are made here too: a region reads the SNP state that the earlier regions sharing a SNP left.
+int xck_local_phase(const xck_phase_problem* p, xck_phase_result** out) {
+    if (out) *out = nullptr;
+    if (!p || !out) { set_thread_error("xck_local_phase: null argument"); return XCK_E_ARG; }
+    const auto t0 = std::chrono::steady_clock::now();
+    auto bad = [](const std::string& s) { set_thread_error("xck_local_phase: " + s); return XCK_E_ARG; };
+    if (p->struct_size < sizeof(xck_phase_problem)) return bad("xck_phase_problem.struct_size mismatch (ABI)");
+    if (p->n_cells <= 0 || p->n_cols < 0 || p->n_snps < 0 || p->n_regions < 0) return bad("invalid table sizes");
+    if (!p->col_ptr || !p->reg_ptr) return bad("null pointer array");
+    if (p->col_ptr[0] != 0 || p->reg_ptr[0] != 0) return bad("pointer arrays must start at 0");
+    for (int32_t c = 0; c < p->n_cols; c++) if (p->col_ptr[c + 1] < p->col_ptr[c]) return bad("col_ptr runs backwards");
+    for (int32_t r = 0; r < p->n_regions; r++) if (p->reg_ptr[r + 1] < p->reg_ptr[r]) return bad("reg_ptr runs backwards");
+    const int64_t nnz = p->col_ptr[p->n_cols], n_slots = p->reg_ptr[p->n_regions];
+    if ((nnz > 0 && (!p->cell || !p->ad || !p->dp)) || (n_slots > 0 && (!p->slot_col || !p->slot_snp || !p->slot_pos)) || (p->n_snps > 0 && (!p->ref_hap || !p->alt_hap)))
+        return bad("null table pointer");
+    for (int32_t c = 0; c < p->n_cols; c++)
+        for (int64_t i = p->col_ptr[c]; i < p->col_ptr[c + 1]; i++) {
+            if (p->cell[i] < 0 || p->cell[i] >= p->n_cells) return bad("cell index outside the table");
+            if (i > p->col_ptr[c] && p->cell[i] <= p->cell[i - 1]) return bad("cells of a column are not strictly ascending");
+            if (p->ad[i] < 0 || p->ad[i] > p->dp[i]) return bad("ad outside [0, dp]");
+        }
+    for (int32_t s = 0; s < p->n_snps; s++) if ((p->ref_hap[s] | p->alt_hap[s]) & ~1) return bad("haplotype index other than 0 / 1");
+    PhasePlan plan;
+    std::vector<int32_t> snp_level(p->n_snps, -1), snp_region(p->n_snps, -1), level(p->n_regions, 0);
+    int n_levels = 0;
+    for (int32_t r = 0; r < p->n_regions; r++) {
+        int64_t entries = 0;
+        int lv = 0;
+        for (int64_t s = p->reg_ptr[r]; s < p->reg_ptr[r + 1]; s++) {
+            const int32_t col = p->slot_col[s], snp = p->slot_snp[s];
+            if (col < -1 || col >= p->n_cols) return bad("slot column outside the pileup");
+            if (snp < 0 || snp >= p->n_snps) return bad("slot SNP outside the list");
+            if (snp_region[snp] == r) return bad("a SNP twice in one region");
+            snp_region[snp] = r;
+            lv = std::max(lv, snp_level[snp] + 1);
+            if (col >= 0) entries += p->col_ptr[col + 1] - p->col_ptr[col];
+        }
+        if (p->reg_ptr[r + 1] - p->reg_ptr[r] > INT32_MAX || entries > INT32_MAX) return bad("region too large");
+        for (int64_t s = p->reg_ptr[r]; s < p->reg_ptr[r + 1]; s++) snp_level[p->slot_snp[s]] = lv;
+        level[r] = lv;
+        n_levels = std::max(n_levels, lv + 1);
+        plan.max_n = std::max(plan.max_n, (int)(p->reg_ptr[r + 1] - p->reg_ptr[r]));
+        plan.max_e = std::max(plan.max_e, (int)entries);
+    }
+    plan.level_beg.assign(n_levels + 1, 0);
+    for (int32_t r = 0; r < p->n_regions; r++) plan.level_beg[level[r] + 1]++;
+    for (int l = 0; l < n_levels; l++) plan.level_beg[l + 1] += plan.level_beg[l];
+    plan.order.resize(p->n_regions);
+    { std::vector<int32_t> cur(plan.level_beg.begin(), plan.level_beg.end() - 1); for (int32_t r = 0; r < p->n_regions; r++) plan.order[cur[level[r]]++] = r; }
+    const double ms_prepare = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return local_phase_run(p, plan, ms_prepare, out);
+}
+
+void xck_free_phase_result(xck_phase_result* r) { local_phase_free(r); }
 
 int xck_get_stats(const xck_engine* e, xck_stats* out) {
     if (!e || !out) return XCK_E_ARG;

@@ -183,6 +183,15 @@ int  engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const
 void engine_release_staging(xck_engine* e);   // frees the staging slots (xck_destroy)
 void fence_wait(void* fence);
 void fence_destroy(void* fence);
+// xck_local_phase (local_phase.hip): api.cpp checks the problem and levels the regions, local_phase_run drives the device
+struct PhasePlan {
+    std::vector<int32_t> order;          // regions sorted by (level, index)
+    std::vector<int32_t> level_beg;      // [n_levels + 1] into order
+    int max_n = 0;                       // most slots of a region
+    int max_e = 0;                       // most pileup entries under the slots of a region
+};
+int  local_phase_run(const xck_phase_problem* p, const PhasePlan& plan, double ms_prepare, xck_phase_result** out);
+void local_phase_free(xck_phase_result* r);
 void* pinned_alloc(size_t bytes);        // hipHostMalloc, falls back to malloc when no device
 void  pinned_free(void* p);
 }
