@@ -54,6 +54,17 @@
  *                                         XCK_F_FEATURE_SUMMARY (xck_get_feature_summary): the front-ends then write feature_summary.tsv and, for the
  *                                         pileup, snp_summary.tsv next to their matrices.  One kernel more per join launch; does not imply XCK_READ_FATE.
  *                                         Off (the default, or 0) nothing is allocated or launched.  Decode-only handles ignore it.
+ *   XCK_GROUP_LONG_ROW=<entries>          xck_group_counts: a source row with at least this many entries is summed by one block with a table in
+ *                                         LDS, a shorter one by one wave in registers (default and upper bound 64, at least 1; tests: a small value
+ *                                         reaches the block shape with small inputs)
+ *   XCK_CELL_GROUPS=<file>                (read by the Python front-ends, not by a handle) a TSV of name<TAB>group lines without a header, name = a
+ *                                         barcode or a sample id; groups are numbered by first appearance, names that are not cells of the run are
+ *                                         ignored (their number goes to the log), cells not named are left out.  The front-ends then write, next to
+ *                                         their cell matrices, the same matrices summed per group (xck_group_counts): groups.tsv + matrix.groups.mtx
+ *                                         (basefc), xcltk.groups.tsv + xcltk.{AD,DP,OTH}.groups.mtx (BAF step 3), cellSNP.groups.tsv +
+ *                                         cellSNP.tag.{AD,DP,OTH}.groups.mtx (BAF step 1, raw and filtered).  A multi-GPU run that gathers its result
+ *                                         on one rank (XCK_DIST_GATHER=1) logs one line and writes no group files.  Unset: nothing is allocated,
+ *                                         launched or written.
  *   XCK_DEVICE_PHASING=1                  (read by the Python front-ends, not by a handle) region-wise local phasing before the allele-specific counting runs
  *                                         on the device (xck_local_phase below; xcltk_amd/baf/fc/phasing_dev.py) instead of the float64 host loop
  *                                         of baf/fc/phasing.py, which stays the default and the specification.  Covers afc_wrapper, afc_variants and the
@@ -427,6 +438,37 @@ int  xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out);
  * the split pileup fold has the same limit).  A handle without hits gives XCK_OK and three empty matrices.  An error leaves the handle as it
  * was: a failure inside the call (no memory for its own buffers) does not mark the handle failed. */
 int  xck_snp_counts(xck_engine* e, xck_result* out);
+/* Pseudo-bulk matrices per cell group (additive: ABI 3 is unchanged): the matrices the handle holds in device memory, with their columns
+ * summed per group of cells under the mapping cell_group[n_cells of the handle] -> 0 .. n_groups - 1, or -1 = the cell is left out.
+ *   Values    out->count / ad / dp / oth are COO with row = the source's row (a region in the handle's current order, a SNP in the
+ *             caller's order) and col = group, sorted by (row, col), without zero entries.  Every value is exactly the sum, over the
+ *             cells mapped to that group, of the source's values in that row.
+ *   Filters   nothing is filtered again: the per-SNP filters, exclusions and no_dup_hap are those the source matrices were counted
+ *             under; a group's AD / DP is the sum of its cells' AD / DP.
+ *   Empty     a group without cells, and a row whose cells are all left out, produce no entries; all cells at -1, or a handle without
+ *             hits, give XCK_OK and empty matrices.
+ *   XCK_GROUP_SRC_RESULT   the matrices of the last xck_finish or xck_refold (after a refold: the refolded ones): a basefc handle fills
+ *             count, a BAF handle ad / dp / oth, a XCK_MODE_BOTH handle all four (its count is the last finish's).
+ *   XCK_GROUP_SRC_SNP      the blocks of the last xck_snp_counts since the last finish or reset: ad / dp / oth, count stays empty.
+ * Valid between a successful xck_finish and the next xck_reset, as often as wanted.  The call uses buffers of its own (grow-only, freed
+ * at xck_destroy): it invalidates nothing that xck_finish, xck_refold, xck_snp_counts or xck_get_result_device handed out, and none of
+ * those invalidates its blocks, which live until the next xck_group_counts, xck_reset or xck_destroy.  A failure inside the call does
+ * not mark the handle failed.
+ * XCK_E_STATE before a finish, after a reset, on a decode-only handle, after a failed fold, or for source SNP when no xck_snp_counts
+ * has run since the last finish or reset.  XCK_E_ARG for null pointers, a short struct_size, an unknown source, source SNP on a
+ * basefc-only handle, n_groups outside 1 .. XCK_GROUP_MAX, or a cell_group entry outside -1 .. n_groups - 1: all found before the device
+ * is touched, the handle stays as it was.  XCK_E_CAPACITY when a sum does not fit int32 (found, never wrapped) or a source matrix
+ * holds 2^32 entries or more.  XCK_DEBUG_TIMING prints one `[xck] group_counts:` line. */
+#define XCK_GROUP_SRC_RESULT 0   /* the matrices the handle holds now: last xck_finish or xck_refold */
+#define XCK_GROUP_SRC_SNP    1   /* the blocks of the last xck_snp_counts */
+#define XCK_GROUP_MAX     4096
+typedef struct xck_group_config {
+    uint32_t struct_size;       /* sizeof(xck_group_config)                                  */
+    int32_t  source;            /* XCK_GROUP_SRC_*                                           */
+    int32_t  n_groups;          /* 1 .. XCK_GROUP_MAX                                        */
+    const int32_t* cell_group;  /* [n_cells of the handle]: group of every cell, or -1 = the cell is left out */
+} xck_group_config;
+int  xck_group_counts(xck_engine* e, const xck_group_config* cfg, xck_result* out);
 /* Forget all pushed reads, keep tables and buffers (lets one engine be re-used per step). */
 int  xck_reset(xck_engine* e);
 int  xck_get_stats(const xck_engine* e, xck_stats* out);

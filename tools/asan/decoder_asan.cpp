@@ -24,6 +24,7 @@ int  engine_finish_async(EngineImpl*) { return XCK_E_ARG; }
 int  engine_result_device(EngineImpl*, xck_result*) { return XCK_E_ARG; }
 int  engine_refold(EngineImpl*, const xck_refold_config*, xck_result*) { return XCK_E_ARG; }
 int  engine_snp_counts(EngineImpl*, xck_result*) { return XCK_E_ARG; }
+int  engine_group_counts(EngineImpl*, int, int, const int32_t*, xck_result*, GroupTimes*) { return XCK_E_ARG; }
 int  local_phase_run(const xck_phase_problem*, const PhasePlan&, double, xck_phase_result**) { return XCK_E_DEVICE; }   // (local_phase.hip)
 void local_phase_free(xck_phase_result*) {}
 int  engine_reset(EngineImpl*) { return XCK_E_ARG; }

@@ -130,6 +130,7 @@ def prepare_config(conf):
             return -1
     if fcc.resolve_tags(conf) < 0:
         return -1
+    conf.cell_groups = fcc.load_cell_groups(conf.samples)     # (XCK_CELL_GROUPS only; ValueError for a bad file, before any BAM is opened)
     if fcc.is_writer_rank():
         fcc.write_samples(conf.out_sample_fn, conf.samples)
     return 0
@@ -199,7 +200,7 @@ def phased_tables(conf, regions, snps, has_snp):
 
 def write_matrices(conf, eng, dist, regions, coo):
     """xcltk.region.tsv and the three .mtx files of one counted table (afc_wrapper, afc_variants and the one-pass `xcltk baf` write
-    through here).  Only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113), unless output_all_reg."""
+    through here), and with XCK_CELL_GROUPS their sums per cell group.  Only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113), unless output_all_reg."""
     rm = fcc.output_row_map(dist, len(regions), conf.output_all_reg, coo["dp"][0], coo["oth"][0])
     n_rows = int(rm.max()) if len(rm) else 0
     if fcc.is_writer_rank():
@@ -207,6 +208,9 @@ def write_matrices(conf, eng, dist, regions, coo):
     fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, n_rows)
     fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, n_rows)
     fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, n_rows)
+    pre = os.path.join(conf.out_dir, conf.out_prefix)                # (XCK_CELL_GROUPS only: the same rows, summed per group)
+    fcc.write_group_matrices(eng, dist, getattr(conf, "cell_groups", None), pre + "groups.tsv",
+                             {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"}, rm, n_rows)
 
 
 def afc_core(conf):

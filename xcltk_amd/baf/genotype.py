@@ -65,17 +65,39 @@ def write_cellsnp_dir(out_dir, snps, cells, mats, is_gzip=True):
         fp.write(text.encode("utf8") if is_gzip else text)
     with open(os.path.join(out_dir, "cellSNP.samples.tsv"), "w") as fp:
         fp.write("".join(c + "\n" for c in cells))
-    for k, (row, col, val) in mats.items():
-        with open(os.path.join(out_dir, "cellSNP.tag.%s.mtx" % k), "w") as fp:
-            fp.write("%%MatrixMarket matrix coordinate integer general\n%\n")
-            fp.write("%d\t%d\t%d\n" % (len(snps), len(cells), len(row)))
-            fp.write("".join("%d\t%d\t%d\n" % (r + 1, c + 1, v) for r, c, v in zip(np.asarray(row).tolist(), np.asarray(col).tolist(), np.asarray(val).tolist())))
+    for k, m in mats.items():
+        _write_tag_mtx(os.path.join(out_dir, "cellSNP.tag.%s.mtx" % k), len(snps), len(cells), m)
     return fn
 
 
-def filter_snps(in_dir, out_dir, min_count, min_maf):
+def _write_tag_mtx(path, n_rows, n_cols, m):
+    """One cellSNP.tag.*.mtx: m = (row, col, val), 0-based."""
+    row, col, val = m
+    with open(path, "w") as fp:
+        fp.write("%%MatrixMarket matrix coordinate integer general\n%\n")
+        fp.write("%d\t%d\t%d\n" % (n_rows, n_cols, len(row)))
+        fp.write("".join("%d\t%d\t%d\n" % (r + 1, c + 1, v) for r, c, v in zip(np.asarray(row).tolist(), np.asarray(col).tolist(), np.asarray(val).tolist())))
+
+
+def write_group_dir(out_dir, n_snps, names, mats, row_of):
+    """cellSNP.groups.tsv and cellSNP.tag.{AD,DP,OTH}.groups.mtx of one pileup directory (XCK_CELL_GROUPS): mats = {"AD" | "DP" |
+    "OTH": (row, group, val)}, sorted by (row, group); row_of[row] = the row of the directory's cell files, or -1 = the SNP is
+    not in this directory.  The rows are those of the cell files next to them."""
+    with open(os.path.join(out_dir, "cellSNP.groups.tsv"), "w") as fp:
+        fp.write("".join(g + "\n" for g in names))
+    out = {}
+    for k, (row, col, val) in mats.items():
+        r = np.asarray(row_of, dtype=np.int64)[np.asarray(row, dtype=np.int64)]
+        keep = r >= 0
+        out[k] = (r[keep], np.asarray(col)[keep], np.asarray(val)[keep])
+        _write_tag_mtx(os.path.join(out_dir, "cellSNP.tag.%s.groups.mtx" % k), n_snps, len(names), out[k])
+    return out
+
+
+def filter_snps(in_dir, out_dir, min_count, min_maf, groups=None):
     """The reference's second filter (baf/genotype.py:190-229): keep SNPs with DP >= min_count and min_maf <= AD / DP <=
-    1 - min_maf, REF and ALT counts only.  -> (output VCF, #SNPs before, #SNPs after)."""
+    1 - min_maf, REF and ALT counts only.  -> (output VCF, #SNPs before, #SNPs after).  groups = (group names, the group matrices
+    of in_dir as write_group_dir returned them): the group files of out_dir are written too, with the rows that survive."""
     from ..utils.csp_io import load_data
     d = load_data(in_dir)
     AD = np.asarray(d.AD.sum(axis=0)).reshape(-1).astype(np.int64)
@@ -90,6 +112,10 @@ def filter_snps(in_dir, out_dir, min_count, min_maf):
         mats[k] = (coo.row, coo.col, coo.data)
     snps = [(str(c), int(p), str(r), str(a)) for c, p, r, a in zip(sub.chrom, sub.pos, sub.ref, sub.alt)]
     fn = write_cellsnp_dir(out_dir, snps, sub.cells, mats)
+    if groups is not None:
+        row_of = np.full(d.shape[1], -1, dtype=np.int64)
+        row_of[keep] = np.arange(len(keep))
+        write_group_dir(out_dir, len(keep), groups[0], groups[1], row_of)
     return fn, d.shape[1], sub.shape[1]
 
 
@@ -121,6 +147,7 @@ def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sa
     """Signature of the reference's pileup() (baf/genotype.py:20-187); the engine replaces the cellsnp-lite call.
     Returns (output VCF, #SNPs in <out_dir>/raw, #SNPs after filtering)."""
     conf = pileup_conf(sam_fn, sam_list_fn, barcode_fn, sample_id_fn, sample_id, mode, cell_tag, umi_tag, ncores)
+    groups = fcc.load_cell_groups(conf.samples, "[pileup]")           # (XCK_CELL_GROUPS only; ValueError for a bad file, before any BAM is opened)
     if not snp_vcf_fn or not os.path.isfile(snp_vcf_fn):
         raise ValueError("SNP vcf '%s' does not exist." % snp_vcf_fn)
     cand = load_candidate_snps(snp_vcf_fn)
@@ -148,10 +175,14 @@ def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sa
             fcc.write_snp_summary(eng, dist, os.path.join(out_dir, "snp_summary.tsv"), snps, log_prefix="[pileup]")
             if coo is not None:                                   # the matrices are views of the engine's pinned buffers: keep copies past close()
                 coo = {k: tuple(np.array(a) for a in v) for k, v in coo.items()}
+                if groups is not None and not fcc.group_output_off(dist, "[pileup]"):   # the SNP rows summed per cell group
+                    groups = (groups[0], eng.group_counts(groups[1], n_groups=max(len(groups[0]), 1)))
+                else:
+                    groups = None
         finally:
             eng.close()
         if coo is not None:
-            result = _write_pileup_dirs(out_dir, cand, conf.samples, coo, min_count, min_maf)
+            result = _write_pileup_dirs(out_dir, cand, conf.samples, coo, min_count, min_maf, groups)
     except Exception as e:                                        # noqa: BLE001 - re-raised below, after the collective
         failure = e
     if dist.active:
@@ -163,15 +194,17 @@ def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sa
     return result
 
 
-def _write_pileup_dirs(out_dir, cand, samples, coo, min_count, min_maf):
-    """raw/ (every covered SNP) and the filtered directory, from the gathered AD / DP / OTH matrices (writer rank)."""
+def _write_pileup_dirs(out_dir, cand, samples, coo, min_count, min_maf, groups=None):
+    """raw/ (every covered SNP) and the filtered directory, from the gathered AD / DP / OTH matrices (writer rank).  groups =
+    (group names, Engine.group_counts() of the same rows) or None: the group files of both directories."""
     raw_dir = os.path.join(out_dir, "raw")
-    _write_raw_dir(raw_dir, cand, samples, coo)
-    return filter_snps(raw_dir, out_dir, min_count, min_maf)
+    raw_groups = _write_raw_dir(raw_dir, cand, samples, coo, groups)
+    return filter_snps(raw_dir, out_dir, min_count, min_maf, raw_groups)
 
 
-def _write_raw_dir(raw_dir, cand, samples, coo):
-    """The raw pileup directory: every candidate SNP with at least one counted UMI (coo = engine / oracle matrices, rows = candidates)."""
+def _write_raw_dir(raw_dir, cand, samples, coo, groups=None):
+    """The raw pileup directory: every candidate SNP with at least one counted UMI (coo = engine / oracle matrices, rows = candidates).
+    -> None, or with groups (see _write_pileup_dirs) the group matrices in the directory's rows, for filter_snps."""
     covered = np.zeros(len(cand), dtype=bool)
     covered[coo["dp"][0]] = True
     covered[coo["oth"][0]] = True
@@ -180,3 +213,6 @@ def _write_raw_dir(raw_dir, cand, samples, coo):
     remap[idx] = np.arange(len(idx))
     mats = {k: (remap[np.asarray(coo[m][0], dtype=np.int64)], coo[m][1], coo[m][2]) for k, m in (("AD", "ad"), ("DP", "dp"), ("OTH", "oth"))}
     write_cellsnp_dir(raw_dir, [cand[i] for i in idx.tolist()], samples, mats)
+    if groups is None:
+        return None
+    return groups[0], write_group_dir(raw_dir, len(idx), groups[0], {k: groups[1][m] for k, m in (("AD", "ad"), ("DP", "dp"), ("OTH", "oth"))}, remap)

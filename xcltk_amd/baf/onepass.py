@@ -99,6 +99,11 @@ def run(sam_fn, sam_list_fn, barcode_fn, sample_id_fn, sample_id, mode, snp_vcf_
     info("one-pass baf: %d candidate SNPs, %d phased SNPs, %d regions, %d cells." % (len(table), len(phased), len(regions), len(conf3.samples)))
     conf3.reg_list = regions
     try:
+        groups = fcc.load_cell_groups(conf3.samples, "[onepass]")          # (XCK_CELL_GROUPS only; a bad file ends the run before any BAM is opened)
+    except ValueError as e:
+        error("one-pass baf: %s" % e)
+        return -1
+    try:
         eng, _, dist = fcc.make_and_count(conf3, XCK_MODE_BAF, regions, table, log_prefix="[onepass]")
     except (ValueError, XckError) as e:
         error("one-pass baf: counting failed: %s" % e)
@@ -106,7 +111,9 @@ def run(sam_fn, sam_list_fn, barcode_fn, sample_id_fn, sample_id, mode, snp_vcf_
     try:
         # step 1: the SNP x cell matrices of the pass, into the directories genotype.pileup writes
         coo = eng.snp_counts()
-        vcf, p_raw, p_new = G._write_pileup_dirs(pileup_dir, cand, conf1.samples, coo, min_count, min_maf)
+        if groups is not None:                                            # the same blocks summed per cell group, while they are in HBM
+            groups = (groups[0], eng.group_counts(groups[1], n_groups=max(len(groups[0]), 1), source="snp"))
+        vcf, p_raw, p_new = G._write_pileup_dirs(pileup_dir, cand, conf1.samples, coo, min_count, min_maf, groups)
         info("pileup #SNP raw=%d; post-filtering=%d." % (p_raw, p_new))
         info("pileup VCF is '%s'." % vcf)
         # step 3: its own preparation on that directory, then the recount under the phased list

@@ -70,6 +70,14 @@ class RefoldConfig(C.Structure):
     ]
 
 
+XCK_GROUP_SRC_RESULT, XCK_GROUP_SRC_SNP = 0, 1
+XCK_GROUP_MAX = 4096
+
+
+class GroupConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("source", C.c_int32), ("n_groups", C.c_int32), ("cell_group", C.POINTER(C.c_int32))]
+
+
 class Batch(C.Structure):
     _fields_ = [
         ("contig", C.c_int32), ("n_reads", C.c_int32), ("ordinal_base", C.c_uint64),
@@ -199,6 +207,7 @@ SYMBOLS = [
     ("xck_get_result_device", C.c_int, [C.c_void_p, _P(Result)]),
     ("xck_refold", C.c_int, [C.c_void_p, _P(RefoldConfig), _P(Result)]),
     ("xck_snp_counts", C.c_int, [C.c_void_p, _P(Result)]),
+    ("xck_group_counts", C.c_int, [C.c_void_p, _P(GroupConfig), _P(Result)]),
     ("xck_reset", C.c_int, [C.c_void_p]),
     ("xck_get_stats", C.c_int, [C.c_void_p, _P(Stats)]),
     ("xck_get_decode_stats", C.c_int, [C.c_void_p, _P(DecodeStats)]),

@@ -62,6 +62,7 @@ Knobs xck::Knobs::from_env() {
     k.read_fate = num("XCK_READ_FATE", 0) != 0;
     k.cell_summary = num("XCK_CELL_SUMMARY", 0) != 0;
     k.feature_summary = num("XCK_FEATURE_SUMMARY", 0) != 0;
+    k.group_long_row = (int)std::max(1ll, std::min(64ll, num("XCK_GROUP_LONG_ROW", 64)));
     k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
     return k;
 }
@@ -325,6 +326,33 @@ int xck_snp_counts(xck_engine* e, xck_result* out) {
     if (e->n_impl <= 0) return no_engine(e);
     if (!(e->mode & XCK_MODE_BAF)) { e->err = "xck_snp_counts: the handle has no BAF pipeline"; return XCK_E_ARG; }
     return engine_snp_counts(e->impls[e->n_impl - 1], out);              // (a fused handle answers from its pileup pipeline)
+}
+
+// The handle's matrices summed per cell group (group_counts.h).  Everything that can be wrong with the arguments is found here, before the
+// device is touched; a fused handle answers from both pipelines, each with buffers of its own.
+int xck_group_counts(xck_engine* e, const xck_group_config* cfg, xck_result* out) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (!cfg || !out) { e->err = "xck_group_counts: null argument"; return XCK_E_ARG; }
+    if (cfg->struct_size < sizeof(xck_group_config)) { e->err = "xck_group_config.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (e->n_impl <= 0) return no_engine(e);
+    if (cfg->source != XCK_GROUP_SRC_RESULT && cfg->source != XCK_GROUP_SRC_SNP) { e->err = "xck_group_counts: unknown source"; return XCK_E_ARG; }
+    if (cfg->source == XCK_GROUP_SRC_SNP && !(e->mode & XCK_MODE_BAF)) { e->err = "xck_group_counts: source SNP on a handle without a BAF pipeline"; return XCK_E_ARG; }
+    if (cfg->n_groups < 1 || cfg->n_groups > XCK_GROUP_MAX) { e->err = "xck_group_counts: n_groups outside 1 .. XCK_GROUP_MAX"; return XCK_E_ARG; }
+    if (!cfg->cell_group) { e->err = "xck_group_counts: null cell_group"; return XCK_E_ARG; }
+    { uint32_t bad = 0;
+      for (int32_t c = 0; c < e->n_cells; c++) bad |= (uint32_t)(cfg->cell_group[c] < -1) | (uint32_t)(cfg->cell_group[c] >= cfg->n_groups);
+      if (bad) { e->err = "xck_group_counts: a cell_group entry outside -1 .. n_groups - 1"; return XCK_E_ARG; } }
+    xck_result r; memset(&r, 0, sizeof r);
+    GroupTimes gt;
+    const int k0 = cfg->source == XCK_GROUP_SRC_SNP ? e->n_impl - 1 : 0;  // (the SNP x cell blocks are the pileup pipeline's)
+    for (int k = k0; k < e->n_impl; k++)
+        if (int rc = engine_group_counts(e->impls[k], cfg->source, cfg->n_groups, cfg->cell_group, &r, &gt)) return rc;
+    if (e->knobs.debug_timing)
+        fprintf(stderr, "[xck] group_counts: source %s, %d groups: total %.3f ms (host clock to the stream synchronise): row pointers %.3f, count + scans %.3f, emit %.3f; "
+                        "wait for the copy-out %.3f; %lld entries, nnz %lld / %lld / %lld / %lld\n", cfg->source == XCK_GROUP_SRC_SNP ? "snp" : "result", cfg->n_groups,
+                gt.ms_total, gt.ms_ptr, gt.ms_count, gt.ms_emit, gt.ms_copy, gt.entries, gt.nnz[0], gt.nnz[1], gt.nnz[2], gt.nnz[3]);
+    *out = r;
+    return XCK_OK;
 }
 
 // Region-wise local phasing on the device (local_phase.hip).  Everything that can be wrong with the arguments is found here, before

@@ -223,6 +223,15 @@ struct EngineImpl {
     size_t sc_nnz[3] = {0, 0, 0}; bool sc_valid = false;
     hipEvent_t ev_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double sc_ms_heads = 0, sc_ms_rows = 0, sc_ms_emit = 0, sc_ms_copy = 0, sc_ms_total = 0;   // the last call, for XCK_DEBUG_TIMING and tools/snp_counts_time.py
+    // xck_group_counts (group_counts.h): buffers of its own, grow-only - scratch (control words, the cell -> group mapping, row pointers,
+    // row counts, the long-row queue), the COO blocks of this pipeline's matrices on the device and in pinned host memory (valid until
+    // the next xck_group_counts / reset)
+    char* d_gc = nullptr; size_t gc_cap = 0;
+    int32_t* d_gc_res = nullptr; size_t gc_res_cap = 0;
+    int32_t* h_gc_res = nullptr; size_t h_gc_res_cap = 0;
+    unsigned long long *h_gc_tot = nullptr, *d_gc_tot_alias = nullptr;   // the totals and the overflow flag: pinned + mapped words and their device alias
+    size_t gc_nnz[3] = {0, 0, 0};
+    hipEvent_t ev_g[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
 
 // d_snp_info: ref nibble | alt nibble << 4 | ref_hap << 8 | alt_hap << 9

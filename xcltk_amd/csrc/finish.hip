@@ -10,6 +10,7 @@
 //                 (k_hap_items; fallback: sort + k_hap_class / k_hap_sum), k_hap_count / k_hap_scatter (AD / DP / OTH -> COO);
 //                 128-bit keys: k_first_read and the sorted path.
 //   snp_counts  : the SNP x cell matrices of the finished pileup from the molecule stage alone (snp_counts.h).
+//   group_counts: the row x group sums of the result blocks or of the SNP x cell blocks under a cell -> group mapping (group_counts.h).
 //                 Copy-out on the copy stream (xck_finish_async).
 //
 // Integer / byte work only - HBM-bound, no MFMA.  See DESIGN.md for layouts, byte counts and measurements.
@@ -1463,6 +1464,7 @@ int snp_verdicts(EngineImpl* im, uint32_t* d_kept) {
 
 #include "refold.h"
 #include "snp_counts.h"
+#include "group_counts.h"
 
 int finish_init(EngineImpl* im) {
     // the hash fold needs 64 KB of dynamic LDS: raise the limit on THIS engine's device (a per-process flag would leave every

@@ -115,6 +115,7 @@ struct Knobs {
     bool cell_summary = false;           // XCK_CELL_SUMMARY=1: XCK_F_CELL_SUMMARY ORed into the flags of every handle that drives a GPU
     int  cell_summary_slots = 0;         // XCK_CELL_SUMMARY_SLOTS: rows of the per-block LDS tables (0 = the built-in 512 per-cell, 1024 per-feature / per-SNP; tests: small tables reach the no-fit path)
     bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
+    int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
     int  verify_crc = 0;                 // XCK_VERIFY_CRC: 0 = as the flags say, 1 = host (XCK_F_VERIFY_CRC ORed in), 2 = device (XCK_F_DEVICE_CRC)
     static Knobs from_env();             // api.cpp
 };
@@ -169,6 +170,9 @@ int  engine_finish_async(EngineImpl* im);
 int  engine_result_device(EngineImpl* im, xck_result* out);
 int  engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out);   // refold.h (finish.hip): the pileup pipeline's region stage under new tables
 int  engine_snp_counts(EngineImpl* im, xck_result* out);           // snp_counts.h (finish.hip): SNP x cell AD / DP / OTH of the finished pileup
+// what one xck_group_counts spent, summed over the handle's pipelines (XCK_DEBUG_TIMING, tools/group_counts_time.py)
+struct GroupTimes { double ms_total = 0, ms_ptr = 0, ms_count = 0, ms_emit = 0, ms_copy = 0; long long entries = 0, nnz[4] = {0, 0, 0, 0}; };
+int  engine_group_counts(EngineImpl* im, int source, int n_groups, const int32_t* cell_group, xck_result* out, GroupTimes* gt);   // group_counts.h (finish.hip): one pipeline's matrices summed per cell group
 int  engine_reset(EngineImpl* im);
 int  engine_stats(const EngineImpl* im, xck_stats* out);
 int  engine_read_fate(EngineImpl* im, xck_read_fate* out);         // read_fate.h

@@ -409,6 +409,34 @@ class Engine(object):
         self._check(self.lib.xck_snp_counts(self.h, C.byref(res)), "xck_snp_counts")
         return dict(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
 
+    def group_counts(self, cell_group, n_groups=None, source="result", copy=True):
+        """The engine's matrices with their columns summed per cell group (xck_group_counts): cell_group[c] is the group of cell c,
+        -1 leaves the cell out; n_groups defaults to max(cell_group) + 1.  source="result": the matrices of the last finish() /
+        refold() -> {"count": (row, col, val)} and / or {"ad": .., "dp": .., "oth": ..} like finish(); source="snp": the blocks of the
+        last snp_counts() -> {"ad", "dp", "oth"} with row = SNP.  col = group, sorted by (row, col), no zero entries.  Valid between
+        finish() and reset(); it leaves every other result alone.  copy=False returns views of the engine's pinned buffers, valid
+        until the next group_counts(), reset() or close()."""
+        src = {"result": capi.XCK_GROUP_SRC_RESULT, "snp": capi.XCK_GROUP_SRC_SNP}.get(source, source)
+        cg = np.ascontiguousarray(cell_group, dtype=np.int32)
+        if cg.ndim != 1 or len(cg) != self.n_cells:
+            raise ValueError("cell_group needs one entry per cell of the engine")
+        if n_groups is None:
+            n_groups = int(cg.max()) + 1 if len(cg) else 0
+            n_groups = max(n_groups, 1)
+        cfg = capi.GroupConfig()
+        cfg.struct_size = C.sizeof(capi.GroupConfig)
+        cfg.source = int(src)
+        cfg.n_groups = int(n_groups)
+        cfg.cell_group = capi.np_ptr(cg, C.c_int32)
+        res = capi.Result()
+        self._check(self.lib.xck_group_counts(self.h, C.byref(cfg), C.byref(res)), "xck_group_counts")
+        out = {}
+        if src == capi.XCK_GROUP_SRC_RESULT and self.mode & XCK_MODE_BASEFC:
+            out["count"] = res.count.to_numpy(copy)
+        if src == capi.XCK_GROUP_SRC_SNP or self.mode & XCK_MODE_BAF:
+            out.update(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
+        return out
+
     def result_device(self):
         """Device-resident copy of the last finish(): {name: (device_ptr_of_[row|col|val], nnz)}."""
         res = capi.Result()
@@ -431,16 +459,16 @@ class Engine(object):
         if rc != 0:
             raise XckError("xck_write_mtx failed (%d)" % rc)
 
-    def write_mtx_arrays(self, path, coo, row_map, n_rows_out):
+    def write_mtx_arrays(self, path, coo, row_map, n_rows_out, n_cols=None):
         """Same writer for (row, col, val) arrays that did not come from this engine's last
-        finish() - e.g. the blocks gathered from all ranks."""
+        finish() - e.g. the blocks gathered from all ranks.  n_cols: the column count of the header (None = the engine's cells)."""
         row, col, val = (np.ascontiguousarray(a, dtype=np.int32) for a in coo)
         c = capi.Coo()
         c.nnz = len(row)
         c.row, c.col, c.val = (capi.np_ptr(a, C.c_int32) for a in (row, col, val))
         rm = np.ascontiguousarray(row_map, dtype=np.int32)
         rc = self.lib.xck_write_mtx(path.encode(), C.byref(c), rm.ctypes.data_as(C.POINTER(C.c_int32)),
-                                    int(n_rows_out), self.n_cells)
+                                    int(n_rows_out), self.n_cells if n_cols is None else int(n_cols))
         if rc != 0:
             raise XckError("xck_write_mtx failed (%d)" % rc)
 

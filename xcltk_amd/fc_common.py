@@ -308,14 +308,90 @@ def output_row_map(dist, n, all_reg, *row_arrays):
     return row_map_from_rows(n, *row_arrays)
 
 
-def write_mtx(eng, dist, path, coo_k, rm, n_rows_out):
+def write_mtx(eng, dist, path, coo_k, rm, n_rows_out, n_cols=None):
     """One matrix file: written by this process, or - sharded output - by all ranks together, each the lines of its own rows
-    (shard.write_mtx_sharded; collective call)."""
+    (shard.write_mtx_sharded; collective call).  n_cols: the column count of the header; None = the engine's cells."""
     if dist is not None and dist.active and dist.sharded_output:
         from .shard import write_mtx_sharded
-        write_mtx_sharded(path, coo_k, rm, dist.row_owner, n_rows_out, eng.n_cells, dist.rank, dist.all_reduce_np, dist.barrier, eng.lib)
+        write_mtx_sharded(path, coo_k, rm, dist.row_owner, n_rows_out, eng.n_cells if n_cols is None else int(n_cols), dist.rank, dist.all_reduce_np,
+                          dist.barrier, eng.lib)
     else:
-        eng.write_mtx_arrays(path, coo_k, rm, n_rows_out)
+        eng.write_mtx_arrays(path, coo_k, rm, n_rows_out, n_cols=n_cols)
+
+
+# ----------------------------------------------------------------------------- cell groups (XCK_CELL_GROUPS)
+def parse_cell_groups(lines, cells):
+    """The group file of XCK_CELL_GROUPS as a pure function.  lines: an iterable of `name<TAB>group` lines without a header (blank
+    lines are skipped); cells: the run's barcodes or sample ids in column order.  Groups are numbered by first appearance in the
+    file, whether or not the line names a cell of the run, so a file numbers its groups the same way for every run; names that
+    are not among `cells` are ignored and counted; cells the file does not name get -1.  -> (group names in column order, int32
+    array [len(cells)] of group indices, number of ignored names).  ValueError for a line without two fields, a name with two
+    different groups, or more than XCK_GROUP_MAX groups."""
+    from .capi import XCK_GROUP_MAX
+    col = {c: i for i, c in enumerate(cells)}
+    names, gidx, seen = [], {}, {}
+    cell_group = np.full(len(cells), -1, dtype=np.int32)
+    n_ignored = 0
+    for nl, line in enumerate(lines, 1):
+        line = line.rstrip("\r\n")
+        if not line.strip():
+            continue
+        parts = line.split("\t")
+        if len(parts) < 2 or not parts[0] or not parts[1]:
+            raise ValueError("cell group file: line %d is not name<TAB>group" % nl)
+        name, grp = parts[0], parts[1]
+        if name in seen:
+            if seen[name] != grp:
+                raise ValueError("cell group file: '%s' is in two groups ('%s' and '%s')" % (name, seen[name], grp))
+            continue
+        seen[name] = grp
+        if grp not in gidx:
+            gidx[grp] = len(names)
+            names.append(grp)
+            if len(names) > XCK_GROUP_MAX:
+                raise ValueError("cell group file: more than %d groups" % XCK_GROUP_MAX)
+        if name in col:
+            cell_group[col[name]] = gidx[grp]
+        else:
+            n_ignored += 1
+    return names, cell_group, n_ignored
+
+
+def load_cell_groups(cells, log_prefix="[engine]"):
+    """(group names, cell -> group array) of the file XCK_CELL_GROUPS names, or None when the knob is unset.  ValueError as
+    parse_cell_groups, or when the file does not exist - raised where the front-ends resolve their inputs, before a BAM is opened."""
+    fn = os.environ.get("XCK_CELL_GROUPS", "")
+    if not fn:
+        return None
+    if not os.path.isfile(fn):
+        raise ValueError("cell group file '%s' does not exist." % fn)
+    with zopen(fn, "rt") as fp:
+        names, cell_group, n_ignored = parse_cell_groups(fp, list(cells))
+    info("%s cell groups: %d groups, %d of %d cells grouped, %d names ignored (not cells of this run)" %
+         (log_prefix, len(names), int((cell_group >= 0).sum()), len(cell_group), n_ignored))
+    return names, cell_group
+
+
+def group_output_off(dist, log_prefix="[engine]"):
+    """True (and one log line) where a multi-GPU run gathers its result on one rank: that form writes no group files."""
+    if dist is not None and dist.active and not dist.sharded_output:
+        info("%s XCK_CELL_GROUPS: the gathered output form (XCK_DIST_GATHER=1 / gather=True) writes no group files." % log_prefix)
+        return True
+    return False
+
+
+def write_group_matrices(eng, dist, groups, names_fn, mtx_fns, rm, n_rows_out, source="result", log_prefix="[engine]"):
+    """The engine's matrices summed per cell group (Engine.group_counts) -> names_fn (group names, one per line) and mtx_fns
+    ({"count": path} or {"ad": .., "dp": .., "oth": ..}), in the rows `rm` gives the cell files.  groups: load_cell_groups() - None
+    (XCK_CELL_GROUPS unset): nothing is launched or written.  Sharded output: a collective call, every rank sums its own rows."""
+    if groups is None or group_output_off(dist, log_prefix):
+        return
+    names, cell_group = groups
+    got = eng.group_counts(cell_group, n_groups=max(len(names), 1), source=source, copy=False)
+    if is_writer_rank():
+        write_samples(names_fn, names)
+    for k, fn in mtx_fns.items():
+        write_mtx(eng, dist, fn, got[k], rm, n_rows_out, n_cols=len(names))
 
 
 def read_summary_text(fate, n_ranks=1, cut_contigs=0):

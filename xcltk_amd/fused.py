@@ -39,8 +39,12 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
     conf.min_count, conf.min_maf, conf.no_dup_hap = min_count, min_maf, no_dup_hap
     conf.min_mapq, conf.min_len, conf.incl_flag, conf.no_orphan = min_mapq, min_len, incl_flag, no_orphan
     conf.excl_flag = -1 if excl_flag is None else excl_flag
-    if baf_prepare(conf) < 0:
-        error("errcode -2")
+    try:
+        if baf_prepare(conf) < 0:
+            error("errcode -2")
+            return -1
+    except ValueError as e:                              # (a bad XCK_CELL_GROUPS file)
+        error(str(e))
         return -1
     regions, snps = conf.reg_list, conf.snp_list
     fc_dir = os.path.join(out_dir, "basefc")
@@ -72,6 +76,11 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
         if fcc.is_writer_rank():
             fcc.write_region_tsv(os.path.join(fc_dir, "features.tsv"), regions, rm)
         fcc.write_mtx(eng, dist, os.path.join(fc_dir, "matrix.mtx"), coo["count"], rm, int(rm.max()) if n else 0)
+        groups = conf.cell_groups                         # (XCK_CELL_GROUPS only; a gathered result writes no group files: one log line)
+        if groups is not None and fcc.group_output_off(dist, "[fused]"):
+            groups = None
+        fcc.write_group_matrices(eng, dist, groups, os.path.join(fc_dir, "groups.tsv"), {"count": os.path.join(fc_dir, "matrix.groups.mtx")}, rm,
+                                 int(rm.max()) if n else 0, log_prefix="[fused]")
         rm = fcc.output_row_map(dist, n, baf_output_all_reg, coo["dp"][0], coo["oth"][0])
         nr = int(rm.max()) if n else 0
         if fcc.is_writer_rank():
@@ -79,6 +88,9 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
         fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, nr)
         fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, nr)
         fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, nr)
+        pre = os.path.join(conf.out_dir, conf.out_prefix)
+        fcc.write_group_matrices(eng, dist, groups, pre + "groups.tsv", {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"},
+                                 rm, nr, log_prefix="[fused]")
     finally:
         eng.close()
     info("fused basefc + baf done in %.2fs" % (time.time() - t0))

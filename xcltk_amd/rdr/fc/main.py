@@ -151,6 +151,7 @@ def prepare_config(conf):
     info("count %d regions in %d single cells." % (len(conf.reg_list), len(conf.samples)))
     if fcc.resolve_tags(conf) < 0:
         return -1
+    conf.cell_groups = fcc.load_cell_groups(conf.samples)     # (XCK_CELL_GROUPS only; ValueError for a bad file, before any BAM is opened)
     if fcc.is_writer_rank():
         fcc.write_samples(conf.out_sample_fn, conf.samples)
     return 0
@@ -172,6 +173,9 @@ def fc_core(conf):
             if fcc.is_writer_rank():
                 fcc.write_region_tsv(conf.out_region_fn, regions, rm)
             fcc.write_mtx(eng, dist, conf.out_mtx_fn, coo["count"], rm, int(rm.max()) if len(rm) else 0)
+            pre = os.path.join(conf.out_dir, conf.out_prefix)
+            fcc.write_group_matrices(eng, dist, conf.cell_groups, pre + "groups.tsv", {"count": pre + "matrix.groups.mtx"}, rm,
+                                     int(rm.max()) if len(rm) else 0)   # (XCK_CELL_GROUPS only)
         if conf.debug > 0:
             info("engine stats: %s" % eng.stats())
     finally:
