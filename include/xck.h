@@ -27,13 +27,20 @@
  *   XCK_PILEUP_LGG=<l>                    at most 2^l cell groups per SNP in the pileup partitions (default 10)
  *   XCK_HIT_CAP0, XCK_HIT_SLACK           first capacity / head room of the hit accumulators (tests: reach the overflow-replay path)
  *   XCK_PUSH_STAGE=0|1, XCK_PUSH_STAGE_BYTES   xck_push_batch: packed one-copy form always / never / below this size (default 2 MB)
- *   XCK_GPU_INFLATE=auto|<percent>|0      share of the BGZF chunks that xck_ingest_bam inflates on the handle's GPU (csrc/inflate_dev.hip; record walk and
- *                                         parse stay on the host).  auto (the default): files of at least XCK_GPU_INFLATE_MIN_MB (96) compressed MB keep
+ *   XCK_GPU_INFLATE=auto|<percent>|0      share of the BGZF chunks that xck_ingest_bam inflates on the handle's GPU (csrc/inflate_dev.hip; the record
+ *                                         walk and parse of these chunks: XCK_GPU_PARSE).  auto (the default): files of at least XCK_GPU_INFLATE_MIN_MB (96) compressed MB keep
  *                                         XCK_GPU_INFLATE_DEPTH (10) chunks on the device and leave the rest to the host pool, XCK_GPU_INFLATE_RING (12)
  *                                         chunks in flight in all; <percent>: a fixed share; 0 = host only.  XCK_GPU_INFLATE_FREE_CUS (32): CUs the
  *                                         inflate streams never use.  Bit-identical results either way (a block the kernel does not finish, and every
  *                                         chunk after a runtime error, is inflated by the host); off for handles without a device and with XCK_F_VERIFY_CRC
  *                                         alone (XCK_F_DEVICE_CRC keeps it on).
+ *   XCK_GPU_PARSE=auto|0                  auto (the default): the records of the GPU-inflated chunks are walked and parsed on the device too
+ *                                         (csrc/parse_dev.hip) and never visit the host - where the handle drives a GPU, the key is a UMI tag, every
+ *                                         barcode is at most 18 bytes and the call sets no max_records.  A chunk the device cannot finish (a record that
+ *                                         straddles blocks, a UMI that has to be interned, a damaged block, bytes carried in from the chunk before, a
+ *                                         reader used through xck_bam_next_batch) takes the host path, which also reports every error; after four such
+ *                                         chunks in a row the reader stops asking.  0: walk and parse on the host.  Bit-identical results either way;
+ *                                         xck_decode_stats.gpu_parse_chunks / gpu_parse_fallbacks count them.
  *   XCK_VERIFY_CRC=0|host|device          check the CRC32 of every BGZF block the record decoder inflates, as if the handle had been made with
  *                                         XCK_F_VERIFY_CRC (host: the GPU share of the inflate is off) or XCK_F_DEVICE_CRC (device: the GPU share checks
  *                                         its own blocks) - for front-ends and benchmarks whose calls do not carry the flags.  0 (the default) adds
@@ -265,6 +272,9 @@ typedef struct xck_decode_stats {
     int64_t crc_mismatch_device;      /* blocks the kernel found with a CRC32 that differs from the footer's                      */
     int64_t crc_device_host_disagree; /* ... of which the host's check passed (the host's bytes are used; 0 unless the device erred) */
     int64_t gpu_path_given_up;        /* readers whose GPU share of the inflate was turned off by a runtime error or lack of memory */
+    /* appended (a caller with the shorter struct gets the fields above): */
+    int64_t gpu_parse_chunks;         /* GPU-inflated chunks whose records were walked and parsed on the device too (XCK_GPU_PARSE) */
+    int64_t gpu_parse_fallbacks;      /* device-walked chunks that took the host path after all (straddling record, UMI to intern, ...) */
 } xck_decode_stats;
 
 /* Where the reads of ONE pipeline went, since the last xck_reset (handles made with XCK_F_READ_FATE; additive, ABI 3 is unchanged).

@@ -13,6 +13,7 @@
 #include "../../include/xck.h"
 #include "../../xcltk_amd/csrc/xck_internal.h"
 #include "../../xcltk_amd/csrc/inflate_dev.h"
+#include "../../xcltk_amd/csrc/parse_dev.h"
 
 namespace xck {   // what engine.hip provides; never reached through a decode-only handle
 int  engine_create(const xck_config*, xck_engine*, EngineImpl**) { return XCK_E_ARG; }
@@ -37,7 +38,12 @@ int  engine_device(const xck_engine*) { return -1; }                          //
 GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }
 void gpu_inflate_slot_destroy(GpuInflateSlot*) {}
 bool gpu_inflate_slot_reserve(GpuInflateSlot*, size_t, size_t, size_t) { return false; }
-int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool) { return -1; }
+int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool, const DpWalk*) { return -1; }
+// device walk + parse (csrc/parse_dev.hip): never reached without a device chunk
+int  dev_parse_copy_out(GpuInflateSlot*, size_t) { return -1; }
+void* dev_parse_upload(int, const void*, size_t, const void*, size_t) { return nullptr; }
+void dev_parse_free(int, void*) {}
+int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int) { return XCK_E_ARG; }
 int  gpu_inflate_slot_wait(GpuInflateSlot*) { return -1; }
 bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
 // stand-in for the engine's block push (called on the decoder's push thread): touches everything the batches claim to own

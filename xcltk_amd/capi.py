@@ -121,7 +121,8 @@ class DecodeStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved0", C.c_uint32),
                 ("gpu_inflate_chunks", C.c_int64), ("gpu_inflate_blocks", C.c_int64), ("gpu_blocks_left_to_host", C.c_int64),
                 ("crc_blocks_device", C.c_int64), ("crc_blocks_host", C.c_int64), ("crc_mismatch_device", C.c_int64),
-                ("crc_device_host_disagree", C.c_int64), ("gpu_path_given_up", C.c_int64)]
+                ("crc_device_host_disagree", C.c_int64), ("gpu_path_given_up", C.c_int64),
+                ("gpu_parse_chunks", C.c_int64), ("gpu_parse_fallbacks", C.c_int64)]
 
 
 class ReadFate(C.Structure):

@@ -54,6 +54,7 @@ Knobs xck::Knobs::from_env() {
     k.push_stage = (int)num("XCK_PUSH_STAGE", -1);
     k.push_stage_bytes = num("XCK_PUSH_STAGE_BYTES", 2ll << 20);
     k.gpu_inflate_pct = (!*str("XCK_GPU_INFLATE") || !strcmp(str("XCK_GPU_INFLATE"), "auto")) ? -1 : (int)std::max(0ll, std::min(100ll, num("XCK_GPU_INFLATE", 0)));
+    k.gpu_parse = strcmp(str("XCK_GPU_PARSE"), "0") != 0;
     k.gpu_inflate_depth = (int)std::max(1ll, std::min(10ll, num("XCK_GPU_INFLATE_DEPTH", 10)));
     k.gpu_inflate_ring = (int)num("XCK_GPU_INFLATE_RING", 12);
     k.gpu_inflate_min_mb = (int)std::max(0ll, num("XCK_GPU_INFLATE_MIN_MB", 96));
@@ -245,10 +246,12 @@ int xck_reset(xck_engine* e) {
 
 int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
     if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
-    if (out->struct_size < sizeof(xck_decode_stats)) { set_thread_error("xck_decode_stats.struct_size mismatch (ABI)"); return XCK_E_ARG; }
+    if (out->struct_size < offsetof(xck_decode_stats, gpu_parse_chunks)) { set_thread_error("xck_decode_stats.struct_size mismatch (ABI)"); return XCK_E_ARG; }
     int64_t* f[DS_N] = { &out->gpu_inflate_chunks, &out->gpu_inflate_blocks, &out->gpu_blocks_left_to_host, &out->crc_blocks_device, &out->crc_blocks_host,
-                         &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up };
-    for (int k = 0; k < DS_N; k++) *f[k] = e->dstat[k].load();
+                         &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up, &out->gpu_parse_chunks, &out->gpu_parse_fallbacks };
+    // (the last two were appended: a caller built before them passes the shorter struct and gets what it knows)
+    const int n = out->struct_size >= sizeof(xck_decode_stats) ? DS_N : DS_PARSE_CHUNKS;
+    for (int k = 0; k < n; k++) *f[k] = e->dstat[k].load();
     return XCK_OK;
 }
 

@@ -28,6 +28,7 @@
 #include "xck_internal.h"
 #include "inflate_fast.h"
 #include "inflate_dev.h"
+#include "parse_dev.h"
 
 namespace xck {
 
@@ -366,6 +367,9 @@ struct Chunk {
     bool gpu = false; std::atomic<int> copy_left{0}; std::atomic<int> gpu_rc{0}; size_t in_total = 0;
     std::atomic<int> launched{0};      // the last gather task has handed the chunk to the device (gpu_rc says how that went)
     bool stage2 = false;               // the walk tasks that follow the device's inflate have been queued
+    // device walk + parse (csrc/parse_dev.hip): the chunk was launched with the walk behind its inflate and nothing stored to the host
+    // (dparse); its summaries came back clean, so no walk task was queued (dp_ok) - until something sends it down the host path after all
+    bool dparse = false, dp_ok = false;
 };
 
 struct PendingBatch { int32_t contig; int64_t r0, r1; uint64_t ordinal_base; };
@@ -390,7 +394,8 @@ struct ContigMap {
 struct DecodeTimes {
     std::atomic<uint64_t> inflate{0}, walk{0}, parse{0};                 // ns, summed over pool threads
     uint64_t wait_inflate = 0, sched = 0, stitch = 0, layout = 0, wait_parse = 0, wait_push = 0;   // ns, coordinating thread
-    uint64_t push = 0;                                                   // ns, push thread (engine_push_block)
+    uint64_t push = 0;                                                   // ns, push thread (engine_push_block, engine_push_parsed)
+    uint64_t push_parsed = 0, dp_layout = 0, dp_copy_out = 0;            // ns: engine_push_parsed alone (push thread); summaries -> batches (coordinator); fallback copies d_out -> h_out
     uint64_t chunks = 0, slow_chunks = 0; std::chrono::steady_clock::time_point t_open;
 };
 static inline uint64_t ns_since(std::chrono::steady_clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
@@ -475,13 +480,16 @@ struct ChunkJob {
     std::atomic<int> parsed{0};        // set by the push thread once the parse tasks have ended: the coordinator may take the ring chunk back
     bool released = true;              // (coordinator) the ring chunk was taken back, or was never held
     std::atomic<int> queued{0};        // with the push thread: set by Pusher::submit, cleared when the job's push has ended
+    // a chunk walked on the device: no parse tasks, the push thread launches the parse kernel (engine_push_parsed) - or, if that kernel
+    // flags the chunk, takes it down the host path itself (redo_on_host), for which it needs what the coordinator knew
+    bool dev = false; xck_bam* b = nullptr; DpChunkLayout lay; ContigMap cm; xck_ingest_opts opts; int64_t rec_before = 0;
 };
 struct Pusher {
     static constexpr int MAXQ = PUSH_Q; // jobs the coordinator may run ahead
     std::thread th; std::mutex mu; std::condition_variable cv;
     bool stop = false; ChunkJob* q[MAXQ] = {}; int qh = 0, qn = 0;
     int rc = 0; std::string err;       // first failure (parse flags or push); later jobs are waited for, not pushed
-    uint64_t push_ns = 0, parse_wait_ns = 0;
+    uint64_t push_ns = 0, parse_wait_ns = 0, push_parsed_ns = 0;
     void run();
     Pusher() { th = std::thread([this] { run(); }); }
     // blocks while MAXQ jobs are outstanding; returns the first failure so far (the job is queued regardless: its parse must be waited for)
@@ -500,6 +508,10 @@ struct GpuShare {
     std::vector<GpuInflateSlot*> free_slots;                             // slots of consumed chunks, reused before a new one is made
     int max_held = 10;                                                   // device chunks in the ring at a time (in flight + inflated, not yet consumed) = slots this reader ever holds
     uint64_t chunks = 0, blocks = 0, left_blocks = 0, wait_ns = 0, copy_ns = 0;
+    // device walk + parse of the device chunks (XCK_GPU_PARSE): whether the handle and its barcode list allow it, the contig tables in
+    // device memory (uploaded anew when a call brings other tables; the old ones live until the reader closes: walks in flight read them)
+    bool parse = false; std::atomic<bool> parse_off{false}; std::atomic<int> fb_row{0};
+    std::vector<int32_t> cm_host; int32_t* d_cm = nullptr; bool cm_tend = false; std::vector<void*> d_cm_all;
 };
 struct CallerBinding;
 struct xck_bam {
@@ -544,10 +556,8 @@ static void soa_free(HostSoA& s) {
 }
 // carve the columns of a chunk with n_reads kept records out of the block (growing it if needed)
 static bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq) {
-    auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t o_umi = 0, o_pos = o_umi + up(n_reads * 8), o_cell = o_pos + up(n_reads * 4), o_cgo = o_cell + up(n_reads * 4),
-                 o_sqo = o_cgo + up((n_reads + 1) * 4), o_cig = o_sqo + up((n_reads + 1) * 4), o_flag = o_cig + up(n_cig * 4),
-                 o_mapq = o_flag + up(n_reads * 2), o_seq = o_mapq + up(n_reads), total = o_seq + up(n_seq);
+    const SoaLayout l = soa_layout(n_reads, n_cig, n_seq);                // (parse_dev.h: the parse kernel writes the same block)
+    const size_t total = l.total;
     if (total > s.cap) {
         if (s.fence) fence_wait(s.fence);
         if (s.base) { if (s.pinned) pinned_free(s.base); else free(s.base); }
@@ -558,9 +568,9 @@ static bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq) 
         s.cap = c;
     }
     s.used = total;
-    s.umi = (uint64_t*)(s.base + o_umi); s.pos = (int32_t*)(s.base + o_pos); s.cell = (int32_t*)(s.base + o_cell);
-    s.cig_off = (uint32_t*)(s.base + o_cgo); s.seq_off = (uint32_t*)(s.base + o_sqo); s.cigar = (uint32_t*)(s.base + o_cig);
-    s.flag = (uint16_t*)(s.base + o_flag); s.mapq = s.base + o_mapq; s.seq = s.base + o_seq;
+    s.umi = (uint64_t*)(s.base + l.o_umi); s.pos = (int32_t*)(s.base + l.o_pos); s.cell = (int32_t*)(s.base + l.o_cell);
+    s.cig_off = (uint32_t*)(s.base + l.o_cgo); s.seq_off = (uint32_t*)(s.base + l.o_sqo); s.cigar = (uint32_t*)(s.base + l.o_cig);
+    s.flag = (uint16_t*)(s.base + l.o_flag); s.mapq = s.base + l.o_mapq; s.seq = s.base + l.o_seq;
     return true;
 }
 
@@ -669,7 +679,7 @@ static int bam_open_impl(const char* path, int n_threads, xck_bam** out, char* e
 
 void xck_bam_close(xck_bam* b) {
     if (!b) return;
-    if (b->pusher) { b->pusher->wait_idle(); b->tm.push += b->pusher->push_ns; b->tm.wait_parse += b->pusher->parse_wait_ns; delete b->pusher; b->pusher = nullptr; }
+    if (b->pusher) { b->pusher->wait_idle(); b->tm.push += b->pusher->push_ns; b->tm.wait_parse += b->pusher->parse_wait_ns; b->tm.push_parsed += b->pusher->push_parsed_ns; delete b->pusher; b->pusher = nullptr; }
     for (auto& j : b->jobs) j.tg.wait();
     delete b->scanner; b->scanner = nullptr;
     for (auto& c : b->ch) c.tg.wait();
@@ -681,9 +691,15 @@ void xck_bam_close(xck_bam* b) {
         fprintf(stderr, "[xck] ingest %s: GPU share of the inflate: %llu chunks / %llu blocks on the device (%llu of them finished by the host), gather %.0f ms of pool time, coordinator waited %.0f ms%s\n",
                 b->path.c_str(), (unsigned long long)b->gi.chunks, (unsigned long long)b->gi.blocks, (unsigned long long)b->gi.left_blocks, b->gi.copy_ns * 1e-6, b->gi.wait_ns * 1e-6,
                 b->gi.broken ? "; the device path was given up (runtime error / no memory)" : "");
+    if (getenv("XCK_DEBUG_TIMING") && (b->dstat[DS_PARSE_CHUNKS].load() || b->dstat[DS_PARSE_FALLBACKS].load()))
+        fprintf(stderr, "[xck] ingest %s: device walk + parse: %lld chunks, %lld fallbacks to the host path%s | coordinator ms: summaries -> batches %.0f | push thread ms: parse kernel + launches %.0f | fallback copies ms: %.0f\n",
+                b->path.c_str(), (long long)b->dstat[DS_PARSE_CHUNKS].load(), (long long)b->dstat[DS_PARSE_FALLBACKS].load(), b->gi.parse_off.load() ? " (given up for this file)" : "",
+                b->tm.dp_layout * 1e-6, b->tm.push_parsed * 1e-6, b->tm.dp_copy_out * 1e-6);
     for (auto& gs : b->gi.slot) { park_gpu_slot(gs); gs = nullptr; }
     for (auto& gs : b->gi.free_slots) park_gpu_slot(gs);
     b->gi.free_slots.clear();
+    for (void* p : b->gi.d_cm_all) dev_parse_free(b->gi.device, p);   // (after the slots were waited for: no walk reads the tables any more)
+    b->gi.d_cm_all.clear();
     if (b->numa_bound && b->pool) b->pool->set_affinity(b->old_affinity);   // a parked pool goes back to the full mask
     if (getenv("XCK_DEBUG_TIMING") && b->tm.chunks) {
         const DecodeTimes& t = b->tm; const double ms = 1e-6;
@@ -823,10 +839,42 @@ static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* w
 // position windows: the reference whose index range the chunk belongs to (ContigMap::only_tid), -1 without windows
 static int32_t range_only_tid(const xck_bam* b, const Chunk& c) { return b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1; }
 
+// XCK_GPU_PARSE: do the device chunks scheduled now get the walk behind their inflate?  begin_decode said whether the reader may at all
+// (gi.parse); a record limit keeps this call's chunks on the host path; the contig tables the walk applies go to device memory here.
+static bool device_parse_now(xck_bam* b, const ContigMap& cm, const xck_ingest_opts* o) {
+    GpuShare& gi = b->gi;
+    if (!gi.on || !gi.parse || gi.broken || gi.parse_off.load() || o->max_records > 0 || cm.n_refs <= 0 || !cm.t2c) return false;
+    const size_t n = (size_t)cm.n_refs; const bool tend = cm.t_end != nullptr;
+    const bool same = gi.d_cm && gi.cm_tend == tend && gi.cm_host.size() == n * (tend ? 2 : 1) && memcmp(gi.cm_host.data(), cm.t2c, n * 4) == 0 &&
+                      (!tend || memcmp(gi.cm_host.data() + n, cm.t_end, n * 4) == 0);
+    if (!same) {
+        void* d = dev_parse_upload(gi.device, cm.t2c, n * 4, cm.t_end, tend ? n * 4 : 0);
+        if (!d) { gi.parse_off = true; return false; }
+        gi.cm_host.assign(cm.t2c, cm.t2c + n); if (tend) gi.cm_host.insert(gi.cm_host.end(), cm.t_end, cm.t_end + n);
+        gi.d_cm = (int32_t*)d; gi.cm_tend = tend; gi.d_cm_all.push_back(d);
+    }
+    return true;
+}
+// a device-walked chunk goes down the host path after all: counted, and after four in a row the reader stops asking for the walk (a
+// file of unaligned blocks, or of UMIs the device cannot code, must not pay for both paths chunk after chunk)
+static void count_parse_fallback(xck_bam* b) {
+    b->dstat[DS_PARSE_FALLBACKS].fetch_add(1, std::memory_order_relaxed);
+    if (b->gi.fb_row.fetch_add(1) + 1 >= 4) b->gi.parse_off.store(true);
+}
+// ... for which its inflated bytes, so far in HBM only, are copied to the slot's host block: from there on it is a device chunk of old
+static bool fallback_copy_out(xck_bam* b, Chunk& c, GpuInflateSlot* gs) {
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool ok = dev_parse_copy_out(gs, c.usize) == 0;
+    __atomic_fetch_add(&b->tm.dp_copy_out, ns_since(t0), __ATOMIC_RELAXED);
+    c.dparse = false; c.dp_ok = false;
+    return ok;
+}
+
 // take the next plan from the scanner and start inflating it into c (asynchronous); the contig map lets the walk tasks
 // prepare the output layout of their own records
-static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool crc_on_device, const ContigMap cm_in, bool want_seq) {
+static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool crc_on_device, const ContigMap cm_in, bool want_seq, bool dev_parse) {
     c.blocks.clear(); c.usize = 0; c.valid = false; c.failed = false; c.err.clear(); c.new_range = false; c.first_skip = 0; c.gpu = false; c.gpu_rc = 0; c.launched = 0; c.stage2 = false;
+    c.dparse = false; c.dp_ok = false;
     if (b->scan_end) return;
     ChunkPlan pl = b->scanner->next();
     if (pl.end) { b->scan_end = true; return; }
@@ -857,12 +905,13 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool c
                 else gi.slot[ci] = take_gpu_slot(gi.device, gi.free_cus, gi.verbose && !gi.chunks);
             }
             gs = gi.slot[ci];
+            if (gs && dev_parse) gs->parse = true;                          // (the slot then holds the walk's buffers too, from here on)
             if (gs && gi.inflight[ci]) { gpu_inflate_slot_wait(gs); gi.inflight[ci] = false; }   // (a chunk that was dropped unconsumed)
             if (!gs || !gpu_inflate_slot_reserve(gs, tin + 8, usz + 8, nb)) { gi.broken = true; gs = nullptr; }   // no device memory: the host does it all from here on
             else c.in_total = tin;
         }
     }
-    if (gs) { c.gpu = true; c.ubase = gs->h_out; gi.inflight[ci] = true; }
+    if (gs) { c.gpu = true; c.ubase = gs->h_out; gi.inflight[ci] = true; c.dparse = dev_parse; }
     else { if (c.ubuf.size() < usz + 8) c.ubuf.resize(usz + 8); c.ubase = c.ubuf.data(); }
     const size_t per = std::max<size_t>(1, (nb + (size_t)b->n_threads * 4 - 1) / ((size_t)b->n_threads * 4));
     const size_t n_parts = (nb + per - 1) / per;
@@ -888,12 +937,15 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool c
         Chunk* cp = &c; const uint8_t* map = b->map; WalkPart* wpp = &wp; DecodeTimes* tmp_ = &b->tm; std::atomic<int64_t>* ds = b->dstat;
         if (!gs) { c.tg.later([cp, map, verify_crc, wpp, tmp_, cm, want_seq, ds] { run_part(cp, map, verify_crc, wpp, tmp_, cm, want_seq, nullptr, ds); }); continue; }
         GpuShare* gip = &gi; const size_t nb_ = nb, usz_ = usz;
-        c.tg.later([cp, map, i0, i1, gs, gip, nb_, usz_, crc_on_device] {
+        // (device walk behind the inflate: the contig map as run_part applies it, its tables in device memory)
+        const bool walk = c.dparse;
+        const DpWalk dw{(uint32_t)skip0, DpContigMap{gi.d_cm, gi.cm_tend && gi.d_cm ? gi.d_cm + cm.n_refs : nullptr, cm.n_refs, cm.only_tid}, want_seq};
+        c.tg.later([cp, map, i0, i1, gs, gip, nb_, usz_, crc_on_device, walk, dw] {
             const auto t_a = std::chrono::steady_clock::now();
             for (size_t i = i0; i < i1; i++) memcpy(gs->h_in + gs->h_bl[i].in_off, map + cp->blocks[i].coff + cp->blocks[i].data_off, cp->blocks[i].data_len);
             __atomic_fetch_add(&gip->copy_ns, ns_since(t_a), __ATOMIC_RELAXED);
             if (cp->copy_left.fetch_sub(1) == 1) {                         // the chunk's compressed bytes are gathered: hand it to the device
-                const int rc = gpu_inflate_slot_launch(gs, cp->in_total, usz_, nb_, crc_on_device);
+                const int rc = gpu_inflate_slot_launch(gs, cp->in_total, usz_, nb_, crc_on_device, walk ? &dw : nullptr);
                 cp->gpu_rc = rc; cp->launched.store(1, std::memory_order_release);
             }
         });
@@ -1078,7 +1130,7 @@ static ChunkJob* take_job(xck_engine* e, xck_bam* b) {
     if (j.queued.load(std::memory_order_acquire) || !j.released) { b->err = "internal: the job slot of this chunk is still in use"; return nullptr; }
     b->n_jobs++; b->cur = &j;
     if (j.soa.fence) fence_wait(j.soa.fence);                           // the H2D copy that last read this block has completed
-    j.e = e; j.flags.store(0); j.parsed.store(0); j.ring_idx = -1; j.batches.clear();
+    j.e = e; j.flags.store(0); j.parsed.store(0); j.ring_idx = -1; j.batches.clear(); j.dev = false;
     return &j;
 }
 // what a chunk's parse tasks reported (flags 1 / 2: parse_record; a task that threw) -> error code and text, 0 if nothing.  Call after tg.wait().
@@ -1100,6 +1152,7 @@ static void fill_batch(const HostSoA& s, const PendingBatch& pb, bool want_seq, 
     if (want_seq) { bt->seq_off = s.seq_off + pb.r0; bt->seq = s.seq; }
 }
 
+static int redo_on_host(ChunkJob* j, std::string* msg);
 void Pusher::run() {
     std::unique_lock<std::mutex> lk(mu);
     for (;;) {
@@ -1110,11 +1163,26 @@ void Pusher::run() {
         lk.unlock();
         std::string msg;
         auto t0 = std::chrono::steady_clock::now();
-        j->tg.wait();
-        parse_wait_ns += ns_since(t0);
-        int r = parse_error(*j, &msg);
+        int r = 0; bool host_chunk = !j->dev;
+        if (j->dev && !failed) {
+            // a chunk the device walked: the parse kernel writes its SoA block into the engine's staging slot and the batches follow - no
+            // parse task, no copy.  A chunk that kernel flags (1) takes the host path here, late but in file order.
+            xck_bam* b = j->b; GpuInflateSlot* gs = b->gi.slot[j->ring_idx];
+            try { r = xck::engine_push_parsed(j->e, gs, b->ch[j->ring_idx].blocks.size(), j->lay.max_rec, j->lay.n_out, j->lay.n_cig, j->lay.n_seq, j->opts.sample, j->lay.batches.data(), (int)j->lay.batches.size()); }
+            catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
+            push_parsed_ns += ns_since(t0); push_ns += ns_since(t0);
+            if (r == 1) { count_parse_fallback(b); r = redo_on_host(j, &msg); host_chunk = r == 0; }
+            else if (r) msg = j->e->err;
+            else { b->dstat[DS_PARSE_CHUNKS].fetch_add(1, std::memory_order_relaxed); b->gi.fb_row.store(0); }
+            t0 = std::chrono::steady_clock::now();
+        }
+        if (host_chunk) {
+            j->tg.wait();
+            parse_wait_ns += ns_since(t0);
+            r = parse_error(*j, &msg);
+        }
         j->parsed.store(1, std::memory_order_release);
-        if (!failed && !r && !j->batches.empty()) {
+        if (host_chunk && !failed && !r && !j->batches.empty()) {
             // the whole chunk crosses PCIe as ONE block; its batches are slices of the block (fused handles: both pipelines read the same copy)
             t0 = std::chrono::steady_clock::now();
             xck_engine* e = j->e; HostSoA& s = j->soa;
@@ -1131,6 +1199,13 @@ void Pusher::run() {
         j->queued.store(0, std::memory_order_release);
         cv.notify_all();
     }
+}
+
+// the walk tasks of a device chunk (and the inflate of what the device left of it), ahead of the later chunks' inflate tasks
+static void queue_host_walk(xck_engine* e, xck_bam* b, Chunk& c, ContigMap cm, const int32_t* st) {
+    Chunk* cp = &c; const uint8_t* map = b->map; DecodeTimes* tmp_ = &b->tm; const bool want_seq = e->dec.want_seq, crc = e->dec.verify_crc; std::atomic<int64_t>* ds = b->dstat;
+    for (WalkPart& wp : c.parts) { WalkPart* wpp = &wp; c.tg.later([cp, map, crc, wpp, tmp_, cm, want_seq, st, ds] { run_part(cp, map, crc, wpp, tmp_, cm, want_seq, st, ds); }); }
+    c.tg.flush(*b->pool, true);
 }
 
 // A device chunk whose inflate is over: whatever the device did not inflate - single blocks with a non-zero status, or the whole chunk
@@ -1150,6 +1225,12 @@ static void start_stage_two(xck_engine* e, xck_bam* b, int ci, ContigMap cm, boo
     if (!dev_ok) b->gi.broken = true;                                    // the device path stays off for the rest of this reader
     else e->gpu_inflate_chunks++;
     const int32_t* st = dev_ok ? gs->h_st : nullptr;
+    bool walked = false;
+    if (c.dparse && dev_ok) {                                            // walked on the device: clean summaries stand in for the walk tasks
+        if (gs->h_head->walk_flags == 0) walked = true;
+        else { count_parse_fallback(b); if (!fallback_copy_out(b, c, gs)) { b->gi.broken = true; st = nullptr; } }   // (no bytes on the host: the pool inflates the chunk)
+    }
+    c.dparse = false;
     const size_t nb = c.blocks.size(); size_t left = nb;
     if (dev_ok) {
         left = 0; size_t crc_ok = 0, crc_bad = 0;
@@ -1159,11 +1240,9 @@ static void start_stage_two(xck_engine* e, xck_bam* b, int ci, ContigMap cm, boo
     }
     b->gi.left_blocks += left; b->dstat[DS_GPU_LEFT] += (int64_t)left;
     cm.only_tid = range_only_tid(b, c);
-    // (what the device left - a CRC mismatch included - is checked on the host as every host block is)
-    Chunk* cp = &c; const uint8_t* map = b->map; DecodeTimes* tmp_ = &b->tm; const bool want_seq = e->dec.want_seq, crc = e->dec.verify_crc; std::atomic<int64_t>* ds = b->dstat;
-    for (WalkPart& wp : c.parts) { WalkPart* wpp = &wp; c.tg.later([cp, map, crc, wpp, tmp_, cm, want_seq, st, ds] { run_part(cp, map, crc, wpp, tmp_, cm, want_seq, st, ds); }); }
-    c.tg.flush(*b->pool, true);                                          // (ahead of the later chunks' inflate tasks)
     c.stage2 = true;
+    if (walked) { c.dp_ok = true; return; }
+    queue_host_walk(e, b, c, cm, st);                                    // (what the device left - a CRC mismatch included - is checked on the host as every host block is)
 }
 
 // ---- decode_next_chunk and its stages ------------------------------------------------------------------------------------
@@ -1198,6 +1277,10 @@ static void begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bo
             gi.depth = e->knobs.gpu_inflate_depth; gi.max_held = std::min(gi.depth + 2, 12);
             gi.free_cus = e->knobs.gpu_inflate_free_cus; gi.verbose = e->knobs.debug_timing;
             b->n_ring = std::max(N_CHUNK + 1, std::min(N_CHUNK_GPU, e->knobs.gpu_inflate_ring));
+            // XCK_GPU_PARSE: walk and parse these chunks on the device too - where the key is a UMI tag (read names are interned on the
+            // host) and every barcode fits a slot of the barcode table, which the kernel probes as it is
+            bool fits = true; for (const std::string& bc : e->dec.barcodes) fits = fits && bc.size() <= sizeof(DecodeCfg::BcSlot::key);
+            gi.parse = e->knobs.gpu_parse && e->dec.use_umi && fits;
         }
     }
     bind_to_numa_node(e, b);                                   // (before the scanner thread is made: it inherits the mask)
@@ -1208,14 +1291,15 @@ static void begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bo
 }
 
 // Stage 2, keep the ring full: while the head chunk is stitched and parsed the pool inflates the next ones
-static void fill_ring(xck_engine* e, xck_bam* b, const ContigMap& cm) {
+static void fill_ring(xck_engine* e, xck_bam* b, const ContigMap& cm, const xck_ingest_opts* o) {
     reap_jobs(b);
+    const bool dev_parse = device_parse_now(b, cm, o);
     // (the chunks behind `head` that a parse in flight still reads must not be scheduled over: `back` = how far the oldest of them lies behind)
     int back = 0;
     for (auto& j : b->jobs) if (!j.released) back = std::max(back, (b->head - j.ring_idx + b->n_ring) % b->n_ring);
     while (b->n_sched + back < b->n_ring && !b->scan_end) {
         const int ci = (b->head + b->n_sched) % b->n_ring;
-        schedule_chunk(b, b->ch[ci], ci, e->dec.verify_crc, e->dec.crc_on_device, cm, e->dec.want_seq);
+        schedule_chunk(b, b->ch[ci], ci, e->dec.verify_crc, e->dec.crc_on_device, cm, e->dec.want_seq, dev_parse);
         if (b->scan_end) break;
         b->n_sched++;
     }
@@ -1349,16 +1433,16 @@ static int stitch_chunk(xck_bam* b, Chunk& c, const ContigMap& cm, const xck_ing
 
 // Stage 5, layout: where every piece's records go in the job's SoA block (prefix sums over the pieces), and the batches - runs of
 // records on one contig, across piece boundaries.  Returns the number of records of the chunk (kept or not), < 0 on error.
-static int64_t layout_chunk(xck_bam* b, ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq) {
+static int64_t layout_chunk(ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq, int64_t records_before, std::string* err) {
     size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0;
     for (WalkPart& wp : pieces) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_rec += wp.recs.size(); }
-    if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { b->err = "chunk too large"; return XCK_E_IO; }
+    if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
     HostSoA& s = j.soa;
-    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) { b->err = "out of host memory"; return XCK_E_NOMEM; }
+    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) { *err = "out of host memory"; return XCK_E_NOMEM; }
     s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
     const uint64_t ord_hi = (uint64_t)(uint32_t)o->sample << ORD_REC_BITS;
     int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0, rec0 = 0;
-    auto close_batch = [&](int64_t oi) { if (cur_c >= 0 && oi > seg0) j.batches.push_back({cur_c, seg0, oi, ord_hi | (uint64_t)(b->n_records + seg_r)}); };
+    auto close_batch = [&](int64_t oi) { if (cur_c >= 0 && oi > seg0) j.batches.push_back({cur_c, seg0, oi, ord_hi | (uint64_t)(records_before + seg_r)}); };
     for (const WalkPart& wp : pieces) {
         int64_t oi = (int64_t)wp.out_base;
         for (size_t ri = 0; ri < wp.runs.size(); ri++) {
@@ -1383,13 +1467,39 @@ static void drop_range_past_window(xck_bam* b, const Chunk& c, const ContigMap& 
     }
 }
 
-// Stage 6, parse: one pool task per piece, record fields -> the job's SoA block.  The coordinator waits for them here, or
-// (defer_parse) hands the job to the push thread, which does; the ring chunk goes with the job until its parse has ended.
-static int parse_or_defer(xck_bam* b, Chunk& c, ChunkJob& j, const std::vector<WalkPart>& pieces, int64_t n_rec, const ContigMap& cm, int32_t sample, PhaseClock& clk) {
+static void queue_parse_tasks(xck_bam* b, ChunkJob& j, const std::vector<WalkPart>& pieces, const ContigMap& cm, int32_t sample) {
     xck_engine* e = j.e; HostSoA* sp = &j.soa; std::atomic<int>* fl = &j.flags;
     for (const WalkPart& wp : pieces) { if (!wp.n_out) continue; const WalkPart* wpp = &wp;
         j.tg.later([b, e, sp, sample, wpp, cm, fl] { parse_part(b, e, sp, sample, wpp, cm, fl); }); }
     j.tg.flush(*b->pool, true);                                         // (ahead of the later chunks' inflate tasks)
+}
+
+// Stages 4 - 6 of a chunk the device walked (c.dp_ok): its summaries -> the batch list (parse_dev.h summaries_to_batches, what
+// layout_chunk makes of the walk parts), no parse tasks; the job goes to the push thread, which launches the parse kernel.
+static int layout_walked_chunk(xck_bam* b, Chunk& c, ChunkJob& j, const ContigMap& cm, const xck_ingest_opts* o, PhaseClock& clk) {
+    GpuInflateSlot* gs = b->gi.slot[b->head];
+    if (c.new_range) b->carry.clear();                                  // (a range start under use_index: see stitch_chunk)
+    summaries_to_batches(gs->h_sum, c.blocks.size(), b->n_records, (uint64_t)(uint32_t)o->sample << ORD_REC_BITS, &j.lay);
+    j.dev = true; j.b = b; j.cm = cm; j.rec_before = b->n_records;
+    memset(&j.opts, 0, sizeof j.opts); memcpy(&j.opts, o, std::min<size_t>(o->struct_size, sizeof j.opts));
+    clk.lap(b->tm.dp_layout);
+    if (b->per_tid_ranges && cm.t_end && j.lay.has_last) {              // drop_range_past_window, on the last record the walk saw
+        const int32_t tid = j.lay.last_tid;
+        if (tid >= 0 && tid < cm.n_refs && cm.t_end[tid] > 0 && j.lay.last_pos >= cm.t_end[tid]) { b->skip_range = c.range_id; b->scanner->abandon(c.range_id); }
+    }
+    b->n_records += (int64_t)j.lay.n_rec;
+    advance_head(b, &j);
+    if (!b->pusher) b->pusher = new Pusher();
+    const int prc = b->pusher->submit(&j);
+    clk.lap(b->tm.wait_push);
+    if (prc) b->err = b->pusher->err;
+    return prc;
+}
+
+// Stage 6, parse: one pool task per piece, record fields -> the job's SoA block.  The coordinator waits for them here, or
+// (defer_parse) hands the job to the push thread, which does; the ring chunk goes with the job until its parse has ended.
+static int parse_or_defer(xck_bam* b, Chunk& c, ChunkJob& j, const std::vector<WalkPart>& pieces, int64_t n_rec, const ContigMap& cm, int32_t sample, PhaseClock& clk) {
+    queue_parse_tasks(b, j, pieces, cm, sample);
     if (!b->defer_parse) {
         j.tg.wait();
         clk.lap(b->tm.wait_parse);
@@ -1406,6 +1516,27 @@ static int parse_or_defer(xck_bam* b, Chunk& c, ChunkJob& j, const std::vector<W
     return prc;
 }
 
+// The push thread's way down the host path, for a chunk whose parse kernel met a record it leaves to the host (a UMI to intern): the
+// chunk's bytes come over, the pool walks its parts and parses them into the job's own SoA block, exactly as the coordinator would have
+// had them do; Pusher::run then waits for the parse tasks and pushes the block.  The ring chunk is still the job's (parsed is not set).
+static int redo_on_host(ChunkJob* j, std::string* msg) {
+    xck_bam* b = j->b; xck_engine* e = j->e; Chunk& c = b->ch[j->ring_idx]; GpuInflateSlot* gs = b->gi.slot[j->ring_idx];
+    j->dev = false;
+    if (!fallback_copy_out(b, c, gs)) { *msg = "device error while copying a chunk's inflated bytes to the host"; return XCK_E_DEVICE; }
+    queue_host_walk(e, b, c, j->cm, gs->h_st);
+    c.tg.wait();
+    if (const int th = c.tg.take_thrown()) { *msg = th == 1 ? "out of host memory (BGZF inflate / record walk)" : "C++ exception in a decoder task"; return th == 1 ? XCK_E_NOMEM : XCK_E_IO; }
+    // (the device's walk ended every block at its end and no bytes were carried in, so the parts' lists are the chunk's)
+    size_t at = c.parts.empty() ? 0 : c.parts[0].spec_start;
+    for (const WalkPart& wp : c.parts) { if (wp.spec_start != at || wp.stop != wp.u_end) { *msg = "internal: host and device walk disagree"; return XCK_E_IO; } at = wp.stop; }
+    j->batches.clear();
+    const int64_t n_rec = layout_chunk(*j, c.parts, &j->opts, e->dec.want_seq, j->rec_before, msg);
+    if (n_rec < 0) return (int)n_rec;
+    if ((size_t)n_rec != j->lay.n_rec) { *msg = "internal: host and device walk disagree"; return XCK_E_IO; }
+    queue_parse_tasks(b, *j, c.parts, j->cm, j->opts.sample);
+    return 0;
+}
+
 // decode the next chunk into the SoA block of its job (b->cur) and fill the job's batch list; returns 1 (decoded: parsed in place or,
 // defer_parse, parse + push in flight), 0 (end of the stream), < 0 on error; schedule_only (xck_bam_prefetch): 1 once the pool is
 // inflating the first chunks
@@ -1417,7 +1548,7 @@ static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o
     int rc;
     do {
         clk = PhaseClock();
-        fill_ring(e, b, cm);
+        fill_ring(e, b, cm, o);
         clk.lap(b->tm.sched);
         if (schedule_only) return 1;
         rc = wait_head(e, b, &cm, clk);
@@ -1426,10 +1557,27 @@ static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o
     Chunk& c = b->ch[b->head];
     ChunkJob* j = take_job(e, b);
     if (!j) return XCK_E_IO;
+    if (c.dp_ok) {
+        // a chunk the device walked stays on the device unless bytes are carried into it (the chunk before ended inside a record), the caller
+        // wants its batches on the host (xck_bam_next_batch) or a record limit was set meanwhile: then its bytes come over and the pool walks it
+        const bool carry_in = !b->carry.empty() && !(c.new_range && b->use_ranges);
+        if (!carry_in && b->defer_parse && o->max_records <= 0) {
+            if ((rc = layout_walked_chunk(b, c, *j, cm, o, clk)) < 0) return rc;
+            return 1;
+        }
+        count_parse_fallback(b);
+        GpuInflateSlot* gs = b->gi.slot[b->head];
+        const bool copied = fallback_copy_out(b, c, gs);
+        if (!copied) b->gi.broken = true;
+        queue_host_walk(e, b, c, cm, copied ? gs->h_st : nullptr);
+        if ((rc = wait_chunk_tasks(b, c))) return rc;
+        if (c.failed) { b->err = c.err.empty() ? "BGZF decode error" : c.err; return XCK_E_IO; }
+        clk.lap(b->tm.wait_inflate);
+    }
     std::vector<WalkPart>* pieces = nullptr; bool hit_limit = false;
     if ((rc = stitch_chunk(b, c, cm, o, e->dec.want_seq, &pieces, &hit_limit)) < 0) return rc;
     clk.lap(b->tm.stitch);
-    const int64_t n_rec = layout_chunk(b, *j, *pieces, o, e->dec.want_seq);
+    const int64_t n_rec = layout_chunk(*j, *pieces, o, e->dec.want_seq, b->n_records, &b->err);
     if (n_rec < 0) return (int)n_rec;
     clk.lap(b->tm.layout);
     if ((rc = parse_or_defer(b, c, *j, *pieces, n_rec, cm, o->sample, clk)) < 0) return rc;

@@ -19,6 +19,7 @@
 // Integer / byte work only - HBM-bound, no MFMA.  See DESIGN.md for layouts, byte counts and measurements.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <limits>
@@ -26,6 +27,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include "engine_impl.h"
+#include "parse_dev.h"
 
 namespace xck {
 #ifndef XCK_WS_SNP
@@ -853,6 +855,7 @@ struct Stager {
     int device = 0; hipStream_t s_copy = nullptr;
     struct Slot { char* buf = nullptr; size_t cap = 0; hipEvent_t t0 = nullptr, copied = nullptr; int users = 0; bool timed = false; } slot[3];
     int next = 0;
+    void* d_bc = nullptr;               // the decoder's barcode table, for the parse kernel (engine_push_parsed)
 };
 
 
@@ -1207,8 +1210,9 @@ int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident) {
     return launch_queue(im, slot_idx);                         // the kernel overlaps the caller's next decode + copy
 }
 
-// ---- host ingest: one decoded chunk = one H2D copy, shared by every pipeline of the handle (which has at least one) ----
-int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence) {
+// ---- host ingest: one decoded chunk = one staging slot, shared by every pipeline of the handle (which has at least one) ----
+// the next staging slot, grown to `bytes`, once every launch that still reads it has been confirmed
+static int stager_take(xck_engine* e, size_t bytes, int* si_out) {
     EngineImpl* im = e->impls[0];                                        // (errors of the shared part are reported through it)
     HIP_TRY(hipSetDevice(im->device));
     Stager* st = e->stager;
@@ -1224,16 +1228,17 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
     if (sl.users != 0) { e->err = "internal: staging slot still in use"; return XCK_E_STATE; }
     if (sl.timed) { float ms = 0; if (hipEventElapsedTime(&ms, sl.t0, sl.copied) == hipSuccess) im->st.ms_h2d += ms; sl.timed = false; }
     if (int rc = grow_device(im, (void**)&sl.buf, &sl.cap, bytes, bytes / 4 + (1 << 20))) return rc;
-    if (!*fence) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); *fence = (void*)ev; }
-    HIP_TRY(hipEventRecord(sl.t0, st->s_copy));
-    HIP_TRY(hipMemcpyAsync(sl.buf, host_base, bytes, hipMemcpyHostToDevice, st->s_copy));
-    HIP_TRY(hipEventRecord(sl.copied, st->s_copy));
-    HIP_TRY(hipEventRecord((hipEvent_t)*fence, st->s_copy));
-    sl.timed = true;
-    const char* hb = (const char*)host_base;
-    auto dev = [&](const void* hp) { return (void*)(sl.buf + ((const char*)hp - hb)); };   // a column's place in the staged copy
+    *si_out = si;
+    return 0;
+}
+// The batches of the chunk in staging slot si -> every pipeline's queue and one fused launch per pipeline (and the opt-in summary
+// passes behind it, launch_queue).  dev(): a column pointer of a batch -> its place in the slot; sizes(i): the batch's CIGAR words
+// and sequence bytes (xck_stats.algo_bytes_join).
+template <class Dev, class Sizes>
+static int push_staged(xck_engine* e, int si, const xck_batch* batches, int n, Dev dev, Sizes sizes) {
+    Stager::Slot& sl = e->stager->slot[si];
     for (int k = 0; k < e->n_impl; k++) {
-        im = e->impls[k];
+        EngineImpl* im = e->impls[k];
         if (im->finished) { e->err = "push after finish (call xck_reset)"; return XCK_E_STATE; }
         int rc = launch_queue(im, -1); if (rc) return rc;                 // earlier device-resident pushes keep their order
         HIP_TRY(hipStreamWaitEvent(im->s_comp, sl.copied, 0));
@@ -1248,8 +1253,8 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
             d.cell = (const int32_t*)dev(b->cell); d.umi = (const uint64_t*)dev(b->umi);
             d.cig_off = (const uint32_t*)dev(b->cig_off); d.cigar = (const uint32_t*)dev(b->cigar);
             if (seq) { d.seq_off = (const uint32_t*)dev(b->seq_off); d.seq = (const uint8_t*)dev(b->seq); }
-            const size_t nr = (size_t)b->n_reads;
-            im->st.algo_bytes_join += join_bytes(nr, b->cig_off[nr] - b->cig_off[0], seq ? b->seq_off[nr] - b->seq_off[0] : 0);
+            size_t n_cig = 0, n_seq = 0; sizes(i, seq, &n_cig, &n_seq);
+            im->st.algo_bytes_join += join_bytes((size_t)b->n_reads, n_cig, n_seq);
             im->queue.push_back(d); im->queued_reads += b->n_reads;
             if ((int)im->queue.size() >= MAX_FUSE) { rc = launch_queue(im, -1, si); if (rc) return rc; }
         }
@@ -1258,12 +1263,69 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
     return XCK_OK;
 }
 
+// a chunk the host decoded: ONE H2D copy of its block into the slot
+int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence) {
+    int si = 0;
+    if (int rc = stager_take(e, bytes, &si)) return rc;
+    EngineImpl* im = e->impls[0];
+    Stager* st = e->stager; Stager::Slot& sl = st->slot[si];
+    if (!*fence) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); *fence = (void*)ev; }
+    HIP_TRY(hipEventRecord(sl.t0, st->s_copy));
+    HIP_TRY(hipMemcpyAsync(sl.buf, host_base, bytes, hipMemcpyHostToDevice, st->s_copy));
+    HIP_TRY(hipEventRecord(sl.copied, st->s_copy));
+    HIP_TRY(hipEventRecord((hipEvent_t)*fence, st->s_copy));
+    sl.timed = true;
+    const char* hb = (const char*)host_base;
+    return push_staged(e, si, batches, n, [&](const void* hp) { return (void*)(sl.buf + ((const char*)hp - hb)); },   // a column's place in the staged copy
+                       [&](int i, bool seq, size_t* n_cig, size_t* n_seq) { const xck_batch* b = &batches[i]; const size_t nr = (size_t)b->n_reads;
+                                                                              *n_cig = b->cig_off[nr] - b->cig_off[0]; *n_seq = seq ? b->seq_off[nr] - b->seq_off[0] : 0; });
+}
+
+// A chunk the device inflated and walked (csrc/parse_dev.hip): no copy - the parse kernel writes the chunk's SoA block straight into the
+// slot, in the place of the H2D copy (same stream, same event), and the batches follow as above.  The kernel's flags are waited for
+// before anything is queued: 1 = it met a record it leaves to the host (nothing was queued; the caller takes the host path).
+int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* dbs, int n) {
+    const DecodeCfg& dc = e->dec;
+    const SoaLayout lay = soa_layout(n_out + 1, n_cig + 1, dc.want_seq ? n_seq + 1 : 1);
+    int si = 0;
+    if (int rc = stager_take(e, lay.total, &si)) return rc;
+    EngineImpl* im = e->impls[0];                                        // (HIP_TRY reports through it)
+    Stager* st = e->stager; Stager::Slot& sl = st->slot[si];
+    if (!st->d_bc && !dc.bc_slots.empty()) {                             // the barcode table, as it is (same hash, same probe order on the device)
+        static_assert(sizeof(DpBcSlot) == sizeof(DecodeCfg::BcSlot) && offsetof(DpBcSlot, key) == offsetof(DecodeCfg::BcSlot, key), "the device reads the host's slots");
+        HIP_TRY(hipMalloc(&st->d_bc, dc.bc_slots.size() * sizeof(DpBcSlot)));
+        HIP_TRY(hipMemcpy(st->d_bc, dc.bc_slots.data(), dc.bc_slots.size() * sizeof(DpBcSlot), hipMemcpyHostToDevice));
+    }
+    DpParseCfg pc; memset(&pc, 0, sizeof pc);
+    pc.bc = (const DpBcSlot*)st->d_bc; pc.bc_mask = dc.bc_mask; pc.use_barcodes = dc.use_barcodes; pc.want_seq = dc.want_seq; pc.umi_bits = dc.umi_bits; pc.sample = sample;
+    memcpy(pc.cell_tag, dc.cell_tag, 2); memcpy(pc.umi_tag, dc.umi_tag, 2);
+    HIP_TRY(hipEventRecord(sl.t0, st->s_copy));
+    // (a launch that fails - dev_parse_launch has taken the error - wrote nothing into the slot: the chunk takes the host path, whose
+    // copy of the chunk's bytes reports a device that is gone)
+    if (dev_parse_launch(st->s_copy, gs, n_blocks, max_rec, pc, (uint8_t*)sl.buf, n_out, n_cig, n_seq) != 0) return 1;
+    HIP_TRY(hipEventRecord(sl.copied, st->s_copy));
+    HIP_TRY(hipEventSynchronize(sl.copied));
+    if (gs->h_head->parse_flags) return 1;
+    std::vector<xck_batch> bts((size_t)n);                               // (column pointers: already the slot's)
+    for (int i = 0; i < n; i++) {
+        xck_batch& bt = bts[(size_t)i]; const DpBatch& pb = dbs[i]; memset(&bt, 0, sizeof bt);
+        bt.contig = pb.contig; bt.n_reads = (int32_t)(pb.r1 - pb.r0); bt.ordinal_base = pb.ordinal_base;
+        bt.umi = (const uint64_t*)(sl.buf + lay.o_umi) + pb.r0; bt.pos = (const int32_t*)(sl.buf + lay.o_pos) + pb.r0; bt.cell = (const int32_t*)(sl.buf + lay.o_cell) + pb.r0;
+        bt.cig_off = (const uint32_t*)(sl.buf + lay.o_cgo) + pb.r0; bt.cigar = (const uint32_t*)(sl.buf + lay.o_cig);
+        bt.flag = (const uint16_t*)(sl.buf + lay.o_flag) + pb.r0; bt.mapq = (const uint8_t*)(sl.buf + lay.o_mapq) + pb.r0;
+        if (dc.want_seq) { bt.seq_off = (const uint32_t*)(sl.buf + lay.o_sqo) + pb.r0; bt.seq = (const uint8_t*)(sl.buf + lay.o_seq); }
+    }
+    return push_staged(e, si, bts.data(), n, [](const void* p) { return (void*)p; },
+                       [&](int i, bool seq, size_t* c, size_t* q) { *c = dbs[i].n_cig; *q = seq ? dbs[i].n_seq : 0; });
+}
+
 void engine_release_staging(xck_engine* e) {
     Stager* st = e->stager;
     if (!st) return;
     hipSetDevice(st->device);
     if (st->s_copy) hipStreamSynchronize(st->s_copy);
     for (auto& sl : st->slot) { if (sl.buf) hipFree(sl.buf); if (sl.t0) hipEventDestroy(sl.t0); if (sl.copied) hipEventDestroy(sl.copied); }
+    if (st->d_bc) hipFree(st->d_bc);
     if (st->s_copy) hipStreamDestroy(st->s_copy);
     delete st; e->stager = nullptr;
 }

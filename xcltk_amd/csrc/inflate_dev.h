@@ -5,6 +5,8 @@
 
 namespace xck {
 
+struct DpRec; struct DpCnt; struct DpBase; struct DpBlockSum; struct DpHead;   // parse_dev.h
+
 // byte ranges of one block's deflate stream / inflated data inside the chunk buffers; crc: the CRC-32 of the BGZF footer (read with check_crc only)
 struct DevBlock { uint32_t in_off, in_len, out_off, out_len; uint32_t crc; };
 constexpr int32_t INFLATE_ST_CRC = 50;   // status: the block was inflated to out_len bytes, but their CRC-32 is not DevBlock.crc (check_crc)
@@ -28,11 +30,16 @@ struct GpuInflateSlot {
     // them back) and stored to h_out by the wave that made them, block by block - no DMA engine is involved (see gpu_inflate_slot_launch)
     uint8_t *h_in = nullptr, *a_in = nullptr, *h_out = nullptr, *a_out = nullptr, *d_out = nullptr; DevBlock *h_bl = nullptr, *a_bl = nullptr; int32_t *h_st = nullptr, *a_st = nullptr;
     size_t cap_in = 0, cap_out = 0, cap_bl = 0;
+    // device walk + parse (csrc/parse_dev.hip): the chunk's record list, per-block counts and bases in device memory; the per-block
+    // summaries and the chunk's head in mapped host memory, visible with `done`
+    DpRec* d_rec = nullptr; DpCnt* d_cnt = nullptr; DpBase* d_base = nullptr; DpBlockSum *h_sum = nullptr, *a_sum = nullptr; DpHead *h_head = nullptr, *a_head = nullptr;
+    bool parse = false;                  // reserve the buffers above as well, and leave h_out unwritten (gpu_inflate_slot_launch)
 };
 GpuInflateSlot* gpu_inflate_slot_create(int device, int free_cus, bool verbose);           // nullptr when the device cannot be used; free_cus: CUs its stream never uses
 void gpu_inflate_slot_destroy(GpuInflateSlot* s);                                          // waits for whatever is in flight
 bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks);   // (re)allocates; false = out of memory
-int  gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks, bool check_crc = false);   // inflate kernel (every wave also stores its finished block to h_out) + event, asynchronous; 0 = enqueued
+struct DpWalk;                                                                             // parse_dev.h: what the walk behind the inflate needs
+int  gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks, bool check_crc = false, const DpWalk* walk = nullptr);   // inflate kernel (every wave also stores its finished block to h_out; with `walk`: nothing goes to h_out, walk and scan follow) + event, asynchronous; 0 = enqueued
 bool gpu_inflate_slot_done(GpuInflateSlot* s);                                            // non-blocking: has the last launch finished?
 int  gpu_inflate_slot_wait(GpuInflateSlot* s);                                             // 0 = the chunk's bytes and statuses are in h_out / h_st
 

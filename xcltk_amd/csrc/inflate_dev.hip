@@ -23,7 +23,7 @@
 #include <cstdio>
 #include <algorithm>
 #include <hip/hip_runtime.h>
-#include "inflate_dev.h"
+#include "parse_dev.h"
 
 namespace xck {
 
@@ -583,6 +583,8 @@ GpuInflateSlot* gpu_inflate_slot_create(int device, int free_cus, bool verbose) 
 static void slot_free_buffers(GpuInflateSlot* s) {
     if (s->h_in) hipHostFree(s->h_in); if (s->h_out) hipHostFree(s->h_out); if (s->d_out) hipFree(s->d_out);
     if (s->h_bl) hipHostFree(s->h_bl); if (s->h_st) hipHostFree(s->h_st);
+    if (s->d_rec) hipFree(s->d_rec); if (s->d_cnt) hipFree(s->d_cnt); if (s->d_base) hipFree(s->d_base); if (s->h_sum) hipHostFree(s->h_sum); if (s->h_head) hipHostFree(s->h_head);
+    s->d_rec = nullptr; s->d_cnt = nullptr; s->d_base = nullptr; s->h_sum = s->a_sum = nullptr; s->h_head = s->a_head = nullptr;
     s->h_in = s->a_in = s->h_out = s->a_out = s->d_out = nullptr; s->h_bl = s->a_bl = nullptr; s->h_st = s->a_st = nullptr; s->cap_in = s->cap_out = s->cap_bl = 0;
 }
 void gpu_inflate_slot_destroy(GpuInflateSlot* s) {
@@ -596,7 +598,7 @@ void gpu_inflate_slot_destroy(GpuInflateSlot* s) {
     delete s;
 }
 bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks) {
-    if (in_bytes <= s->cap_in && out_bytes <= s->cap_out && n_blocks <= s->cap_bl) return true;
+    if (in_bytes <= s->cap_in && out_bytes <= s->cap_out && n_blocks <= s->cap_bl && (!s->parse || s->d_rec)) return true;
     if (hipSetDevice(s->device) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) return false;
     auto grow = [](size_t need, size_t have) { return need > have ? need + need / 4 + 4096 : have; };
     const size_t ci = grow(in_bytes, s->cap_in), co = grow(out_bytes, s->cap_out), cb = grow(n_blocks, s->cap_bl);
@@ -604,6 +606,10 @@ bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_byt
     auto host = [](void** h, void** a, size_t bytes) { return hipHostMalloc(h, bytes, hipHostMallocMapped) == hipSuccess && hipHostGetDevicePointer(a, *h, 0) == hipSuccess; };
     bool ok = host((void**)&s->h_in, (void**)&s->a_in, ci + 16) && host((void**)&s->h_out, (void**)&s->a_out, co + 64) && hipMalloc((void**)&s->d_out, co + 64) == hipSuccess &&
               host((void**)&s->h_bl, (void**)&s->a_bl, cb * sizeof(DevBlock)) && host((void**)&s->h_st, (void**)&s->a_st, cb * sizeof(int32_t));
+    if (ok && s->parse)                                                     // device walk + parse: record list, counts, bases, summaries
+        ok = hipMalloc((void**)&s->d_rec, dp_rec_capacity(co + 64) * sizeof(DpRec)) == hipSuccess && hipMalloc((void**)&s->d_cnt, cb * sizeof(DpCnt)) == hipSuccess &&
+             hipMalloc((void**)&s->d_base, cb * sizeof(DpBase)) == hipSuccess && host((void**)&s->h_sum, (void**)&s->a_sum, cb * sizeof(DpBlockSum)) &&
+             host((void**)&s->h_head, (void**)&s->a_head, sizeof(DpHead));
     if (!ok) { slot_free_buffers(s); (void)hipGetLastError(); return false; }
     s->cap_in = ci; s->cap_out = co; s->cap_bl = cb;
     return true;
@@ -613,12 +619,14 @@ bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_byt
 // push time rose from 0.25 to 1.6 s per 100 M records.  The kernel is bound by its serial Huffman chain, not by bytes: it takes
 // the compressed stream from host memory in 1 KB coalesced windows, every wave stores its finished block to the host block, and the
 // statuses go straight back.
-int gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks, bool check_crc) {
+int gpu_inflate_slot_launch(GpuInflateSlot* s, size_t in_bytes, size_t out_bytes, size_t n_blocks, bool check_crc, const DpWalk* walk) {
     (void)in_bytes;
     if (hipSetDevice(s->device) != hipSuccess) return -1;
     for (size_t i = 0; i < n_blocks; i++) s->h_st[i] = -1;                  // (a block the kernel never reaches is left to the host)
     (void)out_bytes;
-    if (dev_inflate_launch(s->stream, s->a_in, s->a_bl, (int)n_blocks, s->d_out, s->a_st, s->a_out, s->variant, check_crc) != 0) { (void)hipGetLastError(); return -1; }
+    // (with a device walk behind it the chunk's bytes stay in HBM: nothing is stored to h_out unless the chunk falls back, dev_parse_copy_out)
+    if (dev_inflate_launch(s->stream, s->a_in, s->a_bl, (int)n_blocks, s->d_out, s->a_st, walk ? nullptr : s->a_out, s->variant, check_crc) != 0) { (void)hipGetLastError(); return -1; }
+    if (walk && dev_walk_launch(s, n_blocks, *walk) != 0) { (void)hipGetLastError(); return -1; }
     if (hipEventRecord(s->done, s->stream) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return 0;
 }

@@ -116,13 +116,14 @@ struct Knobs {
     int  cell_summary_slots = 0;         // XCK_CELL_SUMMARY_SLOTS: rows of the per-block LDS tables (0 = the built-in 512 per-cell, 1024 per-feature / per-SNP; tests: small tables reach the no-fit path)
     bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
     int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
+    bool gpu_parse = true;               // XCK_GPU_PARSE=auto|0: walk and parse the GPU-inflated chunks on the device where that applies (bam.cpp device_parse_now)
     int  verify_crc = 0;                 // XCK_VERIFY_CRC: 0 = as the flags say, 1 = host (XCK_F_VERIFY_CRC ORed in), 2 = device (XCK_F_DEVICE_CRC)
     static Knobs from_env();             // api.cpp
 };
 
 // xck_decode_stats counters (include/xck.h), in this order.  A reader counts in its own set; every decode call adds what it counted
 // since the last call to its handle's (bam.cpp fold_decode_stats).
-enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_N };
+enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_PARSE_CHUNKS, DS_PARSE_FALLBACKS, DS_N };
 
 struct EngineImpl;                       // one GPU pipeline of a handle (engine_impl.h)
 struct Stager;                           // device staging slots of engine_push_block (engine.hip)
@@ -184,6 +185,10 @@ int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (
 // asynchronous H2D copy into a device staging slot shared by the handle's pipelines, then the join kernel(s) on the batches.
 // *fence (created on first use) is recorded behind the copy: fence_wait() before the host block is overwritten.
 int  engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence);
+// One chunk the device inflated and walked (parse_dev.h): the parse kernel writes the chunk's SoA block into the staging slot - no copy -
+// and the batches follow as in engine_push_block.  1 = the kernel flagged the chunk and nothing was queued: the host path takes it.
+struct GpuInflateSlot; struct DpBatch;
+int  engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* batches, int n);
 void engine_release_staging(xck_engine* e);   // frees the staging slots (xck_destroy)
 void fence_wait(void* fence);
 void fence_destroy(void* fence);
