@@ -99,14 +99,17 @@ def list_cases():
     return sorted(os.listdir(cdir)) if os.path.isdir(cdir) else []
 
 
-def load_case(name, tmpdir):
-    """-> (case dict with substituted paths, dataset dir, out dir, expected dir)"""
+def load_case(name, tmpdir, dataset_dir=None):
+    """-> (case dict with substituted paths, dataset dir, out dir, expected dir).  dataset_dir: where `$D/` points instead of the
+    golden dataset (a temporary copy whose BAMs are re-cut: tests/reblock.py); dataset.json is read from the golden one."""
     cdir = os.path.join(GOLDEN, "cases", name)
     with open(os.path.join(cdir, "case.json")) as fp:
         case = json.load(fp)
     ddir = os.path.join(GOLDEN, "datasets", case["dataset"])
     with open(os.path.join(ddir, "dataset.json")) as fp:
         ds = json.load(fp)
+    if dataset_dir is not None:
+        ddir = str(dataset_dir)
     odir = os.path.join(str(tmpdir), "out_" + name)
     listfile = os.path.join(str(tmpdir), "bam_list_%s.txt" % name)
     with open(listfile, "w") as fp:
