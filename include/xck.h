@@ -41,6 +41,22 @@
  *                                         reader used through xck_bam_next_batch) takes the host path, which also reports every error; after four such
  *                                         chunks in a row the reader stops asking.  0: walk and parse on the host.  Bit-identical results either way;
  *                                         xck_decode_stats.gpu_parse_chunks / gpu_parse_fallbacks count them.
+ *   XCK_GPU_NAMES=1                       (opt-in; unset or 0: nothing is allocated, launched or changed) device-names mode: a handle whose key is the
+ *                                         read name (umi_tag == "") interns the names in a table in HBM (csrc/intern_dev.hip) instead of the host's, so
+ *                                         its GPU-inflated chunks are walked and parsed on the device as those of a UMI handle are.  On for the life of
+ *                                         a handle that drives a GPU, has an empty umi_tag and barcodes of at most 18 bytes (or none), with XCK_GPU_PARSE
+ *                                         not 0 and the GPU share of the inflate not off (XCK_GPU_INFLATE=0, XCK_F_VERIFY_CRC alone); any other handle
+ *                                         ignores the knob.  EVERY read name of xck_ingest_bam is then keyed by the device table: the chunks the host
+ *                                         parses (pool-inflated chunks, the tail of a file, fallbacks, calls with max_records) send their names along
+ *                                         with their columns, so a name has one key whichever side parsed its chunk.  The table is cleared where the
+ *                                         host's is (xck_reset; per BAM without barcodes), grows between launches, and fails the ingest with
+ *                                         XCK_E_CAPACITY when the id space of the key width is used up (as the host's does; XCK_TEST_INTERN_LIMIT
+ *                                         applies), with XCK_E_NOMEM when it cannot grow.  xck_bam_next_batch keeps the host's table: on such a handle
+ *                                         the two kinds of decode call do not mix between two clears - the second kind answers XCK_E_STATE.  Identical
+ *                                         matrices either way; xck_decode_stats.gpu_names_* count.  With XCK_DEBUG_TIMING one line at xck_destroy.
+ *   XCK_GPU_NAMES_SLOTS0=<slots>, XCK_GPU_NAMES_ARENA0=<bytes>   first sizes of that table (defaults 2^21 slots, 64 MB; tests: 64 and 4096 make a small
+ *                                         file grow it several times).  XCK_TEST_NAMES_HASH_BITS=<n> (tests): the device table keeps only the low n bits of
+ *                                         the hash - at 4 every probe chain holds thousands of names and the byte comparison has to decide.
  *   XCK_VERIFY_CRC=0|host|device          check the CRC32 of every BGZF block the record decoder inflates, as if the handle had been made with
  *                                         XCK_F_VERIFY_CRC (host: the GPU share of the inflate is off) or XCK_F_DEVICE_CRC (device: the GPU share checks
  *                                         its own blocks) - for front-ends and benchmarks whose calls do not carry the flags.  0 (the default) adds
@@ -275,6 +291,10 @@ typedef struct xck_decode_stats {
     /* appended (a caller with the shorter struct gets the fields above): */
     int64_t gpu_parse_chunks;         /* GPU-inflated chunks whose records were walked and parsed on the device too (XCK_GPU_PARSE) */
     int64_t gpu_parse_fallbacks;      /* device-walked chunks that took the host path after all (straddling record, UMI to intern, ...) */
+    /* appended after those (XCK_GPU_NAMES; a caller with a shorter struct gets the fields above): */
+    int64_t gpu_names_interned;       /* read names looked up in the device table (directly codable and empty names need no table)  */
+    int64_t gpu_names_distinct;       /* ids the device table handed out since its last clear, summed over the clears               */
+    int64_t gpu_names_host_chunks;    /* host-parsed chunks (pool-inflated, tails, fallbacks, max_records) whose names were keyed on the device */
 } xck_decode_stats;
 
 /* Where the reads of ONE pipeline went, since the last xck_reset (handles made with XCK_F_READ_FATE; additive, ABI 3 is unchanged).

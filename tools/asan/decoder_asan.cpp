@@ -43,7 +43,10 @@ int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool, cons
 int  dev_parse_copy_out(GpuInflateSlot*, size_t) { return -1; }
 void* dev_parse_upload(int, const void*, size_t, const void*, size_t) { return nullptr; }
 void dev_parse_free(int, void*) {}
-int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int) { return XCK_E_ARG; }
+int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
+int  engine_names_clear(xck_engine*, bool) { return 0; }
+void engine_names_stats(const xck_engine*, int64_t* a, int64_t* b) { *a = 0; *b = 0; }
+int  engine_names_check(xck_engine*) { return 0; }
 int  gpu_inflate_slot_wait(GpuInflateSlot*) { return -1; }
 bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
 // stand-in for the engine's block push (called on the decoder's push thread): touches everything the batches claim to own
@@ -55,7 +58,7 @@ static unsigned long long batch_sum(const xck_batch& bt) {
                       if (bt.seq) for (uint32_t q = bt.seq_off[0]; q < bt.seq_off[bt.n_reads]; q++) s += bt.seq[q]; }
     return s + (unsigned long long)bt.contig * 1000003ull + bt.ordinal_base;
 }
-int  engine_push_block(xck_engine*, const void* base, size_t bytes, const xck_batch* bts, int n, void**) {
+int  engine_push_block(xck_engine*, const void* base, size_t bytes, const xck_batch* bts, int n, void**, const NameTrailer*) {
     for (int i = 0; i < n; i++) {
         if (bts[i].n_reads > 0 && ((const char*)bts[i].pos < (const char*)base || (const char*)(bts[i].pos + bts[i].n_reads) > (const char*)base + bytes)) return XCK_E_ARG;
         g_push_sum += batch_sum(bts[i]); g_push_recs += bts[i].n_reads;

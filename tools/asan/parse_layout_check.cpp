@@ -18,8 +18,11 @@ bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
 int  dev_parse_copy_out(GpuInflateSlot*, size_t) { return -1; }
 void* dev_parse_upload(int, const void*, size_t, const void*, size_t) { return nullptr; }
 void dev_parse_free(int, void*) {}
-int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int) { return XCK_E_ARG; }
-int  engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**) { return XCK_E_ARG; }
+int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
+int  engine_names_clear(xck_engine*, bool) { return 0; }
+void engine_names_stats(const xck_engine*, int64_t* a, int64_t* b) { *a = 0; *b = 0; }
+int  engine_names_check(xck_engine*) { return 0; }
+int  engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**, const NameTrailer*) { return XCK_E_ARG; }
 void fence_wait(void*) {}
 void fence_destroy(void*) {}
 void* pinned_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }

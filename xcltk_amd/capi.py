@@ -122,7 +122,8 @@ class DecodeStats(C.Structure):
                 ("gpu_inflate_chunks", C.c_int64), ("gpu_inflate_blocks", C.c_int64), ("gpu_blocks_left_to_host", C.c_int64),
                 ("crc_blocks_device", C.c_int64), ("crc_blocks_host", C.c_int64), ("crc_mismatch_device", C.c_int64),
                 ("crc_device_host_disagree", C.c_int64), ("gpu_path_given_up", C.c_int64),
-                ("gpu_parse_chunks", C.c_int64), ("gpu_parse_fallbacks", C.c_int64)]
+                ("gpu_parse_chunks", C.c_int64), ("gpu_parse_fallbacks", C.c_int64),
+                ("gpu_names_interned", C.c_int64), ("gpu_names_distinct", C.c_int64), ("gpu_names_host_chunks", C.c_int64)]
 
 
 class ReadFate(C.Structure):

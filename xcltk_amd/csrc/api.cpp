@@ -55,6 +55,10 @@ Knobs xck::Knobs::from_env() {
     k.push_stage_bytes = num("XCK_PUSH_STAGE_BYTES", 2ll << 20);
     k.gpu_inflate_pct = (!*str("XCK_GPU_INFLATE") || !strcmp(str("XCK_GPU_INFLATE"), "auto")) ? -1 : (int)std::max(0ll, std::min(100ll, num("XCK_GPU_INFLATE", 0)));
     k.gpu_parse = strcmp(str("XCK_GPU_PARSE"), "0") != 0;
+    k.gpu_names = num("XCK_GPU_NAMES", 0) != 0;
+    k.gpu_names_slots0 = std::max(64ll, std::min(1ll << 30, num("XCK_GPU_NAMES_SLOTS0", 1ll << 21)));
+    k.gpu_names_arena0 = std::max(1024ll, std::min(8ll << 30, num("XCK_GPU_NAMES_ARENA0", 64ll << 20)));
+    k.names_hash_bits = (int)std::max(0ll, std::min(63ll, num("XCK_TEST_NAMES_HASH_BITS", 0)));
     k.gpu_inflate_depth = (int)std::max(1ll, std::min(10ll, num("XCK_GPU_INFLATE_DEPTH", 10)));
     k.gpu_inflate_ring = (int)num("XCK_GPU_INFLATE_RING", 12);
     k.gpu_inflate_min_mb = (int)std::max(0ll, num("XCK_GPU_INFLATE_MIN_MB", 96));
@@ -118,6 +122,10 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     d.crc_on_device = (crc_flags & XCK_F_DEVICE_CRC) != 0;
     d.n_threads = cfg->n_threads;
     d.max_batch_reads = cfg->max_batch_reads;
+    // device-names mode (XCK_GPU_NAMES=1): a handle with a GPU whose key is the read name, whose device chunks may be parsed on the
+    // device (XCK_GPU_PARSE), for which the GPU share of the inflate is not off and whose barcodes all fit the device's table
+    { bool fits = true; for (const std::string& bc : d.barcodes) fits = fits && bc.size() <= sizeof(DecodeCfg::BcSlot::key);
+      e->names_mode = e->knobs.gpu_names && e->n_impl > 0 && !d.use_umi && e->knobs.gpu_parse && e->knobs.gpu_inflate_pct != 0 && (!d.verify_crc || d.crc_on_device) && fits; }
     *out = e;
     return XCK_OK;
 }
@@ -241,6 +249,10 @@ int xck_reset(xck_engine* e) {
     for (auto& v : e->dstat) v = 0;
     if (int rc = for_pipelines(e, engine_reset)) return rc;
     e->gpu_inflate_chunks = 0;
+    if (e->names_mode) {                                                 // the device table is cleared where the host's is; the two kinds of decode call may start over
+        if (int rc = engine_names_clear(e, true)) return rc;
+        e->names_calls = 0;
+    }
     return XCK_OK;
 }
 
@@ -248,10 +260,12 @@ int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
     if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
     if (out->struct_size < offsetof(xck_decode_stats, gpu_parse_chunks)) { set_thread_error("xck_decode_stats.struct_size mismatch (ABI)"); return XCK_E_ARG; }
     int64_t* f[DS_N] = { &out->gpu_inflate_chunks, &out->gpu_inflate_blocks, &out->gpu_blocks_left_to_host, &out->crc_blocks_device, &out->crc_blocks_host,
-                         &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up, &out->gpu_parse_chunks, &out->gpu_parse_fallbacks };
-    // (the last two were appended: a caller built before them passes the shorter struct and gets what it knows)
-    const int n = out->struct_size >= sizeof(xck_decode_stats) ? DS_N : DS_PARSE_CHUNKS;
+                         &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up, &out->gpu_parse_chunks, &out->gpu_parse_fallbacks,
+                         &out->gpu_names_interned, &out->gpu_names_distinct, &out->gpu_names_host_chunks };
+    // (gpu_parse_* and then gpu_names_* were appended: a caller built before them passes the shorter struct and gets what it knows)
+    const int n = out->struct_size >= sizeof(xck_decode_stats) ? DS_N : out->struct_size >= offsetof(xck_decode_stats, gpu_names_interned) ? DS_NAMES_INTERNED : DS_PARSE_CHUNKS;
     for (int k = 0; k < n; k++) *f[k] = e->dstat[k].load();
+    if (n == DS_N) engine_names_stats(e, &out->gpu_names_interned, &out->gpu_names_distinct);   // (the table's own counters)
     return XCK_OK;
 }
 

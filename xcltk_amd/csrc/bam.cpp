@@ -29,6 +29,7 @@
 #include "inflate_fast.h"
 #include "inflate_dev.h"
 #include "parse_dev.h"
+#include "intern_dev.h"
 
 namespace xck {
 
@@ -84,7 +85,7 @@ void InternTable::Shard::grow() {
 // test hook: XCK_TEST_INTERN_LIMIT=<n> makes the id space of 64-bit keys overflow after n ids (tests/test_gpu_frontends.py
 // exercises the front-ends' retry with 128-bit keys without 2^25 distinct read names)
 static const uint64_t g_test_intern_limit = [] { const char* e = getenv("XCK_TEST_INTERN_LIMIT"); return e ? (uint64_t)strtoull(e, nullptr, 10) : ~0ull; }();
-static inline uint64_t intern_id_limit(int umi_bits) {
+uint64_t intern_id_limit(int umi_bits) {
     return umi_bits >= 64 ? (1ull << 63) - 1 : std::min<uint64_t>((1ull << (umi_bits - 1)) - 1, g_test_intern_limit);
 }
 
@@ -332,6 +333,9 @@ struct HostSoA {
     uint8_t* base = nullptr; size_t cap = 0, used = 0; bool pinned = false; void* fence = nullptr;
     int32_t* pos = nullptr; uint16_t* flag = nullptr; uint8_t* mapq = nullptr; int32_t* cell = nullptr; uint64_t* umi = nullptr;
     uint32_t* cig_off = nullptr; uint32_t* cigar = nullptr; uint32_t* seq_off = nullptr; uint8_t* seq = nullptr;
+    // device-names mode: behind the columns (SoaLayout::total) one DiItem per kept record and the packed bytes of the names that have
+    // to be interned - the parse tasks fill them, the block's copy takes them along (engine_push_block)
+    bool has_names = false; xck::NameTrailer nt{0, 0, 0, 0}; xck::DiItem* items = nullptr; uint8_t* name_bytes = nullptr;
 };
 
 struct RecRef { const uint8_t* p; uint32_t len; int32_t tid; uint32_t l_seq; uint16_t n_cig; };
@@ -347,7 +351,8 @@ struct ContigRun { uint32_t first; int32_t contig; };                    // reco
 struct WalkPart {
     size_t u_begin = 0, u_end = 0, spec_start = 0, stop = 0; std::vector<RecRef> recs;
     size_t n_out = 0, n_cig = 0, n_seq = 0; std::vector<ContigRun> runs;
-    size_t out_base = 0, cig_base = 0, seq_base = 0;                      // filled by the coordinator (layout_chunk)
+    size_t n_name = 0;                                                    // l_name summed over the kept records: the room their names can take (device-names mode)
+    size_t out_base = 0, cig_base = 0, seq_base = 0, name_base = 0;       // filled by the coordinator (layout_chunk)
     size_t i0 = 0, i1 = 0;                                                // the part's blocks: [i0, i1) of the chunk
 };
 
@@ -483,6 +488,7 @@ struct ChunkJob {
     // a chunk walked on the device: no parse tasks, the push thread launches the parse kernel (engine_push_parsed) - or, if that kernel
     // flags the chunk, takes it down the host path itself (redo_on_host), for which it needs what the coordinator knew
     bool dev = false; xck_bam* b = nullptr; DpChunkLayout lay; ContigMap cm; xck_ingest_opts opts; int64_t rec_before = 0;
+    bool names = false;                // device-names mode: the chunk's names are keyed by the handle's device table (take_job)
 };
 struct Pusher {
     static constexpr int MAXQ = PUSH_Q; // jobs the coordinator may run ahead
@@ -555,9 +561,10 @@ static void soa_free(HostSoA& s) {
     s = HostSoA();
 }
 // carve the columns of a chunk with n_reads kept records out of the block (growing it if needed)
-static bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq) {
+static bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t name_items = 0, size_t name_bytes = 0, bool names = false) {
     const SoaLayout l = soa_layout(n_reads, n_cig, n_seq);                // (parse_dev.h: the parse kernel writes the same block)
-    const size_t total = l.total;
+    const size_t items_bytes = (name_items * sizeof(DiItem) + 255) & ~size_t(255);
+    const size_t total = l.total + (names ? items_bytes + ((name_bytes + 255) & ~size_t(255)) : 0);   // (the names: a trailer behind the layout's total)
     if (total > s.cap) {
         if (s.fence) fence_wait(s.fence);
         if (s.base) { if (s.pinned) pinned_free(s.base); else free(s.base); }
@@ -571,6 +578,8 @@ static bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq) 
     s.umi = (uint64_t*)(s.base + l.o_umi); s.pos = (int32_t*)(s.base + l.o_pos); s.cell = (int32_t*)(s.base + l.o_cell);
     s.cig_off = (uint32_t*)(s.base + l.o_cgo); s.seq_off = (uint32_t*)(s.base + l.o_sqo); s.cigar = (uint32_t*)(s.base + l.o_cig);
     s.flag = (uint16_t*)(s.base + l.o_flag); s.mapq = s.base + l.o_mapq; s.seq = s.base + l.o_seq;
+    s.has_names = names; s.nt = NameTrailer{l.total, l.total + items_bytes, name_bytes, names ? name_items : 0};
+    s.items = names ? (DiItem*)(s.base + s.nt.items_off) : nullptr; s.name_bytes = names ? s.base + s.nt.bytes_off : nullptr;
     return true;
 }
 
@@ -602,6 +611,9 @@ static std::vector<BamScratch*> g_scratch;                            // at most
 // ... and so are the GPU-inflate slots of closed readers: a slot is ~70 MB of pinned + 50 MB of device memory, and pinning it anew
 // for every file cost 0.2 s per open (a 20 M-record file decodes in 0.45 s)
 static std::vector<GpuInflateSlot*> g_gpu_slots;                      // at most 16; kept until the process ends
+// ... and the contig tables of the device walk (device_parse_now), by content: at most 8, kept until the process ends
+struct CmShared { int device; bool tend; std::vector<int32_t> host; void* d; };
+static std::vector<CmShared> g_cm_shared;
 static GpuInflateSlot* take_gpu_slot(int device, int free_cus, bool verbose) {
     { std::lock_guard<std::mutex> lk(g_scratch_mu);
       for (size_t i = 0; i < g_gpu_slots.size(); i++) if (g_gpu_slots[i]->device == device) { GpuInflateSlot* s = g_gpu_slots[i]; g_gpu_slots.erase(g_gpu_slots.begin() + (long)i); return s; } }
@@ -829,7 +841,7 @@ static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* w
         const RecRef rr{r, bs, (int32_t)le32(r), le32(r + 16), le16(r + 12)};
         const int32_t ctg = cm(rr.tid, (int32_t)le32(r + 4));
         if (ctg != cur_c) { wpp->runs.push_back({(uint32_t)wpp->recs.size(), ctg}); cur_c = ctg; }
-        if (ctg >= 0) { wpp->n_out++; wpp->n_cig += rr.n_cig; if (want_seq) wpp->n_seq += (rr.l_seq + 1) / 2; }
+        if (ctg >= 0) { wpp->n_out++; wpp->n_cig += rr.n_cig; if (want_seq) wpp->n_seq += (rr.l_seq + 1) / 2; wpp->n_name += r[8]; }
         wpp->recs.push_back(rr);
         o += 4 + (size_t)bs;
     }
@@ -848,10 +860,20 @@ static bool device_parse_now(xck_bam* b, const ContigMap& cm, const xck_ingest_o
     const bool same = gi.d_cm && gi.cm_tend == tend && gi.cm_host.size() == n * (tend ? 2 : 1) && memcmp(gi.cm_host.data(), cm.t2c, n * 4) == 0 &&
                       (!tend || memcmp(gi.cm_host.data() + n, cm.t_end, n * 4) == 0);
     if (!same) {
-        void* d = dev_parse_upload(gi.device, cm.t2c, n * 4, cm.t_end, tend ? n * 4 : 0);
-        if (!d) { gi.parse_off = true; return false; }
         gi.cm_host.assign(cm.t2c, cm.t2c + n); if (tend) gi.cm_host.insert(gi.cm_host.end(), cm.t_end, cm.t_end + n);
-        gi.d_cm = (int32_t*)d; gi.cm_tend = tend; gi.d_cm_all.push_back(d);
+        // the per-cell BAMs of a well-based run bring the same tables file after file: a table uploaded once is shared by the readers
+        // that follow (an allocation and, at close, a free - which waits for the whole device, the next files' inflate kernels
+        // included - per file otherwise).  The few shared tables live until the process ends, so no walk in flight outlives one.
+        void* d = nullptr; bool shared = false;
+        { std::lock_guard<std::mutex> lk(g_scratch_mu);
+          for (const CmShared& c : g_cm_shared) if (c.device == gi.device && c.tend == tend && c.host == gi.cm_host) { d = c.d; shared = true; break; } }
+        if (!d) {
+            d = dev_parse_upload(gi.device, cm.t2c, n * 4, cm.t_end, tend ? n * 4 : 0);
+            if (!d) { gi.parse_off = true; gi.cm_host.clear(); return false; }
+            std::lock_guard<std::mutex> lk(g_scratch_mu);
+            if (g_cm_shared.size() < 8) { g_cm_shared.push_back(CmShared{gi.device, tend, gi.cm_host, d}); shared = true; }
+        }
+        gi.d_cm = (int32_t*)d; gi.cm_tend = tend; if (!shared) gi.d_cm_all.push_back(d);
     }
     return true;
 }
@@ -933,7 +955,7 @@ static void schedule_chunk(xck_bam* b, Chunk& c, int ci, bool verify_crc, bool c
         wp.i0 = i0; wp.i1 = i1;
         wp.u_begin = c.blocks[i0].uoff; wp.u_end = c.blocks[i1 - 1].uoff + c.blocks[i1 - 1].isize;
         wp.spec_start = wp.u_begin + (pi == 0 ? skip0 : 0); wp.stop = wp.spec_start; wp.recs.clear();
-        wp.n_out = wp.n_cig = wp.n_seq = 0; wp.runs.clear();
+        wp.n_out = wp.n_cig = wp.n_seq = wp.n_name = 0; wp.runs.clear();
         Chunk* cp = &c; const uint8_t* map = b->map; WalkPart* wpp = &wp; DecodeTimes* tmp_ = &b->tm; std::atomic<int64_t>* ds = b->dstat;
         if (!gs) { c.tg.later([cp, map, verify_crc, wpp, tmp_, cm, want_seq, ds] { run_part(cp, map, verify_crc, wpp, tmp_, cm, want_seq, nullptr, ds); }); continue; }
         GpuShare* gip = &gi; const size_t nb_ = nb, usz_ = usz;
@@ -1105,6 +1127,20 @@ static void parse_part(xck_bam* b, xck_engine* e, HostSoA* sp, int32_t sample, c
         co += rr.n_cig; if (dc.want_seq) so += (rr.l_seq + 1) / 2;
         o++;
     }
+    if (s.has_names) {
+        // device-names mode: no host table.  One item per kept record of the piece (len 0: the key parse_record wrote is final) and the
+        // bytes of the names to intern, packed into the piece's share of the block's trailer; the device table keys them behind the copy
+        DiItem* it0 = s.items + wp->out_base;
+        memset(it0, 0, wp->n_out * sizeof(DiItem));
+        size_t at = wp->name_base; const size_t end = wp->name_base + wp->n_name;
+        for (const InternTable::Item& it : names) {
+            if (at + it.n > end) { flags->fetch_or(1); break; }            // (never: n_name counts every name with its NUL)
+            memcpy(s.name_bytes + at, it.s, it.n);
+            s.items[it.out - s.umi] = DiItem{(uint32_t)at, it.n};
+            at += it.n;
+        }
+        return;
+    }
     if (!names.empty()) { bool ovf = false; e->intern.intern_batch(names, &ovf); if (ovf) flags->fetch_or(2); }
 }
 
@@ -1131,6 +1167,7 @@ static ChunkJob* take_job(xck_engine* e, xck_bam* b) {
     b->n_jobs++; b->cur = &j;
     if (j.soa.fence) fence_wait(j.soa.fence);                           // the H2D copy that last read this block has completed
     j.e = e; j.flags.store(0); j.parsed.store(0); j.ring_idx = -1; j.batches.clear(); j.dev = false;
+    j.b = b; j.names = e->names_mode && b->defer_parse;                          // (xck_ingest_bam on a handle in device-names mode)
     return &j;
 }
 // what a chunk's parse tasks reported (flags 1 / 2: parse_record; a task that threw) -> error code and text, 0 if nothing.  Call after tg.wait().
@@ -1168,7 +1205,7 @@ void Pusher::run() {
             // a chunk the device walked: the parse kernel writes its SoA block into the engine's staging slot and the batches follow - no
             // parse task, no copy.  A chunk that kernel flags (1) takes the host path here, late but in file order.
             xck_bam* b = j->b; GpuInflateSlot* gs = b->gi.slot[j->ring_idx];
-            try { r = xck::engine_push_parsed(j->e, gs, b->ch[j->ring_idx].blocks.size(), j->lay.max_rec, j->lay.n_out, j->lay.n_cig, j->lay.n_seq, j->opts.sample, j->lay.batches.data(), (int)j->lay.batches.size()); }
+            try { r = xck::engine_push_parsed(j->e, gs, b->ch[j->ring_idx].blocks.size(), j->lay.max_rec, j->lay.n_out, j->lay.n_cig, j->lay.n_seq, j->opts.sample, j->lay.batches.data(), (int)j->lay.batches.size(), b->ch[j->ring_idx].usize); }
             catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
             push_parsed_ns += ns_since(t0); push_ns += ns_since(t0);
             if (r == 1) { count_parse_fallback(b); r = redo_on_host(j, &msg); host_chunk = r == 0; }
@@ -1188,7 +1225,9 @@ void Pusher::run() {
             xck_engine* e = j->e; HostSoA& s = j->soa;
             std::vector<xck_batch> bts(j->batches.size());
             for (size_t i = 0; i < bts.size(); i++) fill_batch(s, j->batches[i], e->dec.want_seq, &bts[i]);
-            try { r = xck::engine_push_block(e, s.base, s.used, bts.data(), (int)bts.size(), &s.fence); } catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
+            const bool names = j->names && s.has_names && s.nt.n_out > 0;
+            if (names && j->b) j->b->dstat[DS_NAMES_HOST_CHUNKS].fetch_add(1, std::memory_order_relaxed);
+            try { r = xck::engine_push_block(e, s.base, s.used, bts.data(), (int)bts.size(), &s.fence, names ? &s.nt : nullptr); } catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
             if (r) msg = e->err;
             push_ns += ns_since(t0);
         }
@@ -1254,15 +1293,19 @@ struct PhaseClock {
 
 // Stage 1, at the first call of a reader (decode or prefetch): the index ranges to read, whether the GPU takes a share of the inflate,
 // the NUMA binding, the scanner thread.
-static void begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only) {
+static int begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only) {
     if (!schedule_only && !b->started) {
         b->started = true;
         // well mode without UMIs: the key is the read name and the column is the BAM itself, so names only have to be unique within one file -
         // restart the intern table per BAM (bounded memory for 384 x 2 M reads).  (At the first DECODE call, not at xck_bam_prefetch: the file
         // before this one may still be parsing.)
-        if (!e->dec.use_barcodes && !e->dec.use_umi) e->intern.clear();
+        if (!e->dec.use_barcodes && !e->dec.use_umi) {
+            e->intern.clear();
+            // (device-names mode: the device table with it, stream-ordered on the stream its kernels run on; both kinds of decode call may start over)
+            if (e->names_mode) { if (const int rc = engine_names_clear(e)) { b->err = e->err; return rc; } e->names_calls = 0; }
+        }
     }
-    if (b->ranges_set) return;
+    if (b->ranges_set) return 0;
     set_ranges(b, o);
     GpuShare& gi = b->gi;
     if (!gi.tried) {                                           // GPU share of the inflate: a handle with a device, XCK_GPU_INFLATE > 0, no host-only CRC checks asked for
@@ -1280,7 +1323,8 @@ static void begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bo
             // XCK_GPU_PARSE: walk and parse these chunks on the device too - where the key is a UMI tag (read names are interned on the
             // host) and every barcode fits a slot of the barcode table, which the kernel probes as it is
             bool fits = true; for (const std::string& bc : e->dec.barcodes) fits = fits && bc.size() <= sizeof(DecodeCfg::BcSlot::key);
-            gi.parse = e->knobs.gpu_parse && e->dec.use_umi && fits;
+            // (... or, in device-names mode, the read name: the handle's device table interns it, csrc/intern_dev.hip)
+            gi.parse = e->knobs.gpu_parse && (e->dec.use_umi || e->names_mode) && fits;
         }
     }
     bind_to_numa_node(e, b);                                   // (before the scanner thread is made: it inherits the mask)
@@ -1288,12 +1332,14 @@ static void begin_decode(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bo
     if (b->use_ranges) for (auto& r : b->ranges) rg.push_back({r.first >> 16, (uint32_t)(r.first & 0xffff), r.second >> 16});
     else rg.push_back({b->next_coff, b->first_skip, ~0ull});
     b->scanner = new Scanner(b->map, b->fsize, b->chunk_target, rg);
+    return 0;
 }
 
 // Stage 2, keep the ring full: while the head chunk is stitched and parsed the pool inflates the next ones
 static void fill_ring(xck_engine* e, xck_bam* b, const ContigMap& cm, const xck_ingest_opts* o) {
     reap_jobs(b);
-    const bool dev_parse = device_parse_now(b, cm, o);
+    // (read-name keys come from the device only for xck_ingest_bam: a reader used through xck_bam_next_batch keeps the host's table and walk)
+    const bool dev_parse = (e->dec.use_umi || b->defer_parse) && device_parse_now(b, cm, o);
     // (the chunks behind `head` that a parse in flight still reads must not be scheduled over: `back` = how far the oldest of them lies behind)
     int back = 0;
     for (auto& j : b->jobs) if (!j.released) back = std::max(back, (b->head - j.ring_idx + b->n_ring) % b->n_ring);
@@ -1368,7 +1414,7 @@ static int stitch_serially(xck_bam* b, Chunk& c, const ContigMap& cm, const xck_
         const RecRef rr{r, len, (int32_t)le32(r), le32(r + 16), le16(r + 12)};
         const int32_t ctg = cm(rr.tid, (int32_t)le32(r + 4));
         if (ctg != cur_c) { wp.runs.push_back({(uint32_t)wp.recs.size(), ctg}); cur_c = ctg; }
-        if (ctg >= 0) { wp.n_out++; wp.n_cig += rr.n_cig; if (want_seq) wp.n_seq += (rr.l_seq + 1) / 2; }
+        if (ctg >= 0) { wp.n_out++; wp.n_cig += rr.n_cig; if (want_seq) wp.n_seq += (rr.l_seq + 1) / 2; wp.n_name += r[8]; }
         wp.recs.push_back(rr);
     };
     c.stitch.clear();
@@ -1434,11 +1480,12 @@ static int stitch_chunk(xck_bam* b, Chunk& c, const ContigMap& cm, const xck_ing
 // Stage 5, layout: where every piece's records go in the job's SoA block (prefix sums over the pieces), and the batches - runs of
 // records on one contig, across piece boundaries.  Returns the number of records of the chunk (kept or not), < 0 on error.
 static int64_t layout_chunk(ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq, int64_t records_before, std::string* err) {
-    size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0;
-    for (WalkPart& wp : pieces) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_rec += wp.recs.size(); }
+    size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0, n_name = 0;
+    for (WalkPart& wp : pieces) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; wp.name_base = n_name; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_name += wp.n_name; n_rec += wp.recs.size(); }
     if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
     HostSoA& s = j.soa;
-    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) { *err = "out of host memory"; return XCK_E_NOMEM; }
+    if (n_name >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
+    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1, n_out, n_name, j.names)) { *err = "out of host memory"; return XCK_E_NOMEM; }
     s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
     const uint64_t ord_hi = (uint64_t)(uint32_t)o->sample << ORD_REC_BITS;
     int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0, rec0 = 0;
@@ -1543,7 +1590,7 @@ static int redo_on_host(ChunkJob* j, std::string* msg) {
 static int decode_next_chunk(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, bool schedule_only = false) {
     const bool has_win = o->struct_size >= offsetof(xck_ingest_opts, tid_end) + sizeof(void*);
     ContigMap cm; cm.t2c = o->tid_to_contig; cm.n_refs = (int)b->ref_names.size(); cm.t_end = has_win ? o->tid_end : nullptr;
-    begin_decode(e, b, o, schedule_only);
+    if (const int rc0 = begin_decode(e, b, o, schedule_only)) return rc0;
     PhaseClock clk;
     int rc;
     do {
@@ -1615,14 +1662,27 @@ struct FoldDecodeStats {
     }
 };
 
+// Device-names mode (XCK_GPU_NAMES): xck_ingest_bam keys read names by the handle's device table, xck_bam_next_batch by the host's - ids
+// of the two do not compare, so between two clears of the table a handle serves one kind of call (1 = ingest, 2 = next_batch) only.
+static int names_state_check(xck_engine* e, xck_bam* b, int kind) {
+    if (!e->names_mode) return 0;
+    const bool clears = !b->started && !e->dec.use_barcodes && !e->dec.use_umi;   // (begin_decode empties both tables for this reader)
+    if (clears || !(e->names_calls & (3 - kind))) return 0;
+    e->err = kind == 2 ? "xck_bam_next_batch after xck_ingest_bam on a handle in device-names mode (XCK_GPU_NAMES): read names are keyed by the device table there and by the host table here; call xck_reset first"
+                       : "xck_ingest_bam after xck_bam_next_batch on a handle in device-names mode (XCK_GPU_NAMES): read names are keyed by the host table there and by the device table here; call xck_reset first";
+    return XCK_E_STATE;
+}
+
 static int next_batch_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, xck_batch* out) {
     if (!e || !b || !o || !out) return XCK_E_ARG;
     CallerBinding on_node(b);
     FoldDecodeStats fold{e, b};
     b->defer_parse = false;                                            // (this interface hands out finished batches: parse in place)
+    if (const int src = names_state_check(e, b, 2)) return src;
     while (!b->cur || b->cur->batches.empty()) {
         if (b->done) return 0;
         int rc = decode_next_chunk(e, b, o);
+        if (e->names_mode) e->names_calls |= 2;
         if (rc < 0) { e->err = b->path + ": " + b->err; return rc; }
         if (rc == 0) { b->done = true; return 0; }
     }
@@ -1645,10 +1705,12 @@ static int ingest_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, int6
     const int64_t pause = o->struct_size >= offsetof(xck_ingest_opts, pause_records) + sizeof(int64_t) ? o->pause_records : 0;
     const int64_t start = b->n_records;
     b->defer_parse = e->n_impl > 0;                                    // (a decode-only handle decodes in place and discards: host-ingest benchmarks)
+    if (const int src = names_state_check(e, b, 1)) return src;
     auto fail = [&](int rc) { rc = drain_ingest(b, rc); e->err = b->path + ": " + b->err; return rc; };
     try {
         while (!b->done) {
             const int rc = decode_next_chunk(e, b, o);
+            if (e->names_mode) e->names_calls |= 1;
             if (rc < 0) return fail(rc);
             if (rc == 0) { b->done = true; break; }
             if (!b->defer_parse) b->cur->batches.clear();
@@ -1656,6 +1718,8 @@ static int ingest_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, int6
         }
     } catch (...) { drain_ingest(b, 0); throw; }                       // (XCK_GUARD makes an error code of it: no job may stay with the push thread)
     if (const int drc = drain_ingest(b, 0)) return fail(drc);          // (the caller may talk to the engine now: nothing is in flight)
+    // device-names mode: the intern kernels behind the host-parsed chunks were not waited for - what they flagged (the id space used up) fails the call
+    if (e->names_mode) { if (const int nrc = engine_names_check(e)) { b->err = e->err; return fail(nrc); } }
     if (n_records) *n_records = b->n_records;
     return b->done ? XCK_OK : 1;
 }
@@ -1680,6 +1744,7 @@ static int prefetch_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o) {
     CallerBinding on_node(b);
     FoldDecodeStats fold{e, b};
     b->prefetching = true;
+    if (e->names_mode) b->defer_parse = e->n_impl > 0;                 // (device-names mode: the chunks read ahead are walked on the device, as xck_ingest_bam will want them)
     const int rc = decode_next_chunk(e, b, o, true);
     b->prefetching = false;
     if (rc < 0) { e->err = b->path + ": " + b->err; return rc; }

@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include "engine_impl.h"
 #include "parse_dev.h"
+#include "intern_dev.h"
 
 namespace xck {
 #ifndef XCK_WS_SNP
@@ -1212,15 +1213,20 @@ int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident) {
 
 // ---- host ingest: one decoded chunk = one staging slot, shared by every pipeline of the handle (which has at least one) ----
 // the next staging slot, grown to `bytes`, once every launch that still reads it has been confirmed
-static int stager_take(xck_engine* e, size_t bytes, int* si_out) {
+static int stager_get(xck_engine* e) {
     EngineImpl* im = e->impls[0];                                        // (errors of the shared part are reported through it)
     HIP_TRY(hipSetDevice(im->device));
-    Stager* st = e->stager;
-    if (!st) {
-        st = new Stager(); st->device = im->device; e->stager = st;
+    if (!e->stager) {
+        Stager* st = new Stager(); st->device = im->device; e->stager = st;
         HIP_TRY(hipStreamCreateWithFlags(&st->s_copy, hipStreamNonBlocking));
         for (auto& sl : st->slot) { HIP_TRY(hipEventCreate(&sl.t0)); HIP_TRY(hipEventCreate(&sl.copied)); }
     }
+    return 0;
+}
+static int stager_take(xck_engine* e, size_t bytes, int* si_out) {
+    EngineImpl* im = e->impls[0];
+    if (int rc = stager_get(e)) return rc;
+    Stager* st = e->stager;
     const int si = st->next; st->next = (st->next + 1) % 3;
     Stager::Slot& sl = st->slot[si];
     for (int k = 0; k < e->n_impl && sl.users > 0; k++)                  // launches that still read this slot: confirm them
@@ -1263,15 +1269,71 @@ static int push_staged(xck_engine* e, int si, const xck_batch* batches, int n, D
     return XCK_OK;
 }
 
+// ---- device-names mode (intern_dev.h): the handle's table lives with the staging, its kernels run on the copy stream ----
+static int names_table(xck_engine* e) {
+    if (e->dnames) return 0;
+    const Knobs& k = e->knobs;
+    e->dnames = dev_intern_create(e->impls[0]->device, (size_t)std::max(64ll, k.gpu_names_slots0), (size_t)std::max(1024ll, k.gpu_names_arena0), k.names_hash_bits, k.debug_timing);
+    return 0;
+}
+// what a reserve or a launch of the table answered -> the ingest's error
+static int names_error(xck_engine* e, int rc) {
+    if (rc == XCK_E_NOMEM) e->err = "out of device memory for the read-name table (XCK_GPU_NAMES)";
+    else if (rc) e->err = "device error in the read-name table (XCK_GPU_NAMES)";
+    return rc;
+}
+// ... what its kernels flagged, once the copy stream was waited for behind them
+static int names_flags(xck_engine* e) {
+    const uint32_t fl = dev_intern_synced(e->dnames);
+    if (fl & DI_F_FULL) { e->err = "the read-name table on the device ran out of room (XCK_GPU_NAMES)"; return XCK_E_DEVICE; }
+    if (fl & DI_F_CAPACITY) { e->err = "too many distinct non-ACGT keys for the key width"; return XCK_E_CAPACITY; }
+    return 0;
+}
+int engine_names_clear(xck_engine* e, bool zero_stats) {
+    if (!e->names_mode || !e->dnames || e->n_impl <= 0) return 0;
+    if (int rc = stager_get(e)) return rc;
+    if (int rc = dev_intern_clear(e->dnames, e->stager->s_copy)) return names_error(e, rc);
+    if (zero_stats) dev_intern_zero_stats(e->dnames);
+    return 0;
+}
+int engine_names_check(xck_engine* e) {
+    if (!e->names_mode || !e->dnames || !e->stager) return 0;
+    EngineImpl* im = e->impls[0];
+    HIP_TRY(hipSetDevice(im->device));
+    HIP_TRY(hipStreamSynchronize(e->stager->s_copy));
+    return names_flags(e);
+}
+void engine_names_stats(const xck_engine* e, int64_t* interned, int64_t* distinct) {
+    *interned = 0; *distinct = 0;
+    if (e->dnames) dev_intern_stats(e->dnames, interned, distinct);
+}
+void engine_names_report(xck_engine* e) {                                // XCK_DEBUG_TIMING, at xck_destroy
+    const DevIntern* t = e->dnames;
+    if (!t || !t->d_ctl) return;
+    int64_t lk = 0, di = 0; dev_intern_stats(t, &lk, &di);
+    fprintf(stderr, "[xck] read names on the device: %lld looked up, %lld distinct | table %zu slots, arena %.1f MB (%.1f MB used), grown %d times | intern kernels %.1f ms (those a wait followed)\n",
+            (long long)lk, (long long)di, t->n_slots, t->cap_words * 4e-6, t->exact_words * 4e-6, t->growths, t->kernel_ms);
+}
+
 // a chunk the host decoded: ONE H2D copy of its block into the slot
-int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence) {
+int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence, const NameTrailer* names) {
     int si = 0;
     if (int rc = stager_take(e, bytes, &si)) return rc;
     EngineImpl* im = e->impls[0];
     Stager* st = e->stager; Stager::Slot& sl = st->slot[si];
     if (!*fence) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); *fence = (void*)ev; }
+    if (names && names->n_out) {                                         // (before the copy is queued: growing the table waits for the stream)
+        if (names->items_off + names->n_out * sizeof(DiItem) > bytes || names->bytes_off + names->n_bytes > bytes) { e->err = "internal: name trailer outside its block"; return XCK_E_ARG; }
+        if (int rc = names_table(e)) return rc;
+        if (int rc = dev_intern_reserve(e->dnames, st->s_copy, names->n_out, names->n_bytes)) return names_error(e, rc);
+    }
     HIP_TRY(hipEventRecord(sl.t0, st->s_copy));
     HIP_TRY(hipMemcpyAsync(sl.buf, host_base, bytes, hipMemcpyHostToDevice, st->s_copy));
+    if (names && names->n_out) {
+        // the keys of the chunk's names, into the staged umi column (soa_layout: at the block's start), before `copied`
+        if (int rc = dev_intern_launch_items(e->dnames, st->s_copy, (const DiItem*)(sl.buf + names->items_off), (const uint8_t*)(sl.buf + names->bytes_off), names->n_bytes,
+                                             (uint64_t*)sl.buf, names->n_out, e->dec.umi_bits, intern_id_limit(e->dec.umi_bits))) return names_error(e, rc);
+    }
     HIP_TRY(hipEventRecord(sl.copied, st->s_copy));
     HIP_TRY(hipEventRecord((hipEvent_t)*fence, st->s_copy));
     sl.timed = true;
@@ -1284,7 +1346,7 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
 // A chunk the device inflated and walked (csrc/parse_dev.hip): no copy - the parse kernel writes the chunk's SoA block straight into the
 // slot, in the place of the H2D copy (same stream, same event), and the batches follow as above.  The kernel's flags are waited for
 // before anything is queued: 1 = it met a record it leaves to the host (nothing was queued; the caller takes the host path).
-int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* dbs, int n) {
+int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* dbs, int n, size_t chunk_bytes) {
     const DecodeCfg& dc = e->dec;
     const SoaLayout lay = soa_layout(n_out + 1, n_cig + 1, dc.want_seq ? n_seq + 1 : 1);
     int si = 0;
@@ -1299,12 +1361,22 @@ int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks,
     DpParseCfg pc; memset(&pc, 0, sizeof pc);
     pc.bc = (const DpBcSlot*)st->d_bc; pc.bc_mask = dc.bc_mask; pc.use_barcodes = dc.use_barcodes; pc.want_seq = dc.want_seq; pc.umi_bits = dc.umi_bits; pc.sample = sample;
     memcpy(pc.cell_tag, dc.cell_tag, 2); memcpy(pc.umi_tag, dc.umi_tag, 2);
+    const bool names = e->names_mode && n_out > 0;
+    pc.names = e->names_mode ? 1 : 0;
+    if (names) {                                                         // room for the chunk's names: a kept record has 36 bytes besides its name
+        if (int rc = names_table(e)) return rc;
+        const size_t name_bytes = std::min<size_t>(n_out * 254, chunk_bytes > n_out * 36 ? chunk_bytes - n_out * 36 : 0);
+        if (int rc = dev_intern_reserve(e->dnames, st->s_copy, n_out, name_bytes)) return names_error(e, rc);
+    }
     HIP_TRY(hipEventRecord(sl.t0, st->s_copy));
     // (a launch that fails - dev_parse_launch has taken the error - wrote nothing into the slot: the chunk takes the host path, whose
     // copy of the chunk's bytes reports a device that is gone)
     if (dev_parse_launch(st->s_copy, gs, n_blocks, max_rec, pc, (uint8_t*)sl.buf, n_out, n_cig, n_seq) != 0) return 1;
+    // (the read names' keys behind the parse, same stream: the umi column is final before `copied`)
+    if (names) { if (int rc = dev_intern_launch_recs(e->dnames, st->s_copy, gs, n_blocks, max_rec, (uint64_t*)(sl.buf + lay.o_umi), n_out, dc.umi_bits, intern_id_limit(dc.umi_bits))) return names_error(e, rc); }
     HIP_TRY(hipEventRecord(sl.copied, st->s_copy));
     HIP_TRY(hipEventSynchronize(sl.copied));
+    if (names) { if (int rc = names_flags(e)) return rc; }
     if (gs->h_head->parse_flags) return 1;
     std::vector<xck_batch> bts((size_t)n);                               // (column pointers: already the slot's)
     for (int i = 0; i < n; i++) {
@@ -1326,6 +1398,7 @@ void engine_release_staging(xck_engine* e) {
     if (st->s_copy) hipStreamSynchronize(st->s_copy);
     for (auto& sl : st->slot) { if (sl.buf) hipFree(sl.buf); if (sl.t0) hipEventDestroy(sl.t0); if (sl.copied) hipEventDestroy(sl.copied); }
     if (st->d_bc) hipFree(st->d_bc);
+    if (e->dnames) { if (e->knobs.debug_timing) engine_names_report(e); dev_intern_destroy(e->dnames); e->dnames = nullptr; }
     if (st->s_copy) hipStreamDestroy(st->s_copy);
     delete st; e->stager = nullptr;
 }

@@ -108,6 +108,7 @@ struct DpParseCfg {
     const DpBcSlot* bc; uint64_t bc_mask;  // barcode table in device memory (bc == nullptr: empty list)
     int32_t use_barcodes, want_seq, umi_bits, sample;
     char cell_tag[2], umi_tag[2];
+    int32_t names;                         // device-names mode (intern_dev.h): no UMI tag is looked for and the umi column is left to k_intern_recs
 };
 
 }  // namespace xck

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include "../../include/xck.h"
 #include "parse_dev.h"
+#include "intern_dev.h"
 
 namespace xck {
 
@@ -84,14 +85,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan(const DpCnt* __restrict__ cnt, 
 }
 
 // ---- parse -------------------------------------------------------------------------------------------------------------------------
-// bam.cpp hash_bytes, byte for byte
-__device__ inline uint64_t dp_hash_bytes(const uint8_t* s, uint32_t n) {
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)n * 0xff51afd7ed558ccdull);
-    while (n >= 8) { uint64_t w = 0; for (int k = 0; k < 8; k++) w |= (uint64_t)s[k] << (8 * k); h = (h ^ w) * 0xbf58476d1ce4e5b9ull; h ^= h >> 32; s += 8; n -= 8; }
-    if (n) { uint64_t w = 0; for (uint32_t k = 0; k < n; k++) w |= (uint64_t)s[k] << (8 * k); h = (h ^ w) * 0x94d049bb133111ebull; }
-    h ^= h >> 29; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 32;
-    return h;
-}
+// (dp_hash_bytes = bam.cpp hash_bytes and dp_encode_direct = its encode_key_direct: intern_dev.h, which the name kernels share)
 // DecodeCfg::lookup_cell for lists whose barcodes all fit a slot's key (the device path is on only then): same hash, same probe order
 __device__ inline int32_t dp_lookup_cell(const DpParseCfg& cfg, const uint8_t* s, size_t n) {
     if (!cfg.bc) return -1;
@@ -184,7 +178,7 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
                 if (cfg.want_seq) { seq_src = rr.off + (uint32_t)q; seq_len = (l_seq + 1) / 2; }
                 q += (long long)((l_seq + 1) / 2) + l_seq;
                 // aux tags: first occurrence wins; the scan ends when both are found or a value cannot be skipped
-                long long cb = -1, ub = -1; bool need_cb = cfg.use_barcodes != 0, need_ub = true; long long a = q;
+                long long cb = -1, ub = -1; bool need_cb = cfg.use_barcodes != 0, need_ub = cfg.names == 0; long long a = q;   // (names: the key is the read name, k_intern_recs writes it)
                 while ((need_cb || need_ub) && a >= 0 && a + 3 <= end) {
                     if (need_cb && r[a] == (uint8_t)cfg.cell_tag[0] && r[a + 1] == (uint8_t)cfg.cell_tag[1]) { cb = a + 2; need_cb = false; }
                     else if (need_ub && r[a] == (uint8_t)cfg.umi_tag[0] && r[a + 1] == (uint8_t)cfg.umi_tag[1]) { ub = a + 2; need_ub = false; }
@@ -202,19 +196,10 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
                 if (ub >= 0) {
                     if (r[ub] == 'Z' || r[ub] == 'A' || r[ub] == 'H') {
                         const size_t n = r[ub] == 'A' ? 1 : dp_strnlen(r, ub + 1, end);
-                        if (n != 0) {                                       // encode_key_direct: empty -> NONE, short ACGT -> 2-bit code
-                            bool ok = 2 * (long long)n + 1 <= (long long)cfg.umi_bits - 1;
-                            uint64_t v = 1;
-                            for (size_t k = 0; ok && k < n; k++) {
-                                const uint8_t ch = r[ub + 1 + (long long)k];
-                                const uint32_t code = ch == 'A' ? 0u : ch == 'C' ? 1u : ch == 'G' ? 2u : ch == 'T' ? 3u : 4u;
-                                ok = code < 4u; v = (v << 2) | (code & 3u);
-                            }
-                            if (ok) key = v; else fl |= DP_F_UMI;
-                        }
+                        if (!dp_encode_direct(r + ub + 1, n, cfg.umi_bits, &key)) { key = XCK_UMI_NONE; fl |= DP_F_UMI; }   // (the host interns it)
                     } else fl |= DP_F_UMI;                                  // numeric tag: its key is interned on the host
                 }
-                c_umi[o] = key;
+                if (!cfg.names) c_umi[o] = key;
             }
         }
         // the CIGAR words and sequence bytes of the round, all lanes together

@@ -117,16 +117,25 @@ struct Knobs {
     bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
     int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
     bool gpu_parse = true;               // XCK_GPU_PARSE=auto|0: walk and parse the GPU-inflated chunks on the device where that applies (bam.cpp device_parse_now)
+    bool gpu_names = false;              // XCK_GPU_NAMES=1: read names of a UMI-less handle are interned on the device (intern_dev.h; the conditions: api.cpp xck_create)
+    long long gpu_names_slots0 = 1 << 21;   // XCK_GPU_NAMES_SLOTS0: first size of the device table (slots; tests: 64 makes a small file grow it several times)
+    long long gpu_names_arena0 = 64 << 20;  // XCK_GPU_NAMES_ARENA0: first size of its arena (bytes)
+    int  names_hash_bits = 0;            // XCK_TEST_NAMES_HASH_BITS: the device table keeps only that many low hash bits (0 = all)
     int  verify_crc = 0;                 // XCK_VERIFY_CRC: 0 = as the flags say, 1 = host (XCK_F_VERIFY_CRC ORed in), 2 = device (XCK_F_DEVICE_CRC)
     static Knobs from_env();             // api.cpp
 };
 
 // xck_decode_stats counters (include/xck.h), in this order.  A reader counts in its own set; every decode call adds what it counted
 // since the last call to its handle's (bam.cpp fold_decode_stats).
-enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_PARSE_CHUNKS, DS_PARSE_FALLBACKS, DS_N };
+enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_PARSE_CHUNKS, DS_PARSE_FALLBACKS, DS_NAMES_INTERNED, DS_NAMES_DISTINCT, DS_NAMES_HOST_CHUNKS, DS_N };
+// (DS_NAMES_INTERNED / DS_NAMES_DISTINCT are the device table's own counters: xck_get_decode_stats asks the table)
 
 struct EngineImpl;                       // one GPU pipeline of a handle (engine_impl.h)
 struct Stager;                           // device staging slots of engine_push_block (engine.hip)
+struct DevIntern;                        // the handle's intern table in HBM (intern_dev.h)
+uint64_t intern_id_limit(int umi_bits);  // ids an intern table may hand out for that key width (bam.cpp; XCK_TEST_INTERN_LIMIT)
+// the names a host-parsed chunk hands to the device table: DiItem[n_out] at items_off of its block, the packed bytes behind them
+struct NameTrailer { size_t items_off, bytes_off, n_bytes, n_out; };
 
 // the decoder's own batches are valid by construction and skip the O(n) check of xck_push_batch()
 int push_trusted(xck_engine* e, const xck_batch* b);
@@ -148,6 +157,9 @@ struct xck_engine {
     xck::Stager* stager = nullptr;       // device staging slots of engine_push_block
     struct PushRing { void* blk[3] = {nullptr, nullptr, nullptr}; size_t cap[3] = {0, 0, 0}; void* fence[3] = {nullptr, nullptr, nullptr}; int next = 0; } push_ring;   // pinned blocks of xck_push_batch's one-copy form (api.cpp)
     xck::Knobs knobs;                    // the environment, read once at xck_create
+    // device-names mode (XCK_GPU_NAMES, include/xck.h): set at xck_create for the handle's life.  names_calls: which decode calls the
+    // handle has seen since the table was last cleared (1 = xck_ingest_bam, 2 = xck_bam_next_batch): the two do not mix
+    bool names_mode = false; int names_calls = 0; xck::DevIntern* dnames = nullptr;
     std::atomic<int64_t> gpu_inflate_chunks{0};   // chunks inflated on the device by the readers that fed this handle (xck_stats)
     std::atomic<int64_t> dstat[xck::DS_N] = {};   // xck_decode_stats, summed over the readers that fed this handle since the last xck_reset
     int mode = 0;
@@ -184,11 +196,20 @@ int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE
 // asynchronous H2D copy into a device staging slot shared by the handle's pipelines, then the join kernel(s) on the batches.
 // *fence (created on first use) is recorded behind the copy: fence_wait() before the host block is overwritten.
-int  engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence);
+// names (device-names mode): the chunk's packed read names lie in the block too; their keys are written into the staged umi column
+// by the intern kernel, on the copy stream, before the batches are queued.
+int  engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence, const NameTrailer* names = nullptr);
 // One chunk the device inflated and walked (parse_dev.h): the parse kernel writes the chunk's SoA block into the staging slot - no copy -
 // and the batches follow as in engine_push_block.  1 = the kernel flagged the chunk and nothing was queued: the host path takes it.
 struct GpuInflateSlot; struct DpBatch;
-int  engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* batches, int n);
+// chunk_bytes: the chunk's inflated size (device-names mode: a bound on its name bytes)
+int  engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* batches, int n, size_t chunk_bytes);
+// device-names mode: empty the handle's table (stream-ordered on the copy stream; waits for what is in flight there first);
+// zero_stats (xck_reset): its counters start over too
+int  engine_names_clear(xck_engine* e, bool zero_stats = false);
+// ... wait for the intern kernels in flight and report what they flagged: 0, XCK_E_CAPACITY or XCK_E_DEVICE with e->err set
+int  engine_names_check(xck_engine* e);
+void engine_names_stats(const xck_engine* e, int64_t* interned, int64_t* distinct);
 void engine_release_staging(xck_engine* e);   // frees the staging slots (xck_destroy)
 void fence_wait(void* fence);
 void fence_destroy(void* fence);

@@ -478,7 +478,8 @@ class Engine(object):
         return {k: getattr(st, k) for k, _ in capi.Stats._fields_}
 
     def decode_stats(self):
-        """The BAM decoder's counters since the last reset (xck_get_decode_stats): GPU share of the inflate, CRC checks."""
+        """The BAM decoder's counters since the last reset (xck_get_decode_stats): GPU share of the inflate, CRC checks, chunks
+        walked and parsed on the device, read names interned on the device (XCK_GPU_NAMES)."""
         st = capi.DecodeStats()
         st.struct_size = C.sizeof(capi.DecodeStats)
         self._check(self.lib.xck_get_decode_stats(self.h, C.byref(st)), "xck_get_decode_stats")
