@@ -41,13 +41,13 @@ def expected_layout(n_regions, n_cells, n_snps=0):
 
 
 def intern_id_limit(umi_bits):
-    """Number of interned ids a UMI field of this width holds (bam.cpp intern_id_limit): the top bit marks an interned code and the all-ones
+    """Number of interned ids a UMI field of this width holds (bam_records.cpp intern_id_limit): the top bit marks an interned code and the all-ones
     code is kept free, for XCK_UMI_NONE at 64 bits and for the folds' empty word below."""
     return (1 << 63) - 1 if umi_bits >= 64 else (1 << (umi_bits - 1)) - 1
 
 
 def longest_direct(umi_bits):
-    """Longest UMI the decoder codes with 2 bits per base: 2 L + 1 <= umi_bits - 1 (bam.cpp encode_key_direct)."""
+    """Longest UMI the decoder codes with 2 bits per base: 2 L + 1 <= umi_bits - 1 (bam_records.cpp encode_key_direct)."""
     return (umi_bits - 2) // 2
 
 

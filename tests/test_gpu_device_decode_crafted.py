@@ -5,7 +5,7 @@ longest read name, contig changes and a contig the tables do not know inside one
 and, in a second file, the UMIs the device leaves to the host (too long, with N, lowercase, numeric).  Every such record is the only
 read of its (region, cell) pair and lies on a SNP, so its fate is one entry of `count` and of `ad` / `dp` (tests/device_decode_cases.py
 writes the files; tests/test_device_decode_cases_host.py checks on the CPU that they hold what they are meant to hold).
-The expected matrices are NOT csrc/bam.cpp parse_record's, which k_parse restates line by line: they are the oracle's
+The expected matrices are NOT csrc/bam_records.cpp parse_record's, which k_parse restates line by line: they are the oracle's
 (oracle/xck_oracle.c) on the records as oracle/pybam.py reads them.  Reference boundary: pysam's record iteration and get_tag
 (first occurrence of a tag, str for Z / A / H, the value for numeric types), as restated by oracle/pybam.py."""
 import pytest

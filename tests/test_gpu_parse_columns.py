@@ -1,5 +1,5 @@
 """Every column of every record: xck_gpu_parse_check (tools/gpu_parse_check.hip) runs inflate + walk + scan + parse on the device chunk
-by chunk and compares the nine SoA columns with what the host's parse_record (csrc/bam.cpp) writes for the same bytes - on synthetic
+by chunk and compares the nine SoA columns with what the host's parse_record (csrc/bam_records.cpp) writes for the same bytes - on synthetic
 files of the headline shape (levels 0 and 6), of the Cell Ranger shape and without tags, and on a crafted file with the records the
 synthetic ones do not hold (empty and one-record blocks, a record that fills its block, no CIGAR, no / odd-length sequence, CB of
 type A and H, B arrays ahead of CB, a duplicated tag, a Z value without its NUL, barcodes outside the list, a contig change inside a

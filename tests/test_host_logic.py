@@ -596,7 +596,7 @@ def test_convert_errors_and_feature_tables(tmp_path, capsys):
 
 # ---------------------------------------------------------------- untrusted input: the decoder under ASAN + UBSan (host-only build)
 def test_decoder_survives_corrupt_bams_under_sanitizers(tmp_path):
-    """tools/asan: csrc/bam.cpp + csrc/api.cpp built by g++ with -fsanitize=address,undefined (device side stubbed), run
+    """tools/asan: csrc/bam.cpp + csrc/bam_records.cpp + csrc/api.cpp built by g++ with -fsanitize=address,undefined (device side stubbed), run
     over BAMs whose record stream, compressed bytes, length or index were damaged: an error code or a decode, never a
     bad access (a sanitizer report aborts the harness).  Larger campaigns: tools/asan/mutate_bams.py with more seeds."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

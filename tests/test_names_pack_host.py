@@ -1,4 +1,4 @@
-"""The host code device-names mode adds to the decoder (csrc/bam.cpp: the walk's name byte counts, the trailer behind the SoA columns,
+"""The host code device-names mode adds to the decoder (csrc/bam_records.cpp: the walk's name byte counts, the trailer behind the SoA columns,
 parse_part's packing of the names it no longer interns), without a GPU: tools/asan/names_pack_check.cpp is a stand-alone program
 built with -fsanitize=address,undefined that lays out and parses random chunks with names of 0 to 254 bytes and checks that every
 kept record's item is what the device table needs - length 0 exactly where the key is final, otherwise the name's own bytes, inside

@@ -1,5 +1,5 @@
 """The host logic of the device parse path (csrc/parse_dev.h summaries_to_batches: per-block summaries of the device's record walk ->
-the chunk's batches) against the decoder's own layout (csrc/bam.cpp run_part + layout_chunk), without a GPU: tools/asan/
+the chunk's batches) against the decoder's own layout (csrc/bam_records.cpp run_part + layout_chunk), without a GPU: tools/asan/
 parse_layout_check.cpp is a stand-alone program built with -fsanitize=address,undefined that walks random chunks both ways - the
 summaries come from a host restatement of the walk kernel - and compares batch lists, ordinals, totals, per-batch sizes and the last
 record.  Reference boundary: none (the reference iterates records one by one); this pins two implementations of one layout."""

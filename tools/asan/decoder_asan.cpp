@@ -1,6 +1,6 @@
-// Host-only AddressSanitizer / UBSan harness for the BAM decoder (csrc/bam.cpp + csrc/api.cpp): the device side is
-// stubbed out, the handle is a decode-only one.  Every file given on the command line is opened and decoded to the
-// end in both modes (with and without sequences); corrupt input has to end in an error code, never in a bad access.
+// Host-only AddressSanitizer / UBSan harness for the BAM decoder (csrc/bam.cpp + csrc/bam_records.cpp + csrc/api.cpp): the device
+// side is stubbed out (engine_stubs.cpp, device_stubs.cpp), the handle is a decode-only one.  Every file given on the command line is
+// opened and decoded to the end in both modes (with and without sequences); corrupt input has to end in an error code, never in a bad access.
 // Each decode runs twice: batch by batch (xck_bam_next_batch: parse in place) and through xck_ingest_bam in slices with a
 // stand-in for engine_push_block - the path a GPU-backed handle takes (parse of a chunk and its push behind the coordinator
 // on the push thread, csrc/bam.cpp ChunkJob / Pusher); both must see the same records, field for field.
@@ -15,40 +15,8 @@
 #include "../../xcltk_amd/csrc/inflate_dev.h"
 #include "../../xcltk_amd/csrc/parse_dev.h"
 
-namespace xck {   // what engine.hip provides; never reached through a decode-only handle
-int  engine_create(const xck_config*, xck_engine*, EngineImpl**) { return XCK_E_ARG; }
-void engine_destroy(EngineImpl*) {}
-int  engine_push(EngineImpl*, const xck_batch*, bool) { return XCK_E_ARG; }
-int  engine_flush(EngineImpl*) { return XCK_E_ARG; }
-int  engine_finish(EngineImpl*, xck_result*) { return XCK_E_ARG; }
-int  engine_finish_async(EngineImpl*) { return XCK_E_ARG; }
-int  engine_result_device(EngineImpl*, xck_result*) { return XCK_E_ARG; }
-int  engine_refold(EngineImpl*, const xck_refold_config*, xck_result*) { return XCK_E_ARG; }
-int  engine_snp_counts(EngineImpl*, xck_result*) { return XCK_E_ARG; }
-int  engine_group_counts(EngineImpl*, int, int, const int32_t*, xck_result*, GroupTimes*) { return XCK_E_ARG; }
-int  local_phase_run(const xck_phase_problem*, const PhasePlan&, double, xck_phase_result**) { return XCK_E_DEVICE; }   // (local_phase.hip)
-void local_phase_free(xck_phase_result*) {}
-int  engine_reset(EngineImpl*) { return XCK_E_ARG; }
-int  engine_stats(const EngineImpl*, xck_stats*) { return XCK_E_ARG; }
-int  engine_read_fate(EngineImpl*, xck_read_fate*) { return XCK_E_ARG; }
-int  engine_cell_summary(EngineImpl*, xck_cell_summary*) { return XCK_E_ARG; }
-int  engine_feature_summary(EngineImpl*, xck_feature_summary*) { return XCK_E_ARG; }
-int  engine_numa_node(const xck_engine*) { return -1; }
-int  engine_device(const xck_engine*) { return -1; }                          // no device: the decoder's GPU share of the inflate never starts
-GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }
-void gpu_inflate_slot_destroy(GpuInflateSlot*) {}
-bool gpu_inflate_slot_reserve(GpuInflateSlot*, size_t, size_t, size_t) { return false; }
-int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool, const DpWalk*) { return -1; }
-// device walk + parse (csrc/parse_dev.hip): never reached without a device chunk
-int  dev_parse_copy_out(GpuInflateSlot*, size_t) { return -1; }
-void* dev_parse_upload(int, const void*, size_t, const void*, size_t) { return nullptr; }
-void dev_parse_free(int, void*) {}
-int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
-int  engine_names_clear(xck_engine*, bool) { return 0; }
-void engine_names_stats(const xck_engine*, int64_t* a, int64_t* b) { *a = 0; *b = 0; }
-int  engine_names_check(xck_engine*) { return 0; }
-int  gpu_inflate_slot_wait(GpuInflateSlot*) { return -1; }
-bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
+namespace xck {
+// (everything else the engine and the device decoder provide: engine_stubs.cpp, device_stubs.cpp - never reached through a decode-only handle)
 // stand-in for the engine's block push (called on the decoder's push thread): touches everything the batches claim to own
 static unsigned long long g_push_sum = 0; static long g_push_recs = 0;
 static unsigned long long batch_sum(const xck_batch& bt) {
@@ -65,11 +33,6 @@ int  engine_push_block(xck_engine*, const void* base, size_t bytes, const xck_ba
     }
     return XCK_OK;
 }
-void engine_release_staging(xck_engine*) {}
-void fence_wait(void*) {}
-void fence_destroy(void*) {}
-void* pinned_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }       // plain heap: ASAN sees every overrun
-void  pinned_free(void* p) { free(p); }
 }
 
 int main(int argc, char** argv) {

@@ -1,40 +1,19 @@
-// Host-only check of what device-names mode (XCK_GPU_NAMES) adds to the decoder's host code (csrc/bam.cpp), under AddressSanitizer /
+// Host-only check of what device-names mode (XCK_GPU_NAMES) adds to the decoder's host code (csrc/bam_records.cpp), under AddressSanitizer /
 // UBSan: random chunks of records with names of 0 to 254 bytes - some directly codable - are walked by the decoder's walk tasks, laid
 // out by layout_chunk with the name trailer behind the SoA columns, and parsed by parse_part, which packs the names instead of interning
 // them.  For every kept record the trailer must hold what the device table needs: an item of length 0 exactly where parse_record's key
 // is final (an empty or 2-bit codable name), otherwise the name's own bytes inside the block, no two names overlapping; the host table
-// stays empty.  No device, no HIP call: the device side of bam.cpp is stubbed out.
+// stays empty.  No device, no HIP call: the program links csrc/bam_records.cpp, and engine_stubs.cpp for the block's allocation and its fence.
 //   make -C tools/asan names_pack_check && tools/asan/names_pack_check
-#include "../../xcltk_amd/csrc/bam.cpp"
-
-namespace xck {   // what engine.hip / inflate_dev.hip / parse_dev.hip provide; none of it is reached here
-int  engine_numa_node(const xck_engine*) { return -1; }
-int  engine_device(const xck_engine*) { return -1; }
-GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }
-void gpu_inflate_slot_destroy(GpuInflateSlot*) {}
-bool gpu_inflate_slot_reserve(GpuInflateSlot*, size_t, size_t, size_t) { return false; }
-int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool, const DpWalk*) { return -1; }
-int  gpu_inflate_slot_wait(GpuInflateSlot*) { return -1; }
-bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
-int  dev_parse_copy_out(GpuInflateSlot*, size_t) { return -1; }
-void* dev_parse_upload(int, const void*, size_t, const void*, size_t) { return nullptr; }
-void dev_parse_free(int, void*) {}
-int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
-int  engine_names_clear(xck_engine*, bool) { return 0; }
-int  engine_names_check(xck_engine*) { return 0; }
-int  engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**, const NameTrailer*) { return XCK_E_ARG; }
-void fence_wait(void*) {}
-void fence_destroy(void*) {}
-void* pinned_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }
-void  pinned_free(void* p) { free(p); }
-}
+#include <cstdio>
+#include "../../xcltk_amd/csrc/bam_decode.h"
 
 static uint64_t g_rng = 0x13198A2E03707344ull;
 static uint32_t rnd(uint32_t n) { g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17; return (uint32_t)((g_rng >> 11) % n); }
 
 int main() {
     const int n_refs = 4, umi_bits = 38;
-    xck_bam* b = new xck_bam();
+    DecodeTimes tm;
     xck_engine e; e.dec.use_umi = false; e.dec.use_barcodes = false; e.dec.umi_bits = umi_bits;
     long chunks = 0, names = 0, direct = 0, empty = 0;
     for (int round = 0; round < 600; round++) {
@@ -68,7 +47,7 @@ int main() {
         for (size_t pi = 0; pi < n_parts; pi++) {
             WalkPart& wp = c.parts[pi]; wp.i0 = pi * per; wp.i1 = std::min<size_t>((size_t)nb, wp.i0 + per);
             wp.u_begin = blocks[wp.i0].uoff; wp.u_end = blocks[wp.i1 - 1].uoff + blocks[wp.i1 - 1].isize; wp.spec_start = wp.u_begin; wp.stop = wp.spec_start;
-            run_part(&c, nullptr, false, &wp, &b->tm, cm, want_seq, st.data(), ds);
+            run_part(&c, nullptr, false, &wp, &tm, cm, want_seq, st.data(), ds);
             if (wp.stop != wp.u_end) { fprintf(stderr, "round %d: the walk task did not reach its range's end\n", round); return 1; }
         }
         xck_ingest_opts o; memset(&o, 0, sizeof o); o.struct_size = sizeof o;
@@ -81,7 +60,7 @@ int main() {
             fprintf(stderr, "round %d: the trailer does not lie behind the columns\n", round); return 1; }
         memset(s.base + s.nt.items_off, 0xA5, s.used - s.nt.items_off);             // (whatever the tasks do not write shows)
         std::atomic<int> flags{0};
-        for (const WalkPart& wp : c.parts) if (wp.n_out) parse_part(b, &e, &s, 0, &wp, cm, &flags);
+        for (const WalkPart& wp : c.parts) if (wp.n_out) parse_part(&tm, &e, &s, 0, &wp, cm, &flags);
         if (flags.load() || e.intern.size() != 0) { fprintf(stderr, "round %d: parse flags %d, %llu names in the host table\n", round, flags.load(), (unsigned long long)e.intern.size()); return 1; }
         // ---- every kept record, in output order ----
         std::vector<uint8_t> used(s.nt.n_bytes, 0); size_t oi = 0;
@@ -103,7 +82,6 @@ int main() {
         chunks++;
         soa_free(j.soa);
     }
-    delete b;
     printf("%ld chunks: %ld names packed, %ld directly codable, %ld empty: all as the device table needs them\n", chunks, names, direct, empty);
     return names > 10000 && direct > 100 && empty > 100 ? 0 : 1;
 }

@@ -1,33 +1,11 @@
 // Host-only check of the device parse path's host logic (csrc/parse_dev.h summaries_to_batches) against the decoder's own layout
-// (csrc/bam.cpp run_part + layout_chunk), under AddressSanitizer / UBSan: random chunks of records are walked twice - by the decoder's
-// walk tasks, and by walk_block below, a host restatement of k_walk (csrc/parse_dev.hip) that fills the per-block summaries the kernel
-// writes - and the batch lists, ordinals, totals and per-batch sizes made of either must be the same.  No device, no HIP call: the
-// device side of bam.cpp is stubbed out.
+// (csrc/bam_records.cpp run_part + layout_chunk), under AddressSanitizer / UBSan: random chunks of records are walked twice - by the
+// decoder's walk tasks, and by walk_block below, a host restatement of k_walk (csrc/parse_dev.hip) that fills the per-block summaries the
+// kernel writes - and the batch lists, ordinals, totals and per-batch sizes made of either must be the same.  No device, no HIP call:
+// the program links csrc/bam_records.cpp, and engine_stubs.cpp for the block's allocation and its fence.
 //   make -C tools/asan parse_layout_check && tools/asan/parse_layout_check
-#include "../../xcltk_amd/csrc/bam.cpp"
-
-namespace xck {   // what engine.hip / inflate_dev.hip / parse_dev.hip provide; none of it is reached here
-int  engine_numa_node(const xck_engine*) { return -1; }
-int  engine_device(const xck_engine*) { return -1; }
-GpuInflateSlot* gpu_inflate_slot_create(int, int, bool) { return nullptr; }
-void gpu_inflate_slot_destroy(GpuInflateSlot*) {}
-bool gpu_inflate_slot_reserve(GpuInflateSlot*, size_t, size_t, size_t) { return false; }
-int  gpu_inflate_slot_launch(GpuInflateSlot*, size_t, size_t, size_t, bool, const DpWalk*) { return -1; }
-int  gpu_inflate_slot_wait(GpuInflateSlot*) { return -1; }
-bool gpu_inflate_slot_done(GpuInflateSlot*) { return true; }
-int  dev_parse_copy_out(GpuInflateSlot*, size_t) { return -1; }
-void* dev_parse_upload(int, const void*, size_t, const void*, size_t) { return nullptr; }
-void dev_parse_free(int, void*) {}
-int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
-int  engine_names_clear(xck_engine*, bool) { return 0; }
-void engine_names_stats(const xck_engine*, int64_t* a, int64_t* b) { *a = 0; *b = 0; }
-int  engine_names_check(xck_engine*) { return 0; }
-int  engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**, const NameTrailer*) { return XCK_E_ARG; }
-void fence_wait(void*) {}
-void fence_destroy(void*) {}
-void* pinned_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }
-void  pinned_free(void* p) { free(p); }
-}
+#include <cstdio>
+#include "../../xcltk_amd/csrc/bam_decode.h"
 
 // k_walk of one block, on the host: the same loop, the same summary
 static void walk_block(const uint8_t* u, uint32_t out_off, uint32_t out_len, uint32_t first_skip, const DpContigMap& cm, bool want_seq, DpBlockSum* sum) {

@@ -65,7 +65,7 @@ static bool run_list(const std::vector<std::string>& names, int launches, size_t
     return true;
 }
 
-// the host's rule for what needs no table (bam.cpp encode_key_direct)
+// the host's rule for what needs no table (bam_records.cpp encode_key_direct)
 static bool direct_key(const std::string& s, uint64_t* out) {
     if (s.empty()) { *out = XCK_UMI_NONE; return true; }
     if (2 * (int)s.size() + 1 > UMI_BITS - 1) return false;

@@ -1,26 +1,14 @@
-// xck_gpu_parse_check FILE.bam BARCODES.txt - the device's record walk and parse (csrc/parse_dev.hip) against the host's parse_record
-// (csrc/bam.cpp) on the same bytes: the file's BGZF blocks go through k_inflate + k_walk + k_scan + k_parse in chunks of
+// xck_gpu_parse_check FILE.bam BARCODES.txt - the device's record walk and parse (csrc/parse_dev.hip) against the host's parse_part
+// (csrc/bam_records.cpp) on the same bytes: the file's BGZF blocks go through k_inflate + k_walk + k_scan + k_parse in chunks of
 // PARSE_CHUNK_BLOCKS (128) blocks, and every column of every kept record must equal what the host decoder writes for the chunk.
 // A chunk the device flags (contig runs beyond the list, a UMI to intern, ...) is counted, and must be one the host would not have
 // parsed with direct keys only.  Prints "N chunks, R records compared: D differences, F chunks flagged"; exit status 0 iff D == 0.
 // Environment: PARSE_SEQ=0 (no sequence columns), PARSE_DROP=k (every k-th reference is not wanted), PARSE_TEND=p (position windows end at p).
-#include "../xcltk_amd/csrc/bam.cpp"
+// The program links the decoder (bam.o, bam_records.o) and the device decoder; the engine is not part of it (tools/asan/engine_stubs.cpp).
+#include "../xcltk_amd/csrc/bam_decode.h"
 #include <hip/hip_runtime.h>
+#include <cstdio>
 #include <fstream>
-
-namespace xck {   // the engine is not part of this program
-int  engine_numa_node(const xck_engine*) { return -1; }
-int  engine_device(const xck_engine*) { return -1; }
-int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
-int  engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**, const NameTrailer*) { return XCK_E_ARG; }
-int  engine_names_clear(xck_engine*, bool) { return 0; }
-void engine_names_stats(const xck_engine*, int64_t* a, int64_t* b) { *a = 0; *b = 0; }
-int  engine_names_check(xck_engine*) { return 0; }
-void fence_wait(void*) {}
-void fence_destroy(void*) {}
-void* pinned_alloc(size_t bytes) { return malloc(bytes ? bytes : 1); }
-void  pinned_free(void* p) { free(p); }
-}
 
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: %s FILE.bam BARCODES.txt\n", argv[0]); return 2; }
@@ -57,32 +45,31 @@ int main(int argc, char** argv) {
           for (size_t i = 0; i < nb; i++) { const BlockRef& br = blocks[i0 + i];
               gs->h_bl[i] = DevBlock{(uint32_t)at, br.data_len, (uint32_t)uo, br.isize, 0u};
               memcpy(gs->h_in + at, b->map + br.coff + br.data_off, br.data_len); at += ((size_t)br.data_len + 3) & ~size_t(3);
-              std::string es; if (!bgzf_inflate(b->map, br, u.data() + uo, false, &t_zs.zs, &es)) { fprintf(stderr, "host inflate: %s\n", es.c_str()); return 2; }
+              std::string es; if (!bgzf_inflate(b->map, br, u.data() + uo, false, &es)) { fprintf(stderr, "host inflate: %s\n", es.c_str()); return 2; }
               uoff[i] = uo; uo += br.isize; }
           uoff[nb] = usz; }
         const DpWalk dw{skip, DpContigMap{(const int32_t*)d_cm, cm.t_end ? (const int32_t*)d_cm + n_refs : nullptr, n_refs, -1}, want_seq};
         if (gpu_inflate_slot_launch(gs, tin, usz, nb, false, &dw) != 0 || gpu_inflate_slot_wait(gs) != 0) { fprintf(stderr, "device launch failed\n"); return 2; }
         n_chunks++;
         // ---- the host's chunk: every block walked from its first byte, the kept records parsed into one SoA block ----
-        HostSoA s; std::vector<const uint8_t*> recs; std::vector<uint32_t> lens; size_t n_out = 0, n_cig = 0, n_seq = 0; bool aligned = true;
+        HostSoA s; WalkPart wp; size_t n_out = 0, n_cig = 0, n_seq = 0; bool aligned = true;
         for (size_t i = 0; i < nb && aligned; i++) {
             size_t o = uoff[i] + (i == 0 ? skip : 0); const size_t end = uoff[i + 1];
             while (o + 4 <= end) { const uint32_t bs = le32(u.data() + o); if (bs < 32 || o + 4 + (size_t)bs > end) break;
                 const uint8_t* r = u.data() + o + 4;
-                if (cm((int32_t)le32(r), (int32_t)le32(r + 4)) >= 0) { recs.push_back(r); lens.push_back(bs); n_out++; n_cig += le16(r + 12); if (want_seq) n_seq += (le32(r + 16) + 1) / 2; }
+                if (cm((int32_t)le32(r), (int32_t)le32(r + 4)) >= 0) { wp.recs.push_back(RecRef{r, bs, (int32_t)le32(r), le32(r + 16), le16(r + 12)}); n_out++; n_cig += le16(r + 12); if (want_seq) n_seq += (le32(r + 16) + 1) / 2; }
                 o += 4 + (size_t)bs; }
             aligned = o == end;
         }
         DpChunkLayout lay; summaries_to_batches(gs->h_sum, nb, 0, 0, &lay);
         all_flags |= gs->h_head->walk_flags;
-        std::atomic<int> hflags{0}; std::vector<InternTable::Item> names; e.intern.clear();
+        std::atomic<int> hflags{0}; DecodeTimes tm; e.intern.clear();
         if (aligned && n_cig < (1u << 30) && n_seq < (1u << 30)) {
             if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) return 2;
             memset(s.base, 0, s.used);
-            uint32_t co = 0, so = 0;
-            for (size_t k = 0; k < n_out; k++) { s.cig_off[k] = co; s.seq_off[k] = so; parse_record(e.dec, &e, s, recs[k], lens[k], (int64_t)k, 0, names, &hflags);
-                                                 co += le16(recs[k] + 12); if (want_seq) so += (le32(recs[k] + 16) + 1) / 2; }
-            s.cig_off[n_out] = co; s.seq_off[n_out] = so;
+            wp.n_out = n_out; wp.n_cig = n_cig; wp.n_seq = n_seq;                    // (one piece, at the block's start: what layout_chunk makes of a chunk of one part)
+            parse_part(&tm, &e, &s, 0, &wp, cm, &hflags);
+            s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
         }
         const bool host_direct = aligned && hflags.load() == 0 && e.intern.size() == 0;     // nothing the host interned, nothing it reports
         if (lay.flags || gs->h_head->walk_flags) {

@@ -9,27 +9,17 @@
 // Pipeline per chunk of BGZF blocks:  inflate (parallel over blocks) -> record walk (serial,
 // touches 24 B per record) -> field/tag parse into SoA (parallel over records).  The inflate of
 // chunk i+1 runs while chunk i is walked and parsed.
-#include <zlib.h>
+//
+// This unit is the READER: xck_bam with its chunk ring, the scanner and the index ranges, the GPU share of the inflate and the device
+// walk / parse fallbacks, ChunkJob / Pusher, the coordinator's stages, the NUMA binding and the C entry points.  The work on one chunk
+// that knows nothing of a reader (inflate, walk, parse, layout, keys) is bam_records.cpp; the types both share are bam_decode.h.
 #include <fcntl.h>
-#include <sched.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <cstddef>
-#include <cstring>
-#include <deque>
-#include <functional>
-#include <new>
+#include <algorithm>
 #include <stdexcept>
-#include <thread>
-#include "xck_internal.h"
-#include "inflate_fast.h"
-#include "inflate_dev.h"
-#include "parse_dev.h"
-#include "intern_dev.h"
+#include "bam_decode.h"
 
 namespace xck {
 
@@ -63,525 +53,7 @@ int default_threads() {
     return cached;
 }
 
-uint64_t hash_bytes(const char* s, size_t n) {                       // 8 bytes per step (read names are 20-40 characters)
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ (n * 0xff51afd7ed558ccdull);
-    while (n >= 8) { uint64_t w; memcpy(&w, s, 8); h = (h ^ w) * 0xbf58476d1ce4e5b9ull; h ^= h >> 32; s += 8; n -= 8; }
-    if (n) { uint64_t w = 0; memcpy(&w, s, n); h = (h ^ w) * 0x94d049bb133111ebull; }
-    h ^= h >> 29; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 32;
-    return h;
-}
-
-void InternTable::Shard::grow() {
-    const size_t ncap = slots.empty() ? 1024 : slots.size() * 2;
-    std::vector<Slot> ns(ncap, Slot{0, 0, 0, 0, 0});
-    for (const Slot& sl : slots) if (sl.epoch == epoch) {
-        size_t i = (size_t)(sl.h >> 6) & (ncap - 1);
-        while (ns[i].epoch == epoch) i = (i + 1) & (ncap - 1);
-        ns[i] = sl;
-    }
-    slots.swap(ns);
-}
-
-// test hook: XCK_TEST_INTERN_LIMIT=<n> makes the id space of 64-bit keys overflow after n ids (tests/test_gpu_frontends.py
-// exercises the front-ends' retry with 128-bit keys without 2^25 distinct read names)
-static const uint64_t g_test_intern_limit = [] { const char* e = getenv("XCK_TEST_INTERN_LIMIT"); return e ? (uint64_t)strtoull(e, nullptr, 10) : ~0ull; }();
-uint64_t intern_id_limit(int umi_bits) {
-    return umi_bits >= 64 ? (1ull << 63) - 1 : std::min<uint64_t>((1ull << (umi_bits - 1)) - 1, g_test_intern_limit);
-}
-
-uint64_t InternTable::intern(const char* s, size_t n) {
-    const uint64_t h = hash_bytes(s, n);
-    Shard& sh = shards_[h & (NSHARD - 1)];
-    std::lock_guard<std::mutex> lk(sh.mu);
-    if ((size_t)(sh.count + 1) * 2 > sh.slots.size()) sh.grow();
-    const size_t mask = sh.slots.size() - 1;
-    size_t i = (size_t)(h >> 6) & mask;
-    for (;;) {
-        Slot& sl = sh.slots[i];
-        if (sl.epoch != sh.epoch) {
-            sl.h = h; sl.off = (uint32_t)sh.arena.size(); sl.len1 = (uint32_t)n + 1; sl.idx = sh.count++; sl.epoch = sh.epoch;
-            sh.arena.insert(sh.arena.end(), s, s + n);
-            return ((uint64_t)sl.idx << 6) | (h & (NSHARD - 1));
-        }
-        if (sl.h == h && sl.len1 == (uint32_t)n + 1 && memcmp(sh.arena.data() + sl.off, s, n) == 0) return ((uint64_t)sl.idx << 6) | (h & (NSHARD - 1));
-        i = (i + 1) & mask;
-    }
-}
-uint64_t InternTable::hash(const char* s, size_t n) { return hash_bytes(s, n); }
-
-// UMI-less mode interns every read name: per string the shared table costs a lock and two cache misses (the table of a
-// 2 M-read BAM is ~100 MB).  A parse task therefore collects its names and hands them over here, sorted by shard: one
-// lock per shard, and the probes of a shard (1/64 of the table) hit the cache.
-void InternTable::intern_batch(std::vector<Item>& items, bool* overflow) {
-    std::sort(items.begin(), items.end(), [](const Item& a, const Item& b) { return (a.h & (NSHARD - 1)) < (b.h & (NSHARD - 1)); });
-    size_t i = 0;
-    while (i < items.size()) {
-        const unsigned shard = (unsigned)(items[i].h & (NSHARD - 1));
-        Shard& sh = shards_[shard];
-        std::lock_guard<std::mutex> lk(sh.mu);
-        for (; i < items.size() && (items[i].h & (NSHARD - 1)) == shard; i++) {
-            const Item& it = items[i];
-            if ((size_t)(sh.count + 1) * 2 > sh.slots.size()) sh.grow();
-            const size_t mask = sh.slots.size() - 1;
-            if (i + 4 < items.size()) __builtin_prefetch(&sh.slots[(size_t)(items[i + 4].h >> 6) & mask]);
-            size_t k = (size_t)(it.h >> 6) & mask;
-            uint64_t id;
-            for (;;) {
-                Slot& sl = sh.slots[k];
-                if (sl.epoch != sh.epoch) {
-                    sl.h = it.h; sl.off = (uint32_t)sh.arena.size(); sl.len1 = it.n + 1; sl.idx = sh.count++; sl.epoch = sh.epoch;
-                    sh.arena.insert(sh.arena.end(), it.s, it.s + it.n);
-                    id = ((uint64_t)sl.idx << 6) | shard; break;
-                }
-                if (sl.h == it.h && sl.len1 == it.n + 1 && memcmp(sh.arena.data() + sl.off, it.s, it.n) == 0) { id = ((uint64_t)sl.idx << 6) | shard; break; }
-                k = (k + 1) & mask;
-            }
-            const uint64_t lim = intern_id_limit(it.umi_bits);
-            if (id >= lim) { if (overflow) *overflow = true; *it.out = XCK_UMI_NONE; }
-            else *it.out = (1ull << (it.umi_bits - 1)) | id;
-        }
-    }
-}
-uint64_t InternTable::size() const { uint64_t n = 0; for (auto& s : shards_) n += s.count; return n; }
-void InternTable::clear() {
-    for (auto& s : shards_) {
-        std::lock_guard<std::mutex> lk(s.mu);
-        s.arena.clear(); s.count = 0;
-        if (++s.epoch == 0) { std::fill(s.slots.begin(), s.slots.end(), Slot{0, 0, 0, 0, 0}); s.epoch = 1; }   // slots of older epochs read as empty
-    }
-}
-
-// the part of encode_key() that needs no table: empty string -> NONE, short ACGT string -> 2-bit code
-static bool encode_key_direct(const char* s, size_t n, int umi_bits, uint64_t* out) {
-    if (n == 0) { *out = XCK_UMI_NONE; return true; }
-    if (2 * (int)n + 1 <= umi_bits - 1) {
-        // A C G T -> 0 1 2 3, anything else 4: one table look-up per character, no branch inside the loop
-        static const struct Lut { uint8_t t[256]; Lut() { memset(t, 4, sizeof t); t[(uint8_t)'A'] = 0; t[(uint8_t)'C'] = 1; t[(uint8_t)'G'] = 2; t[(uint8_t)'T'] = 3; } } lut;
-        uint64_t v = 1; unsigned bad = 0;
-        for (size_t i = 0; i < n; i++) { const unsigned c = lut.t[(uint8_t)s[i]]; bad |= c; v = (v << 2) | (c & 3u); }
-        if (!(bad & 4u)) { *out = v; return true; }
-    }
-    return false;
-}
-
-uint64_t encode_key(const char* s, size_t n, int umi_bits, InternTable& tab, bool* overflow) {
-    uint64_t direct;
-    if (encode_key_direct(s, n, umi_bits, &direct)) return direct;
-    uint64_t id = tab.intern(s, n);
-    const uint64_t lim = intern_id_limit(umi_bits);
-    if (id >= lim) { if (overflow) *overflow = true; return XCK_UMI_NONE; }
-    return (1ull << (umi_bits - 1)) | id;
-}
-
-// Barcode -> column: open addressing over slots that hold the full 64-bit hash, the column and the barcode's own bytes (up to
-// 18, the length of a 10x barcode), so a hit costs ONE cache line and still compares the exact string; longer barcodes compare against
-// the string list.  (Slots -> std::string -> heap was three dependent misses per read.)
-void DecodeCfg::build_barcodes(const char* const* names, int n) {
-    barcodes.clear();
-    for (int i = 0; i < n; i++) barcodes.emplace_back(names[i]);
-    size_t cap = 16; while (cap < (size_t)n * 2) cap <<= 1;
-    BcSlot empty; memset(&empty, 0, sizeof empty); empty.idx = -1;
-    bc_slots.assign(cap, empty); bc_mask = cap - 1;
-    for (int i = 0; i < n; i++) {
-        const std::string& b = barcodes[i];
-        const uint64_t hh = hash_bytes(b.data(), b.size());
-        uint64_t h = hh & bc_mask;
-        while (bc_slots[h].idx >= 0) h = (h + 1) & bc_mask;
-        BcSlot& sl = bc_slots[h];
-        sl.h = hh; sl.idx = i; sl.len = (uint16_t)std::min<size_t>(b.size(), 0xFFFF);
-        memcpy(sl.key, b.data(), std::min<size_t>(b.size(), sizeof sl.key));
-    }
-}
-int32_t DecodeCfg::lookup_cell(const char* s, size_t n) const {
-    if (bc_slots.empty()) return -1;
-    const uint64_t hh = hash_bytes(s, n);
-    uint64_t h = hh & bc_mask;
-    while (bc_slots[h].idx >= 0) {
-        const BcSlot& sl = bc_slots[h];
-        if (sl.h == hh && sl.len == (n > 0xFFFF ? 0xFFFF : (uint16_t)n)) {
-            if (n <= sizeof sl.key) { if (memcmp(sl.key, s, n) == 0) return sl.idx; }
-            else { const std::string& b = barcodes[sl.idx]; if (b.size() == n && memcmp(b.data(), s, n) == 0) return sl.idx; }
-        }
-        h = (h + 1) & bc_mask;
-    }
-    return -1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// thread pool
-// ---------------------------------------------------------------------------------------------
-class Pool {
-public:
-    explicit Pool(int n) { for (int i = 0; i < n; i++) th_.emplace_back([this] { run(); }); }
-    ~Pool() { { std::lock_guard<std::mutex> lk(mu_); stop_ = true; } cv_.notify_all(); for (auto& t : th_) t.join(); }
-    // many tasks under ONE lock and one wake-up: a chunk hands ~100 part tasks to the pool three times (inflate / gather, walk, parse), and a
-    // lock + futex wake per task cost the coordinator ~0.7 ms per chunk
-    void submit_many(std::vector<std::function<void()>>& fs, bool front = false) {
-        if (fs.empty()) return;
-        { std::lock_guard<std::mutex> lk(mu_);
-          if (front) for (size_t i = fs.size(); i-- > 0;) q_.push_front(std::move(fs[i])); else for (auto& f : fs) q_.push_back(std::move(f)); }
-        if (fs.size() == 1) cv_.notify_one(); else cv_.notify_all();
-        fs.clear();
-    }
-    int size() const { return (int)th_.size(); }
-    void set_affinity(const cpu_set_t& set) { for (auto& t : th_) pthread_setaffinity_np(t.native_handle(), sizeof set, &set); }
-private:
-    void run() {
-        for (;;) {
-            std::function<void()> f;
-            { std::unique_lock<std::mutex> lk(mu_); cv_.wait(lk, [this] { return stop_ || !q_.empty(); });
-              if (q_.empty()) return; f = std::move(q_.front()); q_.pop_front(); }
-            f();
-        }
-    }
-    std::vector<std::thread> th_; std::deque<std::function<void()>> q_; std::mutex mu_; std::condition_variable cv_; bool stop_ = false;
-};
-
-struct TaskGroup {
-    std::mutex mu; std::condition_variable cv; int pending = 0;
-    std::atomic<int> thrown{0};          // a task body threw: 1 = std::bad_alloc, 2 = anything else (checked by the waiter: an exception
-                                         // that leaves a pool thread would otherwise end the process through std::terminate)
-    int take_thrown() { return thrown.exchange(0); }
-    // collect tasks with later(), hand them to the pool in one go with flush() (front: ahead of what is queued - work the coordinator
-    // is waiting for).  The notify of a finished task happens UNDER the lock: a waiter may reuse or destroy the group as soon as wait()
-    // returns, and wait() cannot return before the task has released the mutex - after which it touches the group no more.
-    // (Notifying after the unlock let a waiter that saw pending == 0 leave first; the late pthread_cond_broadcast then wrote into
-    // whatever the coordinator's stack held by then: "free(): invalid pointer", once per ~14 k chunks with more pool threads than
-    // CPUs, tools/stress_e2e.py.)
-    std::vector<std::function<void()>> batch;
-    void later(std::function<void()> f) {
-        batch.push_back([this, f] {
-            try { f(); } catch (const std::bad_alloc&) { thrown.store(1); } catch (...) { thrown.store(2); }
-            std::lock_guard<std::mutex> lk(mu); if (--pending == 0) cv.notify_all(); });
-    }
-    void flush(Pool& p, bool front = false) {
-        if (batch.empty()) return;
-        { std::lock_guard<std::mutex> lk(mu); pending += (int)batch.size(); }
-        p.submit_many(batch, front);
-    }
-    void wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return pending == 0; }); }
-};
-
-// ---------------------------------------------------------------------------------------------
-// BGZF
-// ---------------------------------------------------------------------------------------------
-static inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-static inline uint16_t le16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-
-struct BlockRef { uint64_t coff; uint32_t clen; uint32_t isize; uint32_t data_off; uint32_t data_len; uint64_t uoff; };
-
-// parse one BGZF block header at file offset `coff`; returns false at EOF / on malformed data
-static bool bgzf_peek(const uint8_t* map, uint64_t fsize, uint64_t coff, BlockRef* out, std::string* err) {
-    if (coff + 18 > fsize) { if (coff != fsize && err) *err = "truncated BGZF block header"; return false; }
-    const uint8_t* p = map + coff;
-    if (p[0] != 0x1f || p[1] != 0x8b || p[2] != 8 || !(p[3] & 4)) { if (err) *err = "not a BGZF block (bad gzip magic)"; return false; }
-    uint32_t xlen = le16(p + 10);
-    if (coff + 12 + xlen > fsize) { if (err) *err = "truncated BGZF extra field"; return false; }
-    const uint8_t* x = p + 12; const uint8_t* xe = x + xlen;
-    int64_t bsize = -1;
-    while (x + 4 <= xe) { uint32_t sl = le16(x + 2); if (x + 4 + sl > xe) break;          // subfield payload must lie inside the extra field
-                          if (x[0] == 'B' && x[1] == 'C' && sl == 2) { bsize = le16(x + 4); } x += 4 + sl; }
-    if (bsize < 0) { if (err) *err = "BGZF block without BC subfield"; return false; }
-    uint32_t total = (uint32_t)bsize + 1;
-    if (coff + total > fsize || total < 12 + xlen + 8) { if (err) *err = "truncated BGZF block"; return false; }
-    out->coff = coff; out->clen = total; out->data_off = 12 + xlen; out->data_len = total - (12 + xlen) - 8;
-    out->isize = le32(p + total - 4); out->uoff = 0;
-    if (out->isize > 65536) { if (err) *err = "BGZF block claims more than 64 KiB of data"; return false; }   // SAMv1 4.1: ISIZE <= 65536
-    return true;
-}
-
-static std::atomic<long> g_inflate_fallbacks{0};
-static const bool g_use_fast_inflate = [] { const char* e = getenv("XCK_INFLATE"); return !(e && strcmp(e, "zlib") == 0); }();
-static thread_local InflateTables t_inflate_tables;
-
-static bool bgzf_inflate(const uint8_t* map, const BlockRef& b, uint8_t* dst, bool verify_crc, z_stream* zs, std::string* err) {
-    if (b.isize == 0) return true;
-    bool done = false;
-    if (g_use_fast_inflate) {                                  // own whole-buffer decoder (inflate_fast.h); zlib on any irregularity
-        done = inflate_raw(map + b.coff + b.data_off, b.data_len, dst, b.isize, &t_inflate_tables) == 0;
-        if (!done) g_inflate_fallbacks.fetch_add(1, std::memory_order_relaxed);
-    }
-    if (!done) {
-        inflateReset(zs);
-        zs->next_in = const_cast<Bytef*>(map + b.coff + b.data_off); zs->avail_in = b.data_len;
-        zs->next_out = dst; zs->avail_out = b.isize;
-        int rc = inflate(zs, Z_FINISH);
-        if (rc != Z_STREAM_END || zs->avail_out != 0) { if (err) *err = "BGZF inflate failed"; return false; }
-    }
-    if (verify_crc) {
-        uint32_t want = le32(map + b.coff + b.clen - 8);
-        if ((uint32_t)crc32(crc32(0L, Z_NULL, 0), dst, b.isize) != want) { if (err) *err = "BGZF CRC mismatch in the block at compressed offset " + std::to_string(b.coff); return false; }
-    }
-    return true;
-}
-
-struct ZStream { z_stream zs; bool ok; ZStream() { memset(&zs, 0, sizeof zs); ok = inflateInit2(&zs, -15) == Z_OK; } ~ZStream() { if (ok) inflateEnd(&zs); } };
-static thread_local ZStream t_zs;
-
 }  // namespace xck
-
-using namespace xck;
-
-// ---------------------------------------------------------------------------------------------
-// the BAM file object
-// ---------------------------------------------------------------------------------------------
-// One decoded chunk as structure-of-arrays, all columns carved out of ONE pinned block: the whole chunk crosses PCIe in a
-// single hipMemcpyAsync (engine_push_block) and the batches of the chunk are slices of it.  Every ChunkJob (below) has one,
-// so the decoder fills the next job's block while this one is still being copied; `fence` (an event owned by this block,
-// recorded by the engine behind the copy) is waited for before the block is overwritten.
-struct HostSoA {
-    uint8_t* base = nullptr; size_t cap = 0, used = 0; bool pinned = false; void* fence = nullptr;
-    int32_t* pos = nullptr; uint16_t* flag = nullptr; uint8_t* mapq = nullptr; int32_t* cell = nullptr; uint64_t* umi = nullptr;
-    uint32_t* cig_off = nullptr; uint32_t* cigar = nullptr; uint32_t* seq_off = nullptr; uint8_t* seq = nullptr;
-    // device-names mode: behind the columns (SoaLayout::total) one DiItem per kept record and the packed bytes of the names that have
-    // to be interned - the parse tasks fill them, the block's copy takes them along (engine_push_block)
-    bool has_names = false; xck::NameTrailer nt{0, 0, 0, 0}; xck::DiItem* items = nullptr; uint8_t* name_bytes = nullptr;
-};
-
-struct RecRef { const uint8_t* p; uint32_t len; int32_t tid; uint32_t l_seq; uint16_t n_cig; };
-
-// Records found by one inflate task in its own byte range, walked right after inflating (data
-// still hot in that core's cache) under the SPECULATION that a record starts at the first byte of
-// the range - true for BGZF writers that flush a block before a record that would not fit (htslib,
-// samtools, this repo's writers).  The task also sums up what its records need in the SoA (kept records, CIGAR words,
-// sequence bytes) and notes where the contig changes: the output layout is a prefix sum over the parts and each part is
-// parsed by its own task.  When a speculation of the chunk failed the stitch re-walks serially and cuts its record list
-// into pieces of the same shape (Chunk::stitched), so layout and parse know one kind of input.
-struct ContigRun { uint32_t first; int32_t contig; };                    // records [first, next run's first) of the part are on `contig` (-1: unused)
-struct WalkPart {
-    size_t u_begin = 0, u_end = 0, spec_start = 0, stop = 0; std::vector<RecRef> recs;
-    size_t n_out = 0, n_cig = 0, n_seq = 0; std::vector<ContigRun> runs;
-    size_t n_name = 0;                                                    // l_name summed over the kept records: the room their names can take (device-names mode)
-    size_t out_base = 0, cig_base = 0, seq_base = 0, name_base = 0;       // filled by the coordinator (layout_chunk)
-    size_t i0 = 0, i1 = 0;                                                // the part's blocks: [i0, i1) of the chunk
-};
-
-struct Chunk {
-    std::vector<BlockRef> blocks;
-    std::vector<uint8_t> ubuf; size_t usize = 0;
-    uint8_t* ubase = nullptr;          // where the chunk's inflated bytes live: ubuf, or the pinned output block of its GPU slot
-    std::vector<WalkPart> parts;
-    // a chunk that was stitched serially: its records in pieces of a parse task's size (only recs, runs and the n_* / *_base fields are
-    // used), and the record that straddles the boundary to the previous chunk, assembled from the reader's carry.  Both are read by the
-    // chunk's parse tasks, which may run behind the coordinator: they live here, with the inflated bytes, until the chunk is released.
-    std::vector<WalkPart> stitched; std::vector<uint8_t> stitch;
-    TaskGroup tg; std::atomic<bool> failed{false}; std::string err; std::mutex emu;
-    bool valid = false, new_range = false; uint32_t first_skip = 0; int range_id = 0;
-    // GPU share of the inflate (csrc/inflate_dev.hip): the pool only gathers the compressed bytes into the slot's pinned block, the task
-    // that finishes last enqueues copy-in, kernel and copy-out; walk (and the blocks the kernel left) follow when the chunk is consumed
-    bool gpu = false; std::atomic<int> copy_left{0}; std::atomic<int> gpu_rc{0}; size_t in_total = 0;
-    std::atomic<int> launched{0};      // the last gather task has handed the chunk to the device (gpu_rc says how that went)
-    bool stage2 = false;               // the walk tasks that follow the device's inflate have been queued
-    // device walk + parse (csrc/parse_dev.hip): the chunk was launched with the walk behind its inflate and nothing stored to the host
-    // (dparse); its summaries came back clean, so no walk task was queued (dp_ok) - until something sends it down the host path after all
-    bool dparse = false, dp_ok = false;
-};
-
-struct PendingBatch { int32_t contig; int64_t r0, r1; uint64_t ordinal_base; };
-
-// BAM tid (+ record position) -> engine contig: -1 for references that are not wanted and for records that start at or
-// beyond the end of the position window of their reference (xck_ingest_opts.tid_end)
-struct ContigMap {
-    const int32_t* t2c = nullptr; const int32_t* t_end = nullptr; int n_refs = 0;
-    int32_t only_tid = -1;               // position windows: the chunk belongs to the index range of ONE reference; the tail block of that
-                                         // range also holds the first records of the next reference, which that reference's own range
-                                         // delivers again - they are dropped here, so no record reaches the consumer twice
-    inline int32_t operator()(int32_t tid, int32_t pos) const {
-        if (tid < 0 || tid >= n_refs || !t2c) return -1;
-        if (only_tid >= 0 && tid != only_tid) return -1;
-        if (t_end && t_end[tid] > 0 && pos >= t_end[tid]) return -1;
-        return t2c[tid];
-    }
-};
-
-// where the ingest time goes (XCK_DEBUG_TIMING=1 prints it when the reader is closed): pool-side CPU time summed over
-// threads, and the phases of the coordinating thread
-struct DecodeTimes {
-    std::atomic<uint64_t> inflate{0}, walk{0}, parse{0};                 // ns, summed over pool threads
-    uint64_t wait_inflate = 0, sched = 0, stitch = 0, layout = 0, wait_parse = 0, wait_push = 0;   // ns, coordinating thread
-    uint64_t push = 0;                                                   // ns, push thread (engine_push_block, engine_push_parsed)
-    uint64_t push_parsed = 0, dp_layout = 0, dp_copy_out = 0;            // ns: engine_push_parsed alone (push thread); summaries -> batches (coordinator); fallback copies d_out -> h_out
-    uint64_t chunks = 0, slow_chunks = 0; std::chrono::steady_clock::time_point t_open;
-};
-static inline uint64_t ns_since(std::chrono::steady_clock::time_point t0) { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
-
-// The BGZF block headers form a chain (every header gives the offset of the next one): a scanner thread walks it ahead of
-// the decoder - it also takes the page faults of the mapping - and hands over one plan per chunk.
-struct ChunkPlan { std::vector<BlockRef> blocks; size_t usize = 0; uint32_t first_skip = 0; int range_id = 0; bool new_range = false, failed = false, end = false; std::string err; };
-struct ScanRange { uint64_t coff; uint32_t skip; uint64_t stop; };
-class Scanner {
-public:
-    Scanner(const uint8_t* map, uint64_t fsize, size_t chunk_target, std::vector<ScanRange> ranges)
-        : map_(map), fsize_(fsize), target_(chunk_target), ranges_(std::move(ranges)) { th_ = std::thread([this] { run(); }); }
-    ~Scanner() { { std::lock_guard<std::mutex> lk(mu_); stop_ = true; } cv_.notify_all(); if (th_.joinable()) th_.join(); }
-    void abandon(int range_id) { abandoned_.store(range_id); }          // the decoder has seen everything it wants of that range
-    ChunkPlan next() {                                                  // blocks until a plan is ready; `end` after the last chunk
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [this] { return !q_.empty(); });
-        ChunkPlan p = std::move(q_.front()); q_.pop_front();
-        lk.unlock(); cv_.notify_all();
-        return p;
-    }
-private:
-    bool put(ChunkPlan&& p) {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [this] { return stop_ || q_.size() < 3; });
-        if (stop_) return false;
-        q_.push_back(std::move(p)); lk.unlock(); cv_.notify_all();
-        return true;
-    }
-    void run() {
-        // (the scanner's only allocations are the block lists: out of memory ends the stream with a failed plan, not the process)
-        try { scan(); }
-        catch (...) { ChunkPlan f; f.failed = true; f.err = "out of host memory (BGZF scanner)"; f.blocks.clear(); if (put(std::move(f))) { ChunkPlan z; z.end = true; put(std::move(z)); } }
-    }
-    void scan() {
-        for (size_t ri = 0; ri < ranges_.size(); ri++) {
-            const ScanRange& rg = ranges_[ri];
-            uint64_t coff = rg.coff; bool first = true, ended = false;
-            while (!ended) {
-                if (abandoned_.load() == (int)ri) break;
-                ChunkPlan p; p.new_range = first; p.first_skip = first ? rg.skip : 0; p.range_id = (int)ri; first = false;
-                size_t usz = 0;
-                while (usz < target_) {
-                    if (coff > rg.stop) { ended = true; break; }          // end of the indexed range
-                    BlockRef br; std::string e;
-                    if (!bgzf_peek(map_, fsize_, coff, &br, &e)) { ended = true; if (!e.empty()) { p.failed = true; p.err = e; } break; }
-                    br.uoff = usz; usz += br.isize; coff += br.clen;
-                    p.blocks.push_back(br);
-                }
-                p.usize = usz;
-                if (p.blocks.empty() && !p.failed) { if (p.new_range) { /* an empty range: nothing to hand over */ } break; }
-                const bool failed = p.failed;
-                if (!put(std::move(p))) return;
-                if (failed) { ChunkPlan z; z.end = true; put(std::move(z)); return; }
-            }
-        }
-        ChunkPlan z; z.end = true; put(std::move(z));
-    }
-    const uint8_t* map_; uint64_t fsize_; size_t target_; std::vector<ScanRange> ranges_;
-    std::thread th_; std::mutex mu_; std::condition_variable cv_; std::deque<ChunkPlan> q_; bool stop_ = false;
-    std::atomic<int> abandoned_{-1};
-};
-
-#ifndef XCK_PUSH_Q
-#define XCK_PUSH_Q 2
-#endif
-constexpr int PUSH_Q = XCK_PUSH_Q;      // chunks the coordinator may run ahead of the push thread (Pusher)
-constexpr int N_CHUNK = 3 + PUSH_Q, N_JOB = PUSH_Q + 1;
-// One decoded chunk in flight, from its layout to the end of its push: the SoA block, the batch list (slices of the block), the parse
-// tasks and their flags, the ring chunk the parse still reads (inflated bytes + record lists, until `parsed`) and the engine the chunk
-// goes to.  The k-th chunk a reader decodes takes jobs[k % N_JOB], whoever consumes it.  xck_bam_next_batch and a decode-only
-// xck_ingest_bam wait for the parse themselves.  On a GPU-backed handle EVERY chunk's job - one without batches too - goes to the push
-// thread (Pusher), which waits for the parse tasks and pushes the block (engine_push_block: one H2D copy + the join launches) in file
-// order while the coordinator schedules, waits for and lays out the next chunks (with the GPU share of the inflate the coordinator had
-// become the limiter: schedule + wait for parse + push = 4.5 ms per chunk, the pool a third idle).  At most Pusher::MAXQ = N_JOB - 1
-// jobs are with the push thread, so the slot of chunk k is free again when chunk k + N_JOB is laid out (take_job checks it).
-struct ChunkJob {
-    HostSoA soa; std::deque<PendingBatch> batches;
-    TaskGroup tg; std::atomic<int> flags{0};   // the parse tasks; what they found (parse_error)
-    xck_engine* e = nullptr;           // the handle of the call that decoded the chunk: where the push thread pushes it
-    int ring_idx = -1;                 // the ring chunk the parse tasks read, while the job holds it
-    std::atomic<int> parsed{0};        // set by the push thread once the parse tasks have ended: the coordinator may take the ring chunk back
-    bool released = true;              // (coordinator) the ring chunk was taken back, or was never held
-    std::atomic<int> queued{0};        // with the push thread: set by Pusher::submit, cleared when the job's push has ended
-    // a chunk walked on the device: no parse tasks, the push thread launches the parse kernel (engine_push_parsed) - or, if that kernel
-    // flags the chunk, takes it down the host path itself (redo_on_host), for which it needs what the coordinator knew
-    bool dev = false; xck_bam* b = nullptr; DpChunkLayout lay; ContigMap cm; xck_ingest_opts opts; int64_t rec_before = 0;
-    bool names = false;                // device-names mode: the chunk's names are keyed by the handle's device table (take_job)
-};
-struct Pusher {
-    static constexpr int MAXQ = PUSH_Q; // jobs the coordinator may run ahead
-    std::thread th; std::mutex mu; std::condition_variable cv;
-    bool stop = false; ChunkJob* q[MAXQ] = {}; int qh = 0, qn = 0;
-    int rc = 0; std::string err;       // first failure (parse flags or push); later jobs are waited for, not pushed
-    uint64_t push_ns = 0, parse_wait_ns = 0, push_parsed_ns = 0;
-    void run();
-    Pusher() { th = std::thread([this] { run(); }); }
-    // blocks while MAXQ jobs are outstanding; returns the first failure so far (the job is queued regardless: its parse must be waited for)
-    int submit(ChunkJob* j) {
-        std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return qn < MAXQ; });
-        j->queued.store(1); q[(qh + qn) % MAXQ] = j; qn++; cv.notify_all(); return rc;
-    }
-    int wait_idle() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [this] { return qn == 0; }); return rc; }
-    ~Pusher() { { std::lock_guard<std::mutex> lk(mu); stop = true; cv.notify_all(); } if (th.joinable()) th.join(); }
-};
-constexpr int N_CHUNK_GPU = 16;        // ring depth with the GPU share on: its chunks need several in flight on the device (one wave per block)
-// XCK_GPU_INFLATE=<percent>: that share of the chunks is inflated on the handle's GPU (0 = off).  State of one reader:
-struct GpuShare {
-    bool tried = false, on = false, broken = false, verbose = false; int pct = 0, acc = 0, device = -1, free_cus = 32, depth = 4;
-    GpuInflateSlot* slot[N_CHUNK_GPU] = {nullptr}; bool inflight[N_CHUNK_GPU] = {false};   // slot[k]: the slot that holds ring chunk k (its inflated bytes live there until the chunk is consumed)
-    std::vector<GpuInflateSlot*> free_slots;                             // slots of consumed chunks, reused before a new one is made
-    int max_held = 10;                                                   // device chunks in the ring at a time (in flight + inflated, not yet consumed) = slots this reader ever holds
-    uint64_t chunks = 0, blocks = 0, left_blocks = 0, wait_ns = 0, copy_ns = 0;
-    // device walk + parse of the device chunks (XCK_GPU_PARSE): whether the handle and its barcode list allow it, the contig tables in
-    // device memory (uploaded anew when a call brings other tables; the old ones live until the reader closes: walks in flight read them)
-    bool parse = false; std::atomic<bool> parse_off{false}; std::atomic<int> fb_row{0};
-    std::vector<int32_t> cm_host; int32_t* d_cm = nullptr; bool cm_tend = false; std::vector<void*> d_cm_all;
-};
-struct CallerBinding;
-struct xck_bam {
-    std::string path; int fd = -1; const uint8_t* map = nullptr; uint64_t fsize = 0;
-    std::vector<std::string> ref_names; std::vector<int64_t> ref_lens;
-    uint64_t next_coff = 0;            // first BGZF block with alignment records
-    // .bai: per reference [beg, end) virtual offsets + record counts (samtools pseudo-bin 37450 or bin chunks)
-    bool idx_loaded = false, idx_ok = false;
-    std::vector<uint64_t> idx_beg, idx_end; std::vector<int64_t> idx_mapped, idx_unmapped; std::vector<std::vector<uint64_t>> idx_lin;
-    std::vector<std::pair<uint64_t, uint64_t>> ranges; bool use_ranges = false, ranges_set = false;
-    uint32_t first_skip = 0;           // bytes of the first block that precede the first record
-    Scanner* scanner = nullptr; bool scan_end = false;
-    std::vector<int32_t> range_tid;                       // per_tid_ranges: reference of every range
-    bool per_tid_ranges = false; int skip_range = -1;   // position windows: one range per reference; a range is dropped once a record starts beyond its window
-    Pool* pool = nullptr; int n_threads = 1;
-    Chunk ch[N_CHUNK_GPU]; int n_ring = N_CHUNK, head = 0, n_sched = 0;      // ring of n_ring chunks: ch[head] is decoded next, n_sched chunks are inflating / inflated
-    GpuShare gi;
-    bool started = false;              // a decode call has been made (xck_bam_prefetch alone does not count)
-    bool prefetching = false;          // inside xck_bam_prefetch
-    Pusher* pusher = nullptr;          // made at the first chunk of a GPU-backed ingest
-    ChunkJob jobs[N_JOB]; uint64_t n_jobs = 0;   // jobs[k % N_JOB] belongs to the k-th chunk decoded (take_job)
-    ChunkJob* cur = nullptr;           // the job of the chunk decoded last: xck_bam_next_batch hands its batches out
-    bool defer_parse = false;          // set by xck_ingest_bam for GPU-backed handles: parse and push run behind the coordinator
-    std::vector<uint8_t> carry;        // partial record from the previous chunk
-    int64_t n_records = 0;             // records walked so far (all, including unused contigs)
-    bool done = false;
-    size_t chunk_target = 48u << 20;   // uncompressed bytes per chunk
-    // NUMA binding (bind_to_numa_node): the pool and the scanner sit on the node of the handle's GPU while the reader is open; the
-    // CALLING thread (it runs the coordinator, and its first touch places the inflate buffers) only for the duration of a decode
-    // call (CallerBinding) - between calls, and on whatever thread closes the reader, the caller's own mask is untouched
-    bool numa_bound = false, threads_auto = false; cpu_set_t numa_set, old_affinity;
-    struct CallerBinding* cur_binding = nullptr;
-    DecodeTimes tm;
-    std::atomic<int64_t> dstat[DS_N] = {}; int64_t dstat_folded[DS_N] = {};   // xck_decode_stats of this reader; the part already added to a handle's
-    std::string err;
-};
-
-static void soa_free(HostSoA& s) {
-    if (s.fence) { fence_wait(s.fence); fence_destroy(s.fence); }
-    if (s.base) { if (s.pinned) pinned_free(s.base); else free(s.base); }
-    s = HostSoA();
-}
-// carve the columns of a chunk with n_reads kept records out of the block (growing it if needed)
-static bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t name_items = 0, size_t name_bytes = 0, bool names = false) {
-    const SoaLayout l = soa_layout(n_reads, n_cig, n_seq);                // (parse_dev.h: the parse kernel writes the same block)
-    const size_t items_bytes = (name_items * sizeof(DiItem) + 255) & ~size_t(255);
-    const size_t total = l.total + (names ? items_bytes + ((name_bytes + 255) & ~size_t(255)) : 0);   // (the names: a trailer behind the layout's total)
-    if (total > s.cap) {
-        if (s.fence) fence_wait(s.fence);
-        if (s.base) { if (s.pinned) pinned_free(s.base); else free(s.base); }
-        const size_t c = total + total / 4;
-        s.base = (uint8_t*)pinned_alloc(c); s.pinned = s.base != nullptr;
-        if (!s.base) s.base = (uint8_t*)malloc(c);
-        if (!s.base) { s.cap = 0; return false; }
-        s.cap = c;
-    }
-    s.used = total;
-    s.umi = (uint64_t*)(s.base + l.o_umi); s.pos = (int32_t*)(s.base + l.o_pos); s.cell = (int32_t*)(s.base + l.o_cell);
-    s.cig_off = (uint32_t*)(s.base + l.o_cgo); s.seq_off = (uint32_t*)(s.base + l.o_sqo); s.cigar = (uint32_t*)(s.base + l.o_cig);
-    s.flag = (uint16_t*)(s.base + l.o_flag); s.mapq = s.base + l.o_mapq; s.seq = s.base + l.o_seq;
-    s.has_names = names; s.nt = NameTrailer{l.total, l.total + items_bytes, name_bytes, names ? name_items : 0};
-    s.items = names ? (DiItem*)(s.base + s.nt.items_off) : nullptr; s.name_bytes = names ? s.base + s.nt.bytes_off : nullptr;
-    return true;
-}
 
 // sequential reader used only for the header
 struct SeqReader {
@@ -592,7 +64,7 @@ struct SeqReader {
             if (!bgzf_peek(b->map, b->fsize, coff, &br, &err)) { if (err.empty()) err = "unexpected end of file in BAM header"; return false; }
             size_t old = buf.size();
             buf.resize(old + br.isize);
-            if (!t_zs.ok || !bgzf_inflate(b->map, br, buf.data() + old, false, &t_zs.zs, &err)) { if (err.empty()) err = "inflate init failed"; return false; }
+            if (!bgzf_inflate(b->map, br, buf.data() + old, false, &err)) { if (err.empty()) err = "inflate init failed"; return false; }
             blk_coff = coff; blk_start = old; coff += br.clen;
         }
         return true;
@@ -803,51 +275,6 @@ static void set_ranges(xck_bam* b, const xck_ingest_opts* o) {
     b->use_ranges = true;
 }
 
-// One part of a chunk: inflate its blocks (all of them, or - st given - only those the GPU kernel left: status != 0), then walk the
-// records of its byte range speculatively.  Pool task.
-// verify_crc: every non-empty block it inflates is CRC-checked (dstat: the reader's counters); a block the kernel found damaged
-// (INFLATE_ST_CRC) that passes here is a disagreement of device and host.
-static void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* wpp, DecodeTimes* tmp_, const ContigMap cm, bool want_seq, const int32_t* st,
-                     std::atomic<int64_t>* dstat) {
-    if (!t_zs.ok) { cp->failed = true; return; }
-    const auto t_a = std::chrono::steady_clock::now();
-    struct Acc { DecodeTimes* t; std::chrono::steady_clock::time_point a, b; bool walked = false;
-                 ~Acc() { const auto e = std::chrono::steady_clock::now(); if (!walked) b = e;
-                          t->inflate += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(b - a).count();
-                          t->walk += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(e - b).count(); } } acc{tmp_, t_a, t_a};
-    for (size_t i = wpp->i0; i < wpp->i1; i++) {
-        if (st && st[i] == 0) continue;
-        std::string e;
-        if (!bgzf_inflate(map, cp->blocks[i], cp->ubase + cp->blocks[i].uoff, verify_crc, &t_zs.zs, &e)) {
-            std::lock_guard<std::mutex> lk(cp->emu); cp->failed = true; cp->err = e; return;
-        }
-        if (verify_crc && cp->blocks[i].isize) {
-            dstat[DS_CRC_HOST].fetch_add(1, std::memory_order_relaxed);
-            if (st && st[i] == INFLATE_ST_CRC) dstat[DS_CRC_DISAGREE].fetch_add(1, std::memory_order_relaxed);
-        }
-    }
-    // speculative record walk over this range
-    acc.b = std::chrono::steady_clock::now(); acc.walked = true;
-    const uint8_t* u = cp->ubase; size_t o = wpp->spec_start; const size_t end = wpp->u_end;
-    if (o > end) { wpp->stop = o; return; }
-    int32_t cur_c = INT32_MIN;
-    while (o + 4 <= end) {
-        uint32_t bs = le32(u + o);
-        if (bs < 32 || o + 4 + (size_t)bs > end) break;
-        const uint8_t* r = u + o + 4;
-        // (a device chunk's bytes come from the GPU, not from this core's inflate: the hop from header to header is a chain of cache
-        // misses unless the lines a few records ahead are asked for early)
-        { const uint8_t* pf = r + 4096; __builtin_prefetch(pf); __builtin_prefetch(pf + 64); __builtin_prefetch(pf + 128); __builtin_prefetch(pf + 192); }   // (every line of the stretch ~18 records ahead: a header may sit on any of them)
-        const RecRef rr{r, bs, (int32_t)le32(r), le32(r + 16), le16(r + 12)};
-        const int32_t ctg = cm(rr.tid, (int32_t)le32(r + 4));
-        if (ctg != cur_c) { wpp->runs.push_back({(uint32_t)wpp->recs.size(), ctg}); cur_c = ctg; }
-        if (ctg >= 0) { wpp->n_out++; wpp->n_cig += rr.n_cig; if (want_seq) wpp->n_seq += (rr.l_seq + 1) / 2; wpp->n_name += r[8]; }
-        wpp->recs.push_back(rr);
-        o += 4 + (size_t)bs;
-    }
-    wpp->stop = o;
-}
-
 // position windows: the reference whose index range the chunk belongs to (ContigMap::only_tid), -1 without windows
 static int32_t range_only_tid(const xck_bam* b, const Chunk& c) { return b->per_tid_ranges && (size_t)c.range_id < b->range_tid.size() ? b->range_tid[c.range_id] : -1; }
 
@@ -1031,119 +458,6 @@ static void bind_to_numa_node(xck_engine* e, xck_bam* b) {
     if (b->cur_binding) b->cur_binding->enter();                     // the rest of this decode call (the scanner thread made next inherits it)
 }
 
-// locate a 2-character aux tag; returns pointer to the type byte or nullptr
-static inline const uint8_t* aux_skip(const uint8_t* p, const uint8_t* e) {       // p at type byte; returns next tag or nullptr
-    if (p >= e) return nullptr;
-    uint8_t t = *p++;
-    switch (t) {
-        case 'A': case 'c': case 'C': p += 1; break;
-        case 's': case 'S': p += 2; break;
-        case 'i': case 'I': case 'f': p += 4; break;
-        case 'Z': case 'H': { const void* z = memchr(p, 0, (size_t)(e - p)); if (!z) return nullptr; p = (const uint8_t*)z + 1; break; }
-        case 'B': { if (p + 5 > e) return nullptr; uint8_t st = *p; uint32_t n = le32(p + 1); p += 5;
-                    size_t sz = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4; p += (size_t)n * sz; break; }
-        default: return nullptr;
-    }
-    return p <= e ? p : nullptr;
-}
-
-// one record -> SoA slot o (cig_off[o] / seq_off[o] are already set)
-static inline void parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, const uint8_t* p, uint32_t len, int64_t o, int32_t sample,
-                                std::vector<InternTable::Item>& names, std::atomic<int>* flags) {
-        const uint8_t* end = p + len;
-        uint32_t l_name = p[8], n_cig = le16(p + 12), l_seq = le32(p + 16);
-        s.pos[o] = (int32_t)le32(p + 4);
-        s.mapq[o] = p[9];
-        s.flag[o] = le16(p + 14);
-        const uint8_t* q = p + 32;
-        const char* qname = (const char*)q; size_t qlen = l_name ? l_name - 1 : 0;
-        q += l_name;
-        if (q + (size_t)n_cig * 4 + (l_seq + 1) / 2 + l_seq > end) { flags->fetch_or(1); s.cell[o] = -1; s.umi[o] = XCK_UMI_NONE; return; }
-        memcpy(s.cigar + s.cig_off[o], q, (size_t)n_cig * 4);
-        q += (size_t)n_cig * 4;
-        if (dc.want_seq) memcpy(s.seq + s.seq_off[o], q, (l_seq + 1) / 2);
-        q += (l_seq + 1) / 2 + l_seq;
-        // aux tags: first occurrence wins (htslib bam_aux_get)
-        const uint8_t* cb = nullptr; const uint8_t* ub = nullptr;
-        bool need_cb = dc.use_barcodes, need_ub = dc.use_umi;
-        const uint8_t* a = q;
-        while ((need_cb || need_ub) && a && a + 3 <= end) {
-            if (need_cb && a[0] == (uint8_t)dc.cell_tag[0] && a[1] == (uint8_t)dc.cell_tag[1]) { cb = a + 2; need_cb = false; }
-            else if (need_ub && a[0] == (uint8_t)dc.umi_tag[0] && a[1] == (uint8_t)dc.umi_tag[1]) { ub = a + 2; need_ub = false; }
-            a = aux_skip(a + 2, end);
-        }
-        int32_t cell = -1;
-        if (dc.use_barcodes) {
-            if (cb && (*cb == 'Z' || *cb == 'A' || *cb == 'H')) {         // get_tag() returns str only for these
-                const char* v = (const char*)cb + 1; size_t n = (*cb == 'A') ? 1 : strnlen(v, (size_t)(end - (cb + 1)));
-                cell = dc.lookup_cell(v, n);
-            }
-        } else cell = sample;
-        s.cell[o] = cell;
-        uint64_t key = XCK_UMI_NONE; bool ovf = false;
-        if (dc.use_umi) {
-            if (ub) {
-                if (*ub == 'Z' || *ub == 'A' || *ub == 'H') {
-                    const char* v = (const char*)ub + 1; size_t n = (*ub == 'A') ? 1 : strnlen(v, (size_t)(end - (ub + 1)));
-                    key = encode_key(v, n, dc.umi_bits, e->intern, &ovf);
-                } else {                                                   // numeric tag: get_tag() gives a number; the key is its VALUE
-                    // (an int 0 / float 0.0 is falsy: `if not umi` skips the read, rdr/fc/mcount.py:41, baf/fc/mcount.py:116-117)
-                    const uint8_t* nx = aux_skip(ub, end);
-                    bool zero = false; std::string t("\1num:");
-                    if (nx) {
-                        const uint8_t* v = ub + 1; long long iv = 0; bool is_int = true;
-                        switch (*ub) { case 'c': iv = (int8_t)v[0]; break; case 'C': iv = v[0]; break; case 's': iv = (int16_t)le16(v); break; case 'S': iv = le16(v); break;
-                                       case 'i': iv = (int32_t)le32(v); break; case 'I': iv = le32(v); break; default: is_int = false; }
-                        if (is_int) { zero = iv == 0; t += std::to_string(iv); }          // equal integers are equal keys whatever their storage width
-                        else if (*ub == 'f') { float f; memcpy(&f, v, 4); zero = f == 0.0f; t.append("f", 1); t.append((const char*)v, 4); }
-                        else t.append((const char*)ub, (size_t)(nx - ub));                 // B arrays: their bytes
-                    }
-                    if (!zero) key = encode_key(t.data(), t.size(), dc.umi_bits, e->intern, &ovf);
-                }
-            }
-        } else if (encode_key_direct(qname, qlen, dc.umi_bits, &key)) { /* empty or 2-bit codable name */ }
-        else { names.push_back(InternTable::Item{InternTable::hash(qname, qlen), qname, (uint32_t)qlen, 0, &s.umi[o], dc.umi_bits}); key = XCK_UMI_NONE; }
-        if (ovf) flags->fetch_or(2);
-        s.umi[o] = key;
-}
-
-// the records of one piece of a chunk (a walk part, or a piece of the serial stitch), whose output slots start at the piece's bases
-// (prefix sums over the pieces: layout_chunk)
-static void parse_part(xck_bam* b, xck_engine* e, HostSoA* sp, int32_t sample, const WalkPart* wp, const ContigMap cm, std::atomic<int>* flags) {
-    const auto t_parse0 = std::chrono::steady_clock::now();
-    struct PAcc { xck_bam* b; std::chrono::steady_clock::time_point t0; ~PAcc() { b->tm.parse += ns_since(t0); } } pacc{b, t_parse0};
-    const DecodeCfg& dc = e->dec;
-    HostSoA& s = *sp;
-    std::vector<InternTable::Item> names;
-    if (!dc.use_umi) names.reserve(wp->n_out);
-    int64_t o = (int64_t)wp->out_base; uint32_t co = (uint32_t)wp->cig_base, so = (uint32_t)wp->seq_base;
-    const RecRef* const rend = wp->recs.data() + wp->recs.size();
-    for (const RecRef& rr : wp->recs) {
-        if (&rr + 3 < rend) { const RecRef& nx = (&rr)[3]; __builtin_prefetch(nx.p); __builtin_prefetch(nx.p + 64); __builtin_prefetch(nx.p + nx.len - 64); __builtin_prefetch(nx.p + nx.len - 128); }
-        const int32_t ctg = cm(rr.tid, (int32_t)le32(rr.p + 4));
-        if (ctg < 0) continue;
-        s.cig_off[o] = co; s.seq_off[o] = so;
-        parse_record(dc, e, s, rr.p, rr.len, o, sample, names, flags);
-        co += rr.n_cig; if (dc.want_seq) so += (rr.l_seq + 1) / 2;
-        o++;
-    }
-    if (s.has_names) {
-        // device-names mode: no host table.  One item per kept record of the piece (len 0: the key parse_record wrote is final) and the
-        // bytes of the names to intern, packed into the piece's share of the block's trailer; the device table keys them behind the copy
-        DiItem* it0 = s.items + wp->out_base;
-        memset(it0, 0, wp->n_out * sizeof(DiItem));
-        size_t at = wp->name_base; const size_t end = wp->name_base + wp->n_name;
-        for (const InternTable::Item& it : names) {
-            if (at + it.n > end) { flags->fetch_or(1); break; }            // (never: n_name counts every name with its NUL)
-            memcpy(s.name_bytes + at, it.s, it.n);
-            s.items[it.out - s.umi] = DiItem{(uint32_t)at, it.n};
-            at += it.n;
-        }
-        return;
-    }
-    if (!names.empty()) { bool ovf = false; e->intern.intern_batch(names, &ovf); if (ovf) flags->fetch_or(2); }
-}
-
 // ---- a decoded chunk's way out: jobs, the push thread ------------------------------------------------------------------
 // the chunk at the head of the ring is consumed (or dropped): its slot, if it had one and nothing is in flight on it, serves the next device chunk
 static void release_chunk(xck_bam* b, int ci) {
@@ -1179,14 +493,6 @@ static int parse_error(ChunkJob& j, std::string* msg) {
     if (fl & 1) { *msg = "corrupt BAM record (fields exceed block_size)"; return XCK_E_IO; }
     if (fl & 2) { *msg = "too many distinct non-ACGT keys for the key width"; return XCK_E_CAPACITY; }
     return 0;
-}
-// a batch = a slice of the chunk's SoA block
-static void fill_batch(const HostSoA& s, const PendingBatch& pb, bool want_seq, xck_batch* bt) {
-    memset(bt, 0, sizeof *bt);
-    bt->contig = pb.contig; bt->n_reads = (int32_t)(pb.r1 - pb.r0); bt->ordinal_base = pb.ordinal_base;
-    bt->pos = s.pos + pb.r0; bt->flag = s.flag + pb.r0; bt->mapq = s.mapq + pb.r0; bt->cell = s.cell + pb.r0; bt->umi = s.umi + pb.r0;
-    bt->cig_off = s.cig_off + pb.r0; bt->cigar = s.cigar;
-    if (want_seq) { bt->seq_off = s.seq_off + pb.r0; bt->seq = s.seq; }
 }
 
 static int redo_on_host(ChunkJob* j, std::string* msg);
@@ -1477,48 +783,31 @@ static int stitch_chunk(xck_bam* b, Chunk& c, const ContigMap& cm, const xck_ing
     return stitch_serially(b, c, cm, o, want_seq, off, hit_limit);
 }
 
-// Stage 5, layout: where every piece's records go in the job's SoA block (prefix sums over the pieces), and the batches - runs of
-// records on one contig, across piece boundaries.  Returns the number of records of the chunk (kept or not), < 0 on error.
-static int64_t layout_chunk(ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq, int64_t records_before, std::string* err) {
-    size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0, n_name = 0;
-    for (WalkPart& wp : pieces) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; wp.name_base = n_name; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_name += wp.n_name; n_rec += wp.recs.size(); }
-    if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
-    HostSoA& s = j.soa;
-    if (n_name >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
-    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1, n_out, n_name, j.names)) { *err = "out of host memory"; return XCK_E_NOMEM; }
-    s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
-    const uint64_t ord_hi = (uint64_t)(uint32_t)o->sample << ORD_REC_BITS;
-    int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0, rec0 = 0;
-    auto close_batch = [&](int64_t oi) { if (cur_c >= 0 && oi > seg0) j.batches.push_back({cur_c, seg0, oi, ord_hi | (uint64_t)(records_before + seg_r)}); };
-    for (const WalkPart& wp : pieces) {
-        int64_t oi = (int64_t)wp.out_base;
-        for (size_t ri = 0; ri < wp.runs.size(); ri++) {
-            const ContigRun& rn = wp.runs[ri];
-            const uint32_t nxt = ri + 1 < wp.runs.size() ? wp.runs[ri + 1].first : (uint32_t)wp.recs.size();
-            if (rn.contig != cur_c) { close_batch(oi); cur_c = rn.contig; seg0 = oi; seg_r = rec0 + rn.first; }
-            if (rn.contig >= 0) oi += nxt - rn.first;
-        }
-        rec0 += (int64_t)wp.recs.size();
-    }
-    close_batch((int64_t)n_out);
-    return (int64_t)n_rec;
-}
+// (Stage 5, layout: layout_chunk, bam_records.cpp)
 
-// position windows: the chunk's last record starts beyond its reference's window - the rest of that reference's range is dropped
-static void drop_range_past_window(xck_bam* b, const Chunk& c, const ContigMap& cm, const std::vector<WalkPart>& pieces) {
+// position windows: the chunk's last record (its tid and pos) starts beyond its reference's window - the rest of that reference's range is dropped
+static void drop_range_past_window(xck_bam* b, const Chunk& c, const ContigMap& cm, int32_t last_tid, int32_t last_pos) {
     if (!b->per_tid_ranges || !cm.t_end) return;
-    const RecRef* last = nullptr;
-    for (size_t pi = pieces.size(); pi-- > 0 && !last;) if (!pieces[pi].recs.empty()) last = &pieces[pi].recs.back();
-    if (last && last->tid >= 0 && last->tid < cm.n_refs && cm.t_end[last->tid] > 0 && (int32_t)le32(last->p + 4) >= cm.t_end[last->tid]) {
+    if (last_tid >= 0 && last_tid < cm.n_refs && cm.t_end[last_tid] > 0 && last_pos >= cm.t_end[last_tid]) {
         b->skip_range = c.range_id; b->scanner->abandon(c.range_id);
     }
 }
 
 static void queue_parse_tasks(xck_bam* b, ChunkJob& j, const std::vector<WalkPart>& pieces, const ContigMap& cm, int32_t sample) {
-    xck_engine* e = j.e; HostSoA* sp = &j.soa; std::atomic<int>* fl = &j.flags;
+    xck_engine* e = j.e; HostSoA* sp = &j.soa; std::atomic<int>* fl = &j.flags; DecodeTimes* tm = &b->tm;
     for (const WalkPart& wp : pieces) { if (!wp.n_out) continue; const WalkPart* wpp = &wp;
-        j.tg.later([b, e, sp, sample, wpp, cm, fl] { parse_part(b, e, sp, sample, wpp, cm, fl); }); }
+        j.tg.later([tm, e, sp, sample, wpp, cm, fl] { parse_part(tm, e, sp, sample, wpp, cm, fl); }); }
     j.tg.flush(*b->pool, true);                                         // (ahead of the later chunks' inflate tasks)
+}
+
+// the job goes to the push thread (made at the first one); waits while Pusher::MAXQ chunks are outstanding behind this one.
+// Returns the push thread's first failure so far.
+static int hand_to_pusher(xck_bam* b, ChunkJob& j, PhaseClock& clk) {
+    if (!b->pusher) b->pusher = new Pusher();
+    const int prc = b->pusher->submit(&j);
+    clk.lap(b->tm.wait_push);
+    if (prc) b->err = b->pusher->err;
+    return prc;
 }
 
 // Stages 4 - 6 of a chunk the device walked (c.dp_ok): its summaries -> the batch list (parse_dev.h summaries_to_batches, what
@@ -1530,17 +819,10 @@ static int layout_walked_chunk(xck_bam* b, Chunk& c, ChunkJob& j, const ContigMa
     j.dev = true; j.b = b; j.cm = cm; j.rec_before = b->n_records;
     memset(&j.opts, 0, sizeof j.opts); memcpy(&j.opts, o, std::min<size_t>(o->struct_size, sizeof j.opts));
     clk.lap(b->tm.dp_layout);
-    if (b->per_tid_ranges && cm.t_end && j.lay.has_last) {              // drop_range_past_window, on the last record the walk saw
-        const int32_t tid = j.lay.last_tid;
-        if (tid >= 0 && tid < cm.n_refs && cm.t_end[tid] > 0 && j.lay.last_pos >= cm.t_end[tid]) { b->skip_range = c.range_id; b->scanner->abandon(c.range_id); }
-    }
+    if (j.lay.has_last) drop_range_past_window(b, c, cm, j.lay.last_tid, j.lay.last_pos);   // (the last record the walk saw)
     b->n_records += (int64_t)j.lay.n_rec;
     advance_head(b, &j);
-    if (!b->pusher) b->pusher = new Pusher();
-    const int prc = b->pusher->submit(&j);
-    clk.lap(b->tm.wait_push);
-    if (prc) b->err = b->pusher->err;
-    return prc;
+    return hand_to_pusher(b, j, clk);
 }
 
 // Stage 6, parse: one pool task per piece, record fields -> the job's SoA block.  The coordinator waits for them here, or
@@ -1552,15 +834,12 @@ static int parse_or_defer(xck_bam* b, Chunk& c, ChunkJob& j, const std::vector<W
         clk.lap(b->tm.wait_parse);
         if (const int rc = parse_error(j, &b->err)) return rc;
     }
-    drop_range_past_window(b, c, cm, pieces);                           // (it only looks at the record lists)
+    const RecRef* last = nullptr;                                       // (the record lists are read, not what the parse tasks write)
+    for (size_t pi = pieces.size(); pi-- > 0 && !last;) if (!pieces[pi].recs.empty()) last = &pieces[pi].recs.back();
+    if (last) drop_range_past_window(b, c, cm, last->tid, (int32_t)le32(last->p + 4));
     b->n_records += n_rec;
     advance_head(b, b->defer_parse ? &j : nullptr);
-    if (!b->defer_parse) return 0;
-    if (!b->pusher) b->pusher = new Pusher();
-    const int prc = b->pusher->submit(&j);                              // waits while two chunks are outstanding behind this one
-    clk.lap(b->tm.wait_push);
-    if (prc) b->err = b->pusher->err;
-    return prc;
+    return b->defer_parse ? hand_to_pusher(b, j, clk) : 0;
 }
 
 // The push thread's way down the host path, for a chunk whose parse kernel met a record it leaves to the host (a UMI to intern): the

@@ -82,7 +82,7 @@ int  dev_intern_launch_recs(DevIntern* t, hipStream_t stream, const GpuInflateSl
 #include <hip/hip_runtime.h>
 namespace xck {
 
-// bam.cpp hash_bytes, byte for byte
+// bam_records.cpp hash_bytes, byte for byte
 __device__ inline uint64_t dp_hash_bytes(const uint8_t* s, uint32_t n) {
     uint64_t h = 0x9E3779B97F4A7C15ull ^ ((uint64_t)n * 0xff51afd7ed558ccdull);
     while (n >= 8) { uint64_t w = 0; for (int k = 0; k < 8; k++) w |= (uint64_t)s[k] << (8 * k); h = (h ^ w) * 0xbf58476d1ce4e5b9ull; h ^= h >> 32; s += 8; n -= 8; }
@@ -90,7 +90,7 @@ __device__ inline uint64_t dp_hash_bytes(const uint8_t* s, uint32_t n) {
     h ^= h >> 29; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 32;
     return h;
 }
-// bam.cpp encode_key_direct: the keys that need no table - empty -> NONE, short ACGT -> 2-bit code.  false: the string is interned
+// bam_records.cpp encode_key_direct: the keys that need no table - empty -> NONE, short ACGT -> 2-bit code.  false: the string is interned
 __device__ inline bool dp_encode_direct(const uint8_t* s, size_t n, int umi_bits, uint64_t* out) {
     if (n == 0) { *out = XCK_UMI_NONE; return true; }
     bool ok = 2 * (long long)n + 1 <= (long long)umi_bits - 1;

@@ -16,7 +16,7 @@
 namespace xck {
 
 // The SoA block of one decoded chunk: nine columns carved out of one block, every column 256-byte aligned.  One layout for the host
-// decoder (bam.cpp soa_reserve) and for the parse kernel, which writes the same block in the engine's staging slot.
+// decoder (bam_records.cpp soa_reserve) and for the parse kernel, which writes the same block in the engine's staging slot.
 struct SoaLayout { size_t o_umi, o_pos, o_cell, o_cgo, o_sqo, o_cig, o_flag, o_mapq, o_seq, total; };
 XCK_HD inline SoaLayout soa_layout(size_t n_reads, size_t n_cig, size_t n_seq) {
     auto up = [](size_t x) { return (x + 255) & ~size_t(255); };
@@ -58,7 +58,7 @@ struct DpHead { uint32_t walk_flags, parse_flags, n_rec, n_out, n_cig, n_seq, pa
 // neighbouring blocks cannot meet
 XCK_HD inline size_t dp_rec_capacity(size_t out_bytes) { return out_bytes / 36 + 1; }
 
-// what the walk applies per record (bam.cpp ContigMap::operator())
+// what the walk applies per record (bam_decode.h ContigMap::operator())
 struct DpContigMap { const int32_t* t2c; const int32_t* t_end; int32_t n_refs, only_tid; };
 XCK_HD inline int32_t dp_contig(const DpContigMap& cm, int32_t tid, int32_t pos) {
     if (tid < 0 || tid >= cm.n_refs || !cm.t2c) return -1;

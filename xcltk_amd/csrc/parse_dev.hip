@@ -4,7 +4,7 @@
 //            has just written; all blocks of the chunk at once), applies the contig map and notes per record where it lies and where
 //            its output goes within the block; per block the counts, the contig runs and the last record's tid / pos.
 //   k_scan   one workgroup: per-block counts -> bases, the chunk's totals and flags.
-//   k_parse  one wave per 64 records of a block, one lane per record: the fixed fields and the aux scan (bam.cpp parse_record, restated bit for bit),
+//   k_parse  one wave per 64 records of a block, one lane per record: the fixed fields and the aux scan (bam_records.cpp parse_record, restated bit for bit),
 //            then CIGAR and sequence bytes wave-cooperatively - the outputs of 64 consecutive records are contiguous.
 // The walk and the scan run on the slot's stream behind k_inflate; the parse is launched by the engine's push path into its staging slot.
 #include <hip/hip_runtime.h>
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(SCAN_T) void k_scan(const DpCnt* __restrict__ cnt, 
 }
 
 // ---- parse -------------------------------------------------------------------------------------------------------------------------
-// (dp_hash_bytes = bam.cpp hash_bytes and dp_encode_direct = its encode_key_direct: intern_dev.h, which the name kernels share)
+// (dp_hash_bytes = bam_records.cpp hash_bytes and dp_encode_direct = its encode_key_direct: intern_dev.h, which the name kernels share)
 // DecodeCfg::lookup_cell for lists whose barcodes all fit a slot's key (the device path is on only then): same hash, same probe order
 __device__ inline int32_t dp_lookup_cell(const DpParseCfg& cfg, const uint8_t* s, size_t n) {
     if (!cfg.bc) return -1;
@@ -104,7 +104,7 @@ __device__ inline int32_t dp_lookup_cell(const DpParseCfg& cfg, const uint8_t* s
         h = (h + 1) & cfg.bc_mask;
     }
 }
-// bam.cpp aux_skip on offsets: a at the type byte, e the record's end; returns the next tag's offset, or -1
+// bam_records.cpp aux_skip on offsets: a at the type byte, e the record's end; returns the next tag's offset, or -1
 __device__ inline long long dp_aux_skip(const uint8_t* r, long long a, long long e) {
     if (a >= e) return -1;
     const uint8_t t = r[a++];

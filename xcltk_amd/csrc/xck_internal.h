@@ -42,6 +42,7 @@ private:
     };
     Shard shards_[NSHARD];
     // id = (local index << 6) | shard  -> unique without a global counter
+    static uint64_t probe_or_insert(Shard& sh, uint64_t h, const char* s, uint32_t n);   // (bam_records.cpp: intern and intern_batch)
 };
 
 // Decoder settings derived from xck_config at xck_create()
@@ -133,7 +134,7 @@ enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_C
 struct EngineImpl;                       // one GPU pipeline of a handle (engine_impl.h)
 struct Stager;                           // device staging slots of engine_push_block (engine.hip)
 struct DevIntern;                        // the handle's intern table in HBM (intern_dev.h)
-uint64_t intern_id_limit(int umi_bits);  // ids an intern table may hand out for that key width (bam.cpp; XCK_TEST_INTERN_LIMIT)
+uint64_t intern_id_limit(int umi_bits);  // ids an intern table may hand out for that key width (bam_records.cpp; XCK_TEST_INTERN_LIMIT)
 // the names a host-parsed chunk hands to the device table: DiItem[n_out] at items_off of its block, the packed bytes behind them
 struct NameTrailer { size_t items_off, bytes_off, n_bytes, n_out; };
 
