@@ -265,6 +265,30 @@ def test_state_and_lifetimes():
         _same(eng.group_counts(cg1, 4), g3, R.MATS)
 
 
+def test_snp_source_on_either_side_of_the_copy_out_threshold():
+    """The dense SNP x cell case of test_gpu_snp_counts.threshold_case as the source.  Under the identity mapping the output is as
+    large as the source and crosses on the copy stream; under a mapping into three groups on the same handle it is stored by the CUs
+    into buffers that the large call grew.  A view of the snp_counts blocks taken before holds the same bytes afterwards."""
+    from test_gpu_snp_counts import COPY_STREAM_BYTES, THR_CELLS, THR_REGIONS, THR_SNPS, coo_bytes, threshold_case
+    snps, batch, exp = threshold_case(THR_SNPS)
+    with Engine(BAF, ["1"], THR_REGIONS, THR_CELLS, snps=snps, **FILT) as eng:
+        eng.push(batch[0])
+        eng.finish()
+        sview = eng.snp_counts(copy=False)
+        ssnap = {k: tuple(x.copy() for x in sview[k]) for k in R.MATS}
+        _same(ssnap, exp, R.MATS)
+        ident = np.arange(THR_CELLS, dtype=np.int32)
+        big = eng.group_counts(ident, THR_CELLS, source="snp")
+        assert coo_bytes(big) >= COPY_STREAM_BYTES
+        _same(big, G.aggregate_all(exp, ident), R.MATS)
+        _same(sview, ssnap, R.MATS)                                        # the source blocks did not move or change
+        cg3 = (np.arange(THR_CELLS) % 3).astype(np.int32)
+        small = eng.group_counts(cg3, 3, source="snp")
+        assert 0 < coo_bytes(small) < COPY_STREAM_BYTES
+        _same(small, G.aggregate_all(exp, cg3), R.MATS)
+        _same(sview, ssnap, R.MATS)
+
+
 def test_debug_timing_prints_one_line():
     code = ("import sys; sys.path[:0] = [%r, %r, %r]\n"
             "import numpy as np, util\nfrom xcltk_amd import capi\nfrom xcltk_amd.engine import Engine\n"

@@ -3,6 +3,7 @@ of the molecule stage (csrc/snp_counts.h), and the one-pass `xcltk baf` built on
 the CPU oracle driven with one one-base region per SNP (REF on haplotype 0, ALT on 1, min_count 1, min_maf 0, no_dup_hap) - the
 construction baf/genotype.py has always used.  Every test calls the new method or the new module, so none passes without them."""
 import collections
+import functools
 import os
 import re
 
@@ -342,7 +343,72 @@ def test_state_and_errors():
         util.assert_coo_equal(eng.finish(), cnt, ["count"])
 
 
-# ---------------------------------------------------------------------------------------------- 5. one pass for `xcltk baf`
+# ---------------------------------------------------------------------------------------------- 5. either side of the copy-out threshold
+COPY_STREAM_BYTES = 8 << 20               # a result of this many bytes or more crosses on the copy stream, a smaller one is stored by the CUs
+THR_SNPS, THR_CELLS, THR_READS = 700, 500, 70
+THR_REGIONS = [("1", 1, 7000, "g")]
+
+
+@functools.lru_cache(maxsize=None)
+def threshold_case(n_snps, cells_with_reads=THR_CELLS):
+    """A pileup whose SNP x cell matrices are dense: SNPs nine bases apart (REF A, ALT C), and for every cell 0 .. cells_with_reads - 1
+    THR_READS 91M reads laid end to end over them (the last base of a read is the first of the next), a UMI each, every base C.  Every
+    cell shows ALT at every SNP, so AD and DP hold n_snps * cells_with_reads entries each and OTH none: with THR_CELLS cells,
+    THR_SNPS SNPs give 3 * 4 * 2 * 350 000 = 8 400 000 bytes >= 8 MiB = 8 388 608 and four SNPs fewer 8 352 000.
+    -> (snps, batch, the oracle's one-base matrices over THR_CELLS columns); made once per size and shared (test_gpu_group_counts.py
+    reads it too): nobody writes to it."""
+    assert n_snps <= THR_SNPS
+    snps = [("1", 101 + 9 * k, "A", "C", 0, 1) for k in range(n_snps)]
+    j, cell = (x.ravel() for x in np.meshgrid(np.arange(THR_READS), np.arange(cells_with_reads), indexing="ij"))
+    n = len(j)
+    d = dict(contig=0, ordinal_base=0, pos=(100 + 90 * j).astype(np.int32), flag=np.zeros(n, np.uint16), mapq=np.full(n, 60, np.uint8),
+             cell=cell.astype(np.int32), umi=((1 << 24) | np.arange(n)).astype(np.uint64), cig_off=np.arange(n + 1, dtype=np.uint32),
+             cigar=np.full(n, (91 << 4) | 0, np.uint32), seq_off=(46 * np.arange(n + 1)).astype(np.uint32), seq=np.full(46 * n, 0x22, np.uint8))
+    batch = util.batch_from_dict(d)
+    exp = R.oracle_of(["1"], onebase(snps), THR_CELLS, [batch[0]], FILT)
+    assert len(exp["ad"][0]) == len(exp["dp"][0]) == n_snps * cells_with_reads and len(exp["oth"][0]) == 0
+    return snps, batch, {k: exp[k] for k in R.MATS}
+
+
+def coo_bytes(m):
+    """What a derived-matrix call hands to the host: three int32 arrays per matrix."""
+    return 3 * 4 * sum(len(m[k][0]) for k in R.MATS)
+
+
+def _snp_counts_of(eng, batch):
+    eng.push(batch[0])
+    eng.finish()
+    return eng.snp_counts()
+
+
+@pytest.mark.parametrize("n_snps,large", [(THR_SNPS, True), (THR_SNPS - 4, False)], ids=["copy_stream", "mapped_store"])
+def test_result_on_either_side_of_the_copy_out_threshold(n_snps, large):
+    snps, batch, exp = threshold_case(n_snps)
+    with Engine(BAF, ["1"], THR_REGIONS, THR_CELLS, snps=snps, **FILT) as eng:
+        got = _snp_counts_of(eng, batch)
+    print("%d SNPs: %d bytes" % (n_snps, coo_bytes(got)))
+    if large:
+        assert coo_bytes(got) >= COPY_STREAM_BYTES
+    else:
+        assert coo_bytes(got) < COPY_STREAM_BYTES
+    _same(got, exp)
+    _sorted_by_row_col(got, n_snps)
+
+
+def test_a_smaller_result_after_a_larger_one_on_one_handle():
+    """small, large, small: the call's buffers only grow, so the third call finds a scratch block, a device block and a pinned block
+    sized for the second - and the large result takes the copy stream where its neighbours take the store kernel."""
+    snps, big, exp_big = threshold_case(THR_SNPS)
+    _, small, exp_small = threshold_case(THR_SNPS, 7)
+    with Engine(BAF, ["1"], THR_REGIONS, THR_CELLS, snps=snps, **FILT) as eng:
+        for batch, exp, large in ((small, exp_small, False), (big, exp_big, True), (small, exp_small, False)):
+            got = _snp_counts_of(eng, batch)
+            assert (coo_bytes(got) >= COPY_STREAM_BYTES) == large
+            _same(got, exp)
+            eng.reset()
+
+
+# ---------------------------------------------------------------------------------------------- 6. one pass for `xcltk baf`
 DS = os.path.join(util.GOLDEN, "datasets", "phasing")
 
 

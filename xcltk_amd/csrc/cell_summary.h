@@ -1,7 +1,8 @@
 // cell_summary.h - opt-in per-cell table (XCK_F_CELL_SUMMARY / XCK_CELL_SUMMARY=1; xck_get_cell_summary, include/xck.h).
 // Included by engine.hip inside namespace xck, in front of read_fate.h: the grouped accumulation below is what the per-cell
 // instantiation of the read-fate pass (k_read_fate_cell, read_fate.h) and the column marginals of the result blocks
-// (k_cell_marginals, here) share.  Uses JOIN_BLOCK, as_global, EngineImpl and HIP_TRY from engine_impl.h.
+// (k_cell_marginals, here) share; launch_marginals() is the one host loop over the result blocks, for the column marginals here and
+// the row marginals of feature_summary.h.  Uses JOIN_BLOCK, as_global, EngineImpl and HIP_TRY from engine_impl.h.
 //
 // The table in HBM: one row per cell plus one for the reads without a listed cell, CS_ROW_WORDS = 16 64-bit words = 128 B a row
 // (the 12 columns of xck_read_fate from low_mapq on, 4 words of padding), so that a row is one aligned line and its columns are
@@ -167,26 +168,33 @@ static int cell_summary_init(EngineImpl* im) {
     return 0;
 }
 
-// column marginals of the matrices of the last finish -> im->h_cmat ([n_cells * k]); once per finish
-static int cell_marginals(EngineImpl* im, const int k) {
-    HIP_TRY(hipMemsetAsync(im->d_cmat, 0, (size_t)im->n_cells * k * sizeof(unsigned long long), im->s_comp));
-    // basefc: umis = column sums of count, features = its entries; BAF: ad, dp, oth sums, features = entries of DP
-    struct { int m, wide_col, c32_base; } job[3] = { {0, 0, 1}, {0, 0, -1}, {0, 0, -1} };
-    int n_job = 1;
-    if (im->mode != XCK_MODE_BASEFC) { job[0] = {1, 0, -1}; job[1] = {2, 1, 3}; job[2] = {3, 2, -1}; n_job = 3; }
+// One k_cell_marginals launch per job: result block m of the last finish, summed by its column array (by_row: by its row array) into
+// `tab` ([n_rows * stride] words): the sum of val goes to wide_col, the number of entries to c32_base (< 0: not counted).
+struct MargJob { int m, wide_col, c32_base; };
+static int launch_marginals(EngineImpl* im, const MargJob* job, const int n_job, const bool by_row, unsigned long long* tab, const int n_rows, const int stride) {
     for (int q = 0; q < n_job; q++) {
         const size_t z = im->res_nnz[job[q].m];
         if (!z) continue;
         const int32_t* d = im->d_res[job[q].m];
         if (!d) { im->eng->err = "internal: result block without a device copy"; return XCK_E_STATE; }
         MargArgs a;
-        a.col = d + z; a.val = d + 2 * z; a.n = (long long)z;
-        a.ca.tab = im->d_cmat; a.ca.n_rows = im->n_cells; a.ca.slot_mask = cs_slot_mask(im); a.ca.stride = k;
+        a.col = by_row ? d : d + z; a.val = d + 2 * z; a.n = (long long)z;
+        a.ca.tab = tab; a.ca.n_rows = n_rows; a.ca.slot_mask = cs_slot_mask(im); a.ca.stride = stride;
         a.ca.c32_base = job[q].c32_base; a.ca.wide_col = job[q].wide_col;
         const size_t per = (size_t)JOIN_BLOCK * MG_ITEMS;
         hipLaunchKernelGGL(k_cell_marginals, dim3((unsigned)((z + per - 1) / per)), dim3(JOIN_BLOCK), 0, im->s_comp, a);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+// column marginals of the matrices of the last finish -> im->h_cmat ([n_cells * k]); once per finish
+static int cell_marginals(EngineImpl* im, const int k) {
+    HIP_TRY(hipMemsetAsync(im->d_cmat, 0, (size_t)im->n_cells * k * sizeof(unsigned long long), im->s_comp));
+    // basefc: umis = column sums of count, features = its entries; BAF: ad, dp, oth sums, features = entries of DP
+    const MargJob fc[1] = { {0, 0, 1} }, baf[3] = { {1, 0, -1}, {2, 1, 3}, {3, 2, -1} };
+    const bool is_fc = im->mode == XCK_MODE_BASEFC;
+    if (int rc = launch_marginals(im, is_fc ? fc : baf, is_fc ? 1 : 3, false, im->d_cmat, im->n_cells, k)) return rc;
     im->h_cmat.resize((size_t)im->n_cells * k);
     HIP_TRY(hipMemcpyAsync(im->h_cmat.data(), im->d_cmat, im->h_cmat.size() * sizeof(int64_t), hipMemcpyDeviceToHost, im->s_comp));
     HIP_TRY(hipStreamSynchronize(im->s_comp));

@@ -1517,14 +1517,11 @@ void engine_destroy(EngineImpl* im) {
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
                      im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept,
-                     im->d_csr_alt, im->d_rf, im->d_sc, im->d_sc_res, im->d_sc_perm, im->d_gc, im->d_gc_res, im->ws1.base, im->ws2.base };
+                     im->d_csr_alt, im->d_rf, im->d_sc_perm, im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }
     for (int m = 0; m < 4; m++) if (im->h_res[m]) hipHostFree(im->h_res[m]);
-    if (im->h_sc_res) hipHostFree(im->h_sc_res);
-    if (im->h_sc_tot) hipHostFree(im->h_sc_tot);
-    if (im->h_gc_res) hipHostFree(im->h_gc_res);
-    if (im->h_gc_tot) hipHostFree(im->h_gc_tot);
+    coo_call_free(im->sc); coo_call_free(im->gc);
     if (im->h_ctl) hipHostFree(im->h_ctl);
     if (im->ev0) hipEventDestroy(im->ev0);
     if (im->ev1) hipEventDestroy(im->ev1);
@@ -1534,8 +1531,6 @@ void engine_destroy(EngineImpl* im) {
     if (im->ev_f1) hipEventDestroy(im->ev_f1);
     if (im->ev_f2) hipEventDestroy(im->ev_f2);
     for (hipEvent_t ev : { im->ev_r0, im->ev_r1, im->ev_r2, im->ev_r3 }) if (ev) hipEventDestroy(ev);
-    for (hipEvent_t ev : im->ev_s) if (ev) hipEventDestroy(ev);
-    for (hipEvent_t ev : im->ev_g) if (ev) hipEventDestroy(ev);
     if (im->s_copy) hipStreamDestroy(im->s_copy);
     if (im->s_comp) hipStreamDestroy(im->s_comp);
     delete im;

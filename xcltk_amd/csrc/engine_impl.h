@@ -131,6 +131,23 @@ struct Arena {
     }
 };
 
+// State of one derived-matrix call (xck_snp_counts, xck_group_counts; the host steps that work on it are in coo_call.h).  Buffers of
+// the call's own, grow-only, freed at destroy (coo_call_free): nothing of it comes from the workspaces or the shard slices.
+struct CooCall {
+    char* d_scratch = nullptr; size_t scratch_cap = 0;                   // one block, laid out anew by every call (ScratchLayout)
+    int32_t* d_res = nullptr; size_t d_res_cap = 0;                      // the call's COO blocks [row | col | val], back to back, on the device
+    int32_t* h_res = nullptr; size_t h_res_cap = 0;                      // ... and in pinned host memory (capacities in bytes)
+    unsigned long long *h_tot = nullptr, *d_tot_alias = nullptr;         // the totals and a flag word: pinned + mapped words and their device alias
+    size_t nnz[3] = {0, 0, 0};                                           // entries of the blocks of the last call
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};    // first phase [0, 1], second [1, 2], emit [3, 4]
+    double ms_total = 0, ms_copy = 0; float ms_phase[3] = {0, 0, 0};     // the last call (host clock; HIP events), for XCK_DEBUG_TIMING and tools/*_counts_time.py
+};
+static inline void coo_call_free(CooCall& c) {
+    for (void* p : { (void*)c.d_scratch, (void*)c.d_res }) if (p) hipFree(p);
+    for (void* p : { (void*)c.h_res, (void*)c.h_tot }) if (p) hipHostFree(p);
+    for (hipEvent_t ev : c.ev) if (ev) hipEventDestroy(ev);
+}
+
 struct EngineImpl {
     xck_engine* eng = nullptr;
     int mode = 0, device = 0;
@@ -213,25 +230,13 @@ struct EngineImpl {
     char* d_rf = nullptr; size_t rf_cap = 0;              // sorted regions, exclusion words, SNP mask, contig table, scan block sums
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr, ev_r2 = nullptr, ev_r3 = nullptr;   // count pass + scan, fill pass
     double rf_ms_upload = 0, rf_ms_build = 0, rf_ms_regions = 0, rf_ms_total = 0;   // the last refold, for XCK_DEBUG_TIMING and tools/refold_time.py
-    // xck_snp_counts (snp_counts.h): buffers of its own, grow-only - scratch, the three COO blocks [ad | dp | oth] on the device and in
-    // pinned host memory (valid until the next xck_snp_counts / reset), the sorted SNP -> caller index table on the device
-    char* d_sc = nullptr; size_t sc_cap = 0;
-    int32_t* d_sc_res = nullptr; size_t sc_res_cap = 0;
-    int32_t* h_sc_res = nullptr; size_t h_sc_res_cap = 0;
+    // xck_snp_counts (snp_counts.h): a CooCall holding the three blocks [ad | dp | oth] (valid until the next xck_snp_counts / reset),
+    // and the sorted SNP -> caller index table on the device
+    CooCall sc;
     int32_t* d_sc_perm = nullptr;
-    unsigned long long *h_sc_tot = nullptr, *d_sc_tot_alias = nullptr;   // the three totals: pinned + mapped words and their device alias
-    size_t sc_nnz[3] = {0, 0, 0}; bool sc_valid = false;
-    hipEvent_t ev_s[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    double sc_ms_heads = 0, sc_ms_rows = 0, sc_ms_emit = 0, sc_ms_copy = 0, sc_ms_total = 0;   // the last call, for XCK_DEBUG_TIMING and tools/snp_counts_time.py
-    // xck_group_counts (group_counts.h): buffers of its own, grow-only - scratch (control words, the cell -> group mapping, row pointers,
-    // row counts, the long-row queue), the COO blocks of this pipeline's matrices on the device and in pinned host memory (valid until
-    // the next xck_group_counts / reset)
-    char* d_gc = nullptr; size_t gc_cap = 0;
-    int32_t* d_gc_res = nullptr; size_t gc_res_cap = 0;
-    int32_t* h_gc_res = nullptr; size_t h_gc_res_cap = 0;
-    unsigned long long *h_gc_tot = nullptr, *d_gc_tot_alias = nullptr;   // the totals and the overflow flag: pinned + mapped words and their device alias
-    size_t gc_nnz[3] = {0, 0, 0};
-    hipEvent_t ev_g[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    bool sc_valid = false;
+    // xck_group_counts (group_counts.h): a CooCall holding the blocks of this pipeline's matrices (valid until the next xck_group_counts / reset)
+    CooCall gc;
 };
 
 // d_snp_info: ref nibble | alt nibble << 4 | ref_hap << 8 | alt_hap << 9

@@ -1,7 +1,7 @@
 // feature_summary.h - opt-in per-feature and per-SNP tables (XCK_F_FEATURE_SUMMARY / XCK_FEATURE_SUMMARY=1; xck_get_feature_summary,
 // include/xck.h).  Included by engine.hip inside namespace xck, behind read_fate.h: it uses that file's FateArgs, read_fate_walk and
-// rf_targets (the read filter and the accept rule are stated there and nowhere else), the grouped accumulation and k_cell_marginals
-// of cell_summary.h, and snp_verdicts() of finish.hip.
+// rf_targets (the read filter and the accept rule are stated there and nowhere else), the grouped accumulation and the marginal
+// launcher (launch_marginals, k_cell_marginals) of cell_summary.h, and snp_verdicts() of finish.hip.
 //
 // The read half.  One more pass over the batches the join has just been launched on, like k_read_fate - but where a read adds one
 // (row, column) to the per-cell table it adds one per (read, region) pair or covered SNP to these, so the loop is a different one:
@@ -106,28 +106,14 @@ static int launch_feature_fate(EngineImpl* im) {
 }
 
 // row marginals of the matrices of the last finish -> im->h_fmat ([n_regions * k]), and for the pileup the tallies and verdicts of
-// its SNPs -> im->h_tally / im->h_kept (sorted SNP order); once per finish.  k_cell_marginals as it stands, with the ROW array of a
-// result block in the place of its column array.
+// its SNPs -> im->h_tally / im->h_kept (sorted SNP order); once per finish.  launch_marginals() of cell_summary.h, keyed by the ROW
+// array of a result block.
 static int feature_marginals(EngineImpl* im, const int k) {
     const bool baf = im->mode != XCK_MODE_BASEFC;
     HIP_TRY(hipMemsetAsync(im->d_fmat, 0, std::max<size_t>((size_t)im->n_regions * k, 1) * sizeof(unsigned long long), im->s_comp));
     // basefc: umis = row sums of count, cells = its entries; BAF: snps, snps_kept (host, below), ad, dp, oth sums, cells = entries of DP
-    struct { int m, wide_col, c32_base; } job[3] = { {0, 0, 1}, {0, 0, -1}, {0, 0, -1} };
-    int n_job = 1;
-    if (baf) { job[0] = {1, 2, -1}; job[1] = {2, 3, 5}; job[2] = {3, 4, -1}; n_job = 3; }
-    for (int q = 0; q < n_job; q++) {
-        const size_t z = im->res_nnz[job[q].m];
-        if (!z) continue;
-        const int32_t* d = im->d_res[job[q].m];
-        if (!d) { im->eng->err = "internal: result block without a device copy"; return XCK_E_STATE; }
-        MargArgs a;
-        a.col = d; a.val = d + 2 * z; a.n = (long long)z;
-        a.ca.tab = im->d_fmat; a.ca.n_rows = im->n_regions; a.ca.slot_mask = cs_slot_mask(im); a.ca.stride = k;
-        a.ca.c32_base = job[q].c32_base; a.ca.wide_col = job[q].wide_col;
-        const size_t per = (size_t)JOIN_BLOCK * MG_ITEMS;
-        hipLaunchKernelGGL(k_cell_marginals, dim3((unsigned)((z + per - 1) / per)), dim3(JOIN_BLOCK), 0, im->s_comp, a);
-        HIP_TRY(hipGetLastError());
-    }
+    const MargJob fc[1] = { {0, 0, 1} }, pile[3] = { {1, 2, -1}, {2, 3, 5}, {3, 4, -1} };
+    if (int rc = launch_marginals(im, baf ? pile : fc, baf ? 3 : 1, true, im->d_fmat, im->n_regions, k)) return rc;
     im->h_fmat.resize((size_t)im->n_regions * k);
     if (!im->h_fmat.empty()) HIP_TRY(hipMemcpyAsync(im->h_fmat.data(), im->d_fmat, im->h_fmat.size() * sizeof(int64_t), hipMemcpyDeviceToHost, im->s_comp));
     if (baf) {

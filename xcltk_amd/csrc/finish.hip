@@ -11,10 +11,11 @@
 //                 128-bit keys: k_first_read and the sorted path.
 //   snp_counts  : the SNP x cell matrices of the finished pileup from the molecule stage alone (snp_counts.h).
 //   group_counts: the row x group sums of the result blocks or of the SNP x cell blocks under a cell -> group mapping (group_counts.h).
-//                 Copy-out on the copy stream (xck_finish_async).
+//                 The host steps the two calls share are coo_call.h's.  Copy-out (deliver_words) on the copy stream (xck_finish_async).
 //
 // Integer / byte work only - HBM-bound, no MFMA.  See DESIGN.md for layouts, byte counts and measurements.
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -678,6 +679,27 @@ __global__ void k_copy_words3(CopySeg3 sg) {                              // blo
     const int32_t* __restrict__ src = sg.src[blockIdx.y]; int32_t* __restrict__ dst = sg.dst[blockIdx.y]; const size_t n = sg.n[blockIdx.y];
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }
+// The copy-out rule, stated here and nowhere else: a block of COPY_STREAM_BYTES or more crosses PCIe on the copy stream while the compute
+// stream (and other engines) keep the CUs busy; the CUs store a smaller one into mapped pinned memory (no DMA queue shared with another
+// engine's bulk copy).  deliver_words: `words` of d_src -> the mapped pinned block h_dst, behind the compute stream's work up to `after`
+// (an event the caller recorded there; only the large side reads it); copy_begin, if given, is recorded on the copy stream ahead of the copy.
+constexpr size_t COPY_STREAM_BYTES = size_t(8) << 20;
+static inline bool on_copy_stream(size_t words) { return words * sizeof(int32_t) >= COPY_STREAM_BYTES; }
+static inline unsigned copy_grid(size_t words) { return (unsigned)std::min<size_t>((words + 255) / 256, 1024); }   // blocks of 256 for k_copy_words / k_copy_words3
+static int host_alias(EngineImpl* im, int32_t* h, int32_t** alias) { HIP_TRY(hipHostGetDevicePointer((void**)alias, h, 0)); return 0; }
+static int deliver_words(EngineImpl* im, const int32_t* d_src, int32_t* h_dst, size_t words, hipEvent_t after, hipEvent_t copy_begin = nullptr) {
+    if (on_copy_stream(words)) {
+        HIP_TRY(hipStreamWaitEvent(im->s_copy, after, 0));
+        if (copy_begin) HIP_TRY(hipEventRecord(copy_begin, im->s_copy));
+        HIP_TRY(hipMemcpyAsync(h_dst, d_src, words * sizeof(int32_t), hipMemcpyDeviceToHost, im->s_copy));
+    } else if (words) {
+        int32_t* alias = nullptr;
+        if (int rc = host_alias(im, h_dst, &alias)) return rc;
+        hipLaunchKernelGGL(k_copy_words, dim3(copy_grid(words)), dim3(256), 0, im->s_comp, d_src, alias, words);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
 // shard slices of (key, value) pairs -> contiguous arrays, one launch (the shard count would be that many copy commands)
 template <class K>
 __global__ void __launch_bounds__(256) k_pack_pairs(const K* __restrict__ sk, const uint64_t* __restrict__ sv, unsigned long long cap, ShardSpan sp,
@@ -863,7 +885,16 @@ static int sort_run(EngineImpl* im, void* tmp, size_t tmp_bytes, K* kin, K* kout
     return 0;
 }
 
-static int copy_out(EngineImpl* im, int m, int32_t* d_o, size_t total);
+// hand matrix m ([row|col|val] at d_o) to the host
+static int copy_out(EngineImpl* im, int m, int32_t* d_o, size_t total) {
+    im->d_res[m] = d_o;
+    // a copy on the copy stream waits for the scatter (ev_res) and is timed from the first of a finish (ev_c0) to the last (ev_c1); xck_finish_async() does not wait for it
+    const bool big = on_copy_stream(total * 3);
+    if (big) HIP_TRY(hipEventRecord(im->ev_res, im->s_comp));
+    if (int rc = deliver_words(im, d_o, im->h_res[m], total * 3, im->ev_res, im->copy_timed ? nullptr : im->ev_c0)) return rc;
+    if (big) { im->copy_timed = true; HIP_TRY(hipEventRecord(im->ev_c1, im->s_copy)); }
+    return 0;
+}
 
 // ordered compaction of the runs' AD / DP / OTH (hap: per-run sums, n staging entries) into the COO blocks of matrices m0..m0+2:
 // counts and scans of all three first, ONE read-back of the totals, then the scatter and the copy-out
@@ -899,35 +930,13 @@ static int compact_coo(EngineImpl* im, Arena& ws, const HapSrc& hap, const K* ke
     for (int y = 0; y < nm; y++) {
         const size_t total = out.total[y];
         if (!total) continue;
-        if (total * 3 * sizeof(int32_t) >= (size_t(8) << 20)) { int rc = copy_out(im, m0 + y, out.o[y], total); if (rc) return rc; continue; }
+        if (on_copy_stream(total * 3)) { int rc = copy_out(im, m0 + y, out.o[y], total); if (rc) return rc; continue; }
         im->d_res[m0 + y] = out.o[y];
-        int32_t* alias = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void**)&alias, im->h_res[m0 + y], 0));
-        sg.src[y] = out.o[y]; sg.dst[y] = alias; sg.n[y] = total * 3; mx = std::max(mx, total * 3);
+        if (int rc = host_alias(im, im->h_res[m0 + y], &sg.dst[y])) return rc;
+        sg.src[y] = out.o[y]; sg.n[y] = total * 3; mx = std::max(mx, total * 3);
     }
     if (mx) {
-        hipLaunchKernelGGL(k_copy_words3, dim3((unsigned)std::min<size_t>((mx + 255) / 256, 1024), nm), dim3(256), 0, im->s_comp, sg);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-// hand matrix m ([row|col|val] at d_o) to the host
-static int copy_out(EngineImpl* im, int m, int32_t* d_o, size_t total) {
-    im->d_res[m] = d_o;
-    // copy-out on the copy stream, ordered behind the scatter: the compute stream (and other engines) keep
-    // the CUs busy while the matrix crosses PCIe; xck_finish() waits for it, xck_finish_async() does not
-    if (total * 3 * sizeof(int32_t) >= (size_t(8) << 20)) {
-        HIP_TRY(hipEventRecord(im->ev_res, im->s_comp));
-        HIP_TRY(hipStreamWaitEvent(im->s_copy, im->ev_res, 0));
-        if (!im->copy_timed) { HIP_TRY(hipEventRecord(im->ev_c0, im->s_copy)); im->copy_timed = true; }
-        HIP_TRY(hipMemcpyAsync(im->h_res[m], d_o, total * 3 * sizeof(int32_t), hipMemcpyDeviceToHost, im->s_copy));
-        HIP_TRY(hipEventRecord(im->ev_c1, im->s_copy));
-    } else {                                                  // small matrix: CUs store it straight into mapped pinned memory
-        int32_t* alias = nullptr;                             // (no DMA queue shared with another engine's bulk copy)
-        HIP_TRY(hipHostGetDevicePointer((void**)&alias, im->h_res[m], 0));
-        const unsigned g = (unsigned)std::min<size_t>((total * 3 + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_copy_words, dim3(g), dim3(256), 0, im->s_comp, (const int32_t*)d_o, alias, total * 3);
+        hipLaunchKernelGGL(k_copy_words3, dim3(copy_grid(mx), nm), dim3(256), 0, im->s_comp, sg);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -1462,6 +1471,7 @@ int snp_verdicts(EngineImpl* im, uint32_t* d_kept) {
     return 0;
 }
 
+#include "coo_call.h"
 #include "refold.h"
 #include "snp_counts.h"
 #include "group_counts.h"

@@ -1,6 +1,7 @@
 // group_counts.h - xck_group_counts (include/xck.h): the row x group sums of matrices the handle already holds in HBM - the result
-// blocks of the last xck_finish / xck_refold (EngineImpl::d_res) or the SNP x cell blocks of the last xck_snp_counts (d_sc_res) - under a
-// cell -> group mapping given with the call.  Included by finish.hip inside namespace xck, behind snp_counts.h (pf_scan, k_copy_words).
+// blocks of the last xck_finish / xck_refold (EngineImpl::d_res) or the SNP x cell blocks of the last xck_snp_counts (sc.d_res) - under a
+// cell -> group mapping given with the call.  Included by finish.hip inside namespace xck, behind fold_partition.h (pf_scan), snp_counts.h
+// and coo_call.h: the host steps around the kernels below (scratch layout, totals and overflow flag, result buffers, copy-out, times) are that file's.
 //
 // A source matrix is [row | col | val], sorted by (row, col).  Inside a row the groups arrive in cell order, not in group order, so the
 // output order is made here: every row is summed per group and its non-zero groups leave in ascending order.
@@ -20,7 +21,7 @@
 // the wave path sums in 64 bits, the block path checks every LDS add against the value it replaced (values are positive, so the first
 // add that crosses 2^31 - 1 sees it before the 32-bit word can wrap) - XCK_E_CAPACITY.
 //
-// Memory: buffers of the call's own (EngineImpl::d_gc, d_gc_res, h_gc_res, h_gc_tot; grow-only, freed at destroy).  Traffic per source
+// Memory: buffers of the call's own (the CooCall EngineImpl::gc; grow-only, freed at destroy).  Traffic per source
 // entry: the column and the value twice (count pass, emit pass), the row array only along the bisections, one gathered word of the
 // mapping per pass: 16 bytes + 2 gathers; 12 bytes per output entry; 12 bytes of scratch per source row and matrix.
 #pragma once
@@ -139,91 +140,53 @@ __global__ __launch_bounds__(GC_BLOCK) void k_grp_long(GcArgs A) {
     }
 }
 
-__global__ void k_grp_totals(const uint32_t* __restrict__ tot, const uint32_t* __restrict__ ctl, unsigned long long* __restrict__ host_alias) {
-    if (threadIdx.x < 3) host_alias[threadIdx.x] = tot[threadIdx.x];
-    if (threadIdx.x == 3) host_alias[3] = ctl[3];
-}
-
-// the kernels of one call on the compute stream, with ONE host synchronise (the totals of all matrices, which size the result block)
+// the kernels of one call on the compute stream, between the shared steps of coo_call.h
 static int group_counts_run(EngineImpl* im, const int32_t* const* src, const size_t* nnz, int nm, size_t n_rows, int n_groups, const int32_t* cell_group,
-                            std::chrono::steady_clock::time_point t0, GroupTimes* gt) {
-    if (!im->h_gc_tot) {                                                  // the totals and the overflow flag reach the host through mapped pinned words of the call's own
-        HIP_TRY(hipHostMalloc((void**)&im->h_gc_tot, 4 * sizeof(unsigned long long), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void**)&im->d_gc_tot_alias, im->h_gc_tot, 0));
-    }
-    for (auto& ev : im->ev_g) if (!ev) HIP_TRY(hipEventCreate(&ev));
-    // scratch: one block; the control words (zero at the start) first, then the mapping, the scans' block sums and totals, the per-row arrays
+                            std::chrono::steady_clock::time_point t0) {
+    CooCall& c = im->gc;
+    // scratch: the control words (zero at the start) first, then the mapping, the scans' block sums and totals, the per-row arrays
     const size_t n_bsum = pf_scan_words(n_rows);
-    struct Piece { size_t bytes, off; } pc[4] = { { 4 * 4, 0 }, { (size_t)im->n_cells * 4, 0 }, { (n_bsum + 4) * 4, 0 }, { 3 * (3 * n_rows + 1) * 4, 0 } };
-    size_t total_b = 0;
-    for (auto& p : pc) { p.off = total_b; total_b += (p.bytes + 255) & ~size_t(255); }
-    if (int rc = grow_device(im, (void**)&im->d_gc, &im->gc_cap, total_b, total_b / 8 + 4096)) return rc;
-    char* d = im->d_gc;
+    ScratchLayout L;
+    const int i_ctl = L.add(4 * 4), i_cg = L.add((size_t)im->n_cells * 4), i_bsum = L.add((n_bsum + 4) * 4), i_rows = L.add(3 * (3 * n_rows + 1) * 4);
+    if (int rc = coo_scratch(im, c, L)) return rc;
+    char* d = c.d_scratch;
     GcArgs A; memset(&A, 0, sizeof A);
-    A.ctl = (uint32_t*)(d + pc[0].off);
-    int32_t* d_cg = (int32_t*)(d + pc[1].off); A.cg = d_cg;
-    uint32_t* bsum = (uint32_t*)(d + pc[2].off); uint32_t* d_tot = bsum + n_bsum;
-    { uint32_t* w = (uint32_t*)(d + pc[3].off);
+    A.ctl = L.at<uint32_t>(d, i_ctl);
+    int32_t* d_cg = L.at<int32_t>(d, i_cg); A.cg = d_cg;
+    uint32_t* bsum = L.at<uint32_t>(d, i_bsum); uint32_t* d_tot = bsum + n_bsum;
+    { uint32_t* w = L.at<uint32_t>(d, i_rows);
       for (int y = 0; y < nm; y++) { A.m[y].src = src[y]; A.m[y].nnz = (uint32_t)nnz[y]; A.m[y].ptr = w; A.m[y].cnt = w + n_rows + 1; A.m[y].list = w + 2 * n_rows + 1; w += 3 * n_rows + 1; } }
     A.n_rows = (uint32_t)n_rows; A.n_cells = (uint32_t)im->n_cells; A.n_groups = n_groups; A.long_row = (uint32_t)im->eng->knobs.group_long_row;
     const dim3 g_ptr((unsigned)((n_rows + 1 + GC_BLOCK - 1) / GC_BLOCK), nm), g_short((unsigned)((n_rows + GC_WAVES - 1) / GC_WAVES), nm), g_long(GC_LONG_GRID, nm);
-    HIP_TRY(hipEventRecord(im->ev_g[0], im->s_comp));
+    HIP_TRY(hipEventRecord(c.ev[0], im->s_comp));
     HIP_TRY(hipMemsetAsync(A.ctl, 0, 4 * 4, im->s_comp));
     HIP_TRY(hipMemsetAsync(d_tot, 0, 4 * 4, im->s_comp));
     HIP_TRY(hipMemcpyAsync(d_cg, cell_group, (size_t)im->n_cells * 4, hipMemcpyHostToDevice, im->s_comp));
     hipLaunchKernelGGL(k_grp_row_ptr, g_ptr, dim3(GC_BLOCK), 0, im->s_comp, A);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(im->ev_g[1], im->s_comp));
+    HIP_TRY(hipEventRecord(c.ev[1], im->s_comp));
     hipLaunchKernelGGL(k_grp_short<false>, g_short, dim3(GC_BLOCK), 0, im->s_comp, A);
     hipLaunchKernelGGL(k_grp_long<false>, g_long, dim3(GC_BLOCK), 0, im->s_comp, A);
     HIP_TRY(hipGetLastError());
     for (int y = 0; y < nm; y++) if (int rc = pf_scan(im, A.m[y].cnt, n_rows, bsum, d_tot + y)) return rc;
-    hipLaunchKernelGGL(k_grp_totals, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)d_tot, (const uint32_t*)A.ctl, im->d_gc_tot_alias);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(im->ev_g[2], im->s_comp));
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    if (im->h_gc_tot[3]) { im->eng->err = "xck_group_counts: the sum of a group does not fit int32"; return XCK_E_CAPACITY; }
-    size_t words = 0;
-    for (int y = 0; y < nm; y++) { A.m[y].total = (uint32_t)im->h_gc_tot[y]; words += 3 * (size_t)A.m[y].total; }
-    if (int rc = grow_device(im, (void**)&im->d_gc_res, &im->gc_res_cap, std::max<size_t>(words, 1) * 4, words + 4096)) return rc;
-    if (int rc = grow_pinned(im, (void**)&im->h_gc_res, &im->h_gc_res_cap, std::max<size_t>(words, 1) * 4, words + 4096)) return rc;
-    { size_t at = 0; for (int y = 0; y < nm; y++) { A.m[y].out = im->d_gc_res + at; at += 3 * (size_t)A.m[y].total; } }
-    HIP_TRY(hipEventRecord(im->ev_g[3], im->s_comp));
-    if (words) {
+    if (int rc = coo_publish_totals(im, c, d_tot, nm, A.ctl + 3)) return rc;
+    if (c.h_tot[COO_FLAG_WORD]) { im->eng->err = "xck_group_counts: the sum of a group does not fit int32"; return XCK_E_CAPACITY; }
+    int32_t* d_out[3];
+    if (int rc = coo_reserve(im, c, d_out)) return rc;
+    for (int y = 0; y < nm; y++) { A.m[y].total = (uint32_t)c.nnz[y]; A.m[y].out = d_out[y]; }
+    if (coo_words(c)) {
         hipLaunchKernelGGL(k_grp_short<true>, g_short, dim3(GC_BLOCK), 0, im->s_comp, A);
         hipLaunchKernelGGL(k_grp_long<true>, g_long, dim3(GC_BLOCK), 0, im->s_comp, A);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(im->ev_g[4], im->s_comp));
-    const bool big = words * 4 >= (size_t(8) << 20);                      // a large block crosses PCIe on the copy stream, as snp_counts.h sends its own
-    if (big) {
-        HIP_TRY(hipStreamWaitEvent(im->s_copy, im->ev_g[4], 0));
-        HIP_TRY(hipMemcpyAsync(im->h_gc_res, im->d_gc_res, words * 4, hipMemcpyDeviceToHost, im->s_copy));
-    } else if (words) {                                                     // small: the CUs store it into mapped pinned memory
-        int32_t* alias = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void**)&alias, im->h_gc_res, 0));
-        hipLaunchKernelGGL(k_copy_words, dim3((unsigned)std::min<size_t>((words + 255) / 256, 1024)), dim3(256), 0, im->s_comp, (const int32_t*)im->d_gc_res, alias, words);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    gt->ms_total += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (big) {
-        const auto t1 = std::chrono::steady_clock::now();
-        HIP_TRY(hipStreamSynchronize(im->s_copy));
-        gt->ms_copy += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    }
-    float ms[3] = {0, 0, 0};
-    HIP_TRY(hipEventElapsedTime(&ms[0], im->ev_g[0], im->ev_g[1])); HIP_TRY(hipEventElapsedTime(&ms[1], im->ev_g[1], im->ev_g[2]));
-    HIP_TRY(hipEventElapsedTime(&ms[2], im->ev_g[3], im->ev_g[4]));
-    gt->ms_ptr += ms[0]; gt->ms_count += ms[1]; gt->ms_emit += ms[2];
-    for (int y = 0; y < nm; y++) im->gc_nnz[y] = (size_t)A.m[y].total;
-    return 0;
+    return coo_deliver(im, c, t0);
 }
 
 // One pipeline's share of xck_group_counts: a basefc pipeline fills out->count, a pileup pipeline out->ad / dp / oth; the rest of *out is
-// left alone (api.cpp clears it and merges the pipelines of a fused handle).  The arguments were checked there.
+// left alone (api.cpp clears it and merges the pipelines of a fused handle, and adds up their times in *gt).  The arguments were checked there.
 int engine_group_counts(EngineImpl* im, int source, int n_groups, const int32_t* cell_group, xck_result* out, GroupTimes* gt) {
     xck_engine* e = im->eng;
+    CooCall& c = im->gc;
     if (im->fold_failed || !im->finished) { e->err = "xck_group_counts: valid between a successful xck_finish and the next xck_reset"; return XCK_E_STATE; }
     const bool snp = source == XCK_GROUP_SRC_SNP;
     if (snp && !im->sc_valid) { e->err = "xck_group_counts: source SNP needs an xck_snp_counts since the last xck_finish / xck_reset"; return XCK_E_STATE; }
@@ -231,11 +194,11 @@ int engine_group_counts(EngineImpl* im, int source, int n_groups, const int32_t*
     const int nm = baf ? 3 : 1;
     const int32_t* src[3] = {nullptr, nullptr, nullptr}; size_t nnz[3] = {0, 0, 0}, any = 0;
     for (int y = 0; y < nm; y++) {
-        nnz[y] = snp ? im->sc_nnz[y] : im->res_nnz[(baf ? 1 : 0) + y];
+        nnz[y] = snp ? im->sc.nnz[y] : im->res_nnz[(baf ? 1 : 0) + y];
         if (nnz[y] >> 32) { e->err = "xck_group_counts: a source matrix holds 2^32 entries or more: the row pointers are 32-bit"; return XCK_E_CAPACITY; }
         any += nnz[y];
     }
-    if (snp) { size_t at = 0; for (int y = 0; y < 3; y++) { src[y] = im->d_sc_res + at; at += 3 * nnz[y]; } }
+    if (snp) { size_t at = 0; for (int y = 0; y < 3; y++) { src[y] = im->sc.d_res + at; at += 3 * nnz[y]; } }
     else for (int y = 0; y < nm; y++) {
         src[y] = im->d_res[(baf ? 1 : 0) + y];
         if (nnz[y] && !src[y]) { e->err = "internal: result block without a device copy"; return XCK_E_STATE; }
@@ -244,21 +207,13 @@ int engine_group_counts(EngineImpl* im, int source, int n_groups, const int32_t*
     HIP_TRY(hipSetDevice(im->device));
     const auto t0 = std::chrono::steady_clock::now();
     clear_stale_error("group_counts", e->knobs.debug_timing);
-    for (auto& z : im->gc_nnz) z = 0;
+    if (int rc = coo_begin(im, c)) return rc;
     if (any && n_rows)
-        if (int rc = group_counts_run(im, src, nnz, nm, n_rows, n_groups, cell_group, t0, gt)) {
-            hipStreamSynchronize(im->s_comp); hipStreamSynchronize(im->s_copy);                             // nothing of the handle was overwritten: it is not marked failed
-            return rc;
-        }
+        if (int rc = group_counts_run(im, src, nnz, nm, n_rows, n_groups, cell_group, t0)) return coo_fail(im, rc);
+    gt->ms_total += c.ms_total; gt->ms_ptr += c.ms_phase[0]; gt->ms_count += c.ms_phase[1]; gt->ms_emit += c.ms_phase[2]; gt->ms_copy += c.ms_copy;
     gt->entries += (long long)any;
-    xck_coo* dst[3] = { baf ? &out->ad : &out->count, &out->dp, &out->oth };
-    size_t at = 0;
-    for (int y = 0; y < nm; y++) {
-        const size_t z = im->gc_nnz[y];
-        dst[y]->nnz = (int64_t)z;
-        if (z) { dst[y]->row = im->h_gc_res + at; dst[y]->col = im->h_gc_res + at + z; dst[y]->val = im->h_gc_res + at + 2 * z; }
-        gt->nnz[(baf ? 1 : 0) + y] = (long long)z;
-        at += 3 * z;
-    }
+    xck_coo* const dst[3] = { baf ? &out->ad : &out->count, &out->dp, &out->oth };
+    coo_fill(c, nm, dst);
+    for (int y = 0; y < nm; y++) gt->nnz[(baf ? 1 : 0) + y] = (long long)c.nnz[y];
     return 0;
 }

@@ -1,6 +1,7 @@
 // refold.h - xck_refold (include/xck.h): the region stage of the pileup fold again, under new regions, REF / ALT, haplotype indices,
 // exclusion pairs and per-SNP filters, on the molecule stage the last xck_finish left (finish.hip fold_molecules / fold_regions).
-// Included by finish.hip inside namespace xck, behind fold_partition.h: it uses that file's device-wide scan (pf_scan).
+// Included by finish.hip inside namespace xck, behind fold_partition.h and coo_call.h: it uses the device-wide scan of the first (pf_scan)
+// and lays out its upload block with the ScratchLayout of the second.
 //
 // The SNP -> region tables (d_csr_off / d_csr_reg) are built on the device.  The host handles only tables of at most n_regions
 // entries: it validates the regions, sorts them per contig by (start, end, index) with the running maximum of the ends
@@ -138,28 +139,29 @@ static int refold_build_tables(EngineImpl* im, const xck_refold_config* cfg, boo
     RefoldHost h;
     refold_host_tables(im, cfg, h);
     const size_t ns = (size_t)im->n_snps_sorted, nsb = (ns + 1 + SC_TILE - 1) / SC_TILE;
-    struct Piece { const void* src; size_t bytes, off; } pc[10] = {
-        { h.start.data(), h.start.size() * 4, 0 }, { h.end.data(), h.end.size() * 4, 0 }, { h.row.data(), h.row.size() * 4, 0 }, { h.pmax.data(), h.pmax.size() * 4, 0 },
-        { h.ct_snp_end.data(), h.ct_snp_end.size() * 4, 0 }, { h.ct_reg_base.data(), h.ct_reg_base.size() * 4, 0 }, { h.ct_reg_n.data(), h.ct_reg_n.size() * 4, 0 },
-        { h.excl.data(), h.excl.size() * 8, 0 }, { h.enabled.data(), h.enabled.size(), 0 }, { nullptr, nsb * 4, 0 } };        // (the last: the scan's block sums)
-    size_t total_b = 0;
-    for (auto& p : pc) { p.off = total_b; total_b += (std::max<size_t>(p.bytes, 4) + 255) & ~size_t(255); }
-    if (int rc = refold_grow(im, (void**)&im->d_rf, &im->rf_cap, total_b)) return rc;
+    const struct { const void* src; size_t bytes; } up[9] = {
+        { h.start.data(), h.start.size() * 4 }, { h.end.data(), h.end.size() * 4 }, { h.row.data(), h.row.size() * 4 }, { h.pmax.data(), h.pmax.size() * 4 },
+        { h.ct_snp_end.data(), h.ct_snp_end.size() * 4 }, { h.ct_reg_base.data(), h.ct_reg_base.size() * 4 }, { h.ct_reg_n.data(), h.ct_reg_n.size() * 4 },
+        { h.excl.data(), h.excl.size() * 8 }, { h.enabled.data(), h.enabled.size() } };
+    ScratchLayout L;                                                      // (coo_call.h) the uploaded tables - an empty one still takes four bytes -, then the scan's block sums
+    for (const auto& u : up) L.add(std::max<size_t>(u.bytes, 4));
+    const int i_bsum = L.add(nsb * 4);
+    if (int rc = refold_grow(im, (void**)&im->d_rf, &im->rf_cap, L.total())) return rc;
     if (!im->d_csr_alt) HIP_TRY(hipMalloc((void**)&im->d_csr_alt, (ns + 1) * sizeof(int32_t)));
     if (!im->ev_r0) { HIP_TRY(hipEventCreate(&im->ev_r0)); HIP_TRY(hipEventCreate(&im->ev_r1)); HIP_TRY(hipEventCreate(&im->ev_r2)); HIP_TRY(hipEventCreate(&im->ev_r3)); }
-    { std::vector<char> blk(pc[9].off);
-      for (int q = 0; q < 9; q++) if (pc[q].bytes) memcpy(blk.data() + pc[q].off, pc[q].src, pc[q].bytes);
+    { std::vector<char> blk(L.offs[i_bsum]);
+      for (int q = 0; q < 9; q++) if (up[q].bytes) memcpy(blk.data() + L.offs[q], up[q].src, up[q].bytes);
       if (!blk.empty()) HIP_TRY(hipMemcpyAsync(im->d_rf, blk.data(), blk.size(), hipMemcpyHostToDevice, im->s_comp));
       HIP_TRY(hipStreamSynchronize(im->s_comp)); }
     im->rf_ms_upload = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     RefoldTabs t;
-    t.snp_p0 = im->d_snp_p0; t.enabled = cfg->snp_enabled ? (const uint8_t*)(im->d_rf + pc[8].off) : nullptr;
-    t.ct_snp_end = (const int32_t*)(im->d_rf + pc[4].off); t.ct_reg_base = (const int32_t*)(im->d_rf + pc[5].off); t.ct_reg_n = (const int32_t*)(im->d_rf + pc[6].off);
+    t.snp_p0 = im->d_snp_p0; t.enabled = cfg->snp_enabled ? L.at<const uint8_t>(im->d_rf, 8) : nullptr;
+    t.ct_snp_end = L.at<const int32_t>(im->d_rf, 4); t.ct_reg_base = L.at<const int32_t>(im->d_rf, 5); t.ct_reg_n = L.at<const int32_t>(im->d_rf, 6);
     t.n_ct = (int32_t)h.ct_snp_end.size();
-    t.start = (const int32_t*)(im->d_rf + pc[0].off); t.end = (const int32_t*)(im->d_rf + pc[1].off); t.row = (const int32_t*)(im->d_rf + pc[2].off); t.pmax = (const int32_t*)(im->d_rf + pc[3].off);
-    t.excl = (const unsigned long long*)(im->d_rf + pc[7].off); t.n_excl = (int32_t)h.excl.size();
+    t.start = L.at<const int32_t>(im->d_rf, 0); t.end = L.at<const int32_t>(im->d_rf, 1); t.row = L.at<const int32_t>(im->d_rf, 2); t.pmax = L.at<const int32_t>(im->d_rf, 3);
+    t.excl = L.at<const unsigned long long>(im->d_rf, 7); t.n_excl = (int32_t)h.excl.size();
     t.n_snps = (uint32_t)ns;
-    uint32_t* bsum = (uint32_t*)(im->d_rf + pc[9].off);
+    uint32_t* bsum = L.at<uint32_t>(im->d_rf, i_bsum);
     const unsigned grid = (unsigned)((ns + 1 + RF_BLOCK - 1) / RF_BLOCK);
     HIP_TRY(hipEventRecord(im->ev_r0, im->s_comp));
     HIP_TRY(hipMemsetAsync(im->d_ctl + CTL_SCRATCH, 0, sizeof(unsigned long long), im->s_comp));

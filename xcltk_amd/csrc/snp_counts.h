@@ -1,7 +1,7 @@
 // snp_counts.h - xck_snp_counts (include/xck.h): the SNP x cell AD / DP / OTH matrices of a finished pileup, counted straight from what
 // the molecule stage of the last xck_finish left (finish.hip fold_molecules): the hits sorted by (SNP, cell, UMI) and, at the head of
 // every molecule, the base its first read shows (EngineImpl::mol_keys / mol_al / mol_n).  Included by finish.hip inside namespace xck,
-// behind fold_partition.h (pf_scan) and refold.h.
+// behind fold_partition.h (pf_scan), refold.h and coo_call.h: the host steps around the kernels below (scratch layout, totals, result buffers, copy-out, times) are that file's.
 //
 // Per (SNP, cell) run of the stream: AD = molecules that show the SNP's ALT, DP = those that show REF or ALT, OTH = those that show
 // another base (allele_side(), the rule k_expand uses); molecules claimed by a gap record (al == 0) count nowhere.  No region table,
@@ -18,7 +18,7 @@
 //                 order with every SNP's entries contiguous and in cell order, so the output is sorted by (caller row, cell) without
 //                 a sort and without a counter per row.
 //
-// Memory: buffers of the call's own (EngineImpl::d_sc, d_sc_res, h_sc_res, d_sc_perm, h_sc_tot; grow-only, freed at destroy) - nothing from
+// Memory: buffers of the call's own (the CooCall EngineImpl::sc, and d_sc_perm; grow-only, freed at destroy) - nothing from
 // workspace 1, workspace 2 or the shard slices, so the call invalidates nothing xck_finish / xck_refold / xck_get_result_device
 // handed out.  Scratch: 13 bytes per entry of the stream (flag byte, three 32-bit sums) + 8 bytes per RUN_WALK entries (long runs)
 // + 12 bytes per tile + 24 bytes per SNP of the sorted table + 12 bytes per SNP of the caller's list.
@@ -165,10 +165,6 @@ __global__ __launch_bounds__(256) void k_snc_row_counts(const int32_t* __restric
     for (int y = 0; y < 3; y++) B.cc[y * B.stride + c] = B.p1[y * B.ns + s] - B.p0[y * B.ns + s];
 }
 
-__global__ void k_snc_totals(const uint32_t* __restrict__ tot, unsigned long long* __restrict__ host_alias) {
-    if (threadIdx.x < 3) host_alias[threadIdx.x] = tot[threadIdx.x];
-}
-
 template <class K>
 __global__ __launch_bounds__(SNC_BLOCK) void k_snc_emit(const K* __restrict__ k, KeyLayout<K> kl, const int32_t* __restrict__ perm, SncBufs B, CooOut3 out) {
     __shared__ unsigned long long s_w[SNC_BLOCK / 64];
@@ -195,116 +191,71 @@ __global__ __launch_bounds__(SNC_BLOCK) void k_snc_emit(const K* __restrict__ k,
     }
 }
 
-// the kernels of one call on the compute stream, with ONE host synchronise (the three totals, which size the result block)
+// the kernels of one call on the compute stream, between the shared steps of coo_call.h
 template <class K>
 static int snp_counts_run(EngineImpl* im, std::chrono::steady_clock::time_point t0) {
+    CooCall& c = im->sc;
     KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
     const K* keys = (const K*)im->mol_keys;
     const size_t n = im->mol_n, ns = (size_t)im->n_snps_sorted, nt = (n + SNC_TILE - 1) / SNC_TILE, stride = ((size_t)im->n_snps_in + 1 + 63) & ~size_t(63);
     if (n >> 32) { im->eng->err = "xck_snp_counts: the sorted stream holds 2^32 hits or more: its 32-bit prefix counts do not reach that far"; return XCK_E_CAPACITY; }
-    if (!im->h_sc_tot) {                                                  // the three totals reach the host through mapped pinned words of the call's own
-        HIP_TRY(hipHostMalloc((void**)&im->h_sc_tot, 4 * sizeof(unsigned long long), hipHostMallocMapped));
-        HIP_TRY(hipHostGetDevicePointer((void**)&im->d_sc_tot_alias, im->h_sc_tot, 0));
-    }
     if (!im->d_sc_perm) {                                                 // sorted SNP -> the caller's index: fixed at xck_create
         int32_t* p = nullptr;
         HIP_TRY(hipMalloc((void**)&p, ns * sizeof(int32_t)));
         if (hipMemcpy(p, im->snp_perm.data(), ns * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) { hipFree(p); im->eng->err = "xck_snp_counts: upload of the SNP order failed"; return XCK_E_DEVICE; }
         im->d_sc_perm = p;
     }
-    for (auto& ev : im->ev_s) if (!ev) HIP_TRY(hipEventCreate(&ev));
-    // scratch: one block; the pieces that start as zero come first (p0, p1, cc, the count word of the long-run list)
+    // scratch: the pieces that start as zero come first (p0, p1, cc, the count word of the long-run list)
     const size_t n_bsum = (std::max(nt, stride) + SC_TILE - 1) / SC_TILE + 8;
-    struct Piece { size_t bytes, off; } pc[8] = {
-        { 3 * ns * 4, 0 }, { 3 * ns * 4, 0 }, { 3 * stride * 4, 0 }, { (n / (size_t)RUN_WALK + 3) * 8, 0 },   // p0; p1; cc; long_runs
-        { n + 8, 0 }, { 3 * n * 4, 0 }, { 3 * nt * 4, 0 }, { (n_bsum + 4) * 4, 0 } };                          // f; sums; tcnt; the scans' block sums + the three totals
-    size_t total_b = 0;
-    for (auto& p : pc) { p.off = total_b; total_b += (p.bytes + 255) & ~size_t(255); }
-    if (int rc = grow_device(im, (void**)&im->d_sc, &im->sc_cap, total_b, total_b / 8 + 4096)) return rc;
-    char* d = im->d_sc;
+    ScratchLayout L;
+    const int i_p0 = L.add(3 * ns * 4), i_p1 = L.add(3 * ns * 4), i_cc = L.add(3 * stride * 4), i_long = L.add((n / (size_t)RUN_WALK + 3) * 8);
+    const int i_f = L.add(n + 8), i_sums = L.add(3 * n * 4), i_tcnt = L.add(3 * nt * 4), i_bsum = L.add((n_bsum + 4) * 4);   // (the last: the scans' block sums + the three totals)
+    if (int rc = coo_scratch(im, c, L)) return rc;
+    char* d = c.d_scratch;
     SncBufs B;
-    B.p0 = (uint32_t*)(d + pc[0].off); B.p1 = (uint32_t*)(d + pc[1].off); B.cc = (uint32_t*)(d + pc[2].off); B.long_runs = (unsigned long long*)(d + pc[3].off);
-    B.f = (uint8_t*)(d + pc[4].off); B.sums = (uint32_t*)(d + pc[5].off); B.tcnt = (uint32_t*)(d + pc[6].off);
-    uint32_t* bsum = (uint32_t*)(d + pc[7].off); uint32_t* d_tot = bsum + n_bsum;
+    B.p0 = L.at<uint32_t>(d, i_p0); B.p1 = L.at<uint32_t>(d, i_p1); B.cc = L.at<uint32_t>(d, i_cc); B.long_runs = L.at<unsigned long long>(d, i_long);
+    B.f = L.at<uint8_t>(d, i_f); B.sums = L.at<uint32_t>(d, i_sums); B.tcnt = L.at<uint32_t>(d, i_tcnt);
+    uint32_t* bsum = L.at<uint32_t>(d, i_bsum); uint32_t* d_tot = bsum + n_bsum;
     B.n = (long long)n; B.nt = (long long)nt; B.ns = (long long)ns; B.stride = (long long)stride;
-    HIP_TRY(hipEventRecord(im->ev_s[0], im->s_comp));
-    HIP_TRY(hipMemsetAsync(d, 0, pc[3].off + 8, im->s_comp));
+    HIP_TRY(hipEventRecord(c.ev[0], im->s_comp));
+    HIP_TRY(hipMemsetAsync(d, 0, L.offs[i_long] + 8, im->s_comp));
     hipLaunchKernelGGL((k_snc_heads<K>), dim3((unsigned)nt), dim3(SNC_BLOCK), 0, im->s_comp, keys, (const uint8_t*)im->mol_al, kl, (const uint32_t*)im->d_snp_info, B);
     hipLaunchKernelGGL((k_snc_long<K>), dim3(256), dim3(256), 0, im->s_comp, keys, (const uint8_t*)im->mol_al, kl, (const uint32_t*)im->d_snp_info, B);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(im->ev_s[1], im->s_comp));
+    HIP_TRY(hipEventRecord(c.ev[1], im->s_comp));
     for (int y = 0; y < 3; y++) if (int rc = pf_scan(im, B.tcnt + (size_t)y * nt, nt, bsum, nullptr)) return rc;
     hipLaunchKernelGGL((k_snc_rows<K>), dim3((unsigned)nt), dim3(SNC_BLOCK), 0, im->s_comp, keys, kl, B);
     hipLaunchKernelGGL(k_snc_row_counts, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, im->s_comp, (const int32_t*)im->d_sc_perm, B);
     HIP_TRY(hipGetLastError());
     for (int y = 0; y < 3; y++) if (int rc = pf_scan(im, B.cc + (size_t)y * stride, (size_t)im->n_snps_in + 1, bsum, d_tot + y)) return rc;
-    hipLaunchKernelGGL(k_snc_totals, dim3(1), dim3(64), 0, im->s_comp, (const uint32_t*)d_tot, im->d_sc_tot_alias);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(im->ev_s[2], im->s_comp));
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
+    if (int rc = coo_publish_totals(im, c, d_tot, 3, nullptr)) return rc;
     CooOut3 out; memset(&out, 0, sizeof out);
-    size_t words = 0;
-    for (int y = 0; y < 3; y++) { out.total[y] = im->h_sc_tot[y]; words += 3 * (size_t)out.total[y]; }
-    if (int rc = grow_device(im, (void**)&im->d_sc_res, &im->sc_res_cap, std::max<size_t>(words, 1) * 4, words + 4096)) return rc;
-    if (int rc = grow_pinned(im, (void**)&im->h_sc_res, &im->h_sc_res_cap, std::max<size_t>(words, 1) * 4, words + 4096)) return rc;
-    { size_t at = 0; for (int y = 0; y < 3; y++) { out.o[y] = im->d_sc_res + at; at += 3 * (size_t)out.total[y]; } }
-    HIP_TRY(hipEventRecord(im->ev_s[3], im->s_comp));
-    if (words) {
+    for (int y = 0; y < 3; y++) out.total[y] = c.nnz[y];
+    if (int rc = coo_reserve(im, c, out.o)) return rc;
+    if (coo_words(c)) {
         hipLaunchKernelGGL((k_snc_emit<K>), dim3((unsigned)nt), dim3(SNC_BLOCK), 0, im->s_comp, keys, kl, (const int32_t*)im->d_sc_perm, B, out);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(im->ev_s[4], im->s_comp));
-    const bool big = words * 4 >= (size_t(8) << 20);                      // a large block crosses PCIe on the copy stream, as copy_out() sends the fold's
-    if (big) {
-        HIP_TRY(hipStreamWaitEvent(im->s_copy, im->ev_s[4], 0));
-        HIP_TRY(hipMemcpyAsync(im->h_sc_res, im->d_sc_res, words * 4, hipMemcpyDeviceToHost, im->s_copy));
-    } else if (words) {                                                     // small: the CUs store it into mapped pinned memory (copy_out())
-        int32_t* alias = nullptr;
-        HIP_TRY(hipHostGetDevicePointer((void**)&alias, im->h_sc_res, 0));
-        hipLaunchKernelGGL(k_copy_words, dim3((unsigned)std::min<size_t>((words + 255) / 256, 1024)), dim3(256), 0, im->s_comp, (const int32_t*)im->d_sc_res, alias, words);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    im->sc_ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (big) {                                                            // (the wait xck_refold spends in result_host())
-        const auto t1 = std::chrono::steady_clock::now();
-        HIP_TRY(hipStreamSynchronize(im->s_copy));
-        im->sc_ms_copy = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
-    }
-    for (int y = 0; y < 3; y++) im->sc_nnz[y] = (size_t)out.total[y];
-    float ms[3] = {0, 0, 0};
-    HIP_TRY(hipEventElapsedTime(&ms[0], im->ev_s[0], im->ev_s[1])); HIP_TRY(hipEventElapsedTime(&ms[1], im->ev_s[1], im->ev_s[2]));
-    HIP_TRY(hipEventElapsedTime(&ms[2], im->ev_s[3], im->ev_s[4]));
-    im->sc_ms_heads = ms[0]; im->sc_ms_rows = ms[1]; im->sc_ms_emit = ms[2];
-    return 0;
+    return coo_deliver(im, c, t0);
 }
 
 int engine_snp_counts(EngineImpl* im, xck_result* out) {
     xck_engine* e = im->eng;
+    CooCall& c = im->sc;
     if (im->mode != XCK_MODE_BAF) { e->err = "xck_snp_counts: not a pileup pipeline"; return XCK_E_ARG; }
     if (im->fold_failed || !im->finished || !im->mol_valid) { e->err = "xck_snp_counts: valid between a successful xck_finish and the next xck_reset"; return XCK_E_STATE; }
     HIP_TRY(hipSetDevice(im->device));
     const auto t0 = std::chrono::steady_clock::now();
     clear_stale_error("snp_counts", e->knobs.debug_timing);
     im->sc_valid = false;
-    im->sc_ms_heads = im->sc_ms_rows = im->sc_ms_emit = im->sc_ms_copy = im->sc_ms_total = 0;
-    if (im->mol_n == 0) { for (auto& z : im->sc_nnz) z = 0; }
-    else if (int rc = im->key_bits == 64 ? snp_counts_run<uint64_t>(im, t0) : snp_counts_run<u128>(im, t0)) {
-        hipStreamSynchronize(im->s_comp); hipStreamSynchronize(im->s_copy);                                 // nothing of the handle was overwritten: it is not marked failed
-        return rc;
-    }
+    if (int rc = coo_begin(im, c)) return rc;
+    if (im->mol_n)
+        if (int rc = im->key_bits == 64 ? snp_counts_run<uint64_t>(im, t0) : snp_counts_run<u128>(im, t0)) return coo_fail(im, rc);
     im->sc_valid = true;
     if (e->knobs.debug_timing) fprintf(stderr, "[xck] snp_counts: total %.3f ms (host clock to the stream synchronise): flags + long runs %.3f, scans + row bases %.3f, emit %.3f; wait for the copy-out %.3f; "
-                                               "%zu entries, nnz %zu / %zu / %zu\n", im->sc_ms_total, im->sc_ms_heads, im->sc_ms_rows, im->sc_ms_emit, im->sc_ms_copy, im->mol_n,
-                                       im->sc_nnz[0], im->sc_nnz[1], im->sc_nnz[2]);
+                                               "%zu entries, nnz %zu / %zu / %zu\n", c.ms_total, c.ms_phase[0], c.ms_phase[1], c.ms_phase[2], c.ms_copy, im->mol_n, c.nnz[0], c.nnz[1], c.nnz[2]);
     memset(out, 0, sizeof *out);
-    xck_coo* dst[3] = { &out->ad, &out->dp, &out->oth };
-    size_t at = 0;
-    for (int y = 0; y < 3; y++) {
-        const size_t z = im->sc_nnz[y];
-        dst[y]->nnz = (int64_t)z;
-        if (z) { dst[y]->row = im->h_sc_res + at; dst[y]->col = im->h_sc_res + at + z; dst[y]->val = im->h_sc_res + at + 2 * z; }
-        at += 3 * z;
-    }
+    xck_coo* const dst[3] = { &out->ad, &out->dp, &out->oth };
+    coo_fill(c, 3, dst);
     return 0;
 }
