@@ -13,7 +13,6 @@ engine then counts with that phase.  XCK_DEVICE_PHASING=1 phases the regions on 
 
 import os
 import sys
-import time
 from logging import error, info
 from logging import warning as warn
 
@@ -21,7 +20,6 @@ import numpy as np
 
 from ... import fc_common as fcc
 from ...capi import XCK_MODE_BAF
-from ...engine import XckError
 from .config import Config
 
 
@@ -30,11 +28,12 @@ def afc_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_list_
                 ref_cell_fn=None, cell_tag="CB", umi_tag="UB", min_count=1, min_maf=0,
                 output_all_reg=False, no_dup_hap=True, min_mapq=20, min_len=30, incl_flag=0,
                 excl_flag=None, no_orphan=True):
-    return afc_run(afc_conf(sam_fn=sam_fn, barcode_fn=barcode_fn, region_fn=region_fn, phased_snp_fn=phased_snp_fn, out_dir=out_dir,
-                            sam_list_fn=sam_list_fn, sample_ids=sample_ids, sample_id_fn=sample_id_fn, debug_level=debug_level, ncores=ncores,
-                            cellsnp_dir=cellsnp_dir, ref_cell_fn=ref_cell_fn, cell_tag=cell_tag, umi_tag=umi_tag, min_count=min_count,
-                            min_maf=min_maf, output_all_reg=output_all_reg, no_dup_hap=no_dup_hap, min_mapq=min_mapq, min_len=min_len,
-                            incl_flag=incl_flag, excl_flag=excl_flag, no_orphan=no_orphan))
+    conf = afc_conf(sam_fn=sam_fn, barcode_fn=barcode_fn, region_fn=region_fn, phased_snp_fn=phased_snp_fn, out_dir=out_dir,
+                    sam_list_fn=sam_list_fn, sample_ids=sample_ids, sample_id_fn=sample_id_fn, debug_level=debug_level, ncores=ncores,
+                    cellsnp_dir=cellsnp_dir, ref_cell_fn=ref_cell_fn, cell_tag=cell_tag, umi_tag=umi_tag, min_count=min_count,
+                    min_maf=min_maf, output_all_reg=output_all_reg, no_dup_hap=no_dup_hap, min_mapq=min_mapq, min_len=min_len,
+                    incl_flag=incl_flag, excl_flag=excl_flag, no_orphan=no_orphan)
+    return fcc.run_logged(afc_core, conf)
 
 
 def afc_conf(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_list_fn=None, sample_ids=None, sample_id_fn=None, debug_level=0,
@@ -201,16 +200,10 @@ def phased_tables(conf, regions, snps, has_snp):
 def write_matrices(conf, eng, dist, regions, coo):
     """xcltk.region.tsv and the three .mtx files of one counted table (afc_wrapper, afc_variants and the one-pass `xcltk baf` write
     through here), and with XCK_CELL_GROUPS their sums per cell group.  Only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113), unless output_all_reg."""
-    rm = fcc.output_row_map(dist, len(regions), conf.output_all_reg, coo["dp"][0], coo["oth"][0])
-    n_rows = int(rm.max()) if len(rm) else 0
-    if fcc.is_writer_rank():
-        fcc.write_region_tsv(conf.out_region_fn, regions, rm)
-    fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, n_rows)
-    fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, n_rows)
-    fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, n_rows)
-    pre = os.path.join(conf.out_dir, conf.out_prefix)                # (XCK_CELL_GROUPS only: the same rows, summed per group)
-    fcc.write_group_matrices(eng, dist, getattr(conf, "cell_groups", None), pre + "groups.tsv",
-                             {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"}, rm, n_rows)
+    pre = os.path.join(conf.out_dir, conf.out_prefix)
+    fcc.write_matrix_set(eng, dist, regions, coo, conf.output_all_reg, conf.out_region_fn, {"ad": conf.out_ad_fn, "dp": conf.out_dp_fn, "oth": conf.out_oth_fn},
+                         ("dp", "oth"), getattr(conf, "cell_groups", None), pre + "groups.tsv",
+                         {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"})
 
 
 def afc_core(conf):
@@ -224,40 +217,11 @@ def afc_core(conf):
     snps, excl = phased_tables(conf, regions, snps, has_snp)
     eng, coo, dist = fcc.make_and_count(conf, XCK_MODE_BAF, regions, snps, excl_pairs=excl)
     try:
-        fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"))   # (XCK_READ_FATE=1 only)
-        fcc.write_cell_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "cell_summary.tsv"), conf.samples)   # (XCK_CELL_SUMMARY=1 only)
-        fcc.write_feature_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "feature_summary.tsv"), regions)   # (XCK_FEATURE_SUMMARY=1 only)
-        fcc.write_snp_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "snp_summary.tsv"), snps)
+        # (XCK_READ_FATE=1 / XCK_CELL_SUMMARY=1 / XCK_FEATURE_SUMMARY=1 only)
+        fcc.write_summaries(eng, dist, os.path.join(conf.out_dir, conf.out_prefix), conf.samples, regions, snps)
         if coo is not None:                               # the only process / rank 0 after a gather / every rank (sharded output)
             write_matrices(conf, eng, dist, regions, coo)
         if conf.debug > 0:
             info("engine stats: %s" % eng.stats())
     finally:
         eng.close()
-
-
-def afc_run(conf):
-    ret = -1
-    cmdline = None
-    start_time = time.time()
-    info("start time: %s." % time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(start_time)))
-    if conf.argv is not None:
-        cmdline = " ".join(conf.argv)
-        info("CMD: %s" % cmdline)
-    try:
-        afc_core(conf)
-    except (ValueError, XckError) as e:
-        error(str(e))
-        error("Running program failed.")
-        error("Quiting ...")
-        ret = -1
-    else:
-        info("All Done!")
-        ret = 0
-    finally:
-        if conf.argv is not None:
-            info("CMD: %s" % cmdline)
-        end_time = time.time()
-        info("end time: %s" % time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(end_time)))
-        info("time spent: %.2fs" % (end_time - start_time))
-    return ret

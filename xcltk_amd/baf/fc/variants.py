@@ -131,16 +131,9 @@ def afc_variants(common, variants):
                 coo = refold_plan(eng, p)
                 info("[engine] variant %d recounted under its own tables (%d regions)" % (i, len(p["regions"])))
             pre = os.path.join(conf.out_dir, conf.out_prefix)
-            fcc.write_read_summary(eng, dist, pre + "read_summary.tsv")
-            fcc.write_cell_summary(eng, dist, pre + "cell_summary.tsv", conf.samples)
-            fcc.write_feature_summary(eng, dist, pre + "feature_summary.tsv", p["regions"])
-            if p["enabled"].all() and np.array_equal(p["u_idx"], np.arange(len(universe))):
-                fcc.write_snp_summary(eng, dist, pre + "snp_summary.tsv", p["snps"])
-            else:                                          # the variant's own SNPs, in its order
-                fs = eng.feature_summary(XCK_MODE_BAF) if hasattr(eng, "feature_summary") else None
-                if fs is not None and fs["snp"] is not None:
-                    with open(pre + "snp_summary.tsv", "w") as fp:
-                        fp.write(fcc.snp_summary_text(list(p["snps"]), np.asarray(fs["snp"], dtype=np.int64)[p["u_idx"]]))
+            fcc.write_summaries(eng, dist, pre, conf.samples, p["regions"])
+            # (the variant's own SNPs, in its order: rows of the universe's table)
+            fcc.write_snp_summary(eng, dist, pre + "snp_summary.tsv", p["snps"], rows=p["u_idx"])
             write_matrices(conf, eng, dist, p["regions"], coo)
     finally:
         eng.close()

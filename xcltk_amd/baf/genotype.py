@@ -167,12 +167,9 @@ def pileup(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, sa
     result, failure = (None, 0, 0), None
     try:
         try:
-            fcc.write_read_summary(eng, dist, os.path.join(out_dir, "read_summary.tsv"), log_prefix="[pileup]")   # (XCK_READ_FATE=1 only)
-            fcc.write_cell_summary(eng, dist, os.path.join(out_dir, "cell_summary.tsv"), conf.samples, log_prefix="[pileup]")   # (XCK_CELL_SUMMARY=1 only)
-            fcc.write_feature_summary(eng, dist, os.path.join(out_dir, "feature_summary.tsv"), regions, log_prefix="[pileup]")   # (XCK_FEATURE_SUMMARY=1 only)
-            # (`kept` / `snps_kept` in the two files: under the engine's min_count 1 / min_maf 0 above, not under the caller's thresholds,
-            # which filter_snps applies to the sums of raw/ afterwards)
-            fcc.write_snp_summary(eng, dist, os.path.join(out_dir, "snp_summary.tsv"), snps, log_prefix="[pileup]")
+            # (XCK_READ_FATE=1 / XCK_CELL_SUMMARY=1 / XCK_FEATURE_SUMMARY=1 only.  `kept` / `snps_kept` in the feature and SNP files: under the
+            # engine's min_count 1 / min_maf 0 above, not under the caller's thresholds, which filter_snps applies to the sums of raw/ afterwards)
+            fcc.write_summaries(eng, dist, os.path.join(out_dir, ""), conf.samples, regions, snps, log_prefix="[pileup]")
             if coo is not None:                                   # the matrices are views of the engine's pinned buffers: keep copies past close()
                 coo = {k: tuple(np.array(a) for a in v) for k, v in coo.items()}
                 if groups is not None and not fcc.group_output_off(dist, "[pileup]"):   # the SNP rows summed per cell group

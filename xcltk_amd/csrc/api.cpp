@@ -83,9 +83,9 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if (cfg->mode != XCK_MODE_BASEFC && cfg->mode != XCK_MODE_BAF && cfg->mode != XCK_MODE_BOTH) { set_thread_error("invalid mode"); return XCK_E_ARG; }
     if (cfg->n_cells <= 0 || cfg->n_contigs < 0 || cfg->n_regions < 0 || cfg->n_snps < 0) { set_thread_error("invalid table sizes"); return XCK_E_ARG; }
     if ((cfg->n_regions > 0 && !cfg->regions) || (cfg->n_snps > 0 && !cfg->snps)) { set_thread_error("null table pointer"); return XCK_E_ARG; }
-    if ((cfg->flags & XCK_F_READ_FATE) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_READ_FATE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
-    if ((cfg->flags & XCK_F_CELL_SUMMARY) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_CELL_SUMMARY needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
-    if ((cfg->flags & XCK_F_FEATURE_SUMMARY) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error("XCK_F_FEATURE_SUMMARY needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+    const struct { int flag; const char* name; } gpu_only[] = { { XCK_F_READ_FATE, "XCK_F_READ_FATE" }, { XCK_F_CELL_SUMMARY, "XCK_F_CELL_SUMMARY" }, { XCK_F_FEATURE_SUMMARY, "XCK_F_FEATURE_SUMMARY" } };
+    for (const auto& g : gpu_only)
+        if ((cfg->flags & g.flag) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error(std::string(g.name) + " needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
     e->cell_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_CELL_SUMMARY) || e->knobs.cell_summary);
@@ -269,38 +269,23 @@ int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
     return XCK_OK;
 }
 
-int xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out) {
+// xck_get_read_fate / xck_get_cell_summary / xck_get_feature_summary: T the struct ("xck_<what>"), kept the handle's switch ("XCK_F_<FLAG>")
+extern "C++" {                                            // (a template cannot have C linkage)
+template <class T>
+static int get_summary(xck_engine* e, int mode, T* out, bool xck_engine::*kept, const char* what, const char* flag, int (*get)(EngineImpl*, T*)) {
     if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
-    if (out->struct_size < sizeof(xck_read_fate)) { e->err = "xck_read_fate.struct_size mismatch (ABI)"; return XCK_E_ARG; }
-    if (!e->read_fate || e->n_impl <= 0) { e->err = "handle made without XCK_F_READ_FATE"; return XCK_E_STATE; }
-    EngineImpl* im = pipeline_of(e, mode, "xck_get_read_fate");
+    if (out->struct_size < sizeof(T)) { e->err = std::string("xck_") + what + ".struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (!(e->*kept) || e->n_impl <= 0) { e->err = std::string("handle made without XCK_F_") + flag; return XCK_E_STATE; }
+    EngineImpl* im = pipeline_of(e, mode, (std::string("xck_get_") + what).c_str());
     if (!im) return XCK_E_ARG;
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
-    return engine_read_fate(im, out);
+    return get(im, out);
 }
-
-int xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out) {
-    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
-    if (out->struct_size < sizeof(xck_cell_summary)) { e->err = "xck_cell_summary.struct_size mismatch (ABI)"; return XCK_E_ARG; }
-    if (!e->cell_summary || e->n_impl <= 0) { e->err = "handle made without XCK_F_CELL_SUMMARY"; return XCK_E_STATE; }
-    EngineImpl* im = pipeline_of(e, mode, "xck_get_cell_summary");
-    if (!im) return XCK_E_ARG;
-    const uint32_t sz = out->struct_size;
-    memset(out, 0, sizeof *out); out->struct_size = sz;
-    return engine_cell_summary(im, out);
 }
-
-int xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out) {
-    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
-    if (out->struct_size < sizeof(xck_feature_summary)) { e->err = "xck_feature_summary.struct_size mismatch (ABI)"; return XCK_E_ARG; }
-    if (!e->feature_summary || e->n_impl <= 0) { e->err = "handle made without XCK_F_FEATURE_SUMMARY"; return XCK_E_STATE; }
-    EngineImpl* im = pipeline_of(e, mode, "xck_get_feature_summary");
-    if (!im) return XCK_E_ARG;
-    const uint32_t sz = out->struct_size;
-    memset(out, 0, sizeof *out); out->struct_size = sz;
-    return engine_feature_summary(im, out);
-}
+int xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out) { return get_summary(e, mode, out, &xck_engine::read_fate, "read_fate", "READ_FATE", engine_read_fate); }
+int xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out) { return get_summary(e, mode, out, &xck_engine::cell_summary, "cell_summary", "CELL_SUMMARY", engine_cell_summary); }
+int xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out) { return get_summary(e, mode, out, &xck_engine::feature_summary, "feature_summary", "FEATURE_SUMMARY", engine_feature_summary); }
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }
 

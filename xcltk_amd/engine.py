@@ -485,20 +485,29 @@ class Engine(object):
         self._check(self.lib.xck_get_decode_stats(self.h, C.byref(st)), "xck_get_decode_stats")
         return {k: getattr(st, k) for k, _ in capi.DecodeStats._fields_ if k not in ("struct_size", "reserved0")}
 
+    def _summary(self, what, struct, mode):
+        """What read_fate / cell_summary / feature_summary share: `mode` defaults to the handle's own pipeline (ValueError on a
+        XCK_MODE_BOTH handle, which has two), xck_get_<what> fills a `struct` -> the struct, or None where the handle keeps no such
+        table (XCK_E_STATE)."""
+        if mode is None:
+            if self.mode == capi.XCK_MODE_BOTH:
+                raise ValueError("%s(): a XCK_MODE_BOTH handle has two pipelines, name one" % what)
+            mode = self.mode
+        out = struct()
+        out.struct_size = C.sizeof(struct)
+        rc = getattr(self.lib, "xck_get_" + what)(self.h, int(mode), C.byref(out))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_" + what)
+        return out
+
     def read_fate(self, mode=None):
         """Where the reads of one pipeline went since the last reset (xck_get_read_fate): dict of the counters in the struct's
         order, or None on a handle made without XCK_F_READ_FATE (and without XCK_READ_FATE=1 in the environment).  mode names the
         pipeline: the handle's own by default, XCK_MODE_BASEFC or XCK_MODE_BAF on a XCK_MODE_BOTH handle.  Waits for queued work."""
-        if mode is None:
-            if self.mode == capi.XCK_MODE_BOTH:
-                raise ValueError("read_fate(): a XCK_MODE_BOTH handle has two pipelines, name one")
-            mode = self.mode
-        rf = capi.ReadFate()
-        rf.struct_size = C.sizeof(capi.ReadFate)
-        rc = self.lib.xck_get_read_fate(self.h, int(mode), C.byref(rf))
-        if rc == capi.XCK_E_STATE:
+        rf = self._summary("read_fate", capi.ReadFate, mode)
+        if rf is None:
             return None
-        self._check(rc, "xck_get_read_fate")
         return {k: int(getattr(rf, k)) for k in capi.READ_FATE_FIELDS}
 
     def cell_summary(self, mode=None):
@@ -506,16 +515,9 @@ class Engine(object):
         (row n_cells: the reads without a listed cell), `matrix`, int64 [n_cells, k] (None before finish()), and the column names
         `fate_cols`, `matrix_cols` - copies, not views; or None on a handle made without XCK_F_CELL_SUMMARY (and without
         XCK_CELL_SUMMARY=1 in the environment).  mode as for read_fate().  Waits for queued work."""
-        if mode is None:
-            if self.mode == capi.XCK_MODE_BOTH:
-                raise ValueError("cell_summary(): a XCK_MODE_BOTH handle has two pipelines, name one")
-            mode = self.mode
-        cs = capi.CellSummary()
-        cs.struct_size = C.sizeof(capi.CellSummary)
-        rc = self.lib.xck_get_cell_summary(self.h, int(mode), C.byref(cs))
-        if rc == capi.XCK_E_STATE:
+        cs = self._summary("cell_summary", capi.CellSummary, mode)
+        if cs is None:
             return None
-        self._check(rc, "xck_get_cell_summary")
         n, k, km = int(cs.n_cells), int(cs.n_fate_cols), int(cs.n_matrix_cols)
         fate = np.ctypeslib.as_array(cs.fate, shape=((n + 1) * k,)).reshape(n + 1, k).copy()
         matrix = np.ctypeslib.as_array(cs.matrix, shape=(n * km,)).reshape(n, km).copy() if cs.has_matrix and cs.matrix else None
@@ -528,16 +530,9 @@ class Engine(object):
         `kept` are zero before finish()), `has_matrix`, and the column names `read_cols`, `matrix_cols`, `snp_cols` - copies, not
         views; or None on a handle made without XCK_F_FEATURE_SUMMARY (and without XCK_FEATURE_SUMMARY=1 in the environment).
         mode as for read_fate().  Waits for queued work."""
-        if mode is None:
-            if self.mode == capi.XCK_MODE_BOTH:
-                raise ValueError("feature_summary(): a XCK_MODE_BOTH handle has two pipelines, name one")
-            mode = self.mode
-        fs = capi.FeatureSummary()
-        fs.struct_size = C.sizeof(capi.FeatureSummary)
-        rc = self.lib.xck_get_feature_summary(self.h, int(mode), C.byref(fs))
-        if rc == capi.XCK_E_STATE:
+        fs = self._summary("feature_summary", capi.FeatureSummary, mode)
+        if fs is None:
             return None
-        self._check(rc, "xck_get_feature_summary")
 
         def table(p, rows, cols):
             if not p:

@@ -16,7 +16,7 @@ from logging import warning as warn
 import numpy as np
 
 from .capi import XCK_MODE_BASEFC
-from .engine import Engine
+from .engine import Engine, XckError
 from .snptable import SnpTable
 from .utils.grange import format_chrom
 from .utils.zfile import zopen
@@ -394,12 +394,51 @@ def write_group_matrices(eng, dist, groups, names_fn, mtx_fns, rm, n_rows_out, s
         write_mtx(eng, dist, fn, got[k], rm, n_rows_out, n_cols=len(names))
 
 
+def write_matrix_set(eng, dist, regions, coo, all_reg, region_fn, mtx_fns, presence, groups, group_names_fn, group_mtx_fns, log_prefix="[engine]"):
+    """One matrix set: the region file (writer rank), the .mtx files of mtx_fns (an ordered {key of coo: path}), and with XCK_CELL_GROUPS
+    the same rows summed per cell group (write_group_matrices).  A region keeps a row when a matrix named in `presence` wrote a line
+    for it - ("count",) for basefc (rdr/fc/core.py:118-124), ("dp", "oth") for BAF (baf/fc/core.py:101-113) - or, all_reg, always:
+    its row is then its input line number.  Sharded output: collective calls, on every rank."""
+    rm = output_row_map(dist, len(regions), all_reg, *[coo[k][0] for k in presence])
+    n_rows_out = int(rm.max()) if len(rm) else 0
+    if is_writer_rank():
+        write_region_tsv(region_fn, regions, rm)
+    for k, fn in mtx_fns.items():
+        write_mtx(eng, dist, fn, coo[k], rm, n_rows_out)
+    write_group_matrices(eng, dist, groups, group_names_fn, group_mtx_fns, rm, n_rows_out, log_prefix=log_prefix)
+
+
 def read_summary_text(fate, n_ranks=1, cut_contigs=0):
     """Text of read_summary.tsv: one `name\\tcount` line per counter of xck_read_fate, in the struct's order; runs of several
     ranks start with `#ranks=N cut_contigs=K`."""
     from .capi import READ_FATE_FIELDS
     head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
     return head + "".join("%s\t%d\n" % (k, int(fate[k])) for k in READ_FATE_FIELDS)
+
+
+def _summary_ranks(dist):
+    """(ranks, contigs cut over ranks) for the `#ranks` line of a summary file"""
+    if dist is None or not dist.active:
+        return 1, 0
+    return dist.world, len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
+
+
+def _write_summary(dist, path, arrays, text, log):
+    """What every summary writer does with its table: the int64 `arrays` are summed over the ranks in ONE all-reduce (concatenated,
+    reduced, split, reshaped; a collective call), log(summed arrays) is logged, and the writer rank creates the directory and writes
+    text(summed arrays, n_ranks, cut_contigs) to `path`.  Returns the summed arrays."""
+    arrays = [np.asarray(a, dtype=np.int64) for a in arrays]
+    n_ranks, cut = _summary_ranks(dist)
+    if dist is not None and dist.active:
+        v = dist.all_reduce_np(np.concatenate([a.ravel() for a in arrays]))
+        ends = np.cumsum([a.size for a in arrays]).tolist()
+        arrays = [v[e - a.size:e].reshape(a.shape) for a, e in zip(arrays, ends)]
+    info(log(arrays))
+    if is_writer_rank():
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as fp:
+            fp.write(text(arrays, n_ranks, cut))
+    return arrays
 
 
 def write_read_summary(eng, dist, path, mode=None, log_prefix="[engine]"):
@@ -413,18 +452,9 @@ def write_read_summary(eng, dist, path, mode=None, log_prefix="[engine]"):
     fate = read_fate(mode) if read_fate else None
     if fate is None:
         return None
-    n_ranks, cut = 1, 0
-    if dist is not None and dist.active:
-        v = dist.all_reduce_np(np.array([fate[k] for k in READ_FATE_FIELDS], dtype=np.int64))
-        fate = dict(zip(READ_FATE_FIELDS, (int(x) for x in v)))
-        n_ranks = dist.world
-        cut = len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
-    info("%s read summary: %s" % (log_prefix, " ".join("%s=%d" % (k, fate[k]) for k in READ_FATE_FIELDS)))
-    if is_writer_rank():
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fp:
-            fp.write(read_summary_text(fate, n_ranks, cut))
-    return fate
+    as_dict = lambda a: dict(zip(READ_FATE_FIELDS, a[0].tolist()))
+    return as_dict(_write_summary(dist, path, [[fate[k] for k in READ_FATE_FIELDS]], lambda a, n_ranks, cut: read_summary_text(as_dict(a), n_ranks, cut),
+                                  lambda a: "%s read summary: %s" % (log_prefix, " ".join("%s=%d" % kv for kv in as_dict(a).items()))))
 
 
 def cell_summary_text(names, fate, matrix, fate_cols, matrix_cols, n_ranks=1, cut_contigs=0):
@@ -455,24 +485,14 @@ def write_cell_summary(eng, dist, path, names, mode=None, log_prefix="[engine]")
     cs = cell_summary(mode) if cell_summary else None
     if cs is None:
         return None
-    fate = np.asarray(cs["fate"], dtype=np.int64)
-    matrix = cs["matrix"]
+    fate, matrix = np.asarray(cs["fate"]), cs["matrix"]
     if matrix is None:
         matrix = np.zeros((fate.shape[0] - 1, len(cs["matrix_cols"])), dtype=np.int64)
-    n_ranks, cut = 1, 0
-    if dist is not None and dist.active:
-        v = dist.all_reduce_np(np.concatenate([fate.ravel(), np.asarray(matrix, dtype=np.int64).ravel()]))
-        fate, matrix = v[:fate.size].reshape(fate.shape), v[fate.size:].reshape(matrix.shape)
-        n_ranks = dist.world
-        cut = len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
-    cs = dict(cs, fate=fate, matrix=matrix)
-    info("%s cell summary: %d cells with reads, %d reads without a listed cell" %
-         (log_prefix, int((fate[:-1].sum(axis=1) > 0).sum()), int(fate[-1, :len(cs["fate_cols"]) - 2].sum())))
-    if is_writer_rank():
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fp:
-            fp.write(cell_summary_text(list(names), fate, matrix, cs["fate_cols"], cs["matrix_cols"], n_ranks, cut))
-    return cs
+    fate, matrix = _write_summary(
+        dist, path, [fate, matrix], lambda a, n_ranks, cut: cell_summary_text(list(names), a[0], a[1], cs["fate_cols"], cs["matrix_cols"], n_ranks, cut),
+        lambda a: "%s cell summary: %d cells with reads, %d reads without a listed cell" %
+        (log_prefix, int((a[0][:-1].sum(axis=1) > 0).sum()), int(a[0][-1, :len(cs["fate_cols"]) - 2].sum())))
+    return dict(cs, fate=fate, matrix=matrix)
 
 
 def feature_summary_text(regions, reads, matrix, mode, n_ranks=1, cut_contigs=0):
@@ -500,43 +520,27 @@ def feature_summary_text(regions, reads, matrix, mode, n_ranks=1, cut_contigs=0)
     return "".join(lines)
 
 
-def _summary_ranks(dist):
-    """(ranks, contigs cut over ranks) for the `#ranks` line of a summary file"""
-    if dist is None or not dist.active:
-        return 1, 0
-    return dist.world, len(set(u["contig"] for u in getattr(dist, "units", ()) if u["window"] is not None))
-
-
 def write_feature_summary(eng, dist, path, regions, mode=None, log_prefix="[engine]"):
     """Per-feature table of one pipeline (Engine.feature_summary, after finish()) -> `path`, when the handle keeps it
     (XCK_FEATURE_SUMMARY=1 in the environment, or XCK_F_FEATURE_SUMMARY): nothing happens otherwise.  `regions`: the input regions
     (chrom, start, end, name) in input order.  Multi-GPU: a collective call - one summing all-reduce, and the writer rank writes
     the file.  Every rank counts only the regions of its region_mask and a region belongs to exactly one rank, so the file is
     exact even where a contig is cut over ranks.  Returns the (summed) dict or None."""
-    from .capi import XCK_MODE_BASEFC
+    from .capi import FEATURE_READ_COLS
     feature_summary = getattr(eng, "feature_summary", None)    # (an engine-like object without the method keeps nothing)
     fs = feature_summary(mode) if feature_summary else None
     if fs is None:
         return None
     mode = eng.mode if mode is None else mode
-    n = len(regions)
-    from .capi import FEATURE_READ_COLS
-    if mode == XCK_MODE_BASEFC:                                # (a handle without a region hands out no array: an empty table of the same columns)
-        reads = np.zeros((n, len(FEATURE_READ_COLS)), dtype=np.int64) if fs["reads"] is None else np.asarray(fs["reads"], dtype=np.int64)
-    else:
-        reads = np.zeros((n, 0), dtype=np.int64)
-    matrix = np.zeros((n, len(fs["matrix_cols"])), dtype=np.int64) if fs["matrix"] is None else np.asarray(fs["matrix"], dtype=np.int64)
-    n_ranks, cut = _summary_ranks(dist)
-    if dist is not None and dist.active:
-        v = dist.all_reduce_np(np.concatenate([reads.ravel(), matrix.ravel()]))
-        reads, matrix = v[:reads.size].reshape(reads.shape), v[reads.size:].reshape(matrix.shape)
-    fs = dict(fs, reads=reads if mode == XCK_MODE_BASEFC else None, matrix=matrix)
-    info("%s feature summary: %d of %d regions with an entry" % (log_prefix, int((matrix[:, -1] > 0).sum()), n))
-    if is_writer_rank():
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fp:
-            fp.write(feature_summary_text(list(regions), fs["reads"], matrix, mode, n_ranks, cut))
-    return fs
+    basefc = mode == XCK_MODE_BASEFC
+    n = len(regions)                                           # (a handle without a region hands out no array: an empty table of the same columns)
+    reads = np.zeros((n, len(FEATURE_READ_COLS) if basefc else 0), dtype=np.int64) if fs["reads"] is None or not basefc else fs["reads"]
+    matrix = np.zeros((n, len(fs["matrix_cols"])), dtype=np.int64) if fs["matrix"] is None else fs["matrix"]
+    reads, matrix = _write_summary(
+        dist, path, [reads, matrix],
+        lambda a, n_ranks, cut: feature_summary_text(list(regions), a[0] if basefc else None, a[1], mode, n_ranks, cut),
+        lambda a: "%s feature summary: %d of %d regions with an entry" % (log_prefix, int((a[1][:, -1] > 0).sum()), n))
+    return dict(fs, reads=reads if basefc else None, matrix=matrix)
 
 
 def snp_summary_text(snps, table, n_ranks=1, cut_contigs=0):
@@ -557,11 +561,12 @@ def snp_summary_text(snps, table, n_ranks=1, cut_contigs=0):
     return "".join(lines)
 
 
-def write_snp_summary(eng, dist, path, snps, mode=None, log_prefix="[engine]"):
+def write_snp_summary(eng, dist, path, snps, mode=None, log_prefix="[engine]", rows=None):
     """Per-SNP table of the pileup pipeline (Engine.feature_summary, after finish()) -> `path`, when the handle keeps it: nothing
-    happens otherwise.  `snps`: the input list, tuples (chrom, pos, ref, alt, ref_hap, alt_hap) or a SnpTable.  Multi-GPU: a
-    collective call - a rank zeroes the rows of the SNPs on contigs it does not stream, one summing all-reduce, and the writer
-    rank writes the file.  Where a contig is cut over ranks (cut_contigs > 0 in the `#ranks` line) both neighbours see the reads
+    happens otherwise.  `snps`: the list to print, tuples (chrom, pos, ref, alt, ref_hap, alt_hap) or a SnpTable - the engine's own
+    SNPs in input order, or with `rows` (an index array into the engine's SNP table, one per SNP of `snps`) a selection of them in
+    any order.  Multi-GPU: a collective call - a rank zeroes the rows of the SNPs on contigs it does not stream, one summing
+    all-reduce, and the writer rank writes the file.  Where a contig is cut over ranks (cut_contigs > 0 in the `#ranks` line) both neighbours see the reads
     and count the tallies of the SNPs near the cut, and `kept` is then the number of ranks that kept the SNP: those rows describe
     the ranks' work, not the file; nothing corrects for it.  `kept` (and `snps_kept` of feature_summary.tsv) is the verdict under
     the min_count / min_maf the ENGINE was made with: baf.genotype.pileup() makes its engine with 1 / 0 and applies the caller's
@@ -573,19 +578,27 @@ def write_snp_summary(eng, dist, path, snps, mode=None, log_prefix="[engine]"):
     if fs is None or fs["snp"] is None:
         return None
     table = np.asarray(fs["snp"], dtype=np.int64)
-    n_ranks, cut = _summary_ranks(dist)
-    if dist is not None and dist.active:
-        mask = getattr(dist, "contig_mask", None)
-        if mask is not None and len(table):
-            table[~np.asarray(mask, dtype=bool)[eng._snp["contig"]]] = 0
-        table = dist.all_reduce_np(table)
+    mask = getattr(dist, "contig_mask", None) if dist is not None and dist.active else None
+    if mask is not None and len(table):
+        table[~np.asarray(mask, dtype=bool)[eng._snp["contig"]]] = 0
+    if rows is not None:
+        table = table[np.asarray(rows, dtype=np.int64)]
     snps = list(snps)
-    info("%s SNP summary: %d of %d SNPs kept" % (log_prefix, int((table[:, 6] > 0).sum()), len(table)))
-    if is_writer_rank():
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as fp:
-            fp.write(snp_summary_text(snps, table, n_ranks, cut))
-    return table
+    return _write_summary(dist, path, [table], lambda a, n_ranks, cut: snp_summary_text(snps, a[0], n_ranks, cut),
+                          lambda a: "%s SNP summary: %d of %d SNPs kept" % (log_prefix, int((a[0][:, 6] > 0).sum()), len(a[0])))[0]
+
+
+def write_summaries(eng, dist, prefix, samples, regions, snps=None, mode=None, log_prefix="[engine]"):
+    """The opt-in tables of one pipeline next to its matrices: `prefix` + read_summary.tsv (XCK_READ_FATE=1), cell_summary.tsv
+    (XCK_CELL_SUMMARY=1), feature_summary.tsv (XCK_FEATURE_SUMMARY=1) and - `snps` given, the pileup pipeline - snp_summary.tsv, each
+    only when the handle keeps it.  `prefix` is a path prefix: a directory with its separator, or e.g. <dir>/xcltk. ; mode names the
+    pipeline of a XCK_MODE_BOTH handle.  Multi-GPU: the writers' collective calls, in this order on every rank."""
+    from .capi import XCK_MODE_BAF
+    write_read_summary(eng, dist, prefix + "read_summary.tsv", mode, log_prefix)
+    write_cell_summary(eng, dist, prefix + "cell_summary.tsv", samples, mode, log_prefix)
+    write_feature_summary(eng, dist, prefix + "feature_summary.tsv", regions, mode, log_prefix)
+    if snps is not None and (mode is None or mode & XCK_MODE_BAF):
+        write_snp_summary(eng, dist, prefix + "snp_summary.tsv", snps, mode, log_prefix)
 
 
 # ----------------------------------------------------------------------------- engine driver
@@ -774,7 +787,6 @@ def make_and_count(conf, mode, regions, snps=(), log_prefix="[engine]", gather=N
     rank 0 instead (coo is None on the other ranks).
     Returns (engine - the caller closes it, coo or None, Dist)."""
     from .capi import XCK_E_CAPACITY, XCK_F_FORCE_KEY128
-    from .engine import XckError
     flags = int(extra.pop("flags", 0))
     while True:
         eng = make_engine(conf, mode, regions, snps, flags=flags, **extra)
@@ -813,3 +825,32 @@ def make_and_count(conf, mode, regions, snps=(), log_prefix="[engine]", gather=N
             eng.close()
             raise
         return eng, coo, dist
+
+
+def run_logged(core, conf):
+    """core(conf) between the reference's start / CMD / end log lines (rdr/fc/main.py:270-302, baf/fc/main.py:262-294): 0, or -1
+    with the error logged when it raises ValueError or XckError."""
+    ret = -1
+    cmdline = None
+    start_time = time.time()
+    info("start time: %s." % time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(start_time)))
+    if conf.argv is not None:
+        cmdline = " ".join(conf.argv)
+        info("CMD: %s" % cmdline)
+    try:
+        core(conf)
+    except (ValueError, XckError) as e:
+        error(str(e))
+        error("Running program failed.")
+        error("Quiting ...")
+        ret = -1
+    else:
+        info("All Done!")
+        ret = 0
+    finally:
+        if conf.argv is not None:
+            info("CMD: %s" % cmdline)
+        end_time = time.time()
+        info("end time: %s" % time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(end_time)))
+        info("time spent: %.2fs" % (end_time - start_time))
+    return ret

@@ -14,6 +14,7 @@ from logging import error, info
 from . import fc_common as fcc
 from .baf.fc.config import Config as BafConfig
 from .baf.fc.main import prepare_config as baf_prepare
+from .baf.fc.main import write_matrices as baf_write_matrices
 from .capi import XCK_MODE_BAF, XCK_MODE_BASEFC, XCK_MODE_BOTH
 from .engine import XckError
 
@@ -36,7 +37,7 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
     conf.out_dir = os.path.join(out_dir, "baf")
     conf.debug, conf.nproc = debug_level, ncores
     conf.cell_tag, conf.umi_tag = cell_tag, umi_tag
-    conf.min_count, conf.min_maf, conf.no_dup_hap = min_count, min_maf, no_dup_hap
+    conf.min_count, conf.min_maf, conf.no_dup_hap, conf.output_all_reg = min_count, min_maf, no_dup_hap, baf_output_all_reg
     conf.min_mapq, conf.min_len, conf.incl_flag, conf.no_orphan = min_mapq, min_len, incl_flag, no_orphan
     conf.excl_flag = -1 if excl_flag is None else excl_flag
     try:
@@ -59,38 +60,18 @@ def fused_wrapper(sam_fn, barcode_fn, region_fn, phased_snp_fn, out_dir, sam_lis
         error(str(e))
         return -1
     try:
-        # (XCK_READ_FATE=1 only; the two pipelines keep their own counters: a contig may have regions and no SNPs)
-        fcc.write_read_summary(eng, dist, os.path.join(fc_dir, "read_summary.tsv"), XCK_MODE_BASEFC, "[fused basefc]")
-        fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"), XCK_MODE_BAF, "[fused baf]")
-        # (XCK_CELL_SUMMARY=1 only; one table per pipeline, next to its matrices)
-        fcc.write_cell_summary(eng, dist, os.path.join(fc_dir, "cell_summary.tsv"), conf.samples, XCK_MODE_BASEFC, "[fused basefc]")
-        fcc.write_cell_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "cell_summary.tsv"), conf.samples, XCK_MODE_BAF, "[fused baf]")
-        # (XCK_FEATURE_SUMMARY=1 only; likewise, and the per-SNP table of the pileup pipeline)
-        fcc.write_feature_summary(eng, dist, os.path.join(fc_dir, "feature_summary.tsv"), regions, XCK_MODE_BASEFC, "[fused basefc]")
-        fcc.write_feature_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "feature_summary.tsv"), regions, XCK_MODE_BAF, "[fused baf]")
-        fcc.write_snp_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "snp_summary.tsv"), snps, XCK_MODE_BAF, "[fused baf]")
+        # (XCK_READ_FATE=1 / XCK_CELL_SUMMARY=1 / XCK_FEATURE_SUMMARY=1 only; the two pipelines keep their own tables, each next to its
+        # matrices: a contig may have regions and no SNPs)
+        fcc.write_summaries(eng, dist, os.path.join(fc_dir, ""), conf.samples, regions, None, XCK_MODE_BASEFC, "[fused basefc]")
+        fcc.write_summaries(eng, dist, os.path.join(conf.out_dir, conf.out_prefix), conf.samples, regions, snps, XCK_MODE_BAF, "[fused baf]")
         if coo is None:
             return 0
-        n = len(regions)                                  # (sharded output: every rank is here and the calls below are collective)
-        rm = fcc.output_row_map(dist, n, rdr_output_all_reg, coo["count"][0])
-        if fcc.is_writer_rank():
-            fcc.write_region_tsv(os.path.join(fc_dir, "features.tsv"), regions, rm)
-        fcc.write_mtx(eng, dist, os.path.join(fc_dir, "matrix.mtx"), coo["count"], rm, int(rm.max()) if n else 0)
-        groups = conf.cell_groups                         # (XCK_CELL_GROUPS only; a gathered result writes no group files: one log line)
-        if groups is not None and fcc.group_output_off(dist, "[fused]"):
-            groups = None
-        fcc.write_group_matrices(eng, dist, groups, os.path.join(fc_dir, "groups.tsv"), {"count": os.path.join(fc_dir, "matrix.groups.mtx")}, rm,
-                                 int(rm.max()) if n else 0, log_prefix="[fused]")
-        rm = fcc.output_row_map(dist, n, baf_output_all_reg, coo["dp"][0], coo["oth"][0])
-        nr = int(rm.max()) if n else 0
-        if fcc.is_writer_rank():
-            fcc.write_region_tsv(conf.out_region_fn, regions, rm)
-        fcc.write_mtx(eng, dist, conf.out_ad_fn, coo["ad"], rm, nr)
-        fcc.write_mtx(eng, dist, conf.out_dp_fn, coo["dp"], rm, nr)
-        fcc.write_mtx(eng, dist, conf.out_oth_fn, coo["oth"], rm, nr)
-        pre = os.path.join(conf.out_dir, conf.out_prefix)
-        fcc.write_group_matrices(eng, dist, groups, pre + "groups.tsv", {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"},
-                                 rm, nr, log_prefix="[fused]")
+        if conf.cell_groups is not None and fcc.group_output_off(dist, "[fused]"):   # (a gathered result writes no group files: one log line)
+            conf.cell_groups = None
+        # (sharded output: every rank is here and the calls below are collective)
+        fcc.write_matrix_set(eng, dist, regions, coo, rdr_output_all_reg, os.path.join(fc_dir, "features.tsv"), {"count": os.path.join(fc_dir, "matrix.mtx")},
+                             ("count",), conf.cell_groups, os.path.join(fc_dir, "groups.tsv"), {"count": os.path.join(fc_dir, "matrix.groups.mtx")}, "[fused]")
+        baf_write_matrices(conf, eng, dist, regions, coo)
     finally:
         eng.close()
     info("fused basefc + baf done in %.2fs" % (time.time() - t0))

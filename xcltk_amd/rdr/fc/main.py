@@ -10,12 +10,10 @@ the HIP engine (csrc/engine.hip) behind the C-ABI of include/xck.h.
 import getopt
 import os
 import sys
-import time
 from logging import error, info
 
 from ... import fc_common as fcc
 from ...capi import XCK_MODE_BASEFC
-from ...engine import XckError
 from ...config import APP, VERSION
 from ...utils.xlog import init_logging
 from .config import Config
@@ -102,7 +100,7 @@ def fc_main(argv, conf=None):
         else:
             error("invalid option: '%s'." % op)
             return -1
-    return fc_run(conf)
+    return fcc.run_logged(fc_core, conf)
 
 
 def fc_wrapper(sam_fn, barcode_fn, region_fn, out_dir, sam_list_fn=None, sample_ids=None,
@@ -124,7 +122,7 @@ def fc_wrapper(sam_fn, barcode_fn, region_fn, out_dir, sam_list_fn=None, sample_
     conf.incl_flag, conf.no_orphan = incl_flag, no_orphan
     if excl_flag is None:
         conf.excl_flag = -1
-    return fc_run(conf)
+    return fcc.run_logged(fc_core, conf)
 
 
 def prepare_config(conf):
@@ -165,45 +163,12 @@ def fc_core(conf):
     regions = conf.reg_list
     eng, coo, dist = fcc.make_and_count(conf, XCK_MODE_BASEFC, regions)
     try:
-        fcc.write_read_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "read_summary.tsv"))   # (XCK_READ_FATE=1 only)
-        fcc.write_cell_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "cell_summary.tsv"), conf.samples)   # (XCK_CELL_SUMMARY=1 only)
-        fcc.write_feature_summary(eng, dist, os.path.join(conf.out_dir, conf.out_prefix + "feature_summary.tsv"), regions)   # (XCK_FEATURE_SUMMARY=1 only)
+        pre = os.path.join(conf.out_dir, conf.out_prefix)
+        fcc.write_summaries(eng, dist, pre, conf.samples, regions)   # (XCK_READ_FATE=1 / XCK_CELL_SUMMARY=1 / XCK_FEATURE_SUMMARY=1 only)
         if coo is not None:                               # the only process / rank 0 after a gather / every rank (sharded output)
-            rm = fcc.output_row_map(dist, len(regions), conf.output_all_reg, coo["count"][0])   # all_reg: row = input line number
-            if fcc.is_writer_rank():
-                fcc.write_region_tsv(conf.out_region_fn, regions, rm)
-            fcc.write_mtx(eng, dist, conf.out_mtx_fn, coo["count"], rm, int(rm.max()) if len(rm) else 0)
-            pre = os.path.join(conf.out_dir, conf.out_prefix)
-            fcc.write_group_matrices(eng, dist, conf.cell_groups, pre + "groups.tsv", {"count": pre + "matrix.groups.mtx"}, rm,
-                                     int(rm.max()) if len(rm) else 0)   # (XCK_CELL_GROUPS only)
+            fcc.write_matrix_set(eng, dist, regions, coo, conf.output_all_reg, conf.out_region_fn, {"count": conf.out_mtx_fn}, ("count",),
+                                 conf.cell_groups, pre + "groups.tsv", {"count": pre + "matrix.groups.mtx"})   # all_reg: row = input line number
         if conf.debug > 0:
             info("engine stats: %s" % eng.stats())
     finally:
         eng.close()
-
-
-def fc_run(conf):
-    ret = -1
-    cmdline = None
-    start_time = time.time()
-    info("start time: %s." % time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(start_time)))
-    if conf.argv is not None:
-        cmdline = " ".join(conf.argv)
-        info("CMD: %s" % cmdline)
-    try:
-        fc_core(conf)
-    except (ValueError, XckError) as e:
-        error(str(e))
-        error("Running program failed.")
-        error("Quiting ...")
-        ret = -1
-    else:
-        info("All Done!")
-        ret = 0
-    finally:
-        if conf.argv is not None:
-            info("CMD: %s" % cmdline)
-        end_time = time.time()
-        info("end time: %s" % time.strftime("%Y-%m-%d %H:%M:%S", time.localtime(end_time)))
-        info("time spent: %.2fs" % (end_time - start_time))
-    return ret
