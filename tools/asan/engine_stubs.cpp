@@ -6,16 +6,17 @@
 #include "../../xcltk_amd/csrc/xck_internal.h"
 
 namespace xck {
-// ---- csrc/engine.hip ----
+// ---- csrc/engine.hip (the summary headers it includes) ----
+int  engine_read_fate(EngineImpl*, xck_read_fate*) { return XCK_E_ARG; }
+int  engine_cell_summary(EngineImpl*, xck_cell_summary*) { return XCK_E_ARG; }
+int  engine_feature_summary(EngineImpl*, xck_feature_summary*) { return XCK_E_ARG; }
+// ---- csrc/pipeline.hip ----
 int  engine_create(const xck_config*, xck_engine*, EngineImpl**) { return XCK_E_ARG; }
 void engine_destroy(EngineImpl*) {}
 int  engine_push(EngineImpl*, const xck_batch*, bool) { return XCK_E_ARG; }
 int  engine_flush(EngineImpl*) { return XCK_E_ARG; }
 int  engine_reset(EngineImpl*) { return XCK_E_ARG; }
 int  engine_stats(const EngineImpl*, xck_stats*) { return XCK_E_ARG; }
-int  engine_read_fate(EngineImpl*, xck_read_fate*) { return XCK_E_ARG; }
-int  engine_cell_summary(EngineImpl*, xck_cell_summary*) { return XCK_E_ARG; }
-int  engine_feature_summary(EngineImpl*, xck_feature_summary*) { return XCK_E_ARG; }
 int  engine_device(const xck_engine*) { return -1; }                          // no device: the decoder's GPU share of the inflate never starts
 int  engine_numa_node(const xck_engine*) { return -1; }
 // (weak: a program that wants to see the chunks a GPU-backed handle would get brings its own, tools/asan/decoder_asan.cpp)

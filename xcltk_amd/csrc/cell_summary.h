@@ -159,12 +159,15 @@ static uint32_t cs_slot_mask(const EngineImpl* im, const int slots = CS_SLOTS) {
     return p - 1u;
 }
 
-// the table's own memory (engine_create; off: nothing)
+// the table's own memory (summaries_init; off: nothing), and its zeroing on s_comp (summaries_reset; off: only the flag)
 static int cell_summary_init(EngineImpl* im) {
-    const size_t rows = (size_t)im->n_cells + 1;
-    HIP_TRY(hipMalloc((void**)&im->d_cell, rows * CS_ROW_WORDS * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(im->d_cell, 0, rows * CS_ROW_WORDS * sizeof(unsigned long long)));
+    if (const int rc = dev_zeroed(im, (void**)&im->d_cell, ((size_t)im->n_cells + 1) * CS_ROW_WORDS * sizeof(unsigned long long))) return rc;
     HIP_TRY(hipMalloc((void**)&im->d_cmat, (size_t)im->n_cells * CS_MATRIX_COLS * sizeof(unsigned long long)));
+    return 0;
+}
+static int cell_summary_reset(EngineImpl* im) {
+    if (im->d_cell) HIP_TRY(hipMemsetAsync(im->d_cell, 0, ((size_t)im->n_cells + 1) * CS_ROW_WORDS * sizeof(unsigned long long), im->s_comp));
+    im->cmat_valid = false;
     return 0;
 }
 

@@ -1,6 +1,8 @@
-// engine_impl.h - what the two translation units of the engine share: engine.hip (tables, join kernels, push pipeline) and
-// finish.hip (fold kernels, finish driver).  Types, control-word layout, the per-GPU state (EngineImpl), the tuning macros both
-// sides read, and the host helpers one side defines for the other.
+// engine_impl.h - what the three translation units of the engine share: engine.hip (tables, join kernels, summary passes),
+// pipeline.hip (buffers, launch queue, push paths, lifecycle; host code only) and finish.hip (fold kernels, finish driver).  Types,
+// control-word layout, the per-GPU state (EngineImpl), the tuning macros more than one unit reads, and the host helpers one unit
+// defines for the others.  Of the join the pipeline sees the batch table it queues for and the handful of functions declared at the
+// end - its tile size, capacities and kernels stay private to engine.hip.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -62,6 +64,12 @@ struct BatchDesc {
     const int32_t* snp_win; int32_t n_swin; int32_t snp_end; // SNP window table of the batch's contig
 };
 
+constexpr int MAX_FUSE = 24;              // batches per fused launch (the table travels in the kernel arguments)
+
+// Batch table, passed BY VALUE: it lives in the kernarg segment and is read with scalar loads
+// through the constant cache instead of costing a dependent round trip to HBM per tile.
+struct BatchTable { int32_t n_batches; int32_t n_tiles; BatchDesc desc[MAX_FUSE]; };
+
 // Per-tile facts computed once by k_tile_meta (one thread per tile, all tiles in parallel) so that
 // the join kernel's prologue is ONE load of this record plus ONE round of independent staging loads.
 struct TileMeta {
@@ -103,12 +111,6 @@ __device__ __forceinline__ uint32_t set_slot(unsigned long long kk) {
     uint32_t p;
     asm("v_mul_u32_u24 %0, %1, %2" : "=v"(p) : "v"(x), "v"(0x9E3779u));
     return (p >> 12) & (SLOTS - 1);
-}
-
-// Control words go to the host through MAPPED pinned memory written by a tiny kernel, never through the
-// DMA engines: a 4 KB hipMemcpy D2H would queue behind a 170 MB result copy-out of another engine.
-static __global__ void k_publish(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ host_alias, int n) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) host_alias[i] = src[i];
 }
 
 struct ContigTab { int32_t reg_base = 0, n_reg = 0, snp_base = 0, n_snp = 0, swin_base = 0, n_swin = 0; };
@@ -275,19 +277,31 @@ static inline void sort_regions_by_contig(const xck_region* regions, int n_regio
     }
 }
 
-// host helpers defined in engine.hip
+// host helpers defined in pipeline.hip
 size_t key_bytes(const EngineImpl* im);
 size_t hit_slack(const EngineImpl* im);
 bool split_mode(const EngineImpl* im);
 int arena_begin(EngineImpl* im, Arena& a, size_t need);
 int grow_device(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack);   // grow-only buffers (capacities in bytes); contents are not kept
 int grow_pinned(EngineImpl* im, void** p, size_t* cap, size_t need, size_t slack);
+int dev_zeroed(EngineImpl* im, void** p, size_t bytes);    // a device buffer of its own, all zero
 int res_reserve(EngineImpl* im, int m, size_t nnz);
 int complete_pending(EngineImpl* im);
 int launch_queue(EngineImpl* im, int slot_idx, int shared_slot = -1);
-void join_stamps_report(const EngineImpl* im);             // XCK_STAMPS builds: the phase table of the last join launch
+// defined in engine.hip: all the pipeline sees of the join and of the summaries behind it
+int build_tables(EngineImpl* im, const xck_config* cfg);   // engine_create: the region / SNP tables the join reads, uploaded
+int launch_join(EngineImpl* im);                           // ONE fused join launch over im->inflight, then the control words to the host
+int join_stamps_collect(EngineImpl* im, float ms);         // XCK_STAMPS builds: sums the stamp records of the launch just waited for
+void join_stamps_report(const EngineImpl* im);             // ... and prints the phase table of the last join launch
+int summaries_init(EngineImpl* im, uint32_t flags);        // engine_create: the memory of the summaries the flags ask for
+int summaries_reset(EngineImpl* im);                       // engine_reset: their tables zeroed on s_comp (the caller synchronises)
+int launch_summaries(EngineImpl* im);                      // launch_queue: their passes behind the first join launch of im->inflight
 // defined in finish.hip
 int finish_init(EngineImpl* im);                           // engine_create: per-device attributes of the fold kernels
 int snp_verdicts(EngineImpl* im, uint32_t* d_kept);        // d_kept[s] = snp_passes() of sorted SNP s on the tallies of the last finish (enqueued on s_comp)
+// Control words go to the host through MAPPED pinned memory written by a tiny kernel, never through the DMA engines: a 4 KB hipMemcpy
+// D2H would queue behind a 170 MB result copy-out of another engine.  One block of `threads` on s_comp copies src[0, n) to host_alias
+// (a device alias of pinned words, d_hctl); the caller checks hipGetLastError().
+void publish_words(EngineImpl* im, const unsigned long long* src, unsigned long long* host_alias, int n, int threads);
 
 }  // namespace xck

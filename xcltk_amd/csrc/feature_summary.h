@@ -64,11 +64,10 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_feature_fate(FateArgs a, const i
     cs_flush(s, ca, tid);
 }
 
-// the tables' own memory (engine_create; off: nothing)
+// the tables' own memory (summaries_init; off: nothing), and their zeroing on s_comp (summaries_reset)
 static int feature_summary_init(EngineImpl* im) {
     const size_t words = im->mode == XCK_MODE_BASEFC ? (size_t)im->n_regions * FS_REG_WORDS : (size_t)im->n_snps_sorted;
-    HIP_TRY(hipMalloc((void**)&im->d_feat, std::max<size_t>(words, 1) * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(im->d_feat, 0, std::max<size_t>(words, 1) * sizeof(unsigned long long)));
+    if (const int rc = dev_zeroed(im, (void**)&im->d_feat, std::max<size_t>(words, 1) * sizeof(unsigned long long))) return rc;
     im->fmat_cap_bytes = std::max<size_t>((size_t)im->n_regions * 6, 1) * sizeof(unsigned long long);
     HIP_TRY(hipMalloc((void**)&im->d_fmat, im->fmat_cap_bytes));
     if (im->mode == XCK_MODE_BAF) {

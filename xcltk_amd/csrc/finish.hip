@@ -26,6 +26,14 @@
 #include "engine_impl.h"
 
 namespace xck {
+// control words -> the host's mapped pinned mirror (engine_impl.h publish_words: the one copy of this kernel, for all three units)
+static __global__ void k_publish(const unsigned long long* __restrict__ src, unsigned long long* __restrict__ host_alias, int n) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) host_alias[i] = src[i];
+}
+void publish_words(EngineImpl* im, const unsigned long long* src, unsigned long long* host_alias, int n, int threads) {
+    hipLaunchKernelGGL(k_publish, dim3(1), dim3(threads), 0, im->s_comp, src, host_alias, n);
+}
+
 // exclusive scan of one uint32 per thread over a 256-thread block; returns block total in `total`
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave, uint32_t& total) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -908,7 +916,7 @@ static int compact_coo(EngineImpl* im, Arena& ws, const HapSrc& hap, const K* ke
     hipLaunchKernelGGL(k_hap_count, dim3(nb), dim3(CP_BLOCK), 0, im->s_comp, hap, d_blk);
     hipLaunchKernelGGL(k_cp_scan, dim3(nm), dim3(1024), 0, im->s_comp, d_blk, (long long)nb, d_off, d_tot);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, im->s_comp, (const unsigned long long*)d_tot, im->d_hctl + CTL_X0, nm);
+    publish_words(im, d_tot, im->d_hctl + CTL_X0, nm, 64);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     CooOut3 out; memset(&out, 0, sizeof out);
@@ -951,7 +959,7 @@ static int fold_coo(EngineImpl* im, Arena& ws, const K* keys, size_t n, KeyLayou
     if (!d_blk || !d_off) { im->eng->err = "workspace exhausted (fold)"; return XCK_E_NOMEM; }
     hipLaunchKernelGGL((k_fold_heads<K>), dim3(nb), dim3(FD_BLOCK), 0, im->s_comp, keys, (long long)n, kl, d_blk);
     hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, im->s_comp, d_blk, (long long)nb, d_off, im->d_ctl + CTL_SCRATCH);
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, im->s_comp, (const unsigned long long*)(im->d_ctl + CTL_SCRATCH), im->d_hctl + CTL_SCRATCH, 1);
+    publish_words(im, im->d_ctl + CTL_SCRATCH, im->d_hctl + CTL_SCRATCH, 1, 64);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     size_t total = im->h_ctl[CTL_SCRATCH];
@@ -968,7 +976,7 @@ static int fold_coo(EngineImpl* im, Arena& ws, const K* keys, size_t n, KeyLayou
             hipLaunchKernelGGL(k_fold_emit_unsorted, dim3(nb), dim3(FU_BLOCK), FU_SLOTS * 8, im->s_comp, (const unsigned long long*)keys, (long long)n, kl8, d_off,
                                d_o, d_o + total, d_o + 2 * total, im->d_ctl + CTL_GIANT, sorted_from);
             HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, im->s_comp, (const unsigned long long*)(im->d_ctl + CTL_GIANT), im->d_hctl + CTL_GIANT, 1);
+            publish_words(im, im->d_ctl + CTL_GIANT, im->d_hctl + CTL_GIANT, 1, 64);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(im->s_comp));
             if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] hash fold: n=%zu nnz=%zu ubits=%d cbits=%d giant=%llu\n", n, total, kl.ubits, kl.cbits, im->h_ctl[CTL_GIANT]);
@@ -1209,7 +1217,7 @@ static int count_region_hits(EngineImpl* im, size_t n, PileupFold<K>& pf) {
     hipLaunchKernelGGL((k_expand<K, false, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, im->d_tally, im->d_snp_info,
                        im->sf, im->d_csr_off, im->d_csr_reg, (K*)nullptr, (V2*)nullptr, im->d_ctl, xb, -1);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(256), 0, im->s_comp, (const unsigned long long*)(im->d_ctl + CTL_X0), im->d_hctl + CTL_X0, XSHARD * CTL_STRIDE);
+    publish_words(im, im->d_ctl + CTL_X0, im->d_hctl + CTL_X0, XSHARD * CTL_STRIDE, 256);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     pf.n2 = 0; pf.cap2 = 0;

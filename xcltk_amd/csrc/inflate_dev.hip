@@ -615,7 +615,7 @@ bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_byt
     return true;
 }
 // No DMA engine on this path: the first version copied in and out with hipMemcpyAsync, and the engine's own copy of every decoded
-// chunk (one hipMemcpyAsync per chunk, csrc/engine.hip engine_push_block) queued up behind the 48 MB copy-outs - the coordinator's
+// chunk (one hipMemcpyAsync per chunk, csrc/pipeline.hip engine_push_block) queued up behind the 48 MB copy-outs - the coordinator's
 // push time rose from 0.25 to 1.6 s per 100 M records.  The kernel is bound by its serial Huffman chain, not by bytes: it takes
 // the compressed stream from host memory in 1 KB coalesced windows, every wave stores its finished block to the host block, and the
 // statuses go straight back.

@@ -1,6 +1,6 @@
 // read_fate.h - opt-in read assignment summary (XCK_F_READ_FATE / XCK_READ_FATE=1; xck_get_read_fate, include/xck.h).
-// Included by engine.hip inside namespace xck, behind launch_join(): it uses the join's BatchTable, ReadInfo, TILE, JOIN_BLOCK, cigar_summary, included_len and
-// frac_below, from engine_impl.h ReadFilter, BatchDesc, as_global, EngineImpl and HIP_TRY, and the grouped accumulation of cell_summary.h.
+// Included by engine.hip inside namespace xck, behind launch_join(): it uses the join's ReadInfo, TILE, fill_batch_table, cigar_summary, included_len and
+// frac_below, from engine_impl.h BatchTable, JOIN_BLOCK, ReadFilter, BatchDesc, as_global, EngineImpl, dev_zeroed and HIP_TRY, and the grouped accumulation of cell_summary.h.
 //
 // One more pass over the batches the join has just been launched on: every read gets exactly ONE class, the first that applies in
 // the order of the reference's check_read() (rdr/fc/core.py:46-62 == baf/fc/core.py:18-34) followed by the fetch overlap and the
@@ -171,19 +171,22 @@ static_assert(RF_WORDS == CS_ROW_WORDS && RF_USED == CS_COLS && RF_MULTI < CS_C3
 // The arguments every pass behind the join shares (launch_read_fate, launch_feature_fate of feature_summary.h): the batches in
 // im->inflight with the join's tile numbering, the filter, the tables.  -> tiles = blocks of the launch; a.out is the caller's.
 static int32_t fill_fate_args(const EngineImpl* im, FateArgs& a) {
-    const int nb = (int)im->inflight.size();
-    int32_t tiles = 0;
-    for (int i = 0; i < nb; i++) { a.bt.desc[i] = im->inflight[i]; tiles += (im->inflight[i].n + TILE - 1) / TILE; }
-    a.bt.n_batches = nb; a.bt.n_tiles = tiles;
+    const int32_t tiles = fill_batch_table(im, a.bt);
     a.f = im->rf;
     a.reg_s0 = im->d_reg_s0; a.reg_e0 = im->d_reg_e0; a.reg_pmax = im->d_reg_pmax; a.snp_p0 = im->d_snp_p0;
     a.out = nullptr;
     return tiles;
 }
 
-// Runs once per batch: called by launch_queue() behind the FIRST join launch of the batches in im->inflight (whose tile0 that
-// launch has set), on the same stream - so it is over before complete_pending() hands their staging slot back - and never by the
-// overflow replay.
+// the counters' own memory (summaries_init), and their zeroing on s_comp (summaries_reset); both only with the flag on
+static int read_fate_init(EngineImpl* im) { return dev_zeroed(im, (void**)&im->d_fate, RF_WORDS * sizeof(unsigned long long)); }
+static int read_fate_reset(EngineImpl* im) {
+    HIP_TRY(hipMemsetAsync(im->d_fate, 0, RF_WORDS * sizeof(unsigned long long), im->s_comp));
+    return 0;
+}
+
+// Runs once per batch: called by launch_queue() (launch_summaries) behind the FIRST join launch of the batches in im->inflight, on the
+// same stream - so it is over before complete_pending() hands their staging slot back - and never by the overflow replay.
 static int launch_read_fate(EngineImpl* im) {
     if (!im->d_fate || im->inflight.empty()) return 0;
     FateArgs a;

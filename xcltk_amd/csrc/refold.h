@@ -169,7 +169,7 @@ static int refold_build_tables(EngineImpl* im, const xck_refold_config* cfg, boo
     HIP_TRY(hipGetLastError());
     if (int rc = pf_scan(im, (uint32_t*)im->d_csr_alt, ns + 1, bsum, nullptr)) return rc;
     HIP_TRY(hipEventRecord(im->ev_r1, im->s_comp));
-    hipLaunchKernelGGL(k_publish, dim3(1), dim3(64), 0, im->s_comp, (const unsigned long long*)(im->d_ctl + CTL_SCRATCH), im->d_hctl + CTL_SCRATCH, 1);
+    publish_words(im, im->d_ctl + CTL_SCRATCH, im->d_hctl + CTL_SCRATCH, 1, 64);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     const unsigned long long total = im->h_ctl[CTL_SCRATCH];

@@ -132,7 +132,7 @@ enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_C
 // (DS_NAMES_INTERNED / DS_NAMES_DISTINCT are the device table's own counters: xck_get_decode_stats asks the table)
 
 struct EngineImpl;                       // one GPU pipeline of a handle (engine_impl.h)
-struct Stager;                           // device staging slots of engine_push_block (engine.hip)
+struct Stager;                           // device staging slots of engine_push_block (pipeline.hip)
 struct DevIntern;                        // the handle's intern table in HBM (intern_dev.h)
 uint64_t intern_id_limit(int umi_bits);  // ids an intern table may hand out for that key width (bam_records.cpp; XCK_TEST_INTERN_LIMIT)
 // the names a host-parsed chunk hands to the device table: DiItem[n_out] at items_off of its block, the packed bytes behind them
@@ -172,7 +172,7 @@ struct xck_engine {
     // host pinned batch staging used by xck_ingest_bam lives in the xck_bam
 };
 
-// implemented in engine.hip (engine_finish, engine_finish_async, engine_result_device: finish.hip).  A per-pipeline call takes the
+// implemented in pipeline.hip (the summaries: the headers engine.hip includes; engine_finish and what follows it: finish.hip).  A per-pipeline call takes the
 // pipeline it works on; nothing in the handle says which one is "current", so calls from several threads do not meet there.
 namespace xck {
 int  engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out);   // *out is set as soon as it exists: a failed create still has to be destroyed
