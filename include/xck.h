@@ -63,6 +63,13 @@
  *                                         nothing to the flags; any other value means host.  Intact files give identical results either way; a damaged
  *                                         block fails the decode call with XCK_E_IO ("BGZF CRC mismatch", the file and the block's offset) instead
  *                                         of being counted.
+ *   XCK_TAG_FILTER=TAG:VALUE[/MASK]       (opt-in; unset: no record is looked at twice and no result changes) the read filter of xck_config.filter_tag /
+ *                                         filter_mask / filter_value for front-ends whose calls do not carry the fields: a record counts only when the first
+ *                                         occurrence of the two-character TAG is an integer v with 0 <= v <= 0xFFFFFFFF and (v & MASK) == VALUE.  VALUE and
+ *                                         MASK are decimal or 0x hex, MASK defaults to 0xFFFFFFFF: xf:25 keeps the reads Cell Ranger counted with the usual
+ *                                         flags, xf:8/8 every read that is the one counted for its UMI.  Non-empty config fields win over the knob; a
+ *                                         malformed value fails xck_create with XCK_E_ARG.  Decode-only handles honour it (the host parser applies it).
+ *                                         A rejected record stays in its batch with cell = XCK_CELL_FILTERED; xck_decode_stats.tag_filtered counts them.
  *   XCK_READ_FATE=1                       every handle that drives a GPU counts where its reads went, as if made with XCK_F_READ_FATE (xck_get_read_fate) -
  *                                         for front-ends whose calls do not carry the flags: they then write read_summary.tsv next to their matrices.
  *                                         One small kernel more per join launch; off (the default, or 0) nothing is allocated or launched.  Decode-only
@@ -129,6 +136,9 @@ extern "C" {
 /* UMI / read-name key code meaning "no usable key" (tag missing or empty string;
  * reference: check_read() -12, rdr/fc/mcount.py:41, baf/fc/mcount.py:116-117) */
 #define XCK_UMI_NONE  0xFFFFFFFFFFFFFFFFull
+/* cell column value of a record the handle's tag filter rejected (xck_config.filter_tag).  To every kernel it means what -1 means:
+ * the join drops the read and xck_read_fate counts it under no_cell.  Callers of xck_push_batch may pass it themselves. */
+#define XCK_CELL_FILTERED (-2)
 
 /* A region ("feature"): 1-based inclusive start/end exactly as in the region TSV
  * (reference load_region_from_txt, rdr/fc/utils.py:10-45).  `contig` indexes the caller's
@@ -191,6 +201,18 @@ typedef struct xck_config {
     int32_t  n_excl_pairs;
     const int32_t* excl_region;
     const int32_t* excl_snp;
+    /* Opt-in read filter on an integer aux tag (10x: "xf"), applied by the decoder (xck_ingest_bam / xck_bam_next_batch, on the host
+     * and in the device parse alike).  filter_tag = "" : off.  A record passes when the FIRST occurrence of the tag (htslib
+     * bam_aux_get, as for cell_tag / umi_tag) has an integer type (c C s S i I), its value v widened to 64 bits lies in
+     * 0 .. 0xFFFFFFFF and ((uint32_t)v & filter_mask) == filter_value.  Every other record - tag absent, of type A Z H f B, negative,
+     * or behind an aux value that cannot be skipped - fails: it keeps its place in its batch (ordinals and every other column are
+     * as without the filter) and its cell becomes XCK_CELL_FILTERED, whatever its barcode or sample.  The matrices are those of a
+     * file from which the failing records were removed.  XCK_E_ARG: a tag that is not two printable characters or equals cell_tag /
+     * umi_tag, or filter_value & ~filter_mask != 0 (nothing could pass).  Read only when struct_size covers the fields; the
+     * environment's XCK_TAG_FILTER supplies them when filter_tag is empty.                                                  */
+    char     filter_tag[4];
+    uint32_t filter_mask;
+    uint32_t filter_value;
 } xck_config;
 
 #define XCK_F_FORCE_KEY128   1  /* always use 128-bit sort keys (testing)                    */
@@ -229,7 +251,9 @@ typedef struct xck_batch {
     const int32_t*  pos;        /* [n]   0-based leftmost reference coordinate               */
     const uint16_t* flag;       /* [n]   BAM FLAG                                            */
     const uint8_t*  mapq;       /* [n]                                                       */
-    const int32_t*  cell;       /* [n]   column index; <0 = tag missing / not in list        */
+    const int32_t*  cell;       /* [n]   column index; <0 = tag missing / not in list (-1), or
+                                   XCK_CELL_FILTERED (-2): rejected by the handle's tag filter -
+                                   callers may pass either, the kernels treat them alike      */
     const uint64_t* umi;        /* [n]   key code (see xck_umi_bits) or XCK_UMI_NONE         */
     const uint32_t* cig_off;    /* [n+1] offsets into cigar[]                                */
     const uint32_t* cigar;      /* BAM CIGAR words (len << 4 | op)                           */
@@ -295,6 +319,8 @@ typedef struct xck_decode_stats {
     int64_t gpu_names_interned;       /* read names looked up in the device table (directly codable and empty names need no table)  */
     int64_t gpu_names_distinct;       /* ids the device table handed out since its last clear, summed over the clears               */
     int64_t gpu_names_host_chunks;    /* host-parsed chunks (pool-inflated, tails, fallbacks, max_records) whose names were keyed on the device */
+    /* appended after those (xck_config.filter_tag / XCK_TAG_FILTER; a caller with a shorter struct gets the fields above): */
+    int64_t tag_filtered;             /* records that reached a batch with cell == XCK_CELL_FILTERED; a device-parsed chunk that fell back to the host counts once */
 } xck_decode_stats;
 
 /* Where the reads of ONE pipeline went, since the last xck_reset (handles made with XCK_F_READ_FATE; additive, ABI 3 is unchanged).
@@ -311,7 +337,8 @@ typedef struct xck_read_fate {
     int64_t  excl_flag;         /* excl_flag && (flag & excl_flag)                    (-3,  :49-50)                           */
     int64_t  incl_flag;         /* incl_flag && !(flag & incl_flag)                   (-4,  :51-52)                           */
     int64_t  orphan;            /* no_orphan, paired and not a proper pair            (-5,  :53-54)                           */
-    int64_t  no_cell;           /* cell < 0: tag missing, empty, or barcode not in the list (-11, :55-56; rdr/fc/mcount.py push_read) */
+    int64_t  no_cell;           /* cell < 0: tag missing, empty, or barcode not in the list (-11, :55-56; rdr/fc/mcount.py push_read);
+                                   includes the reads the handle's tag filter rejected (cell == XCK_CELL_FILTERED) that pass the four tests above */
     int64_t  no_umi;            /* key == XCK_UMI_NONE: tag missing or empty          (-12, :57-58)                           */
     int64_t  short_aligned;     /* aligned (M/=/X) bases < min_len                    (-21, :59-60)                           */
     int64_t  no_target;         /* basefc: no region with pos < end0 && endpos > start0 (the fetch() of utils/sam.py:85-118);
@@ -395,7 +422,8 @@ int  xck_umi_bits(const xck_engine* e);
  * measured); smaller ones are packed into one engine-owned pinned block and cross with ONE copy whose completion is an
  * event, not a wait (XCK_PUSH_STAGE_BYTES / XCK_PUSH_STAGE=0|1 override the rule).
  * The host arrays are checked first (one linear pass): cig_off / seq_off must not run backwards,
- * cell[i] < n_cells, contig < n_contigs, no null column - otherwise XCK_E_ARG and nothing is queued. */
+ * cell[i] < n_cells, contig < n_contigs, no null column - otherwise XCK_E_ARG and nothing is queued.
+ * A negative cell[i] drops the read: -1 and XCK_CELL_FILTERED (-2, a read the caller's own tag filter rejected) mean the same. */
 int  xck_push_batch(xck_engine* e, const xck_batch* b);
 /* Same, but the arrays are DEVICE pointers already resident in HBM (benchmarks, pipelines
  * that decode on the GPU side); no copy is made and they must stay valid until xck_flush().

@@ -14,6 +14,7 @@ XCK_MODE_BASEFC = 1
 XCK_MODE_BAF = 2
 XCK_MODE_BOTH = 3
 XCK_UMI_NONE = 0xFFFFFFFFFFFFFFFF
+XCK_CELL_FILTERED = -2                 # cell of a record the handle's tag filter rejected; to the kernels the same as -1
 XCK_F_FORCE_KEY128 = 1
 XCK_F_VERIFY_CRC = 2
 XCK_F_DECODE_ONLY = 4
@@ -58,6 +59,7 @@ class Config(C.Structure):
         ("cell_tag", C.c_char * 4), ("umi_tag", C.c_char * 4),
         ("max_batch_reads", C.c_int64), ("n_threads", C.c_int32), ("flags", C.c_int32),
         ("n_excl_pairs", C.c_int32), ("excl_region", C.POINTER(C.c_int32)), ("excl_snp", C.POINTER(C.c_int32)),
+        ("filter_tag", C.c_char * 4), ("filter_mask", C.c_uint32), ("filter_value", C.c_uint32),
     ]
 
 
@@ -123,7 +125,8 @@ class DecodeStats(C.Structure):
                 ("crc_blocks_device", C.c_int64), ("crc_blocks_host", C.c_int64), ("crc_mismatch_device", C.c_int64),
                 ("crc_device_host_disagree", C.c_int64), ("gpu_path_given_up", C.c_int64),
                 ("gpu_parse_chunks", C.c_int64), ("gpu_parse_fallbacks", C.c_int64),
-                ("gpu_names_interned", C.c_int64), ("gpu_names_distinct", C.c_int64), ("gpu_names_host_chunks", C.c_int64)]
+                ("gpu_names_interned", C.c_int64), ("gpu_names_distinct", C.c_int64), ("gpu_names_host_chunks", C.c_int64),
+                ("tag_filtered", C.c_int64)]
 
 
 class ReadFate(C.Structure):

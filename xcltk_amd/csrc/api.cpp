@@ -69,6 +69,30 @@ Knobs xck::Knobs::from_env() {
     k.feature_summary = num("XCK_FEATURE_SUMMARY", 0) != 0;
     k.group_long_row = (int)std::max(1ll, std::min(64ll, num("XCK_GROUP_LONG_ROW", 64)));
     k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
+    if (*str("XCK_TAG_FILTER")) {                                        // TAG:VALUE[/MASK], numbers decimal or 0x hex, MASK defaults to all ones
+        k.tag_filter_text = str("XCK_TAG_FILTER");
+        const char* s = k.tag_filter_text.c_str();
+        // a number that fills its field up to `stop` (':' '/' or the end) and fits 32 bits
+        auto u32 = [](const char* p, const char* stop, uint32_t* out) {
+            const bool hex = stop - p > 2 && p[0] == '0' && (p[1] == 'x' || p[1] == 'X');
+            if (hex) p += 2;
+            if (p == stop || stop - p > 10) return false;
+            uint64_t v = 0;
+            for (; p < stop; p++) {
+                const int d = *p >= '0' && *p <= '9' ? *p - '0' : hex && *p >= 'a' && *p <= 'f' ? *p - 'a' + 10 : hex && *p >= 'A' && *p <= 'F' ? *p - 'A' + 10 : -1;
+                if (d < 0) return false;
+                v = v * (hex ? 16 : 10) + (uint64_t)d;
+            }
+            if (v > 0xFFFFFFFFull) return false;
+            *out = (uint32_t)v; return true;
+        };
+        const size_t len = k.tag_filter_text.size();
+        const char* slash = strchr(s, '/'); const char* end = s + len;
+        k.tag_filter_mask = 0xFFFFFFFFu;
+        const bool ok = len >= 4 && s[2] == ':' && u32(s + 3, slash ? slash : end, &k.tag_filter_value) && (!slash || u32(slash + 1, end, &k.tag_filter_mask));
+        k.tag_filter = ok ? 1 : -1;
+        if (ok) { k.tag_filter_tag[0] = s[0]; k.tag_filter_tag[1] = s[1]; }
+    }
     return k;
 }
 
@@ -76,7 +100,8 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if (!cfg_in || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
     *out = nullptr;
     // ABI 1 structs (without the exclusion pairs) are accepted: the missing tail reads as zero
-    if (cfg_in->struct_size != offsetof(xck_config, n_excl_pairs) && cfg_in->struct_size != sizeof(xck_config)) { set_thread_error("xck_config.struct_size mismatch (ABI)"); return XCK_E_ARG; }
+    // ... and so are those without the tag filter (they end where filter_tag begins): no filter from the struct
+    if (cfg_in->struct_size != offsetof(xck_config, n_excl_pairs) && cfg_in->struct_size != offsetof(xck_config, filter_tag) && cfg_in->struct_size != sizeof(xck_config)) { set_thread_error("xck_config.struct_size mismatch (ABI)"); return XCK_E_ARG; }
     xck_config cfg_full; memset(&cfg_full, 0, sizeof cfg_full); memcpy(&cfg_full, cfg_in, cfg_in->struct_size); cfg_full.struct_size = sizeof(xck_config);
     const xck_config* cfg = &cfg_full;
     if (cfg->n_excl_pairs < 0 || (cfg->n_excl_pairs > 0 && (!cfg->excl_region || !cfg->excl_snp))) { set_thread_error("invalid exclusion pairs"); return XCK_E_ARG; }
@@ -88,6 +113,22 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
         if ((cfg->flags & g.flag) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error(std::string(g.name) + " needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
+    // the tag filter: the struct's fields, or - where the struct carries none - the knob; checked before a device is touched
+    {
+        DecodeCfg& d = e->dec;
+        auto bad = [&](const std::string& s) { set_thread_error(s); delete e; return XCK_E_ARG; };
+        if (e->knobs.tag_filter < 0) return bad("malformed XCK_TAG_FILTER \"" + e->knobs.tag_filter_text + "\": expected TAG:VALUE[/MASK], e.g. xf:25 or xf:8/8");
+        if (cfg->filter_tag[0]) { d.filter_on = true; d.filter_tag[0] = cfg->filter_tag[0]; d.filter_tag[1] = cfg->filter_tag[1]; d.filter_mask = cfg->filter_mask; d.filter_value = cfg->filter_value; }
+        else if (e->knobs.tag_filter > 0) { d.filter_on = true; memcpy(d.filter_tag, e->knobs.tag_filter_tag, 2); d.filter_mask = e->knobs.tag_filter_mask; d.filter_value = e->knobs.tag_filter_value; }
+        if (d.filter_on) {
+            const char* src = cfg->filter_tag[0] ? "xck_config.filter_tag" : "XCK_TAG_FILTER";
+            auto printable = [](char c) { return c > 0x20 && c < 0x7f; };
+            if (!printable(d.filter_tag[0]) || !printable(d.filter_tag[1]) || (cfg->filter_tag[0] && cfg->filter_tag[2])) return bad(std::string(src) + ": the tag must be two printable characters");
+            if ((cfg->barcodes && !memcmp(d.filter_tag, cfg->cell_tag, 2)) || (cfg->umi_tag[0] && !memcmp(d.filter_tag, cfg->umi_tag, 2)))
+                return bad(std::string(src) + ": the filter tag is the handle's cell or UMI tag");
+            if (d.filter_value & ~d.filter_mask) return bad(std::string(src) + ": value has bits outside the mask (no record could pass)");
+        }
+    }
     e->cell_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_CELL_SUMMARY) || e->knobs.cell_summary);
     e->feature_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_FEATURE_SUMMARY) || e->knobs.feature_summary);   // (does not imply the read summary)
     e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate || e->cell_summary);
@@ -261,11 +302,12 @@ int xck_get_decode_stats(const xck_engine* e, xck_decode_stats* out) {
     if (out->struct_size < offsetof(xck_decode_stats, gpu_parse_chunks)) { set_thread_error("xck_decode_stats.struct_size mismatch (ABI)"); return XCK_E_ARG; }
     int64_t* f[DS_N] = { &out->gpu_inflate_chunks, &out->gpu_inflate_blocks, &out->gpu_blocks_left_to_host, &out->crc_blocks_device, &out->crc_blocks_host,
                          &out->crc_mismatch_device, &out->crc_device_host_disagree, &out->gpu_path_given_up, &out->gpu_parse_chunks, &out->gpu_parse_fallbacks,
-                         &out->gpu_names_interned, &out->gpu_names_distinct, &out->gpu_names_host_chunks };
-    // (gpu_parse_* and then gpu_names_* were appended: a caller built before them passes the shorter struct and gets what it knows)
-    const int n = out->struct_size >= sizeof(xck_decode_stats) ? DS_N : out->struct_size >= offsetof(xck_decode_stats, gpu_names_interned) ? DS_NAMES_INTERNED : DS_PARSE_CHUNKS;
+                         &out->gpu_names_interned, &out->gpu_names_distinct, &out->gpu_names_host_chunks, &out->tag_filtered };
+    // (gpu_parse_*, then gpu_names_*, then tag_filtered were appended: a caller built before them passes the shorter struct and gets what it knows)
+    const int n = out->struct_size >= sizeof(xck_decode_stats) ? DS_N : out->struct_size >= offsetof(xck_decode_stats, tag_filtered) ? DS_TAG_FILTERED
+                : out->struct_size >= offsetof(xck_decode_stats, gpu_names_interned) ? DS_NAMES_INTERNED : DS_PARSE_CHUNKS;
     for (int k = 0; k < n; k++) *f[k] = e->dstat[k].load();
-    if (n == DS_N) engine_names_stats(e, &out->gpu_names_interned, &out->gpu_names_distinct);   // (the table's own counters)
+    if (n > DS_NAMES_INTERNED) engine_names_stats(e, &out->gpu_names_interned, &out->gpu_names_distinct);   // (the table's own counters)
     return XCK_OK;
 }
 

@@ -516,7 +516,11 @@ void Pusher::run() {
             push_parsed_ns += ns_since(t0); push_ns += ns_since(t0);
             if (r == 1) { count_parse_fallback(b); r = redo_on_host(j, &msg); host_chunk = r == 0; }
             else if (r) msg = j->e->err;
-            else { b->dstat[DS_PARSE_CHUNKS].fetch_add(1, std::memory_order_relaxed); b->gi.fb_row.store(0); }
+            else {
+                b->dstat[DS_PARSE_CHUNKS].fetch_add(1, std::memory_order_relaxed); b->gi.fb_row.store(0);
+                // (the tag filter: what k_parse counted, read behind the event engine_push_parsed waited for; a chunk that fell back is counted by its host parse alone)
+                if (j->e->dec.filter_on) b->dstat[DS_TAG_FILTERED].fetch_add((int64_t)gs->h_head->n_filtered, std::memory_order_relaxed);
+            }
             t0 = std::chrono::steady_clock::now();
         }
         if (host_chunk) {
@@ -795,8 +799,9 @@ static void drop_range_past_window(xck_bam* b, const Chunk& c, const ContigMap& 
 
 static void queue_parse_tasks(xck_bam* b, ChunkJob& j, const std::vector<WalkPart>& pieces, const ContigMap& cm, int32_t sample) {
     xck_engine* e = j.e; HostSoA* sp = &j.soa; std::atomic<int>* fl = &j.flags; DecodeTimes* tm = &b->tm;
+    std::atomic<int64_t>* nf = &b->dstat[DS_TAG_FILTERED];
     for (const WalkPart& wp : pieces) { if (!wp.n_out) continue; const WalkPart* wpp = &wp;
-        j.tg.later([tm, e, sp, sample, wpp, cm, fl] { parse_part(tm, e, sp, sample, wpp, cm, fl); }); }
+        j.tg.later([tm, e, sp, sample, wpp, cm, fl, nf] { parse_part(tm, e, sp, sample, wpp, cm, fl, nf); }); }
     j.tg.flush(*b->pool, true);                                         // (ahead of the later chunks' inflate tasks)
 }
 

@@ -334,7 +334,9 @@ void fill_batch(const HostSoA& s, const PendingBatch& pb, bool want_seq, xck_bat
 void run_part(Chunk* cp, const uint8_t* map, bool verify_crc, WalkPart* wpp, DecodeTimes* tm, const ContigMap cm, bool want_seq, const int32_t* st,
               std::atomic<int64_t>* dstat);
 // pool task: the records of one piece of a chunk -> the SoA block, at the piece's bases (layout_chunk)
-void parse_part(DecodeTimes* tm, xck_engine* e, HostSoA* sp, int32_t sample, const WalkPart* wp, const ContigMap cm, std::atomic<int>* flags);
+// (n_filtered: where the piece adds the records the handle's tag filter rejected - the reader's DS_TAG_FILTERED counter)
+void parse_part(DecodeTimes* tm, xck_engine* e, HostSoA* sp, int32_t sample, const WalkPart* wp, const ContigMap cm, std::atomic<int>* flags,
+                std::atomic<int64_t>* n_filtered = nullptr);
 // where every piece's records go in the job's SoA block, and the job's batches; returns the chunk's record count, < 0 on error
 int64_t layout_chunk(ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq, int64_t records_before, std::string* err);
 }  // namespace xck

@@ -304,8 +304,8 @@ static inline const uint8_t* aux_skip(const uint8_t* p, const uint8_t* e) {     
     return p <= e ? p : nullptr;
 }
 
-// one record -> SoA slot o (cig_off[o] / seq_off[o] are already set)
-static inline void parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, const uint8_t* p, uint32_t len, int64_t o, int32_t sample,
+// one record -> SoA slot o (cig_off[o] / seq_off[o] are already set); true: the handle's tag filter rejected it
+static inline bool parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, const uint8_t* p, uint32_t len, int64_t o, int32_t sample,
                                 std::vector<InternTable::Item>& names, std::atomic<int>* flags) {
         const uint8_t* end = p + len;
         uint32_t l_name = p[8], n_cig = le16(p + 12), l_seq = le32(p + 16);
@@ -315,18 +315,20 @@ static inline void parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, 
         const uint8_t* q = p + 32;
         const char* qname = (const char*)q; size_t qlen = l_name ? l_name - 1 : 0;
         q += l_name;
-        if (q + (size_t)n_cig * 4 + (l_seq + 1) / 2 + l_seq > end) { flags->fetch_or(1); s.cell[o] = -1; s.umi[o] = XCK_UMI_NONE; return; }
+        if (q + (size_t)n_cig * 4 + (l_seq + 1) / 2 + l_seq > end) { flags->fetch_or(1); s.cell[o] = -1; s.umi[o] = XCK_UMI_NONE; return false; }
         memcpy(s.cigar + s.cig_off[o], q, (size_t)n_cig * 4);
         q += (size_t)n_cig * 4;
         if (dc.want_seq) memcpy(s.seq + s.seq_off[o], q, (l_seq + 1) / 2);
         q += (l_seq + 1) / 2 + l_seq;
         // aux tags: first occurrence wins (htslib bam_aux_get)
-        const uint8_t* cb = nullptr; const uint8_t* ub = nullptr;
-        bool need_cb = dc.use_barcodes, need_ub = dc.use_umi;
+        // (xf: the handle's tag filter, looked for only when it is on - a record without the tag is then walked to its end)
+        const uint8_t* cb = nullptr; const uint8_t* ub = nullptr; const uint8_t* xf = nullptr;
+        bool need_cb = dc.use_barcodes, need_ub = dc.use_umi, need_xf = dc.filter_on;
         const uint8_t* a = q;
-        while ((need_cb || need_ub) && a && a + 3 <= end) {
+        while ((need_cb || need_ub || need_xf) && a && a + 3 <= end) {
             if (need_cb && a[0] == (uint8_t)dc.cell_tag[0] && a[1] == (uint8_t)dc.cell_tag[1]) { cb = a + 2; need_cb = false; }
             else if (need_ub && a[0] == (uint8_t)dc.umi_tag[0] && a[1] == (uint8_t)dc.umi_tag[1]) { ub = a + 2; need_ub = false; }
+            else if (need_xf && a[0] == (uint8_t)dc.filter_tag[0] && a[1] == (uint8_t)dc.filter_tag[1]) { xf = a + 2; need_xf = false; }
             a = aux_skip(a + 2, end);
         }
         int32_t cell = -1;
@@ -336,6 +338,9 @@ static inline void parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, 
                 cell = dc.lookup_cell(v, n);
             }
         } else cell = sample;
+        // the tag filter's verdict overrides the cell: absent, not an integer, negative or cut off -> filtered (parse_dev.h tag_filter_pass)
+        const bool filtered = dc.filter_on && !(xf && aux_skip(xf, end) && tag_filter_pass(xf, dc.filter_mask, dc.filter_value));
+        if (filtered) cell = XCK_CELL_FILTERED;
         s.cell[o] = cell;
         uint64_t key = XCK_UMI_NONE; bool ovf = false;
         if (dc.use_umi) {
@@ -362,17 +367,20 @@ static inline void parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, 
         else { names.push_back(InternTable::Item{InternTable::hash(qname, qlen), qname, (uint32_t)qlen, 0, &s.umi[o], dc.umi_bits}); key = XCK_UMI_NONE; }
         if (ovf) flags->fetch_or(2);
         s.umi[o] = key;
+        return filtered;
 }
 
 // the records of one piece of a chunk (a walk part, or a piece of the serial stitch), whose output slots start at the piece's bases
 // (prefix sums over the pieces: layout_chunk)
-void parse_part(DecodeTimes* tm, xck_engine* e, HostSoA* sp, int32_t sample, const WalkPart* wp, const ContigMap cm, std::atomic<int>* flags) {
+void parse_part(DecodeTimes* tm, xck_engine* e, HostSoA* sp, int32_t sample, const WalkPart* wp, const ContigMap cm, std::atomic<int>* flags,
+                std::atomic<int64_t>* n_filtered) {
     const auto t_parse0 = std::chrono::steady_clock::now();
     struct PAcc { DecodeTimes* tm; std::chrono::steady_clock::time_point t0; ~PAcc() { tm->parse += ns_since(t0); } } pacc{tm, t_parse0};
     const DecodeCfg& dc = e->dec;
     HostSoA& s = *sp;
     std::vector<InternTable::Item> names;
     if (!dc.use_umi) names.reserve(wp->n_out);
+    int64_t nf = 0;                                                       // records of the piece the tag filter rejected
     int64_t o = (int64_t)wp->out_base; uint32_t co = (uint32_t)wp->cig_base, so = (uint32_t)wp->seq_base;
     const RecRef* const rend = wp->recs.data() + wp->recs.size();
     for (const RecRef& rr : wp->recs) {
@@ -380,10 +388,11 @@ void parse_part(DecodeTimes* tm, xck_engine* e, HostSoA* sp, int32_t sample, con
         const int32_t ctg = cm(rr.tid, (int32_t)le32(rr.p + 4));
         if (ctg < 0) continue;
         s.cig_off[o] = co; s.seq_off[o] = so;
-        parse_record(dc, e, s, rr.p, rr.len, o, sample, names, flags);
+        nf += parse_record(dc, e, s, rr.p, rr.len, o, sample, names, flags);
         co += rr.n_cig; if (dc.want_seq) so += (rr.l_seq + 1) / 2;
         o++;
     }
+    if (nf && n_filtered) n_filtered->fetch_add(nf, std::memory_order_relaxed);
     if (s.has_names) {
         // device-names mode: no host table.  One item per kept record of the piece (len 0: the key parse_record wrote is final) and the
         // bytes of the names to intern, packed into the piece's share of the block's trailer; the device table keys them behind the copy

@@ -33,6 +33,7 @@ struct GpuInflateSlot {
     // device walk + parse (csrc/parse_dev.hip): the chunk's record list, per-block counts and bases in device memory; the per-block
     // summaries and the chunk's head in mapped host memory, visible with `done`
     DpRec* d_rec = nullptr; DpCnt* d_cnt = nullptr; DpBase* d_base = nullptr; DpBlockSum *h_sum = nullptr, *a_sum = nullptr; DpHead *h_head = nullptr, *a_head = nullptr;
+    uint32_t* d_nfilt = nullptr;         // device counter of the parse kernel: records the handle's tag filter rejected (zero between two parses: k_filtered_out)
     bool parse = false;                  // reserve the buffers above as well, and leave h_out unwritten (gpu_inflate_slot_launch)
 };
 GpuInflateSlot* gpu_inflate_slot_create(int device, int free_cus, bool verbose);           // nullptr when the device cannot be used; free_cus: CUs its stream never uses

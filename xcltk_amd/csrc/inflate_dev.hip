@@ -584,6 +584,7 @@ static void slot_free_buffers(GpuInflateSlot* s) {
     if (s->h_in) hipHostFree(s->h_in); if (s->h_out) hipHostFree(s->h_out); if (s->d_out) hipFree(s->d_out);
     if (s->h_bl) hipHostFree(s->h_bl); if (s->h_st) hipHostFree(s->h_st);
     if (s->d_rec) hipFree(s->d_rec); if (s->d_cnt) hipFree(s->d_cnt); if (s->d_base) hipFree(s->d_base); if (s->h_sum) hipHostFree(s->h_sum); if (s->h_head) hipHostFree(s->h_head);
+    if (s->d_nfilt) hipFree(s->d_nfilt); s->d_nfilt = nullptr;
     s->d_rec = nullptr; s->d_cnt = nullptr; s->d_base = nullptr; s->h_sum = s->a_sum = nullptr; s->h_head = s->a_head = nullptr;
     s->h_in = s->a_in = s->h_out = s->a_out = s->d_out = nullptr; s->h_bl = s->a_bl = nullptr; s->h_st = s->a_st = nullptr; s->cap_in = s->cap_out = s->cap_bl = 0;
 }
@@ -609,7 +610,8 @@ bool gpu_inflate_slot_reserve(GpuInflateSlot* s, size_t in_bytes, size_t out_byt
     if (ok && s->parse)                                                     // device walk + parse: record list, counts, bases, summaries
         ok = hipMalloc((void**)&s->d_rec, dp_rec_capacity(co + 64) * sizeof(DpRec)) == hipSuccess && hipMalloc((void**)&s->d_cnt, cb * sizeof(DpCnt)) == hipSuccess &&
              hipMalloc((void**)&s->d_base, cb * sizeof(DpBase)) == hipSuccess && host((void**)&s->h_sum, (void**)&s->a_sum, cb * sizeof(DpBlockSum)) &&
-             host((void**)&s->h_head, (void**)&s->a_head, sizeof(DpHead));
+             host((void**)&s->h_head, (void**)&s->a_head, sizeof(DpHead)) &&
+             hipMalloc((void**)&s->d_nfilt, 64) == hipSuccess && hipMemsetAsync(s->d_nfilt, 0, 64, s->stream) == hipSuccess && hipStreamSynchronize(s->stream) == hipSuccess;
     if (!ok) { slot_free_buffers(s); (void)hipGetLastError(); return false; }
     s->cap_in = ci; s->cap_out = co; s->cap_bl = cb;
     return true;

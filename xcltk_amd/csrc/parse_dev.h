@@ -53,7 +53,8 @@ struct DpRec { uint32_t off, slot, cig, seq; };     // a record: byte offset of 
                                                     // CIGAR words / sequence bytes of the block's kept records before it
 struct DpCnt { uint32_t n_rec, n_out, n_cig, n_seq, flags, rec_at, pad[2]; };   // per block, device memory: the walk's counts; rec_at: its first DpRec
 struct DpBase { uint32_t out, cig, seq, pad; };     // per block, device memory: the scan's bases
-struct DpHead { uint32_t walk_flags, parse_flags, n_rec, n_out, n_cig, n_seq, pad[2]; };   // per chunk, mapped host memory
+struct DpHead { uint32_t walk_flags, parse_flags, n_rec, n_out, n_cig, n_seq, n_filtered, pad; };   // per chunk, mapped host memory; n_filtered: records the parse gave XCK_CELL_FILTERED (written by k_filtered_out behind the parse; zero with the tag filter off)
+static_assert(sizeof(DpHead) == 32, "the head record keeps its size");
 // most records n inflated bytes can hold (a record is at least 36 bytes): block b's list starts at out_off / 36, and the lists of
 // neighbouring blocks cannot meet
 XCK_HD inline size_t dp_rec_capacity(size_t out_bytes) { return out_bytes / 36 + 1; }
@@ -109,7 +110,27 @@ struct DpParseCfg {
     int32_t use_barcodes, want_seq, umi_bits, sample;
     char cell_tag[2], umi_tag[2];
     int32_t names;                         // device-names mode (intern_dev.h): no UMI tag is looked for and the umi column is left to k_intern_recs
+    int32_t filter_on;                     // the handle's tag filter (DecodeCfg::filter_*): 0 = the aux scan looks for nothing more and nothing is counted
+    char filter_tag[2], pad[2];
+    uint32_t filter_mask, filter_value;
 };
+
+// The tag filter's verdict on the first occurrence of the tag: t at its type byte, its value bytes inside the record (the caller has
+// skipped over it).  Integer types only; the value widened to 64 bits must lie in 0 .. 2^32 - 1 - which every type but a negative
+// c / s / i does - and agree with `value` under `mask`.  One rule for parse_record (bam_records.cpp) and k_parse: byte loads.
+XCK_HD inline bool tag_filter_pass(const uint8_t* t, uint32_t mask, uint32_t value) {
+    long long v;
+    switch (t[0]) {
+        case 'c': v = (int8_t)t[1]; break;
+        case 'C': v = t[1]; break;
+        case 's': v = (int16_t)(uint16_t)((uint32_t)t[1] | ((uint32_t)t[2] << 8)); break;
+        case 'S': v = (long long)((uint32_t)t[1] | ((uint32_t)t[2] << 8)); break;
+        case 'i': v = (int32_t)((uint32_t)t[1] | ((uint32_t)t[2] << 8) | ((uint32_t)t[3] << 16) | ((uint32_t)t[4] << 24)); break;
+        case 'I': v = (long long)((uint32_t)t[1] | ((uint32_t)t[2] << 8) | ((uint32_t)t[3] << 16) | ((uint32_t)t[4] << 24)); break;
+        default: return false;             // A Z H f B
+    }
+    return v >= 0 && v <= 0xFFFFFFFFll && ((uint32_t)v & mask) == value;
+}
 
 }  // namespace xck
 

@@ -5,7 +5,9 @@
 //            its output goes within the block; per block the counts, the contig runs and the last record's tid / pos.
 //   k_scan   one workgroup: per-block counts -> bases, the chunk's totals and flags.
 //   k_parse  one wave per 64 records of a block, one lane per record: the fixed fields and the aux scan (bam_records.cpp parse_record, restated bit for bit),
-//            then CIGAR and sequence bytes wave-cooperatively - the outputs of 64 consecutive records are contiguous.
+//            then CIGAR and sequence bytes wave-cooperatively - the outputs of 64 consecutive records are contiguous.  With the handle's tag
+//            filter on, the aux scan also looks for that tag, a failing record gets XCK_CELL_FILTERED, and k_filtered_out (one thread,
+//            behind it) hands the chunk's count to its head record.
 // The walk and the scan run on the slot's stream behind k_inflate; the parse is launched by the engine's push path into its staging slot.
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -145,7 +147,7 @@ __device__ inline void coop_copy_words(const uint8_t* __restrict__ u, uint32_t* 
 
 __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, const DpRec* __restrict__ rec, const DpCnt* __restrict__ cnt, const DpBase* __restrict__ base,
                                               DpParseCfg cfg, uint8_t* __restrict__ out, SoaLayout lay, uint32_t n_out_total, uint32_t n_cig_total, uint32_t n_seq_total,
-                                              uint32_t* __restrict__ chunk_flags) {
+                                              DpHead* __restrict__ head, uint32_t* __restrict__ n_filtered) {
     __shared__ uint32_t s_cst[65], s_csrc[64], s_sst[65], s_ssrc[64];
     const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
     uint64_t* c_umi = (uint64_t*)(out + lay.o_umi); int32_t* c_pos = (int32_t*)(out + lay.o_pos); int32_t* c_cell = (int32_t*)(out + lay.o_cell);
@@ -164,6 +166,7 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
         DpRec rr = have ? rl[ri] : DpRec{0, DP_DROPPED, c.n_cig, c.n_seq};
         const bool kept = have && rr.slot != DP_DROPPED;
         uint32_t cig_len = 0, seq_len = 0, cig_src = 0, seq_src = 0;
+        bool filtered = false;
         if (kept) {
             const uint8_t* r = u + rr.off;
             const long long end = (long long)ld32(r - 4);                   // block_size: the record's bytes are r[0, end)
@@ -177,11 +180,13 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
                 q += (long long)n_cig * 4;
                 if (cfg.want_seq) { seq_src = rr.off + (uint32_t)q; seq_len = (l_seq + 1) / 2; }
                 q += (long long)((l_seq + 1) / 2) + l_seq;
-                // aux tags: first occurrence wins; the scan ends when both are found or a value cannot be skipped
-                long long cb = -1, ub = -1; bool need_cb = cfg.use_barcodes != 0, need_ub = cfg.names == 0; long long a = q;   // (names: the key is the read name, k_intern_recs writes it)
-                while ((need_cb || need_ub) && a >= 0 && a + 3 <= end) {
+                // aux tags: first occurrence wins; the scan ends when all that are looked for are found or a value cannot be skipped
+                // (xf: the handle's tag filter, looked for only when it is on - a record without the tag is then walked to its end)
+                long long cb = -1, ub = -1, xf = -1; bool need_cb = cfg.use_barcodes != 0, need_ub = cfg.names == 0, need_xf = cfg.filter_on != 0; long long a = q;   // (names: the key is the read name, k_intern_recs writes it)
+                while ((need_cb || need_ub || need_xf) && a >= 0 && a + 3 <= end) {
                     if (need_cb && r[a] == (uint8_t)cfg.cell_tag[0] && r[a + 1] == (uint8_t)cfg.cell_tag[1]) { cb = a + 2; need_cb = false; }
                     else if (need_ub && r[a] == (uint8_t)cfg.umi_tag[0] && r[a + 1] == (uint8_t)cfg.umi_tag[1]) { ub = a + 2; need_ub = false; }
+                    else if (need_xf && r[a] == (uint8_t)cfg.filter_tag[0] && r[a + 1] == (uint8_t)cfg.filter_tag[1]) { xf = a + 2; need_xf = false; }
                     a = dp_aux_skip(r, a + 2, end);
                 }
                 int32_t cell = -1;
@@ -191,6 +196,8 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
                         cell = dp_lookup_cell(cfg, r + cb + 1, n);
                     }
                 } else cell = cfg.sample;
+                // the tag filter's verdict overrides the cell (parse_record): absent, not an integer, negative or cut off -> filtered
+                if (cfg.filter_on && !(xf >= 0 && dp_aux_skip(r, xf, end) >= 0 && tag_filter_pass(r + xf, cfg.filter_mask, cfg.filter_value))) { cell = XCK_CELL_FILTERED; filtered = true; }
                 c_cell[o] = cell;
                 uint64_t key = XCK_UMI_NONE;
                 if (ub >= 0) {
@@ -209,9 +216,19 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
         __syncthreads();
         if (s_cst[64] <= n_cig_total) coop_copy_words(u, c_cig, s_cst, s_csrc, lane);
         if (cfg.want_seq && s_sst[64] <= n_seq_total) coop_copy(u, c_seq, s_sst, s_ssrc, lane);
+        // the chunk's filtered records: one ballot per wave, one add per wave that has any (the whole wave is here: r0 < c.n_rec is uniform).
+        // The counter is in DEVICE memory (k_filtered_out hands it to the head record): with most waves adding, an atomic per wave on the
+        // head's mapped host memory made the parse of a chunk wait for thousands of PCIe round trips
+        if (cfg.filter_on) {
+            const unsigned long long m = __ballot(filtered);
+            if (lane == 0 && m) atomicAdd(n_filtered, (uint32_t)__popcll(m));
+        }
     }
-    if (fl) atomicOr(chunk_flags, fl);
+    if (fl) atomicOr(&head->parse_flags, fl);
 }
+
+// behind k_parse, tag filter on: the chunk's count -> its head record (mapped host memory), the slot's counter back to zero for its next chunk
+__global__ void k_filtered_out(uint32_t* __restrict__ n_filtered, DpHead* __restrict__ head) { head->n_filtered = *n_filtered; *n_filtered = 0; }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------
 int dev_walk_launch(GpuInflateSlot* s, size_t n_blocks, const DpWalk& w) {
@@ -226,10 +243,11 @@ int dev_walk_launch(GpuInflateSlot* s, size_t n_blocks, const DpWalk& w) {
 int dev_parse_launch(hipStream_t stream, const GpuInflateSlot* s, size_t n_blocks, size_t max_rec, const DpParseCfg& cfg, uint8_t* out, size_t n_out, size_t n_cig, size_t n_seq) {
     if (n_blocks == 0) return 0;
     const SoaLayout lay = soa_layout(n_out + 1, n_cig + 1, cfg.want_seq ? n_seq + 1 : 1);
-    s->h_head->parse_flags = 0;
+    s->h_head->parse_flags = 0; s->h_head->n_filtered = 0;
     const unsigned rounds = (unsigned)std::min<size_t>(std::max<size_t>((max_rec + 63) / 64, 1), 65535);   // (a block holds at most 65536 / 36 records)
     hipLaunchKernelGGL(k_parse, dim3((unsigned)n_blocks, rounds), dim3(64), 0, stream, (const uint8_t*)s->d_out, (const DpRec*)s->d_rec, (const DpCnt*)s->d_cnt, (const DpBase*)s->d_base,
-                       cfg, out, lay, (uint32_t)n_out, (uint32_t)n_cig, (uint32_t)n_seq, &s->a_head->parse_flags);
+                       cfg, out, lay, (uint32_t)n_out, (uint32_t)n_cig, (uint32_t)n_seq, s->a_head, s->d_nfilt);
+    if (cfg.filter_on) hipLaunchKernelGGL(k_filtered_out, dim3(1), dim3(1), 0, stream, s->d_nfilt, s->a_head);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

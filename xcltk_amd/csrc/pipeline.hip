@@ -403,6 +403,7 @@ int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks,
     DpParseCfg pc; memset(&pc, 0, sizeof pc);
     pc.bc = (const DpBcSlot*)st->d_bc; pc.bc_mask = dc.bc_mask; pc.use_barcodes = dc.use_barcodes; pc.want_seq = dc.want_seq; pc.umi_bits = dc.umi_bits; pc.sample = sample;
     memcpy(pc.cell_tag, dc.cell_tag, 2); memcpy(pc.umi_tag, dc.umi_tag, 2);
+    pc.filter_on = dc.filter_on ? 1 : 0; memcpy(pc.filter_tag, dc.filter_tag, 2); pc.filter_mask = dc.filter_mask; pc.filter_value = dc.filter_value;   // (the kernel counts what it filters in the chunk's head record: Pusher::run)
     const bool names = e->names_mode && n_out > 0;
     pc.names = e->names_mode ? 1 : 0;
     if (names) {                                                         // room for the chunk's names: a kept record has 36 bytes besides its name

@@ -55,6 +55,11 @@ struct DecodeCfg {
     bool want_seq = false;
     bool verify_crc = false;             // check the CRC32 of every block the record decoder inflates (XCK_F_VERIFY_CRC, XCK_F_DEVICE_CRC)
     bool crc_on_device = false;          // ... and keep the GPU share of the inflate: the kernel checks its blocks (XCK_F_DEVICE_CRC)
+    // the tag filter (xck_config.filter_tag / XCK_TAG_FILTER): a record whose first filter_tag is not an integer v in 0 .. 2^32 - 1 with
+    // (v & filter_mask) == filter_value gets cell = XCK_CELL_FILTERED (parse_dev.h tag_filter_pass: one rule for host and device)
+    bool filter_on = false;
+    char filter_tag[2] = {0, 0};
+    uint32_t filter_mask = 0, filter_value = 0;
     int  n_threads = 0;
     int64_t max_batch_reads = 0;
     // barcode hash (open addressing over the barcode strings)
@@ -123,12 +128,14 @@ struct Knobs {
     long long gpu_names_arena0 = 64 << 20;  // XCK_GPU_NAMES_ARENA0: first size of its arena (bytes)
     int  names_hash_bits = 0;            // XCK_TEST_NAMES_HASH_BITS: the device table keeps only that many low hash bits (0 = all)
     int  verify_crc = 0;                 // XCK_VERIFY_CRC: 0 = as the flags say, 1 = host (XCK_F_VERIFY_CRC ORed in), 2 = device (XCK_F_DEVICE_CRC)
+    // XCK_TAG_FILTER=TAG:VALUE[/MASK]: 0 = unset, 1 = parsed into the three fields, -1 = malformed (xck_create fails and quotes tag_filter_text)
+    int  tag_filter = 0; char tag_filter_tag[2] = {0, 0}; uint32_t tag_filter_mask = 0, tag_filter_value = 0; std::string tag_filter_text;
     static Knobs from_env();             // api.cpp
 };
 
 // xck_decode_stats counters (include/xck.h), in this order.  A reader counts in its own set; every decode call adds what it counted
 // since the last call to its handle's (bam.cpp fold_decode_stats).
-enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_PARSE_CHUNKS, DS_PARSE_FALLBACKS, DS_NAMES_INTERNED, DS_NAMES_DISTINCT, DS_NAMES_HOST_CHUNKS, DS_N };
+enum DecodeStat { DS_GPU_CHUNKS, DS_GPU_BLOCKS, DS_GPU_LEFT, DS_CRC_DEVICE, DS_CRC_HOST, DS_CRC_MISMATCH_DEVICE, DS_CRC_DISAGREE, DS_GPU_GIVEN_UP, DS_PARSE_CHUNKS, DS_PARSE_FALLBACKS, DS_NAMES_INTERNED, DS_NAMES_DISTINCT, DS_NAMES_HOST_CHUNKS, DS_TAG_FILTERED, DS_N };
 // (DS_NAMES_INTERNED / DS_NAMES_DISTINCT are the device table's own counters: xck_get_decode_stats asks the table)
 
 struct EngineImpl;                       // one GPU pipeline of a handle (engine_impl.h)

@@ -11,6 +11,7 @@ decoder alone and refuses push/finish).
 """
 
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -42,6 +43,16 @@ def resolve_contigs(bam_refs, contig_names):
             if y in tid_of:
                 t2c[tid_of[y]] = ci
     return t2c
+
+
+def _parse_tag_filter(text):
+    """(tag, value, mask) of an XCK_TAG_FILTER value TAG:VALUE[/MASK] (include/xck.h), or None where xck_create will refuse it"""
+    num = lambda x: int(x, 16) if x[:2].lower() == "0x" else int(x, 10)
+    try:
+        value, _, mask = text[3:].partition("/")
+        return (text[:2], num(value), num(mask) if mask else 0xFFFFFFFF) if text[2:3] == ":" else None
+    except ValueError:
+        return None
 
 
 def region_array(regions, cidx, strict=True):
@@ -82,12 +93,15 @@ class Engine(object):
     def __init__(self, mode, contig_names, regions, n_cells, snps=(), barcodes=None,
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
                  incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1,
-                 min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None):
+                 min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None):
         """regions: iterable of (chrom, start1, end1_incl[, name]); snps: iterable of
         (chrom, pos1, ref, alt, ref_hap, alt_hap); chrom names must already be stripped of
         'chr' and present in contig_names.  excl_pairs = (region indices, snp indices): pairs left out of the SNP -> region
         join (region-wise local phasing, xck_config.excl_*).  region_mask (bool per region): regions that are False keep
-        their row index but are not counted by this engine (multi-GPU: another rank owns them)."""
+        their row index but are not counted by this engine (multi-GPU: another rank owns them).  tag_filter = (tag, value) or
+        (tag, value, mask): only records whose first `tag` is an integer v >= 0 with (v & mask) == value count (xck_config.filter_tag;
+        mask defaults to 0xFFFFFFFF; ("xf", 25) keeps what Cell Ranger counted); None leaves it to XCK_TAG_FILTER in the environment.
+        self.tag_filter is the (tag, value, mask) the handle applies, or None."""
         self.lib = capi.load()
         self.mode = mode
         self.contig_names = list(contig_names)
@@ -139,6 +153,21 @@ class Engine(object):
             cfg.n_excl_pairs = len(er)
             cfg.excl_region = er.ctypes.data_as(C.POINTER(C.c_int32))
             cfg.excl_snp = es.ctypes.data_as(C.POINTER(C.c_int32))
+        self.tag_filter = None
+        if tag_filter is not None:
+            if len(tag_filter) not in (2, 3) or not isinstance(tag_filter[0], str):
+                raise ValueError("tag_filter must be (tag, value) or (tag, value, mask)")
+            tag, value = tag_filter[0], int(tag_filter[1])
+            mask = int(tag_filter[2]) if len(tag_filter) == 3 else 0xFFFFFFFF
+            if len(tag) != 2:
+                raise ValueError("tag_filter: the tag must be a 2-character tag")
+            if not (0 <= value <= 0xFFFFFFFF and 0 <= mask <= 0xFFFFFFFF):
+                raise ValueError("tag_filter: value and mask must fit 32 bits")
+            cfg.filter_tag = tag.encode("latin-1")
+            cfg.filter_mask, cfg.filter_value = mask, value
+            self.tag_filter = (tag, value, mask)
+        elif os.environ.get("XCK_TAG_FILTER"):                      # (xck_create checks the knob: a malformed one fails below)
+            self.tag_filter = _parse_tag_filter(os.environ["XCK_TAG_FILTER"])
         cfg.n_threads = int(n_threads)
         cfg.flags = int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0)
         self.cfg = cfg
@@ -479,7 +508,8 @@ class Engine(object):
 
     def decode_stats(self):
         """The BAM decoder's counters since the last reset (xck_get_decode_stats): GPU share of the inflate, CRC checks, chunks
-        walked and parsed on the device, read names interned on the device (XCK_GPU_NAMES)."""
+        walked and parsed on the device, read names interned on the device (XCK_GPU_NAMES), records the tag filter rejected
+        (tag_filtered)."""
         st = capi.DecodeStats()
         st.struct_size = C.sizeof(capi.DecodeStats)
         self._check(self.lib.xck_get_decode_stats(self.h, C.byref(st)), "xck_get_decode_stats")

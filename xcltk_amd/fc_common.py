@@ -778,6 +778,19 @@ def stream_bams(eng, conf, log_prefix="[engine]", contig_mask=None, windows=None
     return n_tot
 
 
+def log_tag_filter(eng, dist, log_prefix="[engine]"):
+    """One log line when the handle filters its reads on a tag (Engine(tag_filter=...), or XCK_TAG_FILTER in the environment): the
+    predicate and the records it rejected, summed over the ranks of a multi-GPU run (then a collective call).  Returns the number or None."""
+    tf = getattr(eng, "tag_filter", None)
+    if not tf:
+        return None
+    n = np.array([eng.decode_stats()["tag_filtered"]], dtype=np.int64)
+    if dist is not None and dist.active:
+        n = dist.all_reduce_np(n)
+    info("%s tag filter %s: (value & 0x%X) == %d: %d record(s) filtered out" % (log_prefix, tf[0], tf[2], tf[1], int(n[0])))
+    return int(n[0])
+
+
 def make_and_count(conf, mode, regions, snps=(), log_prefix="[engine]", gather=None, **extra):
     """Build the engine, stream every BAM (this rank's contigs when running multi-GPU), fold, gather.  Keys that are not ACGT strings (IUPAC UMIs, integer tags, read names in UMI-less runs) are
     interned on the host and take one id each; when the ids outgrow the UMI field of a 64-bit key the decoder stops with
@@ -815,6 +828,7 @@ def make_and_count(conf, mode, regions, snps=(), log_prefix="[engine]", gather=N
         if failure is not None:
             eng.close()
             raise failure
+        log_tag_filter(eng, dist, log_prefix)
         try:
             coo = eng.finish(copy=False)
             if gather is not None:
