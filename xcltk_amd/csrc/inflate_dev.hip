@@ -1,7 +1,9 @@
 // inflate_dev.hip - raw-DEFLATE decoder for BGZF blocks on the GPU (gfx950): one 64-lane wave per block.
 //
 // Replaces, for the share of the chunks the host decoder hands over (csrc/bam.cpp, XCK_GPU_INFLATE), the inflate that pysam / htslib
-// do inside AlignmentFile.fetch (xcltk/rdr/fc/core.py:73-76, utils/sam.py:105-118); the record walk and the field parse stay on the host.
+// do inside AlignmentFile.fetch (xcltk/rdr/fc/core.py:73-76, utils/sam.py:105-118).  With the device parse (XCK_GPU_PARSE, csrc/parse_dev.hip)
+// the record walk and the field parse of these chunks follow on the same stream and the inflated bytes stay in HBM; without it they go
+// back to the host's walk and parse.
 // Why: end to end the engine was bound by the host's BGZF inflate (73 - 85 % of the ingest CPU time on 16 cores,
 // profiles/r02_d_ingest_*.log) while the GPU idled.  BGZF blocks are independent <= 64 KiB deflate streams, so a chunk of
 // ~750 blocks is 750 waves of work.  Inside a block the SYMBOL BOUNDARIES are serial - they are only known after the previous
@@ -14,7 +16,9 @@
 //     code lengths (four symbols per hop, prepared by two rounds of ds_bpermute) finds the offsets where symbols really start, those
 //     lanes store their literals at positions from a prefix sum, and the wave copies the matches
 //     (out[dst + i] = out[dst - dist + i % dist] reads only bytes that already exist, so overlapping matches need no serial loop);
-//   * the finished block goes to the chunk's pinned host block by the same wave (16-byte stores over PCIe).
+//     a round's batched match copy loads in that round and stores in the next, so the wave never sleeps on the round trip;
+//   * the finished block stays in HBM for the device walk (host_out == nullptr); only when the host is to walk the chunk does the same
+//     wave also store it to the chunk's pinned host block (16-byte stores over PCIe).
 // Measured: DESIGN.md section 6, profiles/experiments/gpu_inflate/ (every step of the way, against zlib block by block).
 //   * check_crc: the same epilogue computes the block's CRC-32 and compares it with the footer's (DevBlock.crc).
 // Status per block: 0 = inflated (exactly isize bytes; with check_crc also CRC-checked), non-zero = left to the host decoder
@@ -130,6 +134,11 @@ __device__ bool build_table(Smem& sm, const uint8_t* lens, uint16_t* code, int n
 // loads - about a microsecond - per 32 bits of input.)  Coordinates: byte s of the stream sits at c = s + A of the 4-byte
 // aligned buffer that starts at (stream address - A), A = address & 3.
 constexpr int IN_WIN = 1024;                               // bytes staged per fill (a multiple of 256)
+// A round of the symbol loop starts with its first bit's byte (byte0) at least WIN_MARGIN bytes before the window's end: lane 63 begins at
+// bit 7 + 63 of byte0 at most, i.e. in a dword that starts at byte0 + 8 or earlier, and reads that dword and the two after it (64 stream
+// bits: a length + distance pair is 48) - bytes up to byte0 + 8 + 11.
+constexpr int WIN_MARGIN = 32;
+static_assert(IN_WIN % 256 == 0 && WIN_MARGIN % 4 == 0 && WIN_MARGIN >= 8 + 12 && IN_WIN >= 512 + WIN_MARGIN, "a round's three-dword window reads must stay inside win[]");
 struct BitIn {
     uint32_t pos;                                          // next aligned-buffer coordinate to load (multiple of 2)
     uint32_t wlo;                                          // the window holds coordinates [wlo, wlo + IN_WIN)
@@ -232,9 +241,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     const uint32_t A = (uint32_t)((uintptr_t)sp & 3u);
     const uint32_t* const abase = (const uint32_t*)(sp - A);           // 4-byte aligned view of the stream
     const uint32_t c_end = A + blk.in_len;                             // first coordinate past the stream
-    auto fill = [&](uint32_t wlo) {                                    // all lanes; words past the stream read as zero
+    if (blk.in_len == 0) { if (lane == 0) status[b] = 10; return; }    // (no stream: the stored-header check's status; fill() clamps to the last byte)
+    // all lanes; words past the stream read as zero.  The loads are unconditional (index clamped to the dword the stream's last byte lies in, zero selected afterwards) so
+    // that all of them are in flight before the one wait: the stream is in mapped host memory, every wait is a PCIe round trip.
+    auto fill = [&](uint32_t wlo) {
+        uint32_t w[IN_WIN / 256];
 #pragma unroll
-        for (int j = 0; j < IN_WIN / 256; j++) { const uint32_t c = wlo + (uint32_t)(j * 256 + lane * 4); win[j * 64 + lane] = c < c_end ? abase[c >> 2] : 0u; }
+        for (int j = 0; j < IN_WIN / 256; j++) { const uint32_t c = wlo + (uint32_t)(j * 256 + lane * 4); w[j] = abase[min(c, c_end - 1u) >> 2]; }
+#pragma unroll
+        for (int j = 0; j < IN_WIN / 256; j++) { const uint32_t c = wlo + (uint32_t)(j * 256 + lane * 4); win[j * 64 + lane] = c < c_end ? w[j] : 0u; }
         __builtin_amdgcn_wave_barrier();
     };
     BitIn bi; bi.pos = 0; bi.wlo = 0; bi.bb = 0; bi.bc = 0;            // (lane 0's state; the other lanes carry dead copies)
@@ -344,15 +359,35 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
             uint32_t bitpos = (uint32_t)__builtin_amdgcn_readfirstlane((int)(bi.pos * 8u - (uint32_t)bi.bc));
             uint32_t wlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)bi.wlo);
             uint32_t dirty_lo = 0;                                     // lowest position stored since the last fence (0 = assume everything)
+            // The batched match copy of a round is a load in that round and a store in the NEXT one: what is pending between them is the
+            // loaded byte and its destination per lane (PEND_NONE: this lane has none) and, wave-uniform, the batch's lowest destination
+            // (PEND_NONE: nothing pending).  The store is issued - and only then counted in dirty_lo, so that a match reading those bytes
+            // still finds a fence between that store and its load - before anything later loads output bytes: in the next round ahead
+            // of its literal stores and its match phase (batched load or one-by-one copies alike), and behind the loop for whatever
+            // follows the block (stored copy, next tables, the epilogue's read-back).  A round that ends in an error drops it: the
+            // block's status is non-zero and the host inflates it again.  (Destinations were checked against out_end in their round.)
+            constexpr uint32_t PEND_NONE = 0xffffffffu;
+            uint32_t pend_dst = PEND_NONE, pend_first = PEND_NONE; uint8_t pend_bv = 0;
+            auto retire_pending = [&]() {
+                if (pend_first == PEND_NONE) return;
+                if (pend_dst != PEND_NONE) o0v[pend_dst] = pend_bv;
+                dirty_lo = min(dirty_lo, pend_first);
+                pend_dst = PEND_NONE; pend_first = PEND_NONE;
+            };
             bool eob = false;
             while (!eob) {
                 const uint32_t byte0 = bitpos >> 3;
-                if (byte0 < wlo || byte0 + 32 > wlo + IN_WIN) { wlo = byte0 & ~3u; fill(wlo); }   // (bits lane 0 had buffered may lie before a window the header code moved)
+                if (byte0 < wlo || byte0 + WIN_MARGIN > wlo + IN_WIN) { wlo = byte0 & ~3u; fill(wlo); }   // (bits lane 0 had buffered may lie before a window the header code moved)
                 XCK_PROF_AT(2);
                 const uint32_t wbase = wlo >> 2;
                 const uint32_t bp = bitpos + (uint32_t)lane;
-                uint32_t v;
-                { const uint32_t wi = (bp >> 5) - wbase; v = __builtin_amdgcn_alignbit(win[wi + 1], win[wi], bp & 31u); }   // 32 stream bits from offset bp
+                // 64 stream bits from offset bp in ONE trip to LDS (three dwords, issued together): v for the literal / length code, and the
+                // distance code's bits are cut out of (vhi : v) below instead of being read from the window again behind the first look-up.
+                // Bounds: bp <= 8 * byte0 + 7 + 63, so its dword starts at byte byte0 + 8 at most and the third dword ends at byte0 + 8 + 11;
+                // the refill condition above keeps byte0 + WIN_MARGIN inside the window.
+                uint32_t v, vhi;
+                { const uint32_t wi = (bp >> 5) - wbase, sh = bp & 31u; const uint32_t w0 = win[wi], w1 = win[wi + 1], w2 = win[wi + 2];
+                  v = __builtin_amdgcn_alignbit(w1, w0, sh); vhi = __builtin_amdgcn_alignbit(w2, w1, sh); }
                 // a table entry as one 32-bit LDS read: val | len << 16 | op << 24
                 uint32_t e = ((const uint32_t*)sm.lit)[v & ((1u << D_LIT_TB) - 1)];
                 uint32_t used = (e >> 16) & 0xffu;
@@ -365,9 +400,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                 if (kind == 1) {
                     const uint32_t x = eop & 15u;
                     mlen = (e & 0xffffu) + ((v >> used) & ((1u << x) - 1)); used += x;         // <= 20 bits so far
-                    const uint32_t bp2 = bp + used;
-                    uint32_t v2;
-                    { const uint32_t wi = (bp2 >> 5) - wbase; v2 = __builtin_amdgcn_alignbit(win[wi + 1], win[wi], bp2 & 31u); }
+                    const uint32_t v2 = __builtin_amdgcn_alignbit(vhi, v, used);                // 32 bits from bp + used: a distance code + extra bits is <= 28
                     uint32_t dd = ((const uint32_t*)sm.dist)[v2 & ((1u << D_DIST_TB) - 1)];
                     uint32_t u2 = (dd >> 16) & 0xffu;
                     if (dd >> 31) { dd = ((const uint32_t*)sm.dist)[(dd & 0xffffu) + ((v2 >> D_DIST_TB) & ((1u << ((dd >> 24) & 15u)) - 1))]; u2 = D_DIST_TB + ((dd >> 16) & 0xffu); }
@@ -414,6 +447,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                 const bool is_start = (starts >> lane) & 1;
                 olen = is_start ? olen : 0u;
                 const uint32_t off = op + wave_scan_incl(olen) - olen;  // where this lane's output goes
+                retire_pending();                                       // (its load is a round old; nothing of this round has read output bytes yet)
                 if (is_start && kind == 0) o0v[off] = (uint8_t)e;
                 uint64_t mm = starts & __ballot(kind == 1);
                 if (starts & ~mm) dirty_lo = min(dirty_lo, op);
@@ -444,10 +478,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                                 if (t < ml) { act = true; my_dst = dst + t; my_src = dst - md + (md >= ml ? t : t % md); }   // (overlapping: the pattern repeats)
                             }
                             if (need_fence) { __threadfence_block(); dirty_lo = 0xffffffffu; }   // a source was stored since the last fence
-                            uint8_t bv = 0;
-                            if (act) bv = o0v[my_src];
-                            if (act) o0v[my_dst] = bv;
-                            dirty_lo = min(dirty_lo, first_dst);
+                            // the load goes out now; its store waits for the next round (retire_pending), so the wave decodes and walks
+                            // the next 64 offsets - which read input bits only - while the bytes travel
+                            if (act) { pend_bv = o0v[my_src]; pend_dst = my_dst; }
+                            pend_first = first_dst;
                             mm = 0;
                         }
                     }
@@ -470,6 +504,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                 XCK_PROF_AT(7);
             }
             if (err) break;
+            retire_pending();                                          // the last round's batch: the block's output is complete behind this
             // hand the bit position back to lane 0's serial reader (block headers, stored blocks)
             { const uint32_t pos = (bitpos >> 4) << 1;
               if (pos < wlo || pos + 16 > wlo + IN_WIN) { wlo = pos & ~3u; fill(wlo); }
