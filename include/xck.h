@@ -455,16 +455,28 @@ int  xck_get_result_device(xck_engine* e, xck_result* out);
  *   snp_enabled  [n_snps of the handle] or NULL = all; a disabled SNP feeds no region (the handle then answers as one created with
  *                the list without it; in xck_feature_summary.snp its tallies and verdict stay, its regions are 0).
  *   excl_*       as in xck_config: indices into the NEW regions and the handle's SNP order.
+ *   cell_enabled [n_cells of the handle], one byte per cell, or NULL = all; read only when struct_size covers the field (a caller built
+ *                against the header without it passes the shorter struct and gets every cell, as before).  The call then returns, bit for
+ *                bit, what a fresh handle returns that was fed the same reads with cell = -1 for every disabled cell, under the same
+ *                tables and filters: the disabled cells' molecules are gone from the matrices AND from the pseudo-bulk tallies that
+ *                min_count / min_maf are decided on, so a SNP may pass that failed over all cells, and the other way round.  Column
+ *                indices stay the handle's own; a disabled cell simply has no entries.  The mask belongs to the call, as snp_enabled
+ *                does: a later xck_refold without one answers for all cells again (the handle's own tallies are kept beside the masked
+ *                ones).  xck_get_feature_summary's SNP table (a / c / g / t / n, kept) follows the tallies the last refold counted
+ *                with; xck_snp_counts keeps answering for every cell; xck_group_counts with XCK_GROUP_SRC_RESULT sums what the call
+ *                left.  A mask that enables every cell takes the same path as NULL; one that enables none gives XCK_OK and three
+ *                empty matrices.  The basefc half of a XCK_MODE_BOTH handle is not recounted (its matrix under a cell subset is a
+ *                column selection).
  * Valid on a handle with a BAF pipeline (XCK_MODE_BAF, or the BAF half of XCK_MODE_BOTH, whose out->count is the last finish's,
  * untouched), between a successful xck_finish and the next xck_reset, as often as wanted.  Pointers handed out by an earlier
  * xck_finish / xck_refold / xck_get_result_device die with the call, as at a second finish.  The handle's n_regions, filters and
  * tables follow the call, and xck_get_cell_summary / xck_get_feature_summary recompute their matrix halves, the kept and regions
  * columns of the SNP table included; the read-side counters do not change.
  * XCK_E_STATE before a finish, after a reset, on a decode-only handle, or when a fold of the handle has failed; XCK_E_ARG for a
- * basefc-only handle, a short struct_size, an SNP list whose positions differ, exclusion pairs outside the tables, or too many
+ * basefc-only handle, a struct_size below XCK_REFOLD_CONFIG_SIZE_V1, an SNP list whose positions differ, exclusion pairs outside the tables, or too many
  * regions - the handle is then as it was.  A call that fails inside the fold leaves the handle failed, like a finish: xck_reset. */
 typedef struct xck_refold_config {
-    uint32_t struct_size;       /* sizeof(xck_refold_config)                                 */
+    uint32_t struct_size;       /* sizeof(xck_refold_config); >= XCK_REFOLD_CONFIG_SIZE_V1   */
     int32_t  n_regions;
     const xck_region* regions;
     int32_t  n_snps;
@@ -475,7 +487,9 @@ typedef struct xck_refold_config {
     int32_t  n_excl_pairs;
     const int32_t* excl_region;
     const int32_t* excl_snp;
+    const uint8_t* cell_enabled;   /* appended: everything above is the struct of the first header that had xck_refold */
 } xck_refold_config;
+#define XCK_REFOLD_CONFIG_SIZE_V1 ((uint32_t)offsetof(xck_refold_config, cell_enabled))   /* the struct without cell_enabled: still accepted */
 int  xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out);
 /* The SNP x cell matrices of the finished pileup (additive, as xck_refold is: ABI 3 is unchanged; a caller built against an older header
  * of ABI 3 does not see the symbol and loses nothing): out->ad / dp / oth with row = index of the SNP in the
@@ -484,7 +498,7 @@ int  xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out);
  * table and without a sort.  Per (SNP, cell): AD = molecules that show the SNP's ALT, DP = molecules that show REF or ALT (ALT wins when
  * REF == ALT), OTH = molecules that show another base; zero values are not emitted; a molecule that a gap record claims (an N / D
  * gap over the SNP earlier in fetch order) counts nowhere.  These are the matrices of a handle made with one one-base region per SNP,
- * REF on haplotype 0, ALT on haplotype 1, min_count 1, min_maf 0.  Every SNP of the handle's table counts, whatever snp_enabled mask,
+ * REF on haplotype 0, ALT on haplotype 1, min_count 1, min_maf 0.  Every SNP of the handle's table and every cell counts, whatever snp_enabled or cell_enabled mask,
  * regions, exclusion pairs, haplotype indices, filters or no_dup_hap the handle or its last xck_refold carry; REF / ALT are the
  * handle's current ones (an xck_refold with other alleles is followed).
  * Valid where xck_refold is: on a handle with a BAF pipeline (a XCK_MODE_BOTH handle answers from it), between a successful

@@ -197,13 +197,14 @@ def phased_tables(conf, regions, snps, has_snp):
     return snps, (ex_r, ex_s)
 
 
-def write_matrices(conf, eng, dist, regions, coo):
+def write_matrices(conf, eng, dist, regions, coo, n_cols=None):
     """xcltk.region.tsv and the three .mtx files of one counted table (afc_wrapper, afc_variants and the one-pass `xcltk baf` write
-    through here), and with XCK_CELL_GROUPS their sums per cell group.  Only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113), unless output_all_reg."""
+    through here), and with XCK_CELL_GROUPS their sums per cell group.  Only regions that wrote a DP or OTH line keep a row (baf/fc/core.py:101-113), unless output_all_reg.
+    n_cols: the column count of the cell matrices' headers when `coo` is numbered by a subset of the engine's cells (afc_variants); None = the engine's cells."""
     pre = os.path.join(conf.out_dir, conf.out_prefix)
     fcc.write_matrix_set(eng, dist, regions, coo, conf.output_all_reg, conf.out_region_fn, {"ad": conf.out_ad_fn, "dp": conf.out_dp_fn, "oth": conf.out_oth_fn},
                          ("dp", "oth"), getattr(conf, "cell_groups", None), pre + "groups.tsv",
-                         {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"})
+                         {"ad": pre + "AD.groups.mtx", "dp": pre + "DP.groups.mtx", "oth": pre + "OTH.groups.mtx"}, n_cols=n_cols)
 
 
 def afc_core(conf):

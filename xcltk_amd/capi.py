@@ -69,6 +69,7 @@ class RefoldConfig(C.Structure):
         ("n_snps", C.c_int32), ("snps", C.POINTER(Snp)), ("snp_enabled", C.POINTER(C.c_uint8)),
         ("min_count", C.c_double), ("min_maf", C.c_double), ("no_dup_hap", C.c_int32),
         ("n_excl_pairs", C.c_int32), ("excl_region", C.POINTER(C.c_int32)), ("excl_snp", C.POINTER(C.c_int32)),
+        ("cell_enabled", C.POINTER(C.c_uint8)),          # appended: a struct_size that ends in front of it is still accepted
     ]
 
 

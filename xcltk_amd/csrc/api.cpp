@@ -352,9 +352,12 @@ int xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out) {
     if (!e || !cfg || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
     if (e->n_impl <= 0) return no_engine(e);
     if (!(e->mode & XCK_MODE_BAF)) { e->err = "xck_refold: the handle has no BAF pipeline (a basefc recount needs the reads)"; return XCK_E_ARG; }
-    if (cfg->struct_size < sizeof(xck_refold_config)) { e->err = "xck_refold_config.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (cfg->struct_size < XCK_REFOLD_CONFIG_SIZE_V1) { e->err = "xck_refold_config.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    xck_refold_config full;                                // the fields the caller's struct_size covers; the appended ones NULL
+    memset(&full, 0, sizeof full);
+    memcpy(&full, cfg, std::min<size_t>(cfg->struct_size, sizeof full));
     xck_result r;
-    if (int rc = engine_refold(e->impls[e->n_impl - 1], cfg, &r)) return rc;
+    if (int rc = engine_refold(e->impls[e->n_impl - 1], &full, &r)) return rc;
     if (e->mode == XCK_MODE_BOTH) {                        // the count matrix is the last finish's, untouched
         xck_result c;
         if (int rc = engine_finish(e->impls[0], &c)) return rc;

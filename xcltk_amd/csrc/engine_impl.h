@@ -232,6 +232,13 @@ struct EngineImpl {
     char* d_rf = nullptr; size_t rf_cap = 0;              // sorted regions, exclusion words, SNP mask, contig table, scan block sums
     hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr, ev_r2 = nullptr, ev_r3 = nullptr;   // count pass + scan, fill pass
     double rf_ms_upload = 0, rf_ms_build = 0, rf_ms_regions = 0, rf_ms_total = 0;   // the last refold, for XCK_DEBUG_TIMING and tools/refold_time.py
+    // xck_refold with a cell mask (refold.h refold_mask_tallies): one grow-only block holding the mask as a bit table (one bit per cell), the
+    // first index of every SNP in the sorted hits, the list of the deep SNPs' pieces and the tallies of the enabled cells.  d_tally_cur /
+    // d_cell_bits: the tallies and the bit table the last fold counted with - null = d_tally and all cells (every finish, every unmasked refold)
+    char* d_cm = nullptr; size_t cm_cap = 0;
+    uint32_t* d_tally_cur = nullptr; const uint32_t* d_cell_bits = nullptr;
+    hipEvent_t ev_m0 = nullptr, ev_m1 = nullptr;
+    double rf_ms_mask = 0;                                // the last refold: bit table upload, SNP bounds and masked tallies (0 without a mask)
     // xck_snp_counts (snp_counts.h): a CooCall holding the three blocks [ad | dp | oth] (valid until the next xck_snp_counts / reset),
     // and the sorted SNP -> caller index table on the device
     CooCall sc;
@@ -240,6 +247,9 @@ struct EngineImpl {
     // xck_group_counts (group_counts.h): a CooCall holding the blocks of this pipeline's matrices (valid until the next xck_group_counts / reset)
     CooCall gc;
 };
+
+// the per-SNP tallies the verdicts are decided on: the handle's own, or those of the last masked xck_refold
+static inline const uint32_t* cur_tally(const EngineImpl* im) { return im->d_tally_cur ? im->d_tally_cur : im->d_tally; }
 
 // d_snp_info: ref nibble | alt nibble << 4 | ref_hap << 8 | alt_hap << 9
 static inline uint32_t nib_of(uint8_t ch) {

@@ -120,7 +120,7 @@ static int feature_marginals(EngineImpl* im, const int k) {
         if (int rc = snp_verdicts(im, im->d_kept)) return rc;
         im->h_tally.resize(ns * 5); im->h_kept.resize(ns);
         if (ns) {
-            HIP_TRY(hipMemcpyAsync(im->h_tally.data(), im->d_tally, ns * 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, im->s_comp));
+            HIP_TRY(hipMemcpyAsync(im->h_tally.data(), cur_tally(im), ns * 5 * sizeof(uint32_t), hipMemcpyDeviceToHost, im->s_comp));
             HIP_TRY(hipMemcpyAsync(im->h_kept.data(), im->d_kept, ns * sizeof(uint32_t), hipMemcpyDeviceToHost, im->s_comp));
         }
         if (im->csr_host_stale) {                              // xck_refold built new SNP -> region tables on the device

@@ -8,7 +8,8 @@
 //                 than 64), k_claim (gap records that hold a key earlier in fetch order), k_tally_rows, k_expand (per-SNP filters,
 //                 SNP -> region fan-out), region-level hits partitioned again and classified per item by an LDS hash set
 //                 (k_hap_items; fallback: sort + k_hap_class / k_hap_sum), k_hap_count / k_hap_scatter (AD / DP / OTH -> COO);
-//                 128-bit keys: k_first_read and the sorted path.
+//                 128-bit keys: k_first_read and the sorted path.  xck_refold (refold.h) runs the half behind k_tally_rows again; with a
+//                 cell mask: k_row_bounds, k_tally_rows_cells / k_tally_long_cells (tallies of the enabled cells), k_expand<MASK>.
 //   snp_counts  : the SNP x cell matrices of the finished pileup from the molecule stage alone (snp_counts.h).
 //   group_counts: the row x group sums of the result blocks or of the SNP x cell blocks under a cell -> group mapping (group_counts.h).
 //                 The host steps the two calls share are coo_call.h's.  Copy-out (deliver_words) on the copy stream (xck_finish_async).
@@ -496,6 +497,82 @@ __global__ void __launch_bounds__(256) k_tally_long(const uint8_t* __restrict__ 
     }
 }
 
+// ---- the same tallies over the molecules of the ENABLED cells only (xck_refold with a cell mask, refold.h) ----
+// The mask is a bit table, one bit per cell of the handle.  The walk is the one above - eight lanes per SNP, no atomics on the short
+// path, pieces of TALLY_PIECE for the deep SNPs - but every entry's key is read beside its allele byte (both loads are issued before
+// either is looked at), because the cell is a field of the key.  A block asks the table once per entry it walks (32 SNPs' slices, or
+// one piece of 4096), so a table of up to CM_LDS_WORDS words is copied to LDS first (LDS = true: 10 k cells are 313 words, two loads
+// per thread); a larger one is read where it lies (LDS = false: 16 KB and more per block would cost more than they save).
+constexpr uint32_t CM_LDS_WORDS = 4096;                                  // 131072 cells, 16 KB of LDS
+__device__ __forceinline__ bool cell_on(const uint32_t* __restrict__ bits, uint32_t n_words, uint32_t cell) {
+    const uint32_t w = cell >> 5;
+    return w < n_words && ((bits[w] >> (cell & 31u)) & 1u);              // (a cell past the table - no key holds one - is off, not out of bounds)
+}
+// first index of every SNP in the sorted keys, row_lo[n_rows] = n: one bisection per SNP.  k_first_base leaves the same bounds
+// in workspace 1 on the split path only, so a masked recount rebuilds them from the keys (the idiom of k_blk_bounds).
+template <class K>
+__global__ void k_row_bounds(const K* __restrict__ k, long long n, KeyLayout<K> kl, uint32_t n_rows, unsigned long long* __restrict__ row_lo) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s > n_rows) return;
+    long long lo = 0, hi = n;
+    if (s == n_rows) lo = n;
+    while (lo < hi) { const long long mid = lo + ((hi - lo) >> 1); if (kl.row(k[mid]) < s) lo = mid + 1; else hi = mid; }
+    row_lo[s] = (unsigned long long)lo;
+}
+template <class K, bool LDS>
+__global__ void __launch_bounds__(256) k_tally_rows_cells(const K* __restrict__ k, const uint8_t* __restrict__ al, KeyLayout<K> kl, const unsigned long long* __restrict__ row_lo,
+                                                          uint32_t n_rows, const uint32_t* __restrict__ bits, uint32_t n_words,
+                                                          uint32_t* __restrict__ tally, unsigned long long* __restrict__ long_rows) {
+    __shared__ uint32_t s_bits[LDS ? CM_LDS_WORDS : 1];
+    if (LDS) { for (uint32_t w = threadIdx.x; w < n_words; w += 256) s_bits[w] = bits[w]; __syncthreads(); }
+    const unsigned long long gid = (unsigned long long)blockIdx.x * 256 + threadIdx.x, s = gid >> 3; const uint32_t sub = (uint32_t)gid & 7u;
+    unsigned long long lo = 0, len = 0;
+    if (s < n_rows) { lo = row_lo[s]; len = row_lo[s + 1] - lo; }
+    const bool is_long = len > TALLY_LONG;
+    if (is_long) {
+        if (sub == 0) {
+            const unsigned long long np = (len + TALLY_PIECE - 1) / TALLY_PIECE, at = atomicAdd(&long_rows[0], np);
+            for (unsigned long long q = 0; q < np; q++) long_rows[1 + at + q] = (s << 32) | q;      // (at most len / 2048 entries per SNP: the list holds n / 2048 + 1)
+        }
+        len = 0;
+    }
+    uint32_t c[5] = {0, 0, 0, 0, 0};
+    for (unsigned long long t = sub; t < len; t += 8) {
+        const uint32_t code = al[lo + t]; const K me = k[lo + t];
+        const bool on = LDS ? cell_on(s_bits, n_words, kl.cell(me)) : cell_on(bits, n_words, kl.cell(me));
+        tally_code(on ? code : 0u, c);
+    }
+#pragma unroll
+    for (int q = 0; q < 5; q++) { c[q] += __shfl_xor(c[q], 1); c[q] += __shfl_xor(c[q], 2); c[q] += __shfl_xor(c[q], 4); }
+    if (s < n_rows && !is_long && sub < 5) tally[(size_t)s * 5 + sub] = sub == 0 ? c[0] : sub == 1 ? c[1] : sub == 2 ? c[2] : sub == 3 ? c[3] : c[4];
+}
+template <class K, bool LDS>
+__global__ void __launch_bounds__(256) k_tally_long_cells(const K* __restrict__ k, const uint8_t* __restrict__ al, KeyLayout<K> kl, const unsigned long long* __restrict__ row_lo,
+                                                          const uint32_t* __restrict__ bits, uint32_t n_words,
+                                                          const unsigned long long* __restrict__ long_rows, uint32_t* __restrict__ tally) {
+    __shared__ uint32_t s_bits[LDS ? CM_LDS_WORDS : 1];
+    __shared__ uint32_t s_c[4][5];
+    const unsigned long long n_long = long_rows[0];
+    if (LDS) { if (blockIdx.x < n_long) for (uint32_t w = threadIdx.x; w < n_words; w += 256) s_bits[w] = bits[w]; __syncthreads(); }   // (a block without a piece copies nothing)
+    for (unsigned long long r = blockIdx.x; r < n_long; r += gridDim.x) {
+        const unsigned long long ent = long_rows[1 + r];
+        const size_t s = (size_t)(ent >> 32);
+        const unsigned long long lo = row_lo[s] + (ent & 0xffffffffull) * TALLY_PIECE, hi = min(row_lo[s + 1], lo + TALLY_PIECE);
+        uint32_t c[5] = {0, 0, 0, 0, 0};
+        for (unsigned long long t = lo + threadIdx.x; t < hi; t += 256) {
+            const uint32_t code = al[t]; const K me = k[t];
+            const bool on = LDS ? cell_on(s_bits, n_words, kl.cell(me)) : cell_on(bits, n_words, kl.cell(me));
+            tally_code(on ? code : 0u, c);
+        }
+#pragma unroll
+        for (int q = 0; q < 5; q++) { for (int d = 32; d; d >>= 1) c[q] += __shfl_xor(c[q], d); }
+        if ((threadIdx.x & 63) == 0) { for (int q = 0; q < 5; q++) s_c[threadIdx.x >> 6][q] = c[q]; }
+        __syncthreads();
+        if (threadIdx.x < 5) { const uint32_t v = s_c[0][threadIdx.x] + s_c[1][threadIdx.x] + s_c[2][threadIdx.x] + s_c[3][threadIdx.x]; if (v) atomicAdd(&tally[s * 5 + threadIdx.x], v); }
+        __syncthreads();
+    }
+}
+
 // plp_snp() filters, baf/fc/core.py:238-246.  info: ref nibble | alt nibble << 4 | ref_hap << 8 | alt_hap << 9
 __device__ __forceinline__ bool snp_passes(const uint32_t* tally, const uint32_t* info, uint32_t s, SnpFilter f) {
     const uint32_t* t = tally + (size_t)s * 5;
@@ -525,11 +602,14 @@ __device__ __forceinline__ int allele_side(int nib, uint32_t inf) {
 
 // BAF step 2: expand each surviving (snp, cell, umi, allele) to the regions that contain the SNP
 // (baf/fc/main.py:92-101, core.py:156-166).  COUNT pass sums the fan-out, EMIT pass writes.
-template <class K, bool EMIT, class V>
+// MASK (xck_refold with a cell mask): a molecule of a cell whose bit in cell_bits is clear expands to nothing, in both passes, and
+// `tally` is the tallies of the enabled cells; the table is read where it lies (a block asks 256 times: staging ~300 words would not pay).
+template <class K, bool EMIT, class V, bool MASK = false>
 __global__ __launch_bounds__(JOIN_BLOCK) void k_expand(const K* __restrict__ k, const uint8_t* __restrict__ al, long long n,
                                   KeyLayout<K> kl, const uint32_t* __restrict__ tally, const uint32_t* __restrict__ info,
                                   SnpFilter f, const int32_t* __restrict__ csr_off, const int32_t* __restrict__ csr_reg,
-                                  K* __restrict__ k2, V* __restrict__ v2, unsigned long long* ctl, XBases xb, int pack_shift) {
+                                  K* __restrict__ k2, V* __restrict__ v2, unsigned long long* ctl, XBases xb, int pack_shift,
+                                  const uint32_t* __restrict__ cell_bits = nullptr, uint32_t n_words = 0) {
     // pack_shift >= 0 (emit pass, 64-bit keys): no values are written - the haplotype class goes into two UMI-field bits that no UMI code
     // uses (k_join ORs the UMI codes of the reads it accepts into ctl_umi_or; the host finds the free bits)
     __shared__ uint32_t s_wave[JOIN_BLOCK / 64];
@@ -542,7 +622,7 @@ __global__ __launch_bounds__(JOIN_BLOCK) void k_expand(const K* __restrict__ k, 
         // together with its tallies - three dependent stages instead of five)
         code = al[i]; me = k[i]; s = kl.row(me);
         c0 = csr_off[s]; c1 = csr_off[s + 1];
-        if (code && snp_passes(tally, info, s, f)) cnt = uint32_t(c1 - c0);
+        if (code && (!MASK || cell_on(cell_bits, n_words, kl.cell(me))) && snp_passes(tally, info, s, f)) cnt = uint32_t(c1 - c0);
     }
     uint32_t total;
     uint32_t excl = block_excl_scan(cnt, s_wave, total);
@@ -1206,16 +1286,27 @@ static int first_reads_plain(EngineImpl* im, size_t n, const PileupFold<K>& pf) 
     return 0;
 }
 
-// the k_expand count pass: how many region-level hits every shard will write
-template <class K>
-static int count_region_hits(EngineImpl* im, size_t n, PileupFold<K>& pf) {
+// one k_expand pass over the molecule stage: all cells, or (after xck_refold with a cell mask) the enabled ones under their tallies
+template <class K, bool EMIT>
+static void launch_expand(EngineImpl* im, size_t n, const PileupFold<K>& pf, const XBases& xb, int pack_shift) {
     typedef typename PileupFold<K>::V2 V2;
     KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
     const unsigned gs = (unsigned)((n + 255) / 256);
+    K* k2 = EMIT ? pf.k2 : (K*)nullptr; V2* v2 = EMIT ? pf.v2 : (V2*)nullptr;
+    if (!im->d_cell_bits)
+        hipLaunchKernelGGL((k_expand<K, EMIT, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, im->d_tally, im->d_snp_info,
+                           im->sf, im->d_csr_off, im->d_csr_reg, k2, v2, im->d_ctl, xb, pack_shift);
+    else
+        hipLaunchKernelGGL((k_expand<K, EMIT, V2, true>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, cur_tally(im), im->d_snp_info,
+                           im->sf, im->d_csr_off, im->d_csr_reg, k2, v2, im->d_ctl, xb, pack_shift, im->d_cell_bits, (uint32_t)((im->n_cells + 31) / 32));
+}
+
+// the k_expand count pass: how many region-level hits every shard will write
+template <class K>
+static int count_region_hits(EngineImpl* im, size_t n, PileupFold<K>& pf) {
     XBases xb; memset(&xb, 0, sizeof xb);
     HIP_TRY(hipMemsetAsync(im->d_ctl + CTL_X0, 0, XSHARD * CTL_STRIDE * sizeof(unsigned long long), im->s_comp));
-    hipLaunchKernelGGL((k_expand<K, false, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, im->d_tally, im->d_snp_info,
-                       im->sf, im->d_csr_off, im->d_csr_reg, (K*)nullptr, (V2*)nullptr, im->d_ctl, xb, -1);
+    launch_expand<K, false>(im, n, pf, xb, -1);
     HIP_TRY(hipGetLastError());
     publish_words(im, im->d_ctl + CTL_X0, im->d_hctl + CTL_X0, XSHARD * CTL_STRIDE, 256);
     HIP_TRY(hipGetLastError());
@@ -1267,9 +1358,7 @@ template <class K>
 static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<K>& pf, bool* summed) {
     typedef typename PileupFold<K>::V2 V2;
     int rc;
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
     const int top = im->ubits + im->cbits + im->rbits;
-    const unsigned gs = (unsigned)((n + 255) / 256);
     const size_t n2 = pf.n2;
     XBases xb; memset(&xb, 0, sizeof xb);
     *summed = false;
@@ -1281,8 +1370,7 @@ static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<
             //  XCK_PILEUP_HAP=values: keep the haplotype class in a value word beside the key, as when the UMI field has no two free bits)
             const bool hap_items = im->eng->knobs.pileup_hap != 1;
             const int pack_shift = hap_items && im->eng->knobs.pileup_hap != 2 && pf.used2 + 2 <= im->ubits ? pf.used2 : -1;
-            hipLaunchKernelGGL((k_expand<K, true, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, im->d_tally, im->d_snp_info,
-                               im->sf, im->d_csr_off, im->d_csr_reg, pf.k2, pf.v2, im->d_ctl, xb, pack_shift);
+            launch_expand<K, true>(im, n, pf, xb, pack_shift);
             HIP_TRY(hipGetLastError());
             KeyLayout<unsigned long long> kl8; kl8.ubits = im->ubits; kl8.cbits = im->cbits;
             const HapItemsOut ho{(unsigned long long*)pf.acc, (unsigned long long*)pf.k2, pack_shift};   // (the packed sums use the first half of acc)
@@ -1299,8 +1387,7 @@ static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<
     im->pileup_sort2_path = 2;
     void* tmp2 = im->ws2.get<char>(pf.tmpb2);
     { unsigned long long at = 0; for (int sh = 0; sh < XSHARD; sh++) { xb.base[sh] = at; at += pf.tot2[sh]; } }
-    hipLaunchKernelGGL((k_expand<K, true, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, im->d_tally, im->d_snp_info,
-                       im->sf, im->d_csr_off, im->d_csr_reg, pf.k2, pf.v2, im->d_ctl, xb, -1);
+    launch_expand<K, true>(im, n, pf, xb, -1);
     HIP_TRY(hipGetLastError());
     return sort_run<K, V2>(im, tmp2, pf.tmpb2, pf.k2, pf.k2b, pf.v2, pf.v2b, n2, top);
 }
@@ -1403,6 +1490,7 @@ template <class K>
 static int finish_t(EngineImpl* im) {
     clear_stale_error("finish", im->eng->knobs.debug_timing);
     const size_t n = im->cursor;
+    im->d_tally_cur = nullptr; im->d_cell_bits = nullptr;          // (a finish counts every cell)
     for (int m = 0; m < 4; m++) { im->res_nnz[m] = 0; im->d_res[m] = nullptr; }
     { int64_t acc = 0; for (int sh = 0; sh < NSHARD; sh++) acc += (int64_t)im->h_ctl[ctl_accepted(sh)];
       im->st.n_hits = acc; }                          // accepted pairs (before the LDS de-duplication)
@@ -1474,7 +1562,7 @@ int engine_result_device(EngineImpl* im, xck_result* out) {
 int snp_verdicts(EngineImpl* im, uint32_t* d_kept) {
     const uint32_t n = (uint32_t)im->n_snps_sorted;
     if (!n) return 0;
-    hipLaunchKernelGGL(k_snp_verdict, dim3((n + 255) / 256), dim3(256), 0, im->s_comp, (const uint32_t*)im->d_tally, (const uint32_t*)im->d_snp_info, n, im->sf, d_kept);
+    hipLaunchKernelGGL(k_snp_verdict, dim3((n + 255) / 256), dim3(256), 0, im->s_comp, cur_tally(im), (const uint32_t*)im->d_snp_info, n, im->sf, d_kept);
     HIP_TRY(hipGetLastError());
     return 0;
 }

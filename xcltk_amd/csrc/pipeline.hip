@@ -539,7 +539,7 @@ void engine_destroy(EngineImpl* im) {
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
                      im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept,
-                     im->d_csr_alt, im->d_rf, im->d_sc_perm, im->ws1.base, im->ws2.base };
+                     im->d_csr_alt, im->d_rf, im->d_cm, im->d_sc_perm, im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }
     for (int m = 0; m < 4; m++) if (im->h_res[m]) hipHostFree(im->h_res[m]);
@@ -552,7 +552,7 @@ void engine_destroy(EngineImpl* im) {
     if (im->ev_c1) hipEventDestroy(im->ev_c1);
     if (im->ev_f1) hipEventDestroy(im->ev_f1);
     if (im->ev_f2) hipEventDestroy(im->ev_f2);
-    for (hipEvent_t ev : { im->ev_r0, im->ev_r1, im->ev_r2, im->ev_r3 }) if (ev) hipEventDestroy(ev);
+    for (hipEvent_t ev : { im->ev_r0, im->ev_r1, im->ev_r2, im->ev_r3, im->ev_m0, im->ev_m1 }) if (ev) hipEventDestroy(ev);
     if (im->s_copy) hipStreamDestroy(im->s_copy);
     if (im->s_comp) hipStreamDestroy(im->s_comp);
     delete im;

@@ -193,6 +193,60 @@ static int refold_build_tables(EngineImpl* im, const xck_refold_config* cfg, boo
     return 0;
 }
 
+// The cell mask of a call as a bit table, one bit per cell of the handle; empty = the call counts every cell (a NULL mask, or one that
+// enables all: both take the unmasked kernels).
+static std::vector<uint32_t> refold_cell_bits(const EngineImpl* im, const uint8_t* cell_enabled) {
+    std::vector<uint32_t> w;
+    if (!cell_enabled) return w;
+    bool all = true;
+    for (int c = 0; c < im->n_cells; c++) all = all && cell_enabled[c];
+    if (all) return w;
+    w.assign(((size_t)im->n_cells + 31) / 32, 0u);
+    for (int c = 0; c < im->n_cells; c++) if (cell_enabled[c]) w[(size_t)c >> 5] |= 1u << (c & 31);
+    return w;
+}
+
+// Per-SNP tallies of the molecules of the enabled cells, from what the molecule stage left (mol_keys / mol_al): the bit table goes up,
+// one bisection per SNP finds its slice of the sorted hits (k_first_base's bounds exist on the split path only, and workspace 1 is not
+// this call's to take from), and the masked forms of k_tally_rows / k_tally_long count.  Everything lives in one grow-only block of its
+// own (d_cm), so the handle's tallies over all cells stay for the next call without a mask.
+template <class K>
+static int refold_mask_tallies(EngineImpl* im, const std::vector<uint32_t>& bits) {
+    const size_t ns = std::max<size_t>((size_t)im->n_snps_sorted, 1), n = im->mol_n, nw = bits.size();
+    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    ScratchLayout L;
+    const int i_bits = L.add(nw * 4), i_lo = L.add((ns + 1) * 8), i_long = L.add((n / (size_t)TALLY_LONG + 2) * 8), i_tally = L.add(ns * 5 * 4);
+    if (int rc = refold_grow(im, (void**)&im->d_cm, &im->cm_cap, L.total())) return rc;
+    if (!im->ev_m0) { HIP_TRY(hipEventCreate(&im->ev_m0)); HIP_TRY(hipEventCreate(&im->ev_m1)); }
+    uint32_t* d_bits = L.at<uint32_t>(im->d_cm, i_bits); unsigned long long* row_lo = L.at<unsigned long long>(im->d_cm, i_lo);
+    unsigned long long* long_rows = L.at<unsigned long long>(im->d_cm, i_long); uint32_t* tally = L.at<uint32_t>(im->d_cm, i_tally);
+    HIP_TRY(hipEventRecord(im->ev_m0, im->s_comp));
+    HIP_TRY(hipMemcpyAsync(d_bits, bits.data(), nw * 4, hipMemcpyHostToDevice, im->s_comp));
+    HIP_TRY(hipMemsetAsync(tally, 0, ns * 5 * sizeof(uint32_t), im->s_comp));          // (the pieces of a deep SNP add to its counters)
+    HIP_TRY(hipMemsetAsync(long_rows, 0, sizeof(unsigned long long), im->s_comp));
+    if (n) {
+        const K* keys = (const K*)im->mol_keys;
+        hipLaunchKernelGGL((k_row_bounds<K>), dim3((unsigned)((ns + 1 + 255) / 256)), dim3(256), 0, im->s_comp, keys, (long long)n, kl, (uint32_t)ns, row_lo);
+        const dim3 g_rows((unsigned)((ns * 8 + 255) / 256)), g_long(1024);
+        if (nw <= CM_LDS_WORDS) {
+            hipLaunchKernelGGL((k_tally_rows_cells<K, true>), g_rows, dim3(256), 0, im->s_comp, keys, (const uint8_t*)im->mol_al, kl, (const unsigned long long*)row_lo, (uint32_t)ns,
+                               (const uint32_t*)d_bits, (uint32_t)nw, tally, long_rows);
+            hipLaunchKernelGGL((k_tally_long_cells<K, true>), g_long, dim3(256), 0, im->s_comp, keys, (const uint8_t*)im->mol_al, kl, (const unsigned long long*)row_lo,
+                               (const uint32_t*)d_bits, (uint32_t)nw, (const unsigned long long*)long_rows, tally);
+        } else {
+            hipLaunchKernelGGL((k_tally_rows_cells<K, false>), g_rows, dim3(256), 0, im->s_comp, keys, (const uint8_t*)im->mol_al, kl, (const unsigned long long*)row_lo, (uint32_t)ns,
+                               (const uint32_t*)d_bits, (uint32_t)nw, tally, long_rows);
+            hipLaunchKernelGGL((k_tally_long_cells<K, false>), g_long, dim3(256), 0, im->s_comp, keys, (const uint8_t*)im->mol_al, kl, (const unsigned long long*)row_lo,
+                               (const uint32_t*)d_bits, (uint32_t)nw, (const unsigned long long*)long_rows, tally);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(im->ev_m1, im->s_comp));
+    HIP_TRY(hipStreamSynchronize(im->s_comp));                                          // (`bits` is the caller's local)
+    im->d_tally_cur = tally; im->d_cell_bits = d_bits;
+    return 0;
+}
+
 int engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out) {
     xck_engine* e = im->eng;
     if (im->fold_failed) { e->err = "xck_refold: an earlier fold of this handle failed (call xck_reset)"; return XCK_E_STATE; }
@@ -202,9 +256,16 @@ int engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out)
     const auto t0 = std::chrono::steady_clock::now();
     if (im->copy_pending) { HIP_TRY(hipStreamSynchronize(im->s_copy)); im->copy_pending = false; }   // the last fold's copy-out reads workspace 2
     clear_stale_error("refold", e->knobs.debug_timing);
+    const std::vector<uint32_t> cell_bits = refold_cell_bits(im, cfg->cell_enabled);
     bool touched = false;
     int rc = refold_build_tables(im, cfg, &touched);
     if (rc) { if (touched || rc != XCK_E_NOMEM) im->fold_failed = true; hipStreamSynchronize(im->s_comp); return rc; }
+    im->d_tally_cur = nullptr; im->d_cell_bits = nullptr; im->rf_ms_mask = 0;      // the mask is the call's: without one every cell counts again
+    if (!cell_bits.empty()) {
+        rc = im->key_bits == 64 ? refold_mask_tallies<uint64_t>(im, cell_bits) : refold_mask_tallies<u128>(im, cell_bits);
+        if (rc) { im->fold_failed = true; hipStreamSynchronize(im->s_comp); return rc; }
+        float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, im->ev_m0, im->ev_m1)); im->rf_ms_mask = ms;
+    }
     im->n_regions = cfg->n_regions;
     im->sf.min_count = cfg->min_count <= 0.0 ? 0 : (int32_t)std::min(2147483647.0, std::ceil(cfg->min_count));
     im->sf.min_maf = cfg->min_maf;
@@ -225,8 +286,8 @@ int engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out)
     if ((rc = fold())) { im->fold_failed = true; hipStreamSynchronize(im->s_comp); hipStreamSynchronize(im->s_copy); return rc; }
     { float a = 0, b = 0; HIP_TRY(hipEventElapsedTime(&a, im->ev_r0, im->ev_r1)); HIP_TRY(hipEventElapsedTime(&b, im->ev_r2, im->ev_r3)); im->rf_ms_build = (double)a + b; }
     im->rf_ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (e->knobs.debug_timing) fprintf(stderr, "[xck] refold: total %.3f ms (host clock to the stream synchronise): table upload %.3f, builder kernels + scan %.3f, region stage %.3f\n",
-                                       im->rf_ms_total, im->rf_ms_upload, im->rf_ms_build, im->rf_ms_regions);
+    if (e->knobs.debug_timing) fprintf(stderr, "[xck] refold: total %.3f ms (host clock to the stream synchronise): table upload %.3f, builder kernels + scan %.3f, region stage %.3f, cell mask %.3f\n",
+                                       im->rf_ms_total, im->rf_ms_upload, im->rf_ms_build, im->rf_ms_regions, im->rf_ms_mask);
     im->copy_pending = true;
     return result_host(im, out);
 }

@@ -379,12 +379,20 @@ class Engine(object):
             out.update(ad=res.ad.to_numpy(copy), dp=res.dp.to_numpy(copy), oth=res.oth.to_numpy(copy))
         return out
 
-    def refold(self, regions, snps=None, snp_enabled=None, min_count=1, min_maf=0, no_dup_hap=True, excl_pairs=None, copy=True):
+    def refold(self, regions, snps=None, snp_enabled=None, min_count=1, min_maf=0, no_dup_hap=True, excl_pairs=None, copy=True, cell_enabled=None):
         """Recount the pileup of the last finish() under new tables and filters, without the reads (xck_refold): returns what
         finish() returns, as a fresh engine would that was made with these tables and fed the same reads.  regions as for the
         constructor (a chrom outside contig_names gives an empty row); snps=None keeps the engine's, otherwise the same SNPs index
         by index with their own ref / alt / haplotype columns; snp_enabled (bool per SNP): False feeds no region; excl_pairs =
-        (region indices into the NEW regions, snp indices).  Valid between finish() and reset(), as often as wanted."""
+        (region indices into the NEW regions, snp indices).  cell_enabled (bool per cell of the engine; ValueError for another length):
+        the recount is over these cells only - the matrices AND the per-SNP tallies min_count / min_maf are decided on - and equals
+        what a fresh engine returns that saw the same reads with cell = -1 for the others; columns keep the engine's numbering.  The
+        mask holds for this call: the next refold() without one counts every cell again, and snp_counts() always does.  Valid
+        between finish() and reset(), as often as wanted."""
+        if cell_enabled is not None:
+            cen = np.ascontiguousarray(np.asarray(cell_enabled, dtype=bool).astype(np.uint8))
+            if cen.ndim != 1 or len(cen) != self.n_cells:
+                raise ValueError("cell_enabled needs one entry per cell of the engine (%d), got %s" % (self.n_cells, cen.shape))
         cidx = {n: i for i, n in enumerate(self.contig_names)}
         regions = list(regions)
         reg = region_array(regions, cidx, strict=False)
@@ -406,6 +414,9 @@ class Engine(object):
                 raise ValueError("snp_enabled needs one entry per SNP of the engine")
             cfg.snp_enabled = en.ctypes.data_as(C.POINTER(C.c_uint8))
             keep.append(en)
+        if cell_enabled is not None:
+            cfg.cell_enabled = cen.ctypes.data_as(C.POINTER(C.c_uint8))
+            keep.append(cen)
         cfg.min_count = float(min_count)
         cfg.min_maf = float(min_maf)
         cfg.no_dup_hap = 1 if no_dup_hap else 0

@@ -394,17 +394,18 @@ def write_group_matrices(eng, dist, groups, names_fn, mtx_fns, rm, n_rows_out, s
         write_mtx(eng, dist, fn, got[k], rm, n_rows_out, n_cols=len(names))
 
 
-def write_matrix_set(eng, dist, regions, coo, all_reg, region_fn, mtx_fns, presence, groups, group_names_fn, group_mtx_fns, log_prefix="[engine]"):
+def write_matrix_set(eng, dist, regions, coo, all_reg, region_fn, mtx_fns, presence, groups, group_names_fn, group_mtx_fns, log_prefix="[engine]", n_cols=None):
     """One matrix set: the region file (writer rank), the .mtx files of mtx_fns (an ordered {key of coo: path}), and with XCK_CELL_GROUPS
     the same rows summed per cell group (write_group_matrices).  A region keeps a row when a matrix named in `presence` wrote a line
     for it - ("count",) for basefc (rdr/fc/core.py:118-124), ("dp", "oth") for BAF (baf/fc/core.py:101-113) - or, all_reg, always:
-    its row is then its input line number.  Sharded output: collective calls, on every rank."""
+    its row is then its input line number.  n_cols: the column count of the cell matrices' headers (None = the engine's cells).
+    Sharded output: collective calls, on every rank."""
     rm = output_row_map(dist, len(regions), all_reg, *[coo[k][0] for k in presence])
     n_rows_out = int(rm.max()) if len(rm) else 0
     if is_writer_rank():
         write_region_tsv(region_fn, regions, rm)
     for k, fn in mtx_fns.items():
-        write_mtx(eng, dist, fn, coo[k], rm, n_rows_out)
+        write_mtx(eng, dist, fn, coo[k], rm, n_rows_out, n_cols=n_cols)
     write_group_matrices(eng, dist, groups, group_names_fn, group_mtx_fns, rm, n_rows_out, log_prefix=log_prefix)
 
 
