@@ -48,22 +48,26 @@ def _knobs(env, **kv):
         env["XCK_" + k] = str(v)
 
 
-def _engine(mode, names, regions, snps, n_cells, batches, repeat=False, **filt):
-    """The engine alone -> (matrices, stats); repeat: then reset, push and finish again on the same handle -> (first, second, stats)."""
+def _engine(mode, names, regions, snps, n_cells, batches, repeat=False, second=None, **filt):
+    """The engine alone -> (matrices, stats); repeat: then reset, push and finish again on the same handle -> (first, second, stats).
+    second: the batches of that second round when they are not the first's; a pileup handle then also recounts the second finish
+    with its own tables (refold) -> (first, second, refolded or None, (stats of the first round, of the second))."""
     kw = dict(KW); kw.update(filt)
     eng = Engine(mode, names, regions, n_cells, snps=snps if mode == BAF else (), **kw)
     try:
-        outs = []
-        for _ in range(2 if repeat else 1):
-            for b, _keep in batches:
+        outs, sts = [], []
+        for rnd in range(2 if repeat else 1):
+            if rnd:
+                eng.reset()
+            for b, _keep in (second if rnd and second is not None else batches):
                 eng.push(b)
             outs.append({k: tuple(np.array(a) for a in v) for k, v in eng.finish().items()})
-            st = eng.stats()
-            if repeat:
-                eng.reset()
+            sts.append(eng.stats())
+        if second is not None:
+            outs.append({k: tuple(np.array(a) for a in v) for k, v in eng.refold(regions).items()} if mode == BAF else None)
     finally:
         eng.close()
-    return tuple(outs) + (st,)
+    return tuple(outs) + ((tuple(sts),) if second is not None else (sts[-1],))
 
 
 def _oracle(mode, names, regions, snps, n_cells, batches, **filt):
@@ -358,6 +362,48 @@ def test_sort_fold_digits_under_a_giant_run(rc_bits, n_regions, n_cells, fold_en
         util.assert_coo_equal(first, exp, ["count"])
         util.assert_coo_equal(second, exp, ["count"])
         assert st["fold_path"] == 2 and (st["key_bits"], st["umi_bits"]) == (64, ub), kind
+
+
+# ----------------------------------------------------------------------------- 6b. a workspace freed and allocated anew between two finishes
+@functools.lru_cache(maxsize=None)
+def _regrow_case(mode):
+    """-> names, regions, snps, n_cells, small batches, large batches, oracle of the large ones, lower bound on the large input's keys.
+    basefc: 120 genes, 100 reads, then 650 k; the distinct (region, cell, UMI) the oracle counts bound the keys in HBM from below.
+    pileup: 40 000 SNPs on the same genes (one per ~100 bases of gene, so that 250 k reads leave the hits the bound asks for), 100 reads,
+    then 250 k; the bound: the molecules whose first read shows a base (DP + OTH with one one-base region per SNP, REF on haplotype 0
+    and ALT on 1), each of which is at least one hit with a base."""
+    n_cells = 2000
+    regions, snps, names = soa.make_tables(120, 0 if mode == FC else 40000, [1500000], seed=73, max_len=150000)
+    small, large = ([util.batch_from_dict(b) for b in soa.gen_reads(regions, names, n, n_cells, seed=s, with_seq=mode == BAF)] for n, s in ((100, 5), (650000 if mode == FC else 250000, 74)))
+    exp = _oracle(mode, names, regions, snps, n_cells, large)
+    if mode == FC:
+        return names, regions, snps, n_cells, small, large, exp, int(exp["count"][2].sum())
+    one = _oracle(mode, names, [(s[0], s[1], s[1], "s%d" % i) for i, s in enumerate(snps)], [(s[0], s[1], s[2], s[3], 0, 1) for s in snps], n_cells, large)
+    return names, regions, snps, n_cells, small, large, exp, int(one["dp"][2].sum() + one["oth"][2].sum())
+
+
+@pytest.mark.parametrize("knobs", [dict(), dict(FOLD="sort"), dict(PILEUP_SORT="radix")], ids=["default", "fold-sort", "pileup-radix"])
+@pytest.mark.parametrize("mode", [FC, BAF], ids=["fc", "baf"])
+def test_workspaces_grow_between_two_finishes_of_one_handle(mode, knobs, fold_env):
+    """One handle: a first input that leaves at most 1000 keys, finish, reset, then one that leaves at least 400 k keys (basefc) /
+    200 k hits with a base (pileup), finish.  A workspace keeps need + need / 4 + 1 MiB bytes; workspace 1 of the second finish holds at
+    least 8 bytes per basefc key and 16 per pileup hit, 3.2 MB, against at most 2.3 MB kept from the first: every fold's arenas are
+    freed and allocated anew between the two, under the default folds, the radix-sort fold and the library sort of the pileup.  The
+    second result equals the oracle on the second input alone, and on the pileup handle a refold with the handle's own tables equals
+    that finish (the region stage begins workspace 2 again on what the molecule stage left in workspace 1)."""
+    names, regions, snps, n_cells, small, large, exp, keys_at_least = _regrow_case(mode)
+    assert keys_at_least >= (400000 if mode == FC else 200000)
+    _knobs(fold_env, **knobs)
+    first, second, refolded, (st1, st2) = _engine(mode, names, regions, snps, n_cells, small, repeat=True, second=large)
+    print("mode %d %s: n_hits_unique %d then %d (bound from the oracle %d)" % (mode, knobs, st1["n_hits_unique"], st2["n_hits_unique"], keys_at_least))
+    assert 0 < st1["n_hits_unique"] <= 1000 and st2["n_hits_unique"] >= keys_at_least
+    assert all(len(first[m][0]) > 0 for m in MATS[mode])
+    util.assert_coo_equal(second, exp, MATS[mode])
+    if mode == FC:
+        assert st2["fold_path"] == 2 or knobs.get("FOLD") != "sort"
+    else:
+        assert (st2["pileup_sort_path"], st2["pileup_sort2_path"]) == (2, 2) or knobs.get("PILEUP_SORT") != "radix"
+        util.assert_coo_equal(refolded, second, MATS[BAF])
 
 
 # ----------------------------------------------------------------------------- 7. coordinates at the top of BAM's range

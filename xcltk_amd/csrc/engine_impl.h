@@ -11,6 +11,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "xck_internal.h"
+#include "fold_ws.h"                     // Arena, and the fold workspaces cut from it
 
 namespace xck {
 typedef unsigned __int128 u128;
@@ -120,17 +121,6 @@ struct BatchSlot {
     uint64_t* umi = nullptr; uint32_t* cig_off = nullptr; uint32_t* cigar = nullptr; uint32_t* seq_off = nullptr; uint8_t* seq = nullptr;
     size_t cap_reads = 0, cap_cig = 0, cap_seq = 0;          // reads (the seven per-read columns); bytes; bytes
     bool busy = false;
-};
-
-// grow-only device workspace: finish() sub-allocates from it instead of hipMalloc/hipFree per call
-struct Arena {
-    char* base = nullptr; size_t cap = 0, off = 0;
-    template <class T> T* get(size_t n) {
-        off = (off + 255) & ~size_t(255);
-        T* p = reinterpret_cast<T*>(base + off);
-        off += std::max<size_t>(n, 1) * sizeof(T);
-        return off <= cap ? p : nullptr;
-    }
 };
 
 // State of one derived-matrix call (xck_snp_counts, xck_group_counts; the host steps that work on it are in coo_call.h).  Buffers of

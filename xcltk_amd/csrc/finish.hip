@@ -34,6 +34,23 @@ static __global__ void k_publish(const unsigned long long* __restrict__ src, uns
 void publish_words(EngineImpl* im, const unsigned long long* src, unsigned long long* host_alias, int n, int threads) {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(threads), 0, im->s_comp, src, host_alias, n);
 }
+// ... and waited for: control words [at, at + n) as the compute stream leaves them, h = their place in the host mirror.  Also reports
+// a failed launch of the kernels queued just before.
+static int read_ctl_words(EngineImpl* im, int at, int n, const unsigned long long*& h) {
+    publish_words(im, im->d_ctl + at, im->d_hctl + at, n, n > 64 ? 256 : 64);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(im->s_comp));
+    h = im->h_ctl + at;
+    return 0;
+}
+
+template <class K> static KeyLayout<K> key_layout(const EngineImpl* im) { KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits; return kl; }
+// first packed index of every shard slice holding cnt[shard] entries
+static ShardSpan shard_span(const unsigned long long* cnt) {
+    ShardSpan sp; sp.start[0] = 0;
+    for (int sh = 0; sh < NSHARD; sh++) sp.start[sh + 1] = sp.start[sh] + cnt[sh];
+    return sp;
+}
 
 // exclusive scan of one uint32 per thread over a 256-thread block; returns block total in `total`
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* s_wave, uint32_t& total) {
@@ -985,33 +1002,31 @@ static int copy_out(EngineImpl* im, int m, int32_t* d_o, size_t total) {
 }
 
 // ordered compaction of the runs' AD / DP / OTH (hap: per-run sums, n staging entries) into the COO blocks of matrices m0..m0+2:
-// counts and scans of all three first, ONE read-back of the totals, then the scatter and the copy-out
+// counts and scans of all three first, ONE read-back of the totals, then the scatter and the copy-out.  The COO blocks are taken
+// exactly, at the place `ws` reserved for their upper bound (w.coo_at).
+static const char* const WS_REGION_FULL = "workspace exhausted (region-level hits)";
 template <class K>
-static int compact_coo(EngineImpl* im, Arena& ws, const HapSrc& hap, const K* keys, size_t n, KeyLayout<K> kl, int m0) {
+static int compact_coo(EngineImpl* im, Arena& ws, const RegionWs& w, const HapSrc& hap, const K* keys, size_t n, KeyLayout<K> kl, int m0) {
     const int nm = 3;
     size_t nb = (n + CP_TILE - 1) / CP_TILE;
-    uint32_t* d_blk = ws.get<uint32_t>(nb * nm); unsigned long long* d_off = ws.get<unsigned long long>(nb * nm);
-    if (!d_blk || !d_off) { im->eng->err = "workspace exhausted (compaction)"; return XCK_E_NOMEM; }
-    unsigned long long* d_tot = im->d_ctl + CTL_X0;                       // the k_expand words are free again at this point
-    hipLaunchKernelGGL(k_hap_count, dim3(nb), dim3(CP_BLOCK), 0, im->s_comp, hap, d_blk);
-    hipLaunchKernelGGL(k_cp_scan, dim3(nm), dim3(1024), 0, im->s_comp, d_blk, (long long)nb, d_off, d_tot);
-    HIP_TRY(hipGetLastError());
-    publish_words(im, d_tot, im->d_hctl + CTL_X0, nm, 64);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
+    const unsigned long long* h_tot;
+    hipLaunchKernelGGL(k_hap_count, dim3(nb), dim3(CP_BLOCK), 0, im->s_comp, hap, w.d_blk);
+    hipLaunchKernelGGL(k_cp_scan, dim3(nm), dim3(1024), 0, im->s_comp, w.d_blk, (long long)nb, w.d_off, im->d_ctl + CTL_X0);   // the k_expand words are free again at this point
+    if (int rc = read_ctl_words(im, CTL_X0, nm, h_tot)) return rc;
     CooOut3 out; memset(&out, 0, sizeof out);
     bool any = false;
+    ws.off = w.coo_at;
     for (int y = 0; y < nm; y++) {
-        const size_t total = im->h_ctl[CTL_X0 + y];
+        const size_t total = h_tot[y];
         im->res_nnz[m0 + y] = total; im->d_res[m0 + y] = nullptr; out.total[y] = total;
         if (!total) continue;
         int rc = res_reserve(im, m0 + y, total); if (rc) return rc;
         out.o[y] = ws.get<int32_t>(total * 3);
-        if (!out.o[y]) { im->eng->err = "workspace exhausted (COO)"; return XCK_E_NOMEM; }
+        if (!out.o[y]) { im->eng->err = WS_REGION_FULL; return XCK_E_NOMEM; }   // (more non-zeros than runs: the bound the block was reserved at is broken)
         any = true;
     }
     if (!any) return 0;
-    hipLaunchKernelGGL((k_hap_scatter<K>), dim3(nb), dim3(CP_BLOCK), 0, im->s_comp, hap, keys, kl, (const unsigned long long*)d_off, out);
+    hipLaunchKernelGGL((k_hap_scatter<K>), dim3(nb), dim3(CP_BLOCK), 0, im->s_comp, hap, keys, kl, (const unsigned long long*)w.d_off, out);
     HIP_TRY(hipGetLastError());
     // copy-out: large blocks go through copy_out() (copy stream); the small ones share one store kernel into mapped pinned memory
     CopySeg3 sg; memset(&sg, 0, sizeof sg); size_t mx = 0;
@@ -1032,22 +1047,22 @@ static int compact_coo(EngineImpl* im, Arena& ws, const HapSrc& hap, const K* ke
 
 // basefc: sorted keys -> COO (row, col, count of distinct keys) without a dense intermediate
 constexpr int FOLD_GIANT = 1;              // fold_coo(): a (row, cell) run too long for the hash fold - redo on fully sorted keys
+static const char* const WS_RADIX_FULL = "workspace exhausted (radix-sort fold)";
 template <class K>
-static int fold_coo(EngineImpl* im, Arena& ws, const K* keys, size_t n, KeyLayout<K> kl, int m, int sorted_from = 0) {   // sorted_from: lowest key bit the sort covered
+static int fold_coo(EngineImpl* im, Arena& ws, const RadixFoldWs& w, const K* keys, size_t n, KeyLayout<K> kl, int m, int sorted_from = 0) {   // sorted_from: lowest key bit the sort covered
     size_t nb = (n + FD_TILE - 1) / FD_TILE;
-    uint32_t* d_blk = ws.get<uint32_t>(nb); unsigned long long* d_off = ws.get<unsigned long long>(nb);
-    if (!d_blk || !d_off) { im->eng->err = "workspace exhausted (fold)"; return XCK_E_NOMEM; }
+    uint32_t* d_blk = w.d_blk; unsigned long long* d_off = w.d_off;
+    const unsigned long long* h;
     hipLaunchKernelGGL((k_fold_heads<K>), dim3(nb), dim3(FD_BLOCK), 0, im->s_comp, keys, (long long)n, kl, d_blk);
     hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, im->s_comp, d_blk, (long long)nb, d_off, im->d_ctl + CTL_SCRATCH);
-    publish_words(im, im->d_ctl + CTL_SCRATCH, im->d_hctl + CTL_SCRATCH, 1, 64);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    size_t total = im->h_ctl[CTL_SCRATCH];
+    int rc = read_ctl_words(im, CTL_SCRATCH, 1, h); if (rc) return rc;
+    size_t total = h[0];
     im->res_nnz[m] = total; im->d_res[m] = nullptr;
     if (!total) return 0;
-    int rc = res_reserve(im, m, total); if (rc) return rc;
+    rc = res_reserve(im, m, total); if (rc) return rc;
+    ws.off = w.coo_at;                                                    // (an attempt that ended in FOLD_GIANT took its block here as well)
     int32_t* d_o = ws.get<int32_t>(total * 3);
-    if (!d_o) { im->eng->err = "workspace exhausted (COO)"; return XCK_E_NOMEM; }
+    if (!d_o) { im->eng->err = WS_RADIX_FULL; return XCK_E_NOMEM; }       // (more non-zeros than keys: the bound the block was reserved at is broken)
     HIP_TRY(hipMemsetAsync(d_o + 2 * total, 0, total * sizeof(int32_t), im->s_comp));       // k_fold_emit accumulates run pieces into val[]
     if constexpr (sizeof(K) == 8) {
         if (sorted_from > 0) {
@@ -1055,12 +1070,9 @@ static int fold_coo(EngineImpl* im, Arena& ws, const K* keys, size_t n, KeyLayou
             KeyLayout<unsigned long long> kl8; kl8.ubits = kl.ubits; kl8.cbits = kl.cbits;
             hipLaunchKernelGGL(k_fold_emit_unsorted, dim3(nb), dim3(FU_BLOCK), FU_SLOTS * 8, im->s_comp, (const unsigned long long*)keys, (long long)n, kl8, d_off,
                                d_o, d_o + total, d_o + 2 * total, im->d_ctl + CTL_GIANT, sorted_from);
-            HIP_TRY(hipGetLastError());
-            publish_words(im, im->d_ctl + CTL_GIANT, im->d_hctl + CTL_GIANT, 1, 64);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(im->s_comp));
-            if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] hash fold: n=%zu nnz=%zu ubits=%d cbits=%d giant=%llu\n", n, total, kl.ubits, kl.cbits, im->h_ctl[CTL_GIANT]);
-            if (im->h_ctl[CTL_GIANT]) return FOLD_GIANT;
+            if ((rc = read_ctl_words(im, CTL_GIANT, 1, h))) return rc;
+            if (im->eng->knobs.debug_timing) fprintf(stderr, "[xck] hash fold: n=%zu nnz=%zu ubits=%d cbits=%d giant=%llu\n", n, total, kl.ubits, kl.cbits, h[0]);
+            if (h[0]) return FOLD_GIANT;
             return copy_out(im, m, d_o, total);
         }
     }
@@ -1104,28 +1116,22 @@ static int pack_shards(EngineImpl* im, K* dst_keys, uint64_t* dst_vals) {
 // the radix-sort fold: takes every input.  64-bit keys: the sort only orders (row, cell) and fold_coo() tells the UMIs of a run apart
 template <class K>
 static int fold_by_radix_sort(EngineImpl* im, size_t n) {
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    KeyLayout<K> kl = key_layout<K>(im);
     Timer tm{im, im->ev0, im->ev1};
     int rc;
     const int top = im->ubits + im->cbits + im->rbits;
-    const size_t nb = (n + CP_TILE - 1) / CP_TILE;
     K* keys = (K*)im->d_keys;
     im->fold_path = 2;
     const size_t tmpb = sort_tmp_bytes<K, rocprim::empty_type>(n, top);
-    const size_t need = n * sizeof(K)        // alt
-                      + tmpb                 // tmp
-                      + nb * 12              // fold_coo: d_blk (4 bytes) and d_off (8 bytes) per tile of FD_TILE == CP_TILE keys
-                      + n * 12               // fold_coo: d_o, [row | col | val] of at most n non-zeros
-                      + (1 << 20);           // the 256-byte alignment of every get
-    if ((rc = arena_begin(im, im->ws1, need))) return rc;
-    K* alt = im->ws1.get<K>(n); void* tmp = im->ws1.get<char>(tmpb);
+    RadixFoldWs w;
+    if ((rc = pf_carve(im, im->ws1, true, [&](Arena& ar) { radix_fold_carve(ar, n, sizeof(K), tmpb, w); }, WS_RADIX_FULL))) return rc;
+    K* alt = (K*)w.alt; void* tmp = w.tmp;
     if ((rc = tm.start())) return rc;
     int used = im->ubits;                                                       // UMI bits actually in use
     if (sizeof(K) == 8) { unsigned long long uor = 0; for (int sh = 0; sh < NSHARD; sh++) uor |= im->h_ctl[ctl_umi_or(sh)]; used = uor ? 64 - __builtin_clzll(uor) : 1; if (used > im->ubits) used = im->ubits; }
     if (used < im->ubits) {
-        ShardSpan sp; sp.start[0] = 0; for (int sh = 0; sh < NSHARD; sh++) sp.start[sh + 1] = sp.start[sh] + im->cur[sh];
         hipLaunchKernelGGL(k_pack_squeeze, dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, im->s_comp,
-                           (const unsigned long long*)im->d_keys, (unsigned long long)im->hit_cap, sp, im->ubits, used, (unsigned long long*)alt);
+                           (const unsigned long long*)im->d_keys, (unsigned long long)im->hit_cap, shard_span(im->cur), im->ubits, used, (unsigned long long*)alt);
         HIP_TRY(hipGetLastError());
         kl.ubits = used;
     } else
@@ -1144,15 +1150,13 @@ static int fold_by_radix_sort(EngineImpl* im, size_t n) {
     int begin = partial ? begin_for(im->fold_extra_digits) : 0;
     K* src = alt; K* dst = keys;
     if ((rc = sort_run<K, rocprim::empty_type>(im, tmp, tmpb, src, dst, nullptr, nullptr, n, top_fc, begin))) return rc;
-    const size_t ws_mark = im->ws1.off;                              // a discarded attempt gives its workspace back
-    rc = fold_coo<K>(im, im->ws1, dst, n, kl, 0, begin);
-    while (rc == FOLD_GIANT) {
-        im->ws1.off = ws_mark;
+    rc = fold_coo<K>(im, im->ws1, w, dst, n, kl, 0, begin);
+    while (rc == FOLD_GIANT) {                                        // (the next attempt works in the same blocks)
         im->fold_extra_digits++;
         begin = begin_for(im->fold_extra_digits);
         std::swap(src, dst);                                          // any order of the same keys is a valid sort input
         if ((rc = sort_run<K, rocprim::empty_type>(im, tmp, tmpb, src, dst, nullptr, nullptr, n, top_fc, begin))) return rc;
-        rc = fold_coo<K>(im, im->ws1, dst, n, kl, 0, begin);      // begin == 0: fully sorted, classic fold, cannot be giant
+        rc = fold_coo<K>(im, im->ws1, w, dst, n, kl, 0, begin);   // begin == 0: fully sorted, classic fold, cannot be giant
     }
     if (rc) return rc;
     return tm.stop(&im->st.ms_sort);
@@ -1168,8 +1172,7 @@ static int finish_basefc(EngineImpl* im, size_t n) {
             Timer tm{im, im->ev0, im->ev1};
             int rc;
             if ((rc = tm.start())) return rc;
-            KeyLayout<unsigned long long> kl8; kl8.ubits = im->ubits; kl8.cbits = im->cbits;
-            rc = fold_partition(im, kl8, n);
+            rc = fold_partition(im, key_layout<unsigned long long>(im), n);
             if (rc == 0) {
                 im->fold_path = 1;
                 return tm.stop(&im->st.ms_sort);
@@ -1187,44 +1190,43 @@ static int finish_basefc(EngineImpl* im, size_t n) {
 template <class K> struct PileupFold {
     // region-level values: 64-bit words beside 64-bit keys (the partition sort carries 64-bit values), bytes beside 128-bit keys
     typedef typename std::conditional<sizeof(K) == 8, uint64_t, uint8_t>::type V2;
-    // the hits with a base (workspace 1)
+    // the hits with a base: workspace 1 (fold_ws.h; the region stage sees w1.al alone)
+    MoleculeWs w1;
     const K* keys; const uint64_t* vals;   // sorted by (key, value), wherever sort_pileup_hits left them
     PartIndex pidx;                        // the partition's cells, for k_claim's look-ups (stays null after the radix sort)
-    uint8_t* al;                           // per sorted hit: what the first read of its key shows at the SNP
-    unsigned long long* long_runs;         // [0] = count, then the heads of the runs longer than RUN_WALK
     // count_region_hits: region-level hits per k_expand shard, their sum, the widest shard (rounded up to 64), UMI-field bits in use
     unsigned long long tot2[XSHARD], cap2; size_t n2; int used2;
-    // the region-level hits (workspace 2)
+    // the region-level hits: workspace 2, and its key and value blocks under their types
+    RegionWs w2;
     K* k2; V2* v2;                         // as k_expand wrote them; k2 holds the run keys once they are partitioned / sorted
     K* k2b; V2* v2b;                       // sorted
-    uint8_t* cls; uint32_t* acc; long long stride2;   // haplotype class per hit; per run: REF-hap, ALT-hap, either, other-only keys
     size_t tmpb2;
 };
+static_assert(FD_TILE == (int)WS_TILE && CP_TILE == (int)WS_TILE && RUN_WALK == (long long)WS_RUN_WALK && XSHARD == (int)WS_SLICES, "fold_ws.h sizes its blocks by these");
+static const char* const WS_MOLECULE_FULL = "workspace exhausted (pileup fold)";
 
 // the hits sorted by (key, value): by row partition + one LDS sort per item (fold_partition.h); a SNP deeper than an item, or
 // 128-bit keys, take the radix sort
 template <class K>
 static int sort_pileup_hits(EngineImpl* im, size_t n, size_t tmpb, PileupFold<K>& pf) {
     int rc;
-    K* alt = im->ws1.get<K>(n); uint64_t* valt = im->ws1.get<uint64_t>(n); void* tmp = im->ws1.get<char>(tmpb);
+    K* alt = (K*)pf.w1.alt; uint64_t* valt = pf.w1.valt; void* tmp = pf.w1.tmp;
     pf.pidx = PartIndex{nullptr, nullptr};
     if constexpr (sizeof(K) == 8) {
         // (default since the items are sorted by an LDS radix sort: 1.7 ms at configs[2] against 2.3 ms for pack + rocPRIM's eight passes;
         // XCK_PILEUP_SORT=radix forces the library sort)
         const bool want_part = !im->eng->knobs.pileup_radix;
         if (want_part) {
-            KeyLayout<unsigned long long> kl8; kl8.ubits = im->ubits; kl8.cbits = im->cbits;
-            rc = pileup_partition_sort(im, im->ws2, true, kl8, (const unsigned long long*)im->d_keys, (const uint64_t*)im->d_vals, im->hit_cap, im->cur,
+            rc = pileup_partition_sort(im, im->ws2, true, key_layout<unsigned long long>(im), (const unsigned long long*)im->d_keys, (const uint64_t*)im->d_vals, im->hit_cap, im->cur,
                                        (uint32_t)std::max(im->n_snps_sorted, 1), n, (unsigned long long*)alt, valt, nullptr, &pf.pidx);
             if (rc == 0) { im->pileup_sort_path = 1; pf.keys = alt; pf.vals = valt; return 0; }
             else if (rc != PF_FALLBACK) return rc;
         }
     }
     im->pileup_sort_path = 2;
-    { ShardSpan sp; sp.start[0] = 0; for (int sh = 0; sh < NSHARD; sh++) sp.start[sh + 1] = sp.start[sh] + im->cur[sh];
-      hipLaunchKernelGGL((k_pack_pairs<K>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, im->s_comp,
-                         (const K*)im->d_keys, (const uint64_t*)im->d_vals, (unsigned long long)im->hit_cap, sp, alt, valt);
-      HIP_TRY(hipGetLastError()); }
+    hipLaunchKernelGGL((k_pack_pairs<K>), dim3((unsigned)std::min<size_t>((n + 255) / 256, 8192)), dim3(256), 0, im->s_comp,
+                       (const K*)im->d_keys, (const uint64_t*)im->d_vals, (unsigned long long)im->hit_cap, shard_span(im->cur), alt, valt);
+    HIP_TRY(hipGetLastError());
     const int top = im->ubits + im->cbits + im->rbits;
     if ((rc = sort_run<K, uint64_t>(im, tmp, tmpb, alt, (K*)im->d_keys, valt, im->d_vals, n, top))) return rc;
     pf.keys = (const K*)im->d_keys; pf.vals = im->d_vals;       // sorted data now lives in d_keys / d_vals
@@ -1235,16 +1237,15 @@ static int sort_pileup_hits(EngineImpl* im, size_t n, size_t tmpb, PileupFold<K>
 template <class K>
 static int first_reads_split(EngineImpl* im, size_t n, const PileupFold<K>& pf) {
     static_assert(sizeof(K) == 8, "the join kernel splits the pileup hits for 64-bit keys only (split_mode())");
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    const KeyLayout<K> kl = key_layout<K>(im);
     const unsigned gs = (unsigned)((n + 255) / 256);
-    uint8_t* al = pf.al; unsigned long long* long_runs = pf.long_runs;
+    const MoleculeWs& w = pf.w1;
+    uint8_t* al = w.al; unsigned long long* long_runs = w.long_runs;
     const size_t ns = std::max<size_t>((size_t)im->n_snps_sorted, 1);
-    uint64_t* ordv = im->ws1.get<uint64_t>(n); unsigned long long* row_lo = im->ws1.get<unsigned long long>(2 * ns); unsigned long long* row_hi = row_lo + ns;
+    uint64_t* ordv = w.ordv; unsigned long long *row_lo = w.row_lo, *row_hi = w.row_hi;
     if (n >> 32) { im->eng->err = "pileup fold: more than 2^32 hits with a base in one finish"; return XCK_E_NOMEM; }
     const uint32_t n_blk = (uint32_t)((ns + 31) >> 5);
-    unsigned long long* bloom = im->ws1.get<unsigned long long>(n);   // one word per key, laid out along the sorted stream (bloom_slot)
-    unsigned long long* blk_lo = im->ws1.get<unsigned long long>((size_t)n_blk + 1);
-    if (!ordv || !row_lo || !bloom || !blk_lo) { im->eng->err = "workspace exhausted (split pileup)"; return XCK_E_NOMEM; }
+    unsigned long long *bloom = w.bloom, *blk_lo = w.blk_lo;          // bloom: one word per key, laid out along the sorted stream (bloom_slot)
     HIP_TRY(hipMemsetAsync(row_lo, 0, 2 * ns * sizeof(unsigned long long), im->s_comp));
     HIP_TRY(hipMemsetAsync(bloom, 0, n * sizeof(unsigned long long), im->s_comp));
     hipLaunchKernelGGL((k_blk_bounds<K>), dim3((n_blk + 256) / 256), dim3(256), 0, im->s_comp, pf.keys, (long long)n, kl, n_blk, blk_lo);
@@ -1254,8 +1255,8 @@ static int first_reads_split(EngineImpl* im, size_t n, const PileupFold<K>& pf) 
     hipLaunchKernelGGL((k_first_long<K, true>), dim3(1024), dim3(256), 0, im->s_comp, pf.keys, pf.vals, (long long)n, kl, (const unsigned long long*)long_runs, al, ordv, im->d_tally);
     HIP_TRY(hipGetLastError());
     if (im->ncursor) {
-        ShardSpan nsp; nsp.start[0] = 0; unsigned long long mx = 0;
-        for (int sh = 0; sh < NSHARD; sh++) { nsp.start[sh + 1] = nsp.start[sh] + im->ncur[sh]; mx = std::max(mx, im->ncur[sh]); }
+        const ShardSpan nsp = shard_span(im->ncur);
+        const unsigned long long mx = *std::max_element(im->ncur, im->ncur + NSHARD);
         const unsigned long long n_units = ((mx + 256 * CL_U - 1) / (256 * CL_U)) * NSHARD;
         // (one block per unit: blocks start in index order, so the resident ones hold consecutive units = ONE window of the table; a grid-stride
         // loop over 16 k blocks mixed up to 11 windows and every probe went to HBM: 5.5 GB read for 0.74 GB of records)
@@ -1277,11 +1278,11 @@ static int first_reads_split(EngineImpl* im, size_t n, const PileupFold<K>& pf) 
 // first read per key when every hit, with a base or without, is in the sorted stream (128-bit keys; -DXCK_BAF_SPLIT=0 builds)
 template <class K>
 static int first_reads_plain(EngineImpl* im, size_t n, const PileupFold<K>& pf) {
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    const KeyLayout<K> kl = key_layout<K>(im);
     const unsigned gs = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL((k_first_read<K>), dim3(gs), dim3(256), 0, im->s_comp, pf.keys, pf.vals, (long long)n, kl, pf.al, im->d_tally, pf.long_runs);
+    hipLaunchKernelGGL((k_first_read<K>), dim3(gs), dim3(256), 0, im->s_comp, pf.keys, pf.vals, (long long)n, kl, pf.w1.al, im->d_tally, pf.w1.long_runs);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL((k_first_long<K, false>), dim3(1024), dim3(256), 0, im->s_comp, pf.keys, pf.vals, (long long)n, kl, (const unsigned long long*)pf.long_runs, pf.al, (uint64_t*)nullptr, im->d_tally);
+    hipLaunchKernelGGL((k_first_long<K, false>), dim3(1024), dim3(256), 0, im->s_comp, pf.keys, pf.vals, (long long)n, kl, (const unsigned long long*)pf.w1.long_runs, pf.w1.al, (uint64_t*)nullptr, im->d_tally);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1290,14 +1291,14 @@ static int first_reads_plain(EngineImpl* im, size_t n, const PileupFold<K>& pf) 
 template <class K, bool EMIT>
 static void launch_expand(EngineImpl* im, size_t n, const PileupFold<K>& pf, const XBases& xb, int pack_shift) {
     typedef typename PileupFold<K>::V2 V2;
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    const KeyLayout<K> kl = key_layout<K>(im);
     const unsigned gs = (unsigned)((n + 255) / 256);
     K* k2 = EMIT ? pf.k2 : (K*)nullptr; V2* v2 = EMIT ? pf.v2 : (V2*)nullptr;
     if (!im->d_cell_bits)
-        hipLaunchKernelGGL((k_expand<K, EMIT, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, im->d_tally, im->d_snp_info,
+        hipLaunchKernelGGL((k_expand<K, EMIT, V2>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.w1.al, (long long)n, kl, im->d_tally, im->d_snp_info,
                            im->sf, im->d_csr_off, im->d_csr_reg, k2, v2, im->d_ctl, xb, pack_shift);
     else
-        hipLaunchKernelGGL((k_expand<K, EMIT, V2, true>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.al, (long long)n, kl, cur_tally(im), im->d_snp_info,
+        hipLaunchKernelGGL((k_expand<K, EMIT, V2, true>), dim3(gs), dim3(JOIN_BLOCK), 0, im->s_comp, pf.keys, pf.w1.al, (long long)n, kl, cur_tally(im), im->d_snp_info,
                            im->sf, im->d_csr_off, im->d_csr_reg, k2, v2, im->d_ctl, xb, pack_shift, im->d_cell_bits, (uint32_t)((im->n_cells + 31) / 32));
 }
 
@@ -1307,46 +1308,27 @@ static int count_region_hits(EngineImpl* im, size_t n, PileupFold<K>& pf) {
     XBases xb; memset(&xb, 0, sizeof xb);
     HIP_TRY(hipMemsetAsync(im->d_ctl + CTL_X0, 0, XSHARD * CTL_STRIDE * sizeof(unsigned long long), im->s_comp));
     launch_expand<K, false>(im, n, pf, xb, -1);
-    HIP_TRY(hipGetLastError());
-    publish_words(im, im->d_ctl + CTL_X0, im->d_hctl + CTL_X0, XSHARD * CTL_STRIDE, 256);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
+    const unsigned long long* h;
+    if (int rc = read_ctl_words(im, CTL_X0, XSHARD * CTL_STRIDE, h)) return rc;
     pf.n2 = 0; pf.cap2 = 0;
     unsigned long long uor2 = 0;
-    for (int sh = 0; sh < XSHARD; sh++) { pf.tot2[sh] = im->h_ctl[CTL_X0 + sh * CTL_STRIDE]; pf.n2 += pf.tot2[sh]; pf.cap2 = std::max(pf.cap2, pf.tot2[sh]); }
+    for (int sh = 0; sh < XSHARD; sh++) { pf.tot2[sh] = h[sh * CTL_STRIDE]; pf.n2 += pf.tot2[sh]; pf.cap2 = std::max(pf.cap2, pf.tot2[sh]); }
     for (int sh = 0; sh < NSHARD; sh++) uor2 |= im->h_ctl[ctl_umi_or(sh)];
     pf.used2 = uor2 ? 64 - __builtin_clzll(uor2) : 0;            // UMI-field bits in use by the reads the join accepted (a superset of the region-level keys')
     pf.cap2 = (pf.cap2 + 63) & ~63ull;
     return 0;
 }
 
-// workspace 2 for the region-level hits: everything from here to the COO blocks
+// workspace 2 for the region-level hits, carved whole (fold_ws.h region_carve): everything from here to the COO blocks
 template <class K>
 static int reserve_region_hits(EngineImpl* im, bool try_part, PileupFold<K>& pf) {
     typedef typename PileupFold<K>::V2 V2;
-    int rc;
-    const size_t n2 = pf.n2;
-    const int top = im->ubits + im->cbits + im->rbits;
-    const size_t n2s = try_part ? std::max<size_t>((size_t)XSHARD * pf.cap2, n2) : n2;      // entries of the unsorted buffers
-    pf.tmpb2 = sort_tmp_bytes<K, V2>(n2, top);
-    const size_t nb2 = (n2 + CP_TILE - 1) / CP_TILE;
-    const size_t part_bytes = try_part ? partition_sort_scratch(im, n2, (size_t)std::max(im->n_regions, 1)) : 0;
-    const size_t need = (n2s + 8) * sizeof(K) + n2 * sizeof(K)              // k2, k2b
-                      + (n2s + 8) * sizeof(V2) + n2 * sizeof(V2)            // v2 (takes n2s), v2b
-                      + n2                                                  // cls
-                      + 4 * (n2 + 8) * 4                                    // acc: 4 words per run, stride2 <= n2 + 7
-                      + std::max(pf.tmpb2, part_bytes)                      // sort_region_hits: the partition sort's scratch, or tmp2
-                      + ((n2 + FD_TILE - 1) / FD_TILE) * 12                 // sum_sorted_runs: d_blk2 (4 bytes) and d_off2 (8 bytes) per tile
-                      + (n2 / RUN_WALK + 2) * 8                             // sum_sorted_runs: long2
-                      + 3 * (nb2 * 12 + n2 * 12)                            // compact_coo, per matrix: d_blk, d_off; out.o of at most n2 non-zeros
-                      + (1 << 16);                                          // the 256-byte alignment of every get
-    if ((rc = arena_begin(im, im->ws2, need))) return rc;
-    pf.k2 = im->ws2.get<K>(n2s + 8); pf.k2b = im->ws2.get<K>(n2); pf.v2 = im->ws2.get<V2>(n2s); pf.v2b = im->ws2.get<V2>(n2);
-    pf.cls = im->ws2.get<uint8_t>(n2);
-    pf.stride2 = (long long)((n2 + 7) & ~size_t(7));  // (k_hap_count / k_hap_scatter read eight runs with two 16-byte loads)
-    pf.acc = im->ws2.get<uint32_t>(4 * (size_t)pf.stride2);      // per run: REF-hap, ALT-hap, either, other-only keys
-    if (!pf.k2 || !pf.k2b || !pf.v2 || !pf.v2b || !pf.cls || !pf.acc) { im->eng->err = "workspace exhausted (region-level hits)"; return XCK_E_NOMEM; }
-    HIP_TRY(hipMemsetAsync(pf.acc, 0, 2 * (size_t)pf.stride2 * sizeof(uint32_t), im->s_comp));   // (the half that k_hap_items' packed sums use; the rest in sum_sorted_runs, if it runs)
+    RegionWs& w = pf.w2;
+    pf.tmpb2 = sort_tmp_bytes<K, V2>(pf.n2, im->ubits + im->cbits + im->rbits);
+    const size_t part_bytes = partition_sort_scratch(im, pf.n2, (size_t)std::max(im->n_regions, 1));
+    if (int rc = pf_carve(im, im->ws2, true, [&](Arena& ar) { region_carve(ar, pf.n2, (size_t)pf.cap2, sizeof(K), sizeof(V2), pf.tmpb2, part_bytes, try_part, w); }, WS_REGION_FULL)) return rc;
+    pf.k2 = (K*)w.k2; pf.k2b = (K*)w.k2b; pf.v2 = (V2*)w.v2; pf.v2b = (V2*)w.v2b;
+    HIP_TRY(hipMemsetAsync(w.acc, 0, 2 * w.stride2 * sizeof(uint32_t), im->s_comp));   // (the half that k_hap_items' packed sums use; the rest in sum_sorted_runs, if it runs)
     return 0;
 }
 
@@ -1362,7 +1344,6 @@ static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<
     const size_t n2 = pf.n2;
     XBases xb; memset(&xb, 0, sizeof xb);
     *summed = false;
-    const size_t ws2_mark = im->ws2.off;
     if constexpr (sizeof(K) == 8) {
         if (try_part) {
             for (int sh = 0; sh < XSHARD; sh++) xb.base[sh] = (unsigned long long)sh * pf.cap2;
@@ -1372,11 +1353,10 @@ static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<
             const int pack_shift = hap_items && im->eng->knobs.pileup_hap != 2 && pf.used2 + 2 <= im->ubits ? pf.used2 : -1;
             launch_expand<K, true>(im, n, pf, xb, pack_shift);
             HIP_TRY(hipGetLastError());
-            KeyLayout<unsigned long long> kl8; kl8.ubits = im->ubits; kl8.cbits = im->cbits;
-            const HapItemsOut ho{(unsigned long long*)pf.acc, (unsigned long long*)pf.k2, pack_shift};   // (the packed sums use the first half of acc)
-            rc = pileup_partition_sort(im, im->ws2, false, kl8, (const unsigned long long*)pf.k2, pack_shift >= 0 ? (const uint64_t*)nullptr : (const uint64_t*)pf.v2, (size_t)pf.cap2, pf.tot2,
+            const HapItemsOut ho{(unsigned long long*)pf.w2.acc, (unsigned long long*)pf.k2, pack_shift};   // (the packed sums use the first half of acc)
+            im->ws2.off = pf.w2.scratch_at;                            // its scratch: the shared region (the radix sort's tmp, should it hand over)
+            rc = pileup_partition_sort(im, im->ws2, false, key_layout<unsigned long long>(im), (const unsigned long long*)pf.k2, pack_shift >= 0 ? (const uint64_t*)nullptr : (const uint64_t*)pf.v2, (size_t)pf.cap2, pf.tot2,
                                        (uint32_t)std::max(im->n_regions, 1), n2, (unsigned long long*)pf.k2b, pack_shift >= 0 ? (uint64_t*)nullptr : (uint64_t*)pf.v2b, hap_items ? &ho : nullptr);
-            im->ws2.off = ws2_mark;                                    // (its scratch is free again; the kernels that used it are ordered before the next ones)
             if (rc == 0) { *summed = hap_items; im->pileup_sort2_path = hap_items ? 1 : 3; return 0; }
             else if (rc != PF_FALLBACK) return rc;
             else {                                                 // the cursors of the emit pass start again
@@ -1385,7 +1365,7 @@ static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<
         }
     }
     im->pileup_sort2_path = 2;
-    void* tmp2 = im->ws2.get<char>(pf.tmpb2);
+    void* tmp2 = pf.w2.scratch;                                        // (the kernels that used it as the partition sort's scratch are ordered before the sort)
     { unsigned long long at = 0; for (int sh = 0; sh < XSHARD; sh++) { xb.base[sh] = at; at += pf.tot2[sh]; } }
     launch_expand<K, true>(im, n, pf, xb, -1);
     HIP_TRY(hipGetLastError());
@@ -1396,21 +1376,19 @@ static int sort_region_hits(EngineImpl* im, size_t n, bool try_part, PileupFold<
 template <class K>
 static int sum_sorted_runs(EngineImpl* im, const PileupFold<K>& pf) {
     typedef typename PileupFold<K>::V2 V2;
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
-    const size_t n2 = pf.n2; const long long stride2 = pf.stride2;
-    HIP_TRY(hipMemsetAsync(pf.acc + 2 * (size_t)stride2, 0, 2 * (size_t)stride2 * sizeof(uint32_t), im->s_comp));
+    const KeyLayout<K> kl = key_layout<K>(im);
+    const RegionWs& w = pf.w2;
+    const size_t n2 = pf.n2;
+    HIP_TRY(hipMemsetAsync(w.acc + 2 * w.stride2, 0, 2 * w.stride2 * sizeof(uint32_t), im->s_comp));
     const unsigned gs2 = (unsigned)((n2 + 255) / 256);
     const size_t nt2 = (n2 + FD_TILE - 1) / FD_TILE;
-    uint32_t* d_blk2 = im->ws2.get<uint32_t>(nt2); unsigned long long* d_off2 = im->ws2.get<unsigned long long>(nt2);
-    unsigned long long* long2 = im->ws2.get<unsigned long long>(n2 / (size_t)RUN_WALK + 2);   // [0] = count, then the heads of the (row, cell, UMI) runs longer than RUN_WALK
-    if (!d_blk2 || !d_off2 || !long2) { im->eng->err = "workspace exhausted (haplotype classes)"; return XCK_E_NOMEM; }
-    HIP_TRY(hipMemsetAsync(long2, 0, sizeof(unsigned long long), im->s_comp));
-    hipLaunchKernelGGL((k_hap_class<K, V2>), dim3(gs2), dim3(256), 0, im->s_comp, (const K*)pf.k2b, (const V2*)pf.v2b, (long long)n2, pf.cls, long2);
-    hipLaunchKernelGGL((k_hap_class_long<K, V2>), dim3(256), dim3(256), 0, im->s_comp, (const K*)pf.k2b, (const V2*)pf.v2b, (long long)n2, (const unsigned long long*)long2, pf.cls);
-    hipLaunchKernelGGL((k_fold_heads<K>), dim3((unsigned)nt2), dim3(FD_BLOCK), 0, im->s_comp, (const K*)pf.k2b, (long long)n2, kl, d_blk2);
-    hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, im->s_comp, d_blk2, (long long)nt2, d_off2, im->d_ctl + CTL_SCRATCH);
-    hipLaunchKernelGGL((k_hap_sum<K>), dim3((unsigned)nt2), dim3(FD_BLOCK), 0, im->s_comp, (const K*)pf.k2b, (const uint8_t*)pf.cls, (long long)n2, kl,
-                       (const unsigned long long*)d_off2, pf.k2, pf.acc, stride2);
+    HIP_TRY(hipMemsetAsync(w.long2, 0, sizeof(unsigned long long), im->s_comp));
+    hipLaunchKernelGGL((k_hap_class<K, V2>), dim3(gs2), dim3(256), 0, im->s_comp, (const K*)pf.k2b, (const V2*)pf.v2b, (long long)n2, w.cls, w.long2);
+    hipLaunchKernelGGL((k_hap_class_long<K, V2>), dim3(256), dim3(256), 0, im->s_comp, (const K*)pf.k2b, (const V2*)pf.v2b, (long long)n2, (const unsigned long long*)w.long2, w.cls);
+    hipLaunchKernelGGL((k_fold_heads<K>), dim3((unsigned)nt2), dim3(FD_BLOCK), 0, im->s_comp, (const K*)pf.k2b, (long long)n2, kl, w.d_blk2);
+    hipLaunchKernelGGL(k_cp_scan, dim3(1), dim3(1024), 0, im->s_comp, w.d_blk2, (long long)nt2, w.d_off2, im->d_ctl + CTL_SCRATCH);
+    hipLaunchKernelGGL((k_hap_sum<K>), dim3((unsigned)nt2), dim3(FD_BLOCK), 0, im->s_comp, (const K*)pf.k2b, (const uint8_t*)w.cls, (long long)n2, kl,
+                       (const unsigned long long*)w.d_off2, pf.k2, w.acc, (long long)w.stride2);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1425,26 +1403,17 @@ static int fold_molecules(EngineImpl* im, size_t n) {
     const int top = im->ubits + im->cbits + im->rbits;
     PileupFold<K> pf{};
     const size_t tmpb = sort_tmp_bytes<K, uint64_t>(n, top);
-    const size_t need = n * sizeof(K) + n * 8 + tmpb                          // sort_pileup_hits: alt, valt, tmp
-                      + n                                                     // al
-                      + n / 8                                                 // long_runs: 8 bytes per RUN_WALK hits
-                      + n * 8                                                 // first_reads_split: ordv
-                      + (size_t)std::max(im->n_snps_sorted, 1) * 17           // first_reads_split: row_lo and row_hi (16 bytes per SNP), blk_lo (8 bytes per 32 SNPs)
-                      + std::max<size_t>(n * 8, 8192)                         // first_reads_split: bloom
-                      + (1 << 16);                                            // the 256-byte alignment of every get
     im->mol_valid = false;
-    if ((rc = arena_begin(im, im->ws1, need))) return rc;
-    if ((rc = sort_pileup_hits<K>(im, n, tmpb, pf))) return rc;
-    pf.al = im->ws1.get<uint8_t>(n);
-    HIP_TRY(hipMemsetAsync(im->d_tally, 0, std::max<size_t>((size_t)im->n_snps_sorted * 5, 1) * sizeof(uint32_t), im->s_comp));
-    pf.long_runs = im->ws1.get<unsigned long long>(n / (size_t)RUN_WALK + 2);
-    if (!pf.long_runs) { im->eng->err = "workspace exhausted (pileup fold)"; return XCK_E_NOMEM; }
-    HIP_TRY(hipMemsetAsync(pf.long_runs, 0, sizeof(unsigned long long), im->s_comp));
     // (the join kernel splits the hits for 64-bit keys only - split_mode() - so the split path is not instantiated for 128-bit keys)
-    if constexpr (sizeof(K) == 8) rc = split_mode(im) ? first_reads_split<K>(im, n, pf) : first_reads_plain<K>(im, n, pf);
+    const bool split = sizeof(K) == 8 && split_mode(im);
+    if ((rc = pf_carve(im, im->ws1, true, [&](Arena& ar) { molecule_carve(ar, n, sizeof(K), tmpb, (size_t)im->n_snps_sorted, split, pf.w1); }, WS_MOLECULE_FULL))) return rc;
+    if ((rc = sort_pileup_hits<K>(im, n, tmpb, pf))) return rc;
+    HIP_TRY(hipMemsetAsync(im->d_tally, 0, std::max<size_t>((size_t)im->n_snps_sorted * 5, 1) * sizeof(uint32_t), im->s_comp));
+    HIP_TRY(hipMemsetAsync(pf.w1.long_runs, 0, sizeof(unsigned long long), im->s_comp));
+    if constexpr (sizeof(K) == 8) rc = split ? first_reads_split<K>(im, n, pf) : first_reads_plain<K>(im, n, pf);
     else rc = first_reads_plain<K>(im, n, pf);
     if (rc) return rc;
-    im->mol_keys = pf.keys; im->mol_al = pf.al; im->mol_n = n; im->mol_valid = true;
+    im->mol_keys = pf.keys; im->mol_al = pf.w1.al; im->mol_n = n; im->mol_valid = true;
     return 0;
 }
 
@@ -1454,10 +1423,9 @@ static int fold_molecules(EngineImpl* im, size_t n) {
 template <class K>
 static int fold_regions(EngineImpl* im) {
     int rc;
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
     const size_t n = im->mol_n;
     PileupFold<K> pf{};
-    pf.keys = (const K*)im->mol_keys; pf.al = im->mol_al;
+    pf.keys = (const K*)im->mol_keys; pf.w1.al = im->mol_al;
     for (int m = 1; m < 4; m++) { im->res_nnz[m] = 0; im->d_res[m] = nullptr; }
     if (n == 0) return 0;
     if ((rc = count_region_hits<K>(im, n, pf))) return rc;
@@ -1466,12 +1434,12 @@ static int fold_regions(EngineImpl* im) {
         bool summed = false;
         if ((rc = reserve_region_hits<K>(im, try_part, pf))) return rc;
         if ((rc = sort_region_hits<K>(im, n, try_part, pf, &summed))) return rc;
-        HapSrc hs{(const uint32_t*)pf.acc, pf.stride2, (const unsigned long long*)nullptr, (long long)pf.n2, im->no_dup_hap, (const unsigned long long*)pf.acc};   // k_hap_items: runs staged (packed) at their items' offsets
+        HapSrc hs{(const uint32_t*)pf.w2.acc, (long long)pf.w2.stride2, (const unsigned long long*)nullptr, (long long)pf.n2, im->no_dup_hap, (const unsigned long long*)pf.w2.acc};   // k_hap_items: runs staged (packed) at their items' offsets
         if (!summed) {
             if ((rc = sum_sorted_runs<K>(im, pf))) return rc;
             hs.n_runs = (const unsigned long long*)(im->d_ctl + CTL_SCRATCH); hs.packed = nullptr;
         }
-        if ((rc = compact_coo<K>(im, im->ws2, hs, pf.k2, pf.n2, kl, 1))) return rc;   // AD, DP, OTH together, from the per-run sums
+        if ((rc = compact_coo<K>(im, im->ws2, pf.w2, hs, pf.k2, pf.n2, key_layout<K>(im), 1))) return rc;   // AD, DP, OTH together, from the per-run sums
     }
     return 0;
 }

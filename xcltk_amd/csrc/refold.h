@@ -63,14 +63,7 @@ __global__ __launch_bounds__(RF_BLOCK) void k_snp_regions(RefoldTabs t, uint32_t
     }
 }
 
-static int refold_grow(EngineImpl* im, void** p, size_t* cap, size_t need) {
-    if (need <= *cap) return 0;
-    if (*p) HIP_TRY(hipFree(*p));
-    *p = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc(p, need + need / 4 + 4096));
-    *cap = need + need / 4 + 4096;
-    return 0;
-}
+static size_t refold_slack(size_t need) { return need / 4 + 4096; }      // head room of the grow-only buffers of this file (grow_device)
 
 // what the host hands to the builder: one block, one copy
 struct RefoldHost {
@@ -146,7 +139,7 @@ static int refold_build_tables(EngineImpl* im, const xck_refold_config* cfg, boo
     ScratchLayout L;                                                      // (coo_call.h) the uploaded tables - an empty one still takes four bytes -, then the scan's block sums
     for (const auto& u : up) L.add(std::max<size_t>(u.bytes, 4));
     const int i_bsum = L.add(nsb * 4);
-    if (int rc = refold_grow(im, (void**)&im->d_rf, &im->rf_cap, L.total())) return rc;
+    if (int rc = grow_device(im, (void**)&im->d_rf, &im->rf_cap, L.total(), refold_slack(L.total()))) return rc;
     if (!im->d_csr_alt) HIP_TRY(hipMalloc((void**)&im->d_csr_alt, (ns + 1) * sizeof(int32_t)));
     if (!im->ev_r0) { HIP_TRY(hipEventCreate(&im->ev_r0)); HIP_TRY(hipEventCreate(&im->ev_r1)); HIP_TRY(hipEventCreate(&im->ev_r2)); HIP_TRY(hipEventCreate(&im->ev_r3)); }
     { std::vector<char> blk(L.offs[i_bsum]);
@@ -169,16 +162,16 @@ static int refold_build_tables(EngineImpl* im, const xck_refold_config* cfg, boo
     HIP_TRY(hipGetLastError());
     if (int rc = pf_scan(im, (uint32_t*)im->d_csr_alt, ns + 1, bsum, nullptr)) return rc;
     HIP_TRY(hipEventRecord(im->ev_r1, im->s_comp));
-    publish_words(im, im->d_ctl + CTL_SCRATCH, im->d_hctl + CTL_SCRATCH, 1, 64);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(im->s_comp));
-    const unsigned long long total = im->h_ctl[CTL_SCRATCH];
+    const unsigned long long* h_total;
+    if (int rc = read_ctl_words(im, CTL_SCRATCH, 1, h_total)) return rc;
+    const unsigned long long total = *h_total;
     if (total > (unsigned long long)INT32_MAX) {
         char b[200]; snprintf(b, sizeof b, "xck_refold: %llu (SNP, region) pairs: the SNP -> region table holds at most 2^31 - 1", total);
         im->eng->err = b; return XCK_E_NOMEM;
     }
     *touched = true;
-    if (int rc = refold_grow(im, (void**)&im->d_csr_reg, &im->csr_reg_cap_bytes, std::max<size_t>((size_t)total, 1) * sizeof(int32_t))) return rc;
+    const size_t reg_bytes = std::max<size_t>((size_t)total, 1) * sizeof(int32_t);
+    if (int rc = grow_device(im, (void**)&im->d_csr_reg, &im->csr_reg_cap_bytes, reg_bytes, refold_slack(reg_bytes))) return rc;
     HIP_TRY(hipEventRecord(im->ev_r2, im->s_comp));
     hipLaunchKernelGGL((k_snp_regions<true>), dim3(grid), dim3(RF_BLOCK), 0, im->s_comp, t, (uint32_t*)nullptr, (const int32_t*)im->d_csr_alt, im->d_csr_reg, (unsigned long long*)nullptr);
     HIP_TRY(hipGetLastError());
@@ -213,10 +206,10 @@ static std::vector<uint32_t> refold_cell_bits(const EngineImpl* im, const uint8_
 template <class K>
 static int refold_mask_tallies(EngineImpl* im, const std::vector<uint32_t>& bits) {
     const size_t ns = std::max<size_t>((size_t)im->n_snps_sorted, 1), n = im->mol_n, nw = bits.size();
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    const KeyLayout<K> kl = key_layout<K>(im);
     ScratchLayout L;
     const int i_bits = L.add(nw * 4), i_lo = L.add((ns + 1) * 8), i_long = L.add((n / (size_t)TALLY_LONG + 2) * 8), i_tally = L.add(ns * 5 * 4);
-    if (int rc = refold_grow(im, (void**)&im->d_cm, &im->cm_cap, L.total())) return rc;
+    if (int rc = grow_device(im, (void**)&im->d_cm, &im->cm_cap, L.total(), refold_slack(L.total()))) return rc;
     if (!im->ev_m0) { HIP_TRY(hipEventCreate(&im->ev_m0)); HIP_TRY(hipEventCreate(&im->ev_m1)); }
     uint32_t* d_bits = L.at<uint32_t>(im->d_cm, i_bits); unsigned long long* row_lo = L.at<unsigned long long>(im->d_cm, i_lo);
     unsigned long long* long_rows = L.at<unsigned long long>(im->d_cm, i_long); uint32_t* tally = L.at<uint32_t>(im->d_cm, i_tally);
@@ -273,7 +266,8 @@ int engine_refold(EngineImpl* im, const xck_refold_config* cfg, xck_result* out)
     im->cmat_valid = false; im->fmat_valid = false; im->csr_host_stale = im->d_feat != nullptr;
     im->copy_timed = false;
     const auto fold = [&]() -> int {
-        if (im->d_feat) if (int r = refold_grow(im, (void**)&im->d_fmat, &im->fmat_cap_bytes, std::max<size_t>((size_t)im->n_regions * 6, 1) * sizeof(unsigned long long))) return r;
+        const size_t fmat_bytes = std::max<size_t>((size_t)im->n_regions * 6, 1) * sizeof(unsigned long long);
+        if (im->d_feat) if (int r = grow_device(im, (void**)&im->d_fmat, &im->fmat_cap_bytes, fmat_bytes, refold_slack(fmat_bytes))) return r;
         Timer tm{im, im->ev0, im->ev1};
         double ms = 0;
         if (int r = tm.start()) return r;

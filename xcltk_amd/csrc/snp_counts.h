@@ -195,7 +195,7 @@ __global__ __launch_bounds__(SNC_BLOCK) void k_snc_emit(const K* __restrict__ k,
 template <class K>
 static int snp_counts_run(EngineImpl* im, std::chrono::steady_clock::time_point t0) {
     CooCall& c = im->sc;
-    KeyLayout<K> kl; kl.ubits = im->ubits; kl.cbits = im->cbits;
+    const KeyLayout<K> kl = key_layout<K>(im);
     const K* keys = (const K*)im->mol_keys;
     const size_t n = im->mol_n, ns = (size_t)im->n_snps_sorted, nt = (n + SNC_TILE - 1) / SNC_TILE, stride = ((size_t)im->n_snps_in + 1 + 63) & ~size_t(63);
     if (n >> 32) { im->eng->err = "xck_snp_counts: the sorted stream holds 2^32 hits or more: its 32-bit prefix counts do not reach that far"; return XCK_E_CAPACITY; }
