@@ -84,6 +84,11 @@
  *                                         XCK_F_FEATURE_SUMMARY (xck_get_feature_summary): the front-ends then write feature_summary.tsv and, for the
  *                                         pileup, snp_summary.tsv next to their matrices.  One kernel more per join launch; does not imply XCK_READ_FATE.
  *                                         Off (the default, or 0) nothing is allocated or launched.  Decode-only handles ignore it.
+ *   XCK_UMI_CONSENSUS=1                   every handle with a BAF pipeline that drives a GPU decides the base of a molecule by a plurality vote over its
+ *                                         reads, as if made with XCK_F_UMI_CONSENSUS (xck_get_molecule_stats): the front-ends then write
+ *                                         molecule_summary.tsv next to their BAF matrices, and step 1 and step 3 of one `xcltk baf` run use the same
+ *                                         rule.  Off (the default, or 0) the reference's first-read rule holds and every output is byte-identical.
+ *                                         Basefc-only and decode-only handles ignore it.
  *   XCK_GROUP_LONG_ROW=<entries>          xck_group_counts: a source row with at least this many entries is summed by one block with a table in
  *                                         LDS, a shorter one by one wave in registers (default and upper bound 64, at least 1; tests: a small value
  *                                         reaches the block shape with small inputs)
@@ -235,6 +240,14 @@ typedef struct xck_config {
                                    matrices and the allele tallies and filter verdict of every SNP (xck_get_feature_summary; one more
                                    kernel behind every join launch).  Does not imply XCK_F_READ_FATE; combines freely with it and with
                                    XCK_F_CELL_SUMMARY.  Changes no result.  XCK_E_ARG together with XCK_F_DECODE_ONLY            */
+#define XCK_F_UMI_CONSENSUS 256 /* pileup: the base a molecule (SNP, cell, UMI) shows is decided by a plurality vote over its reads that
+                                   show a base there - buckets A / C / G / T, a tie goes to the bucket seen earliest in fetch order,
+                                   a read that shows N abstains unless nothing else was seen - instead of by its first read, and a
+                                   read that spans the SNP in an N / D gap abstains instead of silencing the molecule.  Everything
+                                   downstream (tallies, min_count / min_maf, xck_refold, xck_snp_counts, xck_group_counts, the SNP
+                                   table of xck_get_feature_summary) follows.  The same kernels count how often the reads of a
+                                   molecule disagree (xck_get_molecule_stats).  Any handle with a BAF pipeline; on XCK_MODE_BOTH it
+                                   affects the BAF half only.  XCK_E_ARG on a basefc-only handle and together with XCK_F_DECODE_ONLY */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -383,7 +396,8 @@ typedef struct xck_cell_summary {
  *           ad, dp, oth (row sums), cells (entries of the DP row).
  * snp (BAF only): reads = filtered reads whose fetch span covers the SNP (pos <= p0 < endpos, a SNP inside an N gap included: the per-SNP
  *   split of xck_read_fate.pairs; available before xck_finish); a c g t n = the pseudo-bulk tallies of the fold, one count per
- *   (cell, UMI) that shows a base (the reference's MCount.tcount order); kept = verdict of the fold's own per-SNP filter (plp_snp,
+ *   (cell, UMI) that shows a base, the base being the one the handle's rule decides (the first read's, or the vote of XCK_F_UMI_CONSENSUS;
+ *   the reference's MCount.tcount order); kept = verdict of the fold's own per-SNP filter (plp_snp,
  *   baf/fc/core.py:238-246) under xck_config.min_count / min_maf of THIS handle, 0 or 1 (a front-end that filters later, on sums of the
  *   matrices, creates the handle with 1 / 0: kept then only says that a molecule showed a base); regions = regions the SNP feeds.  Tallies and kept are zero while has_matrix == 0. */
 typedef struct xck_feature_summary {
@@ -399,6 +413,20 @@ typedef struct xck_feature_summary {
     int32_t  n_snp_cols;        /* BAF 8: reads, a, c, g, t, n, kept, regions                                                  */
     const int64_t* snp;         /* [n_snps * n_snp_cols]; NULL for the basefc pipeline                                         */
 } xck_feature_summary;
+
+/* How the reads of the molecules of the last xck_finish agree (handles made with XCK_F_UMI_CONSENSUS; additive, ABI 3 is unchanged).  A
+ * molecule is a (SNP, cell, UMI) with at least one read that shows a base at the SNP; reads that span the SNP in a gap are not looked
+ * at.  Buckets are A, C, G, T and N (any other nibble).  struct_size = sizeof(xck_molecule_stats), as for xck_decode_stats. */
+typedef struct xck_molecule_stats {
+    uint32_t struct_size;
+    int32_t  consensus;         /* 1: the handle votes (the only value a successful call returns)                               */
+    int64_t  molecules;         /* molecules                                                                                   */
+    int64_t  multi_read;        /* ... with two or more reads that show a base                                                 */
+    int64_t  discordant;        /* ... whose reads fall into two or more buckets (N counts as a bucket here)                   */
+    int64_t  tied;              /* ... where two or more of A / C / G / T share the largest number of reads                    */
+    int64_t  changed;           /* ... whose winning bucket is not the bucket of the earliest read with a base: the molecules
+                                   that the first-read rule would have called differently, gap reads aside                    */
+} xck_molecule_stats;
 
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
@@ -442,7 +470,7 @@ int  xck_finish_async(xck_engine* e);
  * per-contig sparse blocks GPU-to-GPU (RCCL over xGMI) without a host round trip. */
 int  xck_get_result_device(xck_engine* e, xck_result* out);
 /* Recount the pileup under new tables without the reads (additive: ABI 3 is unchanged).  The read x SNP join and the first half of
- * the pileup fold - the sort of the hits, the base the first read of every (SNP, cell, UMI) shows, the tallies per SNP - depend on
+ * the pileup fold - the sort of the hits, the base every (SNP, cell, UMI) shows under the handle's rule (its first read's, or the vote of XCK_F_UMI_CONSENSUS), the tallies per SNP - depend on
  * nothing but the reads, the read filters, the cells and the SNP positions; xck_finish keeps what they leave, and xck_refold runs the
  * second half again: the fan-out to the regions, REF / ALT and the haplotype indices, the exclusion pairs, min_count / min_maf and
  * no_dup_hap.  It returns the matrices a fresh handle would return that was created with these tables and filters and the original
@@ -494,7 +522,7 @@ int  xck_refold(xck_engine* e, const xck_refold_config* cfg, xck_result* out);
 /* The SNP x cell matrices of the finished pileup (additive, as xck_refold is: ABI 3 is unchanged; a caller built against an older header
  * of ABI 3 does not see the symbol and loses nothing): out->ad / dp / oth with row = index of the SNP in the
  * list given to xck_create, col = cell, sorted by (row, col); out->count is empty.  Counted from what xck_finish keeps of the molecule
- * stage - the hits sorted by (SNP, cell, UMI) and the base the first read of every molecule shows - without the reads, without a region
+ * stage - the hits sorted by (SNP, cell, UMI) and the base every molecule shows under the handle's rule (its first read's, or the vote of XCK_F_UMI_CONSENSUS, under which no gap record claims) - without the reads, without a region
  * table and without a sort.  Per (SNP, cell): AD = molecules that show the SNP's ALT, DP = molecules that show REF or ALT (ALT wins when
  * REF == ALT), OTH = molecules that show another base; zero values are not emitted; a molecule that a gap record claims (an N / D
  * gap over the SNP earlier in fetch order) counts nowhere.  These are the matrices of a handle made with one one-base region per SNP,
@@ -563,6 +591,12 @@ int  xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out);
  * does not have or a short struct_size.  With contigs cut over several GPUs every handle counts the regions it was given; the SNPs
  * near a cut are seen by both neighbours. */
 int  xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out);
+/* The agreement counters of the handle's pileup pipeline (set out->struct_size first), as the molecule stage of the last xck_finish
+ * counted them; xck_refold, xck_snp_counts and xck_group_counts do not change them, xck_reset clears them.  XCK_E_STATE on a handle
+ * without XCK_F_UMI_CONSENSUS (and without XCK_UMI_CONSENSUS=1), before a successful xck_finish, after an xck_reset, or when a fold of
+ * the handle has failed; XCK_E_ARG for a null pointer or a short struct_size.  With contigs cut over several GPUs every handle counts
+ * the molecules of the reads it saw; a molecule whose reads straddle a cut is counted by both neighbours. */
+int  xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

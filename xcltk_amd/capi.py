@@ -23,6 +23,7 @@ XCK_F_DEVICE_CRC = 16
 XCK_F_READ_FATE = 32
 XCK_F_CELL_SUMMARY = 64
 XCK_F_FEATURE_SUMMARY = 128
+XCK_F_UMI_CONSENSUS = 256
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -164,6 +165,15 @@ FEATURE_MATRIX_COLS = {XCK_MODE_BASEFC: ("umis", "cells"), XCK_MODE_BAF: ("snps"
 SNP_COLS = ("reads", "a", "c", "g", "t", "n", "kept", "regions")
 
 
+class MoleculeStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("consensus", C.c_int32)] + [(k, C.c_int64) for k in (
+        "molecules", "multi_read", "discordant", "tied", "changed")]
+
+
+# the counters of xck_molecule_stats in the struct's order
+MOLECULE_FIELDS = tuple(k for k, _ in MoleculeStats._fields_[2:])
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -220,6 +230,7 @@ SYMBOLS = [
     ("xck_get_read_fate", C.c_int, [C.c_void_p, C.c_int, _P(ReadFate)]),
     ("xck_get_cell_summary", C.c_int, [C.c_void_p, C.c_int, _P(CellSummary)]),
     ("xck_get_feature_summary", C.c_int, [C.c_void_p, C.c_int, _P(FeatureSummary)]),
+    ("xck_get_molecule_stats", C.c_int, [C.c_void_p, _P(MoleculeStats)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

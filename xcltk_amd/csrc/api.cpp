@@ -67,6 +67,7 @@ Knobs xck::Knobs::from_env() {
     k.read_fate = num("XCK_READ_FATE", 0) != 0;
     k.cell_summary = num("XCK_CELL_SUMMARY", 0) != 0;
     k.feature_summary = num("XCK_FEATURE_SUMMARY", 0) != 0;
+    k.umi_consensus = num("XCK_UMI_CONSENSUS", 0) != 0;
     k.group_long_row = (int)std::max(1ll, std::min(64ll, num("XCK_GROUP_LONG_ROW", 64)));
     k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
     if (*str("XCK_TAG_FILTER")) {                                        // TAG:VALUE[/MASK], numbers decimal or 0x hex, MASK defaults to all ones
@@ -111,6 +112,10 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     const struct { int flag; const char* name; } gpu_only[] = { { XCK_F_READ_FATE, "XCK_F_READ_FATE" }, { XCK_F_CELL_SUMMARY, "XCK_F_CELL_SUMMARY" }, { XCK_F_FEATURE_SUMMARY, "XCK_F_FEATURE_SUMMARY" } };
     for (const auto& g : gpu_only)
         if ((cfg->flags & g.flag) && (cfg->flags & XCK_F_DECODE_ONLY)) { set_thread_error(std::string(g.name) + " needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+    if (cfg->flags & XCK_F_UMI_CONSENSUS) {
+        if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("XCK_F_UMI_CONSENSUS needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+        if (!(cfg->mode & XCK_MODE_BAF)) { set_thread_error("XCK_F_UMI_CONSENSUS: the handle has no BAF pipeline"); return XCK_E_ARG; }
+    }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
     // the tag filter: the struct's fields, or - where the struct carries none - the knob; checked before a device is touched
@@ -132,6 +137,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     e->cell_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_CELL_SUMMARY) || e->knobs.cell_summary);
     e->feature_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_FEATURE_SUMMARY) || e->knobs.feature_summary);   // (does not imply the read summary)
     e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate || e->cell_summary);
+    e->umi_consensus = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BAF) && ((cfg->flags & XCK_F_UMI_CONSENSUS) || e->knobs.umi_consensus);   // (the knob: ignored by the other handles)
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
     e->n_cells = cfg->n_cells; e->n_contigs = cfg->n_contigs;
@@ -145,6 +151,8 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             if (e->read_fate) c.flags |= XCK_F_READ_FATE;      // (XCK_READ_FATE=1, or implied by the per-cell table)
             if (e->cell_summary) c.flags |= XCK_F_CELL_SUMMARY;  // (XCK_CELL_SUMMARY=1)
             if (e->feature_summary) c.flags |= XCK_F_FEATURE_SUMMARY;  // (XCK_FEATURE_SUMMARY=1)
+            c.flags &= ~XCK_F_UMI_CONSENSUS;                   // the pileup pipeline's rule alone (XCK_UMI_CONSENSUS=1)
+            if (e->umi_consensus && modes[k] == XCK_MODE_BAF) c.flags |= XCK_F_UMI_CONSENSUS;
             const int rc = engine_create(&c, e, &e->impls[k]);
             e->n_impl = k + 1;                                 // (a pipeline that failed half-way is destroyed with the rest)
             if (rc) { set_thread_error(e->err); xck_destroy(e); return rc; }
@@ -328,6 +336,15 @@ static int get_summary(xck_engine* e, int mode, T* out, bool xck_engine::*kept, 
 int xck_get_read_fate(xck_engine* e, int mode, xck_read_fate* out) { return get_summary(e, mode, out, &xck_engine::read_fate, "read_fate", "READ_FATE", engine_read_fate); }
 int xck_get_cell_summary(xck_engine* e, int mode, xck_cell_summary* out) { return get_summary(e, mode, out, &xck_engine::cell_summary, "cell_summary", "CELL_SUMMARY", engine_cell_summary); }
 int xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out) { return get_summary(e, mode, out, &xck_engine::feature_summary, "feature_summary", "FEATURE_SUMMARY", engine_feature_summary); }
+
+int xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_molecule_stats)) { e->err = "xck_molecule_stats.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (!e->umi_consensus || e->n_impl <= 0) { e->err = "handle made without XCK_F_UMI_CONSENSUS"; return XCK_E_STATE; }
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    return engine_molecule_stats(e->impls[e->n_impl - 1], out);         // (a fused handle answers from its pileup pipeline)
+}
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }
 

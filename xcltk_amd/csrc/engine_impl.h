@@ -214,6 +214,9 @@ struct EngineImpl {
     // by key - in workspace 1 after the partition sort, in d_keys after the radix sort - and the base the first read of every key
     // shows (workspace 1).  Valid from a successful finish to the next reset; nothing in the region stage takes memory in either place.
     const void* mol_keys = nullptr; uint8_t* mol_al = nullptr; size_t mol_n = 0; bool mol_valid = false;
+    // UMI consensus (XCK_F_UMI_CONSENSUS, umi_consensus.h): the five agreement counters in HBM, MOL_SLOTS copies that the getter sums (null = off: the molecule stage keeps the
+    // first read's base), filled by the molecule stage of xck_finish and valid from a successful finish to the next reset
+    unsigned long long* d_mol = nullptr; bool mol_stats_valid = false;
     // xck_refold (refold.h): the caller's SNP list as given to xck_create, the regrown tables' capacities, and the builder's own buffers
     std::vector<xck_snp> snps_in;
     size_t csr_reg_cap_bytes = 0, fmat_cap_bytes = 0;     // of d_csr_reg and d_fmat, which a refold may have to regrow
@@ -299,6 +302,8 @@ int launch_summaries(EngineImpl* im);                      // launch_queue: thei
 // defined in finish.hip
 int finish_init(EngineImpl* im);                           // engine_create: per-device attributes of the fold kernels
 int snp_verdicts(EngineImpl* im, uint32_t* d_kept);        // d_kept[s] = snp_passes() of sorted SNP s on the tallies of the last finish (enqueued on s_comp)
+int molecule_stats_init(EngineImpl* im);                   // engine_create, XCK_F_UMI_CONSENSUS on a pileup pipeline: the counters' memory (umi_consensus.h)
+int molecule_stats_reset(EngineImpl* im);                  // engine_reset: the counters zeroed on s_comp (the caller synchronises)
 // Control words go to the host through MAPPED pinned memory written by a tiny kernel, never through the DMA engines: a 4 KB hipMemcpy
 // D2H would queue behind a 170 MB result copy-out of another engine.  One block of `threads` on s_comp copies src[0, n) to host_alias
 // (a device alias of pinned words, d_hctl); the caller checks hipGetLastError().

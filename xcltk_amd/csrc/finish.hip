@@ -8,7 +8,8 @@
 //                 than 64), k_claim (gap records that hold a key earlier in fetch order), k_tally_rows, k_expand (per-SNP filters,
 //                 SNP -> region fan-out), region-level hits partitioned again and classified per item by an LDS hash set
 //                 (k_hap_items; fallback: sort + k_hap_class / k_hap_sum), k_hap_count / k_hap_scatter (AD / DP / OTH -> COO);
-//                 128-bit keys: k_first_read and the sorted path.  xck_refold (refold.h) runs the half behind k_tally_rows again; with a
+//                 128-bit keys: k_first_read and the sorted path.  XCK_F_UMI_CONSENSUS: a vote per key instead of the first read and no
+//                 claims (umi_consensus.h: k_consensus_base / k_consensus_read / k_consensus_long, the agreement counters).  xck_refold (refold.h) runs the half behind k_tally_rows again; with a
 //                 cell mask: k_row_bounds, k_tally_rows_cells / k_tally_long_cells (tallies of the enabled cells), k_expand<MASK>.
 //   snp_counts  : the SNP x cell matrices of the finished pileup from the molecule stage alone (snp_counts.h).
 //   group_counts: the row x group sums of the result blocks or of the SNP x cell blocks under a cell -> group mapping (group_counts.h).
@@ -1287,6 +1288,9 @@ static int first_reads_plain(EngineImpl* im, size_t n, const PileupFold<K>& pf) 
     return 0;
 }
 
+// the same stage under the handle's other rule (XCK_F_UMI_CONSENSUS): a plurality vote per key, and the agreement counters
+#include "umi_consensus.h"
+
 // one k_expand pass over the molecule stage: all cells, or (after xck_refold with a cell mask) the enabled ones under their tallies
 template <class K, bool EMIT>
 static void launch_expand(EngineImpl* im, size_t n, const PileupFold<K>& pf, const XBases& xb, int pack_shift) {
@@ -1410,6 +1414,11 @@ static int fold_molecules(EngineImpl* im, size_t n) {
     if ((rc = sort_pileup_hits<K>(im, n, tmpb, pf))) return rc;
     HIP_TRY(hipMemsetAsync(im->d_tally, 0, std::max<size_t>((size_t)im->n_snps_sorted * 5, 1) * sizeof(uint32_t), im->s_comp));
     HIP_TRY(hipMemsetAsync(pf.w1.long_runs, 0, sizeof(unsigned long long), im->s_comp));
+    if (im->d_mol) {                                                   // (XCK_F_UMI_CONSENSUS: the vote instead of the first read, no claims)
+        HIP_TRY(hipMemsetAsync(im->d_mol, 0, MOL_BUF_WORDS * sizeof(unsigned long long), im->s_comp));
+        if constexpr (sizeof(K) == 8) rc = split ? consensus_split<K>(im, n, pf) : consensus_plain<K>(im, n, pf);
+        else rc = consensus_plain<K>(im, n, pf);
+    } else
     if constexpr (sizeof(K) == 8) rc = split ? first_reads_split<K>(im, n, pf) : first_reads_plain<K>(im, n, pf);
     else rc = first_reads_plain<K>(im, n, pf);
     if (rc) return rc;
@@ -1460,14 +1469,16 @@ static int finish_t(EngineImpl* im) {
     const size_t n = im->cursor;
     im->d_tally_cur = nullptr; im->d_cell_bits = nullptr;          // (a finish counts every cell)
     for (int m = 0; m < 4; m++) { im->res_nnz[m] = 0; im->d_res[m] = nullptr; }
+    im->mol_stats_valid = false;
     { int64_t acc = 0; for (int sh = 0; sh < NSHARD; sh++) acc += (int64_t)im->h_ctl[ctl_accepted(sh)];
       im->st.n_hits = acc; }                          // accepted pairs (before the LDS de-duplication)
     im->st.n_hits_unique = (int64_t)(n + im->ncursor);   // keys that reached HBM
     join_stamps_report(im);
-    if (n == 0) { im->mol_keys = nullptr; im->mol_al = nullptr; im->mol_n = 0; im->mol_valid = im->mode == XCK_MODE_BAF; return 0; }
+    if (n == 0) { im->mol_keys = nullptr; im->mol_al = nullptr; im->mol_n = 0; im->mol_valid = im->mode == XCK_MODE_BAF; im->mol_stats_valid = im->d_mol != nullptr; return 0; }   // (the counters are zero since the reset)
     const int rc = im->mode == XCK_MODE_BASEFC ? finish_basefc<K>(im, n) : finish_pileup<K>(im, n);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
+    im->mol_stats_valid = im->d_mol != nullptr;
     return 0;
 }
 

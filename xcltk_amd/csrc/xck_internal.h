@@ -121,6 +121,7 @@ struct Knobs {
     bool cell_summary = false;           // XCK_CELL_SUMMARY=1: XCK_F_CELL_SUMMARY ORed into the flags of every handle that drives a GPU
     int  cell_summary_slots = 0;         // XCK_CELL_SUMMARY_SLOTS: rows of the per-block LDS tables (0 = the built-in 512 per-cell, 1024 per-feature / per-SNP; tests: small tables reach the no-fit path)
     bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
+    bool umi_consensus = false;          // XCK_UMI_CONSENSUS=1: XCK_F_UMI_CONSENSUS ORed into the flags of every handle with a BAF pipeline that drives a GPU
     int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
     bool gpu_parse = true;               // XCK_GPU_PARSE=auto|0: walk and parse the GPU-inflated chunks on the device where that applies (bam.cpp device_parse_now)
     bool gpu_names = false;              // XCK_GPU_NAMES=1: read names of a UMI-less handle are interned on the device (intern_dev.h; the conditions: api.cpp xck_create)
@@ -174,6 +175,7 @@ struct xck_engine {
     bool read_fate = false;              // made with XCK_F_READ_FATE (or XCK_READ_FATE=1), or with the flag below, which implies it
     bool cell_summary = false;           // made with XCK_F_CELL_SUMMARY (or XCK_CELL_SUMMARY=1)
     bool feature_summary = false;        // made with XCK_F_FEATURE_SUMMARY (or XCK_FEATURE_SUMMARY=1)
+    bool umi_consensus = false;          // made with XCK_F_UMI_CONSENSUS (or XCK_UMI_CONSENSUS=1) and a BAF pipeline: its molecule stage votes (umi_consensus.h)
     int umi_bits = 64;
     int32_t n_cells = 0, n_contigs = 0;  // bounds that caller-supplied batches are checked against (xck_push_batch)
     // host pinned batch staging used by xck_ingest_bam lives in the xck_bam
@@ -199,6 +201,7 @@ int  engine_stats(const EngineImpl* im, xck_stats* out);
 int  engine_read_fate(EngineImpl* im, xck_read_fate* out);         // read_fate.h
 int  engine_cell_summary(EngineImpl* im, xck_cell_summary* out);   // cell_summary.h
 int  engine_feature_summary(EngineImpl* im, xck_feature_summary* out);   // feature_summary.h
+int  engine_molecule_stats(EngineImpl* im, xck_molecule_stats* out);   // umi_consensus.h (finish.hip)
 int  engine_device(const xck_engine* e);      // HIP device of the handle (-1: decode-only handle)
 int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (sysfs, by PCI bus id); -1 = unknown
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE

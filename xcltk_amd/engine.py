@@ -93,7 +93,8 @@ class Engine(object):
     def __init__(self, mode, contig_names, regions, n_cells, snps=(), barcodes=None,
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
                  incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1,
-                 min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None):
+                 min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None,
+                 umi_consensus=False):
         """regions: iterable of (chrom, start1, end1_incl[, name]); snps: iterable of
         (chrom, pos1, ref, alt, ref_hap, alt_hap); chrom names must already be stripped of
         'chr' and present in contig_names.  excl_pairs = (region indices, snp indices): pairs left out of the SNP -> region
@@ -101,7 +102,10 @@ class Engine(object):
         their row index but are not counted by this engine (multi-GPU: another rank owns them).  tag_filter = (tag, value) or
         (tag, value, mask): only records whose first `tag` is an integer v >= 0 with (v & mask) == value count (xck_config.filter_tag;
         mask defaults to 0xFFFFFFFF; ("xf", 25) keeps what Cell Ranger counted); None leaves it to XCK_TAG_FILTER in the environment.
-        self.tag_filter is the (tag, value, mask) the handle applies, or None."""
+        self.tag_filter is the (tag, value, mask) the handle applies, or None.  umi_consensus=True (XCK_F_UMI_CONSENSUS; needs a BAF
+        pipeline): the base of a molecule is a plurality vote over its reads instead of its first read's, reads that span the SNP
+        in a gap abstain, and molecule_stats() says how often the reads of a molecule disagree; XCK_UMI_CONSENSUS=1 in the
+        environment does the same for every handle with a BAF pipeline."""
         self.lib = capi.load()
         self.mode = mode
         self.contig_names = list(contig_names)
@@ -169,7 +173,7 @@ class Engine(object):
         elif os.environ.get("XCK_TAG_FILTER"):                      # (xck_create checks the knob: a malformed one fails below)
             self.tag_filter = _parse_tag_filter(os.environ["XCK_TAG_FILTER"])
         cfg.n_threads = int(n_threads)
-        cfg.flags = int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0)
+        cfg.flags = int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0) | (capi.XCK_F_UMI_CONSENSUS if umi_consensus else 0)
         self.cfg = cfg
         self.n_cells = int(n_cells)
         self.n_regions = len(regions)
@@ -584,6 +588,19 @@ class Engine(object):
                     matrix=table(fs.matrix, n, int(fs.n_matrix_cols)) if fs.has_matrix else None,
                     snp=table(fs.snp, int(fs.n_snps), int(fs.n_snp_cols)), has_matrix=bool(fs.has_matrix),
                     read_cols=capi.FEATURE_READ_COLS, matrix_cols=capi.FEATURE_MATRIX_COLS[int(fs.mode)], snp_cols=capi.SNP_COLS)
+
+    def molecule_stats(self):
+        """How the reads of the molecules of the last finish() agree (xck_get_molecule_stats): dict of molecules, multi_read,
+        discordant, tied, changed in the struct's order, or None where the handle has nothing to say - made without umi_consensus /
+        XCK_F_UMI_CONSENSUS (and without XCK_UMI_CONSENSUS=1 in the environment), before finish() or after reset().  refold(),
+        snp_counts() and group_counts() do not change the counters."""
+        out = capi.MoleculeStats()
+        out.struct_size = C.sizeof(capi.MoleculeStats)
+        rc = self.lib.xck_get_molecule_stats(self.h, C.byref(out))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_molecule_stats")
+        return {k: int(getattr(out, k)) for k in capi.MOLECULE_FIELDS}
 
 
 class BamStream(object):

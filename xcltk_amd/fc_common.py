@@ -589,17 +589,44 @@ def write_snp_summary(eng, dist, path, snps, mode=None, log_prefix="[engine]", r
                           lambda a: "%s SNP summary: %d of %d SNPs kept" % (log_prefix, int((a[0][:, 6] > 0).sum()), len(a[0])))[0]
 
 
+def molecule_summary_text(stats, n_ranks=1, cut_contigs=0):
+    """Text of molecule_summary.tsv: one `name\\tcount` line per counter of xck_molecule_stats, in the struct's order; runs of several
+    ranks start with `#ranks=N cut_contigs=K`."""
+    from .capi import MOLECULE_FIELDS
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    return head + "".join("%s\t%d\n" % (k, int(stats[k])) for k in MOLECULE_FIELDS)
+
+
+def write_molecule_summary(eng, dist, path, log_prefix="[engine]"):
+    """How the reads of the molecules of the pileup agree (Engine.molecule_stats, after finish()) -> `path`, when the handle decides a
+    molecule's base by vote (XCK_UMI_CONSENSUS=1 in the environment, or XCK_F_UMI_CONSENSUS): nothing happens otherwise.  Multi-GPU:
+    a collective call - the counters are summed over the ranks and the writer rank writes the file.  Where a contig is cut over
+    ranks (cut_contigs > 0) a molecule with reads on both sides of a cut is counted by both neighbours: the sums then describe the
+    ranks' work, not the file.  Returns the (summed) dict or None."""
+    from .capi import MOLECULE_FIELDS
+    molecule_stats = getattr(eng, "molecule_stats", None)      # (an engine-like object without the method votes nowhere)
+    st = molecule_stats() if molecule_stats else None
+    if st is None:
+        return None
+    as_dict = lambda a: dict(zip(MOLECULE_FIELDS, a[0].tolist()))
+    return as_dict(_write_summary(dist, path, [[st[k] for k in MOLECULE_FIELDS]], lambda a, n_ranks, cut: molecule_summary_text(as_dict(a), n_ranks, cut),
+                                  lambda a: "%s UMI consensus: %d of %d molecules changed" % (log_prefix, as_dict(a)["changed"], as_dict(a)["molecules"])))
+
+
 def write_summaries(eng, dist, prefix, samples, regions, snps=None, mode=None, log_prefix="[engine]"):
     """The opt-in tables of one pipeline next to its matrices: `prefix` + read_summary.tsv (XCK_READ_FATE=1), cell_summary.tsv
-    (XCK_CELL_SUMMARY=1), feature_summary.tsv (XCK_FEATURE_SUMMARY=1) and - `snps` given, the pileup pipeline - snp_summary.tsv, each
-    only when the handle keeps it.  `prefix` is a path prefix: a directory with its separator, or e.g. <dir>/xcltk. ; mode names the
-    pipeline of a XCK_MODE_BOTH handle.  Multi-GPU: the writers' collective calls, in this order on every rank."""
+    (XCK_CELL_SUMMARY=1), feature_summary.tsv (XCK_FEATURE_SUMMARY=1), - `snps` given, the pileup pipeline - snp_summary.tsv and - the
+    pileup pipeline under XCK_UMI_CONSENSUS=1 - molecule_summary.tsv, each only when the handle keeps it.  `prefix` is a path
+    prefix: a directory with its separator, or e.g. <dir>/xcltk. ; mode names the pipeline of a XCK_MODE_BOTH handle.  Multi-GPU: the
+    writers' collective calls, in this order on every rank."""
     from .capi import XCK_MODE_BAF
     write_read_summary(eng, dist, prefix + "read_summary.tsv", mode, log_prefix)
     write_cell_summary(eng, dist, prefix + "cell_summary.tsv", samples, mode, log_prefix)
     write_feature_summary(eng, dist, prefix + "feature_summary.tsv", regions, mode, log_prefix)
     if snps is not None and (mode is None or mode & XCK_MODE_BAF):
         write_snp_summary(eng, dist, prefix + "snp_summary.tsv", snps, mode, log_prefix)
+    if getattr(eng, "mode", 0) & XCK_MODE_BAF and (mode is None or mode & XCK_MODE_BAF):
+        write_molecule_summary(eng, dist, prefix + "molecule_summary.tsv", log_prefix)
 
 
 # ----------------------------------------------------------------------------- engine driver
