@@ -109,8 +109,16 @@
  *                                         scratch slice, larger ones recompute them; regions of at most LDS_SNPS SNPs (default and upper bound 1024)
  *                                         keep their per-SNP state in LDS, larger ones in the slice; a launch has at most BLOCKS workgroups (default and upper
  *                                         bound 2048), which walk the regions of a level in a grid-stride loop.  None changes a result.
+ *   XCK_WRITE_MAP=1                       (read at every xck_write_mtx; csrc/mtx_writer.h) the text is formatted straight into a MAP_SHARED mapping of the
+ *                                         file, allocated at its final size first (regular files on file systems with fallocate; anything else, and a
+ *                                         failed allocation, takes the default path).  Unset or 0, the default: threads format into a ring of buffers
+ *                                         and the calling thread writes them in file order.  Identical bytes either way; the mapped path is the faster
+ *                                         one on tmpfs and the slower one where a write fault costs more than the copy it saves (ext4, overlayfs).
+ *                                         Either way a file that is already there is overwritten in place and cut to its new size, never emptied first.
+ *   XCK_WRITE_CHUNK_ENTRIES=<entries>     (read at every xck_write_mtx / xck_mtx_part_size / xck_write_mtx_part) entries per unit of work of the writer's
+ *                                         threads (default 262144, at most 2^24; tests: a small value cuts tiny matrices into many chunks)
  * Decoder (read when a BAM is opened or once per process): XCK_THREADS, XCK_NUMA=0, XCK_INFLATE=zlib, XCK_CHUNK_BYTES,
- * XCK_WRITE_THREADS (writer threads of xck_write_mtx), XCK_TEST_INTERN_LIMIT (tests). */
+ * XCK_WRITE_THREADS (writer threads of xck_write_mtx, read at every call), XCK_TEST_INTERN_LIMIT (tests). */
 #ifndef XCK_H
 #define XCK_H
 
