@@ -89,6 +89,12 @@
  *                                         molecule_summary.tsv next to their BAF matrices, and step 1 and step 3 of one `xcltk baf` run use the same
  *                                         rule.  Off (the default, or 0) the reference's first-read rule holds and every output is byte-identical.
  *                                         Basefc-only and decode-only handles ignore it.
+ *   XCK_MIN_BASEQ=<Q>                     (opt-in; 1 .. 93, unset or 0: off) every handle with a BAF pipeline that drives a GPU and whose
+ *                                         xck_config.min_baseq is 0 runs with that base-quality floor, as if the field were set: the front-ends
+ *                                         (afc_wrapper, afc_variants, pileup(), both `xcltk baf` paths) then log one line with the floor, the (read, SNP)
+ *                                         pairs that showed a base and those the floor masked.  A value above 93 or one that is not a number fails
+ *                                         xck_create with XCK_E_ARG.  Off, no quality byte is read, kept or copied and the default kernels run.
+ *                                         Basefc-only and decode-only handles ignore it.
  *   XCK_GROUP_LONG_ROW=<entries>          xck_group_counts: a source row with at least this many entries is summed by one block with a table in
  *                                         LDS, a shorter one by one wave in registers (default and upper bound 64, at least 1; tests: a small value
  *                                         reaches the block shape with small inputs)
@@ -226,6 +232,22 @@ typedef struct xck_config {
     char     filter_tag[4];
     uint32_t filter_mask;
     uint32_t filter_value;
+    /* Opt-in minimum base quality of the pileup's allele calls (samtools mpileup -Q, pysam min_base_quality).  0 = off; 1 .. 93: a
+     * (read, SNP) pair under an aligned block whose quality byte q at that query offset is not 0xff ("no quality stored", what BAM
+     * writes for `*`) and is below min_baseq shows no base - exactly like a read that spans the SNP in a gap: under the default
+     * molecule rule it still holds its (SNP, cell, UMI) key (a masked first read silences the molecule), under XCK_F_UMI_CONSENSUS it
+     * abstains.  Only allele codes change: the read filter, the hits (xck_stats.n_hits), the summaries' read classes and the basefc half
+     * of an XCK_MODE_BOTH handle are those of min_baseq = 0; tallies, min_count / min_maf, xck_refold, xck_snp_counts and
+     * xck_group_counts follow.  The mask is applied by the join: a refold cannot change it.  The qualities reach the join through
+     * xck_ingest_bam or xck_push_batch_q; xck_push_batch, xck_push_batch_device and xck_bam_next_batch answer XCK_E_STATE on such a
+     * handle.  XCK_E_ARG: a value outside 0 .. 93, a basefc-only handle, XCK_F_DECODE_ONLY.  XCK_MIN_BASEQ supplies it when it is 0.
+     * The field lies in what was the struct's tail padding, so sizeof(xck_config) is what it was and struct_size cannot tell a
+     * caller that knows the field from one whose padding holds whatever was on its stack: the field is read ONLY when flags holds
+     * XCK_F_MIN_BASEQ - a bit no earlier caller sets.  A C caller sets BOTH: `cfg.min_baseq = 13; cfg.flags |= XCK_F_MIN_BASEQ;`.
+     * Without the bit the four bytes are never looked at (so neither a floor nor the XCK_E_ARG cases above come from them); the bit
+     * on a struct whose struct_size ends before the field is XCK_E_ARG.  xck_get_baseq_stats answers XCK_E_STATE on a handle that
+     * ended up without a floor, which is how a caller checks that its floor was taken. */
+    int32_t  min_baseq;
 } xck_config;
 
 #define XCK_F_FORCE_KEY128   1  /* always use 128-bit sort keys (testing)                    */
@@ -256,6 +278,7 @@ typedef struct xck_config {
                                    table of xck_get_feature_summary) follows.  The same kernels count how often the reads of a
                                    molecule disagree (xck_get_molecule_stats).  Any handle with a BAF pipeline; on XCK_MODE_BOTH it
                                    affects the BAF half only.  XCK_E_ARG on a basefc-only handle and together with XCK_F_DECODE_ONLY */
+#define XCK_F_MIN_BASEQ    512  /* xck_config.min_baseq holds a value (see there); without the bit the field's bytes are not read    */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -436,6 +459,16 @@ typedef struct xck_molecule_stats {
                                    that the first-read rule would have called differently, gap reads aside                    */
 } xck_molecule_stats;
 
+/* The pairs the base-quality floor saw (xck_config.min_baseq / XCK_MIN_BASEQ; xck_get_baseq_stats): (read, SNP) pairs of the pileup
+ * pipeline's join since the last reset in which the read stores a base at the SNP, and those of them the floor masked.
+ * struct_size = sizeof(xck_baseq_stats), as for xck_decode_stats. */
+typedef struct xck_baseq_stats {
+    uint32_t struct_size;
+    int32_t  min_baseq;         /* the handle's floor                                         */
+    int64_t  pairs_with_base;
+    int64_t  pairs_masked;
+} xck_baseq_stats;
+
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
 
@@ -465,6 +498,12 @@ int  xck_push_batch(xck_engine* e, const xck_batch* b);
  * that decode on the GPU side); no copy is made and they must stay valid until xck_flush().
  * The contents cannot be checked from the host: the same invariants are the caller's word. */
 int  xck_push_batch_device(xck_engine* e, const xck_batch* b);
+/* xck_push_batch with the reads' base qualities, for a handle with a base-quality floor (xck_config.min_baseq): qual holds
+ * 2 * (seq_off[n] - seq_off[0]) bytes, two per sequence byte - the quality of query offset qi of read i at
+ * 2 * (seq_off[i] - seq_off[0]) + qi, the pad byte of an odd-length read 0xff, 0xff = "no quality stored" anywhere.  Checked and
+ * copied as xck_push_batch does; the caller may reuse qual on return.  On a handle without a floor qual is ignored (it may be NULL)
+ * and the call is xck_push_batch; with a floor a NULL qual is XCK_E_ARG unless the sequence range is empty. */
+int  xck_push_batch_q(xck_engine* e, const xck_batch* b, const uint8_t* qual);
 int  xck_flush(xck_engine* e);                    /* wait for all queued device work */
 /* Fold all hits into the final sparse matrices (on the GPU: partition + one LDS pass per work item, radix sort
  * as the fallback) and copy them to engine-owned pinned host memory. */
@@ -605,6 +644,10 @@ int  xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out);
  * the handle has failed; XCK_E_ARG for a null pointer or a short struct_size.  With contigs cut over several GPUs every handle counts
  * the molecules of the reads it saw; a molecule whose reads straddle a cut is counted by both neighbours. */
 int  xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out);
+/* The pair counters of the handle's base-quality floor (set out->struct_size first).  Waits for the handle's queued work as xck_flush
+ * does; xck_reset clears them, xck_finish and the derived calls do not change them.  A tile the join replays after an overflow counts
+ * once.  XCK_E_STATE on a handle without a floor (and on a decode-only handle), XCK_E_ARG for a null pointer or a short struct_size. */
+int  xck_get_baseq_stats(xck_engine* e, xck_baseq_stats* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

@@ -26,7 +26,7 @@ static unsigned long long batch_sum(const xck_batch& bt) {
                       if (bt.seq) for (uint32_t q = bt.seq_off[0]; q < bt.seq_off[bt.n_reads]; q++) s += bt.seq[q]; }
     return s + (unsigned long long)bt.contig * 1000003ull + bt.ordinal_base;
 }
-int  engine_push_block(xck_engine*, const void* base, size_t bytes, const xck_batch* bts, int n, void**, const NameTrailer*) {
+int  engine_push_block(xck_engine*, const void* base, size_t bytes, const xck_batch* bts, int n, void**, const NameTrailer*, const uint8_t*) {
     for (int i = 0; i < n; i++) {
         if (bts[i].n_reads > 0 && ((const char*)bts[i].pos < (const char*)base || (const char*)(bts[i].pos + bts[i].n_reads) > (const char*)base + bytes)) return XCK_E_ARG;
         g_push_sum += batch_sum(bts[i]); g_push_recs += bts[i].n_reads;

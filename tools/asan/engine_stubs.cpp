@@ -13,14 +13,15 @@ int  engine_feature_summary(EngineImpl*, xck_feature_summary*) { return XCK_E_AR
 // ---- csrc/pipeline.hip ----
 int  engine_create(const xck_config*, xck_engine*, EngineImpl**) { return XCK_E_ARG; }
 void engine_destroy(EngineImpl*) {}
-int  engine_push(EngineImpl*, const xck_batch*, bool) { return XCK_E_ARG; }
+int  engine_push(EngineImpl*, const xck_batch*, bool, const uint8_t*) { return XCK_E_ARG; }
+int  engine_baseq_stats(EngineImpl*, xck_baseq_stats*) { return XCK_E_ARG; }
 int  engine_flush(EngineImpl*) { return XCK_E_ARG; }
 int  engine_reset(EngineImpl*) { return XCK_E_ARG; }
 int  engine_stats(const EngineImpl*, xck_stats*) { return XCK_E_ARG; }
 int  engine_device(const xck_engine*) { return -1; }                          // no device: the decoder's GPU share of the inflate never starts
 int  engine_numa_node(const xck_engine*) { return -1; }
 // (weak: a program that wants to see the chunks a GPU-backed handle would get brings its own, tools/asan/decoder_asan.cpp)
-__attribute__((weak)) int engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**, const NameTrailer*) { return XCK_E_ARG; }
+__attribute__((weak)) int engine_push_block(xck_engine*, const void*, size_t, const xck_batch*, int, void**, const NameTrailer*, const uint8_t*) { return XCK_E_ARG; }
 int  engine_push_parsed(xck_engine*, const GpuInflateSlot*, size_t, size_t, size_t, size_t, size_t, int32_t, const DpBatch*, int, size_t) { return XCK_E_ARG; }
 int  engine_names_clear(xck_engine*, bool) { return 0; }
 int  engine_names_check(xck_engine*) { return 0; }

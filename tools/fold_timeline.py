@@ -7,7 +7,7 @@ f = glob.glob(sys.argv[1] + '/*/*_kernel_trace.csv')[0]
 lim = float(sys.argv[2]) if len(sys.argv) > 2 else 20.0
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r['Start_Timestamp']))
 name = lambda r: r['Kernel_Name'].replace('void ', '').replace('xck::', '').split('(')[0]
-j1 = [i for i, r in enumerate(rows) if 'k_join<unsigned long, 1>' in r['Kernel_Name']][-1]
+j1 = [i for i, r in enumerate(rows) if 'k_join<unsigned long, 1' in r['Kernel_Name']][-1]
 seg = rows[j1 + 1:]
 stop = [i for i, r in enumerate(seg) if 'k_join' in r['Kernel_Name'] or 'k_tile_meta' in r['Kernel_Name']]
 if stop: seg = seg[:stop[0]]

@@ -3,6 +3,8 @@
 // PARSE_CHUNK_BLOCKS (128) blocks, and every column of every kept record must equal what the host decoder writes for the chunk.
 // A chunk the device flags (contig runs beyond the list, a UMI to intern, ...) is counted, and must be one the host would not have
 // parsed with direct keys only.  Prints "N chunks, R records compared: D differences, F chunks flagged"; exit status 0 iff D == 0.
+// PARSE_QUAL=1 (with sequence columns): both parsers also fill the quality region of a handle with a base-quality floor, and the regions -
+// pad bytes included - are compared like a column; the line then ends in ", Q quality bytes compared".
 // Environment: PARSE_SEQ=0 (no sequence columns), PARSE_DROP=k (every k-th reference is not wanted), PARSE_TEND=p (position windows end at p).
 // The program links the decoder (bam.o, bam_records.o) and the device decoder; the engine is not part of it (tools/asan/engine_stubs.cpp).
 #include "../xcltk_amd/csrc/bam_decode.h"
@@ -13,6 +15,7 @@
 int main(int argc, char** argv) {
     if (argc < 3) { fprintf(stderr, "usage: %s FILE.bam BARCODES.txt\n", argv[0]); return 2; }
     const bool want_seq = !(getenv("PARSE_SEQ") && atoi(getenv("PARSE_SEQ")) == 0);
+    const bool want_qual = want_seq && getenv("PARSE_QUAL") && atoi(getenv("PARSE_QUAL")) != 0;
     const int drop = getenv("PARSE_DROP") ? atoi(getenv("PARSE_DROP")) : 0, tend = getenv("PARSE_TEND") ? atoi(getenv("PARSE_TEND")) : 0;
     const size_t per = getenv("PARSE_CHUNK_BLOCKS") ? (size_t)atoi(getenv("PARSE_CHUNK_BLOCKS")) : 128;
     xck_bam* b = nullptr; char err[256] = {0};
@@ -34,7 +37,7 @@ int main(int argc, char** argv) {
     void* d_cm = dev_parse_upload(0, cm.t2c, (size_t)n_refs * 4, cm.t_end, cm.t_end ? (size_t)n_refs * 4 : 0);
     void* d_bc = e.dec.bc_slots.empty() ? nullptr : dev_parse_upload(0, e.dec.bc_slots.data(), e.dec.bc_slots.size() * sizeof(DecodeCfg::BcSlot), nullptr, 0);
     hipStream_t stream; if (hipStreamCreate(&stream) != hipSuccess) return 2;
-    long n_chunks = 0, n_flagged = 0, n_bad_flag = 0, n_cmp = 0, n_diff = 0; uint32_t all_flags = 0;
+    long n_chunks = 0, n_flagged = 0, n_bad_flag = 0, n_cmp = 0, n_diff = 0, n_qual = 0; uint32_t all_flags = 0;
     for (size_t i0 = 0; i0 < blocks.size(); i0 += per) {
         const size_t nb = std::min(per, blocks.size() - i0); const uint32_t skip = i0 == 0 ? b->first_skip : 0;
         size_t tin = 0, usz = 0;
@@ -65,7 +68,7 @@ int main(int argc, char** argv) {
         all_flags |= gs->h_head->walk_flags;
         std::atomic<int> hflags{0}; DecodeTimes tm; e.intern.clear();
         if (aligned && n_cig < (1u << 30) && n_seq < (1u << 30)) {
-            if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) return 2;
+            if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1, 0, 0, false, want_qual)) return 2;
             memset(s.base, 0, s.used);
             wp.n_out = n_out; wp.n_cig = n_cig; wp.n_seq = n_seq;                    // (one piece, at the block's start: what layout_chunk makes of a chunk of one part)
             parse_part(&tm, &e, &s, 0, &wp, cm, &hflags);
@@ -80,7 +83,7 @@ int main(int argc, char** argv) {
         if (!aligned || lay.n_out != n_out || lay.n_cig != n_cig || lay.n_seq != n_seq) { n_diff++; fprintf(stderr, "chunk at block %zu: counts differ (%zu/%zu records)\n", i0, lay.n_out, n_out); soa_free(s); continue; }
         uint8_t* d_soa = nullptr; if (hipMalloc((void**)&d_soa, s.used) != hipSuccess || hipMemset(d_soa, 0, s.used) != hipSuccess) return 2;
         DpParseCfg pc; memset(&pc, 0, sizeof pc);
-        pc.bc = (const DpBcSlot*)d_bc; pc.bc_mask = e.dec.bc_mask; pc.use_barcodes = e.dec.use_barcodes; pc.want_seq = want_seq; pc.umi_bits = e.dec.umi_bits; pc.sample = 0;
+        pc.bc = (const DpBcSlot*)d_bc; pc.bc_mask = e.dec.bc_mask; pc.use_barcodes = e.dec.use_barcodes; pc.want_seq = want_seq; pc.umi_bits = e.dec.umi_bits; pc.sample = 0; pc.want_qual = want_qual;
         memcpy(pc.cell_tag, e.dec.cell_tag, 2); memcpy(pc.umi_tag, e.dec.umi_tag, 2);
         if (dev_parse_launch(stream, gs, nb, lay.max_rec, pc, d_soa, n_out, n_cig, n_seq) != 0 || hipStreamSynchronize(stream) != hipSuccess) { fprintf(stderr, "parse launch failed\n"); return 2; }
         all_flags |= gs->h_head->parse_flags;
@@ -91,17 +94,20 @@ int main(int argc, char** argv) {
         else {
             std::vector<uint8_t> got(s.used); if (hipMemcpy(got.data(), d_soa, s.used, hipMemcpyDeviceToHost) != hipSuccess) return 2;
             const SoaLayout l = soa_layout(n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1);
-            struct { const char* name; size_t off, bytes; } col[9] = { {"umi", l.o_umi, n_out * 8}, {"pos", l.o_pos, n_out * 4}, {"cell", l.o_cell, n_out * 4}, {"cig_off", l.o_cgo, (n_out + 1) * 4},
-                {"seq_off", l.o_sqo, (n_out + 1) * 4}, {"cigar", l.o_cig, n_cig * 4}, {"flag", l.o_flag, n_out * 2}, {"mapq", l.o_mapq, n_out}, {"seq", l.o_seq, want_seq ? n_seq : 0} };
+            struct { const char* name; size_t off, bytes; } col[10] = { {"umi", l.o_umi, n_out * 8}, {"pos", l.o_pos, n_out * 4}, {"cell", l.o_cell, n_out * 4}, {"cig_off", l.o_cgo, (n_out + 1) * 4},
+                {"seq_off", l.o_sqo, (n_out + 1) * 4}, {"cigar", l.o_cig, n_cig * 4}, {"flag", l.o_flag, n_out * 2}, {"mapq", l.o_mapq, n_out}, {"seq", l.o_seq, want_seq ? n_seq : 0},
+                {"qual", l.total, want_qual ? 2 * n_seq : 0} };                              // (behind the layout's total: two bytes per sequence byte, the pads among them)
             for (auto& c : col) if (memcmp(got.data() + c.off, s.base + c.off, c.bytes) != 0) {
                 size_t k = 0; while (got[c.off + k] == s.base[c.off + k]) k++;
                 n_diff++; fprintf(stderr, "chunk at block %zu: column %s differs at byte %zu of %zu\n", i0, c.name, k, c.bytes);
             }
-            n_cmp += (long)n_out;
+            n_cmp += (long)n_out; if (want_qual) n_qual += (long)(2 * n_seq);
         }
         (void)hipFree(d_soa); soa_free(s);
     }
-    printf("%ld chunks, %ld records compared: %ld differences, %ld chunks flagged (flags %u), %ld flagged without cause\n", n_chunks, n_cmp, n_diff, n_flagged, all_flags, n_bad_flag);
+    printf("%ld chunks, %ld records compared: %ld differences, %ld chunks flagged (flags %u), %ld flagged without cause", n_chunks, n_cmp, n_diff, n_flagged, all_flags, n_bad_flag);
+    if (want_qual) printf(", %ld quality bytes compared", n_qual);
+    printf("\n");
     dev_parse_free(0, d_cm); dev_parse_free(0, d_bc); gpu_inflate_slot_destroy(gs); xck_bam_close(b);
     return n_diff == 0 && n_bad_flag == 0 ? 0 : 1;
 }

@@ -24,6 +24,7 @@ XCK_F_READ_FATE = 32
 XCK_F_CELL_SUMMARY = 64
 XCK_F_FEATURE_SUMMARY = 128
 XCK_F_UMI_CONSENSUS = 256
+XCK_F_MIN_BASEQ = 512
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -62,6 +63,21 @@ class Config(C.Structure):
         ("n_excl_pairs", C.c_int32), ("excl_region", C.POINTER(C.c_int32)), ("excl_snp", C.POINTER(C.c_int32)),
         ("filter_tag", C.c_char * 4), ("filter_mask", C.c_uint32), ("filter_value", C.c_uint32),
     ]
+    # xck_config.min_baseq lies in the four bytes behind filter_value that were the struct's tail padding (the size did not change); the
+    # library reads them only when flags holds XCK_F_MIN_BASEQ.  Set through Config.min_baseq, which sets or clears the bit with it.
+    MIN_BASEQ_OFFSET = 172
+
+    @property
+    def min_baseq(self):
+        return C.c_int32.from_buffer(self, Config.MIN_BASEQ_OFFSET).value
+
+    @min_baseq.setter
+    def min_baseq(self, q):
+        C.c_int32.from_buffer(self, Config.MIN_BASEQ_OFFSET).value = int(q)
+        self.flags = (self.flags | XCK_F_MIN_BASEQ) if int(q) else (self.flags & ~XCK_F_MIN_BASEQ)
+
+
+MIN_BASEQ_MAX = 93
 
 
 class RefoldConfig(C.Structure):
@@ -170,6 +186,10 @@ class MoleculeStats(C.Structure):
         "molecules", "multi_read", "discordant", "tied", "changed")]
 
 
+class BaseqStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_baseq", C.c_int32), ("pairs_with_base", C.c_int64), ("pairs_masked", C.c_int64)]
+
+
 # the counters of xck_molecule_stats in the struct's order
 MOLECULE_FIELDS = tuple(k for k, _ in MoleculeStats._fields_[2:])
 
@@ -217,6 +237,7 @@ SYMBOLS = [
     ("xck_umi_bits", C.c_int, [C.c_void_p]),
     ("xck_push_batch", C.c_int, [C.c_void_p, _P(Batch)]),
     ("xck_push_batch_device", C.c_int, [C.c_void_p, _P(Batch)]),
+    ("xck_push_batch_q", C.c_int, [C.c_void_p, _P(Batch), _P(C.c_uint8)]),
     ("xck_flush", C.c_int, [C.c_void_p]),
     ("xck_finish", C.c_int, [C.c_void_p, _P(Result)]),
     ("xck_finish_async", C.c_int, [C.c_void_p]),
@@ -231,6 +252,7 @@ SYMBOLS = [
     ("xck_get_cell_summary", C.c_int, [C.c_void_p, C.c_int, _P(CellSummary)]),
     ("xck_get_feature_summary", C.c_int, [C.c_void_p, C.c_int, _P(FeatureSummary)]),
     ("xck_get_molecule_stats", C.c_int, [C.c_void_p, _P(MoleculeStats)]),
+    ("xck_get_baseq_stats", C.c_int, [C.c_void_p, _P(BaseqStats)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

@@ -64,6 +64,14 @@ Knobs xck::Knobs::from_env() {
     k.cell_summary = num("XCK_CELL_SUMMARY", 0) != 0;
     k.feature_summary = num("XCK_FEATURE_SUMMARY", 0) != 0;
     k.umi_consensus = num("XCK_UMI_CONSENSUS", 0) != 0;
+    if (*str("XCK_MIN_BASEQ")) {                                         // decimal digits only, 0 .. 93; anything else: -1, and xck_create quotes the text
+        k.min_baseq_text = str("XCK_MIN_BASEQ");
+        const std::string& t = k.min_baseq_text;
+        long long v = 0;
+        bool ok = t.size() <= 3;
+        for (char c : t) { ok = ok && c >= '0' && c <= '9'; v = v * 10 + (c - '0'); }
+        k.min_baseq = ok && v <= 93 ? (int)v : -1;
+    }
     k.group_long_row = (int)std::max(1ll, std::min(64ll, num("XCK_GROUP_LONG_ROW", 64)));
     k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
     if (*str("XCK_TAG_FILTER")) {                                        // TAG:VALUE[/MASK], numbers decimal or 0x hex, MASK defaults to all ones
@@ -98,8 +106,15 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     *out = nullptr;
     // ABI 1 structs (without the exclusion pairs) are accepted: the missing tail reads as zero
     // ... and so are those without the tag filter (they end where filter_tag begins): no filter from the struct
+    // (min_baseq sits in what was the tail padding: the size did not change, and sizeof - 4 - where the field begins - is no accepted size)
+    static_assert(offsetof(xck_config, min_baseq) == 172 && sizeof(xck_config) == 176, "min_baseq fills the old tail padding");
     if (cfg_in->struct_size != offsetof(xck_config, n_excl_pairs) && cfg_in->struct_size != offsetof(xck_config, filter_tag) && cfg_in->struct_size != sizeof(xck_config)) { set_thread_error("xck_config.struct_size mismatch (ABI)"); return XCK_E_ARG; }
     xck_config cfg_full; memset(&cfg_full, 0, sizeof cfg_full); memcpy(&cfg_full, cfg_in, cfg_in->struct_size); cfg_full.struct_size = sizeof(xck_config);
+    // the bytes of min_baseq are a caller's padding unless it says otherwise (XCK_F_MIN_BASEQ); a struct that ends before the field cannot
+    // say so - refused, not ignored: the caller asked for a floor and would get none
+    if (cfg_in->struct_size > offsetof(xck_config, flags) && (cfg_full.flags & XCK_F_MIN_BASEQ) && cfg_in->struct_size != sizeof(xck_config)) {
+        set_thread_error("XCK_F_MIN_BASEQ on an xck_config whose struct_size ends before min_baseq"); return XCK_E_ARG; }
+    if (!(cfg_full.flags & XCK_F_MIN_BASEQ)) cfg_full.min_baseq = 0;
     const xck_config* cfg = &cfg_full;
     if (cfg->n_excl_pairs < 0 || (cfg->n_excl_pairs > 0 && (!cfg->excl_region || !cfg->excl_snp))) { set_thread_error("invalid exclusion pairs"); return XCK_E_ARG; }
     if (cfg->mode != XCK_MODE_BASEFC && cfg->mode != XCK_MODE_BAF && cfg->mode != XCK_MODE_BOTH) { set_thread_error("invalid mode"); return XCK_E_ARG; }
@@ -112,8 +127,14 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
         if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("XCK_F_UMI_CONSENSUS needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
         if (!(cfg->mode & XCK_MODE_BAF)) { set_thread_error("XCK_F_UMI_CONSENSUS: the handle has no BAF pipeline"); return XCK_E_ARG; }
     }
+    if (cfg->min_baseq) {
+        if (cfg->min_baseq < 0 || cfg->min_baseq > 93) { set_thread_error("xck_config.min_baseq outside 0 .. 93"); return XCK_E_ARG; }
+        if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("xck_config.min_baseq needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+        if (!(cfg->mode & XCK_MODE_BAF)) { set_thread_error("xck_config.min_baseq: the handle has no BAF pipeline"); return XCK_E_ARG; }
+    }
     xck_engine* e = new xck_engine();
     e->knobs = Knobs::from_env();
+    if (e->knobs.min_baseq < 0) { set_thread_error("malformed XCK_MIN_BASEQ \"" + e->knobs.min_baseq_text + "\": expected a number in 0 .. 93"); delete e; return XCK_E_ARG; }
     // the tag filter: the struct's fields, or - where the struct carries none - the knob; checked before a device is touched
     {
         DecodeCfg& d = e->dec;
@@ -134,6 +155,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     e->feature_summary = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_FEATURE_SUMMARY) || e->knobs.feature_summary);   // (does not imply the read summary)
     e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate || e->cell_summary);
     e->umi_consensus = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BAF) && ((cfg->flags & XCK_F_UMI_CONSENSUS) || e->knobs.umi_consensus);   // (the knob: ignored by the other handles)
+    e->min_baseq = cfg->min_baseq ? cfg->min_baseq : (!(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BAF)) ? e->knobs.min_baseq : 0;   // (the knob: ignored by the other handles)
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
     e->n_cells = cfg->n_cells; e->n_contigs = cfg->n_contigs;
@@ -149,6 +171,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             if (e->feature_summary) c.flags |= XCK_F_FEATURE_SUMMARY;  // (XCK_FEATURE_SUMMARY=1)
             c.flags &= ~XCK_F_UMI_CONSENSUS;                   // the pileup pipeline's rule alone (XCK_UMI_CONSENSUS=1)
             if (e->umi_consensus && modes[k] == XCK_MODE_BAF) c.flags |= XCK_F_UMI_CONSENSUS;
+            c.min_baseq = modes[k] == XCK_MODE_BAF ? e->min_baseq : 0;   // (XCK_MIN_BASEQ folded in)
             const int rc = engine_create(&c, e, &e->impls[k]);
             e->n_impl = k + 1;                                 // (a pipeline that failed half-way is destroyed with the rest)
             if (rc) { set_thread_error(e->err); xck_destroy(e); return rc; }
@@ -162,6 +185,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     if (d.use_umi) { d.umi_tag[0] = cfg->umi_tag[0]; d.umi_tag[1] = cfg->umi_tag[1]; }
     d.umi_bits = e->umi_bits;
     d.want_seq = (cfg->mode & XCK_MODE_BAF) != 0;
+    d.want_qual = e->min_baseq > 0;
     const int crc_flags = cfg->flags | (e->knobs.verify_crc == 2 ? XCK_F_DEVICE_CRC : e->knobs.verify_crc == 1 ? XCK_F_VERIFY_CRC : 0);
     d.verify_crc = (crc_flags & (XCK_F_VERIFY_CRC | XCK_F_DEVICE_CRC)) != 0;
     d.crc_on_device = (crc_flags & XCK_F_DEVICE_CRC) != 0;
@@ -218,7 +242,12 @@ static int check_host_batch(xck_engine* e, const xck_batch* b) {
     if (bad) { e->err = "batch: offsets run backwards or a cell index is outside the cell table"; return XCK_E_ARG; }
     return XCK_OK;
 }
-extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* b) { return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, false); }); } } }
+extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* b, const uint8_t* qual) { return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, false, qual); }); } } }
+// what the calls that carry no qualities answer on a handle whose pileup needs them
+static int needs_qualities(xck_engine* e, const char* who) {
+    e->err = std::string(who) + ": the handle has a base-quality floor (xck_config.min_baseq / XCK_MIN_BASEQ = " + std::to_string(e->min_baseq) + ") and this call carries no qualities; use xck_push_batch_q or xck_ingest_bam";
+    return XCK_E_STATE;
+}
 
 // xck_push_batch, one-copy form for SMALL batches: the caller's nine arrays are packed into ONE engine-owned pinned block (ring of
 // three), which crosses PCIe with ONE hipMemcpyAsync into a device staging slot shared by the handle's pipelines
@@ -229,14 +258,15 @@ extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* 
 // arrays are pinned or plain numpy memory, the packed form 0.6 G reads/s (a host memcpy is slower than the DMA it saves) - so
 // the packed form is used where the nine calls and the wait dominate: below XCK_PUSH_STAGE_BYTES (default 2 MB) per batch.
 // XCK_PUSH_STAGE=0 / 1 forces one form.
-static int push_staged(xck_engine* e, const xck_batch* b) {
+static int push_staged(xck_engine* e, const xck_batch* b, const uint8_t* qual) {
     const bool seq = (e->mode & XCK_MODE_BAF) != 0;
     const size_t n = (size_t)b->n_reads;
     const uint32_t c_lo = b->cig_off[0], s_lo = seq ? b->seq_off[0] : 0;
     const size_t n_cig = b->cig_off[n] - c_lo, n_seq = seq ? b->seq_off[n] - s_lo : 0;
-    struct Seg { const void* src; size_t bytes, off; } seg[9] = {
+    struct Seg { const void* src; size_t bytes, off; } seg[10] = {
         { b->pos, n * 4, 0 }, { b->flag, n * 2, 0 }, { b->mapq, n, 0 }, { b->cell, n * 4, 0 }, { b->umi, n * 8, 0 }, { b->cig_off, (n + 1) * 4, 0 },
-        { b->cigar ? b->cigar + c_lo : nullptr, n_cig * 4, 0 }, { seq ? b->seq_off : nullptr, seq ? (n + 1) * 4 : 0, 0 }, { seq && b->seq ? b->seq + s_lo : nullptr, n_seq, 0 } };
+        { b->cigar ? b->cigar + c_lo : nullptr, n_cig * 4, 0 }, { seq ? b->seq_off : nullptr, seq ? (n + 1) * 4 : 0, 0 }, { seq && b->seq ? b->seq + s_lo : nullptr, n_seq, 0 },
+        { qual, qual ? 2 * n_seq : 0, 0 } };                               // (a handle with a base-quality floor: the tenth column)
     size_t total = 0;
     for (auto& g : seg) { g.off = total; total += (g.bytes + 255) & ~size_t(255); }
     xck_engine::PushRing& ring = e->push_ring;
@@ -274,20 +304,41 @@ static int push_staged(xck_engine* e, const xck_batch* b) {
     sb.cigar = (const uint32_t*)(base + seg[6].off) - c_lo;               // rebased: never read below c_lo
     sb.seq_off = seq ? (const uint32_t*)(base + seg[7].off) : nullptr;
     sb.seq = seq ? (const uint8_t*)(base + seg[8].off) - s_lo : nullptr;
-    return engine_push_block(e, base, total, &sb, 1, &ring.fence[k]);
+    return engine_push_block(e, base, total, &sb, 1, &ring.fence[k], nullptr, qual ? (const uint8_t*)(base + seg[9].off) - 2 * (size_t)s_lo : nullptr);
 }
-int xck_push_batch(xck_engine* e, const xck_batch* b) {
-    if (!e || !b) return XCK_E_ARG;
+static int push_host_batch(xck_engine* e, const xck_batch* b, const uint8_t* qual) {
     if (int rc = check_host_batch(e, b)) return rc;
-    if (b->n_reads <= 0 || b->contig < 0 || e->n_impl <= 0) return push_trusted(e, b);     // nothing to copy / decode-only: reported there
+    if (b->n_reads <= 0 || b->contig < 0 || e->n_impl <= 0) return push_trusted(e, b, qual);     // nothing to copy / decode-only: reported there
     const int force = e->knobs.push_stage;
     const long long small = e->knobs.push_stage_bytes;
     const size_t n = (size_t)b->n_reads;
+    // (the join addresses a quality byte as 2 * sequence offset + query offset in 32 bits)
+    if (qual && (e->mode & XCK_MODE_BAF) && b->seq_off[n] >= (1u << 31)) { e->err = "xck_push_batch_q: sequence offsets of 2^31 and above"; return XCK_E_ARG; }
     const size_t bytes = n * 27 + (size_t)(b->cig_off[n] - b->cig_off[0]) * 4 + ((e->mode & XCK_MODE_BAF) ? n * 4 + (b->seq_off[n] - b->seq_off[0]) : 0);
     const bool stage = force >= 0 ? force != 0 : (long long)bytes < small;
-    return stage ? push_staged(e, b) : push_trusted(e, b);
+    return stage ? push_staged(e, b, qual) : push_trusted(e, b, qual);
 }
-int xck_push_batch_device(xck_engine* e, const xck_batch* b) { if (!e || !b) return XCK_E_ARG; return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, true); }); }
+int xck_push_batch(xck_engine* e, const xck_batch* b) {
+    if (!e || !b) return XCK_E_ARG;
+    if (e->min_baseq > 0) return needs_qualities(e, "xck_push_batch");
+    return push_host_batch(e, b, nullptr);
+}
+int xck_push_batch_q(xck_engine* e, const xck_batch* b, const uint8_t* qual) {
+    if (!e || !b) return XCK_E_ARG;
+    if (e->min_baseq <= 0) return push_host_batch(e, b, nullptr);        // no floor: qual is ignored
+    if (!qual) {                                                         // (only a batch without sequence bytes needs none: a byte that is never read stands in)
+        static const uint8_t none = 0xff;
+        const bool empty = b->n_reads <= 0 || b->contig < 0 || (b->seq_off && b->seq_off[b->n_reads] == b->seq_off[0]);
+        if (!empty) { e->err = "xck_push_batch_q: null qual on a handle with a base-quality floor"; return XCK_E_ARG; }
+        qual = &none;
+    }
+    return push_host_batch(e, b, qual);
+}
+int xck_push_batch_device(xck_engine* e, const xck_batch* b) {
+    if (!e || !b) return XCK_E_ARG;
+    if (e->min_baseq > 0) return needs_qualities(e, "xck_push_batch_device");
+    return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, true); });
+}
 int xck_flush(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_flush); }
 int xck_reset(xck_engine* e) {
     if (!e) return XCK_E_ARG;
@@ -340,6 +391,15 @@ int xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out) {
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
     return engine_molecule_stats(e->impls[e->n_impl - 1], out);         // (a fused handle answers from its pileup pipeline)
+}
+
+int xck_get_baseq_stats(xck_engine* e, xck_baseq_stats* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_baseq_stats)) { e->err = "xck_baseq_stats.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (e->min_baseq <= 0 || e->n_impl <= 0) { e->err = "handle made without a base-quality floor (xck_config.min_baseq / XCK_MIN_BASEQ)"; return XCK_E_STATE; }
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    return engine_baseq_stats(e->impls[e->n_impl - 1], out);            // (a fused handle answers from its pileup pipeline)
 }
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }

@@ -482,6 +482,7 @@ static ChunkJob* take_job(xck_engine* e, xck_bam* b) {
     if (j.soa.fence) fence_wait(j.soa.fence);                           // the H2D copy that last read this block has completed
     j.e = e; j.flags.store(0); j.parsed.store(0); j.ring_idx = -1; j.batches.clear(); j.dev = false;
     j.b = b; j.names = e->names_mode && b->defer_parse;                          // (xck_ingest_bam on a handle in device-names mode)
+    j.qual = e->dec.want_qual;
     return &j;
 }
 // what a chunk's parse tasks reported (flags 1 / 2: parse_record; a task that threw) -> error code and text, 0 if nothing.  Call after tg.wait().
@@ -537,7 +538,7 @@ void Pusher::run() {
             for (size_t i = 0; i < bts.size(); i++) fill_batch(s, j->batches[i], e->dec.want_seq, &bts[i]);
             const bool names = j->names && s.has_names && s.nt.n_out > 0;
             if (names && j->b) j->b->dstat[DS_NAMES_HOST_CHUNKS].fetch_add(1, std::memory_order_relaxed);
-            try { r = xck::engine_push_block(e, s.base, s.used, bts.data(), (int)bts.size(), &s.fence, names ? &s.nt : nullptr); } catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
+            try { r = xck::engine_push_block(e, s.base, s.used, bts.data(), (int)bts.size(), &s.fence, names ? &s.nt : nullptr, s.qual); } catch (const std::bad_alloc&) { r = XCK_E_NOMEM; } catch (...) { r = XCK_E_IO; }
             if (r) msg = e->err;
             push_ns += ns_since(t0);
         }
@@ -962,6 +963,7 @@ static int next_batch_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, 
     CallerBinding on_node(b);
     FoldDecodeStats fold{e, b};
     b->defer_parse = false;                                            // (this interface hands out finished batches: parse in place)
+    if (e->dec.want_qual) { e->err = "xck_bam_next_batch on a handle with a base-quality floor (xck_config.min_baseq / XCK_MIN_BASEQ): the batches it hands out carry no qualities; use xck_ingest_bam"; return XCK_E_STATE; }
     if (const int src = names_state_check(e, b, 2)) return src;
     while (!b->cur || b->cur->batches.empty()) {
         if (b->done) return 0;

@@ -100,6 +100,8 @@ struct HostSoA {
     // device-names mode: behind the columns (SoaLayout::total) one DiItem per kept record and the packed bytes of the names that have
     // to be interned - the parse tasks fill them, the block's copy takes them along (engine_push_block)
     bool has_names = false; xck::NameTrailer nt{0, 0, 0, 0}; xck::DiItem* items = nullptr; uint8_t* name_bytes = nullptr;
+    // a handle with a base-quality floor: the quality region (parse_dev.h soa_qual_bytes) between the columns and the name trailer, else null
+    uint8_t* qual = nullptr;
 };
 
 struct RecRef { const uint8_t* p; uint32_t len; int32_t tid; uint32_t l_seq; uint16_t n_cig; };
@@ -253,6 +255,7 @@ struct ChunkJob {
     // flags the chunk, takes it down the host path itself (redo_on_host), for which it needs what the coordinator knew
     bool dev = false; xck_bam* b = nullptr; DpChunkLayout lay; ContigMap cm; xck_ingest_opts opts; int64_t rec_before = 0;
     bool names = false;                // device-names mode: the chunk's names are keyed by the handle's device table (take_job)
+    bool qual = false;                 // the handle has a base-quality floor: the block carries the records' qualities (take_job)
 };
 struct Pusher {
     static constexpr int MAXQ = PUSH_Q; // jobs the coordinator may run ahead
@@ -326,7 +329,7 @@ namespace xck {
 // the part of encode_key() that needs no table: empty string -> NONE, short ACGT string -> 2-bit code
 bool encode_key_direct(const char* s, size_t n, int umi_bits, uint64_t* out);
 // carve the columns of a chunk with n_reads kept records out of the block (growing it if needed)
-bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t name_items = 0, size_t name_bytes = 0, bool names = false);
+bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t name_items = 0, size_t name_bytes = 0, bool names = false, bool qual = false);
 void soa_free(HostSoA& s);
 // a batch = a slice of the chunk's SoA block
 void fill_batch(const HostSoA& s, const PendingBatch& pb, bool want_seq, xck_batch* bt);

@@ -212,10 +212,11 @@ void soa_free(HostSoA& s) {
     s = HostSoA();
 }
 // carve the columns of a chunk with n_reads kept records out of the block (growing it if needed)
-bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t name_items, size_t name_bytes, bool names) {
+bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t name_items, size_t name_bytes, bool names, bool qual) {
     const SoaLayout l = soa_layout(n_reads, n_cig, n_seq);                // (parse_dev.h: the parse kernel writes the same block)
     const size_t items_bytes = (name_items * sizeof(DiItem) + 255) & ~size_t(255);
-    const size_t total = l.total + (names ? items_bytes + ((name_bytes + 255) & ~size_t(255)) : 0);   // (the names: a trailer behind the layout's total)
+    const size_t qual_bytes = qual ? soa_qual_bytes(n_seq) : 0;           // (the qualities: behind the layout's total, in front of the names)
+    const size_t total = l.total + qual_bytes + (names ? items_bytes + ((name_bytes + 255) & ~size_t(255)) : 0);   // (the names: a trailer behind them)
     if (total > s.cap) {
         if (s.fence) fence_wait(s.fence);
         if (s.base) { if (s.pinned) pinned_free(s.base); else free(s.base); }
@@ -229,7 +230,8 @@ bool soa_reserve(HostSoA& s, size_t n_reads, size_t n_cig, size_t n_seq, size_t 
     s.umi = (uint64_t*)(s.base + l.o_umi); s.pos = (int32_t*)(s.base + l.o_pos); s.cell = (int32_t*)(s.base + l.o_cell);
     s.cig_off = (uint32_t*)(s.base + l.o_cgo); s.seq_off = (uint32_t*)(s.base + l.o_sqo); s.cigar = (uint32_t*)(s.base + l.o_cig);
     s.flag = (uint16_t*)(s.base + l.o_flag); s.mapq = s.base + l.o_mapq; s.seq = s.base + l.o_seq;
-    s.has_names = names; s.nt = NameTrailer{l.total, l.total + items_bytes, name_bytes, names ? name_items : 0};
+    s.qual = qual ? s.base + l.total : nullptr;
+    s.has_names = names; s.nt = NameTrailer{l.total + qual_bytes, l.total + qual_bytes + items_bytes, name_bytes, names ? name_items : 0};
     s.items = names ? (DiItem*)(s.base + s.nt.items_off) : nullptr; s.name_bytes = names ? s.base + s.nt.bytes_off : nullptr;
     return true;
 }
@@ -319,6 +321,11 @@ static inline bool parse_record(const DecodeCfg& dc, xck_engine* e, HostSoA& s, 
         memcpy(s.cigar + s.cig_off[o], q, (size_t)n_cig * 4);
         q += (size_t)n_cig * 4;
         if (dc.want_seq) memcpy(s.seq + s.seq_off[o], q, (l_seq + 1) / 2);
+        if (s.qual) {                                                     // the l_seq quality bytes, two per sequence byte: the pad of an odd read is "no quality"
+            uint8_t* const qd = s.qual + 2 * (size_t)s.seq_off[o];
+            memcpy(qd, q + (l_seq + 1) / 2, l_seq);
+            if (l_seq & 1) qd[l_seq] = 0xff;
+        }
         q += (l_seq + 1) / 2 + l_seq;
         // aux tags: first occurrence wins (htslib bam_aux_get)
         // (xf: the handle's tag filter, looked for only when it is on - a record without the tag is then walked to its end)
@@ -415,10 +422,10 @@ void parse_part(DecodeTimes* tm, xck_engine* e, HostSoA* sp, int32_t sample, con
 int64_t layout_chunk(ChunkJob& j, std::vector<WalkPart>& pieces, const xck_ingest_opts* o, bool want_seq, int64_t records_before, std::string* err) {
     size_t n_out = 0, n_cig = 0, n_seq = 0, n_rec = 0, n_name = 0;
     for (WalkPart& wp : pieces) { wp.out_base = n_out; wp.cig_base = n_cig; wp.seq_base = n_seq; wp.name_base = n_name; n_out += wp.n_out; n_cig += wp.n_cig; n_seq += wp.n_seq; n_name += wp.n_name; n_rec += wp.recs.size(); }
-    if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
+    if (n_cig >= (size_t(1) << 32) || n_seq >= (size_t(1) << 32) || (j.qual && n_seq >= (size_t(1) << 31))) { *err = "chunk too large"; return XCK_E_IO; }
     HostSoA& s = j.soa;
     if (n_name >= (size_t(1) << 32)) { *err = "chunk too large"; return XCK_E_IO; }
-    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1, n_out, n_name, j.names)) { *err = "out of host memory"; return XCK_E_NOMEM; }
+    if (!soa_reserve(s, n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1, n_out, n_name, j.names, j.qual && want_seq)) { *err = "out of host memory"; return XCK_E_NOMEM; }
     s.cig_off[n_out] = (uint32_t)n_cig; s.seq_off[n_out] = (uint32_t)n_seq;
     const uint64_t ord_hi = (uint64_t)(uint32_t)o->sample << ORD_REC_BITS;
     int32_t cur_c = -1; int64_t seg0 = 0, seg_r = 0, rec0 = 0;

@@ -58,6 +58,7 @@ template <class K> struct JoinArgs {
     K* keys; uint64_t* vals; unsigned long long cap;   // cap = capacity of ONE shard
     K* nkeys; uint64_t* nvals;                          // pileup split mode: the stream of hits without a base (same shard capacity)
     unsigned long long* ctl;             // control block, see CTL_* below
+    int32_t min_baseq;                   // pileup, BASEQ kernels only: a base whose quality byte is below it (and not 0xff) is not shown
 };
 
 static_assert(sizeof(JoinArgs<unsigned __int128>) <= 4000, "kernel arguments must stay under the 4 KiB kernarg limit");
@@ -528,21 +529,43 @@ __device__ __forceinline__ int base_at(const BatchDesc& d, uint32_t s0, uint32_t
     if ((uint32_t)(qi >> 1) < sl) { const uint32_t by = as_global(d.seq)[s0 + (uint32_t)(qi >> 1)]; al = (qi & 1) ? int(by & 15u) : int(by >> 4); }
     return al;
 }
+// ... under a base-quality floor (xck_config.min_baseq; the BASEQ kernels only): the quality byte of the same query offset lies at
+// 2 * s0 + qi of the batch's quality column (two bytes per sequence byte, the pad of an odd read 0xff) and is loaded beside the nibble.
+// A stored base with 0xff != q < min_q is masked: the pair keeps its key and shows no base (stored / masked say which of the two happened).
+// BqCount: the pairs drain() has fetched for this wave, wave-uniform (one ballot + popcount each per batch of parked pairs).  The pairs of
+// the set-aside reads, whose walks diverge, are summed per walk and added to the block's two LDS words - st_b[0] / st_c[0], which the
+// pileup's staging leaves unused (JoinSmem::ST_BC), so the default kernels' LDS and registers are what they were.
+struct BqCount { uint32_t w_base = 0, w_masked = 0; };
+template <class K, int MODE> __device__ __forceinline__ uint32_t* bq_lds_base(JoinSmem<K, MODE>& sm) { return (uint32_t*)&sm.st_b[0]; }
+template <class K, int MODE> __device__ __forceinline__ uint32_t* bq_lds_masked(JoinSmem<K, MODE>& sm) { return (uint32_t*)&sm.st_c[0]; }
+__device__ __forceinline__ int base_at_q(const BatchDesc& d, uint32_t s0, uint32_t sl, int32_t qi, int32_t min_q, bool& stored, bool& masked) {
+    int al = -1;
+    stored = (uint32_t)(qi >> 1) < sl; masked = false;
+    if (stored) {
+        const uint32_t by = as_global(d.seq)[s0 + (uint32_t)(qi >> 1)];
+        const int32_t q = as_global(d.qual)[2u * s0 + (uint32_t)qi];          // (a 32-bit offset beside the scalar base, as for the nibble: the push paths keep sequence offsets of such batches below 2^31)
+        al = (qi & 1) ? int(by & 15u) : int(by >> 4);
+        masked = q != 0xff && q < min_q;
+        if (masked) al = -1;
+    }
+    return al;
+}
 // One read whose reference span is not one aligned block (N / D gaps, no CIGAR span, unmapped flag): the pileup of
 // baf/fc/mcount.py:109-127 + utils/sam.py:4-40 over its CIGAR.  SNPs under aligned blocks are hits with a base (fetched
 // here: these reads are few); the SNPs inside a gap - where the read holds the key but shows no base - leave as ONE range
 // record per gap, (first SNP, cell, UMI | ordinal, count - 1), in pieces of 32 SNPs: a spliced read over 20 SNPs costs one
 // 16-byte record instead of 20 hits.  Such reads are collected per tile and walked together (k_join), so that the waves
 // that walk them are full and the other 85 % of the reads never wait for them.
-template <class K, int MODE>
+template <class K, int MODE, bool BASEQ>
 __device__ __forceinline__ uint32_t pileup_complex(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, int32_t pos, int32_t endpos,
-                                                   uint32_t c0, uint32_t c1, int32_t cell, uint64_t umi, uint32_t s0, uint32_t sl, int32_t idx) {
+                                                   uint32_t c0, uint32_t c1, int32_t cell, uint64_t umi, uint32_t s0, uint32_t sl, int32_t idx, BqCount& bq) {
     const int32_t w_lo = max(pos, 0) >> WSS;
     if (w_lo >= d.n_swin) return 0;
     const int32_t k_w = (uint32_t)(w_lo - sm.w0) < (uint32_t)sm.nw ? sm.st_w[w_lo - sm.w0] : as_global(d.snp_win)[w_lo];
     int32_t k = lower_snp<K, MODE>(a, d, sm, k_w, pos);
     const uint64_t ordv = (d.ordinal_base + (uint64_t)idx) << ALLELE_BITS;
     uint32_t n = 0;
+    uint32_t nb = 0, nm = 0;                                                  // BASEQ: pairs of this read with a stored base / masked
     auto gap = [&](int32_t ka, int32_t kb) {
         if constexpr (JoinSmem<K, MODE>::SPLIT) {
             for (int32_t ks = ka; ks < kb; ks += 32)
@@ -558,7 +581,9 @@ __device__ __forceinline__ uint32_t pileup_complex(const JoinArgs<K>& a, const B
             if (op_aligned(op)) {
                 for (int32_t kk = k; kk < k2; kk++) {
                     const int32_t qi = q + (snp_p0<K, MODE>(a, sm, kk) - rp);
-                    const int al = base_at(d, s0, sl, qi);
+                    int al;
+                    if constexpr (BASEQ) { bool st, mk; al = base_at_q(d, s0, sl, qi, a.min_baseq, st, mk); nb += st; nm += mk; }
+                    else al = base_at(d, s0, sl, qi);
                     const K key = a.kl.make((uint32_t)kk, (uint32_t)cell, umi);
                     if (JoinSmem<K, MODE>::SPLIT && al < 0) emit_nobase<K, MODE>(a, sm, key, ordv);
                     else emit<K, MODE>(a, sm, key, ordv | (uint64_t)(al + 1));
@@ -573,6 +598,7 @@ __device__ __forceinline__ uint32_t pileup_complex(const JoinArgs<K>& a, const B
         const int32_t k2 = lower_snp<K, MODE>(a, d, sm, k, endpos);
         if (k2 > k) gap(k, k2);
     }
+    if constexpr (BASEQ) { if (nb) atomicAdd(bq_lds_base(sm), nb); if (nm) atomicAdd(bq_lds_masked(sm), nm); }
     return n;
 }
 
@@ -605,15 +631,17 @@ __global__ __launch_bounds__(256) void k_tile_meta(BatchTable bt, TileMeta* __re
 
 // ---- the pileup walk of one sweep: the counterpart of join_regions() ----
 // the bases of the pairs a wave has parked (pr_n of them, wave-uniform) are fetched together and leave as hits; the segment is free again
-template <class K, int MODE>
-__device__ __forceinline__ void drain(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, int& pr_n) {
+template <class K, int MODE, bool BASEQ>
+__device__ __forceinline__ void drain(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, int& pr_n, BqCount& bq) {
     const int lane = threadIdx.x & 63, wb = threadIdx.x & ~63;          // wb: first slot of this wave's segment
     constexpr uint64_t AL_MASK = (uint64_t)((1u << ALLELE_BITS) - 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+    bool st = false, mk = false;
     if (lane < pr_n) {
         const int u = wb + lane;
-        const int al = base_at(d, sm.pk_s0[u], sm.pk_sl[u], sm.pk_qi[u]);   // -1: key held, no base
+        int al;                                                             // -1: key held, no base
+        if constexpr (BASEQ) al = base_at_q(d, sm.pk_s0[u], sm.pk_sl[u], sm.pk_qi[u], a.min_baseq, st, mk); else al = base_at(d, sm.pk_s0[u], sm.pk_sl[u], sm.pk_qi[u]);
         const K key = a.kl.make((uint32_t)sm.pk_k[u], (uint32_t)sm.pk_cell[u], sm.pk_umi[u]);
         const uint64_t val = ((d.ordinal_base + (uint64_t)sm.pk_idx[u]) << ALLELE_BITS) | (uint64_t)(al + 1);
         if (JoinSmem<K, MODE>::SPLIT && al < 0) emit_nobase<K, MODE>(a, sm, key, val & ~AL_MASK);   // a record of one SNP
@@ -621,6 +649,7 @@ __device__ __forceinline__ void drain(const JoinArgs<K>& a, const BatchDesc& d, 
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
+    if constexpr (BASEQ) { bq.w_base += (uint32_t)__popcll(__ballot(st)); bq.w_masked += (uint32_t)__popcll(__ballot(mk)); }
     pr_n = 0;
 }
 
@@ -631,9 +660,9 @@ __device__ __forceinline__ void drain(const JoinArgs<K>& a, const BatchDesc& d, 
 // fetched together later (drain: one HBM latency per batch, not per hit).  i = the read's index in its batch; pr_n = parked
 // pairs of this wave, wave-uniform state that lives across the sweeps; last_sweep: drain what is parked and walk the tile's
 // set-aside reads.  Returns the (read, SNP) pairs of this lane.
-template <class K, int MODE>
+template <class K, int MODE, bool BASEQ>
 __device__ __forceinline__ uint32_t pileup_sweep(const JoinArgs<K>& a, const BatchDesc& d, JoinSmem<K, MODE>& sm, const ReadInfo& r, const RawRead& cur,
-                                                 const int i, int& pr_n, const bool last_sweep) {
+                                                 const int i, int& pr_n, const bool last_sweep, BqCount& bq) {
     const int tid = threadIdx.x, wb = tid & ~63;
     uint32_t c = 0, n_gap = 0;
     // reads whose reference span is ONE aligned block (no N / D; 85 % of a 10x run) take the wave-uniform walk below; the
@@ -649,7 +678,7 @@ __device__ __forceinline__ uint32_t pileup_sweep(const JoinArgs<K>& a, const Bat
             if (u < (uint32_t)JoinSmem<K, MODE>::CXCAP) {
                 sm.cx_pos[u] = r.pos; sm.cx_end[u] = r.endpos; sm.cx_c0[u] = r.c0; sm.cx_c1[u] = r.c1; sm.cx_cell[u] = r.cell; sm.cx_umi[u] = r.umi;
                 sm.cx_s0[u] = cur.s0; sm.cx_sl[u] = cur.s1 - cur.s0; sm.cx_idx[u] = i;
-            } else n_gap += pileup_complex<K, MODE>(a, d, sm, r.pos, r.endpos, r.c0, r.c1, r.cell, r.umi, cur.s0, cur.s1 - cur.s0, i);   // list full: walk it here
+            } else n_gap += pileup_complex<K, MODE, BASEQ>(a, d, sm, r.pos, r.endpos, r.c0, r.c1, r.cell, r.umi, cur.s0, cur.s1 - cur.s0, i, bq);   // list full: walk it here
         }
     }
     if (__ballot(simple)) {                                         // wave-uniform
@@ -678,7 +707,7 @@ __device__ __forceinline__ uint32_t pileup_sweep(const JoinArgs<K>& a, const Bat
                 }
             }
             const int n_new = __popcll(am);
-            if (pr_n + n_new > 64) drain<K, MODE>(a, d, sm, pr_n);
+            if (pr_n + n_new > 64) drain<K, MODE, BASEQ>(a, d, sm, pr_n, bq);
             if (hit) {
                 const int u = wb + pr_n + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
                 sm.pk_k[u] = k; sm.pk_qi[u] = qi; sm.pk_cell[u] = r.cell; sm.pk_umi[u] = r.umi; sm.pk_s0[u] = cur.s0; sm.pk_sl[u] = cur.s1 - cur.s0; sm.pk_idx[u] = i;
@@ -688,12 +717,12 @@ __device__ __forceinline__ uint32_t pileup_sweep(const JoinArgs<K>& a, const Bat
         }
     }
     if (last_sweep) {
-        if (pr_n) drain<K, MODE>(a, d, sm, pr_n);
+        if (pr_n) drain<K, MODE, BASEQ>(a, d, sm, pr_n, bq);
         // the set-aside reads of the whole tile, one per thread: full waves of long walks instead of one long walk per wave and sweep
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         const uint32_t cx_n = min(sm.cx_n, (uint32_t)JoinSmem<K, MODE>::CXCAP);
         for (uint32_t u = tid; u < cx_n; u += JOIN_BLOCK)
-            n_gap += pileup_complex<K, MODE>(a, d, sm, sm.cx_pos[u], sm.cx_end[u], sm.cx_c0[u], sm.cx_c1[u], sm.cx_cell[u], sm.cx_umi[u], sm.cx_s0[u], sm.cx_sl[u], sm.cx_idx[u]);
+            n_gap += pileup_complex<K, MODE, BASEQ>(a, d, sm, sm.cx_pos[u], sm.cx_end[u], sm.cx_c0[u], sm.cx_c1[u], sm.cx_cell[u], sm.cx_umi[u], sm.cx_s0[u], sm.cx_sl[u], sm.cx_idx[u], bq);
     }
     return c + n_gap;
 }
@@ -763,9 +792,23 @@ __device__ __forceinline__ void publish_tile_totals(const JoinArgs<K>& a, JoinSm
                     if (acc) atomicAdd(&a.ctl[ctl_accepted(JOIN_SHARD)], (unsigned long long)acc); }
 }
 
+// The BASEQ kernels' pair counts (xck_get_baseq_stats): the waves' counts join the set-aside reads' in LDS, then one atomic each per block
+// that has any, on words of the shard's `accepted` cache line in device memory - rewound with it when a launch is replayed, so a replayed tile counts once.
+template <class K, int MODE>
+__device__ __forceinline__ void publish_baseq(const JoinArgs<K>& a, JoinSmem<K, MODE>& sm, const BqCount& bq) {
+    if ((threadIdx.x & 63) == 0) { if (bq.w_base) atomicAdd(bq_lds_base(sm), bq.w_base); if (bq.w_masked) atomicAdd(bq_lds_masked(sm), bq.w_masked); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t nb = *bq_lds_base(sm), nm = *bq_lds_masked(sm);
+        if (nb) atomicAdd(&a.ctl[ctl_bq_base(JOIN_SHARD)], (unsigned long long)nb);
+        if (nm) atomicAdd(&a.ctl[ctl_bq_masked(JOIN_SHARD)], (unsigned long long)nm);
+    }
+}
+
 // (64-bit pileup: asked to stay at 80 VGPRs, i.e. 6 waves per SIMD beside its 26.5 KB of LDS; the others have room anyway, and the
 // 128-bit pileup kernel would spill under that bound)
-template <class K, int MODE>
+// BASEQ (pileup only): the instantiation of a handle with a base-quality floor; the default one holds no trace of it
+template <class K, int MODE, bool BASEQ = false>
 __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((sizeof(K) == 8 && MODE == XCK_MODE_BAF) ? 6 : 4, 8))) void k_join(JoinArgs<K> a) {
     __shared__ JoinSmem<K, MODE> sm;
     const int tid = threadIdx.x;
@@ -792,6 +835,7 @@ __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((siz
         for (int j = 0; j < TILE_ITEMS; j++) W[j] = fetch_read<MODE == XCK_MODE_BAF>(d, tile0, (uint32_t)(j * JOIN_BLOCK + tid), tile0 + j * JOIN_BLOCK + tid < d.n);
     }                                                                 // the whole tile's loads fly during the staging
     stage_tile<K, MODE>(a, d, sm, m, u_lb);
+    if constexpr (BASEQ) { if (tid == 0) { *bq_lds_base(sm) = 0; *bq_lds_masked(sm) = 0; } }
     STAMP(1);
     __syncthreads();
     STAMP(2);
@@ -799,6 +843,7 @@ __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((siz
     uint32_t acc = 0;
     unsigned long long uor = 0;
     int pr_n = 0;                                                     // pileup: parked pairs of this wave (wave-uniform)
+    BqCount bq;                                                       // BASEQ: this lane's pairs with a base / masked
     // sweeps between two flushes: keep the expected fill (256 reads x ~2 pairs per sweep) under half the set / queue
     constexpr int CAP_ENTRIES = JoinSmem<K, MODE>::USE_SET ? JoinSmem<K, MODE>::SLOTS : JoinSmem<K, MODE>::QCAP;
     // set mode: the de-duplicated fill of a 1024-read tile is a few hundred keys, so flush once, at the end
@@ -816,7 +861,7 @@ __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((siz
 #endif
         if (r.ok) uor |= r.umi;                                       // (finish() puts the haplotype class of the region-level keys into UMI-field bits no code uses)
         // wave-uniform calls: the walk over the regions / SNPs is shared by all 64 lanes
-        if constexpr (MODE == XCK_MODE_BAF) acc += pileup_sweep<K, MODE>(a, d, sm, r, W[j], tile0 + j * JOIN_BLOCK + tid, pr_n, j + 1 == TILE_ITEMS);
+        if constexpr (MODE == XCK_MODE_BAF) acc += pileup_sweep<K, MODE, BASEQ>(a, d, sm, r, W[j], tile0 + j * JOIN_BLOCK + tid, pr_n, j + 1 == TILE_ITEMS, bq);
         else acc += join_regions<K, MODE>(a, d, sm, r, u_lb, u_nst, u_p0, &t_s0, j);
         // Flush points are fixed at compile time, never decided from sm.count: a count-based decision read
         // after the barrier races with the next sweep's inserts (threads could disagree and split at the
@@ -834,6 +879,7 @@ __global__ __launch_bounds__(JOIN_BLOCK) __attribute__((amdgpu_waves_per_eu((siz
         }
     }
     publish_tile_totals<K, MODE>(a, sm, acc, uor);
+    if constexpr (BASEQ) publish_baseq<K, MODE>(a, sm, bq);
 #if XCK_STAMPS != 2
     STAMP(11);
 #endif
@@ -961,6 +1007,7 @@ static int launch_join_t(EngineImpl* im) {
     a.kl.ubits = im->ubits; a.kl.cbits = im->cbits;
     a.keys = (K*)im->d_keys; a.vals = im->d_vals; a.cap = im->hit_cap; a.ctl = im->d_ctl;
     a.nkeys = (K*)im->d_nkeys; a.nvals = im->d_nvals;
+    a.min_baseq = im->min_baseq;
     dim3 grid(tiles), block(JOIN_BLOCK);
     clear_stale_error("launch_join", im->eng->knobs.debug_timing);
     HIP_TRY(hipEventRecord(im->ev0, im->s_comp));
@@ -970,7 +1017,8 @@ static int launch_join_t(EngineImpl* im) {
         hipLaunchKernelGGL((k_join<K, XCK_MODE_BASEFC>), grid, block, 0, im->s_comp, a);
     } else {
         hipLaunchKernelGGL((k_tile_meta<XCK_MODE_BAF>), mgrid, mblock, 0, im->s_comp, a.bt, im->d_meta, (const int32_t*)nullptr);
-        hipLaunchKernelGGL((k_join<K, XCK_MODE_BAF>), grid, block, 0, im->s_comp, a);
+        if (im->min_baseq > 0) hipLaunchKernelGGL((k_join<K, XCK_MODE_BAF, true>), grid, block, 0, im->s_comp, a);
+        else hipLaunchKernelGGL((k_join<K, XCK_MODE_BAF>), grid, block, 0, im->s_comp, a);
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(im->ev1, im->s_comp));

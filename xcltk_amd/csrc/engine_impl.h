@@ -63,6 +63,7 @@ struct BatchDesc {
     uint64_t ordinal_base;
     int32_t reg_lo, reg_hi;                                 // regions of the batch's contig: [reg_lo, reg_hi) of the start-sorted arrays
     const int32_t* snp_win; int32_t n_swin; int32_t snp_end; // SNP window table of the batch's contig
+    const uint8_t* qual;                                    // pileup with a base-quality floor: quality of query offset qi of the read at seq offset s0 = qual[2 * s0 + qi] (else null)
 };
 
 constexpr int MAX_FUSE = 24;              // batches per fused launch (the table travels in the kernel arguments)
@@ -95,6 +96,8 @@ __host__ __device__ inline int ctl_cursor(int shard) { return CTL_SHARD0 + shard
 __host__ __device__ inline int ctl_umi_or(int shard) { return CTL_SHARD0 + shard * CTL_STRIDE + 1; }   // OR of the UMI codes seen
 __host__ __device__ inline int ctl_ncursor(int shard) { return CTL_SHARD0 + shard * CTL_STRIDE + 2; }  // cursor of the no-base stream
 __host__ __device__ inline int ctl_accepted(int shard) { return CTL_SHARD0 + (NSHARD + shard) * CTL_STRIDE; }
+__host__ __device__ inline int ctl_bq_base(int shard) { return ctl_accepted(shard) + 1; }     // min_baseq: (read, SNP) pairs with a stored base
+__host__ __device__ inline int ctl_bq_masked(int shard) { return ctl_accepted(shard) + 2; }   // ... and those of them the floor masked
 
 // tuning macros that both translation units read (a variant build passes its -D flags to both)
 #ifndef XCK_BAF_SPLIT
@@ -119,6 +122,7 @@ struct ContigTab { int32_t reg_base = 0, n_reg = 0, snp_base = 0, n_snp = 0, swi
 struct BatchSlot {
     int32_t* pos = nullptr; uint16_t* flag = nullptr; uint8_t* mapq = nullptr; int32_t* cell = nullptr;
     uint64_t* umi = nullptr; uint32_t* cig_off = nullptr; uint32_t* cigar = nullptr; uint32_t* seq_off = nullptr; uint8_t* seq = nullptr;
+    uint8_t* qual = nullptr; size_t cap_qual = 0;            // min_baseq handles only: two bytes per sequence byte
     size_t cap_reads = 0, cap_cig = 0, cap_seq = 0;          // reads (the seven per-read columns); bytes; bytes
     bool busy = false;
 };
@@ -166,6 +170,8 @@ struct EngineImpl {
     unsigned long long* d_hctl = nullptr;      // device alias of h_ctl (written by k_publish)
     unsigned long long cur[NSHARD] = {0};      // host view of the shard cursors after the last completed launch
     unsigned long long cur_before[NSHARD] = {0}, acc_before[NSHARD] = {0};
+    int min_baseq = 0;                         // pileup: base-quality floor of the join (xck_config.min_baseq / XCK_MIN_BASEQ; 0 = off: the default kernels, no quality column)
+    unsigned long long bqb_before[NSHARD] = {0}, bqm_before[NSHARD] = {0};   // its pair counters before the launch in flight (rewound with acc_before on a replay)
     unsigned long long cursor = 0;             // sum of cur[]; hit_cap is the capacity of ONE shard
     int fold_extra_digits = 0;                 // basefc hash fold: extra radix digits that earlier finishes needed (giant runs)
     int fold_path = 0, fold_fallbacks = 0;     // xck_stats: which basefc fold ran last (1 partition, 2 radix sort), hand-overs so far

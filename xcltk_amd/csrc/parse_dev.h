@@ -27,6 +27,11 @@ XCK_HD inline SoaLayout soa_layout(size_t n_reads, size_t n_cig, size_t n_seq) {
     return l;
 }
 
+// The quality region of a chunk whose handle has a base-quality floor (xck_config.min_baseq): two bytes per sequence byte behind the
+// layout's total - the quality of query offset qi of the read at seq offset s0 at 2 * s0 + qi, the pad byte of an odd read 0xff.  The
+// layout itself does not know it: without the floor a block is what it always was.
+XCK_HD inline size_t soa_qual_bytes(size_t n_seq) { return (2 * n_seq + 255) & ~size_t(255); }
+
 // chunk / block flags.  Any of them sends the chunk down the host path, which reports what there is to report.
 constexpr uint32_t DP_F_SHORT = 1;        // a record with block_size < 32
 constexpr uint32_t DP_F_STRADDLE = 2;     // the walk of a block did not end at the block's end (a record straddles blocks)
@@ -113,6 +118,7 @@ struct DpParseCfg {
     int32_t filter_on;                     // the handle's tag filter (DecodeCfg::filter_*): 0 = the aux scan looks for nothing more and nothing is counted
     char filter_tag[2], pad[2];
     uint32_t filter_mask, filter_value;
+    int32_t want_qual;                     // the handle has a base-quality floor: the records' quality bytes go to the block's quality region (wave-uniform, as every field here)
 };
 
 // The tag filter's verdict on the first occurrence of the tag: t at its type byte, its value bytes inside the record (the caller has
@@ -141,6 +147,7 @@ struct DpWalk { uint32_t first_skip; DpContigMap cm; bool want_seq; };       // 
 int dev_walk_launch(GpuInflateSlot* s, size_t n_blocks, const DpWalk& w);
 // the parse of a walked chunk into `out` (a SoA block of soa_layout(n_out + 1, n_cig + 1, want_seq ? n_seq + 1 : 1)) on `stream`
 // (max_rec: most records of one block - a wave parses 64 records of a block)
+// (cfg.want_qual: the block is followed by its quality region, soa_qual_bytes(n_seq + 1) bytes at the layout's total)
 int dev_parse_launch(hipStream_t stream, const GpuInflateSlot* s, size_t n_blocks, size_t max_rec, const DpParseCfg& cfg, uint8_t* out, size_t n_out, size_t n_cig, size_t n_seq);
 // the fallback: the chunk's inflated bytes d_out -> h_out on the slot's stream, waited for; 0 = they are there
 int dev_parse_copy_out(GpuInflateSlot* s, size_t bytes);

@@ -135,6 +135,20 @@ __device__ inline void coop_copy(const uint8_t* __restrict__ u, uint8_t* __restr
     }
 }
 
+// the quality bytes of the round (a handle with a base-quality floor): two per sequence byte, so the destination is [2 * start[0],
+// 2 * start[64]) of the quality region; record i's l_seq[i] bytes lie behind its sequence bytes (src[i] + (start[i + 1] - start[i])
+// for a kept record, carried as qsrc[i]), and the one byte an odd l_seq leaves over is the pad, 0xff = "no quality"
+__device__ inline void coop_copy_qual(const uint8_t* __restrict__ u, uint8_t* __restrict__ dst, const uint32_t* start, const uint32_t* qsrc, const uint32_t* l_seq, int lane) {
+    const size_t lo = 2 * (size_t)start[0], hi = 2 * (size_t)start[64];
+    for (size_t j = lo + (size_t)lane; j < hi; j += 64) {
+        const uint32_t by = (uint32_t)(j >> 1);
+        int a = 0, z = 64;                                                  // last i in [0, 64) with start[i] <= by
+        while (z - a > 1) { const int m = (a + z) >> 1; if (start[m] <= by) a = m; else z = m; }
+        const uint32_t k = (uint32_t)(j - 2 * (size_t)start[a]);
+        dst[j] = k < l_seq[a] ? u[(size_t)qsrc[a] + k] : (uint8_t)0xff;
+    }
+}
+
 // the same for the CIGAR column in whole words: its destination is 4-byte aligned, start[] counts words, a record's source is not aligned
 __device__ inline void coop_copy_words(const uint8_t* __restrict__ u, uint32_t* __restrict__ dst, const uint32_t* start, const uint32_t* src, int lane) {
     const uint32_t lo = start[0], hi = start[64];
@@ -148,7 +162,7 @@ __device__ inline void coop_copy_words(const uint8_t* __restrict__ u, uint32_t* 
 __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, const DpRec* __restrict__ rec, const DpCnt* __restrict__ cnt, const DpBase* __restrict__ base,
                                               DpParseCfg cfg, uint8_t* __restrict__ out, SoaLayout lay, uint32_t n_out_total, uint32_t n_cig_total, uint32_t n_seq_total,
                                               DpHead* __restrict__ head, uint32_t* __restrict__ n_filtered) {
-    __shared__ uint32_t s_cst[65], s_csrc[64], s_sst[65], s_ssrc[64];
+    __shared__ uint32_t s_cst[65], s_csrc[64], s_sst[65], s_ssrc[64], s_qsrc[64], s_lseq[64];
     const int b = (int)blockIdx.x, lane = (int)threadIdx.x;
     uint64_t* c_umi = (uint64_t*)(out + lay.o_umi); int32_t* c_pos = (int32_t*)(out + lay.o_pos); int32_t* c_cell = (int32_t*)(out + lay.o_cell);
     uint32_t* c_cgo = (uint32_t*)(out + lay.o_cgo); uint32_t* c_sqo = (uint32_t*)(out + lay.o_sqo); uint32_t* c_cig = (uint32_t*)(out + lay.o_cig);
@@ -165,7 +179,7 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
         const bool have = ri < c.n_rec;
         DpRec rr = have ? rl[ri] : DpRec{0, DP_DROPPED, c.n_cig, c.n_seq};
         const bool kept = have && rr.slot != DP_DROPPED;
-        uint32_t cig_len = 0, seq_len = 0, cig_src = 0, seq_src = 0;
+        uint32_t cig_len = 0, seq_len = 0, cig_src = 0, seq_src = 0, q_len = 0;
         bool filtered = false;
         if (kept) {
             const uint8_t* r = u + rr.off;
@@ -178,7 +192,7 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
                 long long q = 32 + (long long)l_name;                       // (the walk checked that the fields lie inside the record)
                 cig_src = rr.off + (uint32_t)q; cig_len = n_cig;
                 q += (long long)n_cig * 4;
-                if (cfg.want_seq) { seq_src = rr.off + (uint32_t)q; seq_len = (l_seq + 1) / 2; }
+                if (cfg.want_seq) { seq_src = rr.off + (uint32_t)q; seq_len = (l_seq + 1) / 2; q_len = l_seq; }
                 q += (long long)((l_seq + 1) / 2) + l_seq;
                 // aux tags: first occurrence wins; the scan ends when all that are looked for are found or a value cannot be skipped
                 // (xf: the handle's tag filter, looked for only when it is on - a record without the tag is then walked to its end)
@@ -213,9 +227,11 @@ __global__ __launch_bounds__(64) void k_parse(const uint8_t* __restrict__ u, con
         s_cst[lane] = bs.cig + rr.cig; s_csrc[lane] = cig_src; s_sst[lane] = bs.seq + rr.seq; s_ssrc[lane] = seq_src;
         // (the end of the round's range: the last lane's start + length; lanes past the list start at the block's end, length 0)
         if (lane == 63) { s_cst[64] = bs.cig + rr.cig + cig_len; s_sst[64] = bs.seq + rr.seq + seq_len; }
+        if (cfg.want_qual) { s_qsrc[lane] = seq_src + seq_len; s_lseq[lane] = q_len; }
         __syncthreads();
         if (s_cst[64] <= n_cig_total) coop_copy_words(u, c_cig, s_cst, s_csrc, lane);
         if (cfg.want_seq && s_sst[64] <= n_seq_total) coop_copy(u, c_seq, s_sst, s_ssrc, lane);
+        if (cfg.want_qual && s_sst[64] <= n_seq_total) coop_copy_qual(u, out + lay.total, s_sst, s_qsrc, s_lseq, lane);   // (the region holds 2 * (n_seq_total + 1) bytes at least)
         // the chunk's filtered records: one ballot per wave, one add per wave that has any (the whole wave is here: r0 < c.n_rec is uniform).
         // The counter is in DEVICE memory (k_filtered_out hands it to the head record): with most waves adding, an atomic per wave on the
         // head's mapped host memory made the parse of a chunk wait for thousands of PCIe round trips

@@ -132,7 +132,8 @@ int complete_pending(EngineImpl* im) {
             for (int sh = 0; sh < NSHARD; sh++) mx = std::max(mx, std::max(im->h_ctl[ctl_cursor(sh)], im->h_ctl[ctl_ncursor(sh)]));
             int rc = ensure_hits(im, std::max<size_t>(mx + mx / 4 + 65536, im->hit_cap * 2)); if (rc) return rc;
             for (int sh = 0; sh < NSHARD; sh++) { im->h_ctl[ctl_cursor(sh)] = im->cur_before[sh]; im->h_ctl[ctl_ncursor(sh)] = im->ncur_before[sh];
-                                                  im->h_ctl[ctl_accepted(sh)] = im->acc_before[sh]; }
+                                                  im->h_ctl[ctl_accepted(sh)] = im->acc_before[sh];
+                                                  im->h_ctl[ctl_bq_base(sh)] = im->bqb_before[sh]; im->h_ctl[ctl_bq_masked(sh)] = im->bqm_before[sh]; }
             im->h_ctl[CTL_OVERFLOW] = 0;
             HIP_TRY(hipMemcpyAsync(im->d_ctl, im->h_ctl, CTL_WORDS * sizeof(unsigned long long), hipMemcpyHostToDevice, im->s_comp));
             HIP_TRY(hipStreamSynchronize(im->s_comp));
@@ -163,7 +164,8 @@ int launch_queue(EngineImpl* im, int slot_idx, int shared_slot) {
     im->inflight_slot = slot_idx;
     im->inflight_shared = shared_slot;
     if (shared_slot >= 0) im->eng->stager->slot[shared_slot].users++;
-    for (int sh = 0; sh < NSHARD; sh++) { im->cur_before[sh] = im->cur[sh]; im->ncur_before[sh] = im->ncur[sh]; im->acc_before[sh] = im->h_ctl[ctl_accepted(sh)]; }
+    for (int sh = 0; sh < NSHARD; sh++) { im->cur_before[sh] = im->cur[sh]; im->ncur_before[sh] = im->ncur[sh]; im->acc_before[sh] = im->h_ctl[ctl_accepted(sh)];
+                                          im->bqb_before[sh] = im->h_ctl[ctl_bq_base(sh)]; im->bqm_before[sh] = im->h_ctl[ctl_bq_masked(sh)]; }
     if (slot_idx >= 0) im->slot[slot_idx].busy = true;
     rc = launch_join(im); if (rc) return rc;
     return launch_summaries(im);                               // (off: returns at once)
@@ -206,9 +208,10 @@ static BatchFate describe_batch(EngineImpl* im, const xck_batch* b, Columns cols
 // algorithmic bytes the join reads for a batch whose sizes the host knows (xck_stats.algo_bytes_join; n_seq: 0 without sequences)
 static int64_t join_bytes(size_t n, size_t n_cig, size_t n_seq) { return (int64_t)n * 20 + (int64_t)n_cig * 4 + (int64_t)(n_seq / 2); }
 
-int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident) {
+int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident, const uint8_t* qual) {
     xck_engine* e = im->eng;
     if (im->finished) { e->err = "push after finish (call xck_reset)"; return XCK_E_STATE; }
+    if (im->min_baseq > 0 && (device_resident || !qual)) { e->err = "internal: a batch without qualities on a pipeline with a base-quality floor"; return XCK_E_STATE; }   // (xck_push_batch* refuse first)
     HIP_TRY(hipSetDevice(im->device));
     BatchDesc d;
     const BatchFate fate = describe_batch(im, b, device_resident ? COLS_DEVICE : COLS_HOST, d);
@@ -232,6 +235,8 @@ int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident) {
     BatchSlot& s = im->slot[slot_idx];
     if (s.busy) { rc = complete_pending(im); if (rc) return rc; }   // slot still feeds the launch in flight
     rc = slot_reserve(im, s, n, std::max<uint32_t>(n_cig, 1), std::max<uint32_t>(n_seq, 1)); if (rc) return rc;
+    const bool with_qual = seq && im->min_baseq > 0;                  // the quality column: allocated and copied like seq, two bytes per sequence byte
+    if (with_qual) { const size_t nq = 2 * (size_t)std::max<uint32_t>(n_seq, 1); rc = grow_device(im, (void**)&s.qual, &s.cap_qual, nq, std::max(nq, s.cap_qual * 2) - nq); if (rc) return rc; }
     auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipMemcpyAsync(s.pos, b->pos, n * 4, hipMemcpyHostToDevice, im->s_copy));
     HIP_TRY(hipMemcpyAsync(s.flag, b->flag, n * 2, hipMemcpyHostToDevice, im->s_copy));
@@ -243,12 +248,14 @@ int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident) {
     if (seq) {
         HIP_TRY(hipMemcpyAsync(s.seq_off, b->seq_off, (n + 1) * 4, hipMemcpyHostToDevice, im->s_copy));
         if (n_seq) HIP_TRY(hipMemcpyAsync(s.seq, b->seq + s_lo, n_seq, hipMemcpyHostToDevice, im->s_copy));
+        if (with_qual && n_seq) HIP_TRY(hipMemcpyAsync(s.qual, qual, 2 * (size_t)n_seq, hipMemcpyHostToDevice, im->s_copy));
     }
     HIP_TRY(hipStreamSynchronize(im->s_copy));                 // caller may reuse its arrays now
     im->st.ms_h2d += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     im->st.algo_bytes_join += join_bytes(n, n_cig, n_seq);
     d.pos = s.pos; d.flag = s.flag; d.mapq = s.mapq; d.cell = s.cell; d.umi = s.umi;
     d.cig_off = s.cig_off; d.cigar = s.cigar - c_lo; d.seq_off = s.seq_off; d.seq = s.seq - s_lo;   // rebased, never read below *_lo
+    if (with_qual) d.qual = s.qual - 2 * (size_t)s_lo;
     im->queue.push_back(d); im->queued_reads += b->n_reads;
     return launch_queue(im, slot_idx);                         // the kernel overlaps the caller's next decode + copy
 }
@@ -282,8 +289,10 @@ static int stager_take(xck_engine* e, size_t bytes, int* si_out) {
 // The batches of the chunk in staging slot si -> every pipeline's queue and one fused launch per pipeline (and the opt-in summary
 // passes behind it, launch_queue).  dev(): a column pointer of a batch -> its place in the slot; sizes(i): the batch's CIGAR words
 // and sequence bytes (xck_stats.algo_bytes_join).
+// qual: the chunk's quality column (same addressing as the batches' column pointers, indexed by 2 * seq_off + query offset), for the
+// pipelines with a base-quality floor; null on a handle without one.
 template <class Dev, class Sizes>
-static int push_staged(xck_engine* e, int si, const xck_batch* batches, int n, Dev dev, Sizes sizes) {
+static int push_staged(xck_engine* e, int si, const xck_batch* batches, int n, Dev dev, Sizes sizes, const uint8_t* qual = nullptr) {
     Stager::Slot& sl = e->stager->slot[si];
     for (int k = 0; k < e->n_impl; k++) {
         EngineImpl* im = e->impls[k];
@@ -301,6 +310,10 @@ static int push_staged(xck_engine* e, int si, const xck_batch* batches, int n, D
             d.cell = (const int32_t*)dev(b->cell); d.umi = (const uint64_t*)dev(b->umi);
             d.cig_off = (const uint32_t*)dev(b->cig_off); d.cigar = (const uint32_t*)dev(b->cigar);
             if (seq) { d.seq_off = (const uint32_t*)dev(b->seq_off); d.seq = (const uint8_t*)dev(b->seq); }
+            if (seq && im->min_baseq > 0) {
+                if (!qual) { e->err = "internal: a chunk without qualities on a pipeline with a base-quality floor"; return XCK_E_STATE; }
+                d.qual = (const uint8_t*)dev(qual);
+            }
             size_t n_cig = 0, n_seq = 0; sizes(i, seq, &n_cig, &n_seq);
             im->st.algo_bytes_join += join_bytes((size_t)b->n_reads, n_cig, n_seq);
             im->queue.push_back(d); im->queued_reads += b->n_reads;
@@ -358,7 +371,7 @@ void engine_names_report(xck_engine* e) {                                // XCK_
 }
 
 // a chunk the host decoded: ONE H2D copy of its block into the slot
-int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence, const NameTrailer* names) {
+int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence, const NameTrailer* names, const uint8_t* qual) {
     int si = 0;
     if (int rc = stager_take(e, bytes, &si)) return rc;
     EngineImpl* im = e->impls[0];
@@ -382,7 +395,7 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
     const char* hb = (const char*)host_base;
     return push_staged(e, si, batches, n, [&](const void* hp) { return (void*)(sl.buf + ((const char*)hp - hb)); },   // a column's place in the staged copy
                        [&](int i, bool seq, size_t* n_cig, size_t* n_seq) { const xck_batch* b = &batches[i]; const size_t nr = (size_t)b->n_reads;
-                                                                              *n_cig = b->cig_off[nr] - b->cig_off[0]; *n_seq = seq ? b->seq_off[nr] - b->seq_off[0] : 0; });
+                                                                              *n_cig = b->cig_off[nr] - b->cig_off[0]; *n_seq = seq ? b->seq_off[nr] - b->seq_off[0] : 0; }, qual);
 }
 
 // A chunk the device inflated and walked (csrc/parse_dev.hip): no copy - the parse kernel writes the chunk's SoA block straight into the
@@ -391,8 +404,9 @@ int engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const 
 int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks, size_t max_rec, size_t n_out, size_t n_cig, size_t n_seq, int32_t sample, const DpBatch* dbs, int n, size_t chunk_bytes) {
     const DecodeCfg& dc = e->dec;
     const SoaLayout lay = soa_layout(n_out + 1, n_cig + 1, dc.want_seq ? n_seq + 1 : 1);
+    const bool with_qual = dc.want_qual && dc.want_seq;                  // the quality region: behind the layout's total (parse_dev.h soa_qual_bytes)
     int si = 0;
-    if (int rc = stager_take(e, lay.total, &si)) return rc;
+    if (int rc = stager_take(e, lay.total + (with_qual ? soa_qual_bytes(n_seq + 1) : 0), &si)) return rc;
     EngineImpl* im = e->impls[0];                                        // (HIP_TRY reports through it)
     Stager* st = e->stager; Stager::Slot& sl = st->slot[si];
     if (!st->d_bc && !dc.bc_slots.empty()) {                             // the barcode table, as it is (same hash, same probe order on the device)
@@ -403,6 +417,7 @@ int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks,
     DpParseCfg pc; memset(&pc, 0, sizeof pc);
     pc.bc = (const DpBcSlot*)st->d_bc; pc.bc_mask = dc.bc_mask; pc.use_barcodes = dc.use_barcodes; pc.want_seq = dc.want_seq; pc.umi_bits = dc.umi_bits; pc.sample = sample;
     memcpy(pc.cell_tag, dc.cell_tag, 2); memcpy(pc.umi_tag, dc.umi_tag, 2);
+    pc.want_qual = with_qual ? 1 : 0;
     pc.filter_on = dc.filter_on ? 1 : 0; memcpy(pc.filter_tag, dc.filter_tag, 2); pc.filter_mask = dc.filter_mask; pc.filter_value = dc.filter_value;   // (the kernel counts what it filters in the chunk's head record: Pusher::run)
     const bool names = e->names_mode && n_out > 0;
     pc.names = e->names_mode ? 1 : 0;
@@ -431,7 +446,7 @@ int engine_push_parsed(xck_engine* e, const GpuInflateSlot* gs, size_t n_blocks,
         if (dc.want_seq) { bt.seq_off = (const uint32_t*)(sl.buf + lay.o_sqo) + pb.r0; bt.seq = (const uint8_t*)(sl.buf + lay.o_seq); }
     }
     return push_staged(e, si, bts.data(), n, [](const void* p) { return (void*)p; },
-                       [&](int i, bool seq, size_t* c, size_t* q) { *c = dbs[i].n_cig; *q = seq ? dbs[i].n_seq : 0; });
+                       [&](int i, bool seq, size_t* c, size_t* q) { *c = dbs[i].n_cig; *q = seq ? dbs[i].n_seq : 0; }, with_qual ? (const uint8_t*)(sl.buf + lay.total) : nullptr);
 }
 
 void engine_release_staging(xck_engine* e) {
@@ -471,6 +486,14 @@ int engine_reset(EngineImpl* im) {
     int kb = im->key_bits, ub = im->ubits;
     memset(&im->st, 0, sizeof im->st);
     im->st.key_bits = kb; im->st.umi_bits = ub; im->n_join_launches = 0;
+    return 0;
+}
+
+// the join's pair counters (xck_get_baseq_stats): the control words of the last confirmed launch, summed over the shards
+int engine_baseq_stats(EngineImpl* im, xck_baseq_stats* out) {
+    if (const int rc = engine_flush(im)) return rc;
+    out->min_baseq = im->min_baseq;
+    for (int sh = 0; sh < NSHARD; sh++) { out->pairs_with_base += (int64_t)im->h_ctl[ctl_bq_base(sh)]; out->pairs_masked += (int64_t)im->h_ctl[ctl_bq_masked(sh)]; }
     return 0;
 }
 
@@ -514,6 +537,7 @@ int engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out) {
     im->sf.min_count = cfg->min_count <= 0.0 ? 0 : (int32_t)std::min(2147483647.0, std::ceil(cfg->min_count));
     im->sf.min_maf = cfg->min_maf;
     im->no_dup_hap = cfg->no_dup_hap;
+    im->min_baseq = im->mode == XCK_MODE_BAF ? cfg->min_baseq : 0;       // (xck_create: checked, the knob folded in; the basefc half of a fused handle has none)
     im->n_cells = cfg->n_cells; im->n_regions = cfg->n_regions;
     { KeyBits kb = key_layout(cfg); im->key_bits = kb.key_bits; im->ubits = kb.ubits; im->cbits = kb.cbits; im->rbits = kb.rbits; }
     im->st.key_bits = im->key_bits; im->st.umi_bits = im->ubits;
@@ -543,7 +567,7 @@ void engine_destroy(EngineImpl* im) {
                      im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept, im->d_mol,
                      im->d_csr_alt, im->d_rf, im->d_cm, im->d_sc_perm, im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
-    for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq }; for (void* p : q) if (p) hipFree(p); }
+    for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq, s.qual }; for (void* p : q) if (p) hipFree(p); }
     for (int m = 0; m < 4; m++) if (im->h_res[m]) hipHostFree(im->h_res[m]);
     coo_call_free(im->sc); coo_call_free(im->gc);
     if (im->h_ctl) hipHostFree(im->h_ctl);

@@ -53,6 +53,7 @@ struct DecodeCfg {
     char umi_tag[2] = {0, 0};
     int  umi_bits = 64;
     bool want_seq = false;
+    bool want_qual = false;              // the handle's pileup has a base-quality floor (xck_config.min_baseq): the records' quality bytes are kept
     bool verify_crc = false;             // check the CRC32 of every block the record decoder inflates (XCK_F_VERIFY_CRC, XCK_F_DEVICE_CRC)
     bool crc_on_device = false;          // ... and keep the GPU share of the inflate: the kernel checks its blocks (XCK_F_DEVICE_CRC)
     // the tag filter (xck_config.filter_tag / XCK_TAG_FILTER): a record whose first filter_tag is not an integer v in 0 .. 2^32 - 1 with
@@ -122,6 +123,7 @@ struct Knobs {
     int  cell_summary_slots = 0;         // XCK_CELL_SUMMARY_SLOTS: rows of the per-block LDS tables (0 = the built-in 512 per-cell, 1024 per-feature / per-SNP; tests: small tables reach the no-fit path)
     bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
     bool umi_consensus = false;          // XCK_UMI_CONSENSUS=1: XCK_F_UMI_CONSENSUS ORed into the flags of every handle with a BAF pipeline that drives a GPU
+    int  min_baseq = 0; std::string min_baseq_text;   // XCK_MIN_BASEQ=<0 .. 93>: xck_config.min_baseq of every handle with a BAF pipeline that drives a GPU and sets none; -1 = malformed (xck_create fails and quotes the text)
     int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
     bool gpu_parse = true;               // XCK_GPU_PARSE=auto|0: walk and parse the GPU-inflated chunks on the device where that applies (bam.cpp device_parse_now)
     bool gpu_names = false;              // XCK_GPU_NAMES=1: read names of a UMI-less handle are interned on the device (intern_dev.h; the conditions: api.cpp xck_create)
@@ -147,7 +149,7 @@ uint64_t intern_id_limit(int umi_bits);  // ids an intern table may hand out for
 struct NameTrailer { size_t items_off, bytes_off, n_bytes, n_out; };
 
 // the decoder's own batches are valid by construction and skip the O(n) check of xck_push_batch()
-int push_trusted(xck_engine* e, const xck_batch* b);
+int push_trusted(xck_engine* e, const xck_batch* b, const uint8_t* qual = nullptr);
 // host threads this process may really use: min(hardware threads, CPU affinity, cgroup CPU quota) - a container with a
 // 16-CPU quota on a 256-thread host must not start 256 decoder threads
 int  default_threads();
@@ -176,6 +178,7 @@ struct xck_engine {
     bool cell_summary = false;           // made with XCK_F_CELL_SUMMARY (or XCK_CELL_SUMMARY=1)
     bool feature_summary = false;        // made with XCK_F_FEATURE_SUMMARY (or XCK_FEATURE_SUMMARY=1)
     bool umi_consensus = false;          // made with XCK_F_UMI_CONSENSUS (or XCK_UMI_CONSENSUS=1) and a BAF pipeline: its molecule stage votes (umi_consensus.h)
+    int  min_baseq = 0;                  // base-quality floor of the pileup pipeline's join (xck_config.min_baseq or XCK_MIN_BASEQ), 0 = off
     int umi_bits = 64;
     int32_t n_cells = 0, n_contigs = 0;  // bounds that caller-supplied batches are checked against (xck_push_batch)
     // host pinned batch staging used by xck_ingest_bam lives in the xck_bam
@@ -186,7 +189,8 @@ struct xck_engine {
 namespace xck {
 int  engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out);   // *out is set as soon as it exists: a failed create still has to be destroyed
 void engine_destroy(EngineImpl* im);
-int  engine_push(EngineImpl* im, const xck_batch* b, bool device_resident);
+int  engine_push(EngineImpl* im, const xck_batch* b, bool device_resident, const uint8_t* qual = nullptr);   // qual (a pileup pipeline with a floor, host arrays): 2 * (seq_off[n] - seq_off[0]) bytes
+int  engine_baseq_stats(EngineImpl* im, xck_baseq_stats* out);     // pipeline.hip: the join's pair counters since the last reset
 int  engine_flush(EngineImpl* im);
 int  engine_finish(EngineImpl* im, xck_result* out);
 int  engine_finish_async(EngineImpl* im);
@@ -209,7 +213,9 @@ int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (
 // *fence (created on first use) is recorded behind the copy: fence_wait() before the host block is overwritten.
 // names (device-names mode): the chunk's packed read names lie in the block too; their keys are written into the staged umi column
 // by the intern kernel, on the copy stream, before the batches are queued.
-int  engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence, const NameTrailer* names = nullptr);
+// qual (a handle with a base-quality floor): the block's quality column, inside the block, indexed by 2 * seq_off + query offset with the
+// same offsets the batches' seq pointers are indexed by
+int  engine_push_block(xck_engine* e, const void* host_base, size_t bytes, const xck_batch* batches, int n, void** fence, const NameTrailer* names = nullptr, const uint8_t* qual = nullptr);
 // One chunk the device inflated and walked (parse_dev.h): the parse kernel writes the chunk's SoA block into the staging slot - no copy -
 // and the batches follow as in engine_push_block.  1 = the kernel flagged the chunk and nothing was queued: the host path takes it.
 struct GpuInflateSlot; struct DpBatch;

@@ -94,7 +94,7 @@ class Engine(object):
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
                  incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1,
                  min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None,
-                 umi_consensus=False):
+                 umi_consensus=False, min_baseq=0):
         """regions: iterable of (chrom, start1, end1_incl[, name]); snps: iterable of
         (chrom, pos1, ref, alt, ref_hap, alt_hap); chrom names must already be stripped of
         'chr' and present in contig_names.  excl_pairs = (region indices, snp indices): pairs left out of the SNP -> region
@@ -105,7 +105,10 @@ class Engine(object):
         self.tag_filter is the (tag, value, mask) the handle applies, or None.  umi_consensus=True (XCK_F_UMI_CONSENSUS; needs a BAF
         pipeline): the base of a molecule is a plurality vote over its reads instead of its first read's, reads that span the SNP
         in a gap abstain, and molecule_stats() says how often the reads of a molecule disagree; XCK_UMI_CONSENSUS=1 in the
-        environment does the same for every handle with a BAF pipeline."""
+        environment does the same for every handle with a BAF pipeline.  min_baseq=Q (1 .. 93, xck_config.min_baseq; needs a BAF
+        pipeline; set together with XCK_F_MIN_BASEQ): a base whose quality is below Q (and stored: not 0xff) is not shown at its SNP, as `samtools mpileup -Q` / pysam's
+        min_base_quality do; the qualities come from ingest_bam() or push_batch(..., qual=), and baseq_stats() counts what was masked;
+        XCK_MIN_BASEQ in the environment supplies it where it is 0.  self.min_baseq is the floor the handle runs with."""
         self.lib = capi.load()
         self.mode = mode
         self.contig_names = list(contig_names)
@@ -173,7 +176,12 @@ class Engine(object):
         elif os.environ.get("XCK_TAG_FILTER"):                      # (xck_create checks the knob: a malformed one fails below)
             self.tag_filter = _parse_tag_filter(os.environ["XCK_TAG_FILTER"])
         cfg.n_threads = int(n_threads)
+        self.min_baseq = int(min_baseq)
+        if not self.min_baseq and not decode_only and (mode & XCK_MODE_BAF):     # (xck_create checks the knob: a malformed one fails below)
+            knob = os.environ.get("XCK_MIN_BASEQ", "")
+            self.min_baseq = int(knob) if knob.isdigit() else 0
         cfg.flags = int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0) | (capi.XCK_F_UMI_CONSENSUS if umi_consensus else 0)
+        cfg.min_baseq = int(min_baseq)                              # (behind the flags: a non-zero value sets XCK_F_MIN_BASEQ beside it)
         self.cfg = cfg
         self.n_cells = int(n_cells)
         self.n_regions = len(regions)
@@ -211,6 +219,20 @@ class Engine(object):
     def push(self, batch, device_resident=False):
         fn = self.lib.xck_push_batch_device if device_resident else self.lib.xck_push_batch
         self._check(fn(self.h, C.byref(batch)), "xck_push_batch")
+
+    def push_batch(self, batch, qual=None):
+        """push(), with the reads' base qualities for a handle with min_baseq (xck_push_batch_q): qual is a uint8 array of
+        2 * (seq_off[n] - seq_off[0]) bytes, the quality of query offset qi of read i at 2 * (seq_off[i] - seq_off[0]) + qi, the pad
+        byte of an odd-length read 0xff (0xff: no quality stored).  A handle without a floor ignores it."""
+        if qual is None:
+            return self.push(batch)
+        q = np.ascontiguousarray(qual, dtype=np.uint8)
+        n = int(batch.n_reads)
+        if n > 0 and bool(batch.seq_off):
+            need = 2 * (int(batch.seq_off[n]) - int(batch.seq_off[0]))
+            if len(q) < need:
+                raise ValueError("qual holds %d bytes, the batch needs %d" % (len(q), need))
+        self._check(self.lib.xck_push_batch_q(self.h, C.byref(batch), q.ctypes.data_as(C.POINTER(C.c_uint8))), "xck_push_batch_q")
 
     def flush(self):
         self._check(self.lib.xck_flush(self.h), "xck_flush")
@@ -588,6 +610,17 @@ class Engine(object):
                     matrix=table(fs.matrix, n, int(fs.n_matrix_cols)) if fs.has_matrix else None,
                     snp=table(fs.snp, int(fs.n_snps), int(fs.n_snp_cols)), has_matrix=bool(fs.has_matrix),
                     read_cols=capi.FEATURE_READ_COLS, matrix_cols=capi.FEATURE_MATRIX_COLS[int(fs.mode)], snp_cols=capi.SNP_COLS)
+
+    def baseq_stats(self):
+        """What the base-quality floor saw since the last reset (xck_get_baseq_stats): dict of min_baseq, pairs_with_base (the (read,
+        SNP) pairs of the pileup in which the read stores a base), pairs_masked; None on a handle without a floor."""
+        out = capi.BaseqStats()
+        out.struct_size = C.sizeof(capi.BaseqStats)
+        rc = self.lib.xck_get_baseq_stats(self.h, C.byref(out))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_baseq_stats")
+        return dict(min_baseq=int(out.min_baseq), pairs_with_base=int(out.pairs_with_base), pairs_masked=int(out.pairs_masked))
 
     def molecule_stats(self):
         """How the reads of the molecules of the last finish() agree (xck_get_molecule_stats): dict of molecules, multi_read,

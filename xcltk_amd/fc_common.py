@@ -819,6 +819,22 @@ def log_tag_filter(eng, dist, log_prefix="[engine]"):
     return int(n[0])
 
 
+def log_min_baseq(eng, dist, log_prefix="[engine]"):
+    """One log line when the handle's pileup runs with a base-quality floor (Engine(min_baseq=...), or XCK_MIN_BASEQ in the environment):
+    the floor, the (read, SNP) pairs in which the read stores a base and those of them the floor masked, summed over the ranks of a
+    multi-GPU run (then a collective call; where a contig is cut over ranks both neighbours count the reads at the cut).  Returns
+    the (summed) dict or None."""
+    baseq_stats = getattr(eng, "baseq_stats", None)            # (an engine-like object without the method masks nothing)
+    st = baseq_stats() if baseq_stats and getattr(eng, "min_baseq", 0) else None
+    if st is None:
+        return None
+    n = np.array([st["pairs_with_base"], st["pairs_masked"]], dtype=np.int64)
+    if dist is not None and dist.active:
+        n = dist.all_reduce_np(n)
+    info("%s min base quality %d: %d (read, SNP) pair(s) with a base, %d masked" % (log_prefix, st["min_baseq"], int(n[0]), int(n[1])))
+    return dict(st, pairs_with_base=int(n[0]), pairs_masked=int(n[1]))
+
+
 def make_and_count(conf, mode, regions, snps=(), log_prefix="[engine]", gather=None, **extra):
     """Build the engine, stream every BAM (this rank's contigs when running multi-GPU), fold, gather.  Keys that are not ACGT strings (IUPAC UMIs, integer tags, read names in UMI-less runs) are
     interned on the host and take one id each; when the ids outgrow the UMI field of a 64-bit key the decoder stops with
@@ -857,6 +873,7 @@ def make_and_count(conf, mode, regions, snps=(), log_prefix="[engine]", gather=N
             eng.close()
             raise failure
         log_tag_filter(eng, dist, log_prefix)
+        log_min_baseq(eng, dist, log_prefix)
         try:
             coo = eng.finish(copy=False)
             if gather is not None:
