@@ -95,6 +95,11 @@
  *                                         pairs that showed a base and those the floor masked.  A value above 93 or one that is not a number fails
  *                                         xck_create with XCK_E_ARG.  Off, no quality byte is read, kept or copied and the default kernels run.
  *                                         Basefc-only and decode-only handles ignore it.
+ *   XCK_UMI_FEATURE=unique|all            (opt-in; unset, empty or `all`: off) every handle with a basefc pipeline that drives a GPU counts a molecule
+ *                                         (contig, cell, UMI) only when exactly one region of that contig accepted its reads, as if made with
+ *                                         XCK_F_UNIQUE_FEATURE (xck_get_umi_feature_stats): the front-ends then write umi_feature_summary.tsv next to
+ *                                         their count matrix.  Any other value fails xck_create with XCK_E_ARG.  Off, no kernel is added and every
+ *                                         output is byte-identical.  BAF-only and decode-only handles ignore it.
  *   XCK_GROUP_LONG_ROW=<entries>          xck_group_counts: a source row with at least this many entries is summed by one block with a table in
  *                                         LDS, a shorter one by one wave in registers (default and upper bound 64, at least 1; tests: a small value
  *                                         reaches the block shape with small inputs)
@@ -279,6 +284,15 @@ typedef struct xck_config {
                                    molecule disagree (xck_get_molecule_stats).  Any handle with a BAF pipeline; on XCK_MODE_BOTH it
                                    affects the BAF half only.  XCK_E_ARG on a basefc-only handle and together with XCK_F_DECODE_ONLY */
 #define XCK_F_MIN_BASEQ    512  /* xck_config.min_baseq holds a value (see there); without the bit the field's bytes are not read    */
+#define XCK_F_UNIQUE_FEATURE 1024 /* basefc: a molecule - (contig of the region, cell, UMI key code), over all keys the join accepted since
+                                   the last reset - counts only when exactly one row (entry of the region table) of that contig holds
+                                   it; a molecule that two or more rows hold is dropped from all of them.  Two entries with the same
+                                   interval are two rows: the molecules they share drop.  The same (cell, UMI) on two contigs is two
+                                   molecules.  The read-level numbers (n_hits, n_hits_unique, xck_get_read_fate, the read columns of
+                                   the summaries) describe the join and do not change; the matrix, its marginals in the summaries
+                                   and xck_group_counts follow.  xck_get_umi_feature_stats counts what was dropped.  Any handle with
+                                   a basefc pipeline; on XCK_MODE_BOTH the BAF half is untouched.  XCK_E_ARG on a BAF-only handle
+                                   and together with XCK_F_DECODE_ONLY                                                          */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -458,6 +472,18 @@ typedef struct xck_molecule_stats {
     int64_t  changed;           /* ... whose winning bucket is not the bucket of the earliest read with a base: the molecules
                                    that the first-read rule would have called differently, gap reads aside                    */
 } xck_molecule_stats;
+
+/* What the unique-feature rule of the last xck_finish saw (handles made with XCK_F_UNIQUE_FEATURE; additive, ABI 3 is unchanged).  A
+ * molecule is a (contig, cell, UMI) with at least one accepted (row, cell, UMI) key on that contig.  keys - keys_dropped is the sum of
+ * the count matrix.  struct_size = sizeof(xck_umi_feature_stats), as for xck_decode_stats. */
+typedef struct xck_umi_feature_stats {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t  molecules;         /* molecules with at least one key                                                             */
+    int64_t  multi_feature;     /* ... that two or more rows of their contig hold: dropped from all of them                    */
+    int64_t  keys;              /* distinct (row, cell, UMI) keys: what the fold counts without the flag                        */
+    int64_t  keys_dropped;      /* ... of them the keys of the multi_feature molecules                                         */
+} xck_umi_feature_stats;
 
 /* The pairs the base-quality floor saw (xck_config.min_baseq / XCK_MIN_BASEQ; xck_get_baseq_stats): (read, SNP) pairs of the pileup
  * pipeline's join since the last reset in which the read stores a base at the SNP, and those of them the floor masked.
@@ -644,6 +670,12 @@ int  xck_get_feature_summary(xck_engine* e, int mode, xck_feature_summary* out);
  * the handle has failed; XCK_E_ARG for a null pointer or a short struct_size.  With contigs cut over several GPUs every handle counts
  * the molecules of the reads it saw; a molecule whose reads straddle a cut is counted by both neighbours. */
 int  xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out);
+/* The counters of the unique-feature rule of the handle's basefc pipeline (set out->struct_size first), as the last xck_finish counted
+ * them; xck_group_counts does not change them, xck_reset clears them.  XCK_E_STATE on a handle without XCK_F_UNIQUE_FEATURE (and
+ * without XCK_UMI_FEATURE=unique), before a successful xck_finish, after an xck_reset, or when a fold of the handle has failed;
+ * XCK_E_ARG for a null pointer or a short struct_size.  A run sharded by whole contigs sums its handles' counters to the one-GPU run's;
+ * a molecule of a contig cut over several GPUs would be judged by each on its own part, which is why the front-ends refuse such a plan. */
+int  xck_get_umi_feature_stats(xck_engine* e, xck_umi_feature_stats* out);
 /* The pair counters of the handle's base-quality floor (set out->struct_size first).  Waits for the handle's queued work as xck_flush
  * does; xck_reset clears them, xck_finish and the derived calls do not change them.  A tile the join replays after an overflow counts
  * once.  XCK_E_STATE on a handle without a floor (and on a decode-only handle), XCK_E_ARG for a null pointer or a short struct_size. */

@@ -1,4 +1,4 @@
-// Host-only check of the fold workspaces (csrc/fold_ws.h: radix_fold_carve, molecule_carve, region_carve) under AddressSanitizer /
+// Host-only check of the fold workspaces (csrc/fold_ws.h: radix_fold_carve, unique_feature_carve, molecule_carve, region_carve) under AddressSanitizer /
 // UBSan.  For every point of a grid of sizes each function runs as the engine runs it - on an arena without memory, which gives the
 // size, then on a malloc'ed block of exactly that size - and every block it hands out must be non-null, at a multiple of 256 bytes
 // from the base, inside the block and disjoint from every other; each is then written over its full stated extent, the blocks taken
@@ -78,6 +78,15 @@ static void radix_point(size_t n, size_t kb, size_t tmpb, bool measure_only) {
         return bl;
     });
 }
+// (no formula came before this one: the bound is the sum of its blocks' stated extents plus one alignment gap each)
+static void unique_feature_point(size_t n, size_t kb, size_t tmpb, bool measure_only) {
+    UniqueFeatureWs w;
+    const size_t nt = (n + WS_TILE - 1) / WS_TILE;
+    const size_t bound = 2 * std::max<size_t>(n * kb, 1) + std::max<size_t>(tmpb, 1) + std::max<size_t>(n, 1) + std::max<size_t>(3 * nt, 1) * 12 + 6 * 256;
+    run_point("unique-feature stage", n, bound, measure_only, [&](Arena& ar) { unique_feature_carve(ar, n, kb, tmpb, w); }, [&](Arena&) {
+        return std::vector<Block>{ {"a", w.a, n * kb}, {"b", w.b, n * kb}, {"tmp", w.tmp, tmpb}, {"drop", w.drop, n}, {"d_blk", w.d_blk, 3 * nt * 4}, {"d_off", w.d_off, 3 * nt * 8} };
+    });
+}
 static void molecule_point(size_t n, size_t kb, size_t tmpb, size_t n_snps, bool split, bool measure_only) {
     MoleculeWs w;
     run_point("molecule stage", n, old_need_molecule(n, kb, tmpb, n_snps), measure_only, [&](Arena& ar) { molecule_carve(ar, n, kb, tmpb, n_snps, split, w); }, [&](Arena&) {
@@ -130,6 +139,7 @@ int main() {
             const size_t vb = kb == 8 ? 8 : 1;                             // region-level values: words beside 64-bit keys, bytes beside 128-bit keys
             for (const auto& s : sizes) {
                 radix_point(n, kb, s[0], measure_only);
+                unique_feature_point(n, kb, s[0], measure_only);
                 for (size_t n_snps : { size_t(0), size_t(1) })
                     for (bool split : { false, true }) molecule_point(n, kb, s[0], n_snps, split, measure_only);
                 // the widest of the 16 slices: even slices, or every hit in one (rounded up to 64 as count_region_hits does)

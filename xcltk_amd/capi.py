@@ -25,6 +25,7 @@ XCK_F_CELL_SUMMARY = 64
 XCK_F_FEATURE_SUMMARY = 128
 XCK_F_UMI_CONSENSUS = 256
 XCK_F_MIN_BASEQ = 512
+XCK_F_UNIQUE_FEATURE = 1024
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -194,6 +195,15 @@ class BaseqStats(C.Structure):
 MOLECULE_FIELDS = tuple(k for k, _ in MoleculeStats._fields_[2:])
 
 
+class UmiFeatureStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_int64) for k in (
+        "molecules", "multi_feature", "keys", "keys_dropped")]
+
+
+# the counters of xck_umi_feature_stats in the struct's order
+UMI_FEATURE_FIELDS = tuple(k for k, _ in UmiFeatureStats._fields_[2:])
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -253,6 +263,7 @@ SYMBOLS = [
     ("xck_get_feature_summary", C.c_int, [C.c_void_p, C.c_int, _P(FeatureSummary)]),
     ("xck_get_molecule_stats", C.c_int, [C.c_void_p, _P(MoleculeStats)]),
     ("xck_get_baseq_stats", C.c_int, [C.c_void_p, _P(BaseqStats)]),
+    ("xck_get_umi_feature_stats", C.c_int, [C.c_void_p, _P(UmiFeatureStats)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

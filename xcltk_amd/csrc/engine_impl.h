@@ -223,6 +223,11 @@ struct EngineImpl {
     // UMI consensus (XCK_F_UMI_CONSENSUS, umi_consensus.h): the five agreement counters in HBM, MOL_SLOTS copies that the getter sums (null = off: the molecule stage keeps the
     // first read's base), filled by the molecule stage of xck_finish and valid from a successful finish to the next reset
     unsigned long long* d_mol = nullptr; bool mol_stats_valid = false;
+    // unique-feature molecules (XCK_F_UNIQUE_FEATURE, umi_feature.h; null = off: the fold counts every key): row -> rank in the join
+    // table's (contig, start, end, index) order; per rank the first and one-past-last rank of its contig; the four counters of the last
+    // xck_finish, valid from a successful finish to the next reset
+    uint32_t* d_uf_rank = nullptr; uint2* d_uf_span = nullptr;
+    long long uf_stats[4] = {0, 0, 0, 0}; bool uf_stats_valid = false;
     // xck_refold (refold.h): the caller's SNP list as given to xck_create, the regrown tables' capacities, and the builder's own buffers
     std::vector<xck_snp> snps_in;
     size_t csr_reg_cap_bytes = 0, fmat_cap_bytes = 0;     // of d_csr_reg and d_fmat, which a refold may have to regrow
@@ -310,6 +315,8 @@ int finish_init(EngineImpl* im);                           // engine_create: per
 int snp_verdicts(EngineImpl* im, uint32_t* d_kept);        // d_kept[s] = snp_passes() of sorted SNP s on the tallies of the last finish (enqueued on s_comp)
 int molecule_stats_init(EngineImpl* im);                   // engine_create, XCK_F_UMI_CONSENSUS on a pileup pipeline: the counters' memory (umi_consensus.h)
 int molecule_stats_reset(EngineImpl* im);                  // engine_reset: the counters zeroed on s_comp (the caller synchronises)
+int unique_feature_init(EngineImpl* im, const xck_config* cfg);   // engine_create, XCK_F_UNIQUE_FEATURE on a basefc pipeline: the rank tables (umi_feature.h)
+int unique_feature_reset(EngineImpl* im);                  // engine_reset: the counters are no longer valid
 // Control words go to the host through MAPPED pinned memory written by a tiny kernel, never through the DMA engines: a 4 KB hipMemcpy
 // D2H would queue behind a 170 MB result copy-out of another engine.  One block of `threads` on s_comp copies src[0, n) to host_alias
 // (a device alias of pinned words, d_hctl); the caller checks hipGetLastError().

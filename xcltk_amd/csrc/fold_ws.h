@@ -41,6 +41,19 @@ inline void radix_fold_carve(Arena& ar, size_t n, size_t key_bytes, size_t tmp_b
     w.coo_at = ar.off; ar.get<int32_t>(n * 3);
 }
 
+// ---- basefc, unique-feature molecules (umi_feature.h): workspace 1, ahead of the radix-sort fold, which begins the arena anew ----------
+struct UniqueFeatureWs {
+    void *a, *b, *tmp;                                 // n molecule-major keys: the sort's input, later the distinct keys D; the sorted keys; the sort's scratch
+    uint8_t* drop;                                     // per key of D: 1 = its molecule has another row on the contig
+    uint32_t* d_blk; unsigned long long* d_off;        // per tile of WS_TILE keys, three rows of nt: [distinct keys, later survivors | molecules | multi-feature molecules] and their scans
+};
+inline void unique_feature_carve(Arena& ar, size_t n, size_t key_bytes, size_t tmp_bytes, UniqueFeatureWs& w) {
+    const size_t nt = (n + WS_TILE - 1) / WS_TILE;
+    w.a = ar.get<char>(n * key_bytes); w.b = ar.get<char>(n * key_bytes); w.tmp = ar.get<char>(tmp_bytes);
+    w.drop = ar.get<uint8_t>(n);
+    w.d_blk = ar.get<uint32_t>(3 * nt); w.d_off = ar.get<unsigned long long>(3 * nt);
+}
+
 // ---- pileup, the molecule stage: workspace 1 -----------------------------------------------------------------------------------------
 struct MoleculeWs {
     void* alt; uint64_t* valt; void* tmp;              // n keys and values: the sorted hits, or the radix sort's input; the radix sort's scratch

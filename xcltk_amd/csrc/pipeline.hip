@@ -478,6 +478,7 @@ int engine_reset(EngineImpl* im) {
     HIP_TRY(hipMemsetAsync(im->d_ctl, 0, CTL_WORDS * sizeof(unsigned long long), im->s_comp));
     rc = summaries_reset(im); if (rc) return rc;
     rc = molecule_stats_reset(im); if (rc) return rc;
+    rc = unique_feature_reset(im); if (rc) return rc;
     im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false; im->mol_valid = false; im->sc_valid = false;
@@ -556,6 +557,7 @@ int engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out) {
     HIP_TRY(hipHostGetDevicePointer((void**)&im->d_hctl, im->h_ctl, 0));
     rc = ensure_hits(im, (size_t)e->knobs.hit_cap0); if (rc) return rc;   // (XCK_HIT_CAP0: test knob)
     if ((cfg->flags & XCK_F_UMI_CONSENSUS) && im->mode == XCK_MODE_BAF) { rc = molecule_stats_init(im); if (rc) return rc; }
+    if ((cfg->flags & XCK_F_UNIQUE_FEATURE) && im->mode == XCK_MODE_BASEFC) { rc = unique_feature_init(im, cfg); if (rc) return rc; }
     return summaries_init(im, cfg->flags);
 }
 
@@ -564,7 +566,7 @@ void engine_destroy(EngineImpl* im) {
     hipSetDevice(im->device);
     if (im->s_comp) hipStreamSynchronize(im->s_comp);
     void* ptrs[] = { im->d_reg_s0, im->d_reg_e0, im->d_reg_row, im->d_reg_pmax, im->d_snp_p0, im->d_snp_win,
-                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept, im->d_mol,
+                     im->d_csr_off, im->d_csr_reg, im->d_snp_info, im->d_tally, im->d_keys, im->d_vals, im->d_nkeys, im->d_nvals, im->d_ctl, im->d_meta, im->d_fate, im->d_cell, im->d_cmat, im->d_feat, im->d_fmat, im->d_kept, im->d_mol, im->d_uf_rank, im->d_uf_span,
                      im->d_csr_alt, im->d_rf, im->d_cm, im->d_sc_perm, im->ws1.base, im->ws2.base };
     for (void* p : ptrs) if (p) hipFree(p);
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq, s.qual }; for (void* p : q) if (p) hipFree(p); }

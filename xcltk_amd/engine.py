@@ -94,7 +94,7 @@ class Engine(object):
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
                  incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1,
                  min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None,
-                 umi_consensus=False, min_baseq=0):
+                 umi_consensus=False, min_baseq=0, umi_feature=None):
         """regions: iterable of (chrom, start1, end1_incl[, name]); snps: iterable of
         (chrom, pos1, ref, alt, ref_hap, alt_hap); chrom names must already be stripped of
         'chr' and present in contig_names.  excl_pairs = (region indices, snp indices): pairs left out of the SNP -> region
@@ -108,7 +108,11 @@ class Engine(object):
         environment does the same for every handle with a BAF pipeline.  min_baseq=Q (1 .. 93, xck_config.min_baseq; needs a BAF
         pipeline; set together with XCK_F_MIN_BASEQ): a base whose quality is below Q (and stored: not 0xff) is not shown at its SNP, as `samtools mpileup -Q` / pysam's
         min_base_quality do; the qualities come from ingest_bam() or push_batch(..., qual=), and baseq_stats() counts what was masked;
-        XCK_MIN_BASEQ in the environment supplies it where it is 0.  self.min_baseq is the floor the handle runs with."""
+        XCK_MIN_BASEQ in the environment supplies it where it is 0.  self.min_baseq is the floor the handle runs with.
+        umi_feature="unique" (XCK_F_UNIQUE_FEATURE; needs a basefc pipeline): a molecule (contig, cell, UMI) counts only when exactly
+        one region of its contig accepted its reads - one that two or more regions hold is dropped from all of them - and
+        umi_feature_stats() says how many were; None and "all" count every (region, cell, UMI), the default;
+        XCK_UMI_FEATURE=unique in the environment does the same for every handle with a basefc pipeline."""
         self.lib = capi.load()
         self.mode = mode
         self.contig_names = list(contig_names)
@@ -180,7 +184,10 @@ class Engine(object):
         if not self.min_baseq and not decode_only and (mode & XCK_MODE_BAF):     # (xck_create checks the knob: a malformed one fails below)
             knob = os.environ.get("XCK_MIN_BASEQ", "")
             self.min_baseq = int(knob) if knob.isdigit() else 0
-        cfg.flags = int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0) | (capi.XCK_F_UMI_CONSENSUS if umi_consensus else 0)
+        if umi_feature not in (None, "all", "unique"):
+            raise ValueError("umi_feature must be None, 'all' or 'unique'")
+        cfg.flags = (int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0) | (capi.XCK_F_UMI_CONSENSUS if umi_consensus else 0)
+                     | (capi.XCK_F_UNIQUE_FEATURE if umi_feature == "unique" else 0))
         cfg.min_baseq = int(min_baseq)                              # (behind the flags: a non-zero value sets XCK_F_MIN_BASEQ beside it)
         self.cfg = cfg
         self.n_cells = int(n_cells)
@@ -634,6 +641,19 @@ class Engine(object):
             return None
         self._check(rc, "xck_get_molecule_stats")
         return {k: int(getattr(out, k)) for k in capi.MOLECULE_FIELDS}
+
+    def umi_feature_stats(self):
+        """What the unique-feature rule of the last finish() saw (xck_get_umi_feature_stats): dict of molecules, multi_feature, keys,
+        keys_dropped in the struct's order (keys - keys_dropped = the sum of the count matrix), or None where the handle has nothing
+        to say - made without umi_feature="unique" / XCK_F_UNIQUE_FEATURE (and without XCK_UMI_FEATURE=unique in the environment),
+        before finish() or after reset()."""
+        out = capi.UmiFeatureStats()
+        out.struct_size = C.sizeof(capi.UmiFeatureStats)
+        rc = self.lib.xck_get_umi_feature_stats(self.h, C.byref(out))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_umi_feature_stats")
+        return {k: int(getattr(out, k)) for k in capi.UMI_FEATURE_FIELDS}
 
 
 class BamStream(object):

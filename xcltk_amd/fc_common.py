@@ -613,13 +613,41 @@ def write_molecule_summary(eng, dist, path, log_prefix="[engine]"):
                                   lambda a: "%s UMI consensus: %d of %d molecules changed" % (log_prefix, as_dict(a)["changed"], as_dict(a)["molecules"])))
 
 
+def umi_feature_summary_text(stats, n_ranks=1, cut_contigs=0):
+    """Text of umi_feature_summary.tsv: one `name\\tcount` line per counter of xck_umi_feature_stats, in the struct's order; runs of
+    several ranks start with `#ranks=N cut_contigs=K`."""
+    from .capi import UMI_FEATURE_FIELDS
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    return head + "".join("%s\t%d\n" % (k, int(stats[k])) for k in UMI_FEATURE_FIELDS)
+
+
+def write_umi_feature_summary(eng, dist, path, log_prefix="[engine]"):
+    """What the unique-feature rule of the basefc fold dropped (Engine.umi_feature_stats, after finish()) -> `path`, when the handle
+    counts unique-feature molecules only (XCK_UMI_FEATURE=unique in the environment, or XCK_F_UNIQUE_FEATURE): nothing happens
+    otherwise.  Multi-GPU: a collective call - the counters are summed over the ranks and the writer rank writes the file; the ranks
+    own whole contigs (make_engine refuses a plan that gives the pieces of one to several ranks) and a molecule lives on one contig, so the sums are
+    the one-GPU run's.  Returns the (summed) dict or None."""
+    from .capi import UMI_FEATURE_FIELDS
+    umi_feature_stats = getattr(eng, "umi_feature_stats", None)   # (an engine-like object without the method drops nothing)
+    st = umi_feature_stats() if umi_feature_stats else None
+    if st is None:
+        return None
+    as_dict = lambda a: dict(zip(UMI_FEATURE_FIELDS, a[0].tolist()))
+    return as_dict(_write_summary(dist, path, [[st[k] for k in UMI_FEATURE_FIELDS]], lambda a, n_ranks, cut: umi_feature_summary_text(as_dict(a), n_ranks, cut),
+                                  lambda a: "%s unique-feature molecules: %d of %d molecules on two or more features dropped" %
+                                  (log_prefix, as_dict(a)["multi_feature"], as_dict(a)["molecules"])))
+
+
 def write_summaries(eng, dist, prefix, samples, regions, snps=None, mode=None, log_prefix="[engine]"):
     """The opt-in tables of one pipeline next to its matrices: `prefix` + read_summary.tsv (XCK_READ_FATE=1), cell_summary.tsv
     (XCK_CELL_SUMMARY=1), feature_summary.tsv (XCK_FEATURE_SUMMARY=1), - `snps` given, the pileup pipeline - snp_summary.tsv and - the
-    pileup pipeline under XCK_UMI_CONSENSUS=1 - molecule_summary.tsv, each only when the handle keeps it.  `prefix` is a path
+    pileup pipeline under XCK_UMI_CONSENSUS=1 - molecule_summary.tsv and - the basefc pipeline under XCK_UMI_FEATURE=unique -
+    umi_feature_summary.tsv, each only when the handle keeps it.  `prefix` is a path
     prefix: a directory with its separator, or e.g. <dir>/xcltk. ; mode names the pipeline of a XCK_MODE_BOTH handle.  Multi-GPU: the
     writers' collective calls, in this order on every rank."""
     from .capi import XCK_MODE_BAF
+    if getattr(eng, "mode", 0) & XCK_MODE_BASEFC and (mode is None or mode & XCK_MODE_BASEFC):
+        write_umi_feature_summary(eng, dist, prefix + "umi_feature_summary.tsv", log_prefix)
     write_read_summary(eng, dist, prefix + "read_summary.tsv", mode, log_prefix)
     write_cell_summary(eng, dist, prefix + "cell_summary.tsv", samples, mode, log_prefix)
     write_feature_summary(eng, dist, prefix + "feature_summary.tsv", regions, mode, log_prefix)
@@ -646,6 +674,15 @@ def make_engine(conf, mode, regions, snps=(), device=None, **extra):
     if dist.active:                                   # multi-GPU: this rank counts the regions of its contigs (or contig pieces)
         dist.plan(conf, regions, snps)
         kw["region_mask"] = dist.region_mask
+        # unique-feature molecules: a molecule is judged on the keys of its whole contig, so the pieces of a contig must be one rank's
+        if mode & XCK_MODE_BASEFC and (kw.get("umi_feature") == "unique" or os.environ.get("XCK_UMI_FEATURE", "") == "unique"):
+            owners = {}
+            for u, r in zip(dist.units, dist.unit_owner.tolist()):
+                owners.setdefault(u["contig"], set()).add(r)
+            cut = [names[c] for c in sorted(owners) if len(owners[c]) > 1]
+            if cut:
+                raise XckError("XCK_UMI_FEATURE=unique: the multi-GPU plan cuts contig %s over ranks, and a molecule with keys on both sides of "
+                               "a cut would be judged by two ranks; run with fewer ranks or without the knob." % ", ".join(cut))
     eng = Engine(mode, names, regions, len(conf.samples), snps=snps,
                  barcodes=conf.barcodes if conf.use_barcodes() else None,
                  cell_tag=conf.cell_tag, umi_tag=conf.umi_tag, device=device, **kw)
