@@ -100,6 +100,11 @@
  *                                         XCK_F_UNIQUE_FEATURE (xck_get_umi_feature_stats): the front-ends then write umi_feature_summary.tsv next to
  *                                         their count matrix.  Any other value fails xck_create with XCK_E_ARG.  Off, no kernel is added and every
  *                                         output is byte-identical.  BAF-only and decode-only handles ignore it.
+ *   XCK_UMI_DEDUP=1mm_all|exact           (opt-in; unset, empty or `exact`: off) every handle with a basefc pipeline that drives a GPU counts, per
+ *                                         (region, cell), the connected components of the graph that joins UMIs one substitution apart, as if made
+ *                                         with XCK_F_UMI_COLLAPSE (xck_get_umi_dedup_stats): the front-ends then write umi_dedup_summary.tsv next
+ *                                         to their count matrix.  Any other value fails xck_create with XCK_E_ARG.  Read once, at xck_create.  Off,
+ *                                         no kernel is added and every output is byte-identical.  BAF-only and decode-only handles ignore it.
  *   XCK_GROUP_LONG_ROW=<entries>          xck_group_counts: a source row with at least this many entries is summed by one block with a table in
  *                                         LDS, a shorter one by one wave in registers (default and upper bound 64, at least 1; tests: a small value
  *                                         reaches the block shape with small inputs)
@@ -293,6 +298,18 @@ typedef struct xck_config {
                                    and xck_group_counts follow.  xck_get_umi_feature_stats counts what was dropped.  Any handle with
                                    a basefc pipeline; on XCK_MODE_BOTH the BAF half is untouched.  XCK_E_ARG on a BAF-only handle
                                    and together with XCK_F_DECODE_ONLY                                                          */
+#define XCK_F_UMI_COLLAPSE 2048 /* basefc: 1-mismatch UMI collapsing (STARsolo's 1MM_All, UMI-tools' cluster).  Within one (row, cell) two
+                                   of the distinct keys the join accepted since the last reset are adjacent when both UMI key codes
+                                   are direct 2-bit codes (xck_umi_bits) of the same length that differ in exactly one base; the
+                                   matrix value is the number of connected components of that graph instead of the number of keys.
+                                   Interned codes (a UMI with N, an over-long UMI, a read name) are adjacent to nothing.  Cells and
+                                   rows never interact; the result does not depend on read, batch or shard order.  With
+                                   XCK_F_UNIQUE_FEATURE the unique-feature rule runs first, on exact UMIs, and its survivors are
+                                   collapsed.  The read-level numbers (n_hits, n_hits_unique, xck_get_read_fate, the read columns of
+                                   the summaries) describe the join and do not change; the matrix, its marginals in the summaries
+                                   and xck_group_counts follow.  xck_get_umi_dedup_stats counts what was merged.  Any handle with a
+                                   basefc pipeline; on XCK_MODE_BOTH the BAF half is untouched.  XCK_E_ARG on a BAF-only handle and
+                                   together with XCK_F_DECODE_ONLY                                                              */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -485,6 +502,19 @@ typedef struct xck_umi_feature_stats {
     int64_t  keys_dropped;      /* ... of them the keys of the multi_feature molecules                                         */
 } xck_umi_feature_stats;
 
+/* What the 1-mismatch UMI collapsing of the last xck_finish saw (handles made with XCK_F_UMI_COLLAPSE; additive, ABI 3 is unchanged).
+ * A group is one (row, cell) with at least one key.  struct_size = sizeof(xck_umi_dedup_stats), as for xck_decode_stats. */
+typedef struct xck_umi_dedup_stats {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t  keys;              /* distinct exact (row, cell, UMI) keys entering the stage (behind the unique-feature rule, if set) */
+    int64_t  molecules;         /* connected components: the sum of the count matrix                                           */
+    int64_t  groups;            /* (row, cell) groups: the non-zeros of the count matrix                                       */
+    int64_t  groups_changed;    /* ... whose value is smaller than their number of keys                                        */
+    int64_t  opaque_keys;       /* keys with an interned UMI code: never merged                                                */
+    int64_t  max_group;         /* keys of the largest group                                                                   */
+} xck_umi_dedup_stats;
+
 /* The pairs the base-quality floor saw (xck_config.min_baseq / XCK_MIN_BASEQ; xck_get_baseq_stats): (read, SNP) pairs of the pileup
  * pipeline's join since the last reset in which the read stores a base at the SNP, and those of them the floor masked.
  * struct_size = sizeof(xck_baseq_stats), as for xck_decode_stats. */
@@ -676,6 +706,12 @@ int  xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out);
  * XCK_E_ARG for a null pointer or a short struct_size.  A run sharded by whole contigs sums its handles' counters to the one-GPU run's;
  * a molecule of a contig cut over several GPUs would be judged by each on its own part, which is why the front-ends refuse such a plan. */
 int  xck_get_umi_feature_stats(xck_engine* e, xck_umi_feature_stats* out);
+/* The counters of the 1-mismatch UMI collapsing of the handle's basefc pipeline (set out->struct_size first), as the last xck_finish
+ * counted them; xck_group_counts does not change them, xck_reset clears them.  XCK_E_STATE on a handle without XCK_F_UMI_COLLAPSE (and
+ * without XCK_UMI_DEDUP=1mm_all), before a successful xck_finish, after an xck_reset, or when a fold of the handle has failed; XCK_E_ARG
+ * for a null pointer or a short struct_size.  The handles of a multi-GPU run own disjoint rows, a group never spans two of them, and
+ * their counters add up to the one-GPU run's (max_group: the largest). */
+int  xck_get_umi_dedup_stats(xck_engine* e, xck_umi_dedup_stats* out);
 /* The pair counters of the handle's base-quality floor (set out->struct_size first).  Waits for the handle's queued work as xck_flush
  * does; xck_reset clears them, xck_finish and the derived calls do not change them.  A tile the join replays after an overflow counts
  * once.  XCK_E_STATE on a handle without a floor (and on a decode-only handle), XCK_E_ARG for a null pointer or a short struct_size. */

@@ -40,6 +40,7 @@ int  engine_snp_counts(EngineImpl*, xck_result*) { return XCK_E_ARG; }
 int  engine_group_counts(EngineImpl*, int, int, const int32_t*, xck_result*, GroupTimes*) { return XCK_E_ARG; }
 int  engine_molecule_stats(EngineImpl*, xck_molecule_stats*) { return XCK_E_ARG; }
 int  engine_umi_feature_stats(EngineImpl*, xck_umi_feature_stats*) { return XCK_E_ARG; }
+int  engine_umi_dedup_stats(EngineImpl*, xck_umi_dedup_stats*) { return XCK_E_ARG; }
 // ---- csrc/local_phase.hip ----
 int  local_phase_run(const xck_phase_problem*, const PhasePlan&, double, xck_phase_result**) { return XCK_E_DEVICE; }
 void local_phase_free(xck_phase_result*) {}

@@ -1,4 +1,4 @@
-// Host-only check of the fold workspaces (csrc/fold_ws.h: radix_fold_carve, unique_feature_carve, molecule_carve, region_carve) under AddressSanitizer /
+// Host-only check of the fold workspaces (csrc/fold_ws.h: radix_fold_carve, unique_feature_carve, umi_collapse_carve, molecule_carve, region_carve) under AddressSanitizer /
 // UBSan.  For every point of a grid of sizes each function runs as the engine runs it - on an arena without memory, which gives the
 // size, then on a malloc'ed block of exactly that size - and every block it hands out must be non-null, at a multiple of 256 bytes
 // from the base, inside the block and disjoint from every other; each is then written over its full stated extent, the blocks taken
@@ -87,6 +87,20 @@ static void unique_feature_point(size_t n, size_t kb, size_t tmpb, bool measure_
         return std::vector<Block>{ {"a", w.a, n * kb}, {"b", w.b, n * kb}, {"tmp", w.tmp, tmpb}, {"drop", w.drop, n}, {"d_blk", w.d_blk, 3 * nt * 4}, {"d_off", w.d_off, 3 * nt * 8} };
     });
 }
+// (no formula came before this one either)
+static void umi_collapse_point(size_t n, size_t kb, size_t tmpb, bool measure_only) {
+    UmiCollapseWs w;
+    const size_t nt = (n + WS_TILE - 1) / WS_TILE, nbig = n / (WS_UC_SMALL + 1) + 1;
+    const size_t bound = 2 * std::max<size_t>(n * kb, 1) + std::max<size_t>(tmpb, 1) + std::max<size_t>(n, 1) + nbig * (8 + 4 + 12 + 24) + std::max<size_t>(WS_UC_ROWS * nt, 1) * 12
+                         + std::max<size_t>(n * 3, 1) * 4 + 11 * 256;
+    run_point("UMI collapsing stage", n, bound, measure_only, [&](Arena& ar) { umi_collapse_carve(ar, n, kb, tmpb, w); }, [&](Arena& ar) {
+        if (w.big_cap != nbig) { fprintf(stderr, "FAIL: UMI collapsing stage n=%zu: big_cap %zu, expected %zu\n", n, w.big_cap, nbig); exit(1); }
+        ar.off = w.coo_at;
+        return std::vector<Block>{ {"a", w.a, n * kb}, {"b", w.b, n * kb}, {"tmp", w.tmp, tmpb}, {"root", w.root, n}, {"big_start", w.big_start, nbig * 8}, {"big_size", w.big_size, nbig * 4},
+                                   {"big_words", w.big_words, 3 * nbig * 4}, {"big_off", w.big_off, 3 * nbig * 8}, {"d_blk", w.d_blk, WS_UC_ROWS * nt * 4}, {"d_off", w.d_off, WS_UC_ROWS * nt * 8},
+                                   {"coo", ar.get<int32_t>(n * 3), n * 3 * 4} };
+    });
+}
 static void molecule_point(size_t n, size_t kb, size_t tmpb, size_t n_snps, bool split, bool measure_only) {
     MoleculeWs w;
     run_point("molecule stage", n, old_need_molecule(n, kb, tmpb, n_snps), measure_only, [&](Arena& ar) { molecule_carve(ar, n, kb, tmpb, n_snps, split, w); }, [&](Arena&) {
@@ -140,6 +154,7 @@ int main() {
             for (const auto& s : sizes) {
                 radix_point(n, kb, s[0], measure_only);
                 unique_feature_point(n, kb, s[0], measure_only);
+                umi_collapse_point(n, kb, s[0], measure_only);
                 for (size_t n_snps : { size_t(0), size_t(1) })
                     for (bool split : { false, true }) molecule_point(n, kb, s[0], n_snps, split, measure_only);
                 // the widest of the 16 slices: even slices, or every hit in one (rounded up to 64 as count_region_hits does)

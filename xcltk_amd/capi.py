@@ -26,6 +26,7 @@ XCK_F_FEATURE_SUMMARY = 128
 XCK_F_UMI_CONSENSUS = 256
 XCK_F_MIN_BASEQ = 512
 XCK_F_UNIQUE_FEATURE = 1024
+XCK_F_UMI_COLLAPSE = 2048
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -204,6 +205,15 @@ class UmiFeatureStats(C.Structure):
 UMI_FEATURE_FIELDS = tuple(k for k, _ in UmiFeatureStats._fields_[2:])
 
 
+class UmiDedupStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_int64) for k in (
+        "keys", "molecules", "groups", "groups_changed", "opaque_keys", "max_group")]
+
+
+# the counters of xck_umi_dedup_stats in the struct's order
+UMI_DEDUP_FIELDS = tuple(k for k, _ in UmiDedupStats._fields_[2:])
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -264,6 +274,7 @@ SYMBOLS = [
     ("xck_get_molecule_stats", C.c_int, [C.c_void_p, _P(MoleculeStats)]),
     ("xck_get_baseq_stats", C.c_int, [C.c_void_p, _P(BaseqStats)]),
     ("xck_get_umi_feature_stats", C.c_int, [C.c_void_p, _P(UmiFeatureStats)]),
+    ("xck_get_umi_dedup_stats", C.c_int, [C.c_void_p, _P(UmiDedupStats)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

@@ -68,6 +68,10 @@ Knobs xck::Knobs::from_env() {
         k.umi_feature_text = str("XCK_UMI_FEATURE");
         k.umi_feature = k.umi_feature_text == "unique" ? 1 : k.umi_feature_text == "all" ? 0 : -1;
     }
+    if (*str("XCK_UMI_DEDUP")) {                                         // 1mm_all | exact; anything else: -1, and xck_create quotes the text
+        k.umi_dedup_text = str("XCK_UMI_DEDUP");
+        k.umi_dedup = k.umi_dedup_text == "1mm_all" ? 1 : k.umi_dedup_text == "exact" ? 0 : -1;
+    }
     if (*str("XCK_MIN_BASEQ")) {                                         // decimal digits only, 0 .. 93; anything else: -1, and xck_create quotes the text
         k.min_baseq_text = str("XCK_MIN_BASEQ");
         const std::string& t = k.min_baseq_text;
@@ -135,6 +139,10 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
         if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("XCK_F_UNIQUE_FEATURE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
         if (!(cfg->mode & XCK_MODE_BASEFC)) { set_thread_error("XCK_F_UNIQUE_FEATURE: the handle has no basefc pipeline"); return XCK_E_ARG; }
     }
+    if (cfg->flags & XCK_F_UMI_COLLAPSE) {
+        if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("XCK_F_UMI_COLLAPSE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+        if (!(cfg->mode & XCK_MODE_BASEFC)) { set_thread_error("XCK_F_UMI_COLLAPSE: the handle has no basefc pipeline"); return XCK_E_ARG; }
+    }
     if (cfg->min_baseq) {
         if (cfg->min_baseq < 0 || cfg->min_baseq > 93) { set_thread_error("xck_config.min_baseq outside 0 .. 93"); return XCK_E_ARG; }
         if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("xck_config.min_baseq needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
@@ -144,6 +152,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     e->knobs = Knobs::from_env();
     if (e->knobs.min_baseq < 0) { set_thread_error("malformed XCK_MIN_BASEQ \"" + e->knobs.min_baseq_text + "\": expected a number in 0 .. 93"); delete e; return XCK_E_ARG; }
     if (e->knobs.umi_feature < 0) { set_thread_error("malformed XCK_UMI_FEATURE \"" + e->knobs.umi_feature_text + "\": expected unique or all"); delete e; return XCK_E_ARG; }
+    if (e->knobs.umi_dedup < 0) { set_thread_error("malformed XCK_UMI_DEDUP \"" + e->knobs.umi_dedup_text + "\": expected 1mm_all or exact"); delete e; return XCK_E_ARG; }
     // the tag filter: the struct's fields, or - where the struct carries none - the knob; checked before a device is touched
     {
         DecodeCfg& d = e->dec;
@@ -165,6 +174,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     e->read_fate = !(cfg->flags & XCK_F_DECODE_ONLY) && ((cfg->flags & XCK_F_READ_FATE) || e->knobs.read_fate || e->cell_summary);
     e->umi_consensus = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BAF) && ((cfg->flags & XCK_F_UMI_CONSENSUS) || e->knobs.umi_consensus);   // (the knob: ignored by the other handles)
     e->unique_feature = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BASEFC) && ((cfg->flags & XCK_F_UNIQUE_FEATURE) || e->knobs.umi_feature > 0);   // (the knob: ignored by the other handles)
+    e->umi_collapse = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BASEFC) && ((cfg->flags & XCK_F_UMI_COLLAPSE) || e->knobs.umi_dedup > 0);   // (the knob: ignored by the other handles)
     e->min_baseq = cfg->min_baseq ? cfg->min_baseq : (!(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BAF)) ? e->knobs.min_baseq : 0;   // (the knob: ignored by the other handles)
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
@@ -183,6 +193,8 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
             if (e->umi_consensus && modes[k] == XCK_MODE_BAF) c.flags |= XCK_F_UMI_CONSENSUS;
             c.flags &= ~XCK_F_UNIQUE_FEATURE;                  // the basefc pipeline's rule alone (XCK_UMI_FEATURE=unique)
             if (e->unique_feature && modes[k] == XCK_MODE_BASEFC) c.flags |= XCK_F_UNIQUE_FEATURE;
+            c.flags &= ~XCK_F_UMI_COLLAPSE;                    // the basefc pipeline's rule alone (XCK_UMI_DEDUP=1mm_all)
+            if (e->umi_collapse && modes[k] == XCK_MODE_BASEFC) c.flags |= XCK_F_UMI_COLLAPSE;
             c.min_baseq = modes[k] == XCK_MODE_BAF ? e->min_baseq : 0;   // (XCK_MIN_BASEQ folded in)
             const int rc = engine_create(&c, e, &e->impls[k]);
             e->n_impl = k + 1;                                 // (a pipeline that failed half-way is destroyed with the rest)
@@ -403,6 +415,15 @@ int xck_get_umi_feature_stats(xck_engine* e, xck_umi_feature_stats* out) {
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
     return engine_umi_feature_stats(e->impls[0], out);                  // (a fused handle answers from its basefc pipeline)
+}
+
+int xck_get_umi_dedup_stats(xck_engine* e, xck_umi_dedup_stats* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_umi_dedup_stats)) { e->err = "xck_umi_dedup_stats.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (!e->umi_collapse || e->n_impl <= 0) { e->err = "handle made without XCK_F_UMI_COLLAPSE"; return XCK_E_STATE; }
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    return engine_umi_dedup_stats(e->impls[0], out);                    // (a fused handle answers from its basefc pipeline)
 }
 
 int xck_get_molecule_stats(xck_engine* e, xck_molecule_stats* out) {

@@ -228,6 +228,9 @@ struct EngineImpl {
     // xck_finish, valid from a successful finish to the next reset
     uint32_t* d_uf_rank = nullptr; uint2* d_uf_span = nullptr;
     long long uf_stats[4] = {0, 0, 0, 0}; bool uf_stats_valid = false;
+    // 1-mismatch UMI collapsing (XCK_F_UMI_COLLAPSE, umi_collapse.h; false = off: the fold counts every key): the six counters of the last
+    // xck_finish, valid from a successful finish to the next reset
+    bool umi_collapse = false; long long uc_stats[6] = {0, 0, 0, 0, 0, 0}; bool uc_stats_valid = false;
     // xck_refold (refold.h): the caller's SNP list as given to xck_create, the regrown tables' capacities, and the builder's own buffers
     std::vector<xck_snp> snps_in;
     size_t csr_reg_cap_bytes = 0, fmat_cap_bytes = 0;     // of d_csr_reg and d_fmat, which a refold may have to regrow
@@ -317,6 +320,7 @@ int molecule_stats_init(EngineImpl* im);                   // engine_create, XCK
 int molecule_stats_reset(EngineImpl* im);                  // engine_reset: the counters zeroed on s_comp (the caller synchronises)
 int unique_feature_init(EngineImpl* im, const xck_config* cfg);   // engine_create, XCK_F_UNIQUE_FEATURE on a basefc pipeline: the rank tables (umi_feature.h)
 int unique_feature_reset(EngineImpl* im);                  // engine_reset: the counters are no longer valid
+int umi_collapse_reset(EngineImpl* im);                    // engine_reset: the counters of umi_collapse.h are no longer valid
 // Control words go to the host through MAPPED pinned memory written by a tiny kernel, never through the DMA engines: a 4 KB hipMemcpy
 // D2H would queue behind a 170 MB result copy-out of another engine.  One block of `threads` on s_comp copies src[0, n) to host_alias
 // (a device alias of pinned words, d_hctl); the caller checks hipGetLastError().

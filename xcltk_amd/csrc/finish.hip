@@ -10,7 +10,7 @@
 //                 (k_hap_items; fallback: sort + k_hap_class / k_hap_sum), k_hap_count / k_hap_scatter (AD / DP / OTH -> COO);
 //                 128-bit keys: k_first_read and the sorted path.  XCK_F_UMI_CONSENSUS: a vote per key instead of the first read and no
 //                 claims (umi_consensus.h: k_consensus_base / k_consensus_read / k_consensus_long, the agreement counters).  XCK_F_UNIQUE_FEATURE (basefc): the keys grouped by
-//                 molecule first and those of the molecules on two or more rows removed (umi_feature.h), then the radix-sort fold.  xck_refold (refold.h) runs the half behind k_tally_rows again; with a
+//                 molecule first and those of the molecules on two or more rows removed (umi_feature.h), then the radix-sort fold.  XCK_F_UMI_COLLAPSE (basefc): one key per connected component of the 1-mismatch graph of every (row, cell) (umi_collapse.h), counted by fold_coo.  xck_refold (refold.h) runs the half behind k_tally_rows again; with a
 //                 cell mask: k_row_bounds, k_tally_rows_cells / k_tally_long_cells (tallies of the enabled cells), k_expand<MASK>.
 //   snp_counts  : the SNP x cell matrices of the finished pileup from the molecule stage alone (snp_counts.h).
 //   group_counts: the row x group sums of the result blocks or of the SNP x cell blocks under a cell -> group mapping (group_counts.h).
@@ -1166,6 +1166,8 @@ static int fold_by_radix_sort(EngineImpl* im, size_t n) {
 
 // the same fold over the keys of the unique-feature molecules alone (XCK_F_UNIQUE_FEATURE)
 #include "umi_feature.h"
+// the connected components of the 1-mismatch graph of every (row, cell) instead of its keys (XCK_F_UMI_COLLAPSE)
+#include "umi_collapse.h"
 
 template <class K>
 static int finish_basefc(EngineImpl* im, size_t n) {
@@ -1174,9 +1176,11 @@ static int finish_basefc(EngineImpl* im, size_t n) {
     if (im->d_uf_rank) {
         im->fold_path = 2;
         if (int rc = unique_feature_keys<K>(im, n, &n)) return rc;
-        if (n == 0) return 0;                                             // (every molecule dropped: empty matrix)
+        if (n == 0) return 0;                                             // (every molecule dropped: empty matrix, and the counters of umi_collapse.h stay zero)
+        if (im->umi_collapse) return umi_collapse_fold<K>(im, n);          // (the survivors on exact UMIs, collapsed afterwards)
         return fold_by_radix_sort<K>(im, n);
     }
+    if (im->umi_collapse) { im->fold_path = 2; return umi_collapse_fold<K>(im, n); }
     // 64-bit keys: the partition fold (fold_partition.h - no sort); it hands back PF_FALLBACK for the inputs it cannot place
     // (one (row, cell) with more keys than a work item holds, ...), and the radix-sort fold then takes over
     if constexpr (sizeof(K) == 8) {
@@ -1481,16 +1485,17 @@ static int finish_t(EngineImpl* im) {
     const size_t n = im->cursor;
     im->d_tally_cur = nullptr; im->d_cell_bits = nullptr;          // (a finish counts every cell)
     for (int m = 0; m < 4; m++) { im->res_nnz[m] = 0; im->d_res[m] = nullptr; }
-    im->mol_stats_valid = false; im->uf_stats_valid = false;
+    im->mol_stats_valid = false; im->uf_stats_valid = false; im->uc_stats_valid = false;
+    if (im->umi_collapse) for (long long& v : im->uc_stats) v = 0;
     { int64_t acc = 0; for (int sh = 0; sh < NSHARD; sh++) acc += (int64_t)im->h_ctl[ctl_accepted(sh)];
       im->st.n_hits = acc; }                          // accepted pairs (before the LDS de-duplication)
     im->st.n_hits_unique = (int64_t)(n + im->ncursor);   // keys that reached HBM
     join_stamps_report(im);
-    if (n == 0) { im->mol_keys = nullptr; im->mol_al = nullptr; im->mol_n = 0; im->mol_valid = im->mode == XCK_MODE_BAF; im->mol_stats_valid = im->d_mol != nullptr; im->uf_stats_valid = im->d_uf_rank != nullptr; return 0; }   // (the counters are zero since the reset)
+    if (n == 0) { im->mol_keys = nullptr; im->mol_al = nullptr; im->mol_n = 0; im->mol_valid = im->mode == XCK_MODE_BAF; im->mol_stats_valid = im->d_mol != nullptr; im->uf_stats_valid = im->d_uf_rank != nullptr; im->uc_stats_valid = im->umi_collapse; return 0; }   // (the counters are zero since the reset)
     const int rc = im->mode == XCK_MODE_BASEFC ? finish_basefc<K>(im, n) : finish_pileup<K>(im, n);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
-    im->mol_stats_valid = im->d_mol != nullptr; im->uf_stats_valid = im->d_uf_rank != nullptr;
+    im->mol_stats_valid = im->d_mol != nullptr; im->uf_stats_valid = im->d_uf_rank != nullptr; im->uc_stats_valid = im->umi_collapse;
     return 0;
 }
 

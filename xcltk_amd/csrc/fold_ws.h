@@ -54,6 +54,29 @@ inline void unique_feature_carve(Arena& ar, size_t n, size_t key_bytes, size_t t
     w.d_blk = ar.get<uint32_t>(3 * nt); w.d_off = ar.get<unsigned long long>(3 * nt);
 }
 
+// ---- basefc, 1-mismatch UMI collapsing (umi_collapse.h): workspace 1; it ends with the radix-sort fold's COO block, counted in place ----
+constexpr size_t WS_UC_SMALL = 64;        // a group of more keys than this is listed for k_uc_big (UC_SMALL)
+constexpr size_t WS_UC_ROWS = 5;          // rows of per-tile words of k_uc_small (UCW_ROWS)
+struct UmiCollapseWs {
+    void *a, *b, *tmp;                                 // n packed keys: the sort's input, later the distinct keys D; the sorted keys, later one parent word per key of D; the sort's scratch
+    uint8_t* root;                                     // per key of D: 1 = the root of its component
+    unsigned long long* big_start; uint32_t* big_size; // per group of more than WS_UC_SMALL keys (at most big_cap): its first key in D, its keys
+    uint32_t* big_words; unsigned long long* big_off;  // ... three rows of big_cap: [changed | keys if medium | keys if giant] and their scans
+    size_t big_cap;
+    uint32_t* d_blk; unsigned long long* d_off;        // per tile of WS_TILE keys, WS_UC_ROWS rows of nt: the counters of k_uc_small, later the roots, later the fold's run heads; their scans
+    size_t coo_at;                                     // [row | col | val] of at most n non-zeros
+};
+inline void umi_collapse_carve(Arena& ar, size_t n, size_t key_bytes, size_t tmp_bytes, UmiCollapseWs& w) {
+    const size_t nt = (n + WS_TILE - 1) / WS_TILE;
+    w.big_cap = n / (WS_UC_SMALL + 1) + 1;
+    w.a = ar.get<char>(n * key_bytes); w.b = ar.get<char>(n * key_bytes); w.tmp = ar.get<char>(tmp_bytes);
+    w.root = ar.get<uint8_t>(n);
+    w.big_start = ar.get<unsigned long long>(w.big_cap); w.big_size = ar.get<uint32_t>(w.big_cap);
+    w.big_words = ar.get<uint32_t>(3 * w.big_cap); w.big_off = ar.get<unsigned long long>(3 * w.big_cap);
+    w.d_blk = ar.get<uint32_t>(WS_UC_ROWS * nt); w.d_off = ar.get<unsigned long long>(WS_UC_ROWS * nt);
+    w.coo_at = ar.off; ar.get<int32_t>(n * 3);
+}
+
 // ---- pileup, the molecule stage: workspace 1 -----------------------------------------------------------------------------------------
 struct MoleculeWs {
     void* alt; uint64_t* valt; void* tmp;              // n keys and values: the sorted hits, or the radix sort's input; the radix sort's scratch

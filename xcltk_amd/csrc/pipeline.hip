@@ -479,6 +479,7 @@ int engine_reset(EngineImpl* im) {
     rc = summaries_reset(im); if (rc) return rc;
     rc = molecule_stats_reset(im); if (rc) return rc;
     rc = unique_feature_reset(im); if (rc) return rc;
+    rc = umi_collapse_reset(im); if (rc) return rc;
     im->n_not_joined = 0;
     HIP_TRY(hipStreamSynchronize(im->s_comp));
     im->cursor = 0; im->ncursor = 0; im->finished = false; im->fold_failed = false; im->mol_valid = false; im->sc_valid = false;
@@ -558,6 +559,7 @@ int engine_create(const xck_config* cfg, xck_engine* e, EngineImpl** out) {
     rc = ensure_hits(im, (size_t)e->knobs.hit_cap0); if (rc) return rc;   // (XCK_HIT_CAP0: test knob)
     if ((cfg->flags & XCK_F_UMI_CONSENSUS) && im->mode == XCK_MODE_BAF) { rc = molecule_stats_init(im); if (rc) return rc; }
     if ((cfg->flags & XCK_F_UNIQUE_FEATURE) && im->mode == XCK_MODE_BASEFC) { rc = unique_feature_init(im, cfg); if (rc) return rc; }
+    im->umi_collapse = (cfg->flags & XCK_F_UMI_COLLAPSE) && im->mode == XCK_MODE_BASEFC;
     return summaries_init(im, cfg->flags);
 }
 

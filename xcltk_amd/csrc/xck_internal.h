@@ -124,6 +124,7 @@ struct Knobs {
     bool feature_summary = false;        // XCK_FEATURE_SUMMARY=1: XCK_F_FEATURE_SUMMARY ORed into the flags of every handle that drives a GPU
     bool umi_consensus = false;          // XCK_UMI_CONSENSUS=1: XCK_F_UMI_CONSENSUS ORed into the flags of every handle with a BAF pipeline that drives a GPU
     int  umi_feature = 0; std::string umi_feature_text;   // XCK_UMI_FEATURE=unique: XCK_F_UNIQUE_FEATURE ORed into the flags of every handle with a basefc pipeline that drives a GPU; -1 = a value that is neither `unique` nor `all` nor empty (xck_create fails and quotes the text)
+    int  umi_dedup = 0; std::string umi_dedup_text;   // XCK_UMI_DEDUP=1mm_all: XCK_F_UMI_COLLAPSE ORed into the flags of every handle with a basefc pipeline that drives a GPU; -1 = a value that is neither `1mm_all` nor `exact` nor empty (xck_create fails and quotes the text)
     int  min_baseq = 0; std::string min_baseq_text;   // XCK_MIN_BASEQ=<0 .. 93>: xck_config.min_baseq of every handle with a BAF pipeline that drives a GPU and sets none; -1 = malformed (xck_create fails and quotes the text)
     int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
     bool gpu_parse = true;               // XCK_GPU_PARSE=auto|0: walk and parse the GPU-inflated chunks on the device where that applies (bam.cpp device_parse_now)
@@ -180,6 +181,7 @@ struct xck_engine {
     bool feature_summary = false;        // made with XCK_F_FEATURE_SUMMARY (or XCK_FEATURE_SUMMARY=1)
     bool umi_consensus = false;          // made with XCK_F_UMI_CONSENSUS (or XCK_UMI_CONSENSUS=1) and a BAF pipeline: its molecule stage votes (umi_consensus.h)
     bool unique_feature = false;         // made with XCK_F_UNIQUE_FEATURE (or XCK_UMI_FEATURE=unique) and a basefc pipeline: its fold counts unique-feature molecules only (umi_feature.h)
+    bool umi_collapse = false;           // made with XCK_F_UMI_COLLAPSE (or XCK_UMI_DEDUP=1mm_all) and a basefc pipeline: its fold counts the components of the 1-mismatch graph (umi_collapse.h)
     int  min_baseq = 0;                  // base-quality floor of the pileup pipeline's join (xck_config.min_baseq or XCK_MIN_BASEQ), 0 = off
     int umi_bits = 64;
     int32_t n_cells = 0, n_contigs = 0;  // bounds that caller-supplied batches are checked against (xck_push_batch)
@@ -209,6 +211,7 @@ int  engine_cell_summary(EngineImpl* im, xck_cell_summary* out);   // cell_summa
 int  engine_feature_summary(EngineImpl* im, xck_feature_summary* out);   // feature_summary.h
 int  engine_molecule_stats(EngineImpl* im, xck_molecule_stats* out);   // umi_consensus.h (finish.hip)
 int  engine_umi_feature_stats(EngineImpl* im, xck_umi_feature_stats* out);   // umi_feature.h (finish.hip)
+int  engine_umi_dedup_stats(EngineImpl* im, xck_umi_dedup_stats* out);   // umi_collapse.h (finish.hip)
 int  engine_device(const xck_engine* e);      // HIP device of the handle (-1: decode-only handle)
 int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (sysfs, by PCI bus id); -1 = unknown
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE

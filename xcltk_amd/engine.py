@@ -94,7 +94,7 @@ class Engine(object):
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
                  incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1,
                  min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None,
-                 umi_consensus=False, min_baseq=0, umi_feature=None):
+                 umi_consensus=False, min_baseq=0, umi_feature=None, umi_dedup=None):
         """regions: iterable of (chrom, start1, end1_incl[, name]); snps: iterable of
         (chrom, pos1, ref, alt, ref_hap, alt_hap); chrom names must already be stripped of
         'chr' and present in contig_names.  excl_pairs = (region indices, snp indices): pairs left out of the SNP -> region
@@ -112,7 +112,11 @@ class Engine(object):
         umi_feature="unique" (XCK_F_UNIQUE_FEATURE; needs a basefc pipeline): a molecule (contig, cell, UMI) counts only when exactly
         one region of its contig accepted its reads - one that two or more regions hold is dropped from all of them - and
         umi_feature_stats() says how many were; None and "all" count every (region, cell, UMI), the default;
-        XCK_UMI_FEATURE=unique in the environment does the same for every handle with a basefc pipeline."""
+        XCK_UMI_FEATURE=unique in the environment does the same for every handle with a basefc pipeline.
+        umi_dedup="1mm_all" (XCK_F_UMI_COLLAPSE; needs a basefc pipeline): within one (region, cell) UMIs joined by chains of single-base
+        substitutions count as one molecule (STARsolo's 1MM_All, UMI-tools' cluster), and umi_dedup_stats() says what was merged; with
+        umi_feature="unique" that rule runs first, on exact UMIs; None and "exact" count every distinct UMI, the default;
+        XCK_UMI_DEDUP=1mm_all in the environment does the same for every handle with a basefc pipeline."""
         self.lib = capi.load()
         self.mode = mode
         self.contig_names = list(contig_names)
@@ -186,8 +190,10 @@ class Engine(object):
             self.min_baseq = int(knob) if knob.isdigit() else 0
         if umi_feature not in (None, "all", "unique"):
             raise ValueError("umi_feature must be None, 'all' or 'unique'")
+        if umi_dedup not in (None, "exact", "1mm_all"):
+            raise ValueError("umi_dedup must be None, 'exact' or '1mm_all'")
         cfg.flags = (int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0) | (capi.XCK_F_UMI_CONSENSUS if umi_consensus else 0)
-                     | (capi.XCK_F_UNIQUE_FEATURE if umi_feature == "unique" else 0))
+                     | (capi.XCK_F_UNIQUE_FEATURE if umi_feature == "unique" else 0) | (capi.XCK_F_UMI_COLLAPSE if umi_dedup == "1mm_all" else 0))
         cfg.min_baseq = int(min_baseq)                              # (behind the flags: a non-zero value sets XCK_F_MIN_BASEQ beside it)
         self.cfg = cfg
         self.n_cells = int(n_cells)
@@ -654,6 +660,19 @@ class Engine(object):
             return None
         self._check(rc, "xck_get_umi_feature_stats")
         return {k: int(getattr(out, k)) for k in capi.UMI_FEATURE_FIELDS}
+
+    def umi_dedup_stats(self):
+        """What the 1-mismatch UMI collapsing of the last finish() saw (xck_get_umi_dedup_stats): dict of keys, molecules, groups,
+        groups_changed, opaque_keys, max_group in the struct's order (molecules = the sum of the count matrix, groups = its non-zeros),
+        or None where the handle has nothing to say - made without umi_dedup="1mm_all" / XCK_F_UMI_COLLAPSE (and without
+        XCK_UMI_DEDUP=1mm_all in the environment), before finish() or after reset()."""
+        out = capi.UmiDedupStats()
+        out.struct_size = C.sizeof(capi.UmiDedupStats)
+        rc = self.lib.xck_get_umi_dedup_stats(self.h, C.byref(out))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_umi_dedup_stats")
+        return {k: int(getattr(out, k)) for k in capi.UMI_DEDUP_FIELDS}
 
 
 class BamStream(object):

@@ -638,16 +638,48 @@ def write_umi_feature_summary(eng, dist, path, log_prefix="[engine]"):
                                   (log_prefix, as_dict(a)["multi_feature"], as_dict(a)["molecules"])))
 
 
+def umi_dedup_summary_text(stats, n_ranks=1, cut_contigs=0):
+    """Text of umi_dedup_summary.tsv: one `name\\tcount` line per counter of xck_umi_dedup_stats, in the struct's order; runs of
+    several ranks start with `#ranks=N cut_contigs=K`."""
+    from .capi import UMI_DEDUP_FIELDS
+    head = "#ranks=%d cut_contigs=%d\n" % (n_ranks, cut_contigs) if n_ranks > 1 else ""
+    return head + "".join("%s\t%d\n" % (k, int(stats[k])) for k in UMI_DEDUP_FIELDS)
+
+
+def write_umi_dedup_summary(eng, dist, path, log_prefix="[engine]"):
+    """What the 1-mismatch UMI collapsing of the basefc fold merged (Engine.umi_dedup_stats, after finish()) -> `path`, when the handle
+    collapses (XCK_UMI_DEDUP=1mm_all in the environment, or XCK_F_UMI_COLLAPSE): nothing happens otherwise.  Multi-GPU: a collective
+    call - the ranks own disjoint rows of the region table, a (row, cell) group never spans two of them, so the counters are summed
+    over the ranks (max_group: the largest - every rank's value travels in a slot of its own through the same all-reduce) and the
+    writer rank writes the file; the result is the one-GPU run's.  Returns the dict or None."""
+    from .capi import UMI_DEDUP_FIELDS
+    umi_dedup_stats = getattr(eng, "umi_dedup_stats", None)       # (an engine-like object without the method merges nothing)
+    st = umi_dedup_stats() if umi_dedup_stats else None
+    if st is None:
+        return None
+    n_ranks, rank = (dist.world, dist.rank) if dist is not None and dist.active else (1, 0)
+    slots = [0] * n_ranks
+    slots[rank] = st["max_group"]
+    def as_dict(a):
+        d = dict(zip(UMI_DEDUP_FIELDS, a[0].tolist()))
+        d["max_group"] = int(max(a[1].tolist()))
+        return d
+    return as_dict(_write_summary(dist, path, [[st[k] for k in UMI_DEDUP_FIELDS], slots], lambda a, n_ranks, cut: umi_dedup_summary_text(as_dict(a), n_ranks, cut),
+                                  lambda a: "%s UMI collapsing (1mm_all): %d of %d keys merged away, %d of %d groups changed" %
+                                  (log_prefix, as_dict(a)["keys"] - as_dict(a)["molecules"], as_dict(a)["keys"], as_dict(a)["groups_changed"], as_dict(a)["groups"])))
+
+
 def write_summaries(eng, dist, prefix, samples, regions, snps=None, mode=None, log_prefix="[engine]"):
     """The opt-in tables of one pipeline next to its matrices: `prefix` + read_summary.tsv (XCK_READ_FATE=1), cell_summary.tsv
     (XCK_CELL_SUMMARY=1), feature_summary.tsv (XCK_FEATURE_SUMMARY=1), - `snps` given, the pileup pipeline - snp_summary.tsv and - the
     pileup pipeline under XCK_UMI_CONSENSUS=1 - molecule_summary.tsv and - the basefc pipeline under XCK_UMI_FEATURE=unique -
-    umi_feature_summary.tsv, each only when the handle keeps it.  `prefix` is a path
+    umi_feature_summary.tsv and - the basefc pipeline under XCK_UMI_DEDUP=1mm_all - umi_dedup_summary.tsv, each only when the handle keeps it.  `prefix` is a path
     prefix: a directory with its separator, or e.g. <dir>/xcltk. ; mode names the pipeline of a XCK_MODE_BOTH handle.  Multi-GPU: the
     writers' collective calls, in this order on every rank."""
     from .capi import XCK_MODE_BAF
     if getattr(eng, "mode", 0) & XCK_MODE_BASEFC and (mode is None or mode & XCK_MODE_BASEFC):
         write_umi_feature_summary(eng, dist, prefix + "umi_feature_summary.tsv", log_prefix)
+        write_umi_dedup_summary(eng, dist, prefix + "umi_dedup_summary.tsv", log_prefix)
     write_read_summary(eng, dist, prefix + "read_summary.tsv", mode, log_prefix)
     write_cell_summary(eng, dist, prefix + "cell_summary.tsv", samples, mode, log_prefix)
     write_feature_summary(eng, dist, prefix + "feature_summary.tsv", regions, mode, log_prefix)
