@@ -310,6 +310,19 @@ typedef struct xck_config {
                                    and xck_group_counts follow.  xck_get_umi_dedup_stats counts what was merged.  Any handle with a
                                    basefc pipeline; on XCK_MODE_BOTH the BAF half is untouched.  XCK_E_ARG on a BAF-only handle and
                                    together with XCK_F_DECODE_ONLY                                                              */
+#define XCK_F_BASE_TALLY 0x1000 /* (= 4096) pileup: pseudo-bulk base tallies.  Per contig that received reads the handle keeps four 32-bit counters
+                                   A, C, G, T per reference position (16 bytes per position: about 50 GB for every contig of a human
+                                   genome; a contig's table is allocated and zeroed when its first batch is queued).  Every read that
+                                   passes the read filter (mapq, flags, orphan, cell >= 0, UMI != XCK_UMI_NONE, min_len; regions and
+                                   SNPs are not asked) adds, for every base of an M, = or X operation, one to the counter of the
+                                   4-bit code 1, 2, 4 or 8 at that reference position; any other code (N, IUPAC, the pad nibble, a
+                                   read without stored sequence) counts as bases_other, a base under the handle's base-quality floor
+                                   as bases_masked, a base at or beyond the contig's length as bases_out_of_range.  Reads are
+                                   counted, not molecules.  Needs xck_set_contig_lengths before the first push; with the flag a batch
+                                   on a contig without SNPs is queued like any other.  xck_get_base_tally, xck_get_base_tally_stats
+                                   and xck_find_candidates read the tables.  Any handle with a BAF pipeline; on XCK_MODE_BOTH the
+                                   basefc half is untouched.  XCK_E_ARG on a basefc-only handle and together with XCK_F_DECODE_ONLY.
+                                   No environment knob                                                                          */
 #define XCK_F_DECODE_ONLY    4  /* handle drives the BAM decoder only: no GPU is touched, and
                                    xck_push_batch / xck_finish fail (used to run the host
                                    ingest on machines without a device; NOT a compute path)  */
@@ -525,6 +538,38 @@ typedef struct xck_baseq_stats {
     int64_t  pairs_masked;
 } xck_baseq_stats;
 
+/* The counters of the base tally pass since the last reset (handles made with XCK_F_BASE_TALLY; additive, ABI 3 is unchanged).
+ * struct_size = sizeof(xck_base_tally_stats), as for xck_decode_stats. */
+typedef struct xck_base_tally_stats {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t  reads_tallied;     /* reads that passed the read filter                                              */
+    int64_t  bases_tallied;     /* aligned bases that added to A, C, G or T                                       */
+    int64_t  bases_other;       /* aligned bases whose 4-bit code is not 1, 2, 4, 8 (or that have no stored code) */
+    int64_t  bases_masked;      /* aligned bases under the handle's base-quality floor                            */
+    int64_t  bases_out_of_range;/* aligned bases at or beyond the contig's length                                 */
+} xck_base_tally_stats;
+
+/* xck_find_candidates: thresholds, and the candidate positions it returns.  For a position with counts c[4] (A, C, G, T) and n their sum,
+ * ref is the base with the largest count (the earliest of equals in A, C, G, T), alt the largest of the other three (same tie rule) with
+ * count m; the position is a candidate when m > 0, !((double)n < min_count) and !((double)m < (double)n * min_maf) - the arithmetic of
+ * the SNP filter of xck_finish with the alt count as the minor count. */
+typedef struct xck_candidate_config {
+    uint32_t struct_size;       /* sizeof(xck_candidate_config)                              */
+    uint32_t reserved;
+    double   min_count;
+    double   min_maf;
+} xck_candidate_config;
+typedef struct xck_candidates {
+    int64_t  n;                 /* candidates, in (contig, pos) order                        */
+    const int32_t*  contig;     /* [n] engine contig id                                      */
+    const int32_t*  pos;        /* [n] 1-based                                               */
+    const char*     ref;        /* [n] ASCII                                                 */
+    const char*     alt;        /* [n]                                                       */
+    const uint32_t* count;      /* [n * 4] A C G T                                           */
+    int64_t  positions_covered; /* positions of the allocated tables with n > 0              */
+} xck_candidates;
+
 typedef struct xck_engine xck_engine;     /* opaque: one per GPU */
 typedef struct xck_bam    xck_bam;        /* opaque: one open BAM file */
 
@@ -716,6 +761,21 @@ int  xck_get_umi_dedup_stats(xck_engine* e, xck_umi_dedup_stats* out);
  * does; xck_reset clears them, xck_finish and the derived calls do not change them.  A tile the join replays after an overflow counts
  * once.  XCK_E_STATE on a handle without a floor (and on a decode-only handle), XCK_E_ARG for a null pointer or a short struct_size. */
 int  xck_get_baseq_stats(xck_engine* e, xck_baseq_stats* out);
+
+/* -- pseudo-bulk base tallies (XCK_F_BASE_TALLY) -- */
+/* The contigs' lengths, which bound the tables: n must equal the handle's n_contigs and every length lie in 1 .. 2^31 - 1 (XCK_E_ARG).
+ * XCK_E_STATE on a handle without the flag and after the first push since xck_create / xck_reset; a push or an ingest on a tally handle
+ * without lengths is XCK_E_STATE.  xck_reset keeps the lengths and zeroes the tables. */
+int  xck_set_contig_lengths(xck_engine* e, const int64_t* len, int32_t n);
+/* Copies the n * 4 counters (A C G T per position) of positions [pos0, pos0 + n) of a contig to out, after waiting for the queued work as
+ * xck_flush does.  A contig no read touched reads as zeros.  XCK_E_ARG for a range outside the contig, XCK_E_STATE without the flag. */
+int  xck_get_base_tally(xck_engine* e, int32_t contig, int32_t pos0, int32_t n, uint32_t* out);
+/* The pass's counters since the last reset (set out->struct_size first); waits as xck_flush does.  XCK_E_STATE without the flag. */
+int  xck_get_base_tally_stats(xck_engine* e, xck_base_tally_stats* out);
+/* The candidate positions of every allocated table under cfg's thresholds: a count pass, a scan and an emit pass on the device.  Valid
+ * between a successful xck_finish and the next xck_reset (XCK_E_STATE otherwise, and without the flag); may be called repeatedly with
+ * other thresholds.  The arrays belong to the handle and are valid until the next xck_find_candidates / xck_reset / xck_destroy. */
+int  xck_find_candidates(xck_engine* e, const xck_candidate_config* cfg, xck_candidates* out);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

@@ -41,6 +41,10 @@ int  engine_group_counts(EngineImpl*, int, int, const int32_t*, xck_result*, Gro
 int  engine_molecule_stats(EngineImpl*, xck_molecule_stats*) { return XCK_E_ARG; }
 int  engine_umi_feature_stats(EngineImpl*, xck_umi_feature_stats*) { return XCK_E_ARG; }
 int  engine_umi_dedup_stats(EngineImpl*, xck_umi_dedup_stats*) { return XCK_E_ARG; }
+int  base_tally_set_lengths(EngineImpl*, const int64_t*, int32_t) { return XCK_E_ARG; }
+int  engine_base_tally(EngineImpl*, int32_t, int32_t, int32_t, uint32_t*) { return XCK_E_ARG; }
+int  engine_base_tally_stats(EngineImpl*, xck_base_tally_stats*) { return XCK_E_ARG; }
+int  engine_find_candidates(EngineImpl*, const xck_candidate_config*, xck_candidates*) { return XCK_E_ARG; }
 // ---- csrc/local_phase.hip ----
 int  local_phase_run(const xck_phase_problem*, const PhasePlan&, double, xck_phase_result**) { return XCK_E_DEVICE; }
 void local_phase_free(xck_phase_result*) {}

@@ -27,6 +27,7 @@ XCK_F_UMI_CONSENSUS = 256
 XCK_F_MIN_BASEQ = 512
 XCK_F_UNIQUE_FEATURE = 1024
 XCK_F_UMI_COLLAPSE = 2048
+XCK_F_BASE_TALLY = 4096
 XCK_E_ARG, XCK_E_DEVICE, XCK_E_NOMEM, XCK_E_IO, XCK_E_STATE, XCK_E_CAPACITY = -1, -2, -3, -4, -5, -6
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -214,6 +215,24 @@ class UmiDedupStats(C.Structure):
 UMI_DEDUP_FIELDS = tuple(k for k, _ in UmiDedupStats._fields_[2:])
 
 
+class BaseTallyStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_int64) for k in (
+        "reads_tallied", "bases_tallied", "bases_other", "bases_masked", "bases_out_of_range")]
+
+
+# the counters of xck_base_tally_stats in the struct's order
+BASE_TALLY_FIELDS = tuple(k for k, _ in BaseTallyStats._fields_[2:])
+
+
+class CandidateConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("min_count", C.c_double), ("min_maf", C.c_double)]
+
+
+class Candidates(C.Structure):
+    _fields_ = [("n", C.c_int64), ("contig", C.POINTER(C.c_int32)), ("pos", C.POINTER(C.c_int32)), ("ref", C.POINTER(C.c_char)),
+                ("alt", C.POINTER(C.c_char)), ("count", C.POINTER(C.c_uint32)), ("positions_covered", C.c_int64)]
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -275,6 +294,10 @@ SYMBOLS = [
     ("xck_get_baseq_stats", C.c_int, [C.c_void_p, _P(BaseqStats)]),
     ("xck_get_umi_feature_stats", C.c_int, [C.c_void_p, _P(UmiFeatureStats)]),
     ("xck_get_umi_dedup_stats", C.c_int, [C.c_void_p, _P(UmiDedupStats)]),
+    ("xck_set_contig_lengths", C.c_int, [C.c_void_p, _P(C.c_int64), C.c_int32]),
+    ("xck_get_base_tally", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint32)]),
+    ("xck_get_base_tally_stats", C.c_int, [C.c_void_p, _P(BaseTallyStats)]),
+    ("xck_find_candidates", C.c_int, [C.c_void_p, _P(CandidateConfig), _P(Candidates)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

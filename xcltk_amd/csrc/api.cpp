@@ -143,6 +143,10 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
         if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("XCK_F_UMI_COLLAPSE needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
         if (!(cfg->mode & XCK_MODE_BASEFC)) { set_thread_error("XCK_F_UMI_COLLAPSE: the handle has no basefc pipeline"); return XCK_E_ARG; }
     }
+    if (cfg->flags & XCK_F_BASE_TALLY) {
+        if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("XCK_F_BASE_TALLY needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
+        if (!(cfg->mode & XCK_MODE_BAF)) { set_thread_error("XCK_F_BASE_TALLY: the handle has no BAF pipeline"); return XCK_E_ARG; }
+    }
     if (cfg->min_baseq) {
         if (cfg->min_baseq < 0 || cfg->min_baseq > 93) { set_thread_error("xck_config.min_baseq outside 0 .. 93"); return XCK_E_ARG; }
         if (cfg->flags & XCK_F_DECODE_ONLY) { set_thread_error("xck_config.min_baseq needs a GPU engine: not with XCK_F_DECODE_ONLY"); return XCK_E_ARG; }
@@ -176,6 +180,7 @@ int xck_create(const xck_config* cfg_in, xck_engine** out) {
     e->unique_feature = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BASEFC) && ((cfg->flags & XCK_F_UNIQUE_FEATURE) || e->knobs.umi_feature > 0);   // (the knob: ignored by the other handles)
     e->umi_collapse = !(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BASEFC) && ((cfg->flags & XCK_F_UMI_COLLAPSE) || e->knobs.umi_dedup > 0);   // (the knob: ignored by the other handles)
     e->min_baseq = cfg->min_baseq ? cfg->min_baseq : (!(cfg->flags & XCK_F_DECODE_ONLY) && (cfg->mode & XCK_MODE_BAF)) ? e->knobs.min_baseq : 0;   // (the knob: ignored by the other handles)
+    e->base_tally = (cfg->flags & XCK_F_BASE_TALLY) != 0;              // (checked above: a BAF pipeline, a GPU engine; no knob)
     e->umi_bits = key_layout(cfg).ubits;
     e->mode = cfg->mode;
     e->n_cells = cfg->n_cells; e->n_contigs = cfg->n_contigs;
@@ -267,6 +272,11 @@ static int check_host_batch(xck_engine* e, const xck_batch* b) {
     return XCK_OK;
 }
 extern "C++" { namespace xck { int push_trusted(xck_engine* e, const xck_batch* b, const uint8_t* qual) { return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, false, qual); }); } } }
+// what a push answers on a handle that keeps base tallies and has not been told its contigs' lengths
+static int needs_lengths(xck_engine* e, const char* who) {
+    e->err = std::string(who) + ": the handle keeps base tallies (XCK_F_BASE_TALLY) and has no contig lengths; call xck_set_contig_lengths first";
+    return XCK_E_STATE;
+}
 // what the calls that carry no qualities answer on a handle whose pileup needs them
 static int needs_qualities(xck_engine* e, const char* who) {
     e->err = std::string(who) + ": the handle has a base-quality floor (xck_config.min_baseq / XCK_MIN_BASEQ = " + std::to_string(e->min_baseq) + ") and this call carries no qualities; use xck_push_batch_q or xck_ingest_bam";
@@ -344,11 +354,13 @@ static int push_host_batch(xck_engine* e, const xck_batch* b, const uint8_t* qua
 }
 int xck_push_batch(xck_engine* e, const xck_batch* b) {
     if (!e || !b) return XCK_E_ARG;
+    if (e->base_tally && !e->contig_len_set) return needs_lengths(e, "xck_push_batch");
     if (e->min_baseq > 0) return needs_qualities(e, "xck_push_batch");
     return push_host_batch(e, b, nullptr);
 }
 int xck_push_batch_q(xck_engine* e, const xck_batch* b, const uint8_t* qual) {
     if (!e || !b) return XCK_E_ARG;
+    if (e->base_tally && !e->contig_len_set) return needs_lengths(e, "xck_push_batch_q");
     if (e->min_baseq <= 0) return push_host_batch(e, b, nullptr);        // no floor: qual is ignored
     if (!qual) {                                                         // (only a batch without sequence bytes needs none: a byte that is never read stands in)
         static const uint8_t none = 0xff;
@@ -360,6 +372,7 @@ int xck_push_batch_q(xck_engine* e, const xck_batch* b, const uint8_t* qual) {
 }
 int xck_push_batch_device(xck_engine* e, const xck_batch* b) {
     if (!e || !b) return XCK_E_ARG;
+    if (e->base_tally && !e->contig_len_set) return needs_lengths(e, "xck_push_batch_device");
     if (e->min_baseq > 0) return needs_qualities(e, "xck_push_batch_device");
     return for_pipelines(e, [&](EngineImpl* im) { return engine_push(im, b, true); });
 }
@@ -442,6 +455,44 @@ int xck_get_baseq_stats(xck_engine* e, xck_baseq_stats* out) {
     const uint32_t sz = out->struct_size;
     memset(out, 0, sizeof *out); out->struct_size = sz;
     return engine_baseq_stats(e->impls[e->n_impl - 1], out);            // (a fused handle answers from its pileup pipeline)
+}
+
+// ---- pseudo-bulk base tallies (XCK_F_BASE_TALLY, base_tally.h): the handle's pileup pipeline keeps them ----
+static EngineImpl* tally_pipeline(xck_engine* e) {
+    if (!e->base_tally || e->n_impl <= 0) { e->err = "handle made without XCK_F_BASE_TALLY"; return nullptr; }
+    return e->impls[e->n_impl - 1];                                      // (a fused handle answers from its pileup pipeline)
+}
+int xck_set_contig_lengths(xck_engine* e, const int64_t* len, int32_t n) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    if (!im) return XCK_E_STATE;
+    // (the handle's first pipeline sees every push the pileup pipeline sees: "after the first push" is asked of the tally's own)
+    if (int rc = base_tally_set_lengths(im, len, n)) return rc;
+    e->contig_len_set = true;
+    return XCK_OK;
+}
+int xck_get_base_tally(xck_engine* e, int32_t contig, int32_t pos0, int32_t n, uint32_t* out) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    return im ? engine_base_tally(im, contig, pos0, n, out) : XCK_E_STATE;
+}
+int xck_get_base_tally_stats(xck_engine* e, xck_base_tally_stats* out) {
+    if (!e || !out) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (out->struct_size < sizeof(xck_base_tally_stats)) { e->err = "xck_base_tally_stats.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    if (!im) return XCK_E_STATE;
+    const uint32_t sz = out->struct_size;
+    memset(out, 0, sizeof *out); out->struct_size = sz;
+    return engine_base_tally_stats(im, out);
+}
+int xck_find_candidates(xck_engine* e, const xck_candidate_config* cfg, xck_candidates* out) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (!cfg || !out) { e->err = "xck_find_candidates: null argument"; return XCK_E_ARG; }
+    if (cfg->struct_size < sizeof(xck_candidate_config)) { e->err = "xck_candidate_config.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    if (!im) return XCK_E_STATE;
+    memset(out, 0, sizeof *out);
+    return engine_find_candidates(im, cfg, out);
 }
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }

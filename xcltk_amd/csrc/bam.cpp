@@ -986,6 +986,7 @@ static int drain_ingest(xck_bam* b, int rc) {
 
 static int ingest_impl(xck_engine* e, xck_bam* b, const xck_ingest_opts* o, int64_t* n_records) {
     if (!e || !b || !o) return XCK_E_ARG;
+    if (e->base_tally && !e->contig_len_set) { e->err = "xck_ingest_bam: the handle keeps base tallies (XCK_F_BASE_TALLY) and has no contig lengths; call xck_set_contig_lengths first"; return XCK_E_STATE; }
     CallerBinding on_node(b);
     FoldDecodeStats fold{e, b};
     const int64_t pause = o->struct_size >= offsetof(xck_ingest_opts, pause_records) + sizeof(int64_t) ? o->pause_records : 0;

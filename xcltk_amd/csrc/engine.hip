@@ -1,5 +1,5 @@
 // engine.hip - MI355X (gfx950) counting engine: the join.  k_tile_meta, k_join and every device helper they use, the device tables
-// the join reads (build_tables) and its launch (launch_join), and behind it the three opt-in summary passes, whose kernels use the
+// the join reads (build_tables) and its launch (launch_join), and behind it the opt-in summary passes and the base tally pass, whose kernels use the
 // join's own CIGAR loops and tile size.  Nothing else lives here, for one reason: this is the file the traffic stamp covers
 // (profiles/pmc_traffic.json: bench.py reports roofline.traffic only while engine.hip + fold_partition.h hash to the stamp), so an
 // edit here says "the join's bytes have to be counted again" and a feature's host code must not say that.  The per-GPU push
@@ -1031,24 +1031,28 @@ int launch_join(EngineImpl* im) { return im->key_bits == 64 ? launch_join_t<uint
 #include "cell_summary.h"
 #include "read_fate.h"
 #include "feature_summary.h"
+#include "base_tally.h"
 
-// What the pipeline (pipeline.hip) knows of the three summaries: their memory at create, their zeroing at reset (on s_comp, in front
+// What the pipeline (pipeline.hip) knows of the summaries and the base tally: their memory at create, their zeroing at reset (on s_comp, in front
 // of the reset's synchronise), and their passes behind the FIRST join launch of a queue (each returns at once when its flag is off).
 int summaries_init(EngineImpl* im, uint32_t flags) {
     if (flags & XCK_F_READ_FATE) { if (const int rc = read_fate_init(im)) return rc; }
     if (flags & XCK_F_CELL_SUMMARY) { if (const int rc = cell_summary_init(im)) return rc; }
     if (flags & XCK_F_FEATURE_SUMMARY) { if (const int rc = feature_summary_init(im)) return rc; }
+    if ((flags & XCK_F_BASE_TALLY) && im->mode == XCK_MODE_BAF) { if (const int rc = base_tally_init(im)) return rc; }
     return 0;
 }
 int summaries_reset(EngineImpl* im) {
     if (im->d_fate) { if (const int rc = read_fate_reset(im)) return rc; }
     if (const int rc = cell_summary_reset(im)) return rc;
     if (im->d_feat) { if (const int rc = feature_summary_reset(im)) return rc; }
+    if (im->base_tally) { if (const int rc = base_tally_reset(im)) return rc; }
     return 0;
 }
 int launch_summaries(EngineImpl* im) {
     if (const int rc = launch_read_fate(im)) return rc;
-    return launch_feature_fate(im);
+    if (const int rc = launch_feature_fate(im)) return rc;
+    return launch_base_tally(im);
 }
 
 // XCK_STAMPS builds: the stamp records of the join launch that has just been waited for (ms: its time), summed per slot

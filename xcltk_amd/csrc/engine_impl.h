@@ -64,6 +64,7 @@ struct BatchDesc {
     int32_t reg_lo, reg_hi;                                 // regions of the batch's contig: [reg_lo, reg_hi) of the start-sorted arrays
     const int32_t* snp_win; int32_t n_swin; int32_t snp_end; // SNP window table of the batch's contig
     const uint8_t* qual;                                    // pileup with a base-quality floor: quality of query offset qi of the read at seq offset s0 = qual[2 * s0 + qi] (else null)
+    int32_t contig, pad_;                                   // the batch's contig (the base tally finds its table by it; the join does not read it)
 };
 
 constexpr int MAX_FUSE = 24;              // batches per fused launch (the table travels in the kernel arguments)
@@ -231,6 +232,15 @@ struct EngineImpl {
     // 1-mismatch UMI collapsing (XCK_F_UMI_COLLAPSE, umi_collapse.h; false = off: the fold counts every key): the six counters of the last
     // xck_finish, valid from a successful finish to the next reset
     bool umi_collapse = false; long long uc_stats[6] = {0, 0, 0, 0, 0, 0}; bool uc_stats_valid = false;
+    // base tallies (XCK_F_BASE_TALLY, base_tally.h; false = off): the contigs' lengths (empty until xck_set_contig_lengths), per contig its
+    // table [len * 4] in HBM (null until the contig's first batch is queued), the pass's counters in BT_SLOTS copies, and what
+    // xck_find_candidates needs: per-block counts, the scan's two totals, one contig's output on the device, the host arrays it hands out
+    bool base_tally = false;
+    std::vector<int64_t> bt_len; std::vector<uint32_t*> bt_tab;
+    unsigned long long* d_bt_stats = nullptr; unsigned long long* d_bt_tot = nullptr;
+    char* d_bt_blk = nullptr; size_t bt_blk_cap = 0; char* d_bt_out = nullptr; size_t bt_out_cap = 0;
+    std::vector<int32_t> h_bt_contig, h_bt_pos; std::vector<char> h_bt_ref, h_bt_alt; std::vector<uint32_t> h_bt_cnt;
+    int batch_rc = 0;                                     // describe_batch: the code of the error it reported (XCK_E_ARG unless a table could not be had)
     // xck_refold (refold.h): the caller's SNP list as given to xck_create, the regrown tables' capacities, and the builder's own buffers
     std::vector<xck_snp> snps_in;
     size_t csr_reg_cap_bytes = 0, fmat_cap_bytes = 0;     // of d_csr_reg and d_fmat, which a refold may have to regrow
@@ -313,6 +323,8 @@ void join_stamps_report(const EngineImpl* im);             // ... and prints the
 int summaries_init(EngineImpl* im, uint32_t flags);        // engine_create: the memory of the summaries the flags ask for
 int summaries_reset(EngineImpl* im);                       // engine_reset: their tables zeroed on s_comp (the caller synchronises)
 int launch_summaries(EngineImpl* im);                      // launch_queue: their passes behind the first join launch of im->inflight
+int base_tally_touch(EngineImpl* im, int32_t contig);      // describe_batch, XCK_F_BASE_TALLY: the table of a contig whose batch is about to be queued (base_tally.h)
+void base_tally_free(EngineImpl* im);                      // engine_destroy: the tables and buffers of base_tally.h
 // defined in finish.hip
 int finish_init(EngineImpl* im);                           // engine_create: per-device attributes of the fold kernels
 int snp_verdicts(EngineImpl* im, uint32_t* d_kept);        // d_kept[s] = snp_passes() of sorted SNP s on the tallies of the last finish (enqueued on s_comp)

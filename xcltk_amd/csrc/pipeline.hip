@@ -189,18 +189,21 @@ static const char* null_column(const EngineImpl* im, const xck_batch* b, Columns
 
 // What a push does with one batch, decided in one place: the batch is counted, its contig and its columns are checked, and the table
 // half of its BatchDesc is filled (the column pointers are the caller's: they are what differs between the paths).
-enum BatchFate { BATCH_ERROR = -1, BATCH_SKIP = 0, BATCH_QUEUE = 1 };    // ERROR: XCK_E_ARG, the text is in the handle; SKIP: counted, no kernel will see it
+enum BatchFate { BATCH_ERROR = -1, BATCH_SKIP = 0, BATCH_QUEUE = 1 };    // ERROR: im->batch_rc (XCK_E_ARG unless a tally table could not be had), the text is in the handle; SKIP: counted, no kernel will see it
 static BatchFate describe_batch(EngineImpl* im, const xck_batch* b, Columns cols, BatchDesc& d) {
     im->st.n_batches++; im->st.n_reads += b->n_reads;
+    im->batch_rc = XCK_E_ARG;
     if (b->n_reads <= 0 || b->contig < 0) { im->n_not_joined += std::max(b->n_reads, 0); return BATCH_SKIP; }
     if (b->contig >= (int)im->ctab.size()) { im->eng->err = "batch contig out of range"; return BATCH_ERROR; }
     const ContigTab& t = im->ctab[b->contig];
-    const bool has_targets = im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : t.n_snp > 0;
+    // (XCK_F_BASE_TALLY: the tally pass reads every batch, so a batch on a contig without SNPs is queued too - the join finds nothing in it)
+    const bool has_targets = im->mode == XCK_MODE_BASEFC ? t.n_reg > 0 : (t.n_snp > 0 || im->base_tally);
     if (cols != COLS_BLOCK || has_targets)                           // (a block's batch is asked about only if a kernel will read it)
         if (const char* what = null_column(im, b, cols)) { im->eng->err = what; return BATCH_ERROR; }
     if (!has_targets) { im->n_not_joined += b->n_reads; return BATCH_SKIP; }
+    if (im->base_tally) { if (const int rc = base_tally_touch(im, b->contig)) { im->batch_rc = rc; return BATCH_ERROR; } }
     memset(&d, 0, sizeof d);
-    d.n = b->n_reads; d.ordinal_base = b->ordinal_base;
+    d.n = b->n_reads; d.ordinal_base = b->ordinal_base; d.contig = b->contig;
     d.reg_lo = t.reg_base; d.reg_hi = t.reg_base + t.n_reg;
     d.snp_win = im->d_snp_win + t.swin_base; d.n_swin = t.n_swin; d.snp_end = t.snp_base + t.n_snp;
     return BATCH_QUEUE;
@@ -215,7 +218,7 @@ int engine_push(EngineImpl* im, const xck_batch* b, bool device_resident, const 
     HIP_TRY(hipSetDevice(im->device));
     BatchDesc d;
     const BatchFate fate = describe_batch(im, b, device_resident ? COLS_DEVICE : COLS_HOST, d);
-    if (fate != BATCH_QUEUE) return fate == BATCH_SKIP ? 0 : XCK_E_ARG;
+    if (fate != BATCH_QUEUE) return fate == BATCH_SKIP ? 0 : im->batch_rc;
     if (device_resident) {
         // deferred: consecutive device-resident batches are fused into one launch (>> 256 workgroups)
         d.pos = b->pos; d.flag = b->flag; d.mapq = b->mapq; d.cell = b->cell; d.umi = b->umi;
@@ -304,7 +307,7 @@ static int push_staged(xck_engine* e, int si, const xck_batch* batches, int n, D
             const xck_batch* b = &batches[i];
             BatchDesc d;
             const BatchFate fate = describe_batch(im, b, COLS_BLOCK, d);
-            if (fate == BATCH_ERROR) return XCK_E_ARG;
+            if (fate == BATCH_ERROR) return im->batch_rc;
             if (fate == BATCH_SKIP) continue;
             d.pos = (const int32_t*)dev(b->pos); d.flag = (const uint16_t*)dev(b->flag); d.mapq = (const uint8_t*)dev(b->mapq);
             d.cell = (const int32_t*)dev(b->cell); d.umi = (const uint64_t*)dev(b->umi);
@@ -574,6 +577,7 @@ void engine_destroy(EngineImpl* im) {
     for (auto& s : im->slot) { void* q[] = { s.pos, s.flag, s.mapq, s.cell, s.umi, s.cig_off, s.cigar, s.seq_off, s.seq, s.qual }; for (void* p : q) if (p) hipFree(p); }
     for (int m = 0; m < 4; m++) if (im->h_res[m]) hipHostFree(im->h_res[m]);
     coo_call_free(im->sc); coo_call_free(im->gc);
+    base_tally_free(im);
     if (im->h_ctl) hipHostFree(im->h_ctl);
     if (im->ev0) hipEventDestroy(im->ev0);
     if (im->ev1) hipEventDestroy(im->ev1);

@@ -79,31 +79,40 @@ __device__ __forceinline__ int rf_targets(const FateArgs& a, const BatchDesc& d,
     }
 }
 
-// Class of read i of batch d; n_pairs = regions that accept it / SNPs it covers (0 unless the class is RF_ASSIGNED).  The one statement
-// of the read filter outside the join, in front of the one statement of the accept rule (rf_targets): every pass that follows the
-// join (k_read_fate*, k_feature_fate of feature_summary.h) goes through here.  sp: filled when the read passes the filter.
-template <int MODE, class OnRegion, class OnSnps>
-__device__ __forceinline__ int read_fate_walk(const FateArgs& a, const BatchDesc& d, const int32_t i, uint32_t& n_pairs, RfSpan& sp, OnRegion on_region, OnSnps on_snps) {
-    n_pairs = 0;
+// The read filter alone, the one statement of it outside the join: the class that turns read i of batch d away, or -1 when it passes -
+// then sp holds its fetch span, aligned bases and CIGAR words.  read_fate_walk asks the targets next; the base tally (base_tally.h),
+// which asks about neither regions nor SNPs, stops here.
+__device__ __forceinline__ int rf_filter(const ReadFilter& f, const BatchDesc& d, const int32_t i, RfSpan& sp) {
     const uint32_t flag = as_global(d.flag)[i];
     const int32_t mapq = as_global(d.mapq)[i];
-    if (mapq < a.f.min_mapq) return RF_LOW_MAPQ;
-    if (a.f.excl_flag && (flag & a.f.excl_flag)) return RF_EXCL_FLAG;
-    if (a.f.incl_flag && !(flag & a.f.incl_flag)) return RF_INCL_FLAG;
-    if (a.f.no_orphan && (flag & BAM_FPAIRED) && !(flag & BAM_FPROPER_PAIR)) return RF_ORPHAN;
+    if (mapq < f.min_mapq) return RF_LOW_MAPQ;
+    if (f.excl_flag && (flag & f.excl_flag)) return RF_EXCL_FLAG;
+    if (f.incl_flag && !(flag & f.incl_flag)) return RF_INCL_FLAG;
+    if (f.no_orphan && (flag & BAM_FPAIRED) && !(flag & BAM_FPROPER_PAIR)) return RF_ORPHAN;
     if (as_global(d.cell)[i] < 0) return RF_NO_CELL;
     if (as_global(d.umi)[i] == XCK_UMI_NONE) return RF_NO_UMI;
     const uint32_t c0 = as_global(d.cig_off)[i], c1 = as_global(d.cig_off)[i + 1];
     const auto word_at = [&](uint32_t c) { return as_global(d.cigar)[c]; };
     int32_t rlen = 0, n_al = 0;
     cigar_summary(word_at, c0, c1, rlen, n_al);
-    if (n_al < a.f.min_len) return RF_SHORT;
+    if (n_al < f.min_len) return RF_SHORT;
     // the fetch span, as load_read(): htslib bam_endpos() gives an unmapped-flagged read, or one without reference-consuming
     // CIGAR, one base
     const bool span_is_cigar = !((flag & BAM_FUNMAP) || c1 == c0 || rlen == 0);
     if (!span_is_cigar) rlen = 1;
     const int32_t pos = as_global(d.pos)[i], endpos = pos + rlen;
     sp.pos = pos; sp.endpos = endpos; sp.n_al = n_al; sp.c0 = c0; sp.c1 = c1; sp.span_is_cigar = span_is_cigar;
+    return -1;
+}
+
+// Class of read i of batch d; n_pairs = regions that accept it / SNPs it covers (0 unless the class is RF_ASSIGNED).  The read filter
+// (rf_filter) in front of the one statement of the accept rule (rf_targets): every pass that follows the join and asks about targets
+// (k_read_fate*, k_feature_fate of feature_summary.h) goes through here.  sp: filled when the read passes the filter.
+template <int MODE, class OnRegion, class OnSnps>
+__device__ __forceinline__ int read_fate_walk(const FateArgs& a, const BatchDesc& d, const int32_t i, uint32_t& n_pairs, RfSpan& sp, OnRegion on_region, OnSnps on_snps) {
+    n_pairs = 0;
+    const int cls = rf_filter(a.f, d, i, sp);
+    if (cls >= 0) return cls;
     return rf_targets<MODE>(a, d, sp, -1, n_pairs, on_region, on_snps);
 }
 // ... for a pass that only counts: no hooks

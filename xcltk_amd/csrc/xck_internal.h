@@ -182,6 +182,8 @@ struct xck_engine {
     bool umi_consensus = false;          // made with XCK_F_UMI_CONSENSUS (or XCK_UMI_CONSENSUS=1) and a BAF pipeline: its molecule stage votes (umi_consensus.h)
     bool unique_feature = false;         // made with XCK_F_UNIQUE_FEATURE (or XCK_UMI_FEATURE=unique) and a basefc pipeline: its fold counts unique-feature molecules only (umi_feature.h)
     bool umi_collapse = false;           // made with XCK_F_UMI_COLLAPSE (or XCK_UMI_DEDUP=1mm_all) and a basefc pipeline: its fold counts the components of the 1-mismatch graph (umi_collapse.h)
+    bool base_tally = false;             // made with XCK_F_BASE_TALLY and a BAF pipeline: its pileup pipeline keeps base tallies (base_tally.h)
+    bool contig_len_set = false;         // ... and xck_set_contig_lengths has been called
     int  min_baseq = 0;                  // base-quality floor of the pileup pipeline's join (xck_config.min_baseq or XCK_MIN_BASEQ), 0 = off
     int umi_bits = 64;
     int32_t n_cells = 0, n_contigs = 0;  // bounds that caller-supplied batches are checked against (xck_push_batch)
@@ -212,6 +214,10 @@ int  engine_feature_summary(EngineImpl* im, xck_feature_summary* out);   // feat
 int  engine_molecule_stats(EngineImpl* im, xck_molecule_stats* out);   // umi_consensus.h (finish.hip)
 int  engine_umi_feature_stats(EngineImpl* im, xck_umi_feature_stats* out);   // umi_feature.h (finish.hip)
 int  engine_umi_dedup_stats(EngineImpl* im, xck_umi_dedup_stats* out);   // umi_collapse.h (finish.hip)
+int  base_tally_set_lengths(EngineImpl* im, const int64_t* len, int32_t n);   // base_tally.h (engine.hip)
+int  engine_base_tally(EngineImpl* im, int32_t contig, int32_t pos0, int32_t n, uint32_t* out);
+int  engine_base_tally_stats(EngineImpl* im, xck_base_tally_stats* out);
+int  engine_find_candidates(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out);
 int  engine_device(const xck_engine* e);      // HIP device of the handle (-1: decode-only handle)
 int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (sysfs, by PCI bus id); -1 = unknown
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE

@@ -94,7 +94,7 @@ class Engine(object):
                  cell_tag=None, umi_tag=None, device=0, min_mapq=20, min_len=30,
                  incl_flag=0, excl_flag=772, no_orphan=True, min_include=0.9, min_count=1,
                  min_maf=0, no_dup_hap=True, n_threads=0, flags=0, decode_only=False, excl_pairs=None, region_mask=None, tag_filter=None,
-                 umi_consensus=False, min_baseq=0, umi_feature=None, umi_dedup=None):
+                 umi_consensus=False, min_baseq=0, umi_feature=None, umi_dedup=None, base_tally=False, contig_len=None):
         """regions: iterable of (chrom, start1, end1_incl[, name]); snps: iterable of
         (chrom, pos1, ref, alt, ref_hap, alt_hap); chrom names must already be stripped of
         'chr' and present in contig_names.  excl_pairs = (region indices, snp indices): pairs left out of the SNP -> region
@@ -116,7 +116,11 @@ class Engine(object):
         umi_dedup="1mm_all" (XCK_F_UMI_COLLAPSE; needs a basefc pipeline): within one (region, cell) UMIs joined by chains of single-base
         substitutions count as one molecule (STARsolo's 1MM_All, UMI-tools' cluster), and umi_dedup_stats() says what was merged; with
         umi_feature="unique" that rule runs first, on exact UMIs; None and "exact" count every distinct UMI, the default;
-        XCK_UMI_DEDUP=1mm_all in the environment does the same for every handle with a basefc pipeline."""
+        XCK_UMI_DEDUP=1mm_all in the environment does the same for every handle with a basefc pipeline.
+        base_tally=True (XCK_F_BASE_TALLY; needs a BAF pipeline): the handle keeps pseudo-bulk A / C / G / T counters per reference
+        position of every contig that receives reads (16 bytes a position), read by base_tally(), base_tally_stats() and
+        find_candidates().  contig_len: one length per contig (xck_set_contig_lengths); omitted, ingest_bam() / ingest_bams() take the
+        lengths from the first BAM's header, and push() needs set_contig_lengths() first."""
         self.lib = capi.load()
         self.mode = mode
         self.contig_names = list(contig_names)
@@ -193,7 +197,8 @@ class Engine(object):
         if umi_dedup not in (None, "exact", "1mm_all"):
             raise ValueError("umi_dedup must be None, 'exact' or '1mm_all'")
         cfg.flags = (int(flags) | (capi.XCK_F_DECODE_ONLY if decode_only else 0) | (capi.XCK_F_UMI_CONSENSUS if umi_consensus else 0)
-                     | (capi.XCK_F_UNIQUE_FEATURE if umi_feature == "unique" else 0) | (capi.XCK_F_UMI_COLLAPSE if umi_dedup == "1mm_all" else 0))
+                     | (capi.XCK_F_UNIQUE_FEATURE if umi_feature == "unique" else 0) | (capi.XCK_F_UMI_COLLAPSE if umi_dedup == "1mm_all" else 0)
+                     | (capi.XCK_F_BASE_TALLY if base_tally else 0))
         cfg.min_baseq = int(min_baseq)                              # (behind the flags: a non-zero value sets XCK_F_MIN_BASEQ beside it)
         self.cfg = cfg
         self.n_cells = int(n_cells)
@@ -205,6 +210,10 @@ class Engine(object):
         self.h = h
         self.umi_bits = self.lib.xck_umi_bits(self.h)
         self._result = None
+        self.base_tally_on = bool(cfg.flags & capi.XCK_F_BASE_TALLY)
+        self.contig_len = None
+        if contig_len is not None:
+            self.set_contig_lengths(contig_len)
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -253,6 +262,24 @@ class Engine(object):
     def reset(self):
         self._check(self.lib.xck_reset(self.h), "xck_reset")
         self._result = None
+
+    def set_contig_lengths(self, contig_len):
+        """The contigs' lengths of a base_tally handle (xck_set_contig_lengths): one per contig, each in 1 .. 2^31 - 1, before the
+        first push since the constructor or reset()."""
+        v = np.ascontiguousarray(contig_len, dtype=np.int64)
+        self._check(self.lib.xck_set_contig_lengths(self.h, capi.np_ptr(v, C.c_int64), len(v)), "xck_set_contig_lengths")
+        self.contig_len = v.copy()
+
+    def _lengths_from_bam(self, b, refs):
+        """a base_tally handle without lengths: those of the open BAM's header, through the contig mapping (a contig the BAM does
+        not name gets length 1: no read can reach it)"""
+        if not self.base_tally_on or self.contig_len is not None:
+            return
+        v = np.ones(len(self.contig_names), dtype=np.int64)
+        for tid, c in enumerate(resolve_contigs(refs, self.contig_names).tolist()):
+            if c >= 0:
+                v[c] = max(1, int(self.lib.xck_bam_ref_len(b, tid)))
+        self.set_contig_lengths(v)
 
     def _open(self, path, n_threads=0):
         b = C.c_void_p()
@@ -325,6 +352,7 @@ class Engine(object):
         with use_index the .bai is used to inflate only their byte ranges."""
         b, refs = self._open(path, n_threads or self.cfg.n_threads)
         try:
+            self._lengths_from_bam(b, refs)
             o, keep = self._opts(refs, sample, max_records, contig_mask, use_index, windows)
             n = C.c_int64(0)
             self._check(self.lib.xck_ingest_bam(self.h, b, C.byref(o), C.byref(n)), "xck_ingest_bam")
@@ -341,6 +369,7 @@ class Engine(object):
         def prepare(i):
             b, refs = self._open(paths[i], n_threads or self.cfg.n_threads)
             try:
+                self._lengths_from_bam(b, refs)
                 o, keep = self._opts(refs, i, 0, contig_mask, use_index, windows)
             except Exception:
                 self.lib.xck_bam_close(b)
@@ -635,6 +664,41 @@ class Engine(object):
         self._check(rc, "xck_get_baseq_stats")
         return dict(min_baseq=int(out.min_baseq), pairs_with_base=int(out.pairs_with_base), pairs_masked=int(out.pairs_masked))
 
+    def base_tally(self, contig, start, n):
+        """The A, C, G, T counters of positions [start, start + n) (0-based) of one contig (xck_get_base_tally; contig: index or name)
+        -> uint32 [n, 4].  Waits for queued work; a contig no read touched reads as zeros."""
+        c = self.contig_names.index(contig) if isinstance(contig, str) else int(contig)
+        out = np.zeros((max(int(n), 0), 4), dtype=np.uint32)
+        self._check(self.lib.xck_get_base_tally(self.h, c, int(start), int(n), capi.np_ptr(out, C.c_uint32)), "xck_get_base_tally")
+        return out
+
+    def base_tally_stats(self):
+        """What the base tally pass saw since the last reset (xck_get_base_tally_stats): dict of reads_tallied, bases_tallied,
+        bases_other, bases_masked, bases_out_of_range; None on a handle made without base_tally."""
+        out = capi.BaseTallyStats()
+        out.struct_size = C.sizeof(capi.BaseTallyStats)
+        rc = self.lib.xck_get_base_tally_stats(self.h, C.byref(out))
+        if rc == capi.XCK_E_STATE:
+            return None
+        self._check(rc, "xck_get_base_tally_stats")
+        return {k: int(getattr(out, k)) for k in capi.BASE_TALLY_FIELDS}
+
+    def find_candidates(self, min_count=20, min_maf=0.1):
+        """The candidate SNP positions of the tallies (xck_find_candidates), in (contig, pos) order: dict of contig (int32 index),
+        pos (int32, 1-based), ref, alt (str arrays of one letter), count (uint32 [n, 4]: A C G T), positions_covered - copies.
+        ref is the base with the largest count, alt the largest of the others (ties: the earliest of A, C, G, T); a position is a
+        candidate when alt > 0, not (n < min_count) and not (alt < n * min_maf).  Valid between finish() and reset()."""
+        cfg = capi.CandidateConfig()
+        cfg.struct_size = C.sizeof(capi.CandidateConfig)
+        cfg.min_count, cfg.min_maf = float(min_count), float(min_maf)
+        out = capi.Candidates()
+        self._check(self.lib.xck_find_candidates(self.h, C.byref(cfg), C.byref(out)), "xck_find_candidates")
+        n = int(out.n)
+        take = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(k,)).astype(dt, copy=True) if k else np.zeros(0, dtype=dt)
+        letters = lambda p: np.frombuffer(C.string_at(p, n), dtype="S1").astype("U1") if n else np.zeros(0, dtype="U1")
+        return dict(contig=take(out.contig, n, np.int32), pos=take(out.pos, n, np.int32), ref=letters(out.ref), alt=letters(out.alt),
+                    count=take(out.count, 4 * n, np.uint32).reshape(n, 4), positions_covered=int(out.positions_covered))
+
     def molecule_stats(self):
         """How the reads of the molecules of the last finish() agree (xck_get_molecule_stats): dict of molecules, multi_read,
         discordant, tied, changed in the struct's order, or None where the handle has nothing to say - made without umi_consensus /
@@ -681,6 +745,7 @@ class BamStream(object):
     def __init__(self, eng, path, sample=0, n_threads=0, contig_mask=None, use_index=False, windows=None):
         self.eng = eng
         self.b, refs = eng._open(path, n_threads or eng.cfg.n_threads)
+        eng._lengths_from_bam(self.b, refs)
         self.opts, self._keep = eng._opts(refs, sample, 0, contig_mask, use_index, windows)
         self.n_records = 0
         self.done = False

@@ -17,6 +17,7 @@ def _usage(fp=sys.stdout):
              "Commands:\n"
              "  -- BAF calculation\n"
              "     baf              Preprocessing pipeline for XClone BAF (GPU feature counting).\n"
+             "     discover         Candidate SNPs from the BAMs alone (GPU pseudo-bulk pileup; no SNP panel).\n"
              "\n"
              "  -- RDR calculation\n"
              "     basefc           Basic feature counting (GPU).\n"
@@ -42,6 +43,9 @@ def main(argv=None):
     if command == "baf":
         from .baf.pipeline import pipeline_main
         return pipeline_main(argv)
+    if command == "discover":
+        from .baf.discover import discover_main
+        return discover_main(argv)
     if command in ("-h", "--help"):
         _usage()
         sys.exit(0)
