@@ -108,6 +108,8 @@
  *   XCK_GROUP_LONG_ROW=<entries>          xck_group_counts: a source row with at least this many entries is summed by one block with a table in
  *                                         LDS, a shorter one by one wave in registers (default and upper bound 64, at least 1; tests: a small value
  *                                         reaches the block shape with small inputs)
+ *   XCK_REF_CHUNK_BYTES=<bytes>           xck_set_contig_ref: raw FASTA bytes per staging chunk (default 32 MiB, 64 .. 2^30; tests: 64 cuts a tiny
+ *                                         contig into many chunks).  Read once, at xck_create
  *   XCK_CELL_GROUPS=<file>                (read by the Python front-ends, not by a handle) a TSV of name<TAB>group lines without a header, name = a
  *                                         barcode or a sample id; groups are numbered by first appearance, names that are not cells of the run are
  *                                         ignored (their number goes to the log), cells not named are left out.  The front-ends then write, next to
@@ -776,6 +778,42 @@ int  xck_get_base_tally_stats(xck_engine* e, xck_base_tally_stats* out);
  * between a successful xck_finish and the next xck_reset (XCK_E_STATE otherwise, and without the flag); may be called repeatedly with
  * other thresholds.  The arrays belong to the handle and are valid until the next xck_find_candidates / xck_reset / xck_destroy. */
 int  xck_find_candidates(xck_engine* e, const xck_candidate_config* cfg, xck_candidates* out);
+
+/* -- the genome's sequence on a tally handle (ref_seq.h; additive, ABI 3 is unchanged) -------- */
+/* The sequence of one contig, packed on the device to 4 bits a position (BAM's codes =ACMGRSVTWYHKDBN; 0.5 byte a position).  raw is the
+ * FASTA file's bytes from the contig's first base through its last one, line ends included; line_bases / line_width are the .fai's:
+ * position p lies at raw[(p / line_bases) * line_width + p % line_bases].  Lower case reads as upper case; every byte that is not one of
+ * the 15 letters (`=`, `*`, `-`, digits, ...) reads as N.  The bytes are staged in chunks of XCK_REF_CHUNK_BYTES (read at xck_create,
+ * default 32 MiB, at least 64).  A byte below 33 where the geometry says a base must be - a stale index - fails the call with XCK_E_ARG
+ * ("the FASTA line geometry does not match its index") and drops the contig's sequence.  XCK_E_STATE on a handle without
+ * XCK_F_BASE_TALLY and before xck_set_contig_lengths; XCK_E_ARG for a contig out of range, line_bases < 1, line_width < line_bases and
+ * n_raw smaller than the offset of the contig's last position + 1; XCK_E_NOMEM names the contig.  Valid before or after pushes and
+ * xck_finish (it waits for the queued work); the sequence survives xck_reset, a second call for the contig replaces it, lengths that
+ * xck_set_contig_lengths changes drop it, xck_destroy frees it. */
+int  xck_set_contig_ref(xck_engine* e, int32_t contig, const char* raw, int64_t n_raw, int32_t line_bases, int32_t line_width);
+/* The upper-case letters of positions [pos0, pos0 + n) of a contig's packed sequence (no terminator; tests and debugging).  The range
+ * checks of xck_get_base_tally; XCK_E_STATE for a contig without a sequence. */
+int  xck_get_contig_ref(xck_engine* e, int32_t contig, int32_t pos0, int32_t n, char* out);
+/* has_table[c] = 1 for every contig whose table exists (a batch of it has been queued), else 0; n must be the handle's n_contigs. */
+int  xck_get_base_tally_contigs(xck_engine* e, uint8_t* has_table, int32_t n);
+/* xck_find_candidates oriented by the genome: with g the code of the position's base in the packed sequence,
+ *   g not A, C, G or T (N, IUPAC, no sequence loaded for the contig): never written; counts under ref_unknown when xck_find_candidates'
+ *     rule would have written it;
+ *   otherwise ref = g, alt = the base other than ref with the largest count (the earliest of equals in A, C, G, T), m = min(c[ref],
+ *     c[alt]); a candidate when m > 0, !((double)n < min_count) and !((double)m < (double)n * min_maf).  A written candidate counts
+ *     under ref_major when ref is the base xck_find_candidates would have written as ref, else under ref_minor; a position that
+ *     xck_find_candidates' rule accepts and this one rejects counts under ref_unsupported.
+ * ref_major + ref_minor = out->n, and the four together = the n of xck_find_candidates under the same thresholds.  States, arrays and
+ * positions_covered as xck_find_candidates; the lists of the two calls replace each other.  Set st->struct_size first. */
+typedef struct xck_candidate_ref_stats {
+    uint32_t struct_size;
+    uint32_t reserved;
+    int64_t  ref_major;
+    int64_t  ref_minor;
+    int64_t  ref_unsupported;
+    int64_t  ref_unknown;
+} xck_candidate_ref_stats;
+int  xck_find_candidates_ref(xck_engine* e, const xck_candidate_config* cfg, xck_candidates* out, xck_candidate_ref_stats* st);
 
 /* -- host ingest (replaces pysam.AlignmentFile + fetch(): own BGZF/BAM reader) --------------- */
 /* n_threads = 0: the process's CPU share (affinity and cgroup quota; 1.5 threads per CPU behind a quota).  BAM only: CRAM / SAM text

@@ -45,6 +45,10 @@ int  base_tally_set_lengths(EngineImpl*, const int64_t*, int32_t) { return XCK_E
 int  engine_base_tally(EngineImpl*, int32_t, int32_t, int32_t, uint32_t*) { return XCK_E_ARG; }
 int  engine_base_tally_stats(EngineImpl*, xck_base_tally_stats*) { return XCK_E_ARG; }
 int  engine_find_candidates(EngineImpl*, const xck_candidate_config*, xck_candidates*) { return XCK_E_ARG; }
+int  engine_find_candidates_ref(EngineImpl*, const xck_candidate_config*, xck_candidates*, xck_candidate_ref_stats*) { return XCK_E_ARG; }
+int  engine_set_contig_ref(EngineImpl*, int32_t, const char*, int64_t, int32_t, int32_t) { return XCK_E_ARG; }
+int  engine_get_contig_ref(EngineImpl*, int32_t, int32_t, int32_t, char*) { return XCK_E_ARG; }
+int  engine_base_tally_contigs(EngineImpl*, uint8_t*, int32_t) { return XCK_E_ARG; }
 // ---- csrc/local_phase.hip ----
 int  local_phase_run(const xck_phase_problem*, const PhasePlan&, double, xck_phase_result**) { return XCK_E_DEVICE; }
 void local_phase_free(xck_phase_result*) {}

@@ -7,9 +7,12 @@ tallies (Engine(base_tally=True), XCK_F_BASE_TALLY): the BAMs are streamed once,
 filter adds to the A / C / G / T counters of its reference position, and xck_find_candidates picks the positions.  The VCF it writes is
 what pileup(snp_vcf_fn=...) takes, and that step then applies the molecule-level counts and filter_snps to the candidates.
 
-Reads are counted here, not molecules (UMIs): a genome-wide molecule dedup would need a sort of every aligned base.  REF of a line is the
-base with the largest count and ALT the largest of the others (ties: the earliest of A, C, G, T) - no reference genome is read.
-Memory: 16 bytes of device memory per position of every contig that has reads.  Single GPU only.
+Reads are counted here, not molecules (UMIs): a genome-wide molecule dedup would need a sort of every aligned base.  Without a reference
+genome REF of a line is the base with the largest count and ALT the largest of the others (ties: the earliest of A, C, G, T).  With one
+(refseq_fn, -f / --refseq: cellsnp-lite's -f) the sequence of the contigs that have reads is packed on the device
+and REF is the genome's base, as phasing against a reference panel needs it: ALT is the largest of the other three, a position whose
+genome base is N or whose genome base the reads do not support is not written, and the log says how many lines that turned round.
+Memory: 16 bytes of device memory per position of every contig that has reads, half a byte more with a reference.  Single GPU only.
 """
 import argparse
 import sys
@@ -26,21 +29,22 @@ from .genotype import VCF_HEADER
 BASES = "ACGT"
 
 
-def candidate_vcf_text(names, cand):
+def candidate_vcf_text(names, cand, refseq_fn=None):
     """The VCF text of a candidate list: names[contig] as the BAM names them, cand = dict(contig, pos, ref, alt, count [n, 4]) in
-    (contig, pos) order.  INFO: AD = the ALT count, DP = REF + ALT, OTH = the other two bases."""
+    (contig, pos) order.  INFO: AD = the ALT count, DP = REF + ALT, OTH = the other two bases.  refseq_fn: the reference the
+    candidates were oriented by, named in one more header line."""
     lines = []
     count = np.asarray(cand["count"], dtype=np.int64).reshape(-1, 4)
     for i in range(len(cand["pos"])):
         ref, alt = str(cand["ref"][i]), str(cand["alt"][i])
         r, a, n = int(count[i, BASES.index(ref)]), int(count[i, BASES.index(alt)]), int(count[i].sum())
         lines.append("%s\t%d\t.\t%s\t%s\t.\tPASS\tAD=%d;DP=%d;OTH=%d\n" % (names[int(cand["contig"][i])], int(cand["pos"][i]), ref, alt, a, r + a, n - r - a))
-    return VCF_HEADER + "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n" + "".join(lines)
+    return VCF_HEADER + ("##reference=%s\n" % refseq_fn if refseq_fn else "") + "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n" + "".join(lines)
 
 
-def write_candidate_vcf(out_vcf_fn, names, cand):
+def write_candidate_vcf(out_vcf_fn, names, cand, refseq_fn=None):
     """candidate_vcf_text() to a file, bgzip-compressed when the name ends in .gz -> number of lines written"""
-    text = candidate_vcf_text(names, cand)
+    text = candidate_vcf_text(names, cand, refseq_fn)
     gz = out_vcf_fn.endswith(".gz")
     with zopen(out_vcf_fn, "wb" if gz else "w", ZF_F_BGZIP if gz else None, is_bytes=gz) as fp:
         fp.write(text.encode("utf8") if gz else text)
@@ -48,12 +52,16 @@ def write_candidate_vcf(out_vcf_fn, names, cand):
 
 
 def discover_snps(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=None, out_vcf_fn=None, min_count=20, min_maf=0.1,
-                  cell_tag="CB", umi_tag="UB", min_mapq=20, min_len=30, incl_flag=0, excl_flag=-1, no_orphan=True, ncores=1):
+                  cell_tag="CB", umi_tag="UB", min_mapq=20, min_len=30, incl_flag=0, excl_flag=-1, no_orphan=True, ncores=1, refseq_fn=None):
     """Candidate SNPs of the pseudo-bulk of one BAM (sam_fn; several with commas) or a list file (sam_list_fn), cells from barcode_fn
     (droplet) or sample_id_fn (one BAM per cell), written to out_vcf_fn.  A read counts when it passes the read filter the other
     commands use (min_mapq, min_len, flags, orphans, a listed cell, a UMI where umi_tag is set); min_count / min_maf as
     Engine.find_candidates().  excl_flag < 0: the command's default for the UMI setting.  Returns (#candidates, stats) with stats =
-    Engine.base_tally_stats() + positions_covered.  ValueError for invalid inputs and under a multi-GPU context."""
+    Engine.base_tally_stats() + positions_covered.  refseq_fn: a reference FASTA (indexed by <fasta>.fai, or scanned); the sequence
+    of the contigs that have reads is loaded behind the pass (Engine.set_reference), the candidates are oriented by it
+    (Engine.find_candidates(use_ref=True)), the VCF names it in a ##reference line, and stats gains ref_major, ref_minor,
+    ref_unsupported, ref_unknown, ref_contigs (loaded) and ref_contigs_missing.  ValueError for invalid inputs, a reference of another
+    genome build (a contig's length differs) and under a multi-GPU context."""
     if fcc.dist_requested():
         raise ValueError("discover_snps runs on one GPU: with contigs cut over ranks the reads near a cut are fed to both neighbours and would be "
                          "tallied twice; run it as a single process.")
@@ -88,14 +96,20 @@ def discover_snps(sam_fn=None, sam_list_fn=None, barcode_fn=None, sample_id_fn=N
                     continue
                 raise
             eng.finish()
-            cand = eng.find_candidates(min_count, min_maf)
+            ref = eng.set_reference(refseq_fn) if refseq_fn else None
+            cand = eng.find_candidates(min_count, min_maf, use_ref=bool(refseq_fn))
             stats = dict(eng.base_tally_stats(), positions_covered=cand["positions_covered"])
+            if ref is not None:
+                stats.update(cand["ref_stats"], ref_contigs=ref["loaded"], ref_contigs_missing=ref["missing"])
         finally:
             eng.close()
         break
-    n = write_candidate_vcf(out_vcf_fn, names, cand)
+    n = write_candidate_vcf(out_vcf_fn, names, cand, refseq_fn)
     info("[discover] %d BAM record(s), %d read(s) tallied, %d aligned base(s) on %d position(s): %d candidate SNP(s) (min_count %s, min_maf %s) -> %s"
          % (n_rec, stats["reads_tallied"], stats["bases_tallied"], stats["positions_covered"], n, min_count, min_maf, out_vcf_fn))
+    if refseq_fn:
+        info("[discover] oriented by %s: REF is the majority base at %d, the minority base at %d; left out: %d not supported by the reads, %d with no A/C/G/T in the reference"
+             % (refseq_fn, stats["ref_major"], stats["ref_minor"], stats["ref_unsupported"], stats["ref_unknown"]))
     return n, stats
 
 
@@ -111,6 +125,8 @@ Options:
   -b, --barcode FILE     A plain file listing all effective cell barcodes (droplet data).
   -i, --sampleList FILE  A list file containing sample IDs, each per line (one BAM per cell).
   -O, --outVCF FILE      Output VCF (bgzip-compressed when the name ends in .gz).
+  -f, --refseq FILE      Reference genome FASTA (plain text; FILE.fai is used when it is there): REF of every line is the
+                         genome's base.  Without it REF is the base with the largest count.
   --minCOUNT INT         Minimum aggregated count of a position [20]
   --minMAF FLOAT         Minimum minor allele fraction of a position [0.1]
   --cellTAG STR          Tag for cell barcodes, set to None when using sample IDs [CB]
@@ -132,7 +148,7 @@ def discover_main(argv):
         sys.exit(0)
     ap = argparse.ArgumentParser(prog="xcltk discover", add_help=False)
     ap.add_argument("-s", "--sam"); ap.add_argument("-S", "--samList"); ap.add_argument("-b", "--barcode"); ap.add_argument("-i", "--sampleList")
-    ap.add_argument("-O", "--outVCF", required=True)
+    ap.add_argument("-O", "--outVCF", required=True); ap.add_argument("-f", "--refseq")
     ap.add_argument("--minCOUNT", type=float, default=20); ap.add_argument("--minMAF", type=float, default=0.1)
     ap.add_argument("--cellTAG", default="CB"); ap.add_argument("--UMItag", default="UB")
     ap.add_argument("--minMAPQ", type=int, default=20); ap.add_argument("--minLEN", type=int, default=30)
@@ -142,7 +158,7 @@ def discover_main(argv):
     try:
         n, _ = discover_snps(sam_fn=a.sam, sam_list_fn=a.samList, barcode_fn=a.barcode, sample_id_fn=a.sampleList, out_vcf_fn=a.outVCF,
                              min_count=a.minCOUNT, min_maf=a.minMAF, cell_tag=a.cellTAG, umi_tag=a.UMItag, min_mapq=a.minMAPQ, min_len=a.minLEN,
-                             incl_flag=a.inclFLAG, excl_flag=a.exclFLAG, no_orphan=not a.countORPHAN, ncores=a.ncores)
+                             incl_flag=a.inclFLAG, excl_flag=a.exclFLAG, no_orphan=not a.countORPHAN, ncores=a.ncores, refseq_fn=a.refseq)
     except (ValueError, XckError) as e:
         sys.stderr.write("Error: %s\n" % e)
         return 1

@@ -233,6 +233,15 @@ class Candidates(C.Structure):
                 ("alt", C.POINTER(C.c_char)), ("count", C.POINTER(C.c_uint32)), ("positions_covered", C.c_int64)]
 
 
+class CandidateRefStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + [(k, C.c_int64) for k in (
+        "ref_major", "ref_minor", "ref_unsupported", "ref_unknown")]
+
+
+# the counters of xck_candidate_ref_stats in the struct's order
+CANDIDATE_REF_FIELDS = tuple(k for k, _ in CandidateRefStats._fields_[2:])
+
+
 class IngestOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("sample", C.c_int32),
                 ("tid_to_contig", C.POINTER(C.c_int32)), ("use_index", C.c_int32),
@@ -298,6 +307,10 @@ SYMBOLS = [
     ("xck_get_base_tally", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _P(C.c_uint32)]),
     ("xck_get_base_tally_stats", C.c_int, [C.c_void_p, _P(BaseTallyStats)]),
     ("xck_find_candidates", C.c_int, [C.c_void_p, _P(CandidateConfig), _P(Candidates)]),
+    ("xck_set_contig_ref", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
+    ("xck_get_contig_ref", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_char_p]),
+    ("xck_get_base_tally_contigs", C.c_int, [C.c_void_p, _P(C.c_uint8), C.c_int32]),
+    ("xck_find_candidates_ref", C.c_int, [C.c_void_p, _P(CandidateConfig), _P(Candidates), _P(CandidateRefStats)]),
     ("xck_bam_open", C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p), C.c_char_p, C.c_size_t]),
     ("xck_bam_close", None, [C.c_void_p]),
     ("xck_bam_n_refs", C.c_int, [C.c_void_p]),

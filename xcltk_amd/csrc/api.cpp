@@ -80,6 +80,7 @@ Knobs xck::Knobs::from_env() {
         for (char c : t) { ok = ok && c >= '0' && c <= '9'; v = v * 10 + (c - '0'); }
         k.min_baseq = ok && v <= 93 ? (int)v : -1;
     }
+    k.ref_chunk_bytes = std::max(64ll, std::min(1ll << 30, num("XCK_REF_CHUNK_BYTES", 32ll << 20)));
     k.group_long_row = (int)std::max(1ll, std::min(64ll, num("XCK_GROUP_LONG_ROW", 64)));
     k.cell_summary_slots = (int)std::max(0ll, std::min(1ll << 20, num("XCK_CELL_SUMMARY_SLOTS", 0)));
     if (*str("XCK_TAG_FILTER")) {                                        // TAG:VALUE[/MASK], numbers decimal or 0x hex, MASK defaults to all ones
@@ -493,6 +494,32 @@ int xck_find_candidates(xck_engine* e, const xck_candidate_config* cfg, xck_cand
     if (!im) return XCK_E_STATE;
     memset(out, 0, sizeof *out);
     return engine_find_candidates(im, cfg, out);
+}
+int xck_find_candidates_ref(xck_engine* e, const xck_candidate_config* cfg, xck_candidates* out, xck_candidate_ref_stats* st) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    if (!cfg || !out || !st) { e->err = "xck_find_candidates_ref: null argument"; return XCK_E_ARG; }
+    if (cfg->struct_size < sizeof(xck_candidate_config)) { e->err = "xck_candidate_config.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    if (st->struct_size < sizeof(xck_candidate_ref_stats)) { e->err = "xck_candidate_ref_stats.struct_size mismatch (ABI)"; return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    if (!im) return XCK_E_STATE;
+    const uint32_t sz = st->struct_size;
+    memset(out, 0, sizeof *out); memset(st, 0, sizeof *st); st->struct_size = sz;
+    return engine_find_candidates_ref(im, cfg, out, st);
+}
+int xck_set_contig_ref(xck_engine* e, int32_t contig, const char* raw, int64_t n_raw, int32_t line_bases, int32_t line_width) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    return im ? engine_set_contig_ref(im, contig, raw, n_raw, line_bases, line_width) : XCK_E_STATE;
+}
+int xck_get_contig_ref(xck_engine* e, int32_t contig, int32_t pos0, int32_t n, char* out) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    return im ? engine_get_contig_ref(im, contig, pos0, n, out) : XCK_E_STATE;
+}
+int xck_get_base_tally_contigs(xck_engine* e, uint8_t* has_table, int32_t n) {
+    if (!e) { set_thread_error("null argument"); return XCK_E_ARG; }
+    EngineImpl* im = tally_pipeline(e);
+    return im ? engine_base_tally_contigs(im, has_table, n) : XCK_E_STATE;
 }
 
 int xck_finish_async(xck_engine* e) { if (!e) return XCK_E_ARG; return for_pipelines(e, engine_finish_async); }

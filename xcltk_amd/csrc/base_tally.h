@@ -146,19 +146,56 @@ __host__ __device__ inline bool bt_candidate(const uint32_t c[4], double min_cou
     return m > 0 && !((double)n < min_count) && !((double)m < (double)n * min_maf);
 }
 
+// ... and oriented by the genome's 4-bit code g of the position (xck_find_candidates_ref, include/xck.h; tests/refseq_cases.py states it
+// again): ref = g, alt the largest of the other three, m the smaller of the two counts, the same arithmetic.  Returns the position's class;
+// BT_REF_MAJOR and BT_REF_MINOR are written (ref is, or is not, the base bt_candidate makes ref), the other two count what bt_candidate
+// accepts and this rule does not: a genome base the reads do not support, a genome code that is not one of A C G T.
+constexpr int BT_REF_NONE = 0, BT_REF_MAJOR = 1, BT_REF_MINOR = 2, BT_REF_UNSUPPORTED = 3, BT_REF_UNKNOWN = 4;
+__host__ __device__ inline int bt_candidate_ref(const uint32_t c[4], uint32_t g, double min_count, double min_maf, int& ref, int& alt, bool& covered) {
+    int pref, palt;
+    const bool parent = bt_candidate(c, min_count, min_maf, pref, palt, covered);
+    const int gi = g == 1u ? 0 : g == 2u ? 1 : g == 4u ? 2 : g == 8u ? 3 : -1;
+    ref = pref; alt = palt;
+    if (gi < 0) return parent ? BT_REF_UNKNOWN : BT_REF_NONE;
+    ref = gi;
+    alt = ref == 0 ? 1 : 0;
+    for (int b = alt + 1; b < 4; b++) if (b != ref && c[b] > c[alt]) alt = b;
+    const unsigned long long n = (unsigned long long)c[0] + c[1] + c[2] + c[3];
+    const uint32_t m = c[ref] < c[alt] ? c[ref] : c[alt];
+    if (m > 0 && !((double)n < min_count) && !((double)m < (double)n * min_maf)) return ref == pref ? BT_REF_MAJOR : BT_REF_MINOR;
+    return parent ? BT_REF_UNSUPPORTED : BT_REF_NONE;
+}
+
 // count pass (EMIT = false): candidates and covered positions per block of BT_CAND_BLOCK positions.  Emit pass: the same verdicts again,
 // every candidate written at the block's scanned offset + its rank inside the block, i.e. in position order.
-template <bool EMIT>
+// REF: the verdict is bt_candidate_ref's under the position's nibble of the contig's packed sequence (ref_seq.h; half a byte more a
+// position, two lanes a byte; null: no sequence, every position N), and the count pass leaves the block's four class counts in blk_st.
+// Without REF the two trailing arguments are not read.
+template <bool EMIT, bool REF = false>
 __global__ __launch_bounds__(BT_CAND_BLOCK) void k_bt_candidates(const uint32_t* __restrict__ tab, uint32_t len, double min_count, double min_maf,
                                                                  uint32_t* __restrict__ blk_cand, uint32_t* __restrict__ blk_cov,
-                                                                 int32_t* __restrict__ o_pos, uint32_t* __restrict__ o_cnt, char* __restrict__ o_ref, char* __restrict__ o_alt) {
+                                                                 int32_t* __restrict__ o_pos, uint32_t* __restrict__ o_cnt, char* __restrict__ o_ref, char* __restrict__ o_alt,
+                                                                 const uint8_t* __restrict__ seq, uint32_t* __restrict__ blk_st) {
     __shared__ uint32_t s_c[BT_CAND_BLOCK / 64], s_v[BT_CAND_BLOCK / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t p = blockIdx.x * (uint32_t)BT_CAND_BLOCK + tid;
     uint32_t c[4] = { 0, 0, 0, 0 };
     if (p < len) { const uint4 v = *reinterpret_cast<const uint4*>(tab + (size_t)p * 4); c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w; }
     int ref = 0, alt = 1; bool cov = false;
-    const bool cand = bt_candidate(c, min_count, min_maf, ref, alt, cov);
+    bool cand;
+    if (REF) {
+        __shared__ uint32_t s_k[BT_CAND_BLOCK / 64][4];
+        uint32_t g = 15u;
+        if (seq && p < len) { const uint32_t by = seq[p >> 1]; g = (p & 1u) ? (by & 15u) : (by >> 4); }   // (p < len: inside the (len + 7) / 8 dwords)
+        const int cls = bt_candidate_ref(c, g, min_count, min_maf, ref, alt, cov);
+        cand = cls == BT_REF_MAJOR || cls == BT_REF_MINOR;
+        if (!EMIT) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) { const unsigned long long mk = __ballot(cls == k + 1); if (lane == 0) s_k[wave][k] = (uint32_t)__popcll(mk); }
+            __syncthreads();
+            if (tid < 4) { uint32_t a = 0; for (int w = 0; w < BT_CAND_BLOCK / 64; w++) a += s_k[w][tid]; blk_st[(size_t)blockIdx.x * 4 + tid] = a; }
+        }
+    } else cand = bt_candidate(c, min_count, min_maf, ref, alt, cov);
     const unsigned long long mc = __ballot(cand), mv = __ballot(cov);
     if (lane == 0) { s_c[wave] = (uint32_t)__popcll(mc); s_v[wave] = (uint32_t)__popcll(mv); }
     __syncthreads();
@@ -172,6 +209,22 @@ __global__ __launch_bounds__(BT_CAND_BLOCK) void k_bt_candidates(const uint32_t*
         *reinterpret_cast<uint4*>(o_cnt + (size_t)at * 4) = make_uint4(c[0], c[1], c[2], c[3]);
         o_ref[at] = "ACGT"[ref]; o_alt[at] = "ACGT"[alt];
     }
+}
+
+// one block: the four class counts of blk_st[0, nb) summed into tot[0 .. 4) (xck_find_candidates_ref, behind the count pass)
+__global__ __launch_bounds__(1024) void k_bt_ref_sum(const uint32_t* __restrict__ blk_st, long long nb, unsigned long long* __restrict__ tot) {
+    __shared__ unsigned long long s_w[16][4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    unsigned long long a[4] = { 0, 0, 0, 0 };
+    for (long long i = tid; i < nb; i += 1024) { const uint4 v = *reinterpret_cast<const uint4*>(blk_st + i * 4); a[0] += v.x; a[1] += v.y; a[2] += v.z; a[3] += v.w; }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+#pragma unroll
+        for (int dd = 32; dd >= 1; dd >>= 1) a[k] += __shfl_xor(a[k], dd, 64);
+        if (lane == 0) s_w[wave][k] = a[k];
+    }
+    __syncthreads();
+    if (tid < 4) { unsigned long long t = 0; for (int w = 0; w < 16; w++) t += s_w[w][tid]; tot[tid] = t; }
 }
 
 // one block: blk[0, nb) -> its exclusive prefix sums in place; tot[0] = their total, tot[1] = the sum of cov[0, nb)
@@ -209,9 +262,10 @@ __global__ __launch_bounds__(1024) void k_bt_scan(uint32_t* __restrict__ blk, co
 static int base_tally_init(EngineImpl* im) {
     im->base_tally = true;
     im->bt_tab.assign(std::max(im->eng->n_contigs, 1), nullptr);
+    im->rs_tab.assign(std::max(im->eng->n_contigs, 1), nullptr);
     return dev_zeroed(im, (void**)&im->d_bt_stats, BT_BUF_WORDS * sizeof(unsigned long long));
 }
-// xck_reset: the tables that exist and the counters zeroed on s_comp (the caller synchronises); the lengths stay
+// xck_reset: the tables that exist and the counters zeroed on s_comp (the caller synchronises); the lengths and the packed sequences stay
 static int base_tally_reset(EngineImpl* im) {
     for (size_t c = 0; c < im->bt_tab.size(); c++)
         if (im->bt_tab[c]) HIP_TRY(hipMemsetAsync(im->bt_tab[c], 0, (size_t)im->bt_len[c] * 16, im->s_comp));
@@ -220,6 +274,7 @@ static int base_tally_reset(EngineImpl* im) {
 }
 void base_tally_free(EngineImpl* im) {
     for (uint32_t* p : im->bt_tab) if (p) hipFree(p);
+    ref_seq_free(im);
     for (void* p : { (void*)im->d_bt_stats, (void*)im->d_bt_blk, (void*)im->d_bt_out, (void*)im->d_bt_tot }) if (p) hipFree(p);
 }
 
@@ -232,6 +287,11 @@ int base_tally_set_lengths(EngineImpl* im, const int64_t* len, int32_t n) {
         if (im->bt_tab[c] && (im->bt_len.size() != (size_t)n || im->bt_len[c] != len[c])) {   // (after a reset: a table that exists keeps its size)
             HIP_TRY(hipSetDevice(im->device));
             HIP_TRY(hipFree(im->bt_tab[c])); im->bt_tab[c] = nullptr;
+        }
+    for (int32_t c = 0; c < n; c++)
+        if (im->rs_tab[c] && im->bt_len[c] != len[c]) {                  // (a packed sequence is as long as its contig: ref_seq.h)
+            HIP_TRY(hipSetDevice(im->device));
+            HIP_TRY(hipFree(im->rs_tab[c])); im->rs_tab[c] = nullptr;
         }
     im->bt_len.assign(len, len + n);
     return 0;
@@ -299,37 +359,48 @@ int engine_base_tally_stats(EngineImpl* im, xck_base_tally_stats* out) {
 }
 
 // xck_find_candidates for the pileup pipeline: per allocated table, in contig order, a count pass, a scan and an emit pass; the contig's
-// candidates are copied behind those of the contigs before it, so the arrays are in (contig, pos) order
-int engine_find_candidates(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out) {
+// candidates are copied behind those of the contigs before it, so the arrays are in (contig, pos) order.
+// st (xck_find_candidates_ref): the REF instantiation under the contig's packed sequence (ref_seq.h), its class counts summed per contig
+static int find_candidates(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out, xck_candidate_ref_stats* st) {
     if (!im->base_tally) { im->eng->err = "handle made without XCK_F_BASE_TALLY"; return XCK_E_STATE; }
-    if (!im->finished || im->fold_failed) { im->eng->err = "xck_find_candidates: valid between a successful xck_finish and the next xck_reset"; return XCK_E_STATE; }
+    if (!im->finished || im->fold_failed) {
+        im->eng->err = std::string(st ? "xck_find_candidates_ref" : "xck_find_candidates") + ": valid between a successful xck_finish and the next xck_reset"; return XCK_E_STATE; }
     HIP_TRY(hipSetDevice(im->device));
     const auto t0 = std::chrono::steady_clock::now();
     im->h_bt_contig.clear(); im->h_bt_pos.clear(); im->h_bt_ref.clear(); im->h_bt_alt.clear(); im->h_bt_cnt.clear();
     long long covered = 0;
-    if (!im->d_bt_tot) HIP_TRY(hipMalloc((void**)&im->d_bt_tot, 2 * sizeof(unsigned long long)));
+    if (!im->d_bt_tot) HIP_TRY(hipMalloc((void**)&im->d_bt_tot, 6 * sizeof(unsigned long long)));   // the scan's two totals, the four class counts
+    long long cls[4] = { 0, 0, 0, 0 };
     for (size_t c = 0; c < im->bt_tab.size(); c++) {
         const uint32_t* tab = im->bt_tab[c];
         if (!tab) continue;
         const uint32_t len = (uint32_t)im->bt_len[c];
         const size_t nb = ((size_t)len + BT_CAND_BLOCK - 1) / BT_CAND_BLOCK;
-        if (const int rc = grow_device(im, (void**)&im->d_bt_blk, &im->bt_blk_cap, 2 * nb * sizeof(uint32_t), 0)) return rc;
-        uint32_t* blk_cand = (uint32_t*)im->d_bt_blk; uint32_t* blk_cov = blk_cand + nb;
-        hipLaunchKernelGGL((k_bt_candidates<false>), dim3((unsigned)nb), dim3(BT_CAND_BLOCK), 0, im->s_comp, tab, len, cfg->min_count, cfg->min_maf, blk_cand, blk_cov,
-                           (int32_t*)nullptr, (uint32_t*)nullptr, (char*)nullptr, (char*)nullptr);
+        if (const int rc = grow_device(im, (void**)&im->d_bt_blk, &im->bt_blk_cap, (st ? 6 : 2) * nb * sizeof(uint32_t), 0)) return rc;
+        uint32_t* blk_st = (uint32_t*)im->d_bt_blk;                     // (in front: its rows are read as uint4)
+        uint32_t* blk_cand = blk_st + (st ? 4 * nb : 0); uint32_t* blk_cov = blk_cand + nb;
+        const uint8_t* seq = st ? (const uint8_t*)im->rs_tab[c] : nullptr;
+        if (st) hipLaunchKernelGGL((k_bt_candidates<false, true>), dim3((unsigned)nb), dim3(BT_CAND_BLOCK), 0, im->s_comp, tab, len, cfg->min_count, cfg->min_maf, blk_cand, blk_cov,
+                                   (int32_t*)nullptr, (uint32_t*)nullptr, (char*)nullptr, (char*)nullptr, seq, blk_st);
+        else hipLaunchKernelGGL((k_bt_candidates<false>), dim3((unsigned)nb), dim3(BT_CAND_BLOCK), 0, im->s_comp, tab, len, cfg->min_count, cfg->min_maf, blk_cand, blk_cov,
+                                (int32_t*)nullptr, (uint32_t*)nullptr, (char*)nullptr, (char*)nullptr, (const uint8_t*)nullptr, (uint32_t*)nullptr);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_bt_scan, dim3(1), dim3(1024), 0, im->s_comp, blk_cand, (const uint32_t*)blk_cov, (long long)nb, im->d_bt_tot);
         HIP_TRY(hipGetLastError());
-        unsigned long long tot[2] = { 0, 0 };
-        HIP_TRY(hipMemcpyAsync(tot, im->d_bt_tot, sizeof tot, hipMemcpyDeviceToHost, im->s_comp));
+        if (st) { hipLaunchKernelGGL(k_bt_ref_sum, dim3(1), dim3(1024), 0, im->s_comp, (const uint32_t*)blk_st, (long long)nb, im->d_bt_tot + 2); HIP_TRY(hipGetLastError()); }
+        unsigned long long tot[6] = { 0, 0, 0, 0, 0, 0 };
+        HIP_TRY(hipMemcpyAsync(tot, im->d_bt_tot, (st ? 6 : 2) * sizeof(unsigned long long), hipMemcpyDeviceToHost, im->s_comp));
         HIP_TRY(hipStreamSynchronize(im->s_comp));
         covered += (long long)tot[1];
+        for (int k = 0; k < 4; k++) cls[k] += (long long)tot[2 + k];
         const size_t n = (size_t)tot[0];
         if (!n) continue;
         // the contig's output: [counts n * 16 | pos n * 4 | ref n | alt n]
         if (const int rc = grow_device(im, (void**)&im->d_bt_out, &im->bt_out_cap, n * 22, n * 22 / 4 + 4096)) return rc;
         uint32_t* o_cnt = (uint32_t*)im->d_bt_out; int32_t* o_pos = (int32_t*)(im->d_bt_out + n * 16); char* o_ref = im->d_bt_out + n * 20; char* o_alt = o_ref + n;
-        hipLaunchKernelGGL((k_bt_candidates<true>), dim3((unsigned)nb), dim3(BT_CAND_BLOCK), 0, im->s_comp, tab, len, cfg->min_count, cfg->min_maf, blk_cand, blk_cov, o_pos, o_cnt, o_ref, o_alt);
+        if (st) hipLaunchKernelGGL((k_bt_candidates<true, true>), dim3((unsigned)nb), dim3(BT_CAND_BLOCK), 0, im->s_comp, tab, len, cfg->min_count, cfg->min_maf, blk_cand, blk_cov, o_pos, o_cnt, o_ref, o_alt, seq, blk_st);
+        else hipLaunchKernelGGL((k_bt_candidates<true>), dim3((unsigned)nb), dim3(BT_CAND_BLOCK), 0, im->s_comp, tab, len, cfg->min_count, cfg->min_maf, blk_cand, blk_cov, o_pos, o_cnt, o_ref, o_alt,
+                                (const uint8_t*)nullptr, (uint32_t*)nullptr);
         HIP_TRY(hipGetLastError());
         const size_t at = im->h_bt_pos.size();
         im->h_bt_contig.resize(at + n, (int32_t)c); im->h_bt_pos.resize(at + n); im->h_bt_ref.resize(at + n); im->h_bt_alt.resize(at + n); im->h_bt_cnt.resize((at + n) * 4);
@@ -342,8 +413,11 @@ int engine_find_candidates(EngineImpl* im, const xck_candidate_config* cfg, xck_
     out->n = (int64_t)im->h_bt_pos.size();
     out->contig = im->h_bt_contig.data(); out->pos = im->h_bt_pos.data(); out->ref = im->h_bt_ref.data(); out->alt = im->h_bt_alt.data(); out->count = im->h_bt_cnt.data();
     out->positions_covered = covered;
+    if (st) { st->ref_major = cls[0]; st->ref_minor = cls[1]; st->ref_unsupported = cls[2]; st->ref_unknown = cls[3]; }
     if (im->eng->knobs.debug_timing)
-        fprintf(stderr, "[xck] find_candidates: %.3f ms (host clock), %lld candidates of %lld covered positions\n",
+        fprintf(stderr, "[xck] find_candidates%s: %.3f ms (host clock), %lld candidates of %lld covered positions\n", st ? "_ref" : "",
                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), (long long)out->n, covered);
     return 0;
 }
+int engine_find_candidates(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out) { return find_candidates(im, cfg, out, nullptr); }
+int engine_find_candidates_ref(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out, xck_candidate_ref_stats* st) { return find_candidates(im, cfg, out, st); }

@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include "engine_impl.h"
+#include "ref_geom.h"
 
 namespace xck {
 #ifndef XCK_WS_SNP
@@ -1032,6 +1033,7 @@ int launch_join(EngineImpl* im) { return im->key_bits == 64 ? launch_join_t<uint
 #include "read_fate.h"
 #include "feature_summary.h"
 #include "base_tally.h"
+#include "ref_seq.h"
 
 // What the pipeline (pipeline.hip) knows of the summaries and the base tally: their memory at create, their zeroing at reset (on s_comp, in front
 // of the reset's synchronise), and their passes behind the FIRST join launch of a queue (each returns at once when its flag is off).

@@ -240,6 +240,11 @@ struct EngineImpl {
     unsigned long long* d_bt_stats = nullptr; unsigned long long* d_bt_tot = nullptr;
     char* d_bt_blk = nullptr; size_t bt_blk_cap = 0; char* d_bt_out = nullptr; size_t bt_out_cap = 0;
     std::vector<int32_t> h_bt_contig, h_bt_pos; std::vector<char> h_bt_ref, h_bt_alt; std::vector<uint32_t> h_bt_cnt;
+    // the genome's sequence of a tally handle (ref_seq.h): per contig its (bt_len + 7) / 8 dwords of 4-bit codes in HBM (null: no sequence),
+    // the two pinned and the two device staging chunks of xck_set_contig_ref with the events behind their kernels, the stale-index counter
+    std::vector<uint32_t*> rs_tab;
+    void* h_rs_stage[2] = {nullptr, nullptr}; size_t rs_hcap[2] = {0, 0}; void* d_rs_stage[2] = {nullptr, nullptr}; size_t rs_dcap[2] = {0, 0};
+    hipEvent_t rs_ev[2] = {nullptr, nullptr}; unsigned long long* d_rs_bad = nullptr;
     int batch_rc = 0;                                     // describe_batch: the code of the error it reported (XCK_E_ARG unless a table could not be had)
     // xck_refold (refold.h): the caller's SNP list as given to xck_create, the regrown tables' capacities, and the builder's own buffers
     std::vector<xck_snp> snps_in;
@@ -325,6 +330,7 @@ int summaries_reset(EngineImpl* im);                       // engine_reset: thei
 int launch_summaries(EngineImpl* im);                      // launch_queue: their passes behind the first join launch of im->inflight
 int base_tally_touch(EngineImpl* im, int32_t contig);      // describe_batch, XCK_F_BASE_TALLY: the table of a contig whose batch is about to be queued (base_tally.h)
 void base_tally_free(EngineImpl* im);                      // engine_destroy: the tables and buffers of base_tally.h
+void ref_seq_free(EngineImpl* im);                         // ... and, called by it, the packed sequences and staging chunks of ref_seq.h
 // defined in finish.hip
 int finish_init(EngineImpl* im);                           // engine_create: per-device attributes of the fold kernels
 int snp_verdicts(EngineImpl* im, uint32_t* d_kept);        // d_kept[s] = snp_passes() of sorted SNP s on the tallies of the last finish (enqueued on s_comp)

@@ -126,6 +126,7 @@ struct Knobs {
     int  umi_feature = 0; std::string umi_feature_text;   // XCK_UMI_FEATURE=unique: XCK_F_UNIQUE_FEATURE ORed into the flags of every handle with a basefc pipeline that drives a GPU; -1 = a value that is neither `unique` nor `all` nor empty (xck_create fails and quotes the text)
     int  umi_dedup = 0; std::string umi_dedup_text;   // XCK_UMI_DEDUP=1mm_all: XCK_F_UMI_COLLAPSE ORed into the flags of every handle with a basefc pipeline that drives a GPU; -1 = a value that is neither `1mm_all` nor `exact` nor empty (xck_create fails and quotes the text)
     int  min_baseq = 0; std::string min_baseq_text;   // XCK_MIN_BASEQ=<0 .. 93>: xck_config.min_baseq of every handle with a BAF pipeline that drives a GPU and sets none; -1 = malformed (xck_create fails and quotes the text)
+    long long ref_chunk_bytes = 32ll << 20;   // XCK_REF_CHUNK_BYTES: raw FASTA bytes per staging chunk of xck_set_contig_ref (64 .. 2^30; tests: 64 cuts a tiny contig into many chunks)
     int  group_long_row = 64;            // XCK_GROUP_LONG_ROW: rows of xck_group_counts with at least this many entries take one block each (1 .. 64; tests: a small value reaches that shape with small inputs)
     bool gpu_parse = true;               // XCK_GPU_PARSE=auto|0: walk and parse the GPU-inflated chunks on the device where that applies (bam.cpp device_parse_now)
     bool gpu_names = false;              // XCK_GPU_NAMES=1: read names of a UMI-less handle are interned on the device (intern_dev.h; the conditions: api.cpp xck_create)
@@ -218,6 +219,10 @@ int  base_tally_set_lengths(EngineImpl* im, const int64_t* len, int32_t n);   //
 int  engine_base_tally(EngineImpl* im, int32_t contig, int32_t pos0, int32_t n, uint32_t* out);
 int  engine_base_tally_stats(EngineImpl* im, xck_base_tally_stats* out);
 int  engine_find_candidates(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out);
+int  engine_find_candidates_ref(EngineImpl* im, const xck_candidate_config* cfg, xck_candidates* out, xck_candidate_ref_stats* st);
+int  engine_set_contig_ref(EngineImpl* im, int32_t contig, const char* raw, int64_t n_raw, int32_t line_bases, int32_t line_width);   // ref_seq.h (engine.hip)
+int  engine_get_contig_ref(EngineImpl* im, int32_t contig, int32_t pos0, int32_t n, char* out);
+int  engine_base_tally_contigs(EngineImpl* im, uint8_t* has_table, int32_t n);
 int  engine_device(const xck_engine* e);      // HIP device of the handle (-1: decode-only handle)
 int  engine_numa_node(const xck_engine* e);   // NUMA node of the handle's GPU (sysfs, by PCI bus id); -1 = unknown
 // One decoded chunk (all SoA columns in one pinned host block of `bytes` bytes at host_base; the batches point into it): ONE

@@ -12,6 +12,7 @@ decoder alone and refuses push/finish).
 
 import ctypes as C
 import os
+from logging import info
 
 import numpy as np
 
@@ -212,6 +213,7 @@ class Engine(object):
         self._result = None
         self.base_tally_on = bool(cfg.flags & capi.XCK_F_BASE_TALLY)
         self.contig_len = None
+        self.ref_loaded = False                                     # set_reference() has loaded a sequence: find_candidates() orients by it
         if contig_len is not None:
             self.set_contig_lengths(contig_len)
 
@@ -683,21 +685,72 @@ class Engine(object):
         self._check(rc, "xck_get_base_tally_stats")
         return {k: int(getattr(out, k)) for k in capi.BASE_TALLY_FIELDS}
 
-    def find_candidates(self, min_count=20, min_maf=0.1):
+    def tally_contigs(self):
+        """indices of the contigs whose tally table exists, i.e. that a batch has reached (xck_get_base_tally_contigs)"""
+        has = np.zeros(len(self.contig_names), dtype=np.uint8)
+        self._check(self.lib.xck_get_base_tally_contigs(self.h, capi.np_ptr(has, C.c_uint8), len(has)), "xck_get_base_tally_contigs")
+        return np.flatnonzero(has).tolist()
+
+    def set_reference(self, fasta_fn, names=None):
+        """The genome's sequence of a base_tally handle from a FASTA file (utils/fasta.py: mapped, indexed by <fasta>.fai or by one
+        scan; xck_set_contig_ref packs the text on the device, 0.5 byte a position).  FASTA names are matched to the handle's contigs
+        with the chr tolerance of the BAM mapping.  names: the contigs to load; None: after pushes the contigs that have a table,
+        before them all.  ValueError when a matched contig's length differs from the handle's contig_len (another genome build), for a
+        compressed file and without contig lengths.  -> dict(loaded=[contig names], missing=[asked-for contigs the FASTA lacks]);
+        find_candidates() then orients by the reference, and a contig without a sequence counts as unknown."""
+        from .utils.fasta import Fasta, match_contigs
+        if self.contig_len is None:
+            raise ValueError("set_reference needs the contigs' lengths (contig_len, set_contig_lengths() or an ingest) first")
+        if names is not None:
+            want = [self.contig_names.index(x) for x in names]
+        else:
+            want = self.tally_contigs() or None
+        with Fasta(fasta_fn) as fa:
+            pairs, missing = match_contigs(fa.entries, self.contig_names, self.contig_len, want)
+            for c, e in pairs:
+                addr, n_raw, lb, lw = fa.span(e)
+                self._check(self.lib.xck_set_contig_ref(self.h, c, C.c_void_p(addr), n_raw, lb, lw), "xck_set_contig_ref")
+        loaded = [self.contig_names[c] for c, _ in pairs]
+        self.ref_loaded = self.ref_loaded or bool(loaded)
+        info("[engine] reference %s: %d contig(s) loaded%s" % (fasta_fn, len(loaded), (", not in the FASTA: " + ", ".join(missing)) if missing else ""))
+        return dict(loaded=loaded, missing=missing)
+
+    def contig_ref(self, contig, start, n):
+        """The letters of positions [start, start + n) (0-based) of a contig's packed sequence (xck_get_contig_ref) -> str"""
+        c = self.contig_names.index(contig) if isinstance(contig, str) else int(contig)
+        out = C.create_string_buffer(max(int(n), 0) + 1)
+        self._check(self.lib.xck_get_contig_ref(self.h, c, int(start), int(n), out), "xck_get_contig_ref")
+        return out.raw[:max(int(n), 0)].decode()
+
+    def find_candidates(self, min_count=20, min_maf=0.1, use_ref=None):
         """The candidate SNP positions of the tallies (xck_find_candidates), in (contig, pos) order: dict of contig (int32 index),
         pos (int32, 1-based), ref, alt (str arrays of one letter), count (uint32 [n, 4]: A C G T), positions_covered - copies.
         ref is the base with the largest count, alt the largest of the others (ties: the earliest of A, C, G, T); a position is a
-        candidate when alt > 0, not (n < min_count) and not (alt < n * min_maf).  Valid between finish() and reset()."""
+        candidate when alt > 0, not (n < min_count) and not (alt < n * min_maf).  Valid between finish() and reset().
+        use_ref (None: when set_reference() has loaded a sequence): xck_find_candidates_ref - ref is the genome's base, alt the
+        largest of the others, the smaller of the two counts takes the place of the alt count, positions whose genome base is not
+        A C G T are left out - and the dict carries ref_stats: ref_major, ref_minor (written; ref is / is not the base the plain
+        rule makes ref), ref_unsupported, ref_unknown (candidates of the plain rule that are not written)."""
         cfg = capi.CandidateConfig()
         cfg.struct_size = C.sizeof(capi.CandidateConfig)
         cfg.min_count, cfg.min_maf = float(min_count), float(min_maf)
         out = capi.Candidates()
-        self._check(self.lib.xck_find_candidates(self.h, C.byref(cfg), C.byref(out)), "xck_find_candidates")
+        ref_stats = None
+        if self.ref_loaded if use_ref is None else use_ref:
+            st = capi.CandidateRefStats()
+            st.struct_size = C.sizeof(capi.CandidateRefStats)
+            self._check(self.lib.xck_find_candidates_ref(self.h, C.byref(cfg), C.byref(out), C.byref(st)), "xck_find_candidates_ref")
+            ref_stats = {k: int(getattr(st, k)) for k in capi.CANDIDATE_REF_FIELDS}
+        else:
+            self._check(self.lib.xck_find_candidates(self.h, C.byref(cfg), C.byref(out)), "xck_find_candidates")
         n = int(out.n)
         take = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(k,)).astype(dt, copy=True) if k else np.zeros(0, dtype=dt)
         letters = lambda p: np.frombuffer(C.string_at(p, n), dtype="S1").astype("U1") if n else np.zeros(0, dtype="U1")
-        return dict(contig=take(out.contig, n, np.int32), pos=take(out.pos, n, np.int32), ref=letters(out.ref), alt=letters(out.alt),
-                    count=take(out.count, 4 * n, np.uint32).reshape(n, 4), positions_covered=int(out.positions_covered))
+        res = dict(contig=take(out.contig, n, np.int32), pos=take(out.pos, n, np.int32), ref=letters(out.ref), alt=letters(out.alt),
+                   count=take(out.count, 4 * n, np.uint32).reshape(n, 4), positions_covered=int(out.positions_covered))
+        if ref_stats is not None:
+            res["ref_stats"] = ref_stats
+        return res
 
     def molecule_stats(self):
         """How the reads of the molecules of the last finish() agree (xck_get_molecule_stats): dict of molecules, multi_read,

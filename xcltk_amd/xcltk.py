@@ -56,7 +56,8 @@ def main(argv=None):
         from .tools.convert import convert_main
         return convert_main(argv)
     if command in ("fixref",):
-        sys.stderr.write("Error: command '%s' is outside the accelerated hot path and not provided by %s\n" % (command, ENGINE))
+        sys.stderr.write("Error: command '%s' is outside the accelerated hot path and not provided by %s "
+                         "(candidate SNPs oriented by the reference genome: `discover --refseq`)\n" % (command, ENGINE))
         sys.exit(1)
     sys.stderr.write("Error: wrong command '%s'\n" % command)
     sys.exit(1)
