@@ -2,6 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Ixcltk_amd/csrc tools/gpu_inflate_bench.hip xcltk_amd/csrc/inflate_dev.hip -lz -o tools/scratch/gpu_inflate_bench
 //   [INFLATE_VARIANT=0|1] [INFLATE_CRC=1] tools/scratch/gpu_inflate_bench FILE.bam [max_bytes [blocks_per_launch]]     (variant: see dev_inflate_launch)
 // INFLATE_CRC=1: every block's footer CRC goes to DevBlock.crc and the kernel checks it (check_crc); one more line says what it found.
+// Once per process: "occupancy: N workgroups per CU" - what the runtime fits of the instantiation that is about to run (dev_inflate_occupancy).
 // INFLATE_STATUSES=1: one more line "statuses: s0 s1 ..." with every block's status in file order (tests/test_gpu_inflate_streams.py, tests/test_gpu_inflate.py).
 #include <zlib.h>
 #include <chrono>
@@ -28,6 +29,7 @@ int main(int argc, char** argv) {
     uint8_t *d_in, *d_out; xck::DevBlock* d_bl; int32_t* d_st;
     CK(hipMalloc((void**)&d_in, o)); CK(hipMalloc((void**)&d_out, tot + 64)); CK(hipMalloc((void**)&d_bl, bl.size() * sizeof(xck::DevBlock))); CK(hipMalloc((void**)&d_st, bl.size() * 4));
     CK(hipMemcpy(d_in, d.data(), o, hipMemcpyHostToDevice)); CK(hipMemcpy(d_bl, bl.data(), bl.size() * sizeof(xck::DevBlock), hipMemcpyHostToDevice));
+    printf("occupancy: %d workgroups per CU (variant %d, crc %d)\n", xck::dev_inflate_occupancy(variant, check_crc), variant, (int)check_crc);
     hipStream_t s; CK(hipStreamCreate(&s));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int rep = 0; rep < 3; rep++) {

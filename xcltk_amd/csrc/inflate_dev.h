@@ -20,6 +20,9 @@ int dev_inflate_launch(hipStream_t stream, const uint8_t* d_in, const DevBlock* 
 // phase clocks (bench harness only, dev_inflate_read_prof); check_crc: every inflated non-empty block's CRC-32 (zlib's crc32) is compared with
 // DevBlock.crc - status INFLATE_ST_CRC when they differ (empty blocks are not checked, as on the host)
 
+// workgroups (of one wave) of that instantiation the runtime fits on a CU (hipOccupancyMaxActiveBlocksPerMultiprocessor); -1 = no answer
+int dev_inflate_occupancy(int variant = 0, bool check_crc = false);
+
 // One chunk of BGZF blocks in flight on the GPU (the host decoder keeps a ring of these, csrc/bam.cpp): pinned host buffers for the
 // compressed bytes, the block table, the inflated bytes and the per-block status; device twins; a stream and an event of its own,
 // so that the chunks of a ring overlap on the device (the decoder needs thousands of blocks in flight to pay: one wave per block).

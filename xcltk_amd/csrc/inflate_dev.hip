@@ -8,10 +8,15 @@
 // profiles/r02_d_ingest_*.log) while the GPU idled.  BGZF blocks are independent <= 64 KiB deflate streams, so a chunk of
 // ~750 blocks is 750 waves of work.  Inside a block the SYMBOL BOUNDARIES are serial - they are only known after the previous
 // symbol - but what would be decoded at a given bit offset is not:
-//   * block headers and the code-length code: lane 0, serially (a few per cent of a block's time);
+//   * block headers: the chain of code-length symbols is serial and stays with lane 0 - one look-up in a 128-entry table the lanes build
+//     and one LDS store per symbol, which marks where a run of equal lengths begins; the wave spreads the marks over the lengths (a
+//     prefix maximum), and writes a fixed block's lengths;
 //   * decode tables: built by all lanes into LDS (9-bit primary + sub-tables for literal / length, 8-bit for distance; a code that
 //     needs more LDS than the block's budget marks the block "not done" and the host inflates it - the compressed bytes never left
-//     the host);
+//     the host).  Lane i owns the symbols i, i + 64, ...: counts and ranks per length by ballots, codes from first code + rank, the
+//     sub-table sizes as an LDS maximum on the primary entries, their offsets by a scan over the prefixes; nothing of it is serial
+//     (it was lane 0's, with the header a tenth of a block's time) and no array but the tables and the lengths is left in LDS - 8.4 KB
+//     and 83 VGPRs, so LDS no longer holds a CU at 15 waves (profiles/r36_inflate_setup.txt);
 //   * symbols: 64 bit offsets per round - every lane decodes the code that would start at ITS offset, a scalar walk over the lanes'
 //     code lengths (four symbols per hop, prepared by two rounds of ds_bpermute) finds the offsets where symbols really start, those
 //     lanes store their literals at positions from a prefix sum, and the wave copies the matches
@@ -30,6 +35,9 @@
 #include "parse_dev.h"
 
 namespace xck {
+
+__device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x);
+__device__ __forceinline__ uint32_t wave_scan_max(uint32_t x);
 
 namespace {
 
@@ -51,80 +59,125 @@ __device__ const uint16_t d_dist_base[30] = {1,2,3,4,5,7,9,13,17,25,33,49,65,97,
 __device__ const uint8_t  d_dist_extra[30] = {0,0,0,0,1,1,2,2,3,3,4,4,5,5,6,6,7,7,8,8,9,9,10,10,11,11,12,12,13,13};
 __device__ const uint8_t  d_cl_order[19] = {16,17,18,0,8,7,9,6,10,5,11,4,12,3,13,2,14,1,15};
 
+__host__ __device__ constexpr uint32_t dh(uint32_t val, uint32_t len, uint32_t op) { return val | len << 16 | op << 24; }   // a DHuff as the 32-bit word the tables hold
+constexpr uint32_t DH_INVAL = dh(0, 1, 0x40);
+
+// What a block header needs only until its code lengths stand in lens[]: it lies over lit[], which is dead from the end of one
+// DEFLATE block's symbols to the next table build.
+struct HdrScratch {
+    uint16_t mark[320];                   // mark[i] = (i + 1) << 4 | v where a run of length v starts at lens[i], 0 inside a run
+    uint8_t  cl[128];                     // code-length code: the next 7 stream bits -> symbol | bits << 5
+    uint8_t  pl[32];                      // its 19 code lengths
+};
+constexpr int IN_WIN = 1024;                               // bytes of the compressed stream staged per fill (a multiple of 256; see BitIn)
+// 8,576 B: 19 workgroups of one wave fit a CU's 160 KB of LDS (10,832 B held it at 15), and the kernel's 83 VGPRs allow them: 5 waves per SIMD.
 struct Smem {
-    DHuff lit[D_LIT_MAX];
-    DHuff dist[D_DIST_MAX];
+    union { uint32_t lit[D_LIT_MAX]; HdrScratch hdr; };   // (DHuff words)
+    uint32_t dist[D_DIST_MAX];
     uint8_t lens[320];                    // code lengths: literal / length alphabet, then distance alphabet
-    uint16_t code[320];                   // canonical code (bit-reversed) of every symbol
-    uint16_t sub_off[1 << D_LIT_TB];      // sub-table offset per primary index (0 = none)
-    uint8_t  sub_bits[1 << D_LIT_TB];
-    int32_t  count[16], first[16];
-    int32_t  used, ok;
+    uint32_t first[16];                   // first canonical code of every length (build_table)
+    uint32_t win[IN_WIN / 4];             // the input window (last: the CRC tables of the epilogue end in it)
 };
 
 __device__ __forceinline__ uint32_t brev(uint32_t v, int n) { return __brev(v) >> (32 - n); }
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }   // bits of m below this lane
 
-// all 64 lanes: decode table for `n_sym` code lengths at lens[]; kind 0 literal / length, 1 distance.  Returns false (uniform)
-// when the code is over-subscribed or does not fit the LDS budget.
-__device__ bool build_table(Smem& sm, const uint8_t* lens, uint16_t* code, int n_sym, int tb, DHuff* tab, int tab_max, int kind, int lane) {
-    if (lane < 16) sm.count[lane] = 0;
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {                                       // counts, first codes, canonical code per symbol: 300 cheap serial steps
-        for (int i = 0; i < n_sym; i++) sm.count[lens[i]]++;
-        sm.count[0] = 0;
-        int left = 1, okf = 1; uint32_t c = 0;
-        for (int l = 1; l <= 15; l++) { left = left * 2 - sm.count[l]; if (left < 0) okf = 0; }
-        int nxt[16];
-        for (int l = 1; l <= 15; l++) { c = (c + (uint32_t)sm.count[l - 1]) << 1; nxt[l] = (int)c; }
-        for (int i = 0; i < n_sym; i++) { const int l = lens[i]; code[i] = l ? (uint16_t)brev((uint32_t)nxt[l]++, l) : 0; }
-        sm.ok = okf; sm.used = 1 << tb;
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (!sm.ok) return false;
+// all 64 lanes: decode table for `n_sym` (<= 64 NCH) code lengths at lens[]; kind 0 literal / length, 1 distance.  Returns false
+// (uniform) when the code is over-subscribed or does not fit the LDS budget.  Lane i owns the symbols i, i + 64, ... and keeps their
+// lengths and codes in registers; no step's trip count is the number of symbols or the size of the primary table.
+template <int NCH>
+__device__ bool build_table(Smem& sm, const uint8_t* lens, int n_sym, int tb, uint32_t* tab, int tab_max, int kind, int lane) {
     const int psize = 1 << tb;
-    DHuff inval; inval.val = 0; inval.len = 1; inval.op = 0x40;
-    for (int i = lane; i < psize; i += 64) { tab[i] = inval; sm.sub_bits[i] = 0; sm.sub_off[i] = 0; }
+    // counts per length, and every symbol's rank among the symbols of its length: a ballot per length over each chunk of 64 symbols
+    // (lane L keeps the count of length L; a symbol's rank is the count before its chunk + the equal lengths below it in the chunk)
+    uint32_t len_[NCH], code_[NCH], cnt = 0;
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const int s = c * 64 + lane;
+        const uint32_t l = s < n_sym ? lens[s] : 0u;
+        uint32_t below = 0, add = 0;
+#pragma unroll 1
+        for (uint32_t L = 1; L <= 15; L++) { const uint64_t m = __ballot(l == L); below = l == L ? lanes_below(m) : below; add = (uint32_t)lane == L ? (uint32_t)__popcll(m) : add; }
+        len_[c] = l; code_[c] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(l << 2), (int)cnt) + below;
+        cnt += add;
+    }
+    // over-subscribed at any length: no table.  The first canonical code of length L goes to lane L, and from there to LDS
+    int left = 1; bool ok = true; uint32_t c0 = 0, f = 0, before = 0;
+#pragma unroll 1
+    for (int L = 1; L <= 15; L++) {
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)cnt, L);
+        left = left * 2 - (int)n; ok = ok && left >= 0; c0 = (c0 + before) << 1; before = n; f = lane == L ? c0 : f;
+    }
+    if (!ok) return false;
+    if (lane < 16) sm.first[lane] = f;
+    for (int i = lane; i < psize; i += 64) tab[i] = DH_INVAL;
     __builtin_amdgcn_wave_barrier();
-    // long codes: extra bits every primary prefix needs (max over its codes) - LDS atomicMax on bytes is not available, use lane 0
-    if (lane == 0) {
-        bool any = false;
-        for (int s = 0; s < n_sym; s++) { const int l = lens[s]; if (l > tb) { any = true; const uint32_t p = code[s] & (uint32_t)(psize - 1); if (l - tb > sm.sub_bits[p]) sm.sub_bits[p] = (uint8_t)(l - tb); } }
-        if (any) {
-            int used = psize;
-            for (int p = 0; p < psize && used <= tab_max; p++) if (sm.sub_bits[p]) {
-                const int sz = 1 << sm.sub_bits[p];
-                if (used + sz > tab_max) { used = tab_max + 1; break; }
-                sm.sub_off[p] = (uint16_t)used;
-                DHuff lk; lk.val = (uint16_t)used; lk.len = (uint8_t)tb; lk.op = (uint8_t)(0x80 | sm.sub_bits[p]);
-                tab[p] = lk;
-                for (int k = 0; k < sz; k++) tab[used + k] = inval;
-                used += sz;
-            }
-            sm.used = used;
-            if (used > tab_max) sm.ok = 0;
+    // canonical codes (bit-reversed) from first code + rank.  A long code raises its primary entry to a link with its extra bits: links
+    // compare above the invalid entry and by their bits, so the LDS maximum leaves every prefix with the longest code under it
+    bool is_long = false;
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+        const uint32_t l = len_[c];
+        if (l) {
+            const uint32_t r = brev(sm.first[l] + code_[c], (int)l);
+            code_[c] = r;
+            if ((int)l > tb) { is_long = true; atomicMax(&tab[r & (uint32_t)(psize - 1)], dh(0, (uint32_t)tb, 0x80u | (l - (uint32_t)tb))); }
         }
     }
     __builtin_amdgcn_wave_barrier();
-    if (!sm.ok) return false;
-    for (int s = lane; s < n_sym; s += 64) {               // every lane fills the entries of its symbols
-        const int l = lens[s]; if (!l) continue;
-        DHuff e; e.len = (uint8_t)l;
+    if (__ballot(is_long)) {
+        // sub-tables in ascending order of their prefixes: offsets by a scan over the sizes, 64 prefixes at a time; the link entry
+        // is the record.  The sum decides whether the table fits.
+        uint32_t used = (uint32_t)psize;
+        for (int p0 = 0; p0 < psize; p0 += 64) {
+            const uint32_t e = tab[p0 + lane];
+            const uint32_t sz = (e >> 31) ? 1u << ((e >> 24) & 15u) : 0u;
+            const uint32_t inc = wave_scan_incl(sz);
+            if (sz) tab[p0 + lane] = e | (used + inc - sz);                  // (at most 2^tb + 2^tb 2^(15 - tb) <= 33,280: the 16 bits of val)
+            used += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+        }
+        if ((int)used > tab_max) return false;
+        for (int i = psize + lane; i < (int)used; i += 64) tab[i] = DH_INVAL;   // what an incomplete code leaves uncovered stays invalid
+        __builtin_amdgcn_wave_barrier();
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {                        // every lane fills the entries of its symbols
+        const int s = c * 64 + lane; const uint32_t l = len_[c];
+        if (!l) continue;
+        uint32_t e;
         if (kind == 0) {
-            if (s < 256) { e.val = (uint16_t)s; e.op = 0; }
-            else if (s == 256) { e.val = 0; e.op = 0x20; }
-            else if (s <= 285) { e.val = d_len_base[s - 257]; e.op = (uint8_t)(0x10 | d_len_extra[s - 257]); }
-            else { e.val = 0; e.op = 0x40; }
+            if (s < 256) e = dh((uint32_t)s, 0, 0);
+            else if (s == 256) e = dh(0, 0, 0x20);
+            else if (s <= 285) e = dh(d_len_base[s - 257], 0, 0x10u | d_len_extra[s - 257]);
+            else e = dh(0, 0, 0x40);
         } else {
-            if (s < 30) { e.val = d_dist_base[s]; e.op = (uint8_t)(0x10 | d_dist_extra[s]); } else { e.val = 0; e.op = 0x40; }
+            e = s < 30 ? dh(d_dist_base[s], 0, 0x10u | d_dist_extra[s]) : dh(0, 0, 0x40);
         }
-        const uint32_t r = code[s];
-        if (l <= tb) { for (uint32_t k = r; k < (uint32_t)psize; k += 1u << l) tab[k] = e; }
+        const uint32_t r = code_[c];
+        if ((int)l <= tb) { e |= l << 16; for (uint32_t k = r; k < (uint32_t)psize; k += 1u << l) tab[k] = e; }
         else {
-            const uint32_t p = r & (uint32_t)(psize - 1); const int sb = sm.sub_bits[p];
-            e.len = (uint8_t)(l - tb);
-            for (uint32_t k = r >> tb; k < (1u << sb); k += 1u << (l - tb)) tab[sm.sub_off[p] + k] = e;
+            const uint32_t lk = tab[r & (uint32_t)(psize - 1)], sb = (lk >> 24) & 15u, off = lk & 0xffffu;
+            e |= (l - (uint32_t)tb) << 16;
+            for (uint32_t k = r >> tb; k < (1u << sb); k += 1u << (l - (uint32_t)tb)) tab[off + k] = e;
         }
     }
+    __builtin_amdgcn_wave_barrier();
+    return true;
+}
+
+// all 64 lanes: the code-length code's 7-bit look-up table (hdr.cl) from its 19 lengths (hdr.pl).  False (uniform) unless the code is
+// complete - zlib refuses an incomplete code-length code as well as an over-subscribed one, and a complete one fills the table.
+__device__ bool build_cl_table(Smem& sm, int lane) {
+    const uint32_t l = lane < 19 ? sm.hdr.pl[lane] : 0u;
+    uint32_t r = 0, c0 = 0, f = 0, kraft = 0, prev = 0;
+#pragma unroll
+    for (uint32_t L = 1; L <= 7; L++) {
+        const uint64_t m = __ballot(l == L); const uint32_t n = (uint32_t)__popcll(m);
+        c0 = (c0 + prev) << 1; prev = n; kraft += n << (7 - L);
+        if (l == L) { r = lanes_below(m); f = c0; }
+    }
+    if (kraft != 128u) return false;
+    if (l) { const uint32_t code = brev(f + r, (int)l), e = (uint32_t)lane | l << 5; for (uint32_t k = code; k < 128u; k += 1u << l) sm.hdr.cl[k] = (uint8_t)e; }
     __builtin_amdgcn_wave_barrier();
     return true;
 }
@@ -132,8 +185,7 @@ __device__ bool build_table(Smem& sm, const uint8_t* lens, uint16_t* code, int n
 // The compressed stream reaches lane 0 through an LDS window: the whole wave loads IN_WIN bytes at a time (aligned dwords,
 // coalesced), lane 0 takes aligned dwords out of LDS.  (A per-lane byte pointer into global memory cost four dependent byte
 // loads - about a microsecond - per 32 bits of input.)  Coordinates: byte s of the stream sits at c = s + A of the 4-byte
-// aligned buffer that starts at (stream address - A), A = address & 3.
-constexpr int IN_WIN = 1024;                               // bytes staged per fill (a multiple of 256)
+// aligned buffer that starts at (stream address - A), A = address & 3.  (IN_WIN bytes per fill: above, with Smem.)
 // A round of the symbol loop starts with its first bit's byte (byte0) at least WIN_MARGIN bytes before the window's end: lane 63 begins at
 // bit 7 + 63 of byte0 at most, i.e. in a dword that starts at byte0 + 8 or earlier, and reads that dword and the two after it (64 stream
 // bits: a length + distance pair is 48) - bytes up to byte0 + 8 + 11.
@@ -167,6 +219,17 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false);    // row_shr:8
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false);    // row_bcast:15 -> rows 1, 3
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false);    // row_bcast:31 -> rows 2, 3
+    return x;
+}
+
+// inclusive prefix maximum over the wave (the same steps; the missing neighbours read as 0)
+__device__ __forceinline__ uint32_t wave_scan_max(uint32_t x) {
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, false));    // row_shr:1
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, false));    // row_shr:2
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, false));    // row_shr:4
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, false));    // row_shr:8
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xa, 0xf, false));    // row_bcast:15 -> rows 1, 3
+    x = max(x, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xc, 0xf, false));    // row_bcast:31 -> rows 2, 3
     return x;
 }
 
@@ -227,9 +290,10 @@ __device__ unsigned long long d_prof[8];          // PROF builds only (tools/gpu
 template <bool PROF, bool CRC>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_inflate(const uint8_t* __restrict__ in, const DevBlock* __restrict__ blocks, int n_blocks,
                                                 uint8_t* out, int32_t* __restrict__ status, uint8_t* host_out) {
-    static_assert(sizeof(Smem) >= CRC_LDS_WORDS * sizeof(uint32_t), "the CRC tables live in the decode tables' LDS");
+    static_assert(sizeof(Smem) >= CRC_LDS_WORDS * sizeof(uint32_t), "the CRC tables live in the decode tables' LDS (and the head of the window's)");
+    static_assert(sizeof(Smem) <= 10240, "at least the 16 workgroups per CU that 128 VGPRs would allow");
     __shared__ Smem sm;
-    __shared__ uint32_t win[IN_WIN / 4];
+    uint32_t* const win = sm.win;
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= n_blocks) return;
     unsigned long long prof[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long t_prev = PROF ? clock64() : 0;   // 0 header, 1 tables, 2 window, 3 decode, 4 walk, 5 scan + literals, 6 matches, 7 flush / rest
@@ -258,9 +322,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
     uint32_t op = 0;                                                   // output position (wave-uniform)
     int err = 0;
     for (;;) {
-        // ---- block header (lane 0), broadcast; the window is moved first so that a whole header (< 400 bytes) fits ----
+        // ---- block header: its fields and the 19 lengths of the code-length code by lane 0, broadcast; the window is moved first so that
+        // a whole header (< 400 bytes) fits.  The header's scratch (over lit[], dead here) starts from zero: no mark, no length ----
         { uint32_t pos = __builtin_amdgcn_readfirstlane(bi.pos), wlo = __builtin_amdgcn_readfirstlane(bi.wlo);
           if (pos > wlo + IN_WIN - 512) { fill(pos & ~3u); bi.wlo = pos & ~3u; } }
+        __syncthreads();                                               // (every lane is past its last read of the tables the scratch lies over)
+        for (int i = lane; i < 320; i += 64) sm.hdr.mark[i] = 0;
+        if (lane < 32) sm.hdr.pl[lane] = 0;
+        __builtin_amdgcn_wave_barrier();
         int btype = 0, bfinal = 0, hlit = 0, hdist = 0;
         if (lane == 0) {
             bi.refill(win);
@@ -272,42 +341,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
                 hlit = (int)bi.bits(5) + 257; bi.drop(5); hdist = (int)bi.bits(5) + 1; bi.drop(5);
                 const int hclen = (int)bi.bits(4) + 4; bi.drop(4);
                 if (hlit > 286 || hdist > 30) err = 3;
-                uint8_t pl[19];
-                for (int i = 0; i < 19; i++) pl[i] = 0;
-                for (int i = 0; i < hclen && !err; i++) { if (bi.bc < 3) bi.refill(win); if (bi.bc < 3) { err = 4; break; } pl[d_cl_order[i]] = (uint8_t)bi.bits(3); bi.drop(3); }
-                // code-length code: canonical decode by counting (19 symbols, <= 7 bits)
-                int cnt[8] = {0}, firstc[8], firsts[8]; uint8_t sorted[19];
-                for (int i = 0; i < 19; i++) cnt[pl[i]]++;
-                cnt[0] = 0; { int c = 0, q = 0; for (int l = 1; l <= 7; l++) { c = (c + cnt[l - 1]) << 1; firstc[l] = c; firsts[l] = q; q += cnt[l]; } }
-                { int pos[8]; for (int l = 1; l <= 7; l++) pos[l] = firsts[l]; for (int i = 0; i < 19; i++) if (pl[i]) sorted[pos[pl[i]]++] = (uint8_t)i; }
-                int n = 0; const int tot = hlit + hdist;
-                while (n < tot && !err) {
-                    bi.refill(win);
-                    int code = 0, l = 0, sym = -1;
-                    for (l = 1; l <= 7; l++) {                         // bit-serial canonical decode (codes arrive most significant bit first)
-                        code = (code << 1) | (int)((bi.bb >> (l - 1)) & 1);
-                        const int d = code - firstc[l];
-                        if (cnt[l] && d >= 0 && d < cnt[l]) { sym = sorted[firsts[l] + d]; break; }
-                    }
-                    if (sym < 0 || l > bi.bc) { err = 5; break; }
-                    bi.drop(l);
-                    if (sym < 16) sm.lens[n++] = (uint8_t)sym;
-                    else {
-                        int r; uint8_t v = 0;
-                        if (sym == 16) { if (!n) { err = 6; break; } r = 3 + (int)bi.bits(2); bi.drop(2); v = sm.lens[n - 1]; }
-                        else if (sym == 17) { r = 3 + (int)bi.bits(3); bi.drop(3); }
-                        else { r = 11 + (int)bi.bits(7); bi.drop(7); }
-                        if (n + r > tot) { err = 7; break; }
-                        while (r--) sm.lens[n++] = v;
-                    }
-                    if (bi.bc < 0) { err = 8; break; }
-                }
-                if (!err && sm.lens[256] == 0) err = 9;
-            } else if (!err && btype == 1) {
-                for (int i = 0; i < 144; i++) sm.lens[i] = 8; for (int i = 144; i < 256; i++) sm.lens[i] = 9;
-                for (int i = 256; i < 280; i++) sm.lens[i] = 7; for (int i = 280; i < 288; i++) sm.lens[i] = 8;
-                for (int i = 0; i < 30; i++) sm.lens[288 + i] = 5;
-                hlit = 288; hdist = 30;
+                for (int i = 0; i < hclen && !err; i++) { if (bi.bc < 3) bi.refill(win); if (bi.bc < 3) { err = 4; break; } sm.hdr.pl[d_cl_order[i]] = (uint8_t)bi.bits(3); bi.drop(3); }
             }
         }
         err = __builtin_amdgcn_readfirstlane(err);
@@ -315,6 +349,46 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
         btype = __builtin_amdgcn_readfirstlane(btype); bfinal = __builtin_amdgcn_readfirstlane(bfinal);
         hlit = __builtin_amdgcn_readfirstlane(hlit); hdist = __builtin_amdgcn_readfirstlane(hdist);
         __builtin_amdgcn_wave_barrier();
+        if (btype == 2) {
+            // the code-length code as a 7-bit look-up table, by all lanes; the chain of its symbols is serial by nature and stays with
+            // lane 0, which only MARKS where a run begins (one LDS store per symbol, whatever the run's length); the wave then spreads
+            // every mark over its run: a prefix maximum - marks grow with their position - over 64 lengths at a time
+            if (!build_cl_table(sm, lane)) { err = 5; break; }
+            const int tot = hlit + hdist;
+            if (lane == 0) {
+                int n = 0; uint32_t last = 0;                              // last: the length before position n
+                while (n < tot) {
+                    bi.refill(win);
+                    const uint32_t e = sm.hdr.cl[bi.bb & 127u]; const int l = (int)(e >> 5), sym = (int)(e & 31u);
+                    if (l > bi.bc) { err = 5; break; }
+                    bi.drop(l);
+                    int r = 1;
+                    if (sym < 16) last = (uint32_t)sym;
+                    else if (sym == 16) { if (!n) { err = 6; break; } r = 3 + (int)bi.bits(2); bi.drop(2); }
+                    else if (sym == 17) { r = 3 + (int)bi.bits(3); bi.drop(3); last = 0; }
+                    else { r = 11 + (int)bi.bits(7); bi.drop(7); last = 0; }
+                    if (n + r > tot) { err = 7; break; }
+                    sm.hdr.mark[n] = (uint16_t)(((uint32_t)(n + 1) << 4) | last);
+                    n += r;
+                    if (bi.bc < 0) { err = 8; break; }
+                }
+            }
+            err = __builtin_amdgcn_readfirstlane(err);
+            if (err) break;
+            __builtin_amdgcn_wave_barrier();
+            uint32_t carry = 0;
+            for (int i0 = 0; i0 < tot; i0 += 64) {
+                const uint32_t x = max(wave_scan_max(sm.hdr.mark[i0 + lane]), carry);
+                carry = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+                sm.lens[i0 + lane] = (uint8_t)(x & 15u);
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (sm.lens[256] == 0) { err = 9; break; }
+        } else if (btype == 1) {
+            for (int i = lane; i < 320; i += 64) sm.lens[i] = (uint8_t)(i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : i < 288 ? 8 : 5);
+            hlit = 288; hdist = 30;
+            __builtin_amdgcn_wave_barrier();
+        }
         XCK_PROF_AT(0);
         if (btype == 0) {                                              // stored block: lane 0 finds the byte position, the wave copies
             uint32_t len = 0, s_at = 0;
@@ -346,8 +420,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
             { const uint32_t pos = __builtin_amdgcn_readfirstlane(bi.pos); fill(pos & ~3u); bi.wlo = pos & ~3u; }
             if (lane == 0) { const int skip = -bi.bc; bi.bc = 0; bi.bb = 0; bi.refill(win); if (skip) bi.drop(skip); }
         } else {
-            if (!build_table(sm, sm.lens, sm.code, hlit, D_LIT_TB, sm.lit, D_LIT_MAX, 0, lane)) { err = 20; break; }
-            if (!build_table(sm, sm.lens + hlit, sm.code, hdist, D_DIST_TB, sm.dist, D_DIST_MAX, 1, lane)) { err = 21; break; }
+            __syncthreads();                                           // (the header's scratch is dead: lit[] is the table's again)
+            if (!build_table<5>(sm, sm.lens, hlit, D_LIT_TB, sm.lit, D_LIT_MAX, 0, lane)) { err = 20; break; }
+            if (!build_table<1>(sm, sm.lens + hlit, hdist, D_DIST_TB, sm.dist, D_DIST_MAX, 1, lane)) { err = 21; break; }
             XCK_PROF_AT(1);
             // ---- symbols, 64 bit offsets at a time.  A symbol's boundaries depend on all symbols before it, but WHAT would be decoded at a
             // given bit offset does not: lane i decodes the literal / length (+ distance) code that starts at bit `bitpos + i` - two
@@ -585,6 +660,14 @@ int dev_inflate_launch(hipStream_t stream, const uint8_t* d_in, const DevBlock* 
     } else if (check_crc) hipLaunchKernelGGL((k_inflate<false, true>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
     else hipLaunchKernelGGL((k_inflate<false, false>), g, t, 0, stream, d_in, d_blocks, n_blocks, d_out, d_status, host_out);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int dev_inflate_occupancy(int variant, bool check_crc) {
+    int n = 0; hipError_t e;
+    if (variant >= 10) e = check_crc ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate<true, true>, 64, 0) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate<true, false>, 64, 0);
+    else e = check_crc ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate<false, true>, 64, 0) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_inflate<false, false>, 64, 0);
+    if (e != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return n;
 }
 
 // ---- one chunk in flight (see inflate_dev.h) ------------------------------------------------------------------------------
